@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
 """Headline benchmark: clips/sec of AGCN forward+backward at (N,C,T,V,M) = (64,3,300,25,2) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, plus the step's configuration and whole-step fractions, which cost no extra run).  `--full` adds everything that
+needs runs of its own: the side modes, the inference forward, the dominant kernel's roofline and live traffic, the CPU baseline
+with its parity check, and at N > 1 the collective report and the other scaling reading.  `--dump-outputs DIR` writes what the
+timed step computed in its last step (loss, logits, every parameter gradient) as float32 DIR/<name>.npy files; the inputs and
+the initial state are seeded, so two builds run with the same arguments can be compared file for file.
 
 One "step" = one train-mode forward + backward (CrossEntropy, gradients for all 3.47 M parameters) of the
 10-block AGCN (fusion_gcn_amd.models.mmargcn.agcn.Model, NTU-RGB-D graph, 60 classes) over synthetic clips already
 resident in HBM.  Data parallel (`--gpus N`): ONE 64-clip batch is sharded over the N ranks (strong scaling, the north
 star's "shard the clip batch across the 8 GPUs": 8 clips per GPU at N = 8, per-replica BatchNorm as in the reference's
-DataParallel) and the step includes the single RCCL all-reduce of the flat 13.9 MB gradient buffer; the weak-scaling
-reading (64 clips on every GPU) is measured right after it and reported as `other_scaling` (`--scaling weak` swaps the
-two).  No optimizer step (the metric is fwd+bwd).  Rank 0 prints ONE JSON line.
+DataParallel) and the step includes the single RCCL all-reduce of the flat 13.9 MB gradient buffer; with `--full` the
+weak-scaling reading (64 clips on every GPU) is measured right after it and reported as `other_scaling` (`--scaling weak`
+swaps the two).  No optimizer step (the metric is fwd+bwd).  Rank 0 prints ONE JSON line.
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (a child `torch.distributed.run`, before this
 process touches the GPU) and relays rank 0's JSON line.
@@ -19,9 +26,10 @@ process touches the GPU) and relays rank 0's JSON line.
 Arithmetic (`--math`, reported in `dtype`): the default "bf16x3" forms every float32 product of the convolution / GEMM
 kernels from exact three-way bfloat16 splits of both operands (six partial products, float32 accumulation: float32
 accuracy -- the parity tests run it at the float32 tolerances) on the bf16 matrix pipe; "f32" issues
-v_mfma_f32_32x32x2_f32 directly and is timed in the same run at N = 1 (`f32_mfma_mode`); "bf16" is BASELINE config 5.
+v_mfma_f32_32x32x2_f32 directly and, with `--full`, is timed in the same run at N = 1 (`f32_mfma_mode`); "bf16" is BASELINE
+config 5.
 
-Extra objects in that line:
+Extra objects in the `--full` line:
   roofline      the dominant kernel (halo-tile 9x1 temporal conv), timed live with HIP events on the stream it runs on,
                 against the matrix peak of its arithmetic (MI355X_MICROARCH.md): bf16 dense 2500 TFLOP/s / 6 partial
                 products = 416.7 TFLOP/s of float32-equivalent work in bf16x3 mode, 157.3 TFLOP/s for the f32 MFMA.
@@ -226,6 +234,25 @@ def log(msg: str) -> None:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, model, logits, loss: float) -> None:
+    """--dump-outputs: what a caller of the timed step receives from its last step -- the loss, the logits and every parameter's
+    gradient -- as float32 <out_dir>/<name>.npy (loss.npy, logits.npy, grad.<parameter name>.npy).  About 14 MB at the headline
+    shape; every array is written whole, so the total must stay within DUMP_LIMIT_BYTES."""
+    import numpy as np
+    arrays = {"loss": torch.tensor(loss, dtype=torch.float32), "logits": logits}
+    arrays.update((f"grad.{n}", p.grad) for n, p in model.named_parameters() if p.grad is not None)
+    total = sum(4 * t.numel() for t in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+    log(f"wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
+
+
 TRAFFIC_RECORDS = ("r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json")      # newest first
 
 
@@ -383,7 +410,7 @@ def dry_run(args, world: int, rank: int) -> None:
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     assert float(flat[0]) == world * (world + 1) / 2
-    coll = collective_report(world, rank, os.environ.get("FGCN_BENCH_BACKEND", "gloo"), reps=3) if world > 1 else None
+    coll = collective_report(world, rank, os.environ.get("FGCN_BENCH_BACKEND", "gloo"), reps=3) if world > 1 and args.full else None
     if rank == 0:
         line = {"metric": metric_name(n_global), "value": None, "unit": "clips/s",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True,
@@ -392,7 +419,7 @@ def dry_run(args, world: int, rank: int) -> None:
                            "parallelism": f"dp{world}", "exchange_s": round(float(t), 4)}}
         if coll:
             line["collective"] = coll
-        if world > 1 and not args.no_cpu_baseline:      # the N > 1 line carries the CPU baseline too (rank 0 times it, the others wait)
+        if world > 1 and args.full and not args.no_cpu_baseline:      # the N > 1 --full line carries the CPU baseline too (rank 0 times it, the others wait)
             line["cpu_baseline"] = {"value": None, "unit": "clips/s", "cores": None, "kind": "port", "sample": "dry run: not timed"}
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -406,6 +433,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what needs runs of its own: the side math modes, the inference forward, the dominant "
+                         "kernel's roofline and live traffic, the CPU baseline and its parity check, and at N > 1 the collective report "
+                         "and the other scaling reading (the --no-* options below switch single parts off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (loss, logits, every parameter gradient; "
+                         "rank 0's) as float32 DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=SHAPE["N"], help="clips per GPU (weak) / global clip batch (strong)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="strong (default): ONE batch of --batch clips sharded over the GPUs; weak: --batch clips on every GPU")
@@ -457,6 +491,8 @@ def main():
                     help="only the live timing of the dominant kernel at its dominant shape (256 channels): the command "
                          "profiles/*_dominant_kernel_stats.csv is the rocprofv3 --kernel-trace --stats summary of")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
     if args.joints != 25:
         SHAPE["V"] = args.joints
         SHAPE["classes"] = 35 if args.joints == 22 else 60
@@ -514,6 +550,7 @@ def main():
                else FlatOptimizer(model.parameters(), "SGD", 1e-5, grads=grads, momentum=0.9, nesterov=True, weight_decay=1e-4))
 
     n_global = args.batch * world if args.scaling == "weak" else args.batch
+    last_outputs = {}       # the logits of the most recent step (a replayed graph rewrites the captured tensor in place)
 
     def resident_shard(n_total):
         """This rank's clips of a seeded synthetic batch of n_total clips, resident in HBM before any timed region."""
@@ -534,7 +571,9 @@ def main():
             for m in model.modules():
                 if hasattr(m, "mark_packed_stale") and not args.keep_packed:
                     m.mark_packed_stale()
-            loss = cross_entropy(model(x), y)
+            logits = model(x)
+            last_outputs["logits"] = logits.detach()     # (--dump-outputs; detached: no earlier step's autograd graph outlives the step)
+            loss = cross_entropy(logits, y)
             loss.backward()
             return loss
 
@@ -655,11 +694,13 @@ def main():
     log(f"model + {n_local} clips resident on {device}; warm-up x{args.warmup}, timing {args.steps} steps")
     elapsed, loss_val = timed(step, args.steps, args.warmup)
     log(f"{args.steps} steps in {elapsed:.3f} s")
+    if args.dump_outputs and rank == 0:     # before anything else runs a step: the gradients are still the last timed step's
+        dump_outputs(args.dump_outputs, model, last_outputs["logits"], loss_val)
 
     # With more than one GPU the other reading of "data-parallel scaling" is reported beside the headline number in the
     # same line: ONE batch of --batch clips sharded over the ranks (strong scaling; 8 clips per GPU at N = 8).
     other = None
-    if world > 1 and not args.no_other_scaling and args.batch >= world:
+    if world > 1 and args.full and not args.no_other_scaling and args.batch >= world:
         # (no try/except: a rank that skipped a collective would leave the others hanging; an error ends the job loudly)
         n_other = args.batch if args.scaling == "weak" else args.batch * world
         x2, y2, n_local2 = resident_shard(n_other)
@@ -685,10 +726,11 @@ def main():
         if err != 0.0:      # data_bn and the loss run on libfgcn too: every gradient of the step is a fixed-order sum
             raise SystemExit("verify-dp failed: the replayed step's gradient buffer must equal the eager step's bit for bit")
 
-    coll = collective_report(world, rank, backend, device=device, numel=int(grads.flat.numel())) if world > 1 else None
-    kern = None if args.no_kernel_timing else time_dominant_kernel(device, n_local * SHAPE["M"])
+    # everything from here to the result line needs runs of its own: --full only
+    coll = collective_report(world, rank, backend, device=device, numel=int(grads.flat.numel())) if world > 1 and args.full else None
+    kern = None if args.no_kernel_timing or not args.full else time_dominant_kernel(device, n_local * SHAPE["M"])
     f32_mode = None
-    if world == 1 and args.math == "bf16x3" and not args.no_f32_mode:
+    if world == 1 and args.full and args.math == "bf16x3" and not args.no_f32_mode:
         # the same step with v_mfma_f32_32x32x2_f32 issued directly, for reference beside the headline number
         _ops.set_math_mode("f32")
         step_f, mode_f = make_step(x, y)
@@ -698,7 +740,7 @@ def main():
         _ops.set_math_mode(args.math)
         del step_f
     f16x2_mode = None
-    if world == 1 and args.math == "bf16x3" and not args.no_f16x2_mode:
+    if world == 1 and args.full and args.math == "bf16x3" and not args.no_f16x2_mode:
         # the same step with the temporal / 1x1 convolutions and their weight gradients on block-scaled two-way f16 splits (three
         # MFMAs per product group instead of six; float32-class: tests/test_f16x2_edge_gpu.py) -- reported beside
         # the headline, which stays on the arithmetic the earlier rounds were judged on
@@ -717,7 +759,7 @@ def main():
         _ops.set_math_mode(args.math)
         del step_h
     bf16_mode = None
-    if world == 1 and args.math == "bf16x3" and not args.no_bf16_mode and SHAPE["V"] == 25:
+    if world == 1 and args.full and args.math == "bf16x3" and not args.no_bf16_mode and SHAPE["V"] == 25:
         # BASELINE config 5 on the same model and batch: bf16 MFMA operands AND bf16 storage of the activation-sized tensors (the reference's
         # autocast semantics, DESIGN.md section 3.14 b / g) -- a different numerical contract, reported beside the headline
         _ops.set_math_mode("bf16")
@@ -728,7 +770,7 @@ def main():
         _ops.set_math_mode(args.math)
         del step_b
     inference = None
-    if world == 1 and not args.no_inference and args.math in ("bf16x3", "bf16") and args.loader == "none":
+    if world == 1 and args.full and not args.no_inference and args.math in ("bf16x3", "bf16") and args.loader == "none":
         # the same model's INFERENCE forward (eval-mode BatchNorm, no autograd graph): BatchNorm + shortcut + ReLU are then the epilogues of
         # the two north-star kernels (fgcn_spatial_fwd_tile_bn_relu, fgcn_tconv_halo_bn_relu) -- reported beside the training step
         try:
@@ -824,7 +866,7 @@ def main():
                                       "f16x2": "f16 dense peak (= bf16's) / 3 products (f32-equivalent FLOPs)"}[args.math]
             roofline_detail = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in d.items()} for d in kern]
         parity = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after every timed region (N > 1: the other ranks wait at the barrier below; nothing here is a collective)
             log("timing the CPU oracle on the host cores")
             also = ("f16x2",) if f16x2_mode else ()

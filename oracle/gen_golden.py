@@ -41,7 +41,7 @@ from datasets.utd_mhad import constants as utd  # noqa: E402  (reference)
 from datasets.mmact import constants as mmact  # noqa: E402  (reference)
 from datasets.ntu_rgb_d import constants as ntu  # noqa: E402  (reference)
 
-from oracle import filler  # noqa: E402
+from oracle import filler, golden  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden")
 os.makedirs(OUT, exist_ok=True)
@@ -196,7 +196,7 @@ def main():
         # reference's own float32 run differs from its float64 run: the yardstick for the HIP forward's flip count
         store[f"{tag}.ref_f32_vs_f64_relu_flips"] = np.array([int((a != b).sum()) for a, b in zip(signs64, signs32)], dtype=np.int64)
         store[f"{tag}.relu_decisions"] = np.array([a.numel() for a in signs64], dtype=np.int64)
-    np.savez(os.path.join(OUT, "model.npz"), **store)
+    golden.save(os.path.join(OUT, "model.npz"), store)      # in parts: model.part<N>.npz
 
     # ---- (vi) mmargcn.Model(mode="skeleton_imu_spatial_fusion"), V = 20 + 2 ---------------------
     store = {}

@@ -34,7 +34,7 @@ import models.msg3d.msg3d as ref_msg3d  # noqa: E402  (reference)
 from datasets.utd_mhad import constants as utd  # noqa: E402  (reference)
 from datasets.ntu_rgb_d import constants as ntu  # noqa: E402  (reference)
 
-from oracle import filler  # noqa: E402
+from oracle import filler, golden  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden", "msg3d.npz")
 torch.set_num_threads(8)
@@ -78,8 +78,8 @@ def main():
                 store[f"{tag}.after.{k}"] = v_.numpy().copy()
         model.load_state_dict(before)
     store["torch_version"] = np.array(torch.__version__)
-    np.savez_compressed(OUT, **store)
-    print(OUT, os.path.getsize(OUT), "bytes,", len(store), "entries")
+    files = golden.save(OUT, store, compressed=True)         # in parts: msg3d.part<N>.npz
+    print(OUT, sum(os.path.getsize(f) for f in files), "bytes in", len(files), "files,", len(store), "entries")
 
 
 if __name__ == "__main__":

@@ -35,7 +35,7 @@ def test_bench_starts_its_own_ranks_and_reports_strong_scaling():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["FGCN_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--full"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -43,8 +43,8 @@ def test_bench_starts_its_own_ranks_and_reports_strong_scaling():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["dry_run"] is True
     assert out["config"]["global_batch"] == 64 and out["config"]["per_gpu_batch"] == 32 and out["config"]["parallelism"] == "dp2"
-    # the N > 1 line proves which collective ran where: backend, world, every rank's device, the all-reduce timed alone, and it carries
-    # the CPU baseline too (rank 0; the dry run does not time it)
+    # the N > 1 --full line proves which collective ran where: backend, world, every rank's device, the all-reduce timed alone, and it
+    # carries the CPU baseline too (rank 0; the dry run does not time it)
     coll = out["collective"]
     assert coll["backend"] == "gloo" and coll["world"] == 2 and [d["rank"] for d in coll["devices"]] == [0, 1]
     assert all(set(d) >= {"rank", "local_device", "name"} for d in coll["devices"])
@@ -57,10 +57,16 @@ def test_bench_starts_its_own_ranks_and_reports_strong_scaling():
     assert r8.returncode == 0, r8.stderr[-2000:]
     out8 = json.loads([ln for ln in r8.stdout.splitlines() if ln.startswith("{")][0])
     assert out8["metric"].startswith("clips/sec (N,C,T,V,M)=(8,3,300,25,2)") and out8["config"]["per_gpu_batch"] == 4
+    # without --full the line carries the headline only: no collective report, no CPU baseline
+    assert "collective" not in out8 and "cpu_baseline" not in out8 and out8["steps"] == 2 and "ms_per_step" in out8
     # a batch that does not divide over the ranks is refused before any work
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "7", "--dry-run"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
+    # so is a run without timed steps
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "0", "--dry-run"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
 
 
 def test_round2_traffic_record_shows_the_fetch_reduction():

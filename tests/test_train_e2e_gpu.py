@@ -152,7 +152,7 @@ def test_two_ranks_of_the_real_model_through_the_self_launching_bench():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["FGCN_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "3", "--warmup", "1",
-                        "--verify-dp", "--no-kernel-timing"], env=env, capture_output=True, text=True, timeout=900)
+                        "--verify-dp", "--full", "--no-kernel-timing"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     # every kernel of the step is a fixed-order libfgcn sum (data_bn and the loss included since round 3: MIOpen's BatchNorm backward
     # was the one gradient of 274 that moved under contention), so the replayed step equals the eager one bit for bit, also with
@@ -162,3 +162,41 @@ def test_two_ranks_of_the_real_model_through_the_self_launching_bench():
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["per_gpu_batch"] == 8 and out["config"]["launch"] == "hipgraph"
     assert out["other_scaling"]["scaling"] == "weak" and out["other_scaling"]["per_gpu_batch"] == 16
     assert out["value"] > 0 and abs(out["config"]["loss"]) < 20
+
+
+@pytest.mark.math_modes("bf16x3")
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the line holds the headline only (no side modes,
+    roofline or CPU baseline), `steps` = K and `ms_per_step` agree with `value`, and DIR holds the last timed step's loss, logits
+    and every parameter gradient as float32.  Inputs and state are seeded and every sum of the step has a fixed order, so a second
+    run with the same arguments writes the same arrays bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "8", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        runs.append((out, {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}))
+    out, arrays = runs[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+    assert not {"modes", "inference", "roofline", "cpu_baseline", "parity_at_full_shape", "f32_mfma_mode"} & set(out)
+    assert out["steps"] == 3 and out["unit"] == "clips/s" and out["higher_is_better"] is True
+    assert abs(out["value"] * out["ms_per_step"] - 8 * 1e3) < 1e-2 * 8 * 1e3
+    from fusion_gcn_amd.models.mmargcn.agcn import Model
+    from fusion_gcn_amd.datasets.ntu_rgb_d import constants as ntu
+    from fusion_gcn_amd.util import Graph
+    names = [n for n, _ in Model((2, 300, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint)).named_parameters()]
+    assert set(arrays) == {"loss", "logits"} | {f"grad.{n}" for n in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["logits"].shape == (8, 60) and abs(float(arrays["loss"]) - out["config"]["loss"]) < 1e-5
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert any(np.abs(arrays[f"grad.{n}"]).max() > 0 for n in names)
+    for k, a in runs[1][1].items():
+        assert np.array_equal(a, arrays[k]), k

@@ -9,7 +9,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 Q="--no-cpu-baseline --no-f32-mode --no-f16x2-mode --no-bf16-mode --no-kernel-timing --no-inference --no-live-traffic"
 if [ "$part" = "a" ]; then
-    python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+    python3 bench.py --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err
     echo "bench: $(python3 -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['ms_per_step'])")"
     : > $out/bench_other_configs.jsonl
     python3 bench.py --steps 20 --warmup 5 --joints 27 $Q >> $out/bench_other_configs.jsonl 2>> $out/bench.err

@@ -3,12 +3,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests"))
 import numpy as np, torch
 from conftest import rel_l2
-from oracle import filler
+from oracle import filler, golden
 from fusion_gcn_amd import ops
 from fusion_gcn_amd.datasets.ntu_rgb_d import constants as ntu
 from fusion_gcn_amd.models.mmargcn.agcn import Model
 from fusion_gcn_amd.util import Graph
-ref = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests", "golden", "model.npz"))
+ref = golden.load(os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests", "golden", "model.npz"))
 dev = torch.device("cuda:0")
 shape, classes = (2, 2, 32, 25, 3), 60
 model = Model(shape[1:], classes, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint))

@@ -13,14 +13,14 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 from conftest import rel_l2
-from oracle import filler
+from oracle import filler, golden
 from fusion_gcn_amd import ops
 from fusion_gcn_amd.datasets.ntu_rgb_d import constants as ntu
 from fusion_gcn_amd.models.mmargcn.agcn import Model
 from fusion_gcn_amd.util import Graph
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-ref = np.load(os.path.join(ROOT, "tests", "golden", "model.npz"))
+ref = golden.load(os.path.join(ROOT, "tests", "golden", "model.npz"))
 dev = torch.device("cuda:0")
 shape, classes = (2, 2, T, 25, 3), 60
 model = Model(shape[1:], classes, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint))
