@@ -191,6 +191,9 @@ SIGNATURES = {
     "fgcn_data_bn_apply": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_data_bn_bwd_reduce": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_data_bn_bwd_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fgcn_patch_input_slabs": (_I, [_I, _I, _I, _I, _I]),
+    "fgcn_patch_input_fwd": (_I, [_P] * 8 + [_I] * 10 + [_P]),
+    "fgcn_patch_input_bwd": (_I, [_P] * 10 + [_I] * 10 + [_P]),
     "fgcn_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_optim_step": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _LL, _P]),

@@ -43,6 +43,11 @@ def _r4(c: int) -> int:
     return (c + 3) // 4 * 4
 
 
+# widest input of fgcn_spatial_fwd (eight 32-channel tiles, fgcn_spatial.hip); a wider block input -- the 512 / 516 channels of the RGB
+# patch-feature modes' first block -- takes the joint mixing + row GEMM form of the spatial stage (the skeleton models never reach it)
+SPATIAL_FWD_MAX_C = 256
+
+
 @dataclass(frozen=True)
 class BlockConfig:
     cin: int
@@ -464,7 +469,7 @@ def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, t
     y16 = ha and o_.half_spatial_out and not o_.get("bn_sums_in_dgrad", ops.get_math_mode())
     if cfg.fused_spatial and o_.spatial_tile and cout >= o_.get("spatial_tile_min_cout", ops.get_math_mode()) and "d_s3" in W and ops.spatial_fwd_tile_available(V, cin, cout):
         y, part = ops.spatial_fwd_tile(x if y16 else x32(), a_hat, W["d_s3"], W["d_b"], Cin=cin, Cout=cout, stats=train, y_bf16=y16)
-    elif cfg.fused_spatial:
+    elif cfg.fused_spatial and cin <= SPATIAL_FWD_MAX_C:
         y, part = ops.spatial_fwd(x32(), a_hat, W["d4"], W["d_b"], Cin=cin, Cout=cout, stats=train)
     else:
         agg = new(B, T, V, 3 * cin)
@@ -958,6 +963,75 @@ def data_bn(x: torch.Tensor, bn: torch.nn.BatchNorm1d) -> torch.Tensor:
     if x.shape[1] * x.shape[3] * x.shape[4] != bn.num_features:
         raise ValueError(f"data_bn: input {tuple(x.shape)} does not have {bn.num_features} (m, v, c) channels")
     out = DataBNFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps)
+    if bn.training:
+        bn.num_batches_tracked.add_(1)
+    return out
+
+
+class PatchInputFunction(torch.autograd.Function):
+    """The input stage of the RGB patch-feature early-fusion modes (reference mmargcn/early_fusion_models.py:48-90, 163-210) in front of
+    data_bn: reducer Linear(P, H) . Linear(H, Q), zero rows for the joints without a patch, fusion with the skeleton rows -- one
+    fgcn_patch_input_fwd pass that also leaves data_bn's statistics partials -- then data_bn's finalize / apply.  Backward: data_bn's dx
+    (the network input's gradient) -> fgcn_patch_input_bwd -> the reducer's four gradients.  Skeleton and patch rows are data."""
+
+    @staticmethod
+    def forward(ctx, s, p, w1, b1, w2, b2, weight, bias, running_mean, running_var, train: bool, momentum: float, eps: float, V: int,
+                fusion: str):
+        s = None if s is None else s.contiguous()
+        p = p.contiguous()
+        z, part = ops.patch_input_fwd(s, p, w1, b1, w2, b2, V=V, fusion=fusion, stats=train)
+        N, T, C = z.shape[0], z.shape[2], z.shape[4]
+        if train:
+            vec = ops.bn_finalize(part, N * T, weight, bias, running_mean, running_var, momentum, eps)
+        else:
+            vec = ops.bn_eval_coeffs(weight, bias, running_mean, running_var, eps)
+        ctx.save_for_backward(z, vec, s, p, w1, b1, w2)
+        ctx.train, ctx.fusion = train, fusion
+        return ops.data_bn_apply(z, vec, _r4(C))
+
+    @staticmethod
+    def backward(ctx, d_out):
+        z, vec, s, p, w1, b1, w2 = ctx.saved_tensors
+        need = w1 is not None and any(ctx.needs_input_grad[2:6])
+        dgamma, dbeta, dz = ops.data_bn_bwd(d_out.contiguous(), z, vec, ctx.train, need)
+        dw1 = db1 = dw2 = db2 = None
+        if need:
+            dw1, db1, dw2, db2 = ops.patch_input_bwd(dz, s, p, w1, b1, w2, fusion=ctx.fusion)
+        return None, None, dw1, db1, dw2, db2, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def patch_input(s: Optional[torch.Tensor], p: torch.Tensor, reducer: Optional[Sequence[torch.nn.Linear]], bn: torch.nn.BatchNorm1d,
+                V: int, fusion: str) -> torch.Tensor:
+    """The patch-feature modes' network input -> what ``data_bn`` returns: s (N, M, T, V, Cs) skeleton rows or None, p (N, M, T, Vp, P)
+    patch rows, ``reducer`` = the two nn.Linear of ``patch_feature_dim_reducer`` or None (identity), ``bn`` = the model's data_bn.
+    ``paths.patch_input_fused`` off (this math mode's entry): the same function composed of the row GEMM (LinearFunction, twice), zero pad, the fusion's torch
+    reduction and ``data_bn`` (the A/B route)."""
+    if fusion not in ops.PATCH_FUSIONS:
+        raise ValueError(f"unsupported fusion {fusion!r} for the patch-feature input (known: {', '.join(ops.PATCH_FUSIONS)})")
+    N, M, T, Vp, P = p.shape
+    if not ops.paths().get("patch_input_fused", ops.get_math_mode()) or (s is None and reducer is None):
+        q = p
+        if reducer is not None:
+            h = LinearFunction.apply(p.reshape(-1, P), reducer[0].weight, reducer[0].bias)
+            q = LinearFunction.apply(h, reducer[1].weight, reducer[1].bias).reshape(N, M, T, Vp, -1)
+        if Vp < V:
+            q = F.pad(q, (0, 0, 0, V - Vp))
+        if s is None:
+            z = q
+        elif fusion == "concatenate":
+            z = torch.cat((s, q), dim=-1)
+        elif fusion == "sum":
+            z = s + q
+        elif fusion == "product":
+            z = s * q
+        else:
+            z = torch.stack((s, q), dim=-1).mean(-1)
+        return data_bn(z, bn)
+    if bn.momentum is None or not bn.affine or not bn.track_running_stats:
+        raise NotImplementedError("data_bn: affine BatchNorm1d with exponential running statistics (the reference's default) only")
+    w = (None,) * 4 if reducer is None else (reducer[0].weight, reducer[0].bias, reducer[1].weight, reducer[1].bias)
+    out = PatchInputFunction.apply(s, p, *w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps,
+                                   V, fusion)
     if bn.training:
         bn.num_batches_tracked.add_(1)
     return out

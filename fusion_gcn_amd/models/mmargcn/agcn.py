@@ -343,8 +343,11 @@ class Model(nn.Module):
             torch._foreach_add_([t for b in blocks for t in b.nbt_buffers()], 1)
 
     def forward(self, x):
-        N, M, T, V, C = x.size()
-        h = self._blocks_input(x)
+        return self.forward_blocks(self._blocks_input(x), x.size(0))
+
+    def forward_blocks(self, h: torch.Tensor, N: int) -> torch.Tensor:
+        """Everything after data_bn: ``h`` = what ``block.data_bn`` (or another input stage with its result, block.patch_input)
+        returns for N clips -> logits (or pooled features ``without_fc``)."""
         self._bump_batch_counters()
         refresh_packed_weights(self)
         if self.training and torch.is_grad_enabled():

@@ -794,10 +794,11 @@ def joint_mix(inp: torch.Tensor, out: torch.Tensor, mats: torch.Tensor, spec: Se
     if out.shape[:3] != inp.shape[:3] or mats.shape[-1] != V or mats.shape[-2] != V or mats.shape[0] not in (1, B):
         raise _lib.FgcnError(f"joint_mix: shape mismatch in={tuple(inp.shape)} out={tuple(out.shape)} "
                              f"mats={tuple(mats.shape)}")
-    items = mix_items(spec)
-    check(_lib.load().fgcn_joint_mix(_p(inp), _p(out), _p(mats), B, T, V, ld_in, out.shape[3], in_channels,
-                                     out_channels, mats.shape[1], int(mats.shape[0] != 1),
-                                     items, len(spec), int(accumulate), _stream()), "fgcn_joint_mix")
+    for lo in range(0, len(spec), MIX_MAX_ITEMS):       # (every item writes its own output channels: a wide spec is split over launches)
+        part = spec[lo:lo + MIX_MAX_ITEMS]
+        check(_lib.load().fgcn_joint_mix(_p(inp), _p(out), _p(mats), B, T, V, ld_in, out.shape[3], in_channels,
+                                         out_channels, mats.shape[1], int(mats.shape[0] != 1),
+                                         mix_items(part), len(part), int(accumulate), _stream()), "fgcn_joint_mix")
     return out
 
 
@@ -1240,6 +1241,69 @@ def data_bn_bwd(dout: torch.Tensor, x: torch.Tensor, vec: torch.Tensor, train: b
         check(lib.fgcn_data_bn_bwd_apply(_p(dout), _p(x), _p(vec), _p(sums), _p(dx), N, M, T, V, C, Cp, int(train), _stream()),
               "fgcn_data_bn_bwd_apply")
     return sums[1], sums[0], dx
+
+
+# ---- the input stage of the RGB patch-feature modes (fgcn_patch.hip) ---------------------------------------------------------------
+PATCH_FUSIONS = {"concatenate": 0, "sum": 1, "product": 2, "average": 3}
+
+
+def _patch_dims(s: Optional[torch.Tensor], p: torch.Tensor, w1: Optional[torch.Tensor], w2: Optional[torch.Tensor], V: int, fusion: str):
+    if fusion not in PATCH_FUSIONS:
+        raise _lib.FgcnError(f"patch input: unsupported fusion {fusion!r} (known: {', '.join(PATCH_FUSIONS)})")
+    _chk(p, "patch_input.p")
+    if s is not None:
+        _chk(s, "patch_input.s")
+    N, M, T, Vp, P = p.shape
+    Cs = 0 if s is None else s.shape[-1]
+    if s is not None and tuple(s.shape[:4]) != (N, M, T, V):
+        raise _lib.FgcnError(f"patch input: skeleton rows {tuple(s.shape)} do not match patch rows {tuple(p.shape)} on {V} joints")
+    H = 0 if w1 is None else w1.shape[0]
+    Q = P if w2 is None else w2.shape[0]
+    return N, M, T, Vp, P, Cs, H, Q
+
+
+def patch_input_fwd(s: Optional[torch.Tensor], p: torch.Tensor, w1: Optional[torch.Tensor], b1: Optional[torch.Tensor],
+                    w2: Optional[torch.Tensor], b2: Optional[torch.Tensor], *, V: int, fusion: str, stats: bool = True):
+    """s (N, M, T, V, Cs) or None, p (N, M, T, Vp, P), reducer (w1, b1, w2, b2) or all None (identity) -> (z (N, M, T, V, C), data_bn
+    statistics partials of z (tiles, 2, M*V*C) or None)."""
+    ensure_device()
+    N, M, T, Vp, P, Cs, H, Q = _patch_dims(s, p, w1, w2, V, fusion)
+    for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")):
+        if t is not None:
+            _chk(t, f"patch_input_fwd.{n}")
+    C = Cs + Q if fusion == "concatenate" else Cs
+    lib = _lib.load()
+    z = torch.empty((N, M, T, V, C), device=p.device, dtype=torch.float32)
+    part = (torch.empty((lib.fgcn_data_bn_tiles(N, T), 2, M * V * C), device=p.device, dtype=torch.float32) if stats else None)
+    check(lib.fgcn_patch_input_fwd(_p(s), _p(p), _p(w1), _p(b1), _p(w2), _p(b2), _p(z), _p(part), N, M, T, V, Vp, Cs, P, H, Q,
+                                   PATCH_FUSIONS[fusion], _stream()), "fgcn_patch_input_fwd")
+    return z, part
+
+
+def patch_input_bwd(dz: torch.Tensor, s: Optional[torch.Tensor], p: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                    *, fusion: str):
+    """dz (N, M, T, V, C) -> (dW1 (H, P), db1 (H), dW2 (Q, H), db2 (Q)): slab partials summed by one fgcn_reduce_multi launch."""
+    ensure_device()
+    _chk(dz, "patch_input_bwd.dz")
+    V = dz.shape[3]
+    N, M, T, Vp, P, Cs, H, Q = _patch_dims(s, p, w1, w2, V, fusion)
+    for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2")):
+        _chk(t, f"patch_input_bwd.{n}")
+    lib = _lib.load()
+    S = lib.fgcn_patch_input_slabs(N, M, T, Vp, H)
+    if S <= 0:
+        check(S, "fgcn_patch_input_slabs")
+    f32 = dict(device=p.device, dtype=torch.float32)
+    pw1, pb1, pw2, pb2 = (torch.empty((S, H, P), **f32), torch.empty((S, H), **f32), torch.empty((S, Q, H), **f32),
+                          torch.empty((S, Q), **f32))
+    check(lib.fgcn_patch_input_bwd(_p(dz), _p(s), _p(p), _p(w1), _p(b1), _p(w2), _p(pw1), _p(pb1), _p(pw2), _p(pb2), N, M, T, V, Vp,
+                                   Cs, P, H, Q, PATCH_FUSIONS[fusion], _stream()), "fgcn_patch_input_bwd")
+    dw1, db1, dw2, db2 = torch.empty((H, P), **f32), torch.empty(H, **f32), torch.empty((Q, H), **f32), torch.empty(Q, **f32)
+    batch = ReduceBatch()
+    for dst, src, K, Nn in ((dw1, pw1, H, P), (db1, pb1, 1, H), (dw2, pw2, Q, H), (db2, pb2, 1, Q)):
+        batch.add(dst, src, S, 1, K, Nn, K, K * Nn, Nn, 1, False)
+    batch.flush()
+    return dw1, db1, dw2, db2
 
 
 def cross_entropy_fwd(logits: torch.Tensor, labels: torch.Tensor):

@@ -101,6 +101,13 @@ class PathOptions:
     pool_epilogue: bool = True
     pool_backward_rows: bool = True
     mix_vw_order: Tuple[int, ...] = (2, 1)       # channels per lane preference of the channel-group mix kernel
+    # -- RGB patch-feature early fusion (models/mmargcn/rgb_feature_models.py): reducer + zero pad + fusion + data_bn statistics in one
+    # fgcn_patch_input_fwd pass and the reducer's gradients in one fgcn_patch_input_bwd pass; off: the same function composed of two row
+    # GEMMs, torch pad / cat and data_bn (block.patch_input).  Skeleton models never read it.  MI355X, tools/patch_bench.py, batch 8, T = 128,
+    # reducer 512 -> 128 -> 6, graph-replayed step, on / off / on in one process (profiles/r07_patch_bench.txt): the input stage alone
+    # 0.29-0.35 vs 0.43-0.67 ms in every mode; the step f32 7.18 / 6.90 vs 7.26 ms, bf16x3 5.40 / 5.35 vs 5.45, f16x2 4.76 / 5.10 vs 5.15
+    # (skeleton + rgb; skeleton + IMU + rgb alike), but bf16 3.86 / 3.86 vs 3.55 ms (3.91 / 3.91 vs 3.62): off in bf16
+    patch_input_fused: Dict[str, bool] = field(default_factory=lambda: {"f32": True, "bf16": False, "bf16x3": True, "f16x2": True})
 
     def copy(self) -> "PathOptions":
         return dataclasses.replace(self, **{f.name: dict(getattr(self, f.name)) for f in dataclasses.fields(self)

@@ -792,6 +792,28 @@ int fgcn_data_bn_bwd_reduce(const float* dout, const float* x, const float* vec,
                             int C, int Cp, void* stream);
 int fgcn_data_bn_bwd_apply(const float* dout, const float* x, const float* vec, const float* sums, float* dx, int N, int M, int T,
                            int V, int C, int Cp, int train, void* stream);
+/* ---- the input stage of the RGB patch-feature modes (fgcn_patch.hip) --------------------------------------------------------------
+ * Replaces, in front of data_bn, the reducer / zero-pad / fusion of reference torch_src/models/mmargcn/early_fusion_models.py:48-90
+ * (SkeletonRgbPatchFeaturesEarlyFusion: `patch_feature_dim_reducer` = nn.Sequential(nn.Linear(P, H), nn.Linear(H, Q)), no activation,
+ * then Fusion.combine(skeleton, rgb)) and :163-210 (SkeletonImuRgbPatchFeaturesEarlyFusion: the same, with the reduced rows zero-padded
+ * from Vp patch joints to the V joints of the skeleton + IMU graph AFTER the reducer, so the IMU joints get 0, not b2).
+ *   s  (N, M, T, V, Cs) skeleton rows, or NULL with Cs = 0 (concatenate only);  p (N, M, T, Vp, P) patch rows, Vp <= V;
+ *   w1 (H, P), b1 (H), w2 (Q, H), b2 (Q): the two nn.Linear in their own layout, or w1 = b1 = w2 = b2 = NULL: the identity (Q = P);
+ *   fusion: 0 concatenate z = [s | q] (C = Cs + Q), 1 sum s + q, 2 product s * q, 3 average (s + q) / 2 (1..3: C = Cs = Q);
+ *   z  (N, M, T, V, C): the fused network input, q = 0 for v >= Vp;  stat_partials (may be NULL): what fgcn_data_bn_stats(z) writes,
+ *      float[fgcn_data_bn_tiles(N, T)][2][M*V*C] (it is that kernel, run over z) -> fgcn_bn_finalize / fgcn_data_bn_apply unchanged.
+ * The hidden (rows, H) tensor stays in registers.  Sizes with a reducer: P a multiple of 128 up to 1024, H a multiple of 32 up to 1024,
+ * 1 <= Q <= 32; others are FGCN_E_BADARG.  Math mode: FGCN_MATH_BF16 rounds every operand to bfloat16 once; every other mode (and
+ * product form) multiplies exact float32 operands on v_mfma_f32_32x32x2_f32.
+ * bwd: dz (N, M, T, V, C) = data_bn's dx -> slab partials pw1 float[S][H][P], pb1 [S][H], pw2 [S][Q][H], pb2 [S][Q] of dW1, db1, dW2,
+ *      db2, S = fgcn_patch_input_slabs(N, M, T, Vp, H); sum them with fgcn_reduce_multi (fixed order: bitwise reproducible).  h is
+ *      recomputed from p; s is read for the product's derivative; s and p get no gradient (data).  Identity reducer: nothing to do. */
+int fgcn_patch_input_slabs(int N, int M, int T, int Vp, int H);
+int fgcn_patch_input_fwd(const float* s, const float* p, const float* w1, const float* b1, const float* w2, const float* b2, float* z,
+                         float* stat_partials, int N, int M, int T, int V, int Vp, int Cs, int P, int H, int Q, int fusion, void* stream);
+int fgcn_patch_input_bwd(const float* dz, const float* s, const float* p, const float* w1, const float* b1, const float* w2, float* pw1,
+                         float* pb1, float* pw2, float* pb2, int N, int M, int T, int V, int Vp, int Cs, int P, int H, int Q, int fusion,
+                         void* stream);
 /* nn.CrossEntropyLoss() (mean reduction; session/session.py:53, procedures/step.py:38-46) over logits (rows, classes) with row
  * stride ld and int64 labels: probs float[rows][classes] = softmax (kept for the backward), row_loss float[rows], loss float[2] =
  * {mean over the rows whose label is not -100 (torch's ignore_index rows do not count), that row count}; any OTHER label outside
