@@ -131,6 +131,10 @@ SIGNATURES = {
     "fgcn_joint_dagg": (_I, [_P] * 5 + [_I] * 11 + [_P] * 5),
     "fgcn_adj_softmax_fwd": (_I, [_P, _I, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "fgcn_adj_softmax_bwd": (_I, [_P, _I, _F, _P, _P, _P, _I, _I, _I, _P]),
+    "fgcn_joint_mix_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(MixVItem), _I, _I, _P]),
+    "fgcn_joint_gram_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(GramItem), _I, _P]),
+    "fgcn_adj_softmax_fwd_wide": (_I, [_P, _I, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "fgcn_adj_softmax_bwd_wide": (_I, [_P, _I, _F, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_bn_finalize": (_I, [_P, _I, _LL, _P, _P, _P, _P, _F, _F, _P, _I, _P]),
     "fgcn_bn_eval_coeffs": (_I, [_P, _P, _P, _P, _F, _P, _I, _P]),
     "fgcn_bn_act": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),

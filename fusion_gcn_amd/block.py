@@ -244,9 +244,18 @@ def _vec_width(c: int, order: Sequence[int] = None) -> int:
     return min(narrow) if narrow else 0
 
 
+def _wide_groups(c: int) -> List[Tuple[int, int]]:
+    """(first channel, width) of the 32-channel groups of a ``c``-channel mix on the wide joint kernel (the last group may be narrower)"""
+    return [(c0, min(32, c - c0)) for c0 in range(0, c, 32)]
+
+
 def mix_agg(x: torch.Tensor, agg: torch.Tensor, a_hat: torch.Tensor, cin: int, amax_out=None) -> bool:
     """agg[(k, c)] = x . A^_k for the three subsets (items of one channel group are adjacent: x is loaded once).  ``amax_out``:
-    records max |agg| (ops.joint_mix_vec); -> whether it was recorded."""
+    records max |agg| (ops.joint_mix_vec); -> whether it was recorded (never on a wide graph)."""
+    if ops.wide_graph(x.shape[2]):
+        ops.joint_mix_wide(x, agg, a_hat, [dict(out_c=k * cin + c0, nch=w, terms=[(k, 1, c0)])
+                                           for c0, w in _wide_groups(cin) for k in range(NUM_SUBSETS)])
+        return False
     vw = _vec_width(cin)
     if not vw:
         ops.joint_mix(x, agg, a_hat, spec_agg(cin), in_channels=cin, out_channels=3 * cin)
@@ -260,6 +269,10 @@ def mix_agg(x: torch.Tensor, agg: torch.Tensor, a_hat: torch.Tensor, cin: int, a
 
 def mix_dx(dagg: torch.Tensor, dx: torch.Tensor, a_hat: torch.Tensor, cin: int, accumulate: bool) -> None:
     """dx (+)= sum_k dagg_k . A^_k^T."""
+    if ops.wide_graph(dagg.shape[2]):
+        ops.joint_mix_wide(dagg, dx, a_hat, [dict(out_c=c0, nch=w, terms=[(k, 0, k * cin + c0) for k in range(NUM_SUBSETS)])
+                                             for c0, w in _wide_groups(cin)], accumulate=accumulate)
+        return
     vw = _vec_width(cin)
     if not vw:
         ops.joint_mix(dagg, dx, a_hat, spec_dx(cin), in_channels=3 * cin, out_channels=cin, accumulate=accumulate)
@@ -273,6 +286,15 @@ def mix_dx(dagg: torch.Tensor, dx: torch.Tensor, a_hat: torch.Tensor, cin: int, 
 def mix_demb(emb: torch.Tensor, demb: torch.Tensor, d_s: torch.Tensor, ic: int) -> torch.Tensor:
     """dtheta_k = dS_k . phi_k, dphi_k = dS_k^T . theta_k over the embedding layout [th0 ph0 th1 ph1 th2 ph2];
     returns the column sums of demb (the theta|phi bias gradient), fused into the mix where the kernel allows."""
+    if ops.wide_graph(emb.shape[2]):
+        spec = []
+        for k in range(NUM_SUBSETS):
+            th, ph = 2 * k * ic, (2 * k + 1) * ic
+            for c0, w in _wide_groups(ic):
+                spec.append(dict(out_c=th + c0, nch=w, terms=[(k, 0, ph + c0)]))
+                spec.append(dict(out_c=ph + c0, nch=w, terms=[(k, 1, th + c0)]))
+        ops.joint_mix_wide(emb, demb, d_s, spec)
+        return ops.col_sum(demb, 6 * ic)
     vw = _vec_width(ic)
     if not vw:
         ops.joint_mix(emb, demb, d_s, spec_demb(ic), in_channels=6 * ic, out_channels=6 * ic)
@@ -291,15 +313,20 @@ def mix_demb(emb: torch.Tensor, demb: torch.Tensor, d_s: torch.Tensor, ic: int) 
     return sums
 
 
-def temporal_fwd_records_amax(W, kt: int, s: int, T: int) -> bool:
-    """Whether temporal_fwd takes a halo-kernel route for these sizes (the only routes that record max |g| in math mode f16x2)."""
+def temporal_fwd_records_amax(W, kt: int, s: int, T: int, V: int = 0) -> bool:
+    """Whether temporal_fwd takes a halo-kernel route for these sizes (the only routes that record max |g| in math mode f16x2).
+    ``V``: joints of the graph (a wide graph takes the row GEMM)."""
     pad = (kt - 1) // 2
+    if ops.wide_graph(V):
+        return False
     return (s == 1 and "t4" in W) or (s == 2 and "t4_e" in W and pad % 2 == 0 and T > 1)
 
 
-def temporal_dgrad_records_amax(W, kt: int, s: int) -> bool:
+def temporal_dgrad_records_amax(W, kt: int, s: int, V: int = 0) -> bool:
     """The same for temporal_dgrad and max |du|."""
     pad = (kt - 1) // 2
+    if ops.wide_graph(V):
+        return False
     return (s == 1 and "t_t4" in W) or (s == 2 and "t_t4_e" in W and pad % 2 == 0)
 
 
@@ -310,6 +337,11 @@ def temporal_fwd(g: torch.Tensor, u: torch.Tensor, W: Dict[str, torch.Tensor], b
     g = relu(BatchNorm(y) + shortcut) is formed inside the conv (ops.tconv_halo)."""
     pad = (kt - 1) // 2
     T, Tp = g.shape[1], u.shape[1]
+    if ops.wide_graph(g.shape[2]):
+        # a graph of more than 32 joints: the per-tap row GEMM (the halo kernel's image of (tile rows + (kt - 1) V) rows is sized for
+        # V <= 32: DESIGN.md section 2.1)
+        assert fuse_in is None
+        return ops.rows_gemm(g, W["t"], u, K=g.shape[3], N=u.shape[3], tmap=ops.conv_tmap(kt, s), bias=bias, stats=stats)
     if s == 1 and "t4" in W:
         return ops.tconv_halo(g, W["t4"], u, Th=T, taps=kt, tb=1, tc=-pad, bias=bias, stats=stats, fuse_in=fuse_in, amax_out=amax_out)
     assert fuse_in is None
@@ -331,6 +363,10 @@ def temporal_dgrad(du: torch.Tensor, dg: torch.Tensor, W: Dict[str, torch.Tensor
     the BatchNorm-backward sums of dg against (a, sign image, vec) from the kernel's epilogue -> partials, else None."""
     pad = (kt - 1) // 2
     T, Tp = dg.shape[1], du.shape[1]
+    if ops.wide_graph(dg.shape[2]):
+        assert bn_bwd is None
+        ops.rows_gemm(du, W["t_t"], dg, K=du.shape[3], N=dg.shape[3], tmap=ops.conv_dgrad_tmap(kt, s))
+        return None
     if s == 1 and "t_t4" in W:
         return ops.tconv_halo(du, W["t_t4"], dg, Th=T, taps=kt, tb=-1, tc=pad, bn_bwd=bn_bwd, amax_out=amax_out)
     elif s == 2 and "t_t4_e" in W and pad % 2 == 0:
@@ -369,11 +405,12 @@ def emb_bwd_tile_ok(W, cfg: BlockConfig, B: int, T: int, V: int, cx: int, o_) ->
                 and ops.emb_tile_available(V, ic, cin) and small)
 
 
-def half_storage_ok(W, kt: int, s: int, T: int, train: bool, o_) -> bool:
+def half_storage_ok(W, kt: int, s: int, T: int, train: bool, o_, V: int = 0) -> bool:
     """Whether this block keeps G and dU in bfloat16 (paths.half_storage): math mode bf16, a training step (the eval-mode bias
     gradient reads dU as f32), and the three consumers on their bfloat16-input kernels -- the halo conv forward and data gradient
-    (the routes temporal_fwd / temporal_dgrad take for these sizes) and the all-taps weight gradient (tap counts it is built for)."""
-    if not (train and ops.get_math_mode() == "bf16" and o_.get("half_storage", "bf16")) or kt <= 1:
+    (the routes temporal_fwd / temporal_dgrad take for these sizes) and the all-taps weight gradient (tap counts it is built for).
+    A wide graph (``V`` > 32 joints) keeps float32: those kernels are 32-joint forms."""
+    if not (train and ops.get_math_mode() == "bf16" and o_.get("half_storage", "bf16")) or kt <= 1 or ops.wide_graph(V):
         return False
     pad = (kt - 1) // 2
     per_pass = [kt] if s == 1 else [len([j for j in range(kt) if (j - pad) % s == par]) for par in range(s)]
@@ -390,9 +427,11 @@ def _bn_vec(part, count, P, bufs, name, train):
     return ops.bn_eval_coeffs(g, b, rm, rv)
 
 
-def half_activations_on(train: bool, o_) -> bool:
-    """Whether this block keeps its activation-sized tensors in bfloat16 (paths.half_activations): math mode bf16, a training step."""
-    return bool(train and ops.get_math_mode() == "bf16" and o_.get("half_activations", "bf16") and o_.get("half_storage", "bf16"))
+def half_activations_on(train: bool, o_, V: int = 0) -> bool:
+    """Whether this block keeps its activation-sized tensors in bfloat16 (paths.half_activations): math mode bf16, a training step, a
+    graph of at most 32 joints (the typed bfloat16 forms are 32-joint kernels: a wide graph stores float32 in every math mode)."""
+    return bool(train and ops.get_math_mode() == "bf16" and o_.get("half_activations", "bf16") and o_.get("half_storage", "bf16")
+                and not ops.wide_graph(V))
 
 
 def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, torch.Tensor], W: Dict[str, torch.Tensor],
@@ -412,7 +451,8 @@ def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, t
     o_ = ops.paths()             # this context's kernel-form options (fusion_gcn_amd/paths.py)
     new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
     S: Dict[str, Optional[torch.Tensor]] = {"x": x}
-    ha = half_activations_on(train, o_)
+    wide = ops.wide_graph(V)      # more than 32 joints: the wide joint kernels, the joint-mix spatial form, the row-GEMM temporal conv
+    ha = half_activations_on(train, o_, V)
     x16 = x.dtype == torch.bfloat16
     _x32: List[torch.Tensor] = []
 
@@ -469,7 +509,7 @@ def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, t
     y16 = ha and o_.half_spatial_out and not o_.get("bn_sums_in_dgrad", ops.get_math_mode())
     if cfg.fused_spatial and o_.spatial_tile and cout >= o_.get("spatial_tile_min_cout", ops.get_math_mode()) and "d_s3" in W and ops.spatial_fwd_tile_available(V, cin, cout):
         y, part = ops.spatial_fwd_tile(x if y16 else x32(), a_hat, W["d_s3"], W["d_b"], Cin=cin, Cout=cout, stats=train, y_bf16=y16)
-    elif cfg.fused_spatial and cin <= SPATIAL_FWD_MAX_C:
+    elif cfg.fused_spatial and cin <= SPATIAL_FWD_MAX_C and not wide:
         y, part = ops.spatial_fwd(x32(), a_hat, W["d4"], W["d_b"], Cin=cin, Cout=cout, stats=train)
     else:
         agg = new(B, T, V, 3 * cin)
@@ -480,7 +520,7 @@ def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, t
     # math mode bf16, training: G (the temporal conv's input) is stored as bfloat16 -- only bf16 MFMA staging reads it (the conv and its
     # weight gradient), so the values those kernels multiply are the same and they copy half the bytes (paths.half_storage)
     kt = P["tcn1.conv.weight"].shape[2]
-    half = half_storage_ok(W, kt, s, T, train, o_)
+    half = half_storage_ok(W, kt, s, T, train, o_, V)
     if cfg.has_down:
         # (paths.half_activations: the shortcut conv reads the bfloat16 x and writes a bfloat16 d -- the typed row GEMMs)
         d = torch.empty((B, T, V, cout), device=dev, dtype=torch.bfloat16) if (ha and o_.half_shortcuts) else new(B, T, V, cout)
@@ -519,7 +559,7 @@ def _temporal_stage(x, g, S, P, bufs, W, cfg: BlockConfig, train: bool, pool_gro
     amax = S["amax"]
     if x32 is None:
         x32 = lambda: x          # noqa: E731
-    if infer and s == 1 and kt > 1 and "t4" in W and not pool_groups and cfg.residual in ("none", "identity", "conv") and (cfg.residual != "identity" or x.shape[3] == cout):
+    if infer and s == 1 and kt > 1 and "t4" in W and not pool_groups and not ops.wide_graph(V) and cfg.residual in ("none", "identity", "conv") and (cfg.residual != "identity" or x.shape[3] == cout):
         # north-star kernel 2 as the north star states it, inference form: temporal conv + BatchNorm + shortcut + ReLU in one kernel
         vec_u = _bn_vec(None, B * Tp * V, P, bufs, "tcn1.bn", False)
         r, vec_r = None, None
@@ -535,9 +575,9 @@ def _temporal_stage(x, g, S, P, bufs, W, cfg: BlockConfig, train: bool, pool_gro
         return o, S
     # paths.half_activations: U as bfloat16 where the conv that writes it has the form (the stride-1 halo kernel on a bfloat16 G; the strided
     # conv's second pass accumulates into its output and keeps float32)
-    u16 = bool(half_activations_on(train, o_) and o_.half_conv_out and S.get("half") and s == 1 and kt > 1 and "t4" in W and fuse_in is None)
+    u16 = bool(half_activations_on(train, o_, V) and o_.half_conv_out and S.get("half") and s == 1 and kt > 1 and "t4" in W and fuse_in is None)
     u = torch.empty((B, Tp, V, cout), device=dev, dtype=torch.bfloat16) if u16 else new(B, Tp, V, cout)
-    S["g_amax"] = f16x2 and temporal_fwd_records_amax(W, kt, s, T)
+    S["g_amax"] = f16x2 and temporal_fwd_records_amax(W, kt, s, T, V)
     part = temporal_fwd(g, u, W, P["tcn1.conv.bias"], kt, s, stats=train,
                         fuse_in=fuse_in, amax_out=amax[1:2] if S["g_amax"] else None)
     vec_u = _bn_vec(part, B * Tp * V, P, bufs, "tcn1.bn", train)
@@ -549,7 +589,7 @@ def _temporal_stage(x, g, S, P, bufs, W, cfg: BlockConfig, train: bool, pool_gro
     elif cfg.residual == "identity":
         o, o_sign = epilogue(u, vec_u, x, None)
     else:
-        hs = bool(half_activations_on(train, o_) and o_.half_shortcuts)
+        hs = bool(half_activations_on(train, o_, V) and o_.half_shortcuts)
         r = torch.empty((B, Tp, V, cout), device=dev, dtype=torch.bfloat16) if hs else new(B, Tp, V, cout)
         part = ops.rows_gemm(x if hs else x32(), W["res"], r, K=cin, N=cout, tmap=(1, s, 0, 0, 1), bias=P["residual.conv.bias"], stats=train)
         vec_r = _bn_vec(part, B * Tp * V, P, bufs, "residual.bn", train)
@@ -628,7 +668,8 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     d_o = d_o.contiguous()
     o_numel = B * Tp * V * cout
     kt = P["tcn1.conv.weight"].shape[2]
-    ha = half_activations_on(train, o_)
+    wide = ops.wide_graph(V)     # more than 32 joints: the wide joint kernels and the row-GEMM temporal conv (block_forward)
+    ha = half_activations_on(train, o_, V)
     x16 = x.dtype == torch.bfloat16          # the block's input arrived as bfloat16 (paths.half_activations): its gradient leaves as bfloat16
     # Identity shortcuts (cin == cout, stride 1: both the graph convolution's `y += x` and the block residual) send the ReLU-gated
     # incoming gradients straight to dx.  Instead of the BatchNorm-backward kernels writing / read-modify-writing dx, the kernel
@@ -636,14 +677,14 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     small = lambda width: B * max(T, Tp) * V * width * 4 < 0x7FFF0000      # noqa: E731  the tile kernels address with 32-bit byte offsets
     tile_ok = (o_.spatial_bwd_tile and cin >= o_.spatial_bwd_tile_min_cin and "d_t_b3" in W and ops.spatial_bwd_tile_available(V, cin, cout)
                and (ops.get_math_mode() in ("bf16x3", "bf16") or o_.spatial_bwd_tile_f16x2) and small(max(cin, cout)))
-    gate_in_dagg = ((o_.gated_shortcuts_tile if tile_ok else o_.gated_shortcuts) and o_.fused_dagg and not cfg.has_down and cfg.residual == "identity"
+    gate_in_dagg = ((o_.gated_shortcuts_tile if tile_ok else o_.gated_shortcuts) and o_.fused_dagg and not wide and not cfg.has_down and cfg.residual == "identity"
                     and cx == cfg.cin and cout % 8 == 0 and S["o_sign"] is not None and S["g_sign"] is not None
                     and o_numel * 4 < 0x7FFF0000)
     # -- paths.half_activations: which gradients are bfloat16 tensors --------------------------------------------------------------------
     # dG (written by the temporal data gradient's halo kernel from a bfloat16 dU; not when that kernel's epilogue carries the BatchNorm sums)
     fuse_sums = (o_.get("bn_sums_in_dgrad", ops.get_math_mode()) and cout <= o_.bn_sums_max_c and train and s == 1 and not cfg.has_down and S["g_sign"] is not None
-                 and "t_t4" in W and ops.tconv_halo_bn_sums())
-    dg16 = bool(ha and half and kt > 1 and temporal_dgrad_records_amax(W, kt, s) and not fuse_sums and S["g_sign"] is not None)     # (narrowed below)
+                 and "t_t4" in W and ops.tconv_halo_bn_sums() and not wide)
+    dg16 = bool(ha and half and kt > 1 and temporal_dgrad_records_amax(W, kt, s, V) and not fuse_sums and S["g_sign"] is not None)     # (narrowed below)
     wgrad_tile = (o_.spatial_wgrad_tile and x.shape[3] == cin and ops.spatial_wgrad_tile_available(V, cin, cout) and small(max(cin, cout))
                   and (ops.get_math_mode() in ("bf16x3", "bf16") or o_.spatial_wgrad_tile_f16x2))
     half_dy = bool(train and ops.get_math_mode() == "bf16" and o_.get("half_storage", "bf16") and wgrad_tile and tile_ok and x.shape[3] == cin
@@ -716,11 +757,11 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     bamax = torch.zeros(4, device=dev, dtype=torch.int32) if f16x2 else None
     # (a slot only counts when the kernel that ran really recorded it: the row-GEMM fallbacks of odd paddings / T == 1 record
     # nothing, and a weight gradient scaled by a zero-initialised slot would silently leave the f16 range)
-    du_amax = f16x2 and temporal_dgrad_records_amax(W, kt, s)
+    du_amax = f16x2 and temporal_dgrad_records_amax(W, kt, s, V)
     g_partials = temporal_dgrad(du, dg, W, kt, s, bn_bwd=(S["y"], S["g_sign"], S["vec_y"]) if fuse_sums else None,
                                 amax_out=bamax[0:1] if du_amax else None)
     # weight gradients are reduced straight into the parameter's (out, in, kt, 1) layout: autograd takes them as they are
-    G["tcn1.conv.weight"] = ops.tconv_wgrad(S["g"], du, taps=kt, stride=s, conv_param=(1, cout),
+    G["tcn1.conv.weight"] = ops.tconv_wgrad(S["g"], du, taps=kt, stride=s, conv_param=(1, cout), all_taps=False if wide else None,
                                             amax=(S["amax"][1:2], bamax[0:1]) if du_amax and S.get("g_amax") else None)
     G["tcn1.conv.bias"] = bias_grad(du, cout)
 
@@ -760,7 +801,7 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     # weight gradient of conv_d: agg is recomputed (cheaper than keeping 3 activations per block) and contracted with dy
     if wgrad_tile:
         gw = ops.spatial_wgrad_tile(x_h if dy.dtype == torch.bfloat16 else xf(), dy, a_hat, conv_param=(NUM_SUBSETS, cin_true))   # agg on chip, whole frame tiles
-    elif o_.fused_agg_wgrad and x_h.shape[3] == cin and cin >= 32 and cout <= o_.get("fused_agg_wgrad_max_cout", ops.get_math_mode()):
+    elif o_.fused_agg_wgrad and x_h.shape[3] == cin and cin >= 32 and not wide and cout <= o_.get("fused_agg_wgrad_max_cout", ops.get_math_mode()):
         # agg = x . A^ is formed in registers and contracted with dy at once: never written
         gw = ops.spatial_wgrad(xf(), dy, a_hat, conv_param=(NUM_SUBSETS, cin_true))
     else:
@@ -777,7 +818,7 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     if bwd_tile:
         # dagg on chip: dx and dA^ in one launch (the bfloat16 x beside a bfloat16 dy, whatever dx is)
         part = ops.spatial_bwd_tile(dy, x_h if dy.dtype == torch.bfloat16 else xf(), a_hat, W["d_t_b3"], dx, accumulate=dx_live, gated=gated)
-    elif o_.fused_dagg and x_h.shape[3] == cin:
+    elif o_.fused_dagg and x_h.shape[3] == cin and not wide:
         part = ops.joint_dagg(xf(), dagg, a_hat, dx, accumulate=dx_live, gated=gated)   # dx and dA^ from one pass over dagg
     else:
         mix_dx(dagg, dx, a_hat, cin, accumulate=dx_live)

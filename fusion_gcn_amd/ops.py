@@ -656,6 +656,8 @@ def rows_wgrad(a: torch.Tensor, g: torch.Tensor, *, K: int, N: int, tmap=TMAP_PO
         # measured (tools/kbench.py wgrad): f32 +2-3 % at K = 384 / 768, -10..-25 % for narrower inputs; bf16 mode: faster or
         # equal at every width (the per-tap kernel's two LDS dwords per MFMA become the limit)
         wide = K >= 384 or get_math_mode() != "f32"
+    if wide and wide_graph(V) and not a16:
+        wide = False     # (the multi-accumulator kernel walks the rows of at most 32 joints per frame: fgcn_pw_wgrad)
     if wide and taps == 1 and tc == 0 and td == 1 and ta >= 1 and K % 32 == 0 and (T_g - 1) * ta < T_a:
         # 1x1 (optionally strided) convolution: one accumulator per 32-channel chunk, every g fragment feeds 2-6 MFMAs
         chunks = lib.fgcn_pw_wgrad_chunks(K, N)
@@ -803,6 +805,14 @@ def joint_mix(inp: torch.Tensor, out: torch.Tensor, mats: torch.Tensor, spec: Se
 
 
 MIX_MAX_ITEMS = 24   # FGCN_MIX_MAX_ITEMS (include/fgcn.h)
+MAX_V = 32           # FGCN_MAX_V: joints of the 32-joint kernels (every tile form, the halo conv, the fused spatial kernels)
+MAX_V_WIDE = 64      # FGCN_MAX_V_WIDE: joints of the wide joint kernels (fgcn_joint_wide.hip), the AGCN block's limit
+
+
+def wide_graph(V: int) -> bool:
+    """Whether a graph of V joints takes the block's wide route (block.py): the joint kernels of fgcn_joint_wide.hip and the row-GEMM
+    temporal conv.  V > MAX_V_WIDE takes it too and fails at its first wide kernel with an FgcnError that names the limit."""
+    return V > MAX_V
 
 
 def joint_mix_vec(inp: torch.Tensor, out: torch.Tensor, mats: torch.Tensor, spec: Sequence[dict], *, vw: int,
@@ -838,6 +848,27 @@ def joint_mix_vec(inp: torch.Tensor, out: torch.Tensor, mats: torch.Tensor, spec
     return out
 
 
+def joint_mix_wide(inp: torch.Tensor, out: torch.Tensor, mats: torch.Tensor, spec: Sequence[dict], *, accumulate: bool = False):
+    """``joint_mix_vec``'s formula for graphs of up to MAX_V_WIDE joints (fgcn_joint_mix_wide): spec [{out_c, nch <= 32, terms: [(mat,
+    transpose, in_c)]}], one channel per lane, every item its own width; no column sums, no amax."""
+    ensure_device()
+    _chk(inp, "joint_mix_wide.in"), _chk(out, "joint_mix_wide.out"), _chk(mats, "joint_mix_wide.mats")
+    B, T, V, ld_in = inp.shape
+    if out.shape[:3] != inp.shape[:3] or mats.shape[-1] != V or mats.shape[-2] != V or mats.shape[0] not in (1, B):
+        raise _lib.FgcnError(f"joint_mix_wide: shape mismatch in={tuple(inp.shape)} out={tuple(out.shape)} mats={tuple(mats.shape)}")
+    lib = _lib.load()
+    for lo in range(0, len(spec), MIX_MAX_ITEMS):   # (every item writes its own output channels: a wide spec is split over launches)
+        part = spec[lo:lo + MIX_MAX_ITEMS]
+        arr = (_lib.MixVItem * len(part))()
+        for i, it in enumerate(part):
+            arr[i].out_c, arr[i].nch, arr[i].nterms = it["out_c"], it["nch"], len(it["terms"])
+            for j, (mat, tr, in_c) in enumerate(it["terms"]):
+                arr[i].term[j] = _lib.MixVTerm(mat, tr, in_c)
+        check(lib.fgcn_joint_mix_wide(_p(inp), _p(out), _p(mats), B, T, V, ld_in, out.shape[3], mats.shape[1], int(mats.shape[0] != 1),
+                                      arr, len(part), int(accumulate), _stream()), "fgcn_joint_mix_wide")
+    return out
+
+
 def gram_t_chunk(B: int, T: int) -> int:
     chunk = 32
     while chunk > 4 and B * ((T + chunk - 1) // chunk) < 1024:
@@ -846,7 +877,8 @@ def gram_t_chunk(B: int, T: int) -> int:
 
 
 def joint_gram(in1: torch.Tensor, in2: torch.Tensor, items: Sequence[Tuple[int, int, int]]) -> torch.Tensor:
-    """items: [(c1, c2, width)] (matrix i from item i) -> partial (B, nchunk, n, 32, 32)."""
+    """items: [(c1, c2, width)] (matrix i from item i) -> partial (B, nchunk, n, 32, 32); (B, nchunk, n, 64, 64) for a wide graph
+    (fgcn_joint_gram_wide), the input format adj_softmax_fwd / adj_softmax_bwd read for those V."""
     ensure_device()
     _chk(in1, "joint_gram.in1"), _chk(in2, "joint_gram.in2")
     B, T, V, ld1 = in1.shape
@@ -858,6 +890,11 @@ def joint_gram(in1: torch.Tensor, in2: torch.Tensor, items: Sequence[Tuple[int, 
         arr[i] = GramItem(c1, c2, width, i)
     chunk = gram_t_chunk(B, T)
     nchunk = (T + chunk - 1) // chunk
+    if wide_graph(V):
+        partial = torch.empty((B, nchunk, n, 64, 64), device=in1.device, dtype=torch.float32)
+        check(_lib.load().fgcn_joint_gram_wide(_p(in1), _p(in2), _p(partial), B, T, V, ld1, in2.shape[3], chunk, arr, n, _stream()),
+              "fgcn_joint_gram_wide")
+        return partial
     partial = torch.empty((B, nchunk, n, 32, 32), device=in1.device, dtype=torch.float32)
     check(_lib.load().fgcn_joint_gram(_p(in1), _p(in2), _p(partial), B, T, V, ld1, in2.shape[3], chunk, n, arr, n,
                                       _stream()), "fgcn_joint_gram")
@@ -967,6 +1004,12 @@ def adj_softmax_fwd(partial: Optional[torch.Tensor], scale: float, adj_a: torch.
     a_hat = torch.empty((B, K, V, V), device=adj_a.device, dtype=torch.float32)
     c_out = torch.empty_like(a_hat) if use_softmax else None
     nchunk = partial.shape[1] if partial is not None else 0
+    if wide_graph(V):                # (partials of 64 x 64 matrices: joint_gram's wide form)
+        if partial is not None and tuple(partial.shape[2:]) != (K, 64, 64):
+            raise _lib.FgcnError(f"adj_softmax_fwd: partials {tuple(partial.shape)} are not the wide gram's (B, nchunk, {K}, 64, 64)")
+        check(_lib.load().fgcn_adj_softmax_fwd_wide(_p(partial), nchunk, float(scale), _p(adj_a), _p(adj_b), _p(c_out), _p(a_hat), B,
+                                                    K, V, int(use_softmax), _stream()), "fgcn_adj_softmax_fwd_wide")
+        return c_out, a_hat
     check(_lib.load().fgcn_adj_softmax_fwd(_p(partial), nchunk, float(scale), _p(adj_a), _p(adj_b), _p(c_out), _p(a_hat), B,
                                            K, V, int(use_softmax), _stream()), "fgcn_adj_softmax_fwd")
     return c_out, a_hat
@@ -979,6 +1022,12 @@ def adj_softmax_bwd(partial: torch.Tensor, scale: float, c_in: Optional[torch.Te
     B, nchunk, K = partial.shape[:3]
     d_a_hat = torch.empty((B, K, V, V), device=partial.device, dtype=torch.float32)
     d_s = torch.empty_like(d_a_hat) if c_in is not None else None
+    if wide_graph(V):
+        if tuple(partial.shape[3:]) != (64, 64):
+            raise _lib.FgcnError(f"adj_softmax_bwd: partials {tuple(partial.shape)} are not the wide gram's (B, nchunk, K, 64, 64)")
+        check(_lib.load().fgcn_adj_softmax_bwd_wide(_p(partial), nchunk, float(scale), _p(c_in), _p(d_a_hat), _p(d_s), B, K, V,
+                                                    _stream()), "fgcn_adj_softmax_bwd_wide")
+        return d_a_hat, d_s
     check(_lib.load().fgcn_adj_softmax_bwd(_p(partial), nchunk, float(scale), _p(c_in), _p(d_a_hat), _p(d_s), B, K, V,
                                            _stream()), "fgcn_adj_softmax_bwd")
     return d_a_hat, d_s

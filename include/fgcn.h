@@ -30,6 +30,7 @@ extern "C" {
 #define FGCN_E_ARCH (-4)     /* device is not gfx950 */
 
 #define FGCN_MAX_V 32        /* joints per skeleton graph (reference graphs: 18..27) */
+#define FGCN_MAX_V_WIDE 64   /* joints per graph of the wide joint kernels (fgcn_*_wide), the AGCN block's limit; 33..64 take them */
 #define FGCN_MIX_MAX_ITEMS 24
 #define FGCN_GRAM_MAX_ITEMS 4
 
@@ -537,6 +538,25 @@ int fgcn_adj_softmax_fwd(const float* partial, int nchunk, float scale, const fl
 /* d_a_hat[n,k] = sum_chunks partial ; dS = scale * C .* (dC - colsum(C .* dC))  with dC = d_a_hat (softmax backward) */
 int fgcn_adj_softmax_bwd(const float* partial, int nchunk, float scale, const float* c_in,
                          float* d_a_hat, float* d_s, int B, int K, int V, void* stream);
+
+/* ---- wide graphs: 33 .. FGCN_MAX_V_WIDE joints ------------------------------------------------------------ */
+/* The joint-contracting kernels above hold a joint index on one 32-wide MFMA dimension (V <= FGCN_MAX_V).  These take graphs up to
+ * FGCN_MAX_V_WIDE joints (64 x 64 matrices as 2 x 2 blocks of 32 x 32); the host uses them only for V > FGCN_MAX_V.  Same formulas,
+ * f32 products and accumulation in every math mode.  V > FGCN_MAX_V_WIDE: FGCN_E_BADARG, the message names the limit.
+ *
+ * fgcn_joint_mix_wide: fgcn_joint_mix_vec's formula with its item table, one channel per lane: every item covers 1..32 channels
+ *   (its own nch; in_c / out_c need no alignment), no column sums, no amax.  mats: float[B or 1][n_mats][V][V], n_mats <= 3. */
+int fgcn_joint_mix_wide(const float* in, float* out, const float* mats, int B, int T, int V, int ld_in, int ld_out,
+                        int n_mats, int mats_batched, const fgcn_mixv_item* items, int n_items, int accumulate, void* stream);
+/* fgcn_joint_gram_wide: fgcn_joint_gram's formula, matrix i from item i (1..3 items; channels, widths and strides multiples of 4),
+ *   partial: float[B][ceil(T / t_chunk)][n_items][64][64] (rows / columns >= V are zeros). */
+int fgcn_joint_gram_wide(const float* in1, const float* in2, float* partial, int B, int T, int V, int ld1, int ld2, int t_chunk,
+                         const fgcn_gram_item* items, int n_items, void* stream);
+/* fgcn_adj_softmax_{fwd,bwd}_wide: fgcn_adj_softmax_{fwd,bwd} on partials of 64 x 64 matrices (fgcn_joint_gram_wide's layout, n_items = K). */
+int fgcn_adj_softmax_fwd_wide(const float* partial, int nchunk, float scale, const float* adj_a, const float* adj_b,
+                              float* c_out, float* a_hat, int B, int K, int V, int use_softmax, void* stream);
+int fgcn_adj_softmax_bwd_wide(const float* partial, int nchunk, float scale, const float* c_in,
+                              float* d_a_hat, float* d_s, int B, int K, int V, void* stream);
 
 /* ---- BatchNorm / activation epilogues ------------------------------------------------------------------ */
 /* mean/var from row-tile partials -> scale = gamma*rstd, shift = beta - mean*scale, and the running-stat update
