@@ -7,6 +7,9 @@ Internal layout is channels-last (B, T, V, C) with C padded to a multiple of 4 (
 needs padding).  Every arithmetic step is a libfgcn kernel (fusion_gcn_amd/ops.py); torch is used for buffers,
 the stream and trivial weight re-layout (cat / permute of the small parameter tensors, cached per parameter version).
 
+Which of the forms below a stage runs, and which activation-sized tensor is stored as bfloat16, is decided once per block call by
+routes.plan_block; block_forward keeps the plan in its saved dict and the backward follows it (fusion_gcn_amd/routes.py).
+
 Kernel schedule of one block, train mode (B = N*M samples):
   forward   emb_fwd_tile [split modes: theta|phi 1x1 with the V x V affinity gram formed from the tile on chip]
                (else: rows_gemm / pw_gemm(theta|phi 1x1) -> joint_gram) -> adj_softmax (A^ = A + B + C)
@@ -35,17 +38,13 @@ import torch.nn.functional as F
 
 from . import ops
 from .packing import Form, PackedWeights, Seg
+from .routes import BlockPlan, plan_block, pw_routed, temporal_route
 
 NUM_SUBSETS = 3
 
 
 def _r4(c: int) -> int:
     return (c + 3) // 4 * 4
-
-
-# widest input of fgcn_spatial_fwd (eight 32-channel tiles, fgcn_spatial.hip); a wider block input -- the 512 / 516 channels of the RGB
-# patch-feature modes' first block -- takes the joint mixing + row GEMM form of the spatial stage (the skeleton models never reach it)
-SPATIAL_FWD_MAX_C = 256
 
 
 @dataclass(frozen=True)
@@ -188,29 +187,13 @@ def pack_weights(P: Dict[str, torch.Tensor], cfg: BlockConfig) -> PackedWeights:
     return PackedWeights(F, P["tcn1.conv.weight"].device)
 
 
-# Which kernel form a stage takes (tile forms, fusions, thresholds) is a per-context option: fusion_gcn_amd/paths.py carries the fields,
-# their defaults and the measurement behind each; `ops.paths()` is the calling thread's current set (the backward of a block runs in
-# its forward's context, so both halves see the same options).
-def _pw_min_k(rows: int) -> int:
-    """contraction depth from which a 1x1 convolution with a split form goes to the persistent split-bf16 row GEMM (ops.pw_gemm,
-    fgcn_pw.hip); below it (and in math mode f32) the exact-f32 row GEMM runs (paths.PathOptions.pw_min_k)"""
-    o = ops.paths()
-    if ops.get_math_mode() == "f16x2":
-        return o.pw_min_k_f16x2
-    return min(o.pw_min_k, 64) if rows < o.pw_small_rows else o.pw_min_k
-
-
-def pw_routed(W, key: str, x: torch.Tensor, K: int) -> bool:
-    """Whether pw_gemm sends this 1x1 convolution to the persistent split row GEMM (the kernel that can record max |x|)."""
-    return (key + "_s3") in W and K % 32 == 0 and x.shape[3] == K and K >= _pw_min_k(x.numel() // x.shape[3])
-
-
 def pw_gemm(x: torch.Tensor, W: Dict[str, torch.Tensor], key: str, out: torch.Tensor, *, K: int, N: int,
             bias: Optional[torch.Tensor] = None, stats: bool = False, accumulate: bool = False, amax_out: Optional[torch.Tensor] = None):
     """1x1 convolution over all rows: in the split-bf16 math modes (the packed set then holds the split form of the weight) the
-    persistent split-bf16 row GEMM; the exact-f32 row GEMM otherwise.  ``amax_out``: see ops.pw_gemm (ignored by the f32 kernel)."""
-    w3 = W.get(key + "_s3")
-    if w3 is not None and K % 32 == 0 and x.shape[3] == K and K >= _pw_min_k(x.numel() // x.shape[3]):
+    persistent split-bf16 row GEMM from the contraction depth routes.pw_min_k on; the exact-f32 row GEMM otherwise.  ``amax_out``: see
+    ops.pw_gemm (ignored by the f32 kernel)."""
+    w3 = W.get(key + "_s3")      # (materialises the split form on first use, routed or not)
+    if w3 is not None and x.shape[3] == K and pw_routed(W, key, K, x.numel() // K):
         return ops.pw_gemm(x, w3, out, bias=bias, stats=stats, accumulate=accumulate, amax_out=amax_out)
     return ops.rows_gemm(x, W[key], out, K=K, N=N, bias=bias, stats=stats, accumulate=accumulate)
 
@@ -244,132 +227,100 @@ def _vec_width(c: int, order: Sequence[int] = None) -> int:
     return min(narrow) if narrow else 0
 
 
-def _wide_groups(c: int) -> List[Tuple[int, int]]:
-    """(first channel, width) of the 32-channel groups of a ``c``-channel mix on the wide joint kernel (the last group may be narrower)"""
-    return [(c0, min(32, c - c0)) for c0 in range(0, c, 32)]
+def _mix_groups(c: int, V: int) -> Tuple[List[Tuple[int, int]], int]:
+    """-> ([(first channel, width)] of the channel groups of a ``c``-channel mix on a graph of V joints, channels per lane): 32-channel
+    groups on the wide joint kernel (channels per lane 0; the last group may be narrower), groups of 32 * vw on the vector kernel (they
+    tile ``c`` or are one narrower group), or ([], 0): the dword kernel with its own tables (spec_*)."""
+    wide = ops.wide_graph(V)
+    vw = 0 if wide else _vec_width(c)
+    g = 32 if wide else 32 * vw
+    return ([(c0, min(g, c - c0)) for c0 in range(0, c, g)] if g else []), vw
 
 
 def mix_agg(x: torch.Tensor, agg: torch.Tensor, a_hat: torch.Tensor, cin: int, amax_out=None) -> bool:
     """agg[(k, c)] = x . A^_k for the three subsets (items of one channel group are adjacent: x is loaded once).  ``amax_out``:
     records max |agg| (ops.joint_mix_vec); -> whether it was recorded (never on a wide graph)."""
-    if ops.wide_graph(x.shape[2]):
-        ops.joint_mix_wide(x, agg, a_hat, [dict(out_c=k * cin + c0, nch=w, terms=[(k, 1, c0)])
-                                           for c0, w in _wide_groups(cin) for k in range(NUM_SUBSETS)])
-        return False
-    vw = _vec_width(cin)
-    if not vw:
+    groups, vw = _mix_groups(cin, x.shape[2])
+    spec = [dict(out_c=k * cin + c0, nch=w, terms=[(k, 1, c0)]) for c0, w in groups for k in range(NUM_SUBSETS)]
+    if vw:
+        ops.joint_mix_vec(x, agg, a_hat, spec, vw=vw, amax_out=amax_out)
+        return amax_out is not None
+    if spec:
+        ops.joint_mix_wide(x, agg, a_hat, spec)
+    else:
         ops.joint_mix(x, agg, a_hat, spec_agg(cin), in_channels=cin, out_channels=3 * cin)
-        return False
-    g = 32 * vw
-    spec = [dict(out_c=k * cin + c0, nch=min(g, cin), terms=[(k, 1, c0)])
-            for c0 in range(0, cin, g) for k in range(NUM_SUBSETS)]
-    ops.joint_mix_vec(x, agg, a_hat, spec, vw=vw, amax_out=amax_out)
-    return amax_out is not None
+    return False
 
 
 def mix_dx(dagg: torch.Tensor, dx: torch.Tensor, a_hat: torch.Tensor, cin: int, accumulate: bool) -> None:
     """dx (+)= sum_k dagg_k . A^_k^T."""
-    if ops.wide_graph(dagg.shape[2]):
-        ops.joint_mix_wide(dagg, dx, a_hat, [dict(out_c=c0, nch=w, terms=[(k, 0, k * cin + c0) for k in range(NUM_SUBSETS)])
-                                             for c0, w in _wide_groups(cin)], accumulate=accumulate)
-        return
-    vw = _vec_width(cin)
-    if not vw:
+    groups, vw = _mix_groups(cin, dagg.shape[2])
+    spec = [dict(out_c=c0, nch=w, terms=[(k, 0, k * cin + c0) for k in range(NUM_SUBSETS)]) for c0, w in groups]
+    if vw:
+        ops.joint_mix_vec(dagg, dx, a_hat, spec, vw=vw, accumulate=accumulate)
+    elif spec:
+        ops.joint_mix_wide(dagg, dx, a_hat, spec, accumulate=accumulate)
+    else:
         ops.joint_mix(dagg, dx, a_hat, spec_dx(cin), in_channels=3 * cin, out_channels=cin, accumulate=accumulate)
-        return
-    g = 32 * vw
-    spec = [dict(out_c=c0, nch=min(g, cin), terms=[(k, 0, k * cin + c0) for k in range(NUM_SUBSETS)])
-            for c0 in range(0, cin, g)]
-    ops.joint_mix_vec(dagg, dx, a_hat, spec, vw=vw, accumulate=accumulate)
 
 
 def mix_demb(emb: torch.Tensor, demb: torch.Tensor, d_s: torch.Tensor, ic: int) -> torch.Tensor:
     """dtheta_k = dS_k . phi_k, dphi_k = dS_k^T . theta_k over the embedding layout [th0 ph0 th1 ph1 th2 ph2];
     returns the column sums of demb (the theta|phi bias gradient), fused into the mix where the kernel allows."""
-    if ops.wide_graph(emb.shape[2]):
-        spec = []
-        for k in range(NUM_SUBSETS):
-            th, ph = 2 * k * ic, (2 * k + 1) * ic
-            for c0, w in _wide_groups(ic):
-                spec.append(dict(out_c=th + c0, nch=w, terms=[(k, 0, ph + c0)]))
-                spec.append(dict(out_c=ph + c0, nch=w, terms=[(k, 1, th + c0)]))
-        ops.joint_mix_wide(emb, demb, d_s, spec)
-        return ops.col_sum(demb, 6 * ic)
-    vw = _vec_width(ic)
-    if not vw:
-        ops.joint_mix(emb, demb, d_s, spec_demb(ic), in_channels=6 * ic, out_channels=6 * ic)
-        return ops.col_sum(demb, 6 * ic)
-    g = 32 * vw
+    groups, vw = _mix_groups(ic, emb.shape[2])
     spec = []
     for k in range(NUM_SUBSETS):
         th, ph = 2 * k * ic, (2 * k + 1) * ic
-        for c0 in range(0, ic, g):
-            spec.append(dict(out_c=th + c0, nch=min(g, ic), terms=[(k, 0, ph + c0)]))
-            spec.append(dict(out_c=ph + c0, nch=min(g, ic), terms=[(k, 1, th + c0)]))
-    if len(spec) > ops.MIX_MAX_ITEMS:
+        for c0, w in groups:
+            spec.append(dict(out_c=th + c0, nch=w, terms=[(k, 0, ph + c0)]))
+            spec.append(dict(out_c=ph + c0, nch=w, terms=[(k, 1, th + c0)]))
+    if vw and len(spec) <= ops.MIX_MAX_ITEMS:
+        return ops.joint_mix_vec(emb, demb, d_s, spec, vw=vw, colsum=True)[1]
+    if vw:
         ops.joint_mix_vec(emb, demb, d_s, spec, vw=vw)
-        return ops.col_sum(demb, 6 * ic)
-    _, sums = ops.joint_mix_vec(emb, demb, d_s, spec, vw=vw, colsum=True)
-    return sums
-
-
-def temporal_fwd_records_amax(W, kt: int, s: int, T: int, V: int = 0) -> bool:
-    """Whether temporal_fwd takes a halo-kernel route for these sizes (the only routes that record max |g| in math mode f16x2).
-    ``V``: joints of the graph (a wide graph takes the row GEMM)."""
-    pad = (kt - 1) // 2
-    if ops.wide_graph(V):
-        return False
-    return (s == 1 and "t4" in W) or (s == 2 and "t4_e" in W and pad % 2 == 0 and T > 1)
-
-
-def temporal_dgrad_records_amax(W, kt: int, s: int, V: int = 0) -> bool:
-    """The same for temporal_dgrad and max |du|."""
-    pad = (kt - 1) // 2
-    if ops.wide_graph(V):
-        return False
-    return (s == 1 and "t_t4" in W) or (s == 2 and "t_t4_e" in W and pad % 2 == 0)
+    elif spec:
+        ops.joint_mix_wide(emb, demb, d_s, spec)
+    else:
+        ops.joint_mix(emb, demb, d_s, spec_demb(ic), in_channels=6 * ic, out_channels=6 * ic)
+    return ops.col_sum(demb, 6 * ic)
 
 
 def temporal_fwd(g: torch.Tensor, u: torch.Tensor, W: Dict[str, torch.Tensor], bias: torch.Tensor, kt: int, s: int,
-                 stats: bool, fuse_in=None, amax_out=None):
-    """u = Conv(kt x 1, stride s, pad (kt-1)//2)(g) + bias, with BatchNorm partial sums of u when ``stats``.
+                 stats: bool, fuse_in=None, amax_out=None, route: Optional[str] = None):
+    """u = Conv(kt x 1, stride s, pad (kt-1)//2)(g) + bias, with BatchNorm partial sums of u when ``stats``.  ``route``: the block's
+    plan (routes.temporal_route, asked here when a caller has none).
     ``fuse_in = (vec, shortcut, g_out, g_sign)`` (stride 1, split-bf16 kernel): the first argument is the BatchNorm input y and
     g = relu(BatchNorm(y) + shortcut) is formed inside the conv (ops.tconv_halo)."""
     pad = (kt - 1) // 2
     T, Tp = g.shape[1], u.shape[1]
-    if ops.wide_graph(g.shape[2]):
-        # a graph of more than 32 joints: the per-tap row GEMM (the halo kernel's image of (tile rows + (kt - 1) V) rows is sized for
-        # V <= 32: DESIGN.md section 2.1)
-        assert fuse_in is None
-        return ops.rows_gemm(g, W["t"], u, K=g.shape[3], N=u.shape[3], tmap=ops.conv_tmap(kt, s), bias=bias, stats=stats)
-    if s == 1 and "t4" in W:
+    route = route or temporal_route(W, kt, s, T, ops.wide_graph(g.shape[2]), "fwd")
+    if route == "halo":
         return ops.tconv_halo(g, W["t4"], u, Th=T, taps=kt, tb=1, tc=-pad, bias=bias, stats=stats, fuse_in=fuse_in, amax_out=amax_out)
     assert fuse_in is None
-    if s == 2 and "t4_e" in W and pad % 2 == 0 and T > 1:
+    if route == "halo_parity":
         # output frame to meets tap j = 2j' + par at input frame 2 (to + j' - pad/2) + par: one pass over the even input
         # frames (taps 0, 2, ..), one accumulating pass over the odd ones (which also takes the BatchNorm sums)
         ops.tconv_halo(g, W["t4_e"], u, Th=Tp, taps=(kt + 1) // 2, tb=1, tc=-(pad // 2), in_view=(2, 0, (T + 1) // 2),
                        bias=bias, amax_out=amax_out)
         return ops.tconv_halo(g, W["t4_o"], u, Th=Tp, taps=kt // 2, tb=1, tc=-(pad // 2), in_view=(2, 1, T // 2),
                               stats=stats, accumulate=True, amax_out=amax_out)
-    # strided forward in f32: the per-tap row GEMM measures faster than two accumulating halo passes over the even / odd
-    # input frames (1.26 vs 1.54 ms at 128 channels, T 300 -> 150); on the split-bf16 kernels (math mode bf16x3: the packed
-    # set then holds t4_e / t4_o) the two passes win
+    # the per-tap row GEMM.  A graph of more than 32 joints: the halo kernel's image is sized for V <= 32 (DESIGN.md section 2.1).  Strided forward
+    # in f32: it measures faster than two accumulating halo passes over the even / odd input frames (1.26 vs 1.54 ms at 128 channels, T 300 ->
+    # 150); on the split-bf16 kernels (the packed set then holds t4_e / t4_o) the two passes win
     return ops.rows_gemm(g, W["t"], u, K=g.shape[3], N=u.shape[3], tmap=ops.conv_tmap(kt, s), bias=bias, stats=stats)
 
 
-def temporal_dgrad(du: torch.Tensor, dg: torch.Tensor, W: Dict[str, torch.Tensor], kt: int, s: int, bn_bwd=None, amax_out=None):
+def temporal_dgrad(du: torch.Tensor, dg: torch.Tensor, W: Dict[str, torch.Tensor], kt: int, s: int, bn_bwd=None, amax_out=None,
+                   route: Optional[str] = None):
     """dg = data gradient of that convolution: dg[t] = sum_j W_j^T du[(t + pad - j) / s].  ``bn_bwd`` (stride 1, split-bf16 kernel):
     the BatchNorm-backward sums of dg against (a, sign image, vec) from the kernel's epilogue -> partials, else None."""
     pad = (kt - 1) // 2
-    T, Tp = dg.shape[1], du.shape[1]
-    if ops.wide_graph(dg.shape[2]):
-        assert bn_bwd is None
-        ops.rows_gemm(du, W["t_t"], dg, K=du.shape[3], N=dg.shape[3], tmap=ops.conv_dgrad_tmap(kt, s))
-        return None
-    if s == 1 and "t_t4" in W:
+    T = dg.shape[1]
+    route = route or temporal_route(W, kt, s, T, ops.wide_graph(dg.shape[2]), "dgrad")
+    if route == "halo":
         return ops.tconv_halo(du, W["t_t4"], dg, Th=T, taps=kt, tb=-1, tc=pad, bn_bwd=bn_bwd, amax_out=amax_out)
-    elif s == 2 and "t_t4_e" in W and pad % 2 == 0:
+    assert bn_bwd is None
+    if route == "halo_parity":
         # frame t = 2*th + par only meets taps j = 2j' + par, at du frame th + pad/2 - j'
         ops.tconv_halo(du, W["t_t4_e"], dg, Th=(T + 1) // 2, taps=(kt + 1) // 2, tb=-1, tc=pad // 2, out_view=(2, 0), amax_out=amax_out)
         if T > 1:
@@ -396,28 +347,6 @@ def spec_demb(ic: int) -> List[dict]:
     return out
 
 
-def emb_bwd_tile_ok(W, cfg: BlockConfig, B: int, T: int, V: int, cx: int, o_) -> bool:
-    """Whether block_backward takes the tile form of the embedding backward (ops.emb_dx_tile + ops.emb_wgrad_tile) for this block -- one
-    predicate for the backward and for the forward, which stores emb as bfloat16 in math mode bf16 only if its readers are those two."""
-    cin, ic = cx, cfg.ic
-    small = B * T * V * max(6 * ic, cx) * 4 < 0x7FFF0000
-    return bool(o_.emb_tile and cin <= o_.get("emb_tile_max_cin", ops.get_math_mode()) and "emb_t_b3" in W and cx == cfg.cin
-                and ops.emb_tile_available(V, ic, cin) and small)
-
-
-def half_storage_ok(W, kt: int, s: int, T: int, train: bool, o_, V: int = 0) -> bool:
-    """Whether this block keeps G and dU in bfloat16 (paths.half_storage): math mode bf16, a training step (the eval-mode bias
-    gradient reads dU as f32), and the three consumers on their bfloat16-input kernels -- the halo conv forward and data gradient
-    (the routes temporal_fwd / temporal_dgrad take for these sizes) and the all-taps weight gradient (tap counts it is built for).
-    A wide graph (``V`` > 32 joints) keeps float32: those kernels are 32-joint forms."""
-    if not (train and ops.get_math_mode() == "bf16" and o_.get("half_storage", "bf16")) or kt <= 1 or ops.wide_graph(V):
-        return False
-    pad = (kt - 1) // 2
-    per_pass = [kt] if s == 1 else [len([j for j in range(kt) if (j - pad) % s == par]) for par in range(s)]
-    return (temporal_fwd_records_amax(W, kt, s, T) and temporal_dgrad_records_amax(W, kt, s)
-            and all(n in ops.TWGRAD_TAPS_SPLIT for n in per_pass if n))
-
-
 # ---- forward ---------------------------------------------------------------------------------------------------------
 def _bn_vec(part, count, P, bufs, name, train):
     g, b = P[f"{name}.weight"], P[f"{name}.bias"]
@@ -427,11 +356,15 @@ def _bn_vec(part, count, P, bufs, name, train):
     return ops.bn_eval_coeffs(g, b, rm, rv)
 
 
-def half_activations_on(train: bool, o_, V: int = 0) -> bool:
-    """Whether this block keeps its activation-sized tensors in bfloat16 (paths.half_activations): math mode bf16, a training step, a
-    graph of at most 32 joints (the typed bfloat16 forms are 32-joint kernels: a wide graph stores float32 in every math mode)."""
-    return bool(train and ops.get_math_mode() == "bf16" and o_.get("half_activations", "bf16") and o_.get("half_storage", "bf16")
-                and not ops.wide_graph(V))
+def _f32_once(x: torch.Tensor):
+    """-> a function returning x as float32, for the kernels without a bfloat16-input form: converted once, on first use"""
+    cache = [] if x.dtype == torch.bfloat16 else [x]
+
+    def get() -> torch.Tensor:
+        if not cache:
+            cache.append(x.float())
+        return cache[0]
+    return get
 
 
 def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, torch.Tensor], W: Dict[str, torch.Tensor],
@@ -441,60 +374,41 @@ def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, t
     ``inference`` (eval mode, no autograd graph): BatchNorm + shortcut + ReLU run as the EPILOGUES of the two north-star kernels where
     their inference forms exist (paths.fused_inference) -- no pre-BatchNorm tensors, no bn_act passes, nothing saved for a backward.
     Math mode bf16 (paths.half_activations): ``x`` may be a bfloat16 tensor (the previous block's output), Y / U are stored as bfloat16 where
-    their producers have the form, and ``out_half`` (the caller takes a bfloat16 output: the next block) makes O one too."""
+    their producers have the form, and ``out_half`` (the caller takes a bfloat16 output: the next block) makes O one too.
+    Every kernel form and storage type is a field of the routes.BlockPlan made here, first, from the math mode and the context's options
+    read once; it travels to the backward in the saved dict (``S["plan"]``), and the backward follows it."""
     B, T, V, cx = x.shape
-    cout, ic, s = cfg.cout, cfg.ic, cfg.stride
+    cout, ic = cfg.cout, cfg.ic
     assert cx == cfg.cx, (cx, cfg.cx)
     cin = cx                     # kernels work on the padded channel count; the pad channel is identically zero
-    Tp = (T - 1) // s + 1
     dev = x.device
-    o_ = ops.paths()             # this context's kernel-form options (fusion_gcn_amd/paths.py)
+    pl = plan_block(cfg, B, T, V, x_bf16=x.dtype == torch.bfloat16, train=train, inference=inference, pool_groups=pool_groups, out_half=out_half,
+                    forms=W, mode=ops.get_math_mode(), paths=ops.paths(), kt=P["tcn1.conv.weight"].shape[2])
     new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
-    S: Dict[str, Optional[torch.Tensor]] = {"x": x}
-    wide = ops.wide_graph(V)      # more than 32 joints: the wide joint kernels, the joint-mix spatial form, the row-GEMM temporal conv
-    ha = half_activations_on(train, o_, V)
-    x16 = x.dtype == torch.bfloat16
-    _x32: List[torch.Tensor] = []
-
-    def x32() -> torch.Tensor:      # x for a kernel without a bfloat16-input form (converted once, on first use)
-        if not x16:
-            return x
-        if not _x32:
-            _x32.append(x.float())
-        return _x32[0]
-    if x16 and not ha:
-        raise ops._lib.FgcnError("block_forward: a bfloat16 input needs math mode bf16 with paths.half_activations (a training step)")
-    # math mode f16x2: the largest magnitudes of x and G, recorded by the kernels that stage them (pw_gemm / tconv_halo), scale the
-    # same tensors in the backward's weight gradients; slot 0 = x (only when the embedding runs on the split row GEMM), 1 = G
-    f16x2 = ops.get_math_mode() == "f16x2"
-    amax = torch.zeros(4, device=dev, dtype=torch.int32) if f16x2 else None
-    S["amax"], S["x_amax"], S["g_amax"] = amax, False, False   # *_amax: the slot was really recorded (a row-GEMM fallback records nothing)
+    S: Dict[str, Optional[torch.Tensor]] = {"x": x, "plan": pl}
+    x32 = _f32_once(x)
+    # math mode f16x2: the largest magnitudes of x and G, recorded by the kernels that stage them (pw_gemm / tconv_halo), scale the same tensors
+    # in the backward's weight gradients; slot 0 = x, 1 = G (plan.x_amax / g_amax: really recorded -- a row-GEMM fallback records nothing)
+    amax = S["amax"] = torch.zeros(4, device=dev, dtype=torch.int32) if pl.mode == "f16x2" else None
 
     # -- data-dependent adjacency ------------------------------------------------------------------------------------
     adj_a, adj_b = bufs["gcn1.adj_a"], P["gcn1.adj_b"].detach()
-    if cfg.static_adjacency:
+    if pl.emb_fwd is None:
         emb, c_mat = None, None
         _, a_hat = ops.adj_softmax_fwd(None, 1.0, adj_a, 1, use_softmax=False, adj_b=adj_b)
     else:
-        no_emb = bool(inference and not train and o_.fused_inference)      # inference: the tile form writes no embeddings at all -- it stays at every ic
-        if (o_.emb_fwd_tile and cin <= o_.get("emb_fwd_tile_max_cin", ops.get_math_mode()) and (no_emb or ic <= o_.get("emb_fwd_tile_max_ic", ops.get_math_mode()))
-                and "emb_b3" in W and ops.emb_fwd_tile_available(V, ic, cin)
-                and B * T * V * max(cin, 6 * ic) * 4 < 0x7FFF0000):
+        if pl.emb_fwd == "tile":
             # emb written once, the gram from the tile on chip (inference: not written at all -- only the backward reads it)
-            half_emb = bool(train and ops.get_math_mode() == "bf16" and o_.get("half_storage", "bf16") and emb_bwd_tile_ok(W, cfg, B, T, V, cx, o_))
-            emb, part = ops.emb_fwd_tile(x, W["emb_b3"], W["emb_b"], ic=ic, write_emb=not no_emb, emb_bf16=half_emb)
+            emb, part = ops.emb_fwd_tile(x, W["emb_b3"], W["emb_b"], ic=ic, write_emb=pl.write_emb, emb_bf16=pl.emb_bf16)
         else:
             emb = new(B, T, V, 6 * ic)
-            S["x_amax"] = f16x2 and pw_routed(W, "emb", x, cin)
-            pw_gemm(x, W, "emb", emb, K=cin, N=6 * ic, bias=W["emb_b"], amax_out=amax[0:1] if S["x_amax"] else None)
+            pw_gemm(x, W, "emb", emb, K=cin, N=6 * ic, bias=W["emb_b"], amax_out=amax[0:1] if pl.x_amax else None)
             part = ops.joint_gram(emb, emb, [(2 * k * ic, (2 * k + 1) * ic, ic) for k in range(NUM_SUBSETS)])
         c_mat, a_hat = ops.adj_softmax_fwd(part, 1.0 / (ic * T), adj_a, B, adj_b=adj_b)
     S.update(emb=emb, c_mat=c_mat, a_hat=a_hat)
 
     # -- spatial aggregation + conv_d ------------------------------------------------------------------------------------
-    infer = bool(inference and not train and o_.fused_inference and ops.inference_kernels_available())
-    kt = P["tcn1.conv.weight"].shape[2]
-    if infer and cfg.fused_spatial and "d_s3" in W and ops.spatial_fwd_tile_available(V, cin, cout) and (cfg.has_down or x.shape[3] >= cout):
+    if pl.spatial_fwd == "tile_bn_relu":
         # north-star kernel 1, inference form: aggregation + feature contraction + BatchNorm + shortcut + ReLU in one kernel
         vec_y = _bn_vec(None, B * T * V, P, bufs, "gcn1.bn", False)
         d, vec_d = None, None
@@ -503,13 +417,11 @@ def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, t
             pw_gemm(x32(), W, "down", d, K=cin, N=cout, bias=P["gcn1.down.0.bias"])
             vec_d = _bn_vec(None, B * T * V, P, bufs, "gcn1.down.1", False)
         g = ops.spatial_fwd_tile_bn_relu(x, a_hat, W["d_s3"], W["d_b"], vec_y, Cin=cin, Cout=cout, res=d if cfg.has_down else x, res_vec=vec_d)
-        S.update(y=None, vec_y=vec_y, d=None, vec_d=vec_d, g=g, g_sign=None, half=False)
-        return _temporal_stage(x, g, S, P, bufs, W, cfg, train, pool_groups, infer, kt, o_)
-    # (Y as bfloat16: not when the temporal data gradient is to carry the BatchNorm-backward sums -- that epilogue reads Y as float32)
-    y16 = ha and o_.half_spatial_out and not o_.get("bn_sums_in_dgrad", ops.get_math_mode())
-    if cfg.fused_spatial and o_.spatial_tile and cout >= o_.get("spatial_tile_min_cout", ops.get_math_mode()) and "d_s3" in W and ops.spatial_fwd_tile_available(V, cin, cout):
-        y, part = ops.spatial_fwd_tile(x if y16 else x32(), a_hat, W["d_s3"], W["d_b"], Cin=cin, Cout=cout, stats=train, y_bf16=y16)
-    elif cfg.fused_spatial and cin <= SPATIAL_FWD_MAX_C and not wide:
+        S.update(y=None, vec_y=vec_y, d=None, vec_d=vec_d, g=g, g_sign=None)
+        return _temporal_stage(x, S, P, bufs, W, cfg, pl, x32)
+    if pl.spatial_fwd == "tile":
+        y, part = ops.spatial_fwd_tile(x if pl.y_bf16 else x32(), a_hat, W["d_s3"], W["d_b"], Cin=cin, Cout=cout, stats=train, y_bf16=pl.y_bf16)
+    elif pl.spatial_fwd == "fused":
         y, part = ops.spatial_fwd(x32(), a_hat, W["d4"], W["d_b"], Cin=cin, Cout=cout, stats=train)
     else:
         agg = new(B, T, V, 3 * cin)
@@ -517,49 +429,34 @@ def block_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], bufs: Dict[str, t
         y = new(B, T, V, cout)
         part = ops.rows_gemm(agg, W["d"].unsqueeze(0), y, K=3 * cin, N=cout, bias=W["d_b"], stats=train)
     vec_y = _bn_vec(part, B * T * V, P, bufs, "gcn1.bn", train)
-    # math mode bf16, training: G (the temporal conv's input) is stored as bfloat16 -- only bf16 MFMA staging reads it (the conv and its
-    # weight gradient), so the values those kernels multiply are the same and they copy half the bytes (paths.half_storage)
-    kt = P["tcn1.conv.weight"].shape[2]
-    half = half_storage_ok(W, kt, s, T, train, o_, V)
+    # (plan.g_bf16: G, the temporal conv's input, as bfloat16 -- only bf16 MFMA staging reads it, so the values multiplied are the same)
+    d, vec_d = None, None
     if cfg.has_down:
-        # (paths.half_activations: the shortcut conv reads the bfloat16 x and writes a bfloat16 d -- the typed row GEMMs)
-        d = torch.empty((B, T, V, cout), device=dev, dtype=torch.bfloat16) if (ha and o_.half_shortcuts) else new(B, T, V, cout)
-        part = pw_gemm(x if (ha and o_.half_shortcuts) else x32(), W, "down", d, K=cin, N=cout, bias=P["gcn1.down.0.bias"], stats=train)
+        # (plan.shortcuts_bf16: the shortcut conv reads the bfloat16 x and writes a bfloat16 d -- the typed row GEMMs)
+        d = torch.empty((B, T, V, cout), device=dev, dtype=torch.bfloat16) if pl.shortcuts_bf16 else new(B, T, V, cout)
+        part = pw_gemm(x if pl.shortcuts_bf16 else x32(), W, "down", d, K=cin, N=cout, bias=P["gcn1.down.0.bias"], stats=train)
         vec_d = _bn_vec(part, B * T * V, P, bufs, "gcn1.down.1", train)
-        g, g_sign = ops.bn_act(y, vec_y, d, vec_d, relu=True, sign_mask=True, out_bf16=half)
-    else:
-        d, vec_d = None, None
-    # identity blocks on the split-bf16 kernels: G = relu(BatchNorm(y) + x) is formed INSIDE the temporal conv while it stages its
-    # image (north-star kernel 2: "temporal 9x1 conv + BN + ReLU"), G and its sign image come out as by-products -- no bn_act pass
-    fuse_g = (o_.fuse_g and not half and not ha and not cfg.has_down and s == 1 and kt > 1 and "t4" in W and ops.tconv_halo_bn_sums()
-              and cx == cout and V <= 32 and (B * T * V * cout) % 8 == 0)
-    if fuse_g:
+        g, g_sign = ops.bn_act(y, vec_y, d, vec_d, relu=True, sign_mask=True, out_bf16=pl.g_bf16)
+    elif pl.fuse_g:
+        # identity blocks on the split-bf16 kernels: G = relu(BatchNorm(y) + x) is formed INSIDE the temporal conv while it stages its
+        # image (north-star kernel 2: "temporal 9x1 conv + BN + ReLU"), G and its sign image come out as by-products -- no bn_act pass
         g = new(B, T, V, cout)
         g_sign = torch.empty((B * T * V * cout) // 8, device=dev, dtype=torch.uint8)
-    elif not cfg.has_down:
-        g, g_sign = ops.bn_act(y, vec_y, x, None, relu=True, sign_mask=True, out_bf16=half)
-    if half and g_sign is None:      # (no sign image: the backward would gate on g itself, which it reads as f32 -- cout % 64 == 0 rules it out)
-        raise ops._lib.FgcnError("half-precision storage of G needs the sign image (element count a multiple of 8)")
-    S.update(y=y, vec_y=vec_y, d=d, vec_d=vec_d, g=g, g_sign=g_sign, half=half)   # *_sign: 1 bit per element, the backward's ReLU gate
-
-    return _temporal_stage(x, y if fuse_g else g, S, P, bufs, W, cfg, train, pool_groups, infer, kt, o_, fuse_in=(vec_y, x, g, g_sign) if fuse_g else None,
-                           x32=x32, out_half=bool(ha and out_half))
+    else:
+        g, g_sign = ops.bn_act(y, vec_y, x, None, relu=True, sign_mask=True, out_bf16=pl.g_bf16)
+    S.update(y=y, vec_y=vec_y, d=d, vec_d=vec_d, g=g, g_sign=g_sign)   # *_sign: 1 bit per element, the backward's ReLU gate
+    return _temporal_stage(x, S, P, bufs, W, cfg, pl, x32)
 
 
-def _temporal_stage(x, g, S, P, bufs, W, cfg: BlockConfig, train: bool, pool_groups: int, infer: bool, kt: int, o_, fuse_in=None, x32=None,
-                    out_half: bool = False):
+def _temporal_stage(x, S, P, bufs, W, cfg: BlockConfig, pl: BlockPlan, x32):
     """The second half of block_forward: the temporal conv, its BatchNorm, the block's shortcut and ReLU (agcn.py:49-51,125-136)."""
-    B, T, V, cx = x.shape
-    cout, s = cfg.cout, cfg.stride
-    cin = cx
+    B, T, V, cin = x.shape
+    cout, s, train, pool_groups = cfg.cout, cfg.stride, pl.train, pl.pool_groups
+    kt = P["tcn1.conv.weight"].shape[2]
     Tp = (T - 1) // s + 1
     dev = x.device
     new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
-    f16x2 = ops.get_math_mode() == "f16x2"
-    amax = S["amax"]
-    if x32 is None:
-        x32 = lambda: x          # noqa: E731
-    if infer and s == 1 and kt > 1 and "t4" in W and not pool_groups and not ops.wide_graph(V) and cfg.residual in ("none", "identity", "conv") and (cfg.residual != "identity" or x.shape[3] == cout):
+    if pl.temporal_bn_relu:
         # north-star kernel 2 as the north star states it, inference form: temporal conv + BatchNorm + shortcut + ReLU in one kernel
         vec_u = _bn_vec(None, B * Tp * V, P, bufs, "tcn1.bn", False)
         r, vec_r = None, None
@@ -568,34 +465,26 @@ def _temporal_stage(x, g, S, P, bufs, W, cfg: BlockConfig, train: bool, pool_gro
             ops.rows_gemm(x, W["res"], r, K=cin, N=cout, tmap=(1, s, 0, 0, 1), bias=P["residual.conv.bias"])
             vec_r = _bn_vec(None, B * Tp * V, P, bufs, "residual.bn", False)
         o = new(B, Tp, V, cout)
-        pad = (kt - 1) // 2
-        ops.tconv_halo_bn_relu(g, W["t4"], o, taps=kt, tb=1, tc=-pad, vec=vec_u, bias=P["tcn1.conv.bias"],
+        ops.tconv_halo_bn_relu(S["g"], W["t4"], o, taps=kt, tb=1, tc=-((kt - 1) // 2), vec=vec_u, bias=P["tcn1.conv.bias"],
                                res=x if cfg.residual == "identity" else r, res_vec=vec_r)
         S.update(u=None, vec_u=vec_u, r=None, vec_r=vec_r, o=o, o_sign=None)
         return o, S
-    # paths.half_activations: U as bfloat16 where the conv that writes it has the form (the stride-1 halo kernel on a bfloat16 G; the strided
-    # conv's second pass accumulates into its output and keeps float32)
-    u16 = bool(half_activations_on(train, o_, V) and o_.half_conv_out and S.get("half") and s == 1 and kt > 1 and "t4" in W and fuse_in is None)
-    u = torch.empty((B, Tp, V, cout), device=dev, dtype=torch.bfloat16) if u16 else new(B, Tp, V, cout)
-    S["g_amax"] = f16x2 and temporal_fwd_records_amax(W, kt, s, T, V)
-    part = temporal_fwd(g, u, W, P["tcn1.conv.bias"], kt, s, stats=train,
-                        fuse_in=fuse_in, amax_out=amax[1:2] if S["g_amax"] else None)
+    u = torch.empty((B, Tp, V, cout), device=dev, dtype=torch.bfloat16) if pl.u_bf16 else new(B, Tp, V, cout)
+    # (plan.fuse_g: the conv's first argument is the BatchNorm input y; it forms G and its sign image on the way)
+    part = temporal_fwd(S["y"] if pl.fuse_g else S["g"], u, W, P["tcn1.conv.bias"], kt, s, stats=train, route=pl.temporal_fwd,
+                        fuse_in=(S["vec_y"], x, S["g"], S["g_sign"]) if pl.fuse_g else None, amax_out=S["amax"][1:2] if pl.g_amax else None)
     vec_u = _bn_vec(part, B * Tp * V, P, bufs, "tcn1.bn", train)
     r, vec_r = None, None
-    epilogue = (lambda a, va, b, vb: ops.bn_act_pool(a, va, b, vb, pool_groups)) if pool_groups else \
-               (lambda a, va, b, vb: ops.bn_act(a, va, b, vb, relu=True, sign_mask=True, out_bf16=out_half))
-    if cfg.residual == "none":
-        o, o_sign = epilogue(u, vec_u, None, None)
-    elif cfg.residual == "identity":
-        o, o_sign = epilogue(u, vec_u, x, None)
-    else:
-        hs = bool(half_activations_on(train, o_, V) and o_.half_shortcuts)
+    if cfg.residual == "conv":
+        hs = pl.shortcuts_bf16
         r = torch.empty((B, Tp, V, cout), device=dev, dtype=torch.bfloat16) if hs else new(B, Tp, V, cout)
         part = ops.rows_gemm(x if hs else x32(), W["res"], r, K=cin, N=cout, tmap=(1, s, 0, 0, 1), bias=P["residual.conv.bias"], stats=train)
         vec_r = _bn_vec(part, B * Tp * V, P, bufs, "residual.bn", train)
-        o, o_sign = epilogue(u, vec_u, r, vec_r)
-    if out_half and not pool_groups and o_sign is None:
-        raise ops._lib.FgcnError("half-precision storage of the block's output needs the sign image (element count a multiple of 8)")
+    res = x if cfg.residual == "identity" else r
+    if pool_groups:
+        o, o_sign = ops.bn_act_pool(u, vec_u, res, vec_r, pool_groups)
+    else:
+        o, o_sign = ops.bn_act(u, vec_u, res, vec_r, relu=True, sign_mask=True, out_bf16=pl.o_bf16)
     S.update(u=u, vec_u=vec_u, r=r, vec_r=vec_r, o=None if pool_groups else o, o_sign=o_sign)
     return o, S
 
@@ -656,58 +545,27 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     ``d_o`` is the gradient of that, (groups, cout); it is consumed as a per-group row (divided by the group's rows) where the kernels
     take one (POOL_BACKWARD_ROWS) and expanded to the output's shape otherwise."""
     x = S["x"]
+    pl: BlockPlan = S["plan"]    # the forward's plan: this function evaluates no route predicate of its own
     B, T, V, cx = x.shape
     cout, ic, s = cfg.cout, cfg.ic, cfg.stride
     cin, cin_true = cx, cfg.cin  # kernels work on the padded channel count; gradients are cut back to cin_true
     Tp = d_o.shape[1] if pool is None else pool[1][1]
     dev = x.device
-    o_ = ops.paths()             # this context's kernel-form options (the forward's context: ops.context_bound)
-    half = bool(S.get("half")) and train     # G was stored as bfloat16: dU (the gradient of the temporal conv's output) is too
     new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
     G: Dict[str, torch.Tensor] = {}
     d_o = d_o.contiguous()
     o_numel = B * Tp * V * cout
     kt = P["tcn1.conv.weight"].shape[2]
-    wide = ops.wide_graph(V)     # more than 32 joints: the wide joint kernels and the row-GEMM temporal conv (block_forward)
-    ha = half_activations_on(train, o_, V)
-    x16 = x.dtype == torch.bfloat16          # the block's input arrived as bfloat16 (paths.half_activations): its gradient leaves as bfloat16
-    # Identity shortcuts (cin == cout, stride 1: both the graph convolution's `y += x` and the block residual) send the ReLU-gated
-    # incoming gradients straight to dx.  Instead of the BatchNorm-backward kernels writing / read-modify-writing dx, the kernel
-    # that forms the spatial term of dx (joint_dagg) adds both from their sign images: two activation passes less per block.
-    small = lambda width: B * max(T, Tp) * V * width * 4 < 0x7FFF0000      # noqa: E731  the tile kernels address with 32-bit byte offsets
-    tile_ok = (o_.spatial_bwd_tile and cin >= o_.spatial_bwd_tile_min_cin and "d_t_b3" in W and ops.spatial_bwd_tile_available(V, cin, cout)
-               and (ops.get_math_mode() in ("bf16x3", "bf16") or o_.spatial_bwd_tile_f16x2) and small(max(cin, cout)))
-    gate_in_dagg = ((o_.gated_shortcuts_tile if tile_ok else o_.gated_shortcuts) and o_.fused_dagg and not wide and not cfg.has_down and cfg.residual == "identity"
-                    and cx == cfg.cin and cout % 8 == 0 and S["o_sign"] is not None and S["g_sign"] is not None
-                    and o_numel * 4 < 0x7FFF0000)
-    # -- paths.half_activations: which gradients are bfloat16 tensors --------------------------------------------------------------------
-    # dG (written by the temporal data gradient's halo kernel from a bfloat16 dU; not when that kernel's epilogue carries the BatchNorm sums)
-    fuse_sums = (o_.get("bn_sums_in_dgrad", ops.get_math_mode()) and cout <= o_.bn_sums_max_c and train and s == 1 and not cfg.has_down and S["g_sign"] is not None
-                 and "t_t4" in W and ops.tconv_halo_bn_sums() and not wide)
-    dg16 = bool(ha and half and kt > 1 and temporal_dgrad_records_amax(W, kt, s, V) and not fuse_sums and S["g_sign"] is not None)     # (narrowed below)
-    wgrad_tile = (o_.spatial_wgrad_tile and x.shape[3] == cin and ops.spatial_wgrad_tile_available(V, cin, cout) and small(max(cin, cout))
-                  and (ops.get_math_mode() in ("bf16x3", "bf16") or o_.spatial_wgrad_tile_f16x2))
-    half_dy = bool(train and ops.get_math_mode() == "bf16" and o_.get("half_storage", "bf16") and wgrad_tile and tile_ok and x.shape[3] == cin
-                   and S["g_sign"] is not None)
-    emb_tile_bwd = (not cfg.static_adjacency) and emb_bwd_tile_ok(W, cfg, B, T, V, cx, o_) and x.shape[3] == cin
-    # dx itself: every writer of dx must have the bfloat16 form -- the fused spatial backward first (with both gated shortcuts, or none to
-    # add), then the embedding tile kernel; a residual / down conv or an ungated shortcut writes float32, and the block converts at the end
-    dx16 = bool(x16 and ha and tile_ok and x.shape[3] == cin and half_dy and not cfg.has_down and cfg.residual != "conv"
-                and (cfg.residual == "none" or gate_in_dagg)
-                and (cfg.static_adjacency or (emb_tile_bwd and S["emb"] is not None and S["emb"].dtype == torch.bfloat16))
-                and (not gate_in_dagg or (dg16 and (d_o.dtype == torch.bfloat16 or (pool is not None and o_.pool_backward_rows)))))
-    dg16 = dg16 and (dx16 or not gate_in_dagg)       # (a gated addend has dx's storage type: the fused backward adds it)
+    # what the plan predicted of this call (the sign images exist where the element counts say so; train / pool are the forward's)
+    seen = (train, pool[0] if pool is not None else 0, S["o_sign"] is not None, S["g_sign"] is not None)
+    if seen != (pl.train, pl.pool_groups, pl.o_sign, pl.g_sign):
+        raise ops._lib.FgcnError(f"block backward: (train, pool groups, o_sign, g_sign) = {seen} contradicts the forward's plan: {pl}")
+    half, half_dy, hs, x16 = pl.g_bf16, pl.dy_bf16, pl.dshortcuts_bf16, pl.x_bf16      # (g_bf16: dU is bfloat16 as G is)
+    gate_in_dagg, fuse_sums = pl.gate_in_dagg, pl.bn_sums_in_dgrad
+    # run-time refinement, the one thing only the backward sees: the storage type of the incoming gradient (BlockPlan.refine_dx)
+    dx16, dg16 = pl.refine_dx(d_o.dtype == torch.bfloat16)
     x_h = x                                  # the input as it arrived: the kernels with a typed form take the bfloat16 x beside a bfloat16 dy / emb / gradient
-    # the shortcut branches' gradients (dd / dr) as bfloat16 and their kernels on the bfloat16 x: the typed row GEMMs / 1x1 weight gradient
-    hs = bool(x16 and ha and o_.half_shortcuts and cin % 32 == 0 and cout % 8 == 0)
-    _xf: List[torch.Tensor] = []
-
-    def xf() -> torch.Tensor:                # x for a kernel without a bfloat16-input form (converted once, on first use)
-        if not x16:
-            return x_h
-        if not _xf:
-            _xf.append(x_h.float())
-        return _xf[0]
+    xf = _f32_once(x)
     del x                                    # (every use below names the form it needs: x_h, or xf())
     dx = torch.empty((B, T, V, cx), device=dev, dtype=torch.bfloat16) if dx16 else new(B, T, V, cx)
     dx_live = False      # becomes True once dx holds a valid partial sum
@@ -718,24 +576,21 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
         groups = pool[0]
         rows = o_numel // cout // groups
         d_o = d_o / rows                             # (groups, cout): every row of a group receives the group's gradient / rows
-        if o_.pool_backward_rows and (not gate_in_dagg or (tile_ok and x_h.shape[3] == cin)):
+        if pl.pool_rows:
             grp_rows, grp_samples = rows, B // groups        # the BatchNorm-backward passes and the gated addend read the group's row
         else:
             d_o = d_o.unsqueeze(1).expand(groups, rows, cout).contiguous().view(B, Tp, V, cout)
     bias_grad = _BiasGrads(cfg, dev, train, zeros)
 
     # -- O = relu(BN(u) + res) ---------------------------------------------------------------------------------------------
-    if cfg.residual == "none":
-        du, _, sums = ops.bn_act_bwd(d_o, S["o"], S["u"], S["vec_u"], None, None, res_mode=0, train=train,
-                                     sign_mask=S["o_sign"], grp_rows=grp_rows, da_bf16=half)
-    elif cfg.residual == "identity" and gate_in_dagg:
-        du, _, sums = ops.bn_act_bwd(d_o, S["o"], S["u"], S["vec_u"], x_h, None, res_mode=1, train=train, need_db=False,
-                                     sign_mask=S["o_sign"], grp_rows=grp_rows, da_bf16=half)
-        gated.append((d_o, S["o_sign"], grp_samples) if grp_samples else (as_extra(d_o), S["o_sign"]))   # dx += d_o * [o > 0], added by joint_dagg below
-    elif cfg.residual == "identity":
-        du, _, sums = ops.bn_act_bwd(d_o, S["o"], S["u"], S["vec_u"], x_h, None, res_mode=1, train=train, db=dx,
-                                     sign_mask=S["o_sign"], grp_rows=grp_rows, da_bf16=half)
-        dx_live = True
+    if cfg.residual != "conv":
+        ident = cfg.residual == "identity"       # its gated gradient goes to dx: written here, or (gate_in_dagg) added by the spatial backward below
+        du, _, sums = ops.bn_act_bwd(d_o, S["o"], S["u"], S["vec_u"], x_h if ident else None, None, res_mode=int(ident), train=train,
+                                     need_db=not gate_in_dagg, db=dx if ident and not gate_in_dagg else None, sign_mask=S["o_sign"],
+                                     grp_rows=grp_rows, da_bf16=half)
+        if gate_in_dagg:
+            gated.append((d_o, S["o_sign"], grp_samples) if grp_samples else (as_extra(d_o), S["o_sign"]))   # dx += d_o * [o > 0]
+        dx_live = ident and not gate_in_dagg
     else:
         du, dr, sums = ops.bn_act_bwd(d_o, S["o"], S["u"], S["vec_u"], S["r"], S["vec_r"], res_mode=2, train=train,
                                       sign_mask=S["o_sign"], grp_rows=grp_rows, da_bf16=half, db_bf16=hs)
@@ -749,25 +604,20 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
 
     # -- temporal conv -------------------------------------------------------------------------------------------------------
     dg = torch.empty((B, T, V, cout), device=dev, dtype=torch.bfloat16) if dg16 else new(B, T, V, cout)
-    # identity blocks in the split-bf16 modes: the data-gradient kernel sums dg * [g > 0] and dg * [g > 0] * y_hat in its epilogue,
-    # so the BatchNorm backward of the graph convolution below needs no reduction pass of its own over dg and y (fuse_sums, above)
-    # math mode f16x2: the data-gradient kernels record the largest magnitudes of the tensors they stage (slot 0 = du, 1 = demb);
-    # with the forward's slots they are the operand scales of the weight gradients, which therefore follow those kernels
-    f16x2 = S.get("amax") is not None and ops.get_math_mode() == "f16x2"
-    bamax = torch.zeros(4, device=dev, dtype=torch.int32) if f16x2 else None
-    # (a slot only counts when the kernel that ran really recorded it: the row-GEMM fallbacks of odd paddings / T == 1 record
-    # nothing, and a weight gradient scaled by a zero-initialised slot would silently leave the f16 range)
-    du_amax = f16x2 and temporal_dgrad_records_amax(W, kt, s, V)
+    # plan.bn_sums_in_dgrad (identity blocks, split-bf16 modes): the data-gradient kernel sums dg * [g > 0] and dg * [g > 0] * y_hat in its
+    # epilogue, so the BatchNorm backward of the graph convolution below needs no reduction pass of its own over dg and y
+    # math mode f16x2: the data-gradient kernels record the largest magnitudes of the tensors they stage (slot 0 = du, 1 = demb); with the
+    # forward's slots they are the operand scales of the weight gradients, which therefore follow those kernels.  A slot only counts when
+    # the kernel that ran really recorded it (plan.*_amax): a weight gradient scaled by a zero-initialised slot would leave the f16 range
+    bamax = torch.zeros(4, device=dev, dtype=torch.int32) if pl.mode == "f16x2" else None
     g_partials = temporal_dgrad(du, dg, W, kt, s, bn_bwd=(S["y"], S["g_sign"], S["vec_y"]) if fuse_sums else None,
-                                amax_out=bamax[0:1] if du_amax else None)
+                                amax_out=bamax[0:1] if pl.du_amax else None, route=pl.temporal_dgrad)
     # weight gradients are reduced straight into the parameter's (out, in, kt, 1) layout: autograd takes them as they are
-    G["tcn1.conv.weight"] = ops.tconv_wgrad(S["g"], du, taps=kt, stride=s, conv_param=(1, cout), all_taps=False if wide else None,
-                                            amax=(S["amax"][1:2], bamax[0:1]) if du_amax and S.get("g_amax") else None)
+    G["tcn1.conv.weight"] = ops.tconv_wgrad(S["g"], du, taps=kt, stride=s, conv_param=(1, cout), all_taps=False if pl.wide else None,
+                                            amax=(S["amax"][1:2], bamax[0:1]) if pl.du_amax and pl.g_amax else None)
     G["tcn1.conv.bias"] = bias_grad(du, cout)
 
     # -- G = relu(BN(y) + down(x)) ---------------------------------------------------------------------------------------------
-    # math mode bf16, training, both consumers of dy on their tile kernels: dy is stored as bfloat16 (only their staging reads it;
-    # wgrad_tile / half_dy: above)
     if cfg.has_down:
         dy, dd, sums = ops.bn_act_bwd(dg, S["g"], S["y"], S["vec_y"], S["d"], S["vec_d"], res_mode=2, train=train,
                                       sign_mask=S["g_sign"], da_bf16=half_dy, db_bf16=hs)
@@ -776,37 +626,32 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
         dx_live = True
         G["gcn1.down.0.weight"] = ops.rows_wgrad(x_h if dd.dtype == torch.bfloat16 else xf(), dd, K=cin, N=cout, conv_param=(1, cin_true))
         G["gcn1.down.0.bias"] = bias_grad(dd, cout)
-    elif gate_in_dagg:
-        dy, _, sums = ops.bn_act_bwd(dg, S["g"], S["y"], S["vec_y"], x_h, None, res_mode=1, train=train, need_db=False,
-                                     sign_mask=S["g_sign"], partials=g_partials if fuse_sums else None, da_bf16=half_dy)
-        gated.append((as_extra(dg), S["g_sign"]))  # dx += dg * [g > 0]
     else:
-        dy, _, sums = ops.bn_act_bwd(dg, S["g"], S["y"], S["vec_y"], x_h, None, res_mode=1, train=train, db=dx,
-                                     db_accumulate=dx_live, sign_mask=S["g_sign"], partials=g_partials if fuse_sums else None, da_bf16=half_dy)
-        dx_live = True
+        dy, _, sums = ops.bn_act_bwd(dg, S["g"], S["y"], S["vec_y"], x_h, None, res_mode=1, train=train, need_db=not gate_in_dagg,
+                                     db=None if gate_in_dagg else dx, db_accumulate=dx_live, sign_mask=S["g_sign"],
+                                     partials=g_partials if fuse_sums else None, da_bf16=half_dy)
+        if gate_in_dagg:
+            gated.append((as_extra(dg), S["g_sign"]))  # dx += dg * [g > 0]  (dx is still empty: both shortcuts are gated)
+        dx_live = not gate_in_dagg
     G["gcn1.bn.weight"], G["gcn1.bn.bias"] = sums[1], sums[0]
 
     # -- conv_d and the joint aggregation ------------------------------------------------------------------------------------------
     a_hat = S["a_hat"]
     c3 = 3 * cin
-    bwd_tile = tile_ok and x_h.shape[3] == cin and (not gated or len(gated) == 2)
-    if half_dy and not bwd_tile:     # (cannot happen: the gated list holds none or both shortcuts by construction)
-        raise ops._lib.FgcnError("block backward: dy was stored as bfloat16 but the fused spatial backward is not taken")
-    dagg, dy_amax = None, False
-    if not bwd_tile:
+    dagg = None                  # (the gated list holds none or both shortcuts: gate_in_dagg needs an identity block without a down conv)
+    if pl.spatial_bwd != "tile":
         # dagg = dy . Wd first: in math mode f16x2 the row GEMM records max |dy| (slot 3), the operand scale of conv_d's weight gradient
         dagg = new(B, T, V, c3)
-        dy_amax = f16x2 and pw_routed(W, "d_t", dy, cout)
-        pw_gemm(dy, W, "d_t", dagg, K=cout, N=c3, amax_out=bamax[3:4] if dy_amax else None)
+        pw_gemm(dy, W, "d_t", dagg, K=cout, N=c3, amax_out=bamax[3:4] if pl.dy_amax else None)
     # weight gradient of conv_d: agg is recomputed (cheaper than keeping 3 activations per block) and contracted with dy
-    if wgrad_tile:
+    if pl.spatial_wgrad == "tile":
         gw = ops.spatial_wgrad_tile(x_h if dy.dtype == torch.bfloat16 else xf(), dy, a_hat, conv_param=(NUM_SUBSETS, cin_true))   # agg on chip, whole frame tiles
-    elif o_.fused_agg_wgrad and x_h.shape[3] == cin and cin >= 32 and not wide and cout <= o_.get("fused_agg_wgrad_max_cout", ops.get_math_mode()):
+    elif pl.spatial_wgrad == "fused":
         # agg = x . A^ is formed in registers and contracted with dy at once: never written
         gw = ops.spatial_wgrad(xf(), dy, a_hat, conv_param=(NUM_SUBSETS, cin_true))
     else:
         agg = new(B, T, V, c3)
-        agg_amax = mix_agg(xf(), agg, a_hat, cin, amax_out=bamax[2:3] if dy_amax else None)
+        agg_amax = mix_agg(xf(), agg, a_hat, cin, amax_out=bamax[2:3] if pl.dy_amax else None)
         gw = ops.rows_wgrad(agg, dy, K=3 * cin, N=cout, conv_param=(NUM_SUBSETS, cin_true),   # (3, cout, cin_true, 1, 1)
                             amax=(bamax[2:3], bamax[3:4]) if agg_amax else None)
         del agg
@@ -815,10 +660,10 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
         G[f"gcn1.conv_d.{k}.weight"] = gw[k]
         # three parameters, three buffers (the sum of the three biases is what the kernel adds: equal gradients)
         G[f"gcn1.conv_d.{k}.bias"] = bias_grad(dy, cout) if train else (dbias if k == 0 else dbias.clone())
-    if bwd_tile:
+    if pl.spatial_bwd == "tile":
         # dagg on chip: dx and dA^ in one launch (the bfloat16 x beside a bfloat16 dy, whatever dx is)
         part = ops.spatial_bwd_tile(dy, x_h if dy.dtype == torch.bfloat16 else xf(), a_hat, W["d_t_b3"], dx, accumulate=dx_live, gated=gated)
-    elif o_.fused_dagg and x_h.shape[3] == cin and not wide:
+    elif pl.spatial_bwd == "dagg":
         part = ops.joint_dagg(xf(), dagg, a_hat, dx, accumulate=dx_live, gated=gated)   # dx and dA^ from one pass over dagg
     else:
         mix_dx(dagg, dx, a_hat, cin, accumulate=dx_live)
@@ -832,9 +677,9 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     # -- attention embeddings -----------------------------------------------------------------------------------------------------
     if not cfg.static_adjacency:
         emb = S["emb"]
-        if emb_tile_bwd:
+        if pl.emb_bwd == "tile":
             # demb on chip: dx += demb . Wemb, then (a leaf) dWemb = demb^T . x and the bias gradient
-            if x16 and dx.dtype == torch.float32 and emb.dtype == torch.bfloat16 and dx_live:
+            if x16 and not dx16 and pl.emb_bf16:
                 # the last writer of this block's float32-accumulated dx hands it over as the bfloat16 tensor the bfloat16 input asks for
                 dx16_out = torch.empty(dx.shape, device=dev, dtype=torch.bfloat16)
                 ops.emb_dx_tile(emb, d_s, W["emb_t_b3"], dx16_out, ic=ic, accumulate=True, dx_old=dx)
@@ -844,14 +689,11 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
             gw, gb = ops.emb_wgrad_tile(emb, x_h if emb.dtype == torch.bfloat16 else xf(), d_s, ic=ic)
             gw = gw.view(6 * ic, cin_true, 1, 1)
         else:
-            if emb.dtype != torch.float32:       # (cannot happen: the forward asked the same predicate before it chose the storage)
-                raise ops._lib.FgcnError("block backward: emb was stored as bfloat16 but the tile form of its backward is not taken")
             demb = new(B, T, V, 6 * ic)
             gb = mix_demb(emb, demb, d_s, ic)                                             # + column sums = bias gradient
-            demb_amax = f16x2 and S["x_amax"] and pw_routed(W, "emb_t", demb, 6 * ic)
-            pw_gemm(demb, W, "emb_t", dx, K=6 * ic, N=cx, accumulate=dx_live, amax_out=bamax[1:2] if demb_amax else None)
+            pw_gemm(demb, W, "emb_t", dx, K=6 * ic, N=cx, accumulate=dx_live, amax_out=bamax[1:2] if pl.demb_amax else None)
             gw = ops.rows_wgrad(xf(), demb, K=cin, N=6 * ic, conv_param=(1, cin_true),     # (6ic, cin_true, 1, 1)
-                                amax=(S["amax"][0:1], bamax[1:2]) if demb_amax else None)
+                                amax=(S["amax"][0:1], bamax[1:2]) if pl.demb_amax else None)
         for k in range(NUM_SUBSETS):
             for j, grp in enumerate(("conv_a", "conv_b")):
                 lo = (2 * k + j) * ic

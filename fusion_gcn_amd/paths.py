@@ -8,7 +8,7 @@ settings", include/fgcn.h) stopped at ops.py.  They now live in a ``PathOptions`
         ctx.paths.emb_tile = False                # this model's blocks run the unfused embedding chain
         out = model(x); out.sum().backward()      # (the backward runs in the forward's context, wherever autograd runs it)
 
-``block.py`` reads ``ops.current_context().paths`` once per block call.  The process-wide default context takes its initial values
+``block.block_forward`` reads ``ops.paths()`` once per block call and plans the block from it (routes.plan_block).  The process-wide default context takes its initial values
 from ONE environment variable, ``FGCN_PATHS="name=value,name=value"`` (the same-call A/B scripts under tools/ set it per child
 process); nothing else in the package reads the environment for a path decision.
 
