@@ -182,6 +182,7 @@ SIGNATURES = {
     "fgcn_spatial_bwd_tile_segments": (_I, [_I, _I, _I]),
     "fgcn_spatial_bwd_tile_available": (_I, [_I, _I, _I]),
     "fgcn_transpose": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "fgcn_graph_spmm": (_I, [_P] * 8 + [_I] * 8 + [_P]),
     "fgcn_row_softmax_fwd": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _F, _P]),
     "fgcn_row_softmax_bwd": (_I, [_P, _P, _P, _LL, _I, _I, _F, _P]),
     "fgcn_tmaxpool3_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -11,6 +11,11 @@ points plus a transpose (include/fgcn.h):
     (Vp x Vp) weight by the same row GEMM (``B*O`` rows), then transposed back;
   * residual (identity, or Conv1d + BatchNorm1d with batch statistics from the GEMM epilogue) + ReLU = ``fgcn_bn_act``.
 
+With ``sparse=True`` (the reference's kwarg) the adjacency product is a gather instead (``fgcn_graph_spmm``): the
+static adjacency has 8 .. 30 non-zeros per row, its CSR form is built once from the dense buffer, the support stays node-major (no
+transpose, no padding) and the residual + ReLU + sign image are the gather's epilogue; the data gradient is the same kernel over adj^T's
+CSR form.  Parameters, buffers and state-dict keys are those of the dense route.
+
 ``AGCNGraphConvolution`` (:56-113: per-sample V x V attention) reuses the same pieces with per-sample matrices as the GEMM
 weight and a row softmax on the transposed scores (``fgcn_row_softmax_*``); see ``_AgcnConv1dFunction``.
 """
@@ -75,8 +80,7 @@ class _GraphConv1dFunction(torch.autograd.Function):
         B, V, Fp = x.shape
         O, Fin = weight.shape[0], weight.shape[1]
         dev = x.device
-        A = mod._adjacency_forms()
-        Vp = A["Vp"]
+        sparse = mod.takes_sparse_route()
         with torch.no_grad():
             w = torch.zeros((1, Fp, O), device=dev, dtype=torch.float32)
             w[0, :Fin] = weight.view(O, Fin).t()
@@ -85,17 +89,17 @@ class _GraphConv1dFunction(torch.autograd.Function):
             W["w_s3"] = _split_form(mod, "w", w)        # split form of the current products (bf16x3 / f16x2)
         support = torch.empty((B, V, O), device=dev, dtype=torch.float32)
         pw_gemm(_rows4(x), W, "w", _rows4(support), K=Fp, N=O, bias=bias)
-        sup_fm = ops.transpose(support, Vp)                                   # (B, O, Vp), zero padding columns
-        out_fm = torch.empty((B, O, Vp), device=dev, dtype=torch.float32)
-        pw_gemm(_rows4(sup_fm), A, "adjT", _rows4(out_fm), K=Vp, N=Vp)
-        main = ops.transpose_into(out_fm, V)                                  # (B, V, O)
-        vec_id = _identity_vec(O, dev)
+        main = None
+        if not sparse:
+            A = mod._adjacency_forms()
+            Vp = A["Vp"]
+            sup_fm = ops.transpose(support, Vp)                               # (B, O, Vp), zero padding columns
+            out_fm = torch.empty((B, O, Vp), device=dev, dtype=torch.float32)
+            pw_gemm(_rows4(sup_fm), A, "adjT", _rows4(out_fm), K=Vp, N=Vp)
+            main = ops.transpose_into(out_fm, V)                              # (B, V, O)
+            vec_id = _identity_vec(O, dev)
         r = vec_r = None
-        if mod.res_kind == "none":
-            out, mask = ops.bn_act(main, vec_id, None, None, relu=True, sign_mask=True)
-        elif mod.res_kind == "identity":
-            out, mask = ops.bn_act(main, vec_id, x, None, relu=True, sign_mask=True)
-        else:
+        if mod.res_kind == "conv":
             with torch.no_grad():
                 wr = torch.zeros((1, Fp, O), device=dev, dtype=torch.float32)
                 wr[0, :Fin] = res_w.view(O, Fin).t()
@@ -109,7 +113,19 @@ class _GraphConv1dFunction(torch.autograd.Function):
                      else ops.bn_eval_coeffs(res_g, res_beta, bn.running_mean, bn.running_var))
             if train:
                 bn.num_batches_tracked += 1
+        if sparse:
+            # the aggregation as a gather over adj's CSR form with the residual and the ReLU in its epilogue: no transposes, no bn_act pass
+            # (mask None when O % 8 != 0: the backward then gates from `out`)
+            csr = mod._csr_forms()["adj"]
+            res = {"none": None, "identity": x, "conv": r}[mod.res_kind]
+            out, mask = ops.graph_spmm(support, csr, relu=True, b=res, vec_b=vec_r, sign_mask=True)
+        elif mod.res_kind == "none":
+            out, mask = ops.bn_act(main, vec_id, None, None, relu=True, sign_mask=True)
+        elif mod.res_kind == "identity":
+            out, mask = ops.bn_act(main, vec_id, x, None, relu=True, sign_mask=True)
+        else:
             out, mask = ops.bn_act(r, vec_r, main, None, relu=True, sign_mask=True)   # relu(BN(r) + main)
+        ctx.sparse = sparse
         ctx.mod, ctx.train, ctx.W = mod, train, W
         ctx.save_for_backward(x, out, mask, r, vec_r, weight, res_w)
         return out
@@ -121,8 +137,6 @@ class _GraphConv1dFunction(torch.autograd.Function):
         B, V, Fp = x.shape
         O, Fin = weight.shape[0], weight.shape[1]
         dev = x.device
-        A = mod._adjacency_forms()
-        Vp = A["Vp"]
         d_out = d_out.contiguous()
         vec_id = _identity_vec(O, dev)
         dx = None
@@ -144,11 +158,16 @@ class _GraphConv1dFunction(torch.autograd.Function):
             if "wr_s3" in W and O % 32 == 0:
                 Wt["wr_t_s3"] = _split_form(mod, "wr_t", Wt["wr_t"])
             pw_gemm(_rows4(dr), Wt, "wr_t", _rows4(dx), K=O, N=Fp)
-        # main path: d_support = d_main . adj  (feature-major), then the conv's data and weight gradients
-        dm_fm = ops.transpose(d_main, Vp)
-        ds_fm = torch.empty((B, O, Vp), device=dev, dtype=torch.float32)
-        pw_gemm(_rows4(dm_fm), A, "adj", _rows4(ds_fm), K=Vp, N=Vp)
-        d_support = ops.transpose_into(ds_fm, V)
+        # main path: d_support = d_main . adj  (feature-major; sparse route: node-major gather), then the conv's data and weight gradients
+        if ctx.sparse:
+            d_support = ops.graph_spmm(d_main, mod._csr_forms()["adjT"])      # a gather over adj^T's rows: no atomics, no transposes
+        else:
+            A = mod._adjacency_forms()
+            Vp = A["Vp"]
+            dm_fm = ops.transpose(d_main, Vp)
+            ds_fm = torch.empty((B, O, Vp), device=dev, dtype=torch.float32)
+            pw_gemm(_rows4(dm_fm), A, "adj", _rows4(ds_fm), K=Vp, N=Vp)
+            d_support = ops.transpose_into(ds_fm, V)
         g_w = ops.rows_wgrad(_rows4(x), _rows4(d_support), K=Fp, N=O, conv_param=(1, Fin)).view(O, Fin, 1)
         g_b = ops.col_sum(_rows4(d_support), O)
         if ctx.needs_input_grad[0]:
@@ -172,7 +191,9 @@ class STGCNGraphConvolution(nn.Module):
                  **kwargs):
         super().__init__()
         dropout = kwargs.get("dropout", 0.)
-        self.sparse = kwargs.get("sparse", False)      # the reference's sparse path computes the same product
+        # the reference's sparse path (graph_convolution.py:36-43) computes the same product; here it selects the CSR gather route
+        # (ops.graph_spmm) instead of the padded V x V GEMM between two transposes.  The buffer below stays dense either way.
+        self.sparse = bool(kwargs.get("sparse", False))
         if out_features % 4:
             raise ValueError(f"HIP graph convolution needs out_features % 4 == 0 (got {out_features})")
         if not bias:
@@ -193,6 +214,28 @@ class STGCNGraphConvolution(nn.Module):
             self.res_kind = "conv"
             self.residual = nn.Sequential(nn.Conv1d(in_features, out_features, 1), nn.BatchNorm1d(out_features))
         self._adj_cache = None
+        self._csr_cache = None
+
+    def takes_sparse_route(self) -> bool:
+        """sparse=True, or PathOptions.graph_spmm_auto with an adjacency below its density threshold (same-call A/B of a dense-configured model)."""
+        if self.sparse:
+            return True
+        po = ops.paths()
+        if not po.graph_spmm_auto:
+            return False
+        return self._csr_forms()["nnz"] * 1_000_000 < po.graph_spmm_auto_density_ppm * self.adj.shape[0] * self.adj.shape[1]
+
+    def _csr_forms(self) -> Dict[str, object]:
+        """CSR forms of adj (forward) and adj^T (data gradient) on adj's device, built once on the host from the dense buffer
+        (ops.csr_from_dense); cached per (device, adj.data_ptr()) like the dense forms: a moved or replaced buffer rebuilds them (the
+        build reads the buffer on the host, so it cannot happen inside a HIP-graph capture: GraphStep's eager warm-up step does it)."""
+        key = (self.adj.device, self.adj.data_ptr())
+        if self._csr_cache is None or self._csr_cache[0] != key:
+            with torch.no_grad():
+                fwd = ops.csr_from_dense(self.adj)
+                forms = {"adj": fwd, "adjT": ops.csr_from_dense(self.adj, transpose=True), "nnz": int(fwd[1].numel())}
+            self._csr_cache = (key, forms)
+        return self._csr_cache[1]
 
     def _adjacency_forms(self) -> Dict[str, object]:
         """adj^T (forward) and adj (data gradient) as shared (1, Vp, Vp) row-GEMM weights, Vp = V padded to 64 with zeros, and
@@ -212,8 +255,8 @@ class STGCNGraphConvolution(nn.Module):
         return self._adj_cache[1]
 
     def recording_pins(self) -> list:
-        """GraphStep hook: the padded adjacency forms a recording made now reads."""
-        return [] if self._adj_cache is None else [self._adj_cache[1]]
+        """GraphStep hook: the padded adjacency forms and the CSR forms a recording made now reads."""
+        return [c[1] for c in (self._adj_cache, self._csr_cache) if c is not None]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         res = self.residual

@@ -34,7 +34,8 @@ def build_imu_graph_adjacency(data_shape: tuple, num_signals: int = 0, gc_model:
                               normalization="row", temporal_back_connections: int = 1,
                               inter_signal_back_connections: bool = False, build_graph_fn=build_imu_graph):
     """``agcn``: the (3, V, V) partition-strategy stack; otherwise the self-connected, normalised (V, V) adjacency as a float32
-    tensor (the reference's sparse variant holds the same matrix; kept dense here)."""
+    tensor.  ``sparse=True`` returns the SAME dense tensor (the reference's sparse variant holds the same matrix): the module buffer and
+    the state dict stay dense, and ``STGCNGraphConvolution(sparse=True)`` builds its CSR forms from that buffer (ops.csr_from_dense)."""
     graph = build_graph_fn(data_shape, num_signals, temporal_back_connections, inter_signal_back_connections)
     if gc_model == "agcn":
         return GraphPartitionStrategy().get_adjacency_matrix_array(graph)

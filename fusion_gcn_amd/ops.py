@@ -1666,6 +1666,79 @@ def transpose_into(x: torch.Tensor, rows: int) -> torch.Tensor:
     return out
 
 
+CSR_PAD = 8      # entries kept readable behind col / val: fgcn_graph_spmm fetches a row's entries in groups of eight (include/fgcn.h)
+
+
+def csr_from_dense(adj: torch.Tensor, transpose: bool = False, device=None):
+    """(row_ptr (V + 1) int32, col (nnz) int32, val (nnz) float32) of the (V, V) matrix ``adj`` -- of ``adj.T`` with ``transpose`` --
+    built on the host: columns ascending inside a row, explicit zeros dropped, then moved to ``device`` (default: ``adj``'s).  ``col`` and
+    ``val`` are views of the first nnz entries of buffers that hold CSR_PAD more (zeros): the readable padding fgcn_graph_spmm asks for."""
+    if adj.dim() != 2:
+        raise ValueError(f"csr_from_dense: expected a matrix, got shape {tuple(adj.shape)}")
+    device = adj.device if device is None else torch.device(device)
+    a = adj.detach().to("cpu", torch.float32)
+    if transpose:
+        a = a.t()
+    a = a.contiguous()
+    nz = a != 0
+    row_ptr = torch.zeros(a.shape[0] + 1, dtype=torch.int32)
+    row_ptr[1:] = torch.cumsum(nz.sum(1), 0).to(torch.int32)
+    idx = nz.nonzero()                                   # row-major order: rows ascending, columns ascending inside a row
+    nnz = idx.shape[0]
+    col = torch.zeros(nnz + CSR_PAD, dtype=torch.int32)
+    val = torch.zeros(nnz + CSR_PAD, dtype=torch.float32)
+    col[:nnz] = idx[:, 1].to(torch.int32)
+    val[:nnz] = a[nz]
+    return row_ptr.to(device), col.to(device)[:nnz], val.to(device)[:nnz]
+
+
+def _csr_padded(t: torch.Tensor) -> bool:
+    return t.untyped_storage().nbytes() >= (t.storage_offset() + t.numel() + CSR_PAD - 1) * t.element_size()
+
+
+def graph_spmm(x: torch.Tensor, csr, out: Optional[torch.Tensor] = None, relu: bool = False, b: Optional[torch.Tensor] = None,
+               vec_b: Optional[torch.Tensor] = None, sign_mask: bool = False):
+    """out[b, v, :] = act(sum_j val[j] * x[b, col[j], :] + [b | b * scale_b + shift_b]) over row v's entries of ``csr`` = (row_ptr, col,
+    val) from ``csr_from_dense`` (fgcn_graph_spmm): the adjacency product of the static-graph IMU convolution as a gather, float32 FMAs in
+    ascending column order in every math mode.  x: (B, V, C) float32 whose rows may be wider than C (a channel window: last stride 1,
+    x.stride(0) == V * x.stride(1)); b like out; vec_b: the (4, C) vector of ``bn_finalize``.  ``sign_mask``: -> (out, mask), mask = the
+    bit image [out > 0] in ``bn_act``'s format (None when C % 8 != 0: the backward then gates from ``out``)."""
+    ensure_device()
+    row_ptr, col, val = csr
+    if x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32 or x.stride(2) != 1 or (x.shape[0] > 1 and x.stride(0) != x.shape[1] * x.stride(1)):
+        raise _lib.FgcnError(f"graph_spmm.x: expected a float32 CUDA (B, V, C) tensor with uniform row stride, got {x.dtype} {x.device} "
+                             f"shape={tuple(x.shape)} strides={x.stride()}")
+    B, V, C = x.shape
+    for t, name, dt in ((row_ptr, "row_ptr", torch.int32), (col, "col", torch.int32), (val, "val", torch.float32)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise _lib.FgcnError(f"graph_spmm.{name}: expected a contiguous {dt} CUDA tensor, got {t.dtype} {t.device}")
+    if row_ptr.numel() != V + 1 or col.numel() != val.numel():
+        raise _lib.FgcnError(f"graph_spmm: CSR of {row_ptr.numel() - 1} rows, {col.numel()} / {val.numel()} entries for V = {V}")
+    if not (_csr_padded(col) and _csr_padded(val)):
+        raise _lib.FgcnError(f"graph_spmm: col / val need {CSR_PAD - 1} readable entries behind the last one (build them with ops.csr_from_dense)")
+    if out is None:
+        out = torch.empty((B, V, C), device=x.device, dtype=torch.float32)
+    _chk(out, "graph_spmm.out")
+    if tuple(out.shape) != (B, V, C):
+        raise _lib.FgcnError(f"graph_spmm.out: shape {tuple(out.shape)} != {(B, V, C)}")
+    res_mode = 0 if b is None else (1 if vec_b is None else 2)
+    if b is not None:
+        _chk(b, "graph_spmm.b")
+        if tuple(b.shape) != (B, V, C):
+            raise _lib.FgcnError(f"graph_spmm: residual shape {tuple(b.shape)} != {(B, V, C)}")
+    if vec_b is not None:
+        _chk(vec_b, "graph_spmm.vec_b")
+        if b is None or tuple(vec_b.shape) != (4, C):
+            raise _lib.FgcnError(f"graph_spmm.vec_b: a (4, {C}) coefficient vector of a residual operand, got {tuple(vec_b.shape)}")
+    mask = None
+    if sign_mask and C % 8 == 0:
+        mask = torch.empty(B * V * C // 8, device=x.device, dtype=torch.uint8)
+    base = lambda t: t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size()      # noqa: E731  (an empty view's data_ptr() is 0)
+    check(_lib.load().fgcn_graph_spmm(x.data_ptr(), row_ptr.data_ptr(), base(col), base(val), _p(b), _p(vec_b), _p(out), _p(mask),
+                                      B, V, C, x.stride(1), C, C, res_mode, int(relu), _stream()), "fgcn_graph_spmm")
+    return (out, mask) if sign_mask else out
+
+
 def row_softmax_fwd(st: torch.Tensor, adj_t: torch.Tensor, V: int, scale: float):
     """st (B, K, V, ld) transposed scores -> (c, a): c = softmax over the last axis of scale*st[..., :V], a = c + adj_t (K, V, ld);
     padding columns zero."""

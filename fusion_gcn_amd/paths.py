@@ -108,6 +108,14 @@ class PathOptions:
     # 0.29-0.35 vs 0.43-0.67 ms in every mode; the step f32 7.18 / 6.90 vs 7.26 ms, bf16x3 5.40 / 5.35 vs 5.45, f16x2 4.76 / 5.10 vs 5.15
     # (skeleton + rgb; skeleton + IMU + rgb alike), but bf16 3.86 / 3.86 vs 3.55 ms (3.91 / 3.91 vs 3.62): off in bf16
     patch_input_fused: Dict[str, bool] = field(default_factory=lambda: {"f32": True, "bf16": False, "bf16x3": True, "f16x2": True})
+    # -- static-adjacency IMU graph convolution (models/mmargcn/graph_convolution.py, STGCNGraphConvolution): the sparse aggregation route
+    # (ops.graph_spmm: CSR gather, no transposes, no padded V x V GEMM) for a layer that was NOT built with sparse=True, when its adjacency's
+    # density (non-zeros / V^2) is below graph_spmm_auto_density_ppm millionths -- the config's graph has 0.41 %, its densest form 1.5 %; 5 %
+    # keeps every graph build_imu_graph_adjacency can make at V >= 48 on the route and a dense matrix off it.  A same-call A/B switch for
+    # FGCN_PATHS and tools/imu_gcn_bench.py --ab; a layer built with sparse=True takes the route whatever this says.  Measurement
+    # (profiles/r10_imu_gcn_sparse_ab.json) -- off by default all the same: flipping it is a change of its own
+    graph_spmm_auto: bool = False
+    graph_spmm_auto_density_ppm: int = 50_000
 
     def copy(self) -> "PathOptions":
         return dataclasses.replace(self, **{f.name: dict(getattr(self, f.name)) for f in dataclasses.fields(self)

@@ -738,6 +738,23 @@ int fgcn_emb_tile_available(int V, int ic, int Cx);
  * over feature-major rows with the V x V adjacency as the shared weight, residual + ReLU = fgcn_bn_act. */
 int fgcn_transpose(const float* in, float* out, int B, int R, int C, int ld_in, int ld_out, void* stream);
 
+/* Sparse form of that adjacency product (the reference's `sparse: true`, graph_convolution.py:36-43): the IMU graph's adjacency has
+ * 8 .. 30 non-zeros in a row of ~2000, so `support . adj^T` is a gather of a few node rows -- no transpose, no padding, no matrix pipe:
+ *     out[b][v][c] = act( sum_{j in [row_ptr[v], row_ptr[v+1])} val[j] * in[b][col[j]][c]  +  r ),   r = 0 | b | b*scale_b + shift_b
+ *   in / b / out: float32 node-major (B, V, C) with row strides ld_in / ld_b / ld_out >= C (multiples of 4, 16-byte aligned bases),
+ *   C % 4 == 0.  The matrix is CSR in device memory: row_ptr int[V + 1], col int[nnz], val float[nnz], columns ascending inside a row;
+ *   col and val must be followed by SEVEN more readable entries (the kernel fetches entries in groups of eight and ignores those
+ *   past a row's end).  Column indices are not checked on the device.
+ *   res_mode / vec_b / relu / sign_mask: the epilogue of fgcn_bn_act (0 none, 1 identity, 2 `b*scale + shift` from vec_b's float[4][C]);
+ *   sign_mask (may be NULL; needs C % 8 == 0): bit e%8 of byte e/8 = [out[e] > 0], e = (b*V + v)*C + c -- fgcn_bn_act's image.
+ *   With the CSR form of adj this is the layer's forward (no separate fgcn_bn_act pass), with that of adj^T and no epilogue its data
+ *   gradient d_support = d_main . adj: both gathers, no atomics.  float32 FMAs in ascending column order in EVERY math mode: launches
+ *   agree bit for bit and the math mode changes nothing.  FGCN_E_BADARG: C % 4 != 0, a null CSR array, B*V >= 2^29 rows or a tensor
+ *   of 2^31 bytes or more (the kernel's 32-bit row math). */
+int fgcn_graph_spmm(const float* in, const int* row_ptr, const int* col, const float* val, const float* b, const float* vec_b,
+                    float* out, unsigned char* sign_mask, int B, int V, int C, int ld_in, int ld_b, int ld_out, int res_mode,
+                    int relu, void* stream);
+
 /* Softmax of AGCNGraphConvolution's attention (graph_convolution.py:95-100: softmax over dim -2 of theta^T phi / ic, then
  * + adj[i]) on the TRANSPOSED scores st[row = (b, k, w)][v], so that it runs along the contiguous axis (V up to thousands):
  *     c = softmax_v(scale * st[row][0:V]);   a = c + adj_t[row % KV][0:V]   (adj_t: float[K*V][ld] = (adj_a + adj_b)^T per subset)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Step time of the IMU graph model of config/utd-mhad/imu/imu_gcn_v1_stgcn.yaml (mode imu_gcn, gc_model stgcn, node_per_value,
 inner_feature_dim 512, 10 layers, batch 8; UTD-MHAD inertial sequences resampled to 326 x 6 -> 1956 nodes): fwd+bwd on one
-MI355X in the math modes, with the algorithmic FLOPs, next to the float32 CPU oracle on a 2-sample slice."""
+MI355X in the math modes, with the algorithmic FLOPs, next to the float32 CPU oracle on a 2-sample slice.
+``--sparse``: the model is built with ``sparse=True`` (the CSR gather route of STGCNGraphConvolution, ops.graph_spmm).  ``--ab``: dense /
+sparse / dense in one process and one call, per math mode (same weights, same batch): the yardstick of the sparse route."""
 import argparse
 import json
 import os
@@ -27,26 +29,27 @@ def main():
     ap.add_argument("--late", action="store_true",
                     help="instead: mode skeleton_imu_gcn_late_fusion as config/utd-mhad/skeleton+imu/late_fusion/*.yaml (skeleton "
                          "(1, 128, 20, 3) + inertial (326, 6), gc_model agcn, node_per_sensor, num_signals 2, batch 8)")
+    ap.add_argument("--sparse", action="store_true", help="build the model with sparse=True (adjacency products as CSR gathers)")
+    ap.add_argument("--ab", action="store_true", help="dense / sparse / dense in one process, per math mode")
+    ap.add_argument("--inter-signal", action="store_true", help="inter_signal_back_connections=True (the graph's densest form)")
     args = ap.parse_args()
     if args.late:
         return late(args)
+    if args.ab:
+        return ab(args)
     from fusion_gcn_amd import ops
-    from fusion_gcn_amd.models.mmargcn.mmargcn import Model
     dev = torch.device("cuda:0")
     shape, classes = (args.frames, 6), 27
     torch.manual_seed(1)
-    model = Model({"inertial": shape}, classes, None, mode="imu_gcn", gc_model="stgcn", graph_node_format="node_per_value",
-                  inner_feature_dim=args.width, num_layers=args.layers).to(dev).train()
+    model = _model(args, args.sparse).to(dev).train()
     x = torch.randn(args.batch, *shape, device=dev)
     y = torch.randint(0, classes, (args.batch,), device=dev)
     V = shape[0] * shape[1]
-    flops, f = 0.0, 1
-    for layer in model._model.gcn.layers:
-        o = layer.out_features
-        flops += 2.0 * args.batch * V * f * o * (2 if layer.res_kind == "conv" else 1) + 2.0 * args.batch * o * V * V
-        f = o
-    flops *= 3
+    flops = _flops(model, args.batch, V, args.sparse)
     out = {"nodes": V, "batch": args.batch, "algorithmic_gflop_per_step": round(flops / 1e9, 1)}
+    if args.sparse:
+        out["sparse"] = True
+        out["adjacency_nnz"] = _nnz(model)
     from steptime import time_step
     # dense matrix peaks (MI355X_MICROARCH.md) per arithmetic: exact f32 MFMA, bf16 / 6 products, f16 / 3 products, bf16
     peaks = {"f32": 157.3, "bf16x3": 2500.0 / 6, "f16x2": 2500.0 / 3, "bf16": 2500.0}
@@ -72,6 +75,58 @@ def main():
         O.loss_and_grads(xs, ys, sd)
         dt = time.perf_counter() - t0
         out["cpu_oracle"] = {"samples_per_s": round(2 / dt, 3), "threads": torch.get_num_threads(), "sample": "2 samples, 1 iteration"}
+    print(json.dumps(out))
+
+
+def _model(args, sparse: bool):
+    from fusion_gcn_amd.models.mmargcn.mmargcn import Model
+    kw = dict(sparse=True) if sparse else {}
+    if args.inter_signal:
+        kw["inter_signal_back_connections"] = True
+    return Model({"inertial": (args.frames, 6)}, 27, None, mode="imu_gcn", gc_model="stgcn", graph_node_format="node_per_value",
+                 inner_feature_dim=args.width, num_layers=args.layers, **kw)
+
+
+def _nnz(model) -> int:
+    return int((model._model.gcn.layers[0].adj != 0).sum())
+
+
+def _flops(model, batch: int, V: int, sparse: bool) -> float:
+    """Algorithmic FLOPs of fwd + bwd.  Dense: 3 x forward (the count this tool has always reported).  Sparse: the feature GEMMs 3 x, the
+    adjacency term 2 * B * O * nnz counted TWICE -- forward and data gradient; a static adjacency has no weight gradient."""
+    feat, adjt, f = 0.0, 0.0, 1
+    nnz = _nnz(model)
+    for layer in model._model.gcn.layers:
+        o = layer.out_features
+        feat += 2.0 * batch * V * f * o * (2 if layer.res_kind == "conv" else 1)
+        adjt += 2.0 * batch * o * (nnz if sparse else V * V)
+        f = o
+    return 3 * feat + (2 if sparse else 3) * adjt
+
+
+def ab(args):
+    """dense / sparse / dense, per math mode, in one process: two models with the same parameters and the same batch."""
+    from fusion_gcn_amd import ops
+    from steptime import time_step
+    dev = torch.device("cuda:0")
+    torch.manual_seed(1)
+    dense = _model(args, False).to(dev).train()
+    sparse = _model(args, True).to(dev).train()
+    sparse.load_state_dict(dense.state_dict())
+    x = torch.randn(args.batch, args.frames, 6, device=dev)
+    y = torch.randint(0, 27, (args.batch,), device=dev)
+    V = args.frames * 6
+    out = {"nodes": V, "batch": args.batch, "adjacency_nnz": _nnz(dense), "order": ["dense", "sparse", "dense"],
+           "algorithmic_gflop_per_step": {"dense": round(_flops(dense, args.batch, V, False) / 1e9, 1),
+                                          "sparse": round(_flops(sparse, args.batch, V, True) / 1e9, 1)}}
+    for mode in ("f32", "bf16x3", "f16x2", "bf16"):
+        runs = []
+        with ops.math_mode(mode):
+            for name, model in (("dense", dense), ("sparse", sparse), ("dense", dense)):
+                t = time_step(model, x, y, args.steps, graph=args.graph)
+                runs.append({"route": name, "eager_ms": t["eager"]["ms_per_step"], "loss": t["eager"]["loss"],
+                             **({"graph_ms": t["graph"]["ms_per_step"]} if args.graph else {})})
+        out[mode] = runs
     print(json.dumps(out))
 
 

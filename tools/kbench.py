@@ -3,7 +3,7 @@
 family with HIP events on torch's current stream and prints ms, TFLOP/s (algorithmic) and GB/s (algorithmic).
 Used to A/B kernel variants (fgcn_set_tuning) in one process on one device.
 
-    python tools/kbench.py [--b 128] [--reps 10] [--only gemm,wgrad,spatial,joint,elem] [--tune 5=1]
+    python tools/kbench.py [--b 128] [--reps 10] [--only gemm,wgrad,spatial,joint,elem,spmm] [--tune 5=1]
 """
 import argparse
 import os
@@ -349,6 +349,34 @@ def bench_elem(B, reps):
         report(f"col_sum T{T} C{c}", ms, 0, 4.0 * rows * c)
 
 
+def bench_spmm(B, reps):
+    """fgcn_graph_spmm at config/utd-mhad/imu/imu_gcn_v1_stgcn.yaml's shapes (batch 8 whatever --b says: the config's), the config's
+    adjacency and its densest form, next to fgcn_bn_act on the same tensors in the same call (the same bytes without the gather)."""
+    from fusion_gcn_amd.models.mmargcn.imu_feature_models import build_imu_graph_adjacency
+    B, Vn = 8, 326 * 6
+    for label, kw in (("config", {}), ("inter-signal", dict(inter_signal_back_connections=True))):
+        adj = build_imu_graph_adjacency((326, 6), 0, "stgcn", False, "column", 1, **kw).to(DEV)
+        csr, csr_t = ops.csr_from_dense(adj), ops.csr_from_dense(adj, transpose=True)
+        nnz = csr[1].numel()
+        print(f"-- graph_spmm, {label} adjacency: V = {Vn}, nnz = {nnz} ({nnz / Vn:.1f} per row)")
+        for c in (512, 1024, 2048, 4096):
+            x, b = rnd(B, Vn, c), rnd(B, Vn, c)
+            vec = torch.stack([torch.zeros(c), torch.ones(c), torch.ones(c), torch.zeros(c)]).to(DEV).contiguous()
+            out = torch.empty_like(x)
+            n = 4.0 * B * Vn * c
+            ms = timeit(lambda: ops.graph_spmm(x, csr_t, out=out), reps)
+            report(f"graph_spmm adj^T, no epilogue (data gradient) C{c}", ms, 2.0 * B * c * nnz, 2 * n)
+            ms = timeit(lambda: ops.graph_spmm(x, csr, out=out, relu=True, sign_mask=True), reps)
+            report(f"graph_spmm relu + sign bits C{c}", ms, 2.0 * B * c * nnz, (2 + 1 / 32) * n)
+            ms = timeit(lambda: ops.graph_spmm(x, csr, out=out, relu=True, b=b, sign_mask=True), reps)
+            report(f"graph_spmm + b, relu + sign bits C{c}", ms, 2.0 * B * c * nnz, (3 + 1 / 32) * n)
+            ms = timeit(lambda: ops.graph_spmm(x, csr, out=out, relu=True, b=b, vec_b=vec, sign_mask=True), reps)
+            report(f"graph_spmm + b*scale+shift, relu + sign bits C{c}", ms, 2.0 * B * c * nnz, (3 + 1 / 32) * n)
+            ms_b = timeit(lambda: ops.bn_act(x, vec, b, None, relu=True, out=out, sign_mask=True), reps)
+            report(f"bn_act identity + sign bits (same tensors) C{c}", ms_b, 0, (3 + 1 / 32) * n)
+            print(f"   graph_spmm (+ b) / bn_act time ratio C{c}: {ms / ms_b:.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--b", type=int, default=128)
@@ -364,7 +392,7 @@ def main():
         print(f"-- tuning {k} = {v}")
     ops.set_math_mode(args.math)
     print(f"-- math mode {args.math}")
-    fns = dict(gemm=bench_gemm, pw=bench_pw, tconv=bench_tconv, wgrad=bench_wgrad, spatial=bench_spatial, spatial_wgrad=bench_spatial_wgrad, spatial_bwd=bench_spatial_bwd, emb_fwd=bench_emb_fwd, emb_bwd=bench_emb_bwd, joint=bench_joint, elem=bench_elem)
+    fns = dict(gemm=bench_gemm, pw=bench_pw, tconv=bench_tconv, wgrad=bench_wgrad, spatial=bench_spatial, spatial_wgrad=bench_spatial_wgrad, spatial_bwd=bench_spatial_bwd, emb_fwd=bench_emb_fwd, emb_bwd=bench_emb_bwd, joint=bench_joint, elem=bench_elem, spmm=bench_spmm)
     for k in args.only.split(","):
         fns[k](args.b, args.reps)
 
