@@ -151,7 +151,9 @@ def plan_block(cfg, B: int, T: int, V: int, *, x_bf16: bool, train: bool, infere
     g_bf16 = bool(half_storage and kt > 1 and not wide and t_fwd != "rows" and t_dgrad != "rows"
                   and all(n in ops.TWGRAD_TAPS_SPLIT for n in per_pass if n))
     g_sign = staged and (rows * cout) % 8 == 0
-    fuse_g = bool(staged and o.fuse_g and not g_bf16 and not ha and not cfg.has_down and halo9 and halo_sums
+    # (the conv's fused input stage exists with the bf16x3 / bf16 products only: fgcn_tconv_halo refuses it with the f16x2 products, whose
+    # BatchNorm-sums epilogue -- halo_sums -- does exist)
+    fuse_g = bool(staged and o.fuse_g and not f16x2 and not g_bf16 and not ha and not cfg.has_down and halo9 and halo_sums
                   and cin == cout and V <= 32 and (rows * cout) % 8 == 0)
     if g_bf16 and not g_sign:    # (no sign image: the backward would gate on g itself, which it reads as f32 -- cout % 64 == 0 rules it out)
         raise ops._lib.FgcnError("half-precision storage of G needs the sign image (element count a multiple of 8)")
@@ -184,10 +186,11 @@ def plan_block(cfg, B: int, T: int, V: int, *, x_bf16: bool, train: bool, infere
     # dY: both of its consumers on their tile kernels (only their staging reads it)
     dy_bf16 = bool(half_storage and wgrad_tile and bwd_tile and g_sign)
     # dx: every writer of dx must have the bfloat16 form -- the fused spatial backward first (with both gated shortcuts, or none to add),
-    # then the embedding tile kernel; a residual / down conv or an ungated shortcut writes float32, and the block converts at the end
+    # then the embedding tile kernel; a residual / down conv or an ungated shortcut writes float32, and the block converts at the end.
+    # (A block without a down conv always has the graph convolution's identity shortcut `y += x`: ungated -- also in a block without a
+    # residual, where nothing can gate it -- bn_act_bwd writes its gradient into dx, which it takes as float32 only.)
     dx_bf16 = bool(x_bf16 and ha and bwd_tile and dy_bf16 and not cfg.has_down and cfg.residual != "conv"
-                   and (cfg.residual == "none" or gate_in_dagg) and (cfg.static_adjacency or (emb_bwd == "tile" and emb_bf16))
-                   and (not gate_in_dagg or dg_bf16))
+                   and gate_in_dagg and (cfg.static_adjacency or (emb_bwd == "tile" and emb_bf16)) and dg_bf16)
     return BlockPlan(
         mode=mode, train=train, pool_groups=pool_groups, wide=wide, half_activations=ha, x_bf16=x_bf16,
         emb_fwd=emb_fwd, write_emb=emb_fwd == "gemm" or not no_emb, emb_bf16=emb_bf16, x_amax=x_amax, g_amax=f16x2 and t_fwd != "rows",

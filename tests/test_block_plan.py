@@ -49,9 +49,9 @@ def check(pl, cfg, mode, train):
         assert (not dx16 or pl.dx_bf16) and (not dg16 or pl.dg_bf16)
         if dx16:     # every writer of dx has the bfloat16 form
             assert pl.x_bf16 and pl.spatial_bwd == "tile" and pl.dy_bf16 and not cfg.has_down and cfg.residual != "conv"
-            assert cfg.residual == "none" or pl.gate_in_dagg
+            assert pl.gate_in_dagg      # (the graph convolution's own identity shortcut, ungated, is written by bn_act_bwd: float32 only)
             assert cfg.static_adjacency or (pl.emb_bwd == "tile" and pl.emb_bf16)
-            assert not pl.gate_in_dagg or (dg16 and (d_o_bf16 or pl.pool_rows))
+            assert dg16 and (d_o_bf16 or pl.pool_rows)
         assert not (dg16 and pl.gate_in_dagg) or dx16                # a gated addend has dx's storage type
         assert not dg16 or (pl.g_bf16 and pl.temporal_dgrad != "rows" and not pl.bn_sums_in_dgrad)
     assert not pl.gate_in_dagg or (pl.o_sign and pl.g_sign and pl.spatial_bwd in ("tile", "dagg") and cfg.residual == "identity" and not cfg.has_down)
