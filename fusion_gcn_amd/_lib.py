@@ -202,7 +202,13 @@ SIGNATURES = {
     "fgcn_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_optim_step": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _LL, _P]),
+    "fgcn_classify_state_bytes": (_LL, [_I]),
+    "fgcn_classify_update": (_I, [_P, _P, _P, _P, _P, _LL, _LL, _I, _I, _I, _I, _P]),
 }
+
+# enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)
+CLS_EXAMPLES, CLS_TOP1, CLS_TOPK, CLS_IGNORED, CLS_INVALID, CLS_DROPPED, CLS_LOSS_ITEMS, CLS_LOSS_SUM, CLS_WORDS = range(9)
+CLS_MAX_CLASSES = 1024      # FGCN_CLS_MAX_CLASSES
 
 _lib = None
 

@@ -1380,6 +1380,38 @@ def cross_entropy_bwd(probs: torch.Tensor, labels: torch.Tensor, loss: torch.Ten
     return dl
 
 
+def classify_state_bytes(classes: int) -> int:
+    """Size of the state buffer of ``classify_update`` (host-only query; 0 for a class count the kernel does not take)."""
+    return int(_lib.load().fgcn_classify_state_bytes(classes))
+
+
+def classify_update(logits: torch.Tensor, labels: torch.Tensor, state: torch.Tensor, *, k: int = 1, loss: Optional[torch.Tensor] = None,
+                    pred_out: Optional[torch.Tensor] = None, pred_offset: int = 0) -> None:
+    """One launch on the current stream: adds this batch to ``state`` (include/fgcn.h, fgcn_classify_update: counters, loss sum,
+    confusion matrix).  logits (rows, classes) float32 with unit column stride (any row stride), labels int64 (rows,), ``state`` a
+    contiguous int64 device tensor of at least ``classify_state_bytes(classes)`` bytes, ``loss`` one float32 on the device (the
+    step's loss), ``pred_out`` a contiguous int32 device tensor that receives the argmax of row r at ``pred_offset + r``."""
+    ensure_device()
+    if logits.dim() != 2 or labels.dim() != 1:
+        raise _lib.FgcnError("classify_update: logits (rows, classes) and labels (rows,)")
+    rows, classes = logits.shape
+    if not (logits.is_cuda and logits.dtype == torch.float32 and (classes == 1 or logits.stride(1) == 1) and labels.dtype == torch.int64
+            and labels.is_cuda and labels.is_contiguous() and labels.numel() == rows):
+        raise _lib.FgcnError("classify_update: float32 logits (rows, classes) with contiguous classes and int64 labels (rows,) on the device")
+    need = classify_state_bytes(classes)
+    if not (state.is_cuda and state.dtype == torch.int64 and state.is_contiguous() and need and state.numel() * 8 >= need):
+        raise _lib.FgcnError(f"classify_update: state must be a contiguous int64 device tensor of >= {need} bytes for {classes} classes "
+                             f"(at most {_lib.CLS_MAX_CLASSES})")
+    if loss is not None and not (loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+        raise _lib.FgcnError("classify_update: loss must be one float32 on the device")
+    if pred_out is not None and not (pred_out.is_cuda and pred_out.dtype == torch.int32 and pred_out.is_contiguous()):
+        raise _lib.FgcnError("classify_update: pred_out must be a contiguous int32 device tensor")
+    ld = logits.stride(0) if rows > 1 else max(logits.stride(0), classes)        # a single row's stride is arbitrary
+    check(_lib.load().fgcn_classify_update(logits.data_ptr(), labels.data_ptr(), None if loss is None else loss.data_ptr(),
+                                           state.data_ptr(), None if pred_out is None else pred_out.data_ptr(), pred_offset,
+                                           0 if pred_out is None else pred_out.numel(), rows, classes, ld, k, _stream()), "fgcn_classify_update")
+
+
 # ---- fused spatial forward -----------------------------------------------------------------------------------------
 def spatial_fwd(x: torch.Tensor, a_hat: torch.Tensor, wd: torch.Tensor, bias_sum: Optional[torch.Tensor], *, Cin: int,
                 Cout: int, stats: bool = True):

@@ -1,8 +1,10 @@
 """The epoch loops around the batch processors (reference torch_src/session/session.py:161-205, ``Session.train_epoch`` /
 ``Session.validate_epoch``): same arguments and order of operations -- batch to the device as float32 / int64, ``zero_grad``,
 process the batch, optimizer step, progress -- with the copy left to ``data.ClipBatches`` when it already delivers device tensors
-(its pinned double-buffered H2D pipeline).  Everything else of the reference's Session (config, checkpoints, logging, metrics
-classes) is control plane and out of scope; ``metrics`` / ``progress`` are duck-typed and optional."""
+(its pinned double-buffered H2D pipeline).  ``metrics`` is duck-typed and optional: ``fusion_gcn_amd.metrics.build_metrics``
+builds the reference's container on a device-side state (one kernel launch per batch, progress lines that never wait for the device:
+DESIGN.md section 8b).  Everything else of the reference's Session (config, checkpoints, logging) is control plane and out of scope
+(DESIGN.md section 0); ``progress`` is duck-typed and optional too."""
 from __future__ import annotations
 
 import torch

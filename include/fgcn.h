@@ -861,6 +861,49 @@ int fgcn_cross_entropy_fwd(const float* logits, const long long* labels, float* 
 int fgcn_cross_entropy_bwd(const float* probs, const long long* labels, const float* loss, const float* dloss, float* dlogits,
                            int rows, int classes, int ld_out, void* stream);
 
+/* Classification metrics accumulated on the device (metrics.py; reference torch_src/metrics.py Mean / MultiClassAccuracy /
+ * TopKAccuracy / ConfusionMatrix / MisclassifiedSamplesList): ONE launch per batch adds everything those classes derive their values
+ * from to a caller-owned state buffer; the host reads it when it wants a value, not once per batch.
+ *
+ * state (8-byte aligned, fgcn_classify_state_bytes(classes) bytes; the caller zeroes it to reset; the library allocates nothing
+ * and keeps no state):
+ *     bytes [0, 64)                    FGCN_CLS_WORDS = 8 words of 8 bytes, indexed by the enum below: int64 counters, except
+ *                                      word FGCN_CLS_LOSS_SUM, which is one float64
+ *     bytes [64, 64 + 4*classes^2)     int32 confusion[classes][classes], row = label, column = prediction
+ *     (+ 4 bytes of padding when classes is odd: the size is a multiple of 8)
+ *
+ * Per row r < rows of logits (float32, row stride ld >= classes) with label y = labels[r] (int64).  Logits compare in torch's
+ * order: NaN is greater than every number and equal to NaN; for rows without NaN that is plain > and ==.
+ *     pred    = the FIRST index of the row's maximum (torch.argmax; a NaN is the maximum).
+ *     rank(y) = #{j : logit_j > logit_y} + #{j < y : logit_j == logit_y}; the row is a top-k hit when rank(y) < k.  torch.topk
+ *               leaves the order of equal logits unspecified; this rule resolves ties towards the lower class index and makes a
+ *               top-1 hit the same thing as pred == y.
+ *     y == -100 (torch's ignore_index, as in fgcn_cross_entropy_fwd): ++IGNORED, nothing else.
+ *     any other y outside [0, classes): ++INVALID, nothing else; no address is ever formed from such a label.
+ *     otherwise: ++EXAMPLES, ++TOP1 if pred == y, ++TOPK on a hit, ++confusion[y][pred].
+ *     pred_out (may be NULL; int32[pred_capacity]): pred_out[pred_offset + r] = pred, or -1 for an ignored / invalid row, when
+ *               pred_offset + r < pred_capacity; a row past the capacity is not stored and counted in DROPPED.
+ * loss (may be NULL; device pointer to ONE float32, the step's loss): LOSS_SUM += (double)loss[0] * rows, LOSS_ITEMS += rows, by a
+ * single thread -- the reference's Mean.update(loss, num_items=len(label)), gradient-accumulation quotient included.
+ * Integer sums are exact in any order and the loss term is one addition per call: the same calls leave bit-identical state.
+ * FGCN_E_BADARG: a null logits / labels / state, rows <= 0, classes outside [1, FGCN_CLS_MAX_CLASSES], ld < classes, k outside
+ * [1, classes] (torch.topk raises there too), a negative pred_offset or pred_capacity; FGCN_E_ALIGN: state not 8-byte aligned. */
+enum fgcn_cls_word {
+    FGCN_CLS_EXAMPLES = 0,   /* rows with a label in [0, classes) */
+    FGCN_CLS_TOP1 = 1,       /* of those, pred == label */
+    FGCN_CLS_TOPK = 2,       /* of those, rank(label) < k */
+    FGCN_CLS_IGNORED = 3,    /* rows labelled -100 */
+    FGCN_CLS_INVALID = 4,    /* rows with any other label outside [0, classes) */
+    FGCN_CLS_DROPPED = 5,    /* rows whose prediction did not fit into pred_out */
+    FGCN_CLS_LOSS_ITEMS = 6, /* sum of `rows` over the calls that passed a loss */
+    FGCN_CLS_LOSS_SUM = 7,   /* float64: sum of loss[0] * rows over those calls */
+    FGCN_CLS_WORDS = 8
+};
+#define FGCN_CLS_MAX_CLASSES 1024
+long long fgcn_classify_state_bytes(int classes);   /* 0 for classes outside [1, FGCN_CLS_MAX_CLASSES] */
+int fgcn_classify_update(const float* logits, const long long* labels, const float* loss, void* state, int* pred_out,
+                         long long pred_offset, long long pred_capacity, int rows, int classes, int ld, int k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
