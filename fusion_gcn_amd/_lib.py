@@ -67,7 +67,8 @@ REDUCE_MAX_ITEMS = 8        # FGCN_REDUCE_MAX_ITEMS
 
 _I, _LL, _F, _P = C.c_int, C.c_longlong, C.c_float, C.c_void_p
 
-# name -> (restype, argtypes); mirrors include/fgcn.h one to one
+# name -> (restype, argtypes); mirrors include/fgcn.h one to one.  The fifteen kernels that take bfloat16 activation tensors carry `half_mask`
+# (an int) immediately before the stream (include/fgcn.h, "storage types and half_mask")
 SIGNATURES = {
     "fgcn_version": (_I, []),
     "fgcn_last_error": (C.c_char_p, []),
@@ -82,21 +83,21 @@ SIGNATURES = {
     "fgcn_get_math_mode": (_I, []),
     "fgcn_set_products": (_I, [_I]),
     "fgcn_get_products": (_I, []),
-    "fgcn_rows_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, TMap, _I, _P]),
+    "fgcn_rows_gemm": (_I, [_P] * 5 + [_I] * 8 + [TMap, _I, _I, _P]),
     "fgcn_rows_gemm_batched": (_I, [_P, _P, _P, _I, _LL, _LL, _LL, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_rows_gemm_batched2": (_I, [_P, _P, _P, _I, _LL, _LL, _LL, _I, _LL, _LL, _LL, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_rows_gemm_tiles": (_I, [_LL]),
     "fgcn_tconv_halo_tiles": (_I, [_I, _I, _I, _I]),
-    "fgcn_tconv_halo": (_I, [_P, _P, _P, _P, _P] + [_I] * 18 + [_P, _P, _P] + [_P, _P, _P, _P] + [_P, _P]),
+    "fgcn_tconv_halo": (_I, [_P] * 5 + [_I] * 18 + [_P] * 8 + [_I, _P]),
     "fgcn_tconv_halo_bn_sums": (_I, []),
     "fgcn_rows_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, TMap, _I, _P]),
     "fgcn_tconv_wgrad_slabs": (_I, [_I, _I]),
     "fgcn_pw_wgrad_slabs": (_I, [_I, _I]),
     "fgcn_tconv_wgrad_resident": (_I, [_I]),
     "fgcn_pw_wgrad_resident": (_I, [_I]),
-    "fgcn_tconv_wgrad": (_I, [_P, _P, _P] + [_I] * 17 + [_P, _P, _P]),
+    "fgcn_tconv_wgrad": (_I, [_P] * 3 + [_I] * 17 + [_P, _P, _I, _P]),
     "fgcn_pw_wgrad_chunks": (_I, [_I, _I]),
-    "fgcn_pw_wgrad": (_I, [_P, _P, _P] + [_I] * 11 + [_P, _P, _P]),
+    "fgcn_pw_wgrad": (_I, [_P] * 3 + [_I] * 11 + [_P, _P, _I, _P]),
     "fgcn_reduce_sum": (_I, [_P, _P, _I, _LL, _I, _P]),
     "fgcn_reduce_sum_strided": (_I, [_P, _P, _I, _I, _I, _I, _I, _LL, _LL, _LL, _I, _P]),
     "fgcn_reduce_multi": (_I, [C.POINTER(ReduceItem), _I, _P]),
@@ -114,18 +115,15 @@ SIGNATURES = {
     "fgcn_joint_gram": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(GramItem), _I, _P]),
     "fgcn_spatial_wgrad_chunks": (_I, [_I, _I, _I, _I]),
     "fgcn_spatial_wgrad": (_I, [_P] * 4 + [_I] * 9 + [_P]),
-    "fgcn_spatial_wgrad_tile": (_I, [_P] * 4 + [_I] * 8 + [_P]),
+    "fgcn_spatial_wgrad_tile": (_I, [_P] * 4 + [_I] * 9 + [_P]),
     "fgcn_spatial_wgrad_tile_slabs": (_I, [_I] * 5),
     "fgcn_spatial_wgrad_tile_available": (_I, [_I] * 3),
-    "fgcn_emb_fwd_tile": (_I, [_P] * 5 + [_I] * 7 + [_P]),
-    "fgcn_emb_fwd_tile_h": (_I, [_P] * 5 + [_I] * 7 + [_P]),
+    "fgcn_emb_fwd_tile": (_I, [_P] * 5 + [_I] * 8 + [_P]),
     "fgcn_emb_fwd_tile_segments": (_I, [_I] * 4),
     "fgcn_emb_fwd_tile_available": (_I, [_I] * 3),
-    "fgcn_emb_dx_tile": (_I, [_P] * 5 + [_I] * 9 + [_P]),
-    "fgcn_emb_dx_tile_h": (_I, [_P] * 5 + [_I] * 9 + [_P]),
+    "fgcn_emb_dx_tile": (_I, [_P] * 5 + [_I] * 9 + [_P, _I, _P]),
     "fgcn_emb_dx_tile_workspace": (_LL, [_I, _I]),
-    "fgcn_emb_wgrad_tile": (_I, [_P] * 5 + [_I] * 8 + [_P]),
-    "fgcn_emb_wgrad_tile_h": (_I, [_P] * 5 + [_I] * 8 + [_P]),
+    "fgcn_emb_wgrad_tile": (_I, [_P] * 5 + [_I] * 9 + [_P]),
     "fgcn_emb_wgrad_tile_slabs": (_I, [_I] * 5),
     "fgcn_emb_tile_available": (_I, [_I] * 3),
     "fgcn_joint_dagg": (_I, [_P] * 5 + [_I] * 11 + [_P] * 5),
@@ -137,36 +135,13 @@ SIGNATURES = {
     "fgcn_adj_softmax_bwd_wide": (_I, [_P, _I, _F, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_bn_finalize": (_I, [_P, _I, _LL, _P, _P, _P, _P, _F, _F, _P, _I, _P]),
     "fgcn_bn_eval_coeffs": (_I, [_P, _P, _P, _P, _F, _P, _I, _P]),
-    "fgcn_bn_act": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
+    "fgcn_bn_act": (_I, [_P] * 6 + [_LL, _I, _I, _I, _I, _P]),
     "fgcn_tconv_halo_bn_relu": (_I, [_P] * 7 + [_I] * 10 + [_P]),
     "fgcn_spatial_fwd_tile_bn_relu": (_I, [_P] * 7 + [_I] + [_P] + [_I] * 8 + [_P]),
-    "fgcn_bn_act_h": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
-    "fgcn_bn_act_bwd_apply_h": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
-    "fgcn_tconv_halo_h": (_I, [_P, _P, _P, _P, _P] + [_I] * 18 + [_P, _P, _P] + [_P]),
-    "fgcn_tconv_wgrad_h": (_I, [_P, _P, _P] + [_I] * 17 + [_P]),
-    "fgcn_pw_wgrad_h": (_I, [_P, _P, _P] + [_I] * 11 + [_P]),
-    "fgcn_spatial_bwd_tile_h": (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 10 + [_P, _I, _P, _P, _P, _P]),
-    "fgcn_spatial_wgrad_tile_h": (_I, [_P, _P, _P, _P] + [_I] * 8 + [_P]),
-    # typed forms (half-precision activation storage, math mode bf16): `half_mask` before the stream
-    "fgcn_bn_act_t": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
-    "fgcn_bn_act_pool_t": (_I, [_P] * 7 + [_I] * 5 + [_P]),
-    "fgcn_bn_act_bwd_reduce_t": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _I, _I, _I, _I, _P]),
-    "fgcn_bn_act_bwd_apply_t": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _P]),
-    "fgcn_tconv_halo_t": (_I, [_P, _P, _P, _P, _P] + [_I] * 18 + [_P]),
-    "fgcn_spatial_fwd_tile_t": (_I, [_P] * 6 + [_I] * 9 + [_P]),
-    "fgcn_emb_fwd_tile_t": (_I, [_P] * 5 + [_I] * 8 + [_P]),
-    "fgcn_spatial_bwd_tile_t": (_I, [_P] * 6 + [_I] * 10 + [_P, _I, _P, _P, _P, _I, _P]),
-    "fgcn_spatial_wgrad_tile_t": (_I, [_P] * 4 + [_I] * 9 + [_P]),
-    "fgcn_emb_dx_tile_t": (_I, [_P] * 5 + [_I] * 9 + [_P, _I, _P]),
-    "fgcn_emb_wgrad_tile_t": (_I, [_P] * 5 + [_I] * 9 + [_P]),
-    "fgcn_rows_gemm_t": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, TMap, _I, _I, _P]),
-    "fgcn_pw_gemm_t": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_bn_act_pool_splits": (_I, [_I, _I]),
-    "fgcn_bn_act_pool": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "fgcn_bn_act_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _I, _I, _I, _P]),
-    "fgcn_bn_act_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
-    "fgcn_bn_act_bwd_reduce_g": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _I, _I, _I, _P]),
-    "fgcn_bn_act_bwd_apply_g": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
+    "fgcn_bn_act_pool": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "fgcn_bn_act_bwd_reduce": (_I, [_P, _I] + [_P] * 7 + [_I, _LL, _I, _I, _I, _I, _P]),
+    "fgcn_bn_act_bwd_apply": (_I, [_P, _I] + [_P] * 9 + [_LL] + [_I] * 6 + [_P]),
     "fgcn_elem_tiles": (_I, [_LL]),
     "fgcn_bn_apply_ld": (_I, [_P, _P, _P, _LL, _I, _I, _P]),
     "fgcn_bn_bwd_reduce_ld": (_I, [_P, _I, _P, _P, _P, _I, _LL, _I, _P]),
@@ -174,11 +149,10 @@ SIGNATURES = {
     "fgcn_col_sum": (_I, [_P, _P, _LL, _I, _I, _P]),
     "fgcn_spatial_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_spatial_tiles": (_I, [_I, _I]),
-    "fgcn_spatial_fwd_tile": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fgcn_spatial_fwd_tile": (_I, [_P] * 6 + [_I] * 9 + [_P]),
     "fgcn_spatial_fwd_tile_tiles": (_I, [_I, _I, _I]),
     "fgcn_spatial_fwd_tile_available": (_I, [_I, _I, _I]),
-    "fgcn_spatial_bwd_tile": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "fgcn_spatial_bwd_tile_g": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "fgcn_spatial_bwd_tile": (_I, [_P] * 6 + [_I] * 10 + [_P, _I, _P, _P, _P, _I, _P]),
     "fgcn_spatial_bwd_tile_segments": (_I, [_I, _I, _I]),
     "fgcn_spatial_bwd_tile_available": (_I, [_I, _I, _I]),
     "fgcn_transpose": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
@@ -190,7 +164,7 @@ SIGNATURES = {
     "fgcn_unfold_windows": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_pw_gemm_available": (_I, []),
     "fgcn_pw_gemm_tiles": (_I, [_LL]),
-    "fgcn_pw_gemm": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P, _P]),
+    "fgcn_pw_gemm": (_I, [_P] * 5 + [_LL] + [_I] * 5 + [_P, _I, _P]),
     "fgcn_data_bn_tiles": (_I, [_I, _I]),
     "fgcn_data_bn_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "fgcn_data_bn_apply": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -75,7 +75,7 @@ extern "C" int fgcn_set_tuning(int key, int value) {
 
 extern "C" int fgcn_get_tuning(int key) { return fgcn::tuning(key); }
 
-extern "C" int fgcn_version(void) { return 100; }  // 0.1.0
+extern "C" int fgcn_version(void) { return 200; }  // 0.2.0
 
 extern "C" const char* fgcn_last_error(void) { return fgcn::error_buffer(); }
 

@@ -870,7 +870,7 @@ static int bn_act_bwd_apply_impl(const float* dout, const float* out, const unsi
     dim3 g(stream_blocks(n4)), blk(256);
     const int str = fgcn::stream_out(n4 * 16) ? 1 : 0;
     FGCN_REQUIRE(!db16 || (hm && C % 8 == 0 && ld_dout == C && !db_accumulate && db && (!relu || sign_mask)), FGCN_E_BADARG,
-                 "bn_act_bwd_apply_t: a bfloat16 db needs the eight-wide typed kernel (C %% 8 == 0) and no accumulation");
+                 "bn_act_bwd_apply: a bfloat16 db needs the eight-wide typed kernel (C %% 8 == 0) and no accumulation");
     if (hm && C % 8 == 0 && ld_dout == C && (!relu || sign_mask)) {      // typed operands: eight elements per thread
         const long long n8 = n4 / 2;
         const int hm8 = hm | (o16 ? 8 : 0);
@@ -1065,35 +1065,33 @@ extern "C" int fgcn_row_softmax_bwd(const float* da, const float* c, float* ds, 
     return fgcn::launch_status("row_softmax_bwd");
 }
 
-extern "C" int fgcn_bn_act(const float* a, const float* vec_a, const float* b, const float* vec_b, float* out,
-                           unsigned char* sign_mask, long long rows, int C, int res_mode, int relu, void* stream) {
-    return bn_act_impl(a, vec_a, b, vec_b, out, sign_mask, rows, C, res_mode, relu, C, stream);
+// half_mask of the four entry points below: which activation operands are bfloat16 tensors (math mode bf16 with half-precision activation
+// storage: the reference's autocast semantics, session/procedures/step.py:55-78); bit order = argument order, see include/fgcn.h
+extern "C" int fgcn_bn_act(const void* a, const float* vec_a, const void* b, const float* vec_b, void* out, unsigned char* sign_mask,
+                           long long rows, int C, int res_mode, int relu, int half_mask, void* stream) {
+    FGCN_REQUIRE((half_mask & ~7) == 0, FGCN_E_BADARG, "bn_act: half_mask=%d", half_mask);
+    // bit 0 a, bit 1 b -> hm; bit 2 out -> o16
+    return bn_act_impl(static_cast<const float*>(a), vec_a, static_cast<const float*>(b), vec_b, static_cast<float*>(out), sign_mask, rows, C,
+                       res_mode, relu, C, stream, (half_mask & 4) != 0, half_mask & 3);
 }
-extern "C" int fgcn_bn_act_h(const float* a, const float* vec_a, const float* b, const float* vec_b, unsigned short* out_h,
-                             unsigned char* sign_mask, long long rows, int C, int res_mode, int relu, void* stream) {
-    return bn_act_impl(a, vec_a, b, vec_b, reinterpret_cast<float*>(out_h), sign_mask, rows, C, res_mode, relu, C, stream, true);
+// grp_rows > 0: the gradient of a POOLED output (fgcn_bn_act_pool) -- dout is float[rows / grp_rows][C], one row per group of grp_rows consecutive
+// rows (already divided by the group size), read in place of the rows x C broadcast of it
+extern "C" int fgcn_bn_act_bwd_reduce(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
+                                      const float* vec_a, const void* b, const float* vec_b, float* partials, int n_tiles, long long rows,
+                                      int C, int res_mode, int relu, int half_mask, void* stream) {
+    FGCN_REQUIRE((half_mask & ~7) == 0 && grp_rows >= 0, FGCN_E_BADARG, "bn_act_bwd_reduce: half_mask=%d grp_rows=%d", half_mask, grp_rows);
+    // bit 0 dout, bit 1 a, bit 2 b -> hm
+    return bn_act_bwd_reduce_impl(static_cast<const float*>(dout), out, sign_mask, static_cast<const float*>(a), vec_a, static_cast<const float*>(b),
+                                  vec_b, partials, n_tiles, rows, C, res_mode, relu, C, stream, grp_rows, half_mask);
 }
-extern "C" int fgcn_bn_act_bwd_apply_h(const float* dout, int grp_rows, const float* out, const unsigned char* sign_mask,
-                                       const float* a, const float* vec_a, const float* b, const float* vec_b,
-                                       const float* sums, unsigned short* da_h, float* db,
-                                       long long rows, int C, int res_mode, int relu, int train, int db_accumulate, void* stream) {
-    FGCN_REQUIRE(grp_rows >= 0, FGCN_E_BADARG, "bn_act_bwd_apply_h: grp_rows=%d", grp_rows);
-    return bn_act_bwd_apply_impl(dout, out, sign_mask, a, vec_a, b, vec_b, sums, reinterpret_cast<float*>(da_h), db, rows, C, res_mode, relu,
-                                 train, db_accumulate, C, stream, grp_rows, true);
-}
-extern "C" int fgcn_bn_act_bwd_reduce(const float* dout, const float* out, const unsigned char* sign_mask,
-                                      const float* a, const float* vec_a, const float* b, const float* vec_b,
-                                      float* partials, int n_tiles, long long rows, int C, int res_mode, int relu,
-                                      void* stream) {
-    return bn_act_bwd_reduce_impl(dout, out, sign_mask, a, vec_a, b, vec_b, partials, n_tiles, rows, C, res_mode, relu, C, stream);
-}
-extern "C" int fgcn_bn_act_bwd_apply(const float* dout, const float* out, const unsigned char* sign_mask,
-                                     const float* a, const float* vec_a, const float* b, const float* vec_b,
-                                     const float* sums, float* da, float* db,
-                                     long long rows, int C, int res_mode, int relu, int train, int db_accumulate,
-                                     void* stream) {
-    return bn_act_bwd_apply_impl(dout, out, sign_mask, a, vec_a, b, vec_b, sums, da, db, rows, C, res_mode, relu, train, db_accumulate, C,
-                                 stream);
+extern "C" int fgcn_bn_act_bwd_apply(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
+                                     const float* vec_a, const void* b, const float* vec_b, const float* sums, void* da, void* db,
+                                     long long rows, int C, int res_mode, int relu, int train, int db_accumulate, int half_mask, void* stream) {
+    FGCN_REQUIRE((half_mask & ~31) == 0 && grp_rows >= 0, FGCN_E_BADARG, "bn_act_bwd_apply: half_mask=%d grp_rows=%d", half_mask, grp_rows);
+    // bit 0 dout, bit 1 a, bit 2 b -> hm; bit 3 da -> o16; bit 4 db -> db16
+    return bn_act_bwd_apply_impl(static_cast<const float*>(dout), out, sign_mask, static_cast<const float*>(a), vec_a, static_cast<const float*>(b),
+                                 vec_b, sums, static_cast<float*>(da), static_cast<float*>(db), rows, C, res_mode, relu, train, db_accumulate, C, stream,
+                                 grp_rows, (half_mask & 8) != 0, half_mask & 7, (half_mask & 16) ? 1 : 0);
 }
 
 // fgcn_bn_act followed by fgcn_group_mean without the tensor between them (the last block of the model): see bn_act_pool_kernel
@@ -1133,56 +1131,11 @@ static int bn_act_pool_impl(const float* a, const float* vec_a, const float* b, 
     return launch_status("bn_act_pool");
 }
 
-extern "C" int fgcn_bn_act_pool(const float* a, const float* vec_a, const float* b, const float* vec_b, unsigned char* sign_mask,
-                                float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, void* stream) {
-    return bn_act_pool_impl(a, vec_a, b, vec_b, sign_mask, partial, pooled, groups, grp_rows, C, res_mode, stream, 0);
-}
-
-// ---- typed forms (`_t`): `half_mask` says which activation operands are bfloat16 tensors (math mode bf16 with half-precision activation
-// storage: the reference's autocast semantics, session/procedures/step.py:55-78); bit order = argument order, see include/fgcn.h ------------
-extern "C" int fgcn_bn_act_t(const void* a, const float* vec_a, const void* b, const float* vec_b, void* out, unsigned char* sign_mask,
-                             long long rows, int C, int res_mode, int relu, int half_mask, void* stream) {
-    FGCN_REQUIRE((half_mask & ~7) == 0, FGCN_E_BADARG, "bn_act_t: half_mask=%d", half_mask);
-    return bn_act_impl(static_cast<const float*>(a), vec_a, static_cast<const float*>(b), vec_b, static_cast<float*>(out), sign_mask, rows, C,
-                       res_mode, relu, C, stream, (half_mask & 4) != 0, half_mask & 3);
-}
-extern "C" int fgcn_bn_act_pool_t(const void* a, const float* vec_a, const void* b, const float* vec_b, unsigned char* sign_mask,
-                                  float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, int half_mask, void* stream) {
-    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "bn_act_pool_t: half_mask=%d", half_mask);
+extern "C" int fgcn_bn_act_pool(const void* a, const float* vec_a, const void* b, const float* vec_b, unsigned char* sign_mask,
+                                float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, int half_mask, void* stream) {
+    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "bn_act_pool: half_mask=%d", half_mask);      // bit 0 a, bit 1 b -> hm
     return bn_act_pool_impl(static_cast<const float*>(a), vec_a, static_cast<const float*>(b), vec_b, sign_mask, partial, pooled, groups,
                             grp_rows, C, res_mode, stream, half_mask);
-}
-extern "C" int fgcn_bn_act_bwd_reduce_t(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
-                                        const float* vec_a, const void* b, const float* vec_b, float* partials, int n_tiles, long long rows,
-                                        int C, int res_mode, int relu, int half_mask, void* stream) {
-    FGCN_REQUIRE((half_mask & ~7) == 0 && grp_rows >= 0, FGCN_E_BADARG, "bn_act_bwd_reduce_t: half_mask=%d grp_rows=%d", half_mask, grp_rows);
-    return bn_act_bwd_reduce_impl(static_cast<const float*>(dout), out, sign_mask, static_cast<const float*>(a), vec_a, static_cast<const float*>(b),
-                                  vec_b, partials, n_tiles, rows, C, res_mode, relu, C, stream, grp_rows, half_mask);
-}
-extern "C" int fgcn_bn_act_bwd_apply_t(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
-                                       const float* vec_a, const void* b, const float* vec_b, const float* sums, void* da, void* db,
-                                       long long rows, int C, int res_mode, int relu, int train, int db_accumulate, int half_mask, void* stream) {
-    FGCN_REQUIRE((half_mask & ~31) == 0 && grp_rows >= 0, FGCN_E_BADARG, "bn_act_bwd_apply_t: half_mask=%d grp_rows=%d", half_mask, grp_rows);
-    return bn_act_bwd_apply_impl(static_cast<const float*>(dout), out, sign_mask, static_cast<const float*>(a), vec_a, static_cast<const float*>(b),
-                                 vec_b, sums, static_cast<float*>(da), static_cast<float*>(db), rows, C, res_mode, relu, train, db_accumulate, C, stream,
-                                 grp_rows, (half_mask & 8) != 0, half_mask & 7, (half_mask & 16) ? 1 : 0);
-}
-
-// The two backward passes with the gradient of a POOLED output (fgcn_bn_act_pool): dout is float[rows / grp_rows][C], one row per group of
-// grp_rows consecutive rows (already divided by the group size), read in place of the rows x C broadcast of it
-extern "C" int fgcn_bn_act_bwd_reduce_g(const float* dout_g, int grp_rows, const float* out, const unsigned char* sign_mask,
-                                        const float* a, const float* vec_a, const float* b, const float* vec_b,
-                                        float* partials, int n_tiles, long long rows, int C, int res_mode, int relu, void* stream) {
-    FGCN_REQUIRE(grp_rows > 0, FGCN_E_BADARG, "bn_act_bwd_reduce_g: grp_rows=%d", grp_rows);
-    return bn_act_bwd_reduce_impl(dout_g, out, sign_mask, a, vec_a, b, vec_b, partials, n_tiles, rows, C, res_mode, relu, C, stream, grp_rows);
-}
-extern "C" int fgcn_bn_act_bwd_apply_g(const float* dout_g, int grp_rows, const float* out, const unsigned char* sign_mask,
-                                       const float* a, const float* vec_a, const float* b, const float* vec_b,
-                                       const float* sums, float* da, float* db,
-                                       long long rows, int C, int res_mode, int relu, int train, int db_accumulate, void* stream) {
-    FGCN_REQUIRE(grp_rows > 0, FGCN_E_BADARG, "bn_act_bwd_apply_g: grp_rows=%d", grp_rows);
-    return bn_act_bwd_apply_impl(dout_g, out, sign_mask, a, vec_a, b, vec_b, sums, da, db, rows, C, res_mode, relu, train, db_accumulate, C,
-                                 stream, grp_rows);
 }
 
 // The same three passes for a plain BatchNorm (no residual, no activation) whose RESULT is a channel window of a wider tensor -- one

@@ -49,7 +49,7 @@ template <int NP> constexpr int ef_lds(int ic) { return std::max(NP * EF_XPLANE,
 
 // MU: 16-channel units per wave (CW = 32 MU channels per workgroup); IC: channels per group (16, 32, 64); NSUB: subsets of the workgroup
 // (3 when it holds all 6 ic channels, 1 when it holds th_k | ph_k of one subset)
-// E16 (NP = 1): emb is written as BFLOAT16 (half-precision storage: only the bf16 staging of fgcn_emb_dx_tile_h / fgcn_emb_wgrad_tile_h reads
+// E16 (NP = 1): emb is written as BFLOAT16 (half-precision storage: only the bf16 staging of fgcn_emb_dx_tile / fgcn_emb_wgrad_tile reads
 // it, and that staging rounds to bfloat16 anyway -- the same values, half the bytes; ld_e in elements)
 // H16 bit 0 = that (emb bfloat16), bit 1 = x is a BFLOAT16 tensor too (half-precision activation storage, the `_t` entry point; ld_x in
 // elements): its rows are copied into the image, 8 bytes per four channels -- the staged bytes of the float32 tensor of the same values
@@ -297,30 +297,20 @@ extern "C" int fgcn_emb_fwd_tile_segments(int B, int T, int V, int ic) {
 static int emb_fwd_tile_impl(const float* x, const void* w3, const float* bias, float* emb, float* partial, int B, int T, int V, int Cin,
                              int ic, int ld_x, int ld_e, void* stream, int e16);
 
-extern "C" int fgcn_emb_fwd_tile(const float* x, const void* w3, const float* bias, float* emb, float* partial, int B, int T, int V, int Cin,
-                                 int ic, int ld_x, int ld_e, void* stream) {
-    return emb_fwd_tile_impl(x, w3, bias, emb, partial, B, T, V, Cin, ic, ld_x, ld_e, stream, 0);
-}
-
-// emb written as BFLOAT16 (math mode bf16 only; ld_e in elements): its only readers, fgcn_emb_dx_tile_h / fgcn_emb_wgrad_tile_h, copy instead of
-// convert -- bit-identical results, half the bytes of the 1.5-activation-wide tensor
-extern "C" int fgcn_emb_fwd_tile_h(const float* x, const void* w3, const float* bias, unsigned short* emb_h, float* partial, int B, int T, int V,
-                                   int Cin, int ic, int ld_x, int ld_e, void* stream) {
-    FGCN_REQUIRE(emb_h, FGCN_E_BADARG, "emb_fwd_tile_h: null pointer");
-    return emb_fwd_tile_impl(x, w3, bias, reinterpret_cast<float*>(emb_h), partial, B, T, V, Cin, ic, ld_x, ld_e, stream, 1);
-}
-
-// typed form (math mode bf16): half_mask bit 0 = x is a bfloat16 tensor, bit 1 = emb is written as bfloat16 (emb may be NULL)
-extern "C" int fgcn_emb_fwd_tile_t(const void* x, const void* w3, const float* bias, void* emb, float* partial, int B, int T, int V, int Cin,
-                                   int ic, int ld_x, int ld_e, int half_mask, void* stream) {
-    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "emb_fwd_tile_t: half_mask=%d", half_mask);
+// half_mask (math mode bf16): bit 0 = x is a bfloat16 tensor, bit 1 = emb is written as BFLOAT16 (ld_e in elements): its only readers,
+// fgcn_emb_dx_tile / fgcn_emb_wgrad_tile, copy instead of convert -- bit-identical results, half the bytes of the 1.5-activation-wide tensor
+extern "C" int fgcn_emb_fwd_tile(const void* x, const void* w3, const float* bias, void* emb, float* partial, int B, int T, int V, int Cin,
+                                 int ic, int ld_x, int ld_e, int half_mask, void* stream) {
+    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "emb_fwd_tile: half_mask=%d", half_mask);
+    FGCN_REQUIRE(!(half_mask & 2) || emb, FGCN_E_BADARG, "emb_fwd_tile: null pointer (half_mask=%d names a bfloat16 emb)", half_mask);
+    // the kernel's selector has the bits the other way round: e16 bit 0 = emb, bit 1 = x
     return emb_fwd_tile_impl(static_cast<const float*>(x), w3, bias, static_cast<float*>(emb), partial, B, T, V, Cin, ic, ld_x, ld_e, stream,
                              ((half_mask & 2) ? 1 : 0) | ((half_mask & 1) ? 2 : 0));
 }
 
 static int emb_fwd_tile_impl(const float* x, const void* w3, const float* bias, float* emb, float* partial, int B, int T, int V, int Cin,
                              int ic, int ld_x, int ld_e, void* stream, int e16) {      // e16: bit 0 = emb bfloat16, bit 1 = x bfloat16 (1 or 3)
-    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_fwd_tile_h: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_fwd_tile: bfloat16 tensors need math mode bf16");
     // emb == NULL (inference: nothing reads the embeddings after the gram): the kernel's stores of emb go to an empty buffer descriptor and are
     // dropped by the hardware -- the 1.5-activation-wide tensor is never written
     const bool write_emb = emb != nullptr;

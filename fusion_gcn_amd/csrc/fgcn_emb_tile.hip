@@ -137,7 +137,7 @@ template <int NP> constexpr int ed_lds() { return NP * ED_PLANE + ED_NMAT * NP *
 // PD: chunks the emb values are requested ahead (the chunk loop is unrolled PD times; 6 ic / 32 is a multiple of 3); RSN: weight ring slots
 // (Measured and not kept, profiles/r05_kbench_emb_bwd_variants.txt: the emb values of all three chunks requested at once -- 215-244 registers,
 // 3-10 % slower; eight waves per workgroup, 4 x 2 over the tile, four waves per SIMD at 104-122 registers -- bit-identical, 6-14 % slower.)
-// E16 (NP = 1): emb is a BFLOAT16 tensor (fgcn_emb_fwd_tile_h; ld_e in elements): the strided requests fetch two bytes per value and the value
+// E16 (NP = 1): emb is a BFLOAT16 tensor (fgcn_emb_fwd_tile; ld_e in elements): the strided requests fetch two bytes per value and the value
 // is widened by a shift -- the fragment then holds the same bfloat16 the f32 form would have rounded to
 // H16 bit 0 = that, bit 1 = dx is a BFLOAT16 tensor too (half-precision activation storage, the `_t` entry point; ld_dx in elements): the old
 // values are 2-byte loads, the result is rounded once and adjacent lanes pair their columns into dword stores (fgcn_tconv.hip's bfloat16 epilogue)
@@ -737,27 +737,17 @@ static void ed_go(int e16, dim3 grid, hipStream_t s, const EmbDxP& p) {      // 
 static int emb_dx_tile_impl(const float* emb, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V, int ic, int Cx,
                             int ld_e, int ld_dx, int d_s_batched, int accumulate, void* stream, int e16, const float* dx_old = nullptr);
 
-extern "C" int fgcn_emb_dx_tile(const float* emb, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V, int ic, int Cx,
-                                int ld_e, int ld_dx, int d_s_batched, int accumulate, void* stream) {
-    return emb_dx_tile_impl(emb, d_s, w3, dx, workspace, B, T, V, ic, Cx, ld_e, ld_dx, d_s_batched, accumulate, stream, 0);
-}
-
-// emb as a BFLOAT16 tensor (fgcn_emb_fwd_tile_h; math mode bf16 only; ld_e in elements): bit-identical to the f32-emb call on the same values
-extern "C" int fgcn_emb_dx_tile_h(const unsigned short* emb_h, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V,
-                                  int ic, int Cx, int ld_e, int ld_dx, int d_s_batched, int accumulate, void* stream) {
-    return emb_dx_tile_impl(reinterpret_cast<const float*>(emb_h), d_s, w3, dx, workspace, B, T, V, ic, Cx, ld_e, ld_dx, d_s_batched, accumulate, stream,
-                            1);
-}
-
-// typed form (math mode bf16): half_mask bit 0 = emb is a bfloat16 tensor, bit 1 = dx is (masks 0, 1, 3); strides in elements.
+// half_mask (math mode bf16): bit 0 = emb is a BFLOAT16 tensor (as fgcn_emb_fwd_tile writes it: bit-identical to the f32-emb call on the same
+// values), bit 1 = dx is (masks 0, 1, 3); strides in elements.
 // dx_old (mask 3, accumulate): a float32 tensor laid out like dx that holds the values to add to -- dx itself is then only written
 // (dx = bfloat16(dx_old + term): the last writer of a float32-accumulated gradient hands it over as bfloat16); NULL: dx is read and written.
-extern "C" int fgcn_emb_dx_tile_t(const void* emb, const float* d_s, const void* w3, void* dx, void* workspace, int B, int T, int V,
-                                  int ic, int Cx, int ld_e, int ld_dx, int d_s_batched, int accumulate, const float* dx_old, int half_mask,
-                                  void* stream) {
-    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "emb_dx_tile_t: half_mask=%d (0, 1 or 3)", half_mask);
+extern "C" int fgcn_emb_dx_tile(const void* emb, const float* d_s, const void* w3, void* dx, void* workspace, int B, int T, int V,
+                                int ic, int Cx, int ld_e, int ld_dx, int d_s_batched, int accumulate, const float* dx_old, int half_mask,
+                                void* stream) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "emb_dx_tile: half_mask=%d (0, 1 or 3)", half_mask);
     FGCN_REQUIRE(!dx_old || (half_mask == 3 && accumulate && aligned16(dx_old)), FGCN_E_BADARG,
-                 "emb_dx_tile_t: dx_old comes with a bfloat16 emb and dx and accumulation");
+                 "emb_dx_tile: dx_old comes with a bfloat16 emb and dx and accumulation");
+    // e16: bit 0 emb, bit 1 dx, 7 = both with the addend read from dx_old
     return emb_dx_tile_impl(static_cast<const float*>(emb), d_s, w3, static_cast<float*>(dx), workspace, B, T, V, ic, Cx, ld_e, ld_dx, d_s_batched,
                             accumulate, stream, dx_old ? 7 : half_mask, dx_old);
 }
@@ -765,7 +755,7 @@ extern "C" int fgcn_emb_dx_tile_t(const void* emb, const float* d_s, const void*
 static int emb_dx_tile_impl(const float* emb, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V, int ic, int Cx,
                             int ld_e, int ld_dx, int d_s_batched, int accumulate, void* stream, int e16, const float* dx_old) {
     FGCN_REQUIRE(emb && d_s && w3 && dx && workspace, FGCN_E_BADARG, "emb_dx_tile: null pointer");
-    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_dx_tile_h: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_dx_tile: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(B > 0 && T > 0, FGCN_E_BADARG, "emb_dx_tile: bad sizes B=%d T=%d", B, T);
     FGCN_REQUIRE(emb_tile_mode_ok() && emb_tile_sizes_ok(V, ic, Cx), FGCN_E_BADARG,
                  "emb_dx_tile: needs math mode bf16x3 or bf16, 16 <= V <= %d, ic %% 16 == 0, Cx %% 64 == 0 (V=%d ic=%d Cx=%d, mode %d)", FGCN_MAX_V, V,
@@ -877,30 +867,18 @@ static void ew_go(int e16, dim3 grid, hipStream_t s, const EmbWgP& p) {      // 
 static int emb_wgrad_tile_impl(const float* emb, const float* x, const float* d_s, float* partial, float* bias_partial, int B, int T,
                                int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, void* stream, int e16);
 
-extern "C" int fgcn_emb_wgrad_tile(const float* emb, const float* x, const float* d_s, float* partial, float* bias_partial, int B, int T,
-                                   int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, void* stream) {
-    return emb_wgrad_tile_impl(emb, x, d_s, partial, bias_partial, B, T, V, ic, Cx, ld_e, ld_x, d_s_batched, stream, 0);
-}
-
-// emb as a BFLOAT16 tensor (fgcn_emb_fwd_tile_h; math mode bf16 only; ld_e in elements)
-extern "C" int fgcn_emb_wgrad_tile_h(const unsigned short* emb_h, const float* x, const float* d_s, float* partial, float* bias_partial, int B,
-                                     int T, int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, void* stream) {
-    return emb_wgrad_tile_impl(reinterpret_cast<const float*>(emb_h), x, d_s, partial, bias_partial, B, T, V, ic, Cx, ld_e, ld_x, d_s_batched, stream,
-                               1);
-}
-
-// typed form (math mode bf16): half_mask bit 0 = emb is a bfloat16 tensor, bit 1 = x is (masks 0, 1, 3); strides in elements
-extern "C" int fgcn_emb_wgrad_tile_t(const void* emb, const void* x, const float* d_s, float* partial, float* bias_partial, int B,
-                                     int T, int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, int half_mask, void* stream) {
-    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "emb_wgrad_tile_t: half_mask=%d (0, 1 or 3)", half_mask);
+// half_mask (math mode bf16): bit 0 = emb is a BFLOAT16 tensor (as fgcn_emb_fwd_tile writes it), bit 1 = x is (masks 0, 1, 3); strides in elements
+extern "C" int fgcn_emb_wgrad_tile(const void* emb, const void* x, const float* d_s, float* partial, float* bias_partial, int B,
+                                   int T, int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, int half_mask, void* stream) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "emb_wgrad_tile: half_mask=%d (0, 1 or 3)", half_mask);
     return emb_wgrad_tile_impl(static_cast<const float*>(emb), static_cast<const float*>(x), d_s, partial, bias_partial, B, T, V, ic, Cx, ld_e, ld_x,
-                               d_s_batched, stream, half_mask);
+                               d_s_batched, stream, half_mask);      // e16 = half_mask: bit 0 emb, bit 1 x
 }
 
 static int emb_wgrad_tile_impl(const float* emb, const float* x, const float* d_s, float* partial, float* bias_partial, int B, int T,
                                int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, void* stream, int e16) {
     FGCN_REQUIRE(emb && x && d_s && partial && bias_partial, FGCN_E_BADARG, "emb_wgrad_tile: null pointer");
-    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_wgrad_tile_h: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_wgrad_tile: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(B > 0 && T > 0, FGCN_E_BADARG, "emb_wgrad_tile: bad sizes B=%d T=%d", B, T);
     FGCN_REQUIRE(fgcn_emb_tile_available(V, ic, Cx), FGCN_E_BADARG,
                  "emb_wgrad_tile: V=%d ic=%d Cx=%d in math mode %d not supported (bf16x3 or bf16, 16 <= V <= %d, ic %% 16 == 0, Cx in 64s)", V, ic,

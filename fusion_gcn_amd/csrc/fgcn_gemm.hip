@@ -41,7 +41,7 @@ struct RowsGemmP {
 // MT x NT 32x32 accumulators per wave; the four waves stack along the rows: tile = (128*MT) rows x (32*NT) channels.
 // DB = double-buffered LDS (one barrier per K chunk instead of two, at twice the LDS footprint).
 // BF: FGCN_MATH_BF16 (one bf16 MFMA per four f32 MFMAs, operands rounded as the fragments are read)
-// IO (BF only; the typed entry point fgcn_rows_gemm_t, half-precision activation storage): bit 0 = `in` is a BFLOAT16 tensor (its values are
+// IO (BF only; the typed entry point fgcn_rows_gemm, half-precision activation storage): bit 0 = `in` is a BFLOAT16 tensor (its values are
 // widened into the same float32 LDS image: the fragments round them back to the same 16 bits), bit 1 = `out` is (the float32 result rounded
 // once; BatchNorm sums of the float32 values; not with accumulation; adjacent lanes pair their columns into dword stores)
 template <int MT, int NT, bool DB, bool BF, int IO = 0>
@@ -662,7 +662,7 @@ static int rows_gemm_launch(const float* in, float* out, const float* w, const f
                             void* stream, int inner = 1, long long in_bs2 = 0, long long out_bs2 = 0, long long w_bs2 = 0, int io = 0) {
     FGCN_REQUIRE(in && out && w, FGCN_E_BADARG, "rows_gemm: null pointer");
     FGCN_REQUIRE(io == 0 || (fgcn::math_mode() == FGCN_MATH_BF16 && batch == 1 && inner == 1 && !((io & 2) && accumulate)), FGCN_E_BADARG,
-                 "rows_gemm_t: bfloat16 tensors need math mode bf16, a single problem and (for a bfloat16 output) no accumulation");
+                 "rows_gemm: bfloat16 tensors need math mode bf16, a single problem and (for a bfloat16 output) no accumulation");
     FGCN_REQUIRE(batch >= 1 && inner >= 1 && (long long)batch * inner <= 65535 && in_bs % 4 == 0 && out_bs % 4 == 0 && w_bs % 4 == 0 &&
                      in_bs2 % 4 == 0 && out_bs2 % 4 == 0 && w_bs2 % 4 == 0,
                  FGCN_E_BADARG, "rows_gemm: batch=%d x %d / batch strides must be multiples of 4 floats", batch, inner);
@@ -746,21 +746,14 @@ static int rows_gemm_launch(const float* in, float* out, const float* w, const f
     return launch_status("rows_gemm");
 }
 
-extern "C" int fgcn_rows_gemm(const float* in, float* out, const float* w, const float* bias, float* stat_partials,
-                              int B, int T_in, int T_out, int V, int K, int N, int ld_in, int ld_out,
-                              fgcn_tmap map, int accumulate, void* stream) {
-    return rows_gemm_launch(in, out, w, bias, stat_partials, B, T_in, T_out, V, K, N, ld_in, ld_out, map, accumulate, 1, 0, 0, 0,
-                            stream);
-}
-
-// typed form (math mode bf16, half-precision activation storage): half_mask bit 0 = `in` is a bfloat16 tensor, bit 1 = `out` is (not with accumulation);
+// half_mask (math mode bf16, half-precision activation storage): bit 0 = `in` is a bfloat16 tensor, bit 1 = `out` is (not with accumulation);
 // strides in elements, stat_partials: the moments of the float32 results
-extern "C" int fgcn_rows_gemm_t(const void* in, void* out, const float* w, const float* bias, float* stat_partials,
-                                int B, int T_in, int T_out, int V, int K, int N, int ld_in, int ld_out,
-                                fgcn_tmap map, int accumulate, int half_mask, void* stream) {
-    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "rows_gemm_t: half_mask=%d", half_mask);
+extern "C" int fgcn_rows_gemm(const void* in, void* out, const float* w, const float* bias, float* stat_partials,
+                              int B, int T_in, int T_out, int V, int K, int N, int ld_in, int ld_out,
+                              fgcn_tmap map, int accumulate, int half_mask, void* stream) {
+    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "rows_gemm: half_mask=%d", half_mask);
     return rows_gemm_launch(static_cast<const float*>(in), static_cast<float*>(out), w, bias, stat_partials, B, T_in, T_out, V, K, N, ld_in, ld_out,
-                            map, accumulate, 1, 0, 0, 0, stream, 1, 0, 0, 0, half_mask);
+                            map, accumulate, 1, 0, 0, 0, stream, 1, 0, 0, 0, half_mask);      // io = half_mask: bit 0 in, bit 1 out
 }
 
 extern "C" int fgcn_rows_gemm_batched(const float* in, float* out, const float* w, int batch, long long in_bstride,

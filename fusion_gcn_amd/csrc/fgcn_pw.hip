@@ -49,7 +49,7 @@ using u32x4p = __attribute__((ext_vector_type(4))) unsigned int;
 // drained vmcnt(0) in front of EVERY group of four stores, i.e. sixteen full write round trips per tile and wave (found with the
 // FGCN_PROBE_PW timing probes: the stores cost 22 % of the kernel, the time the written bytes take at the HBM rate, with nothing
 // overlapping them).
-// IO (NP = 1; the typed entry point fgcn_pw_gemm_t, half-precision activation storage): bit 0 = `in` is a BFLOAT16 tensor (its rows are copied into
+// IO (NP = 1; the typed entry point fgcn_pw_gemm, half-precision activation storage): bit 0 = `in` is a BFLOAT16 tensor (its rows are copied into
 // the image: the staged bytes of the float32 tensor of the same values), bit 1 = `out` is (not with ACC; the float32 result rounded once, BatchNorm
 // sums of the float32 values, adjacent lanes pair their columns into dword stores)
 template <int NT, int NP, bool ACC, bool STR = false, int IO = 0>          // STR: non-temporal output stores (fgcn_common.hpp, stream_out)
@@ -387,25 +387,20 @@ extern "C" int fgcn_pw_gemm_available(void) {
 static int pw_gemm_impl(const float* in, float* out, const void* w3, const float* bias, float* stat_partials, long long rows,
                         int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, void* stream_, int io);
 
-extern "C" int fgcn_pw_gemm(const float* in, float* out, const void* w3, const float* bias, float* stat_partials, long long rows,
-                            int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, void* stream_) {
-    return pw_gemm_impl(in, out, w3, bias, stat_partials, rows, K, N, ld_in, ld_out, accumulate, in_amax, stream_, 0);
-}
-
-// typed form (math mode bf16, half-precision activation storage): half_mask bit 0 = `in` is a bfloat16 tensor, bit 1 = `out` is (not with
+// half_mask (math mode bf16, half-precision activation storage): bit 0 = `in` is a bfloat16 tensor, bit 1 = `out` is (not with
 // accumulation); strides in elements; stat_partials: the moments of the float32 results
-extern "C" int fgcn_pw_gemm_t(const void* in, void* out, const void* w3, const float* bias, float* stat_partials, long long rows,
-                              int K, int N, int ld_in, int ld_out, int accumulate, int half_mask, void* stream_) {
-    FGCN_REQUIRE((half_mask & ~3) == 0 && !((half_mask & 2) && accumulate), FGCN_E_BADARG, "pw_gemm_t: half_mask=%d (a bfloat16 output: no accumulation)",
+extern "C" int fgcn_pw_gemm(const void* in, void* out, const void* w3, const float* bias, float* stat_partials, long long rows,
+                            int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, int half_mask, void* stream_) {
+    FGCN_REQUIRE((half_mask & ~3) == 0 && !((half_mask & 2) && accumulate), FGCN_E_BADARG, "pw_gemm: half_mask=%d (a bfloat16 output: no accumulation)",
                  half_mask);
     return pw_gemm_impl(static_cast<const float*>(in), static_cast<float*>(out), w3, bias, stat_partials, rows, K, N, ld_in, ld_out, accumulate,
-                        nullptr, stream_, half_mask);
+                        in_amax, stream_, half_mask);      // io = half_mask: bit 0 in, bit 1 out
 }
 
 static int pw_gemm_impl(const float* in, float* out, const void* w3, const float* bias, float* stat_partials, long long rows,
                         int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, void* stream_, int io) {
     FGCN_REQUIRE(in && out && w3 && rows > 0, FGCN_E_BADARG, "pw_gemm: null pointer or no rows");
-    FGCN_REQUIRE(io == 0 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "pw_gemm_t: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(io == 0 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "pw_gemm: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(fgcn_pw_gemm_available(), FGCN_E_BADARG, "pw_gemm: a split-bf16 math mode (bf16x3 / bf16) only");
     FGCN_REQUIRE(K > 0 && K % 32 == 0 && N > 0 && N % 4 == 0 && ld_in % 4 == 0 && ld_out % 4 == 0 && ld_in >= K && ld_out >= N,
                  FGCN_E_ALIGN, "pw_gemm: K must be a multiple of 32, N and the row strides multiples of 4 (K=%d N=%d ld_in=%d ld_out=%d)", K,
@@ -451,7 +446,7 @@ static int pw_gemm_impl(const float* in, float* out, const void* w3, const float
         else hipLaunchKernelGGL((pw_x3_kernel<NT_, 1, false, false, 3>), grid, dim3(256), lds, s, p);                    \
     } while (0)
     if (io) {
-        FGCN_REQUIRE(one && !(accumulate && io != 1), FGCN_E_BADARG, "pw_gemm_t: an accumulating call takes a bfloat16 input only");
+        FGCN_REQUIRE(one && !(accumulate && io != 1), FGCN_E_BADARG, "pw_gemm: an accumulating call takes a bfloat16 input only");
         if (narrow) FGCN_PW_LAUNCH_T(1);
         else FGCN_PW_LAUNCH_T(2);
         return launch_status("pw_gemm");

@@ -84,7 +84,7 @@ __device__ __forceinline__ u32x2 sb_read_tr16(const unsigned char* p) {
 // NE: gated addends of dx (0 or 2; 2 only without accumulation)
 // NP: bf16 parts per operand -- 3: exact three-way splits (FGCN_MATH_BF16X3), 1: operands rounded to bfloat16 once (FGCN_MATH_BF16; the LDS
 // layout keeps room for three parts, the first is used)
-// IN16 (NP = 1): dy is a BFLOAT16 tensor (half-precision storage written by fgcn_bn_act_bwd_apply_h; ld_dy in elements): its rows are
+// IN16 (NP = 1): dy is a BFLOAT16 tensor (half-precision storage written by fgcn_bn_act_bwd_apply; ld_dy in elements): its rows are
 // copied into the staging plane instead of fetched as f32 and rounded -- the same staged bytes, half the reads
 // IN16 bit 1: x is a BFLOAT16 tensor as well, bit 2: dx and the gated addends are (half-precision activation storage, the `_t` entry point; strides
 // in elements; forms 0, 1, 3, 7): x's gram fragment is one 16-byte load of eight bfloat16 and needs no split, the addends / old dx values are
@@ -538,58 +538,29 @@ static int spatial_bwd_tile_launch(const float* dy, const float* x, const float*
                                    int accumulate, const float* extra1, const unsigned char* mask1, const float* extra2,
                                    const unsigned char* mask2, int extra1_group, void* stream, int dy16 = 0);
 
-// dy as a BFLOAT16 tensor (math mode bf16 only; ld_dy in elements): fgcn_spatial_bwd_tile (extra1_group = 0) / fgcn_spatial_bwd_tile_g
-// otherwise unchanged; bit-identical to the f32-dy call on the tensor fgcn_bn_act_bwd_apply would have written
-extern "C" int fgcn_spatial_bwd_tile_h(const unsigned short* dy_h, const float* x, const float* a_hat, const void* w3, float* dx, float* partial,
-                                       int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched, int accumulate,
-                                       const float* extra1, int extra1_group, const unsigned char* mask1, const float* extra2,
-                                       const unsigned char* mask2, void* stream) {
-    FGCN_REQUIRE(extra1_group >= 0 && (extra1_group == 0 || (extra1 && B % extra1_group == 0 && !accumulate)), FGCN_E_BADARG,
-                 "spatial_bwd_tile_h: %d samples are not whole groups of %d", B, extra1_group);
-    return spatial_bwd_tile_launch(reinterpret_cast<const float*>(dy_h), x, a_hat, w3, dx, partial, B, T, V, Cin, Cout, ld_dy, ld_x, ld_dx,
-                                   a_hat_batched, accumulate, extra1, mask1, extra2, mask2, extra1_group, stream, 1);
-}
-
-// typed form (math mode bf16): half_mask bit 0 = dy is a bfloat16 tensor, bit 1 = x is, bit 2 = dx AND the gated addends are (a per-group extra1
-// stays float32); masks 0, 1, 3, 7.  Strides in elements.
-extern "C" int fgcn_spatial_bwd_tile_t(const void* dy, const void* x, const float* a_hat, const void* w3, void* dx, float* partial,
-                                       int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched, int accumulate,
-                                       const void* extra1, int extra1_group, const unsigned char* mask1, const void* extra2,
-                                       const unsigned char* mask2, int half_mask, void* stream) {
-    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3 || half_mask == 7, FGCN_E_BADARG, "spatial_bwd_tile_t: half_mask=%d (0, 1, 3 or 7)",
+// extra1_group > 0: the first gated addend is given per GROUP of `extra1_group` consecutive samples, extra1 = float[B / extra1_group][Cin]
+// (not accumulating).  half_mask (math mode bf16; strides in elements): bit 0 = dy is a BFLOAT16 tensor (bit-identical to the f32-dy call on
+// the tensor fgcn_bn_act_bwd_apply would have written), bit 1 = x is, bit 2 = dx AND the gated addends are (a per-group extra1 stays float32);
+// masks 0, 1, 3, 7.
+extern "C" int fgcn_spatial_bwd_tile(const void* dy, const void* x, const float* a_hat, const void* w3, void* dx, float* partial,
+                                     int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched, int accumulate,
+                                     const void* extra1, int extra1_group, const unsigned char* mask1, const void* extra2,
+                                     const unsigned char* mask2, int half_mask, void* stream) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3 || half_mask == 7, FGCN_E_BADARG, "spatial_bwd_tile: half_mask=%d (0, 1, 3 or 7)",
                  half_mask);
     FGCN_REQUIRE(extra1_group >= 0 && (extra1_group == 0 || (extra1 && B % extra1_group == 0 && !accumulate)), FGCN_E_BADARG,
-                 "spatial_bwd_tile_t: %d samples are not whole groups of %d", B, extra1_group);
+                 "spatial_bwd_tile: %d samples are not whole groups of %d", B, extra1_group);
     return spatial_bwd_tile_launch(static_cast<const float*>(dy), static_cast<const float*>(x), a_hat, w3, static_cast<float*>(dx), partial, B, T, V,
                                    Cin, Cout, ld_dy, ld_x, ld_dx, a_hat_batched, accumulate, static_cast<const float*>(extra1), mask1,
-                                   static_cast<const float*>(extra2), mask2, extra1_group, stream, half_mask);
-}
-
-extern "C" int fgcn_spatial_bwd_tile(const float* dy, const float* x, const float* a_hat, const void* w3, float* dx, float* partial,
-                                     int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched,
-                                     int accumulate, const float* extra1, const unsigned char* mask1, const float* extra2,
-                                     const unsigned char* mask2, void* stream) {
-    return spatial_bwd_tile_launch(dy, x, a_hat, w3, dx, partial, B, T, V, Cin, Cout, ld_dy, ld_x, ld_dx, a_hat_batched, accumulate, extra1, mask1,
-                                   extra2, mask2, 0, stream);
-}
-
-// the same with the first gated addend given per GROUP of `extra1_group` consecutive samples: extra1 is float[B / extra1_group][Cin]
-extern "C" int fgcn_spatial_bwd_tile_g(const float* dy, const float* x, const float* a_hat, const void* w3, float* dx, float* partial,
-                                       int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched,
-                                       const float* extra1, int extra1_group, const unsigned char* mask1, const float* extra2,
-                                       const unsigned char* mask2, void* stream) {
-    FGCN_REQUIRE(extra1 && extra1_group > 0 && B % extra1_group == 0, FGCN_E_BADARG, "spatial_bwd_tile_g: %d samples are not whole groups of %d", B,
-                 extra1_group);
-    return spatial_bwd_tile_launch(dy, x, a_hat, w3, dx, partial, B, T, V, Cin, Cout, ld_dy, ld_x, ld_dx, a_hat_batched, 0, extra1, mask1, extra2,
-                                   mask2, extra1_group, stream);
+                                   static_cast<const float*>(extra2), mask2, extra1_group, stream, half_mask);      // dy16 = half_mask
 }
 
 static int spatial_bwd_tile_launch(const float* dy, const float* x, const float* a_hat, const void* w3, float* dx, float* partial,
                                    int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched,
                                    int accumulate, const float* extra1, const unsigned char* mask1, const float* extra2,
-                                   const unsigned char* mask2, int extra1_group, void* stream, int dy16) {      // dy16: the typed entry's half_mask (0, 1, 3, 7)
+                                   const unsigned char* mask2, int extra1_group, void* stream, int dy16) {      // dy16: the entry point's half_mask (0, 1, 3, 7)
     const bool gated = extra1 != nullptr;
-    FGCN_REQUIRE(!dy16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_bwd_tile_h: a bfloat16 dy needs math mode bf16");
+    FGCN_REQUIRE(!dy16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_bwd_tile: a bfloat16 dy needs math mode bf16");
     FGCN_REQUIRE(!gated || (mask1 && extra2 && mask2 && !accumulate && ld_x == Cin && Cin % 8 == 0), FGCN_E_BADARG,
                  "spatial_bwd_tile: gated addends come in pairs with their sign images, without accumulation, on contiguous (B, T, V, Cin) tensors");
     FGCN_REQUIRE(!gated || (aligned16(extra1) && aligned16(extra2)), FGCN_E_ALIGN, "spatial_bwd_tile: 16-byte aligned addends");

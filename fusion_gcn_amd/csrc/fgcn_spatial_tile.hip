@@ -414,21 +414,14 @@ static int spatial_fwd_tile_impl(const float* x, const float* a_hat, const void*
                                  float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
                                  int a_hat_batched, void* stream, const float* ep_vec, const float* ep_res, int ld_res, const float* ep_rvec, int io = 0);
 
-extern "C" int fgcn_spatial_fwd_tile(const float* x, const float* a_hat, const void* w3, const float* bias_sum, float* y,
-                                     float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
-                                     int a_hat_batched, void* stream) {
-    return spatial_fwd_tile_impl(x, a_hat, w3, bias_sum, y, stat_partials, B, T, V, Cin, Cout, ld_x, ld_y, a_hat_batched, stream, nullptr, nullptr, 0,
-                                 nullptr);
-}
-
-// typed form (math mode bf16, half-precision activation storage): half_mask bit 0 = x is a bfloat16 tensor, bit 1 = y is (masks 0, 2, 3);
+// half_mask (math mode bf16, half-precision activation storage): bit 0 = x is a bfloat16 tensor, bit 1 = y is (masks 0, 2, 3);
 // ld_x / ld_y in elements; stat_partials: the moments of the float32 accumulators
-extern "C" int fgcn_spatial_fwd_tile_t(const void* x, const float* a_hat, const void* w3, const float* bias_sum, void* y,
-                                       float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
-                                       int a_hat_batched, int half_mask, void* stream) {
-    FGCN_REQUIRE(half_mask == 0 || half_mask == 2 || half_mask == 3, FGCN_E_BADARG, "spatial_fwd_tile_t: half_mask=%d (0, 2 or 3)", half_mask);
+extern "C" int fgcn_spatial_fwd_tile(const void* x, const float* a_hat, const void* w3, const float* bias_sum, void* y,
+                                     float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
+                                     int a_hat_batched, int half_mask, void* stream) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 2 || half_mask == 3, FGCN_E_BADARG, "spatial_fwd_tile: half_mask=%d (0, 2 or 3)", half_mask);
     return spatial_fwd_tile_impl(static_cast<const float*>(x), a_hat, w3, bias_sum, static_cast<float*>(y), stat_partials, B, T, V, Cin, Cout, ld_x,
-                                 ld_y, a_hat_batched, stream, nullptr, nullptr, 0, nullptr, half_mask);
+                                 ld_y, a_hat_batched, stream, nullptr, nullptr, 0, nullptr, half_mask);      // io = half_mask: bit 0 x, bit 1 y
 }
 
 // Inference form of north-star kernel 1: aggregation + 1x1 feature contraction + (eval-mode) BatchNorm + shortcut + ReLU in ONE kernel --
@@ -448,7 +441,7 @@ static int spatial_fwd_tile_impl(const float* x, const float* a_hat, const void*
                                  int a_hat_batched, void* stream, const float* ep_vec, const float* ep_res, int ld_res, const float* ep_rvec, int io) {
     FGCN_REQUIRE(x && a_hat && w3 && y, FGCN_E_BADARG, "spatial_fwd_tile: null pointer");
     FGCN_REQUIRE(io == 0 || ((io == 2 || io == 3) && fgcn::math_mode() == FGCN_MATH_BF16 && !ep_vec), FGCN_E_BADARG,
-                 "spatial_fwd_tile_t: bfloat16 tensors (half_mask 2 or 3) need math mode bf16 and the training form");
+                 "spatial_fwd_tile: bfloat16 tensors (half_mask 2 or 3) need math mode bf16 and the training form");
     FGCN_REQUIRE(B > 0 && T > 0 && Cin > 0 && Cout > 0, FGCN_E_BADARG, "spatial_fwd_tile: bad sizes B=%d T=%d Cin=%d Cout=%d", B, T, Cin, Cout);
     FGCN_REQUIRE(fgcn_spatial_fwd_tile_available(V, Cin, Cout), FGCN_E_BADARG,
                  "spatial_fwd_tile: needs math mode bf16x3 (bf16x3 products) or bf16, 16 <= V <= %d, Cin %% 64 == 0, Cout %% 4 == 0 (V=%d Cin=%d Cout=%d)",

@@ -74,7 +74,7 @@ __device__ __forceinline__ void swt_for_slots(Fn&& fn, std::integer_sequence<int
 // slot loop put an s_waitcnt vmcnt(0) and register copies on its back edge: every request made ahead was waited for one slot later))
 // NP: bf16 parts per operand -- 3: exact three-way splits (FGCN_MATH_BF16X3), 1: operands rounded to bfloat16 once (FGCN_MATH_BF16; the LDS layout
 // keeps room for three parts, the first is used)
-// IN16 (NP = 1): dy is a BFLOAT16 tensor (fgcn_bn_act_bwd_apply_h; ld_dy in elements): its rows are copied into the plane, half the reads
+// IN16 (NP = 1): dy is a BFLOAT16 tensor (fgcn_bn_act_bwd_apply; ld_dy in elements): its rows are copied into the plane, half the reads
 // IN16 = 3: x is a BFLOAT16 tensor as well (half-precision activation storage, the `_t` entry point; ld_x in elements): 2-byte loads of the
 // values the float32 form would round to the same 16 bits
 template <int CT, int NT, int NSLOT, int NP = 3, int IN16 = 0>
@@ -334,23 +334,12 @@ extern "C" int fgcn_spatial_wgrad_tile_slabs(int B, int T, int V, int Cin, int C
 static int spatial_wgrad_tile_launch(const float* x, const float* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
                                      int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream, int dy16);
 
-extern "C" int fgcn_spatial_wgrad_tile(const float* x, const float* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
-                                       int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream) {
-    return spatial_wgrad_tile_launch(x, dy, a_hat, partial, B, T, V, Cin, Cout, ld_x, ld_dy, a_hat_batched, stream, 0);
-}
-
-// dy as a BFLOAT16 tensor (math mode bf16 only; ld_dy in elements); otherwise fgcn_spatial_wgrad_tile, bit-identical to its result on the
-// f32 tensor fgcn_bn_act_bwd_apply would have written
-extern "C" int fgcn_spatial_wgrad_tile_h(const float* x, const unsigned short* dy_h, const float* a_hat, float* partial, int B, int T, int V,
-                                         int Cin, int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream) {
-    return spatial_wgrad_tile_launch(x, reinterpret_cast<const float*>(dy_h), a_hat, partial, B, T, V, Cin, Cout, ld_x, ld_dy, a_hat_batched, stream,
-                                     1);
-}
-
-// typed form (math mode bf16): half_mask bit 0 = x is a bfloat16 tensor, bit 1 = dy is (masks 0, 2, 3: a bfloat16 x comes with a bfloat16 dy)
-extern "C" int fgcn_spatial_wgrad_tile_t(const void* x, const void* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
-                                         int Cout, int ld_x, int ld_dy, int a_hat_batched, int half_mask, void* stream) {
-    FGCN_REQUIRE(half_mask == 0 || half_mask == 2 || half_mask == 3, FGCN_E_BADARG, "spatial_wgrad_tile_t: half_mask=%d (0, 2 or 3)", half_mask);
+// half_mask (math mode bf16; strides in elements): bit 0 = x is a BFLOAT16 tensor, bit 1 = dy is (masks 0, 2, 3: a bfloat16 x comes with a
+// bfloat16 dy); a bfloat16 dy alone is bit-identical to the call on the f32 tensor fgcn_bn_act_bwd_apply would have written
+extern "C" int fgcn_spatial_wgrad_tile(const void* x, const void* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
+                                       int Cout, int ld_x, int ld_dy, int a_hat_batched, int half_mask, void* stream) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 2 || half_mask == 3, FGCN_E_BADARG, "spatial_wgrad_tile: half_mask=%d (0, 2 or 3)", half_mask);
+    // the kernel's selector counts from dy: dy16 1 = dy bfloat16, 3 = dy and x
     return spatial_wgrad_tile_launch(static_cast<const float*>(x), static_cast<const float*>(dy), a_hat, partial, B, T, V, Cin, Cout, ld_x, ld_dy,
                                      a_hat_batched, stream, half_mask == 3 ? 3 : (half_mask == 2 ? 1 : 0));
 }
@@ -358,7 +347,7 @@ extern "C" int fgcn_spatial_wgrad_tile_t(const void* x, const void* dy, const fl
 static int spatial_wgrad_tile_launch(const float* x, const float* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
                                      int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream, int dy16) {   // dy16: 1 = dy bfloat16, 3 = dy and x
     FGCN_REQUIRE(x && dy && a_hat && partial, FGCN_E_BADARG, "spatial_wgrad_tile: null pointer");
-    FGCN_REQUIRE(!dy16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_wgrad_tile_h: a bfloat16 dy needs math mode bf16");
+    FGCN_REQUIRE(!dy16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_wgrad_tile: a bfloat16 dy needs math mode bf16");
     FGCN_REQUIRE(fgcn_spatial_wgrad_tile_available(V, Cin, Cout), FGCN_E_BADARG,
                  "spatial_wgrad_tile: V=%d Cin=%d Cout=%d in math mode %d not supported (split-bf16 mode, 16 <= V <= %d, channels in 64s)", V,
                  Cin, Cout, fgcn::math_mode(), FGCN_MAX_V);

@@ -346,8 +346,8 @@ __global__ __launch_bounds__(256, MINB) void conv_halo_kernel(HaloP p) {
 // WR = wave rows: 2 = waves 2 x 2 over (128 rows x 64 NT columns); 4 = waves 4 x 1 over (192 rows x 32 NT columns), the form for 64
 // output columns (NT = 2): every image fragment then feeds FOUR 16-column units instead of two (half the LDS fragment reads per MFMA --
 // the 2 x 2 form at 64 columns reads 12 KB of fragments per 48 MFMAs and wave) and the halo image is re-staged 2.04x instead of 2.56x.
-// IN16 (NP = 1): `in` is a BFLOAT16 tensor (half-precision storage of the conv's input, written by its producer: fgcn_bn_act_h /
-// fgcn_bn_act_bwd_apply_h) -- the image rows are copied, 8 bytes per four channels, instead of fetched as f32 and rounded here.  The staged
+// IN16 (NP = 1): `in` is a BFLOAT16 tensor (half-precision storage of the conv's input, written by its producer: fgcn_bn_act /
+// fgcn_bn_act_bwd_apply) -- the image rows are copied, 8 bytes per four channels, instead of fetched as f32 and rounded here.  The staged
 // bytes are the same either way (one round-to-nearest-even per value), so the results are bit-identical to the f32-input form; the row
 // traffic through L2 -- what bounds this kernel in math mode bf16, where the matrix work is a sixth -- halves.
 // IN16 = 2: `out` is a bfloat16 tensor as well (half-precision ACTIVATION storage, the `_t` entry point: the pre-BatchNorm output U of the
@@ -926,10 +926,10 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
                  FGCN_E_BADARG, "tconv_halo_bn_relu: the inference output stage needs the split kernel (bf16x3 products or bf16), the tap form, a "
                  "plain output view, no statistics / accumulation / fused input stage");
     FGCN_REQUIRE(!in16 || (fgcn::math_mode() == FGCN_MATH_BF16 && !(fin_vec || fin_res || fin_out || fin_mask) && !(taps == 1 && K % 64 == 0)),
-                 FGCN_E_BADARG, "tconv_halo_h: a bfloat16 input needs math mode bf16, the tap form and no fused input stage");
+                 FGCN_E_BADARG, "tconv_halo: a bfloat16 input needs math mode bf16, the tap form and no fused input stage");
     // (in16 == 2: the output is bfloat16 too -- the plain store epilogue, with or without the forward moments)
     FGCN_REQUIRE(in16 != 2 || (!accumulate && !bn_a && !fep && ld_out % 2 == 0), FGCN_E_BADARG,
-                 "tconv_halo_t: a bfloat16 output is written by the plain store epilogue (no accumulation, no BatchNorm-backward sums)");
+                 "tconv_halo: a bfloat16 output is written by the plain store epilogue (no accumulation, no BatchNorm-backward sums)");
     const bool fin = fin_vec || fin_res || fin_out || fin_mask;
     FGCN_REQUIRE(!fin || !fgcn::f16x2_products(), FGCN_E_BADARG, "tconv_halo: the fused input stage is not built for the f16x2 products");
     FGCN_REQUIRE(!fin || (fin_vec && fin_res && fin_out && fin_mask && fgcn_tconv_halo_bn_sums() && !bn_a && !accumulate && taps > 1 &&
@@ -1122,42 +1122,22 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
     return launch_status("tconv_halo");
 }
 
-extern "C" int fgcn_tconv_halo(const float* in, float* out, const float* w4, const float* bias, float* stat_partials,
+// half_mask bit 0 = `in` is a BFLOAT16 tensor, bit 1 = `out` is (math mode bf16; strides in elements; a bfloat16 output needs a bfloat16
+// input: masks 0, 1, 3).  A bfloat16 input (G of fgcn_bn_act, dU of fgcn_bn_act_bwd_apply) is bit-identical to the call on the f32 tensor those
+// kernels would have written: the bf16 kernel rounds its input to bfloat16, to nearest even, as it stages it.  A bfloat16 output takes the plain
+// store epilogue; stat_partials are then the forward moments of the float32 accumulators.
+extern "C" int fgcn_tconv_halo(const void* in, void* out, const float* w4, const float* bias, float* stat_partials,
                                int B, int Th, int V, int K, int N, int ld_in, int ld_out,
                                int T_in_full, int in_s, int in_o, int Th_in,
                                int T_out_full, int out_s, int out_o,
                                int taps, int tb, int tc, int accumulate, const float* bn_a, const unsigned char* bn_mask,
                                const float* bn_vec, const float* fin_vec, const float* fin_res, float* fin_out,
-                               unsigned char* fin_mask, unsigned* in_amax, void* stream) {
-    return tconv_halo_impl(in, out, w4, bias, stat_partials, B, Th, V, K, N, ld_in, ld_out, T_in_full, in_s, in_o, Th_in, T_out_full, out_s, out_o,
-                           taps, tb, tc, accumulate, bn_a, bn_mask, bn_vec, fin_vec, fin_res, fin_out, fin_mask, in_amax, stream, false);
-}
-
-// The same convolution with a BFLOAT16 input tensor (math mode bf16 only; ld_in in elements): half-precision storage of the conv's input,
-// written by fgcn_bn_act_h (G) / fgcn_bn_act_bwd_apply_h (dU).  Bit-identical to fgcn_tconv_halo on the f32 tensor those kernels would
-// have written (the bf16 kernel rounds its input to bfloat16, to nearest even, as it stages it).
-extern "C" int fgcn_tconv_halo_h(const unsigned short* in_h, float* out, const float* w4, const float* bias, float* stat_partials,
-                                 int B, int Th, int V, int K, int N, int ld_in, int ld_out,
-                                 int T_in_full, int in_s, int in_o, int Th_in,
-                                 int T_out_full, int out_s, int out_o,
-                                 int taps, int tb, int tc, int accumulate, const float* bn_a, const unsigned char* bn_mask,
-                                 const float* bn_vec, void* stream) {
-    return tconv_halo_impl(reinterpret_cast<const float*>(in_h), out, w4, bias, stat_partials, B, Th, V, K, N, ld_in, ld_out, T_in_full, in_s, in_o,
-                           Th_in, T_out_full, out_s, out_o, taps, tb, tc, accumulate, bn_a, bn_mask, bn_vec, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, stream, 1);
-}
-
-// typed form: half_mask bit 0 = `in` is bfloat16, bit 1 = `out` is (math mode bf16; a bfloat16 output needs a bfloat16 input: masks 0, 1, 3).
-// The plain store epilogue (no accumulation, no BatchNorm-backward sums); stat_partials: the forward moments of the float32 accumulators.
-extern "C" int fgcn_tconv_halo_t(const void* in, void* out, const float* w4, const float* bias, float* stat_partials,
-                                 int B, int Th, int V, int K, int N, int ld_in, int ld_out,
-                                 int T_in_full, int in_s, int in_o, int Th_in,
-                                 int T_out_full, int out_s, int out_o,
-                                 int taps, int tb, int tc, int half_mask, void* stream) {
-    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "tconv_halo_t: half_mask=%d (0, 1 or 3)", half_mask);
+                               unsigned char* fin_mask, unsigned* in_amax, int half_mask, void* stream) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "tconv_halo: half_mask=%d (0, 1 or 3)", half_mask);
+    const int in16 = half_mask == 3 ? 2 : half_mask;      // 0 float32, 1 bfloat16 in, 2 bfloat16 in and out
     return tconv_halo_impl(static_cast<const float*>(in), static_cast<float*>(out), w4, bias, stat_partials, B, Th, V, K, N, ld_in, ld_out, T_in_full,
-                           in_s, in_o, Th_in, T_out_full, out_s, out_o, taps, tb, tc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, stream, half_mask == 3 ? 2 : half_mask);
+                           in_s, in_o, Th_in, T_out_full, out_s, out_o, taps, tb, tc, accumulate, bn_a, bn_mask, bn_vec, fin_vec, fin_res, fin_out,
+                           fin_mask, in_amax, stream, in16);
 }
 
 // North-star kernel 2 as the north star states it, for INFERENCE: the (taps x 1) temporal convolution (stride 1) with the block's output

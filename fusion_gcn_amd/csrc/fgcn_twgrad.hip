@@ -217,7 +217,7 @@ __device__ __forceinline__ u32x2 lds_read_tr16(const unsigned char* p) {
 // 9 taps, V = 25) the a planes are a circular image: row q of the sample's frame view lives at slot q & (ring_rows - 1), a stage
 // adds its X3_R new rows (prefetched across the previous stage's MFMAs), and only the first stage of a sample (or of the
 // workgroup's share) fills the (NTAP-1) V older rows, synchronously.  Fragment addresses wrap per read.
-// IN16 (NP = 1, tap mode): a and g are BFLOAT16 tensors (half-precision storage written by fgcn_bn_act_h / fgcn_bn_act_bwd_apply_h): the
+// IN16 (NP = 1, tap mode): a and g are BFLOAT16 tensors (half-precision storage written by fgcn_bn_act / fgcn_bn_act_bwd_apply): the
 // stage is copied, 8 bytes per four values, instead of fetched as f32 and rounded here -- the same staged bytes, half the reads.
 template <int NTAP, int TN, bool CH, int NP, int WV = 8, bool RING = false, bool IN16 = false>
 __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void tconv_wgrad_x3_kernel(TWgradP p) {
@@ -695,35 +695,25 @@ static int twgrad_launch(const float* a, const float* g, float* partial, int B, 
     return launch_status(what);
 }
 
-extern "C" int fgcn_tconv_wgrad(const float* a, const float* g, float* partial, int B, int T_g, int V, int K, int N,
+// half_mask of the two weight-gradient entry points: bit 0 = a (the conv's input), bit 1 = g (the gradient of its output) are BFLOAT16 tensors
+// (math mode bf16; ld_a / ld_g in elements) -- both or neither: masks 0 and 3.  Bit-identical to the call on the f32 tensors the producers would
+// have written (operands are rounded to bfloat16, to nearest even, when staged either way).  The operand scales belong to the f16x2 products of
+// float32 tensors: a bfloat16 pair refuses them.
+static int twgrad_mask(const char* what, int half_mask, const unsigned* a_amax, const unsigned* g_amax) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 3, FGCN_E_BADARG, "%s: half_mask=%d (0 or 3)", what, half_mask);
+    FGCN_REQUIRE(!half_mask || (!a_amax && !g_amax), FGCN_E_BADARG, "%s: bfloat16 inputs (half_mask=3) take no a_amax / g_amax", what);
+    return FGCN_OK;
+}
+
+extern "C" int fgcn_tconv_wgrad(const void* a, const void* g, float* partial, int B, int T_g, int V, int K, int N,
                                 int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int Th_a,
                                 int ntaps, int shift0, int tap0, int tap_step, int taps_total, int nsplit,
-                                const unsigned* a_amax, const unsigned* g_amax, void* stream) {
+                                const unsigned* a_amax, const unsigned* g_amax, int half_mask, void* stream) {
+    if (int e = twgrad_mask("tconv_wgrad", half_mask, a_amax, g_amax)) return e;
     FGCN_REQUIRE(ntaps >= 1 && ntaps <= 9 && tap_step >= 1 && tap0 >= 0 && tap0 + (ntaps - 1) * tap_step < taps_total,
                  FGCN_E_BADARG, "tconv_wgrad: taps (%d from %d step %d of %d)", ntaps, tap0, tap_step, taps_total);
-    return twgrad_launch(a, g, partial, B, T_g, V, K, N, ld_a, ld_g, T_a_full, a_s, a_o, Th_a, ntaps, 0, shift0, tap0,
-                         tap_step, taps_total, nsplit, a_amax, g_amax, stream, "tconv_wgrad");
-}
-
-// The same weight gradient from BFLOAT16 tensors a (the conv's input) and g (the gradient of its output), math mode bf16 only; ld_a / ld_g in
-// elements.  Bit-identical to fgcn_tconv_wgrad on the f32 tensors the producers would have written (operands are rounded to bfloat16, to
-// nearest even, when staged either way).
-extern "C" int fgcn_tconv_wgrad_h(const unsigned short* a_h, const unsigned short* g_h, float* partial, int B, int T_g, int V, int K, int N,
-                                  int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int Th_a,
-                                  int ntaps, int shift0, int tap0, int tap_step, int taps_total, int nsplit, void* stream) {
-    FGCN_REQUIRE(ntaps >= 1 && ntaps <= 9 && tap_step >= 1 && tap0 >= 0 && tap0 + (ntaps - 1) * tap_step < taps_total,
-                 FGCN_E_BADARG, "tconv_wgrad_h: taps (%d from %d step %d of %d)", ntaps, tap0, tap_step, taps_total);
-    return twgrad_launch(reinterpret_cast<const float*>(a_h), reinterpret_cast<const float*>(g_h), partial, B, T_g, V, K, N, ld_a, ld_g, T_a_full,
-                         a_s, a_o, Th_a, ntaps, 0, shift0, tap0, tap_step, taps_total, nsplit, nullptr, nullptr, stream, "tconv_wgrad_h", true);
-}
-
-// fgcn_pw_wgrad with bfloat16 tensors a and g (math mode bf16; ld_a / ld_g in elements): the shortcut convolutions' weight gradients under
-// half-precision activation storage -- bit-identical to the float32 call on the same values
-extern "C" int fgcn_pw_wgrad_h(const unsigned short* a_h, const unsigned short* g_h, float* partial, int B, int T_g, int V, int K, int N,
-                               int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int nsplit, void* stream) {
-    FGCN_REQUIRE(a_s >= 1 && T_g > 0, FGCN_E_BADARG, "pw_wgrad_h: bad frame view");
-    return twgrad_launch(reinterpret_cast<const float*>(a_h), reinterpret_cast<const float*>(g_h), partial, B, T_g, V, K, N, ld_a, ld_g, T_a_full, a_s,
-                         a_o, T_g, fgcn_pw_wgrad_chunks(K, N), 1, 0, 0, 1, 1, nsplit, nullptr, nullptr, stream, "pw_wgrad_h", true);
+    return twgrad_launch(static_cast<const float*>(a), static_cast<const float*>(g), partial, B, T_g, V, K, N, ld_a, ld_g, T_a_full, a_s, a_o,
+                         Th_a, ntaps, 0, shift0, tap0, tap_step, taps_total, nsplit, a_amax, g_amax, stream, "tconv_wgrad", half_mask == 3);
 }
 
 /* in-channel chunks (32 channels each = one accumulator) per wave for a 1x1 weight gradient: a divisor of the chunk
@@ -736,10 +726,11 @@ extern "C" int fgcn_pw_wgrad_chunks(int K, int N) {
     return cap;
 }
 
-extern "C" int fgcn_pw_wgrad(const float* a, const float* g, float* partial, int B, int T_g, int V, int K, int N,
+extern "C" int fgcn_pw_wgrad(const void* a, const void* g, float* partial, int B, int T_g, int V, int K, int N,
                              int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int nsplit, const unsigned* a_amax,
-                             const unsigned* g_amax, void* stream) {
+                             const unsigned* g_amax, int half_mask, void* stream) {
+    if (int e = twgrad_mask("pw_wgrad", half_mask, a_amax, g_amax)) return e;
     FGCN_REQUIRE(a_s >= 1 && T_g > 0, FGCN_E_BADARG, "pw_wgrad: bad frame view");
-    return twgrad_launch(a, g, partial, B, T_g, V, K, N, ld_a, ld_g, T_a_full, a_s, a_o, T_g, fgcn_pw_wgrad_chunks(K, N), 1,
-                         0, 0, 1, 1, nsplit, a_amax, g_amax, stream, "pw_wgrad");
+    return twgrad_launch(static_cast<const float*>(a), static_cast<const float*>(g), partial, B, T_g, V, K, N, ld_a, ld_g, T_a_full, a_s, a_o,
+                         T_g, fgcn_pw_wgrad_chunks(K, N), 1, 0, 0, 1, 1, nsplit, a_amax, g_amax, stream, "pw_wgrad", half_mask == 3);
 }

@@ -240,13 +240,13 @@ def _chk(t: torch.Tensor, name: str) -> None:
 
 
 def _chk16(t: torch.Tensor, name: str) -> None:
-    """a half-precision-storage tensor (include/fgcn.h, the `_h` entry points): contiguous bfloat16 on the device"""
+    """a half-precision-storage tensor (include/fgcn.h, "storage types and half_mask"): contiguous bfloat16 on the device"""
     if not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous():
         raise _lib.FgcnError(f"{name}: expected a contiguous bfloat16 CUDA tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
 
 
 def _chka(t: Optional[torch.Tensor], name: str) -> bool:
-    """an activation tensor of a typed entry point (include/fgcn.h, `_t`): contiguous float32 or bfloat16 on the device -> whether it is
+    """an activation tensor of an entry point that takes `half_mask` (include/fgcn.h): contiguous float32 or bfloat16 on the device -> whether it is
     bfloat16 (half-precision activation storage, math mode bf16); None -> False"""
     if t is None:
         return False
@@ -260,7 +260,7 @@ def _chka(t: Optional[torch.Tensor], name: str) -> bool:
 
 
 def _half_mask(*flags: bool) -> int:
-    """`half_mask` of a typed entry point: bit i = the i-th activation tensor (in the entry point's order) is bfloat16"""
+    """`half_mask` of an entry point (include/fgcn.h): bit i = the i-th activation tensor (in the entry point's order) is bfloat16"""
     return sum(1 << i for i, f in enumerate(flags) if f)
 
 
@@ -284,7 +284,7 @@ def rows_gemm(inp: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, K: int, 
               in_coff: int = 0, out_coff: int = 0) -> Optional[torch.Tensor]:
     """out[..., out_coff:out_coff+N] (+)= conv(inp[..., in_coff:in_coff+K]); w packed (taps, K, N).
     Returns the (tiles, 2, N) statistics partials when ``stats``.  Math mode bf16: ``inp`` / ``out`` may be bfloat16 tensors
-    (half-precision activation storage, fgcn_rows_gemm_t; whole tensors, a bfloat16 ``out`` without accumulation)."""
+    (half-precision activation storage, `half_mask`; whole tensors, a bfloat16 ``out`` without accumulation)."""
     ensure_device()
     in16, out16 = _chka(inp, "rows_gemm.in"), _chka(out, "rows_gemm.out")
     _chk(w, "rows_gemm.w")
@@ -306,12 +306,8 @@ def rows_gemm(inp: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, K: int, 
     part = None
     if stats:
         part = torch.empty((lib.fgcn_rows_gemm_tiles(B * T_out * V), 2, N), device=inp.device, dtype=torch.float32)
-    if in16 or out16:
-        check(lib.fgcn_rows_gemm_t(inp.data_ptr(), out.data_ptr(), _p(w), _p(bias), _p(part), B, T_in, T_out, V, K, N, ld_in, ld_out, TMap(*tmap),
-                                   int(accumulate), _half_mask(in16, out16), _stream()), "fgcn_rows_gemm_t")
-        return part
     check(lib.fgcn_rows_gemm(_p(inp, in_coff), _p(out, out_coff), _p(w), _p(bias), _p(part), B, T_in, T_out, V, K, N,
-                             ld_in, ld_out, TMap(*tmap), int(accumulate), _stream()), "fgcn_rows_gemm")
+                             ld_in, ld_out, TMap(*tmap), int(accumulate), _half_mask(in16, out16), _stream()), "fgcn_rows_gemm")
     return part
 
 
@@ -382,14 +378,14 @@ def tconv_halo(inp: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, *, Th: in
     g = relu(inp * scale + shift + shortcut), formed while the image is staged; g and its sign image (``bn_act``'s layout) are
     written as by-products -- the block's ``bn_act`` pass in front of the conv folded into it (split-bf16 kernel, taps > 1)."""
     ensure_device()
-    in16 = inp.dtype == torch.bfloat16           # half-precision storage of the conv's input (math mode bf16: fgcn_tconv_halo_h)
+    in16 = inp.dtype == torch.bfloat16           # half-precision storage of the conv's input (math mode bf16: half_mask bit 0)
     if in16:
         _chk16(inp, "tconv_halo.in")
         if get_math_mode() != "bf16" or fuse_in is not None or amax_out is not None:
             raise _lib.FgcnError("tconv_halo: a bfloat16 input needs math mode bf16 and takes neither a fused input stage nor amax_out")
     else:
         _chk(inp, "tconv_halo.in")
-    out16 = _chka(out, "tconv_halo.out")         # half-precision ACTIVATION storage: the output as bfloat16 too (fgcn_tconv_halo_t)
+    out16 = _chka(out, "tconv_halo.out")         # half-precision ACTIVATION storage: the output as bfloat16 too (half_mask 3)
     if out16 and (not in16 or accumulate or bn_bwd is not None):
         raise _lib.FgcnError("tconv_halo: a bfloat16 output comes with a bfloat16 input, without accumulation or BatchNorm-backward sums")
     B, T_in, V, ld_in = inp.shape
@@ -431,19 +427,9 @@ def tconv_halo(inp: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, *, Th: in
             raise _lib.FgcnError("tconv_halo: fuse_in needs the (4, K) BatchNorm vector, a shortcut and an output like the input "
                                  "(contiguous, K channels) and the uint8 sign image of numel / 8 bytes")
         fin = (_p(vec), _p(res), _p(g), g_sign.data_ptr())
-    if out16:
-        check(lib.fgcn_tconv_halo_t(inp.data_ptr(), out.data_ptr(), w4.data_ptr(), _p(bias), _p(part), B, Th, V, K, N, ld_in, ld_out,
-                                    T_in, in_s, in_o, Th_in, T_out, out_s, out_o, taps, tb, tc, 3, _stream()), "fgcn_tconv_halo_t")
-        return part
-    if in16:
-        check(lib.fgcn_tconv_halo_h(inp.data_ptr(), _p(out), w4.data_ptr(), _p(bias), _p(part), B, Th, V, K, N, ld_in, ld_out,
-                                    T_in, in_s, in_o, Th_in, T_out, out_s, out_o, taps, tb, tc, int(accumulate), *bn, _stream()),
-              "fgcn_tconv_halo_h")
-        return part
     check(lib.fgcn_tconv_halo(_p(inp), _p(out), w4.data_ptr(), _p(bias), _p(part), B, Th, V, K, N, ld_in, ld_out,
                               T_in, in_s, in_o, Th_in, T_out, out_s, out_o, taps, tb, tc, int(accumulate), *bn, *fin,
-                              None if amax_out is None else amax_out.data_ptr(), _stream()),
-          "fgcn_tconv_halo")
+                              _p(amax_out), _half_mask(in16, out16), _stream()), "fgcn_tconv_halo")
     return part
 
 
@@ -512,7 +498,7 @@ def pw_gemm(inp: torch.Tensor, w3, out: torch.Tensor, *, bias: Optional[torch.Te
             accumulate: bool = False, amax_out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """1x1 convolution over all rows on the persistent split-bf16 row GEMM: inp (..., ld_in) and out (..., ld_out) contiguous with the
     same number of rows, w3 = pack_split3 of the (1, K, N) matrix.  Returns the BatchNorm partial sums (tiles, 2, N) when asked.
-    Math mode bf16: ``inp`` / ``out`` may be bfloat16 tensors (fgcn_pw_gemm_t; a bfloat16 ``out`` without accumulation)."""
+    Math mode bf16: ``inp`` / ``out`` may be bfloat16 tensors (`half_mask`; a bfloat16 ``out`` without accumulation)."""
     ensure_device()
     in16, out16 = _chka(inp, "pw_gemm.in"), _chka(out, "pw_gemm.out")
     if out16 and accumulate:
@@ -532,12 +518,8 @@ def pw_gemm(inp: torch.Tensor, w3, out: torch.Tensor, *, bias: Optional[torch.Te
         raise _lib.FgcnError(f"pw_gemm: shape mismatch in={tuple(inp.shape)} out={tuple(out.shape)} weights (K, N) = {(K, N)}")
     lib = _lib.load()
     part = torch.empty((lib.fgcn_pw_gemm_tiles(rows), 2, N), device=inp.device, dtype=torch.float32) if stats else None
-    if in16 or out16:
-        check(lib.fgcn_pw_gemm_t(inp.data_ptr(), out.data_ptr(), w3.data_ptr(), _p(bias), _p(part), rows, K, N, ld_in, ld_out, int(accumulate),
-                                 _half_mask(in16, out16), _stream()), "fgcn_pw_gemm_t")
-        return part
     check(lib.fgcn_pw_gemm(_p(inp), _p(out), w3.data_ptr(), _p(bias), _p(part), rows, K, N, ld_in, ld_out, int(accumulate),
-                           None if amax_out is None else amax_out.data_ptr(), _stream()), "fgcn_pw_gemm")
+                           _p(amax_out), _half_mask(in16, out16), _stream()), "fgcn_pw_gemm")
     return part
 
 
@@ -642,7 +624,7 @@ def rows_wgrad(a: torch.Tensor, g: torch.Tensor, *, K: int, N: int, tmap=TMAP_PO
     one-element int32 tensors in which ``tconv_halo`` / ``pw_gemm`` left the operands' largest magnitudes (math mode f16x2: the
     split kernel then forms its products from two-way f16 splits; without them it runs bf16x3)."""
     ensure_device()
-    a16, g16 = _chka(a, "rows_wgrad.a"), _chka(g, "rows_wgrad.g")      # math mode bf16: both bfloat16 (fgcn_pw_wgrad_h: the 1x1 form, K % 32 == 0)
+    a16, g16 = _chka(a, "rows_wgrad.a"), _chka(g, "rows_wgrad.g")      # math mode bf16: both bfloat16 (half_mask 3 of fgcn_pw_wgrad: the 1x1 form, K % 32 == 0)
     if a16 != g16 or (a16 and (a_coff or g_coff or amax is not None)):
         raise _lib.FgcnError("rows_wgrad: bfloat16 operands come as a pair, whole tensors")
     B, T_a, V, ld_a = a.shape
@@ -669,12 +651,8 @@ def rows_wgrad(a: torch.Tensor, g: torch.Tensor, *, K: int, N: int, tmap=TMAP_PO
         am = (None, None) if amax is None or a_coff or g_coff else (amax[0].data_ptr(), amax[1].data_ptr())
         if am[0] is not None and lib.fgcn_get_math_mode() == 2:
             check(lib.fgcn_set_products(1), "fgcn_set_products")   # (operand scales given: the f16x2 form of the split kernel)
-        if a16:
-            check(lib.fgcn_pw_wgrad_h(a.data_ptr(), g.data_ptr(), _p(partial), B, T_g, V, K, N, ld_a, ld_g, T_a, ta, 0, nsplit, _stream()),
-                  "fgcn_pw_wgrad_h")
-            return _reduce_slabs(partial.view(slabs, 1, K, N), 1, K, N, out, accumulate, conv_param)
         check(lib.fgcn_pw_wgrad(_p(a, a_coff), _p(g, g_coff), _p(partial), B, T_g, V, K, N, ld_a, ld_g, T_a, ta, 0,
-                                nsplit, *am, _stream()), "fgcn_pw_wgrad")
+                                nsplit, *am, _half_mask(a16, g16), _stream()), "fgcn_pw_wgrad")
         _mode_products()
         return _reduce_slabs(partial.view(slabs, 1, K, N), 1, K, N, out, accumulate, conv_param)
     if a16:
@@ -699,7 +677,7 @@ def tconv_wgrad(a: torch.Tensor, g: torch.Tensor, *, taps: int, stride: int = 1,
     a: (B, T_a, V, K) conv input, g: (B, T_g, V, N) gradient of the conv output.  ``all_taps`` False forces the
     per-tap kernel (measured slower: 105-107 vs 107-126 TFLOP/s at 64-256 channels, 111-113 for the strided ones)."""
     ensure_device()
-    in16 = a.dtype == torch.bfloat16 or g.dtype == torch.bfloat16     # half-precision storage of both operands (fgcn_tconv_wgrad_h)
+    in16 = a.dtype == torch.bfloat16 or g.dtype == torch.bfloat16     # half-precision storage of both operands (half_mask 3)
     if in16:
         _chk16(a, "tconv_wgrad.a"), _chk16(g, "tconv_wgrad.g")
         if get_math_mode() != "bf16" or amax is not None or all_taps is False:
@@ -733,17 +711,13 @@ def tconv_wgrad(a: torch.Tensor, g: torch.Tensor, *, taps: int, stride: int = 1,
     nsplit = max(1, min(cap, max(stages // WGRAD_MIN_STAGES, min(stages, max(1, 256 // max(tiles, 1))))))
     slabs = lib.fgcn_tconv_wgrad_slabs(N, nsplit)
     partial = torch.empty((slabs, taps, K, N), device=a.device, dtype=torch.float32)
+    am = (None, None) if amax is None else (amax[0].data_ptr(), amax[1].data_ptr())      # (bfloat16 operands: refused with amax above)
     for par, tap0, ntaps, shift0 in calls:
         th_a = (T_a - par + stride - 1) // stride
-        if in16:
-            check(lib.fgcn_tconv_wgrad_h(a.data_ptr(), g.data_ptr(), _p(partial), B, T_g, V, K, N, K, N, T_a, stride, par, th_a,
-                                         ntaps, shift0, tap0, stride, taps, nsplit, _stream()), "fgcn_tconv_wgrad_h")
-            continue
-        am = (None, None) if amax is None else (amax[0].data_ptr(), amax[1].data_ptr())
         if am[0] is not None and lib.fgcn_get_math_mode() == 2:
             check(lib.fgcn_set_products(1), "fgcn_set_products")   # (operand scales given: the f16x2 form of the split kernel)
         check(lib.fgcn_tconv_wgrad(_p(a), _p(g), _p(partial), B, T_g, V, K, N, K, N, T_a, stride, par, th_a,
-                                   ntaps, shift0, tap0, stride, taps, nsplit, *am, _stream()), "fgcn_tconv_wgrad")
+                                   ntaps, shift0, tap0, stride, taps, nsplit, *am, _half_mask(in16, in16), _stream()), "fgcn_tconv_wgrad")
     _mode_products()
     return _reduce_slabs(partial, taps, K, N, out, accumulate, conv_param)
 
@@ -930,14 +904,14 @@ def spatial_wgrad_tile(x: torch.Tensor, dy: torch.Tensor, mats: torch.Tensor, *,
     result layout.  x (B,T,V,ld_x), dy (B,T,V,ld_dy), mats (B or 1, 3, V, V); ``cin`` / ``cout``: the leading channels of wider
     rows that take part (default: all)."""
     ensure_device()
-    dy16 = dy.dtype == torch.bfloat16            # half-precision storage of dy (math mode bf16: fgcn_spatial_wgrad_tile_h)
+    dy16 = dy.dtype == torch.bfloat16            # half-precision storage of dy (math mode bf16: half_mask bit 1)
     if dy16:
         _chk16(dy, "spatial_wgrad_tile.dy")
         if get_math_mode() != "bf16":
             raise _lib.FgcnError("spatial_wgrad_tile: a bfloat16 dy needs math mode bf16")
     else:
         _chk(dy, "spatial_wgrad_tile.dy")
-    x16 = _chka(x, "spatial_wgrad_tile.x")        # half-precision activation storage (fgcn_spatial_wgrad_tile_t): with a bfloat16 dy
+    x16 = _chka(x, "spatial_wgrad_tile.x")        # half-precision activation storage (half_mask 3): with a bfloat16 dy
     _chk(mats, "spatial_wgrad_tile.mats")
     if x16 and not dy16:
         raise _lib.FgcnError("spatial_wgrad_tile: a bfloat16 x comes with a bfloat16 dy")
@@ -953,15 +927,8 @@ def spatial_wgrad_tile(x: torch.Tensor, dy: torch.Tensor, mats: torch.Tensor, *,
     if slabs <= 0:
         raise _lib.FgcnError(f"spatial_wgrad_tile: sizes not supported: V={V} Cin={Cin} Cout={Cout}")
     partial = torch.empty((slabs, 1, 3 * Cin, Cout), device=x.device, dtype=torch.float32)
-    if x16:
-        check(lib.fgcn_spatial_wgrad_tile_t(x.data_ptr(), dy.data_ptr(), _p(mats), _p(partial), B, T, V, Cin, Cout, ld_x, ld_dy,
-                                            int(mats.shape[0] != 1), 3, _stream()), "fgcn_spatial_wgrad_tile_t")
-    elif dy16:
-        check(lib.fgcn_spatial_wgrad_tile_h(_p(x), dy.data_ptr(), _p(mats), _p(partial), B, T, V, Cin, Cout, ld_x, ld_dy,
-                                            int(mats.shape[0] != 1), _stream()), "fgcn_spatial_wgrad_tile_h")
-    else:
-        check(lib.fgcn_spatial_wgrad_tile(_p(x), _p(dy), _p(mats), _p(partial), B, T, V, Cin, Cout, ld_x, ld_dy,
-                                          int(mats.shape[0] != 1), _stream()), "fgcn_spatial_wgrad_tile")
+    check(lib.fgcn_spatial_wgrad_tile(_p(x), _p(dy), _p(mats), _p(partial), B, T, V, Cin, Cout, ld_x, ld_dy,
+                                      int(mats.shape[0] != 1), _half_mask(x16, dy16), _stream()), "fgcn_spatial_wgrad_tile")
     return _reduce_slabs(partial, 1, 3 * Cin, Cout, out, accumulate, conv_param)
 
 
@@ -1059,9 +1026,9 @@ def bn_act(a: torch.Tensor, vec_a: torch.Tensor, b: Optional[torch.Tensor] = Non
            relu: bool = True, out: Optional[torch.Tensor] = None, sign_mask: bool = False, out_bf16: bool = False):
     """act(a*scale_a + shift_a + [b | b*scale_b + shift_b]).  ``sign_mask``: -> (out, mask) where mask holds one bit per
     element, [out > 0] (uint8, numel/8; None when the element count is not a multiple of 8) -- what the backward's
-    ReLU gate reads instead of ``out``.  ``out_bf16``: the result is stored as bfloat16 (round to nearest even; fgcn_bn_act_h) -- for a
+    ReLU gate reads instead of ``out``.  ``out_bf16``: the result is stored as bfloat16 (round to nearest even; half_mask bit 2) -- for a
     tensor that only the bf16 kernels' staging reads (math mode bf16: the temporal conv's input).  ``a`` / ``b`` may be bfloat16 tensors
-    themselves (half-precision activation storage, math mode bf16: fgcn_bn_act_t)."""
+    themselves (half-precision activation storage, math mode bf16: half_mask bits 0 and 1)."""
     ensure_device()
     a16, b16 = _chka(a, "bn_act.a"), _chka(b, "bn_act.b")
     C = a.shape[-1]
@@ -1074,17 +1041,10 @@ def bn_act(a: torch.Tensor, vec_a: torch.Tensor, b: Optional[torch.Tensor] = Non
     mask = None
     if sign_mask and relu and a.numel() % 8 == 0:
         mask = torch.empty(a.numel() // 8, device=a.device, dtype=torch.uint8)
-    if a16 or b16:
+    if a16 or b16 or out_bf16:
         (_chk16 if out_bf16 else _chk)(out, "bn_act.out")
-        check(_lib.load().fgcn_bn_act_t(a.data_ptr(), _p(vec_a), None if b is None else b.data_ptr(), _p(vec_b), out.data_ptr(), _p(mask), rows, C,
-                                        res_mode, int(relu), _half_mask(a16, b16, out_bf16), _stream()), "fgcn_bn_act_t")
-    elif out_bf16:
-        _chk16(out, "bn_act.out")
-        check(_lib.load().fgcn_bn_act_h(_p(a), _p(vec_a), _p(b), _p(vec_b), out.data_ptr(), _p(mask), rows, C, res_mode, int(relu),
-                                        _stream()), "fgcn_bn_act_h")
-    else:
-        check(_lib.load().fgcn_bn_act(_p(a), _p(vec_a), _p(b), _p(vec_b), _p(out), _p(mask), rows, C, res_mode, int(relu),
-                                      _stream()), "fgcn_bn_act")
+    check(_lib.load().fgcn_bn_act(_p(a), _p(vec_a), _p(b), _p(vec_b), _p(out), _p(mask), rows, C, res_mode, int(relu),
+                                  _half_mask(a16, b16, out_bf16), _stream()), "fgcn_bn_act")
     return (out, mask) if sign_mask else out
 
 
@@ -1093,7 +1053,7 @@ def bn_act_pool(a: torch.Tensor, vec_a: torch.Tensor, b: Optional[torch.Tensor],
     ``bn_act`` + ``group_mean`` of the last block without the activation between them (fgcn_bn_act_pool).  a: (..., C) whose rows
     form ``groups`` equal consecutive groups; C % 8 == 0."""
     ensure_device()
-    a16, b16 = _chka(a, "bn_act_pool.a"), _chka(b, "bn_act_pool.b")     # (bfloat16 operands: fgcn_bn_act_pool_t)
+    a16, b16 = _chka(a, "bn_act_pool.a"), _chka(b, "bn_act_pool.b")     # (bfloat16 operands: half_mask)
     C = a.shape[-1]
     rows = a.numel() // C
     if rows % groups or C % 8:
@@ -1106,12 +1066,8 @@ def bn_act_pool(a: torch.Tensor, vec_a: torch.Tensor, b: Optional[torch.Tensor],
     partial = torch.empty((groups * splits, C), device=a.device, dtype=torch.float32)
     pooled = torch.empty((groups, C), device=a.device, dtype=torch.float32)
     mask = torch.empty(a.numel() // 8, device=a.device, dtype=torch.uint8)
-    if a16 or b16:
-        check(lib.fgcn_bn_act_pool_t(a.data_ptr(), _p(vec_a), None if b is None else b.data_ptr(), _p(vec_b), _p(mask), _p(partial), _p(pooled),
-                                     groups, rows // groups, C, res_mode, _half_mask(a16, b16), _stream()), "fgcn_bn_act_pool_t")
-    else:
-        check(lib.fgcn_bn_act_pool(_p(a), _p(vec_a), _p(b), _p(vec_b), _p(mask), _p(partial), _p(pooled), groups, rows // groups, C,
-                                   res_mode, _stream()), "fgcn_bn_act_pool")
+    check(lib.fgcn_bn_act_pool(_p(a), _p(vec_a), _p(b), _p(vec_b), _p(mask), _p(partial), _p(pooled), groups, rows // groups, C,
+                               res_mode, _half_mask(a16, b16), _stream()), "fgcn_bn_act_pool")
     return pooled, mask
 
 
@@ -1121,12 +1077,12 @@ def bn_act_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], a: torch.Tensor,
                sign_mask: Optional[torch.Tensor] = None, need_sums: bool = True, need_db: bool = True,
                partials: Optional[torch.Tensor] = None, grp_rows: int = 0, da_bf16: bool = False, db_bf16: bool = False):
     """Backward of bn_act.  Returns (da, db, sums (3, C)): sums[0] = d beta, sums[1] = d gamma_a, sums[2] = d gamma_b.
-    ``da_bf16``: da is stored as bfloat16 (fgcn_bn_act_bwd_apply_h: the gradient of the temporal conv's output in math mode bf16).
+    ``da_bf16``: da is stored as bfloat16 (half_mask bit 3 of fgcn_bn_act_bwd_apply: the gradient of the temporal conv's output in math mode bf16).
     The ReLU gate is read from ``sign_mask`` (bn_act's bit image) when given, else from ``out``.  ``need_sums=False`` with
     ``train=False`` (no BatchNorm statistics in the graph: only the gate and the scale) skips the reduction pass.
     ``grp_rows`` > 0: ``dout`` is (rows / grp_rows, C), one row per group of consecutive rows -- the gradient of ``bn_act_pool``'s
     output, already divided by the group size -- instead of its rows x C broadcast.
-    ``dout`` / ``a`` / ``b`` may be bfloat16 tensors (half-precision activation storage, math mode bf16: the `_t` entry points; the gate
+    ``dout`` / ``a`` / ``b`` may be bfloat16 tensors (half-precision activation storage, math mode bf16: half_mask bits 0 to 2; the gate
     is then the sign image and a per-group ``dout`` stays float32); ``db_bf16``: a freshly allocated db (the shortcut branch's gradient) is
     bfloat16 too (typed operands, C % 8 == 0, no accumulation)."""
     ensure_device()
@@ -1142,6 +1098,7 @@ def bn_act_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], a: torch.Tensor,
     lib = _lib.load()
     if sign_mask is not None and (sign_mask.dtype != torch.uint8 or sign_mask.numel() * 8 != a.numel()):
         raise _lib.FgcnError("bn_act_bwd: sign_mask must be the uint8 bit image of bn_act (numel/8 bytes)")
+    gate_out = None if typed else _p(out)      # (bfloat16 tensors: the gate is the sign image, checked above)
     sums = None
     if partials is not None:            # the producer of dout already summed (tconv_halo bn_bwd): (tiles, 2, C) -> sums[0:2]
         if res_mode == 2 or partials.shape[1:] != (2, C):
@@ -1151,16 +1108,8 @@ def bn_act_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], a: torch.Tensor,
     elif need_sums or train:
         tiles = lib.fgcn_elem_tiles(rows)
         partials = torch.empty((tiles, 3, C), device=a.device, dtype=torch.float32)
-        if typed:
-            check(lib.fgcn_bn_act_bwd_reduce_t(dout.data_ptr(), grp_rows, None, _p(sign_mask), a.data_ptr(), _p(vec_a),
-                                               None if b is None else b.data_ptr(), _p(vec_b), _p(partials), tiles, rows, C, res_mode, int(relu),
-                                               _half_mask(d16, a16, b16), _stream()), "fgcn_bn_act_bwd_reduce_t")
-        elif grp_rows:
-            check(lib.fgcn_bn_act_bwd_reduce_g(_p(dout), grp_rows, _p(out), _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(partials),
-                                               tiles, rows, C, res_mode, int(relu), _stream()), "fgcn_bn_act_bwd_reduce_g")
-        else:
-            check(lib.fgcn_bn_act_bwd_reduce(_p(dout), _p(out), _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(partials),
-                                             tiles, rows, C, res_mode, int(relu), _stream()), "fgcn_bn_act_bwd_reduce")
+        check(lib.fgcn_bn_act_bwd_reduce(_p(dout), grp_rows, gate_out, _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(partials),
+                                         tiles, rows, C, res_mode, int(relu), _half_mask(d16, a16, b16), _stream()), "fgcn_bn_act_bwd_reduce")
         sums = torch.empty((3, C), device=a.device, dtype=torch.float32)
         reduce_sum(partials.view(tiles, -1), sums.view(-1))
     da = torch.empty_like(a, dtype=torch.bfloat16 if da_bf16 else torch.float32)
@@ -1170,23 +1119,9 @@ def bn_act_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], a: torch.Tensor,
         db = torch.empty_like(a, dtype=torch.bfloat16 if db16 else torch.float32)
     elif db is not None:
         _chk(db, "bn_act_bwd.db")
-    if typed:
-        check(lib.fgcn_bn_act_bwd_apply_t(dout.data_ptr(), grp_rows, None, _p(sign_mask), a.data_ptr(), _p(vec_a),
-                                          None if b is None else b.data_ptr(), _p(vec_b), _p(sums), da.data_ptr(), None if db is None else db.data_ptr(), rows, C, res_mode,
-                                          int(relu), int(train), int(db_accumulate), _half_mask(d16, a16, b16, da_bf16, db16), _stream()),
-              "fgcn_bn_act_bwd_apply_t")
-    elif da_bf16:
-        check(lib.fgcn_bn_act_bwd_apply_h(_p(dout), grp_rows, _p(out), _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(sums),
-                                          da.data_ptr(), _p(db), rows, C, res_mode, int(relu), int(train), int(db_accumulate), _stream()),
-              "fgcn_bn_act_bwd_apply_h")
-    elif grp_rows:
-        check(lib.fgcn_bn_act_bwd_apply_g(_p(dout), grp_rows, _p(out), _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(sums), _p(da),
-                                          _p(db), rows, C, res_mode, int(relu), int(train), int(db_accumulate), _stream()),
-              "fgcn_bn_act_bwd_apply_g")
-    else:
-        check(lib.fgcn_bn_act_bwd_apply(_p(dout), _p(out), _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(sums), _p(da),
-                                        _p(db), rows, C, res_mode, int(relu), int(train), int(db_accumulate), _stream()),
-              "fgcn_bn_act_bwd_apply")
+    check(lib.fgcn_bn_act_bwd_apply(_p(dout), grp_rows, gate_out, _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(sums), _p(da),
+                                    _p(db), rows, C, res_mode, int(relu), int(train), int(db_accumulate),
+                                    _half_mask(d16, a16, b16, da_bf16, db16), _stream()), "fgcn_bn_act_bwd_apply")
     return da, db, sums
 
 
@@ -1451,7 +1386,7 @@ def spatial_fwd_tile(x: torch.Tensor, a_hat: torch.Tensor, w3: torch.Tensor, bia
                      Cout: int, stats: bool = True, y_bf16: bool = False):
     """y = sum_k conv_d[k](x . A^_k), the tile form of the fused kernel (fgcn_spatial_tile.hip): w3 = ``pack_split3`` of the stacked
     (1, 3 Cin, Cout) matrix.  -> (y (B,T,V,Cout), stats partials or None).  Math mode bf16: ``x`` may be a bfloat16 tensor and ``y_bf16``
-    stores y as bfloat16 (half-precision activation storage, fgcn_spatial_fwd_tile_t; the statistics are those of the float32 accumulators)."""
+    stores y as bfloat16 (half-precision activation storage, `half_mask`; the statistics are those of the float32 accumulators)."""
     ensure_device()
     x16 = _chka(x, "spatial_fwd_tile.x")
     _chk(a_hat, "spatial_fwd_tile.a_hat")
@@ -1466,12 +1401,8 @@ def spatial_fwd_tile(x: torch.Tensor, a_hat: torch.Tensor, w3: torch.Tensor, bia
     _mode_products()
     y = torch.empty((B, T, V, Cout), device=x.device, dtype=torch.bfloat16 if y_bf16 else torch.float32)
     part = torch.empty((lib.fgcn_spatial_fwd_tile_tiles(B, T, V), 2, Cout), device=x.device, dtype=torch.float32) if stats else None
-    if y_bf16:
-        check(lib.fgcn_spatial_fwd_tile_t(x.data_ptr(), _p(a_hat), w3.data_ptr(), _p(bias_sum), y.data_ptr(), _p(part), B, T, V, Cin, Cout, ld_x,
-                                          Cout, int(a_hat.shape[0] == B), _half_mask(x16, True), _stream()), "fgcn_spatial_fwd_tile_t")
-        return y, part
     check(lib.fgcn_spatial_fwd_tile(_p(x), _p(a_hat), w3.data_ptr(), _p(bias_sum), _p(y), _p(part), B, T, V, Cin, Cout, ld_x, Cout,
-                                    int(a_hat.shape[0] == B), _stream()), "fgcn_spatial_fwd_tile")
+                                    int(a_hat.shape[0] == B), _half_mask(x16, y_bf16), _stream()), "fgcn_spatial_fwd_tile")
     return y, part
 
 
@@ -1489,7 +1420,7 @@ def spatial_bwd_tile(dy: torch.Tensor, x: torch.Tensor, a_hat: torch.Tensor, w3:
     (tensor, sign image) pairs added to dx where the image's bit is set (as in ``joint_dagg``; not with ``accumulate``).  The FIRST pair
     may carry a third member, the number of consecutive samples per group: its tensor is then (B / group, Cin), one row per group, added
     to every row of the group's samples (the gradient of a pooled block output, ``bn_act_pool``).
-    Math mode bf16, half-precision activation storage (fgcn_spatial_bwd_tile_t): x, dx and the gated addends bfloat16 TOGETHER (with a
+    Math mode bf16, half-precision activation storage (half_mask 3 / 7): x, dx and the gated addends bfloat16 TOGETHER (with a
     bfloat16 dy; a per-group first addend stays float32)."""
     ensure_device()
     if len(gated) not in (0, 2) or (gated and accumulate):
@@ -1504,7 +1435,7 @@ def spatial_bwd_tile(dy: torch.Tensor, x: torch.Tensor, a_hat: torch.Tensor, w3:
         if tuple(e.shape) != want or m.dtype != torch.uint8 or m.numel() * 8 != x.numel() or not m.is_cuda or (group and x.shape[0] % group):
             raise _lib.FgcnError(f"spatial_bwd_tile: gated addend {tuple(e.shape)} / image {m.numel()} bytes do not match x {tuple(x.shape)}")
     ex = [(e.data_ptr(), m.data_ptr()) for e, m, *_ in gated] + [(None, None)] * (2 - len(gated))
-    dy16 = dy.dtype == torch.bfloat16            # half-precision storage of dy (math mode bf16: fgcn_spatial_bwd_tile_h)
+    dy16 = dy.dtype == torch.bfloat16            # half-precision storage of dy (math mode bf16: half_mask bit 0)
     if dy16:
         _chk16(dy, "spatial_bwd_tile.dy")
         if get_math_mode() != "bf16":
@@ -1525,24 +1456,9 @@ def spatial_bwd_tile(dy: torch.Tensor, x: torch.Tensor, a_hat: torch.Tensor, w3:
     _mode_products()
     nseg = lib.fgcn_spatial_bwd_tile_segments(B, T, V)
     partial = torch.empty((B, max(nseg, 1), 3, 32, 32), device=x.device, dtype=torch.float32)
-    if x16:
-        check(lib.fgcn_spatial_bwd_tile_t(dy.data_ptr(), x.data_ptr(), _p(a_hat), w3.data_ptr(), dx.data_ptr(), _p(partial), B, T, V, Cin, Cout, Cout,
-                                          Cin, dx.shape[3], int(a_hat.shape[0] == B), int(accumulate), ex[0][0], group, ex[0][1], ex[1][0], ex[1][1],
-                                          7 if all16 else 3, _stream()), "fgcn_spatial_bwd_tile_t")
-        return partial
-    if dy16:
-        check(lib.fgcn_spatial_bwd_tile_h(dy.data_ptr(), _p(x), _p(a_hat), w3.data_ptr(), _p(dx), _p(partial), B, T, V, Cin, Cout, Cout, Cin,
-                                          dx.shape[3], int(a_hat.shape[0] == B), int(accumulate), ex[0][0], group, ex[0][1], ex[1][0], ex[1][1],
-                                          _stream()), "fgcn_spatial_bwd_tile_h")
-        return partial
-    if group:
-        check(lib.fgcn_spatial_bwd_tile_g(_p(dy), _p(x), _p(a_hat), w3.data_ptr(), _p(dx), _p(partial), B, T, V, Cin, Cout, Cout, Cin,
-                                          dx.shape[3], int(a_hat.shape[0] == B), ex[0][0], group, ex[0][1], ex[1][0], ex[1][1], _stream()),
-              "fgcn_spatial_bwd_tile_g")
-        return partial
     check(lib.fgcn_spatial_bwd_tile(_p(dy), _p(x), _p(a_hat), w3.data_ptr(), _p(dx), _p(partial), B, T, V, Cin, Cout, Cout, Cin,
-                                    dx.shape[3], int(a_hat.shape[0] == B), int(accumulate), ex[0][0], ex[0][1], ex[1][0], ex[1][1], _stream()),
-          "fgcn_spatial_bwd_tile")
+                                    dx.shape[3], int(a_hat.shape[0] == B), int(accumulate), ex[0][0], group, ex[0][1], ex[1][0], ex[1][1],
+                                    _half_mask(dy16, x16, all16), _stream()), "fgcn_spatial_bwd_tile")
     return partial
 
 
@@ -1556,9 +1472,9 @@ def emb_fwd_tile(x: torch.Tensor, w3: torch.Tensor, bias: torch.Tensor, *, ic: i
     """-> (emb (B,T,V,6 ic) = x . Wemb + bias, partial (B, segments, 3, 32, 32) of the affinity grams theta_k^T phi_k) in one launch
     (fgcn_emb_fwd_tile.hip; agcn.py:104-106).  w3 = ``pack_split3`` of the (1, cin, 6 ic) matrix; ``partial`` goes to ``adj_softmax_fwd``.
     ``write_emb=False`` (inference: only the backward reads the embeddings): emb is not written and None comes back in its place.
-    ``emb_bf16`` (math mode bf16): emb is stored as bfloat16 (fgcn_emb_fwd_tile_h; its readers ``emb_dx_tile`` / ``emb_wgrad_tile`` take it)."""
+    ``emb_bf16`` (math mode bf16): emb is stored as bfloat16 (half_mask bit 1; its readers ``emb_dx_tile`` / ``emb_wgrad_tile`` take it)."""
     ensure_device()
-    x16 = _chka(x, "emb_fwd_tile.x")              # half-precision activation storage (math mode bf16: fgcn_emb_fwd_tile_t)
+    x16 = _chka(x, "emb_fwd_tile.x")              # half-precision activation storage (math mode bf16: half_mask bit 0)
     _chk(bias, "emb_fwd_tile.bias")
     B, T, V, ld_x = x.shape
     cin = ld_x if cin is None else int(cin)
@@ -1571,20 +1487,10 @@ def emb_fwd_tile(x: torch.Tensor, w3: torch.Tensor, bias: torch.Tensor, *, ic: i
     if nseg <= 0:
         raise _lib.FgcnError(f"emb_fwd_tile: sizes not supported: V={V} ic={ic}")
     partial = torch.empty((B, nseg, 3, 32, 32), device=x.device, dtype=torch.float32)
-    if x16:
-        e16 = bool(emb_bf16 and write_emb)
-        emb = torch.empty((B, T, V, 6 * ic), device=x.device, dtype=torch.bfloat16 if e16 else torch.float32) if write_emb else None
-        check(lib.fgcn_emb_fwd_tile_t(x.data_ptr(), w3.data_ptr(), _p(bias), None if emb is None else emb.data_ptr(), _p(partial), B, T, V, cin, ic,
-                                      ld_x, 6 * ic, _half_mask(True, e16), _stream()), "fgcn_emb_fwd_tile_t")
-        return emb, partial
-    if emb_bf16 and write_emb:
-        emb = torch.empty((B, T, V, 6 * ic), device=x.device, dtype=torch.bfloat16)
-        check(lib.fgcn_emb_fwd_tile_h(_p(x), w3.data_ptr(), _p(bias), emb.data_ptr(), _p(partial), B, T, V, cin, ic, ld_x, 6 * ic, _stream()),
-              "fgcn_emb_fwd_tile_h")
-        return emb, partial
-    emb = torch.empty((B, T, V, 6 * ic), device=x.device, dtype=torch.float32) if write_emb else None
-    check(lib.fgcn_emb_fwd_tile(_p(x), w3.data_ptr(), _p(bias), _p(emb), _p(partial), B, T, V, cin, ic, ld_x, 6 * ic, _stream()),
-          "fgcn_emb_fwd_tile")
+    e16 = bool(emb_bf16 and write_emb)
+    emb = torch.empty((B, T, V, 6 * ic), device=x.device, dtype=torch.bfloat16 if e16 else torch.float32) if write_emb else None
+    check(lib.fgcn_emb_fwd_tile(_p(x), w3.data_ptr(), _p(bias), _p(emb), _p(partial), B, T, V, cin, ic, ld_x, 6 * ic, _half_mask(x16, e16),
+                                _stream()), "fgcn_emb_fwd_tile")
     return emb, partial
 
 
@@ -1595,7 +1501,7 @@ def emb_tile_available(V: int, ic: int, cx: int) -> bool:
 
 
 def _chk_emb(name: str, emb: torch.Tensor, d_s: torch.Tensor, ic: int) -> None:
-    if emb.dtype == torch.bfloat16:       # half-precision storage (math mode bf16: the `_h` entry points)
+    if emb.dtype == torch.bfloat16:       # half-precision storage (math mode bf16: half_mask bit 0)
         _chk16(emb, f"{name}.emb")
         if get_math_mode() != "bf16":
             raise _lib.FgcnError(f"{name}: a bfloat16 emb needs math mode bf16")
@@ -1614,7 +1520,7 @@ def emb_dx_tile(emb: torch.Tensor, d_s: torch.Tensor, w3: torch.Tensor, dx: torc
     w3 = ``pack_split3`` of the (1, 6 ic, cx) matrix [j][c] = Wemb[j][c], dx (B,T,V,>=cx)."""
     ensure_device()
     _chk_emb("emb_dx_tile", emb, d_s, ic)
-    dx16 = _chka(dx, "emb_dx_tile.dx")            # half-precision activation storage (fgcn_emb_dx_tile_t): with a bfloat16 emb
+    dx16 = _chka(dx, "emb_dx_tile.dx")            # half-precision activation storage (half_mask 3): with a bfloat16 emb
     if dx16 and emb.dtype != torch.bfloat16:
         raise _lib.FgcnError("emb_dx_tile: a bfloat16 dx comes with a bfloat16 emb")
     B, T, V, ld_e = emb.shape
@@ -1630,16 +1536,8 @@ def emb_dx_tile(emb: torch.Tensor, d_s: torch.Tensor, w3: torch.Tensor, dx: torc
         _chk(dx_old, "emb_dx_tile.dx_old")
         if not (dx16 and accumulate) or tuple(dx_old.shape) != tuple(dx.shape):
             raise _lib.FgcnError("emb_dx_tile: dx_old (float32, dx's shape) comes with a bfloat16 dx and accumulate=True")
-    if dx16:
-        check(lib.fgcn_emb_dx_tile_t(emb.data_ptr(), _p(d_s), w3.data_ptr(), dx.data_ptr(), ws.data_ptr(), B, T, V, ic, cx, ld_e, dx.shape[3], batched,
-                                     int(accumulate), _p(dx_old), 3, _stream()), "fgcn_emb_dx_tile_t")
-        return dx
-    if emb.dtype == torch.bfloat16:
-        check(lib.fgcn_emb_dx_tile_h(emb.data_ptr(), _p(d_s), w3.data_ptr(), _p(dx), ws.data_ptr(), B, T, V, ic, cx, ld_e, dx.shape[3], batched,
-                                     int(accumulate), _stream()), "fgcn_emb_dx_tile_h")
-        return dx
     check(lib.fgcn_emb_dx_tile(_p(emb), _p(d_s), w3.data_ptr(), _p(dx), ws.data_ptr(), B, T, V, ic, cx, ld_e, dx.shape[3], batched,
-                               int(accumulate), _stream()), "fgcn_emb_dx_tile")
+                               int(accumulate), _p(dx_old), _half_mask(emb.dtype == torch.bfloat16, dx16), _stream()), "fgcn_emb_dx_tile")
     return dx
 
 
@@ -1648,7 +1546,7 @@ def emb_wgrad_tile(emb: torch.Tensor, x: torch.Tensor, d_s: torch.Tensor, *, ic:
     (see ``emb_dx_tile``).  x (B,T,V,>=cx): the embedding convolutions' input."""
     ensure_device()
     _chk_emb("emb_wgrad_tile", emb, d_s, ic)
-    x16 = _chka(x, "emb_wgrad_tile.x")            # half-precision activation storage (fgcn_emb_wgrad_tile_t): with a bfloat16 emb
+    x16 = _chka(x, "emb_wgrad_tile.x")            # half-precision activation storage (half_mask 3): with a bfloat16 emb
     if x16 and emb.dtype != torch.bfloat16:
         raise _lib.FgcnError("emb_wgrad_tile: a bfloat16 x comes with a bfloat16 emb")
     B, T, V, ld_e = emb.shape
@@ -1661,15 +1559,8 @@ def emb_wgrad_tile(emb: torch.Tensor, x: torch.Tensor, d_s: torch.Tensor, *, ic:
         raise _lib.FgcnError(f"emb_wgrad_tile: sizes not supported: V={V} ic={ic} cx={cx}")
     partial = torch.empty((slabs, 1, 6 * ic, cx), device=x.device, dtype=torch.float32)
     bpart = torch.empty((slabs, 6 * ic), device=x.device, dtype=torch.float32)
-    if x16:
-        check(lib.fgcn_emb_wgrad_tile_t(emb.data_ptr(), x.data_ptr(), _p(d_s), _p(partial), _p(bpart), B, T, V, ic, cx, ld_e, x.shape[3],
-                                        int(d_s.shape[0] != 1), 3, _stream()), "fgcn_emb_wgrad_tile_t")
-    elif emb.dtype == torch.bfloat16:
-        check(lib.fgcn_emb_wgrad_tile_h(emb.data_ptr(), _p(x), _p(d_s), _p(partial), _p(bpart), B, T, V, ic, cx, ld_e, x.shape[3],
-                                        int(d_s.shape[0] != 1), _stream()), "fgcn_emb_wgrad_tile_h")
-    else:
-        check(lib.fgcn_emb_wgrad_tile(_p(emb), _p(x), _p(d_s), _p(partial), _p(bpart), B, T, V, ic, cx, ld_e, x.shape[3],
-                                      int(d_s.shape[0] != 1), _stream()), "fgcn_emb_wgrad_tile")
+    check(lib.fgcn_emb_wgrad_tile(_p(emb), _p(x), _p(d_s), _p(partial), _p(bpart), B, T, V, ic, cx, ld_e, x.shape[3],
+                                  int(d_s.shape[0] != 1), _half_mask(emb.dtype == torch.bfloat16, x16), _stream()), "fgcn_emb_wgrad_tile")
     gw = _reduce_slabs(partial, 1, 6 * ic, cx, None, False, None)[0]
     gb = torch.empty((6 * ic,), device=x.device, dtype=torch.float32)
     reduce_sum(bpart, gb, leaf=True)
@@ -1899,6 +1790,6 @@ def col_moments(x: torch.Tensor) -> torch.Tensor:
         vec[1:3] = 1.0
         _identity_vecs[key] = vec
     partials = torch.empty((tiles, 3, C), device=x.device, dtype=torch.float32)
-    check(lib.fgcn_bn_act_bwd_reduce(_p(x), None, None, _p(x), _p(vec), None, None, _p(partials), tiles, rows, C, 0, 0, _stream()),
+    check(lib.fgcn_bn_act_bwd_reduce(_p(x), 0, None, None, _p(x), _p(vec), None, None, _p(partials), tiles, rows, C, 0, 0, 0, _stream()),
           "fgcn_bn_act_bwd_reduce")
     return partials[:, :2].contiguous()

@@ -79,7 +79,7 @@ class PathOptions:
     emb_fwd_tile_max_ic: Dict[str, int] = field(default_factory=lambda: {"f32": 32, "bf16": 64, "bf16x3": 32, "f16x2": 32})
     # -- math mode bf16 (BASELINE config 5): half-precision STORAGE of the tensors that only bf16 MFMA staging reads -- G (the temporal conv's
     # input), dU (the gradient of its output) and dY (the gradient of the spatial stage's output) are written as bfloat16 by the BatchNorm
-    # passes that produce them and copied by their consumers (include/fgcn.h, the `_h` entry points).  Bit-identical to f32 storage (the bf16 kernels round these tensors to bfloat16
+    # passes that produce them and copied by their consumers (include/fgcn.h, "storage types and half_mask": output bits of the producers).  Bit-identical to f32 storage (the bf16 kernels round these tensors to bfloat16
     # when they stage them anyway); the halo conv, bound by its row traffic through L2 in this mode, moves half of it
     # (probe: 34.38 -> 32.9 ms from the conv's input alone, profiles/r06_ab_bf16_half_storage.txt).  Only the mode's own entry counts.
     half_storage: Dict[str, bool] = field(default_factory=lambda: {"f32": False, "bf16": True, "bf16x3": False, "f16x2": False})
@@ -87,7 +87,7 @@ class PathOptions:
     # outputs Y / U, the block boundary x / O and its gradient, dG -- as the reference's autocast step keeps them (session/procedures/step.py:
     # 55-78); BatchNorm statistics, softmax, accumulators stay float32.  Unlike half_storage this changes VALUES (one more rounding per
     # stored tensor): SURVEY.md section 7's contract instead of bit-identity (tests/test_bf16_gpu.py; tools/probes/half_act_probe.py: logits
-    # 2.3e-3 -> 2.2e-3, gradient cosine 0.9977 -> 0.9972 against the float32 path).  The typed `_t` entry points of include/fgcn.h.
+    # 2.3e-3 -> 2.2e-3, gradient cosine 0.9977 -> 0.9972 against the float32 path).  The `half_mask` input and output bits of include/fgcn.h.
     half_activations: Dict[str, bool] = field(default_factory=lambda: {"f32": False, "bf16": True, "bf16x3": False, "f16x2": False})
     # ... per producer (A/B switches inside half_activations): the temporal conv's output U, the spatial tile kernel's output Y
     half_conv_out: bool = True

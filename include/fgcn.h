@@ -8,7 +8,7 @@
  *
  * Conventions
  *   - plain C types only: device pointers, sizes, a hipStream_t passed as void*.
- *   - activations are float32, channels-last: element (n, t, v, c) of a tensor with row stride `ld`
+ *   - activations are float32 (bfloat16 where a `half_mask` says so, see "storage types and half_mask"), channels-last: element (n, t, v, c) of a tensor with row stride `ld`
  *     lives at base[((n*T + t)*V + v)*ld + c].  `ld` and every channel offset are multiples of 4 floats
  *     and every base pointer is 16-byte aligned.
  *   - the caller owns every buffer (outputs, workspaces, partial-sum scratch); the library allocates nothing,
@@ -135,10 +135,10 @@ typedef struct {
  *   w is packed [taps][K][N] (N contiguous, N % 4 == 0).  bias may be NULL.
  *   stat_partials (may be NULL): float[ceil(M/128)][2][N] receives per-row-tile sum and sum of squares of the
  *   values written (the BatchNorm batch statistics of agcn.py:44,78,83 come from these).  accumulate: out += .
- *   At most 2^29 rows (B * T_out * V) per call. */
-int fgcn_rows_gemm(const float* in, float* out, const float* w, const float* bias, float* stat_partials,
+ *   At most 2^29 rows (B * T_out * V) per call.  half_mask: "storage types and half_mask" below. */
+int fgcn_rows_gemm(const void* in, void* out, const float* w, const float* bias, float* stat_partials,
                    int B, int T_in, int T_out, int V, int K, int N, int ld_in, int ld_out,
-                   fgcn_tmap map, int accumulate, void* stream);
+                   fgcn_tmap map, int accumulate, int half_mask, void* stream);
 /* `batch` independent problems out_b[rows x N] (+)= in_b[rows x K] . w_b[K x N] in one launch (one per blockIdx.z): problem b
  * reads in + b*in_bstride, w + b*w_bstride and writes out + b*out_bstride (strides in floats, multiples of 4; row strides
  * ld_in / ld_out as above).  The per-sample V x V products of AGCNGraphConvolution on IMU graphs
@@ -185,111 +185,39 @@ int fgcn_spatial_fwd_tile_bn_relu(const float* x, const float* a_hat, const void
                                   const float* bn_vec, const float* res, int ld_res, const float* res_vec,
                                   int B, int T, int V, int Cin, int Cout, int ld_x, int ld_g, int a_hat_batched, void* stream);
 
-/* ---- half-precision STORAGE of the temporal convolution's operands (math mode FGCN_MATH_BF16 only; round 6) -----------------------------
- * The reference's MixedPrecisionStep (torch_src/session/procedures/step.py:55-78, autocast) keeps conv inputs in half precision.  In
- * FGCN_MATH_BF16 the matrix kernels round their f32 inputs to bfloat16 (to nearest even) as they stage them; for the two tensors that
- * ONLY such staging reads -- G, the temporal conv's input (fgcn_bn_act), and dU, the gradient of its output (fgcn_bn_act_bwd_apply) --
- * the producer can write the bfloat16 values directly: the consumers copy instead of convert and move half the bytes, and every result
- * is BIT-IDENTICAL to the f32-storage form (one rounding per value either way).  `_h` entry points take / write `unsigned short`
- * (bfloat16 bit patterns), contiguous (rows, C); everything else is as in the entry point without the suffix. */
-int fgcn_bn_act_h(const float* a, const float* vec_a, const float* b, const float* vec_b, unsigned short* out_h,
-                  unsigned char* sign_mask, long long rows, int C, int res_mode, int relu, void* stream);
-/* grp_rows >= 0 (0: dout is (rows, C); > 0: one row per group, as fgcn_bn_act_bwd_apply_g) */
-int fgcn_bn_act_bwd_apply_h(const float* dout, int grp_rows, const float* out, const unsigned char* sign_mask,
-                            const float* a, const float* vec_a, const float* b, const float* vec_b,
-                            const float* sums, unsigned short* da_h, float* db,
-                            long long rows, int C, int res_mode, int relu, int train, int db_accumulate, void* stream);
-/* fgcn_tconv_halo with a bfloat16 input tensor (ld_in in elements; the tap form, no fused input stage) */
-int fgcn_tconv_halo_h(const unsigned short* in_h, float* out, const float* w4, const float* bias, float* stat_partials,
-                      int B, int Th, int V, int K, int N, int ld_in, int ld_out,
-                      int T_in_full, int in_s, int in_o, int Th_in,
-                      int T_out_full, int out_s, int out_o,
-                      int taps, int tb, int tc, int accumulate, const float* bn_a, const unsigned char* bn_mask,
-                      const float* bn_vec, void* stream);
-/* fgcn_tconv_wgrad with bfloat16 tensors a and g (ld_a / ld_g in elements) */
-int fgcn_tconv_wgrad_h(const unsigned short* a_h, const unsigned short* g_h, float* partial, int B, int T_g, int V, int K, int N,
-                       int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int Th_a,
-                       int ntaps, int shift0, int tap0, int tap_step, int taps_total, int nsplit, void* stream);
-/* fgcn_pw_wgrad (the 1x1 weight gradient, channel chunks) with bfloat16 tensors a and g */
-int fgcn_pw_wgrad_h(const unsigned short* a_h, const unsigned short* g_h, float* partial, int B, int T_g, int V, int K, int N,
-                    int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int nsplit, void* stream);
-/* ... and of dY, the gradient of the spatial stage's output (written by fgcn_bn_act_bwd_apply_h; read only by the staging of the two tile
- * kernels of the spatial backward): fgcn_spatial_bwd_tile / _g (extra1_group = 0: the plain form) and fgcn_spatial_wgrad_tile with dy as
- * bfloat16 (ld_dy in elements) */
-int fgcn_spatial_bwd_tile_h(const unsigned short* dy_h, const float* x, const float* a_hat, const void* w3, float* dx, float* partial,
-                            int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched, int accumulate,
-                            const float* extra1, int extra1_group, const unsigned char* mask1, const float* extra2,
-                            const unsigned char* mask2, void* stream);
-int fgcn_spatial_wgrad_tile_h(const float* x, const unsigned short* dy_h, const float* a_hat, float* partial, int B, int T, int V,
-                              int Cin, int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream);
-/* ... and of emb, the attention embeddings (1.5 activations wide; written by fgcn_emb_fwd_tile, whose own gram reads the tile on chip; read
- * only by the operand fetches of the two tile kernels of the embedding backward): ld_e in elements */
-int fgcn_emb_fwd_tile_h(const float* x, const void* w3, const float* bias, unsigned short* emb_h, float* partial, int B, int T, int V,
-                        int Cin, int ic, int ld_x, int ld_e, void* stream);
-int fgcn_emb_dx_tile_h(const unsigned short* emb_h, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V,
-                       int ic, int Cx, int ld_e, int ld_dx, int d_s_batched, int accumulate, void* stream);
-int fgcn_emb_wgrad_tile_h(const unsigned short* emb_h, const float* x, const float* d_s, float* partial, float* bias_partial, int B,
-                          int T, int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, void* stream);
-/* ---- half-precision ACTIVATION storage (math mode FGCN_MATH_BF16 only; round 6): the typed entry points `_t` ---------------------------
- * The `_h` entry points above keep results bit-identical (only tensors that bf16 MFMA staging alone reads are bfloat16).  The reference's
- * MixedPrecisionStep (torch_src/session/procedures/step.py:55-78: torch.cuda.amp.autocast around model(x)) goes further: under autocast every
- * convolution / matmul OUTPUT is a half-precision tensor and BatchNorm / ReLU / the residual adds read and write half precision too; only
- * statistics, softmax and accumulators are float32.  The `_t` entry points give the hot path that storage format: each takes `half_mask`,
- * one bit per activation-sized tensor argument in argument order (set = the tensor is bfloat16, `unsigned short` bit patterns, strides in
- * elements); accumulation, BatchNorm statistics (summed from the float32 accumulators, before the rounding of the stored value) and every
- * small tensor stay float32.  A bfloat16 INPUT of a matrix kernel changes nothing (the FGCN_MATH_BF16 kernels round their operands to
- * bfloat16 anyway: same staged bytes); a bfloat16 OUTPUT is the float32 result rounded to nearest even once.  Masks a kernel is not built for
- * are refused with FGCN_E_BADARG.  Contract of the mode: SURVEY.md section 7 (logits <= 1e-2, loss <= 1e-3 abs ..., gradient cosine >= 0.98).
- *   fgcn_bn_act_t             bit 0 a, 1 b (shortcut), 2 out
- *   fgcn_bn_act_pool_t        bit 0 a, 1 b
- *   fgcn_bn_act_bwd_reduce_t  bit 0 dout, 1 a, 2 b          (grp_rows > 0: dout is the float32 per-group form; the ReLU gate is the sign image)
- *   fgcn_bn_act_bwd_apply_t   bit 0 dout, 1 a, 2 b, 3 da, 4 db  (a bfloat16 db: C % 8 == 0, not accumulating)
- *   fgcn_tconv_halo_t         bit 0 in, 1 out               masks 0, 1, 3; plain store epilogue (no accumulation / BatchNorm-backward sums)
- *   fgcn_spatial_fwd_tile_t   bit 0 x, 1 y                  masks 0, 2, 3
- *   fgcn_emb_fwd_tile_t       bit 0 x, 1 emb
- *   fgcn_spatial_bwd_tile_t   bit 0 dy, 1 x, 2 dx + gated addends (a per-group extra1 stays float32)     masks 0, 1, 3, 7
- *   fgcn_spatial_wgrad_tile_t bit 0 x, 1 dy                 masks 0, 2, 3
- *   fgcn_emb_dx_tile_t        bit 0 emb, 1 dx               masks 0, 1, 3
- *   fgcn_emb_wgrad_tile_t     bit 0 emb, 1 x                masks 0, 1, 3
- *   fgcn_rows_gemm_t          bit 0 in, 1 out               (a bfloat16 out: no accumulation; a single problem)
- *   fgcn_pw_gemm_t            bit 0 in, 1 out               (a bfloat16 out: no accumulation) */
-int fgcn_bn_act_t(const void* a, const float* vec_a, const void* b, const float* vec_b, void* out, unsigned char* sign_mask,
-                  long long rows, int C, int res_mode, int relu, int half_mask, void* stream);
-int fgcn_bn_act_pool_t(const void* a, const float* vec_a, const void* b, const float* vec_b, unsigned char* sign_mask,
-                       float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, int half_mask, void* stream);
-int fgcn_bn_act_bwd_reduce_t(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
-                             const float* vec_a, const void* b, const float* vec_b, float* partials, int n_tiles, long long rows,
-                             int C, int res_mode, int relu, int half_mask, void* stream);
-int fgcn_bn_act_bwd_apply_t(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
-                            const float* vec_a, const void* b, const float* vec_b, const float* sums, void* da, void* db,
-                            long long rows, int C, int res_mode, int relu, int train, int db_accumulate, int half_mask, void* stream);
-int fgcn_tconv_halo_t(const void* in, void* out, const float* w4, const float* bias, float* stat_partials,
-                      int B, int Th, int V, int K, int N, int ld_in, int ld_out,
-                      int T_in_full, int in_s, int in_o, int Th_in,
-                      int T_out_full, int out_s, int out_o,
-                      int taps, int tb, int tc, int half_mask, void* stream);
-int fgcn_spatial_fwd_tile_t(const void* x, const float* a_hat, const void* w3, const float* bias_sum, void* y,
-                            float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
-                            int a_hat_batched, int half_mask, void* stream);
-int fgcn_emb_fwd_tile_t(const void* x, const void* w3, const float* bias, void* emb, float* partial, int B, int T, int V, int Cin,
-                        int ic, int ld_x, int ld_e, int half_mask, void* stream);
-int fgcn_spatial_bwd_tile_t(const void* dy, const void* x, const float* a_hat, const void* w3, void* dx, float* partial,
-                            int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched, int accumulate,
-                            const void* extra1, int extra1_group, const unsigned char* mask1, const void* extra2,
-                            const unsigned char* mask2, int half_mask, void* stream);
-int fgcn_spatial_wgrad_tile_t(const void* x, const void* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
-                              int Cout, int ld_x, int ld_dy, int a_hat_batched, int half_mask, void* stream);
-/* dx_old (mask 3, accumulate; or NULL): the float32 tensor that holds the values to add to -- dx = bfloat16(dx_old + term) is then only written */
-int fgcn_emb_dx_tile_t(const void* emb, const float* d_s, const void* w3, void* dx, void* workspace, int B, int T, int V,
-                       int ic, int Cx, int ld_e, int ld_dx, int d_s_batched, int accumulate, const float* dx_old, int half_mask,
-                       void* stream);
-int fgcn_emb_wgrad_tile_t(const void* emb, const void* x, const float* d_s, float* partial, float* bias_partial, int B,
-                          int T, int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, int half_mask, void* stream);
-int fgcn_rows_gemm_t(const void* in, void* out, const float* w, const float* bias, float* stat_partials,
-                     int B, int T_in, int T_out, int V, int K, int N, int ld_in, int ld_out,
-                     fgcn_tmap map, int accumulate, int half_mask, void* stream);
-int fgcn_pw_gemm_t(const void* in, void* out, const void* w3, const float* bias, float* stat_partials, long long rows,
-                   int K, int N, int ld_in, int ld_out, int accumulate, int half_mask, void* stream);
+/* ---- storage types and `half_mask` (bfloat16 tensors: math mode FGCN_MATH_BF16 only; round 6) ------------------------------------------------
+ * The reference's MixedPrecisionStep (torch_src/session/procedures/step.py:55-78: torch.cuda.amp.autocast around model(x)) keeps activations in
+ * half precision: every convolution / matmul OUTPUT is a half-precision tensor and BatchNorm / ReLU / the residual adds read and write half
+ * precision too; only statistics, softmax and accumulators are float32.  The fifteen entry points of the table take `half_mask`, immediately
+ * before `stream`: one bit per activation-sized tensor argument, in argument order (set = the tensor is bfloat16, `unsigned short` bit patterns,
+ * contiguous, strides in elements; those arguments are `void*`).  Mask 0 = all float32, valid in every math mode; any other mask needs
+ * FGCN_MATH_BF16.  Accumulation, BatchNorm statistics (summed from the float32 accumulators, before the rounding of the stored value) and
+ * every small tensor stay float32.
+ *   A bfloat16 INPUT of a matrix kernel changes nothing: the FGCN_MATH_BF16 kernels round their f32 operands to bfloat16 (to nearest even) as
+ *   they stage them, so a producer that writes the bfloat16 values directly -- G, the temporal conv's input (fgcn_bn_act, mask 4); dU, the
+ *   gradient of its output, and dY, that of the spatial stage's (fgcn_bn_act_bwd_apply, mask 8); emb, the attention embeddings
+ *   (fgcn_emb_fwd_tile, mask 2) -- leaves every result BIT-IDENTICAL to the f32-storage form (one rounding per value either way) while the
+ *   consumers copy instead of convert and move half the bytes.
+ *   A bfloat16 OUTPUT is the float32 result rounded to nearest even once.  Contract of the mode with half-precision activations: SURVEY.md
+ *   section 7 (logits <= 1e-2, loss <= 1e-3 abs ..., gradient cosine >= 0.98).
+ * Masks a kernel is not built for are refused with FGCN_E_BADARG before any launch.
+ *   fgcn_bn_act             bit 0 a, 1 b (shortcut), 2 out
+ *   fgcn_bn_act_pool        bit 0 a, 1 b
+ *   fgcn_bn_act_bwd_reduce  bit 0 dout, 1 a, 2 b          (grp_rows > 0: dout is the float32 per-group form; the ReLU gate is the sign image)
+ *   fgcn_bn_act_bwd_apply   bit 0 dout, 1 a, 2 b, 3 da, 4 db  (a bfloat16 db: C % 8 == 0, not accumulating)
+ *   fgcn_tconv_halo         bit 0 in, 1 out               masks 0, 1, 3; a bfloat16 in: the tap form, no fused input stage; a bfloat16 out: the
+ *                                                         plain store epilogue (no accumulation / BatchNorm-backward sums)
+ *   fgcn_tconv_wgrad        bit 0 a, 1 g                  masks 0, 3 (mask 3: a_amax = g_amax = NULL)
+ *   fgcn_pw_wgrad           bit 0 a, 1 g                  masks 0, 3 (mask 3: a_amax = g_amax = NULL)
+ *   fgcn_spatial_fwd_tile   bit 0 x, 1 y                  masks 0, 2, 3
+ *   fgcn_emb_fwd_tile       bit 0 x, 1 emb                (bit 1: emb is not NULL)
+ *   fgcn_spatial_bwd_tile   bit 0 dy, 1 x, 2 dx + gated addends (a per-group extra1 stays float32)     masks 0, 1, 3, 7
+ *   fgcn_spatial_wgrad_tile bit 0 x, 1 dy                 masks 0, 2, 3
+ *   fgcn_emb_dx_tile        bit 0 emb, 1 dx               masks 0, 1, 3
+ *   fgcn_emb_wgrad_tile     bit 0 emb, 1 x                masks 0, 1, 3
+ *   fgcn_rows_gemm          bit 0 in, 1 out               (a bfloat16 tensor: a single problem, taken whole; a bfloat16 out: no accumulation)
+ *   fgcn_pw_gemm            bit 0 in, 1 out               (a bfloat16 out: no accumulation) */
+
 /* bn_a / bn_mask / bn_vec (all NULL, or all given where fgcn_tconv_halo_bn_sums() == 1: the split-bf16 kernel of the bf16 math
  * modes): the call is the data gradient that produces dG, the gradient of G = relu(BatchNorm(a) + shortcut) (agcn.py:113-115), and
  * stat_partials receives the BatchNorm-backward sums instead of the forward moments -- per row tile and channel
@@ -305,13 +233,13 @@ int fgcn_tconv_halo_bn_sums(void);
  * shortcut x, laid out like `in`), formed as the rows are staged; G (fin_out, like `in`) and its sign image (fin_mask, fgcn_bn_act's
  * layout, rows*K/8 bytes) are written once as by-products (the backward's weight gradient and ReLU gate read them): what an
  * fgcn_bn_act(res_mode = 1, relu = 1) pass in front of this call computes, without that pass. */
-int fgcn_tconv_halo(const float* in, float* out, const float* w4, const float* bias, float* stat_partials,
+int fgcn_tconv_halo(const void* in, void* out, const float* w4, const float* bias, float* stat_partials,
                     int B, int Th, int V, int K, int N, int ld_in, int ld_out,
                     int T_in_full, int in_s, int in_o, int Th_in,
                     int T_out_full, int out_s, int out_o,
                     int taps, int tb, int tc, int accumulate, const float* bn_a, const unsigned char* bn_mask,
                     const float* bn_vec, const float* fin_vec, const float* fin_res, float* fin_out, unsigned char* fin_mask,
-                    unsigned* in_amax, void* stream);
+                    unsigned* in_amax, int half_mask, void* stream);
 /* in_amax (may be NULL; FGCN_PRODUCTS_F16X2 only): a device word that receives, by integer atomic maximum (order-independent), the
  * float bits of max |in| over everything this call stages -- zero it before the first call that should count; the weight gradient of
  * the same tensor takes it as its operand scale (fgcn_tconv_wgrad). */
@@ -337,23 +265,23 @@ int fgcn_tconv_wgrad_slabs(int N, int nsplit);
 int fgcn_pw_wgrad_slabs(int N, int nsplit);
 int fgcn_tconv_wgrad_resident(int N);
 int fgcn_pw_wgrad_resident(int N);
-int fgcn_tconv_wgrad(const float* a, const float* g, float* partial, int B, int T_g, int V, int K, int N,
+int fgcn_tconv_wgrad(const void* a, const void* g, float* partial, int B, int T_g, int V, int K, int N,
                      int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int Th_a,
                      int ntaps, int shift0, int tap0, int tap_step, int taps_total, int nsplit,
-                     const unsigned* a_amax, const unsigned* g_amax, void* stream);
+                     const unsigned* a_amax, const unsigned* g_amax, int half_mask, void* stream);
 
 /* Weight gradient of a 1x1 convolution (theta|phi embedding, conv_d on the stacked agg, down, residual): the same
  * kernel with one accumulator per 32-channel chunk of a instead of per tap (each g fragment feeds up to 6 MFMAs):
  *     partial[slab][k][n] = sum over the slab's rows (b, t, v) of a[(b, t*a_s + a_o, v), k] * g[(b, t, v), n]
  *   partial: float[fgcn_tconv_wgrad_slabs(N, nsplit)][K][N].  Same alignment / size rules as fgcn_tconv_wgrad. */
 int fgcn_pw_wgrad_chunks(int K, int N);
-int fgcn_pw_wgrad(const float* a, const float* g, float* partial, int B, int T_g, int V, int K, int N,
+int fgcn_pw_wgrad(const void* a, const void* g, float* partial, int B, int T_g, int V, int K, int N,
                   int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int nsplit,
-                  const unsigned* a_amax, const unsigned* g_amax, void* stream);
+                  const unsigned* a_amax, const unsigned* g_amax, int half_mask, void* stream);
 /* a_amax / g_amax (both weight-gradient entry points; may be NULL): device words holding the float bits of max |a| / max |g| over
  * the whole tensors, as fgcn_tconv_halo / fgcn_pw_gemm leave them in `in_amax`.  With both given and FGCN_PRODUCTS_F16X2 selected the
  * split kernel runs its f16x2 form (operands scaled by the exact powers of two that put those maxima into [2^14, 2^15)); without
- * them it runs the bf16x3 form. */
+ * them it runs the bf16x3 form.  A bfloat16 operand pair (half_mask 3) takes neither: FGCN_E_BADARG. */
 
 /* dst[i] (+)= sum_s src[s*count + i]   (deterministic tree-free column sum; also bias / adj_b gradients) */
 int fgcn_reduce_sum(float* dst, const float* src, int S, long long count, int accumulate, void* stream);
@@ -574,8 +502,8 @@ int fgcn_bn_eval_coeffs(const float* gamma, const float* beta, const float* runn
  *   rows x C elements, all tensors share row stride ld (== C). relu: 0/1. */
 /*   sign_mask (may be NULL; needs rows*C % 8 == 0): also stores bit e%8 of byte e/8 = [out[e] > 0] -- rows*C/8 bytes the
  *   backward passes can read instead of the whole of `out` (the ReLU gate of the reference's autograd). */
-int fgcn_bn_act(const float* a, const float* vec_a, const float* b, const float* vec_b, float* out,
-                unsigned char* sign_mask, long long rows, int C, int res_mode, int relu, void* stream);
+int fgcn_bn_act(const void* a, const float* vec_a, const void* b, const float* vec_b, void* out, unsigned char* sign_mask,
+                long long rows, int C, int res_mode, int relu, int half_mask, void* stream);
 
 /* The last block's epilogue and the pooling behind it in one pass (agcn.py:135-136 then :196-197):
  *     pooled[g][c] = mean over the grp_rows consecutive rows r of group g of relu( a*scale_a + shift_a + r-term )[(g*grp_rows + r), c]
@@ -583,30 +511,24 @@ int fgcn_bn_act(const float* a, const float* vec_a, const float* b, const float*
  *   what the backward reads) and the sums.  C % 8 == 0; partial: float[groups * fgcn_bn_act_pool_splits(groups, grp_rows)][C].
  *   Fixed summation order (another one than fgcn_group_mean's). */
 int fgcn_bn_act_pool_splits(int groups, int grp_rows);
-int fgcn_bn_act_pool(const float* a, const float* vec_a, const float* b, const float* vec_b, unsigned char* sign_mask,
-                     float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, void* stream);
+int fgcn_bn_act_pool(const void* a, const float* vec_a, const void* b, const float* vec_b, unsigned char* sign_mask,
+                     float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, int half_mask, void* stream);
 
 /* Backward of the above, pass 1 (reductions): with dP = dout .* [out > 0] (or dout when relu = 0)
  *   partials[tile][0][c] = sum dP, [1] = sum dP * a_hat, [2] = sum dP * b_hat   (a_hat = (a-mean_a)*rstd_a).
- *   The gate comes from sign_mask when it is given (then `out` may be NULL), else from `out`. */
-int fgcn_bn_act_bwd_reduce(const float* dout, const float* out, const unsigned char* sign_mask, const float* a,
-                           const float* vec_a, const float* b, const float* vec_b, float* partials, int n_tiles,
-                           long long rows, int C, int res_mode, int relu, void* stream);
+ *   The gate comes from sign_mask when it is given (then `out` may be NULL), else from `out`.
+ *   grp_rows (both passes; 0: dout is (rows, C)) > 0: the gradient of a POOLED output (fgcn_bn_act_pool) -- dout is float[rows / grp_rows][C],
+ *   one row per group of grp_rows consecutive rows (the pooled gradient already divided by the group size); every row reads its group's row
+ *   instead of a rows x C broadcast of it. */
+int fgcn_bn_act_bwd_reduce(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
+                           const float* vec_a, const void* b, const float* vec_b, float* partials, int n_tiles, long long rows,
+                           int C, int res_mode, int relu, int half_mask, void* stream);
 /* pass 2: da = scale_a * (dP - s1/m - a_hat*s2a/m) (train) or scale_a*dP (eval);
  *         db = dP (identity) or scale_b*(dP - s1/m - b_hat*s2b/m);  sums: float[3][C] reduced partials.
  *   db may be NULL (res_mode 0); db_accumulate adds into db instead of storing. */
-int fgcn_bn_act_bwd_apply(const float* dout, const float* out, const unsigned char* sign_mask, const float* a,
-                          const float* vec_a, const float* b, const float* vec_b, const float* sums, float* da, float* db,
-                          long long rows, int C, int res_mode, int relu, int train, int db_accumulate,
-                          void* stream);
-/* Both passes with the gradient of a POOLED output (fgcn_bn_act_pool): dout_g is float[rows / grp_rows][C], one row per group of grp_rows consecutive
- * rows (the pooled gradient already divided by the group size); every row reads its group's row instead of a rows x C broadcast of it. */
-int fgcn_bn_act_bwd_reduce_g(const float* dout_g, int grp_rows, const float* out, const unsigned char* sign_mask, const float* a,
-                             const float* vec_a, const float* b, const float* vec_b, float* partials, int n_tiles,
-                             long long rows, int C, int res_mode, int relu, void* stream);
-int fgcn_bn_act_bwd_apply_g(const float* dout_g, int grp_rows, const float* out, const unsigned char* sign_mask, const float* a,
-                            const float* vec_a, const float* b, const float* vec_b, const float* sums, float* da, float* db,
-                            long long rows, int C, int res_mode, int relu, int train, int db_accumulate, void* stream);
+int fgcn_bn_act_bwd_apply(const void* dout, int grp_rows, const float* out, const unsigned char* sign_mask, const void* a,
+                          const float* vec_a, const void* b, const float* vec_b, const float* sums, void* da, void* db,
+                          long long rows, int C, int res_mode, int relu, int train, int db_accumulate, int half_mask, void* stream);
 /* number of row tiles the reduce kernel uses for `rows` rows (leading dim of its partials) */
 int fgcn_elem_tiles(long long rows);
 /* The same three passes for a plain BatchNorm (no residual, no activation) whose result is a CHANNEL WINDOW of a wider tensor: one of the
@@ -642,9 +564,9 @@ int fgcn_spatial_tiles(int B, int T);
  *   w3: fgcn_pack_split3 form (acc_order 0) of the (3 Cin) x Cout matrix [k * Cin + c][o] = Wd_k[o][c] (one tap, K = 3 Cin); three
  *   subsets; Cin % 64 == 0; 16 <= V <= 32.  stat_partials: float[fgcn_spatial_fwd_tile_tiles(B, T, V)][2][Cout] or NULL.
  *   fgcn_spatial_fwd_tile_available: 1 when the current math mode / products and these sizes run on this kernel. */
-int fgcn_spatial_fwd_tile(const float* x, const float* a_hat, const void* w3, const float* bias_sum, float* y,
+int fgcn_spatial_fwd_tile(const void* x, const float* a_hat, const void* w3, const float* bias_sum, void* y,
                           float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
-                          int a_hat_batched, void* stream);
+                          int a_hat_batched, int half_mask, void* stream);
 int fgcn_spatial_fwd_tile_tiles(int B, int T, int V);
 int fgcn_spatial_fwd_tile_available(int V, int Cin, int Cout);
 
@@ -659,18 +581,14 @@ int fgcn_spatial_fwd_tile_available(int V, int Cin, int Cout);
  *   kernel always multiplies three-way bf16 splits: fgcn_spatial_bwd_tile_available).  accumulate != 0: dx += (load, add, store); every sum has a fixed order.
  *   extra1 / mask1, extra2 / mask2 (all four or none; not with accumulate; ld_x == Cin): dx = ... + extra_i * [bit of mask_i] -- contiguous
  *   (B, T, V, Cin) tensors with fgcn_bn_act's one-bit sign images: the ReLU-gated gradients of the block's two identity shortcuts
- *   (agcn.py:114,135), as in fgcn_joint_dagg. */
-int fgcn_spatial_bwd_tile(const float* dy, const float* x, const float* a_hat, const void* w3, float* dx, float* partial, int B,
-                          int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched, int accumulate,
-                          const float* extra1, const unsigned char* mask1, const float* extra2, const unsigned char* mask2,
-                          void* stream);
-/* ... with the first gated addend given per GROUP of extra1_group consecutive samples: extra1 = float[B / extra1_group][Cin], every row of a group's
- * samples adds its group's row (gated by mask1's bits as before) -- the gradient of the pooled output of the model's last block (fgcn_bn_act_pool)
- * without its (B, T, V, Cin) broadcast.  Not accumulating. */
-int fgcn_spatial_bwd_tile_g(const float* dy, const float* x, const float* a_hat, const void* w3, float* dx, float* partial, int B,
-                            int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched,
-                            const float* extra1, int extra1_group, const unsigned char* mask1, const float* extra2,
-                            const unsigned char* mask2, void* stream);
+ *   (agcn.py:114,135), as in fgcn_joint_dagg.
+ *   extra1_group (0: the form above) > 0: the first gated addend is given per GROUP of extra1_group consecutive samples, extra1 =
+ *   float[B / extra1_group][Cin]; every row of a group's samples adds its group's row (gated by mask1's bits as before) -- the gradient of the
+ *   pooled output of the model's last block (fgcn_bn_act_pool) without its (B, T, V, Cin) broadcast.  Not accumulating. */
+int fgcn_spatial_bwd_tile(const void* dy, const void* x, const float* a_hat, const void* w3, void* dx, float* partial,
+                          int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched, int accumulate,
+                          const void* extra1, int extra1_group, const unsigned char* mask1, const void* extra2,
+                          const unsigned char* mask2, int half_mask, void* stream);
 int fgcn_spatial_bwd_tile_segments(int B, int T, int V);
 int fgcn_spatial_bwd_tile_available(int V, int Cin, int Cout);
 
@@ -684,8 +602,8 @@ int fgcn_spatial_bwd_tile_available(int V, int Cin, int Cout);
  *   [3 * Cin][Cout]; the caller sums the slabs (fgcn_reduce_multi).  Math mode FGCN_MATH_BF16X3 only (either product form; the kernel
  *   always multiplies three-way bf16 splits, the mixing included): fgcn_spatial_wgrad_tile_available.  Every sum has a fixed order.
  *   Tuning key 16: workgroups to aim for (0 = 256, one per CU; sets the slab count). */
-int fgcn_spatial_wgrad_tile(const float* x, const float* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
-                            int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream);
+int fgcn_spatial_wgrad_tile(const void* x, const void* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
+                            int Cout, int ld_x, int ld_dy, int a_hat_batched, int half_mask, void* stream);
 int fgcn_spatial_wgrad_tile_slabs(int B, int T, int V, int Cin, int Cout);
 int fgcn_spatial_wgrad_tile_available(int V, int Cin, int Cout);
 
@@ -699,8 +617,8 @@ int fgcn_spatial_wgrad_tile_available(int V, int Cin, int Cout);
  * FGCN_MAX_V, ic 16 / 32 / 64, Cin a multiple of 32; math modes FGCN_MATH_BF16X3 (either product form: exact three-way bf16 splits) and
  * FGCN_MATH_BF16: fgcn_emb_fwd_tile_available.  Tuning key 22: resident workgroups to aim for (0 = 512; sets the segment count).
  * emb == NULL (inference: only the backward reads the embeddings): emb is not written, `partial` is all the call produces. */
-int fgcn_emb_fwd_tile(const float* x, const void* w3, const float* bias, float* emb, float* partial, int B, int T, int V, int Cin, int ic,
-                      int ld_x, int ld_e, void* stream);
+int fgcn_emb_fwd_tile(const void* x, const void* w3, const float* bias, void* emb, float* partial, int B, int T, int V, int Cin, int ic,
+                      int ld_x, int ld_e, int half_mask, void* stream);
 int fgcn_emb_fwd_tile_segments(int B, int T, int V, int ic);
 int fgcn_emb_fwd_tile_available(int V, int ic, int Cin);
 
@@ -711,7 +629,8 @@ int fgcn_emb_fwd_tile_available(int V, int ic, int Cin);
  *   demb[(n,t,v), th_k + e] = sum_w dS_k[v][w] emb[(n,t,w), ph_k + e],  demb[(n,t,w), ph_k + e] = sum_v dS_k[v][w] emb[(n,t,v), th_k + e]
  * is formed per frame on the matrix pipe inside both kernels and never written:
  *   fgcn_emb_dx_tile     dx[(n,t,v), 0:Cx] (+)= demb[(n,t,v), :] . Wemb^T, w3 = fgcn_pack_split3 of the (1, 6 ic, Cx) matrix [j][c] = Wemb[j][c]
- *                        (accumulate: dx += ...);
+ *                        (accumulate: dx += ...; dx_old -- half_mask 3 with accumulate, or NULL -- is the float32 tensor that holds the values
+ *                        to add to: dx = bfloat16(dx_old + term) is then only written);
  *   fgcn_emb_wgrad_tile  partial[s][j][c] = sum over the rows of slab s of demb[row, j] x[row, c]  (float[slabs][6 ic][Cx]: already the
  *                        parameters' (out, in) order) and bias_partial[s][j] = sum of demb[row, j] (float[slabs][6 ic]); the caller adds the
  *                        fgcn_emb_wgrad_tile_slabs(B, T, V, ic, Cx) slabs (fgcn_reduce_multi).
@@ -720,13 +639,13 @@ int fgcn_emb_fwd_tile_available(int V, int ic, int Cin);
  * fgcn_emb_tile_available.  Replaces fgcn_joint_mix_vec(demb) + fgcn_pw_gemm / fgcn_rows_gemm(demb . W) + fgcn_pw_wgrad(x, demb) and the
  * 1.5-activation-wide demb tensor between them.  Every sum has a fixed order.
  * Tuning key 17: fgcn_emb_wgrad_tile workgroups to aim for (0 = 256; sets the slab count). */
-int fgcn_emb_dx_tile(const float* emb, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V, int ic, int Cx, int ld_e,
-                     int ld_dx, int d_s_batched, int accumulate, void* stream);
+int fgcn_emb_dx_tile(const void* emb, const float* d_s, const void* w3, void* dx, void* workspace, int B, int T, int V, int ic, int Cx, int ld_e,
+                     int ld_dx, int d_s_batched, int accumulate, const float* dx_old, int half_mask, void* stream);
 /* bytes of fgcn_emb_dx_tile's caller-owned workspace (16-byte aligned; the split bf16 planes of dS and dS^T of every sample, written by a
  * small first launch and read by every workgroup of the main one) in the current math mode */
 long long fgcn_emb_dx_tile_workspace(int B, int d_s_batched);
-int fgcn_emb_wgrad_tile(const float* emb, const float* x, const float* d_s, float* partial, float* bias_partial, int B, int T, int V, int ic,
-                        int Cx, int ld_e, int ld_x, int d_s_batched, void* stream);
+int fgcn_emb_wgrad_tile(const void* emb, const void* x, const float* d_s, float* partial, float* bias_partial, int B, int T, int V, int ic,
+                        int Cx, int ld_e, int ld_x, int d_s_batched, int half_mask, void* stream);
 int fgcn_emb_wgrad_tile_slabs(int B, int T, int V, int ic, int Cx);
 int fgcn_emb_tile_available(int V, int ic, int Cx);
 
@@ -810,8 +729,8 @@ int fgcn_unfold_windows(const float* in, float* out, int B, int T, int T_out, in
  * (K = 64..384) to hide their own staging latency and store tail.  fgcn_pw_gemm_available() = 1 in FGCN_MATH_BF16X3 / FGCN_MATH_BF16. */
 int fgcn_pw_gemm_available(void);
 int fgcn_pw_gemm_tiles(long long rows);
-int fgcn_pw_gemm(const float* in, float* out, const void* w3, const float* bias, float* stat_partials, long long rows,
-                 int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, void* stream);
+int fgcn_pw_gemm(const void* in, void* out, const void* w3, const float* bias, float* stat_partials, long long rows,
+                 int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, int half_mask, void* stream);
 /* (w3: the FGCN_PACK_SPLIT2H form with FGCN_PRODUCTS_F16X2 selected; in_amax as for fgcn_tconv_halo) */
 
 /* ---- the two ends of the step: input BatchNorm and loss (fgcn_head.hip) ------------------------------------------------------

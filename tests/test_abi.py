@@ -31,8 +31,8 @@ def test_header_symbols_are_exported_and_bound(lib):
 
 
 def test_version_and_error_text(lib):
-    assert lib.fgcn_version() >= 100
-    rc = lib.fgcn_rows_gemm(None, None, None, None, None, 1, 1, 1, 1, 1, 4, 4, 4, _lib.TMap(1, 1, 0, 0, 1), 0, None)
+    assert lib.fgcn_version() >= 200
+    rc = lib.fgcn_rows_gemm(None, None, None, None, None, 1, 1, 1, 1, 1, 4, 4, 4, _lib.TMap(1, 1, 0, 0, 1), 0, 0, None)
     assert rc == -1 and b"null pointer" in lib.fgcn_last_error()
     with pytest.raises(_lib.FgcnError, match="null pointer"):
         _lib.check(rc, "fgcn_rows_gemm")
@@ -44,13 +44,13 @@ def test_host_side_validation(lib):
     p16 = (p + 15) // 16 * 16
     ident = _lib.TMap(1, 1, 0, 0, 1)
     # N not a multiple of 4
-    assert lib.fgcn_rows_gemm(p16, p16, p16, None, None, 1, 1, 1, 1, 4, 3, 4, 4, ident, 0, None) == -2
+    assert lib.fgcn_rows_gemm(p16, p16, p16, None, None, 1, 1, 1, 1, 4, 3, 4, 4, ident, 0, 0, None) == -2
     # row stride smaller than the channel window
-    assert lib.fgcn_rows_gemm(p16, p16, p16, None, None, 1, 1, 1, 1, 8, 4, 4, 4, ident, 0, None) == -1
+    assert lib.fgcn_rows_gemm(p16, p16, p16, None, None, 1, 1, 1, 1, 8, 4, 4, 4, ident, 0, 0, None) == -1
     # misaligned base pointer
-    assert lib.fgcn_rows_gemm(p16 + 4, p16, p16, None, None, 1, 1, 1, 1, 4, 4, 4, 4, ident, 0, None) == -2
+    assert lib.fgcn_rows_gemm(p16 + 4, p16, p16, None, None, 1, 1, 1, 1, 4, 4, 4, 4, ident, 0, 0, None) == -2
     # bad temporal map
-    assert lib.fgcn_rows_gemm(p16, p16, p16, None, None, 1, 1, 1, 1, 4, 4, 4, 4, _lib.TMap(0, 1, 0, 0, 1), 0, None) == -1
+    assert lib.fgcn_rows_gemm(p16, p16, p16, None, None, 1, 1, 1, 1, 4, 4, 4, 4, _lib.TMap(0, 1, 0, 0, 1), 0, 0, None) == -1
     # more joints than the kernels' 32-wide joint tile
     item = (_lib.MixItem * 1)()
     assert lib.fgcn_joint_mix(p16, p16, p16, 1, 1, 33, 4, 4, 4, 4, 1, 0, item, 1, 0, None) == -1
@@ -59,21 +59,37 @@ def test_host_side_validation(lib):
     assert lib.fgcn_spatial_fwd(p16, p16, p16, None, p16, None, 1, 1, 25, 512, 64, 512, 64, 3, 1, None) == -1
     assert lib.fgcn_spatial_fwd(p16, p16, p16, None, p16, None, 1, 1, 25, 3, 64, 4, 64, 3, 1, None) == -2   # Cin % 4
     # bn reduce with a wrong tile count
-    assert lib.fgcn_bn_act_bwd_reduce(p16, p16, None, p16, p16, None, None, p16, 7, 1000, 64, 0, 1, None) == -1   # needs 16 tiles
+    assert lib.fgcn_bn_act_bwd_reduce(p16, 0, p16, None, p16, p16, None, None, p16, 7, 1000, 64, 0, 1, 0, None) == -1   # needs 16 tiles
     assert lib.fgcn_elem_tiles(1000) == 16 and lib.fgcn_elem_tiles(10 ** 7) == 1024 and lib.fgcn_rows_gemm_tiles(129) == 2
     assert lib.fgcn_spatial_tiles(128, 300) == 128 * 10
-    # typed entry points (half-precision activation storage): a mask the kernel is not built for, and bfloat16 tensors outside math mode bf16
-    assert lib.fgcn_bn_act_t(p16, p16, None, None, p16, None, 16, 8, 0, 1, 8, None) == -1                  # bit 3 does not exist
+    # half_mask (half-precision activation storage): a mask the kernel is not built for, and bfloat16 tensors outside math mode bf16
+    halo = (p16, p16, p16, None, None, 1, 4, 25, 32, 32, 32, 32, 4, 1, 0, 4, 4, 1, 0, 9, 1, -4)      # ... up to tc; then accumulate, 8 pointers
+    assert lib.fgcn_bn_act(p16, p16, None, None, p16, None, 16, 8, 0, 1, 8, None) == -1                  # bit 3 does not exist
     assert b"half_mask" in lib.fgcn_last_error()
-    assert lib.fgcn_tconv_halo_t(p16, p16, p16, None, None, 1, 4, 25, 32, 32, 32, 32, 4, 1, 0, 4, 4, 1, 0, 9, 1, -4, 2, None) == -1   # out without in
-    assert lib.fgcn_spatial_bwd_tile_t(p16, p16, p16, p16, p16, p16, 1, 4, 25, 64, 64, 64, 64, 64, 1, 0, None, 0, None, None, None, 5, None) == -1
-    assert lib.fgcn_emb_dx_tile_t(p16, p16, p16, p16, p16, 1, 4, 25, 16, 64, 96, 64, 1, 0, None, 2, None) == -1
+    assert lib.fgcn_tconv_halo(*halo, 0, *[None] * 8, 2, None) == -1   # out without in
+    assert lib.fgcn_spatial_bwd_tile(p16, p16, p16, p16, p16, p16, 1, 4, 25, 64, 64, 64, 64, 64, 1, 0, None, 0, None, None, None, 5, None) == -1
+    assert lib.fgcn_emb_dx_tile(p16, p16, p16, p16, p16, 1, 4, 25, 16, 64, 96, 64, 1, 0, None, 2, None) == -1
     mode = lib.fgcn_get_math_mode()
     lib.fgcn_set_math_mode(2)          # bf16x3: bfloat16 tensors are refused before anything is launched
     try:
-        assert lib.fgcn_bn_act_t(p16, p16, None, None, p16, None, 16, 8, 0, 1, 1, None) == -1
+        assert lib.fgcn_bn_act(p16, p16, None, None, p16, None, 16, 8, 0, 1, 1, None) == -1
         assert b"math mode bf16" in lib.fgcn_last_error()
-        assert lib.fgcn_bn_act_bwd_apply_t(p16, 0, None, p16, p16, p16, None, None, p16, p16, None, 16, 8, 0, 1, 1, 0, 3, None) == -1
+        assert lib.fgcn_bn_act_bwd_apply(p16, 0, None, p16, p16, p16, None, None, p16, p16, None, 16, 8, 0, 1, 1, 0, 3, None) == -1
+        # the weight gradients take bfloat16 operands as a pair, and then no operand scales
+        twg = (p16, p16, p16, 1, 4, 25, 32, 32, 32, 32, 4, 1, 0, 4, 9, -4, 0, 1, 9, 1)
+        pwg = (p16, p16, p16, 1, 4, 25, 32, 32, 32, 32, 4, 1, 0, 1)
+        for fn, args in ((lib.fgcn_tconv_wgrad, twg), (lib.fgcn_pw_wgrad, pwg)):
+            for mask in (1, 2):
+                assert fn(*args, None, None, mask, None) == -1
+                assert b"half_mask" in lib.fgcn_last_error()
+            assert fn(*args, p16, p16, 3, None) == -1
+            assert b"half_mask" in lib.fgcn_last_error()
+            assert fn(*args, p16, None, 3, None) == -1 and fn(*args, None, p16, 3, None) == -1
+        lib.fgcn_set_math_mode(1)          # bf16: the combinations the kernels are not built for are refused in the mode that takes bfloat16 tensors too
+        assert lib.fgcn_tconv_halo(*halo, 1, *[None] * 8, 3, None) == -1                              # a bfloat16 output, accumulating
+        assert b"no accumulation" in lib.fgcn_last_error()
+        assert lib.fgcn_bn_act_bwd_reduce(p16, 4, None, p16, p16, p16, None, None, p16, 1, 16, 8, 0, 1, 1, None) == -1   # a bfloat16 per-group dout
+        assert b"float32 per-group gradient" in lib.fgcn_last_error()
     finally:
         lib.fgcn_set_math_mode(mode)
 
@@ -102,13 +118,13 @@ def test_tile_kernel_geometry_and_tuning_keys(lib):
             assert lib.fgcn_set_tuning(k, 0) == 0
     # the launcher validates on the host before any HIP call: null pointers, channel counts outside the 64s, a misaligned dY
     one = C.c_void_p(16)
-    assert lib.fgcn_spatial_wgrad_tile(None, one, one, one, 2, 13, 25, 64, 64, 64, 64, 1, None) == -1
+    assert lib.fgcn_spatial_wgrad_tile(None, one, one, one, 2, 13, 25, 64, 64, 64, 64, 1, 0, None) == -1
     assert lib.fgcn_set_math_mode(2) == 0
     try:
-        assert lib.fgcn_spatial_wgrad_tile(one, one, one, one, 2, 13, 25, 96, 64, 96, 64, 1, None) == -1
-        assert lib.fgcn_spatial_wgrad_tile(one, C.c_void_p(20), one, one, 2, 13, 25, 64, 64, 64, 64, 1, None) == -2
+        assert lib.fgcn_spatial_wgrad_tile(one, one, one, one, 2, 13, 25, 96, 64, 96, 64, 1, 0, None) == -1
+        assert lib.fgcn_spatial_wgrad_tile(one, C.c_void_p(20), one, one, 2, 13, 25, 64, 64, 64, 64, 1, 0, None) == -2
         assert b"aligned" in lib.fgcn_last_error()
-        assert lib.fgcn_spatial_wgrad_tile(one, one, one, one, 2, 13, 25, 64, 64, 32, 64, 1, None) == -1     # ld_x < Cin
+        assert lib.fgcn_spatial_wgrad_tile(one, one, one, one, 2, 13, 25, 64, 64, 32, 64, 1, 0, None) == -1     # ld_x < Cin
     finally:
         assert lib.fgcn_set_math_mode(0) == 0
     assert lib.fgcn_set_tuning(32, 1) == -1 and b"out of range" in lib.fgcn_last_error()

@@ -302,11 +302,11 @@ def test_embedding_forward_tile_form_bf16(V, T, cin, ic, B):
     assert rel_l2(part.double().sum(1)[:, :, :V, :V].cpu().numpy(), want_s.numpy()) < 2e-4
 
 
-# ---- half-precision STORAGE of the temporal conv's operands (include/fgcn.h, the `_h` entry points; paths.half_storage) -------------
+# ---- half-precision STORAGE of the temporal conv's operands (include/fgcn.h, half_mask output bits; paths.half_storage) -------------
 @pytest.mark.parametrize("rows,C,res", [(1000, 64, 0), (777, 128, 1), (2048, 256, 2), (50, 8, 1)])
 def test_bn_act_and_its_backward_write_bfloat16(rows, C, res):
-    """fgcn_bn_act_h / fgcn_bn_act_bwd_apply_h: the bfloat16 tensor they write is the round-to-nearest-even of what the f32 entry
-    points write, bit for bit; the sign image and the sums are those of the f32 values."""
+    """fgcn_bn_act (half_mask 4) / fgcn_bn_act_bwd_apply (half_mask 8): the bfloat16 tensor they write is the round-to-nearest-even of what
+    the all-f32 calls write, bit for bit; the sign image and the sums are those of the f32 values."""
     from fusion_gcn_amd import ops
     a, b = gpu(rnd(rows, C, seed=1)), gpu(rnd(rows, C, seed=2))
     mk = lambda seed: gpu(torch.stack([rnd(C, seed=seed), rnd(C, seed=seed + 1).abs() + 0.5, rnd(C, seed=seed + 2), rnd(C, seed=seed + 3)]))  # noqa: E731
@@ -327,8 +327,8 @@ def test_bn_act_and_its_backward_write_bfloat16(rows, C, res):
 @pytest.mark.parametrize("B,T,V,C,N,kt,s", [(2, 20, 25, 64, 64, 9, 1), (2, 21, 25, 128, 128, 9, 2), (3, 13, 18, 256, 256, 9, 1),
                                             (2, 30, 27, 64, 128, 5, 1), (1, 9, 32, 128, 64, 3, 1), (2, 12, 22, 64, 64, 9, 2)])
 def test_halo_conv_and_weight_gradient_from_bfloat16_tensors(B, T, V, C, N, kt, s):
-    """fgcn_tconv_halo_h (forward, data gradient; strided passes) and fgcn_tconv_wgrad_h on bfloat16 tensors against the f32 entry
-    points on the f32 tensors holding the same (bfloat16-representable) values: bit for bit -- the kernels stage the same bytes."""
+    """fgcn_tconv_halo with half_mask 1 (forward, data gradient; strided passes) and fgcn_tconv_wgrad with half_mask 3 against the f32
+    calls on the f32 tensors holding the same (bfloat16-representable) values: bit for bit -- the kernels stage the same bytes."""
     from fusion_gcn_amd import block, ops
     from fusion_gcn_amd.packing import Form, Seg
     pad = (kt - 1) // 2
@@ -474,7 +474,7 @@ def test_model_step_with_half_precision_activations():
 
 @pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 256, 256, 2), (32, 5, 128, 64, 1)])
 def test_spatial_backward_tile_kernels_from_a_bfloat16_dy(V, T, cin, cout, B):
-    """fgcn_spatial_bwd_tile_h / fgcn_spatial_wgrad_tile_h on a bfloat16 dy against the f32 entry points on the f32 tensor holding the
+    """fgcn_spatial_bwd_tile (half_mask 1) / fgcn_spatial_wgrad_tile (half_mask 2) on a bfloat16 dy against the f32 calls on the f32 tensor holding the
     same values: bit for bit (plain, accumulating, gated and per-group-gated forms of the fused backward)."""
     from fusion_gcn_amd import ops
     x, a = gpu(rnd(B, T, V, cin, seed=41)), gpu(rnd(B, 3, V, V, seed=42, scale=0.3))
@@ -539,8 +539,8 @@ def test_inference_kernels_in_bf16_mode():
 
 @pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 128, 32, 2), (27, 9, 64, 32, 1), (18, 10, 128, 64, 2), (22, 31, 256, 64, 1)])
 def test_embedding_kernels_with_a_bfloat16_emb(V, T, cin, ic, B):
-    """fgcn_emb_fwd_tile_h writes the bfloat16 rounding of what fgcn_emb_fwd_tile writes (same gram partials); fgcn_emb_dx_tile_h /
-    fgcn_emb_wgrad_tile_h on that tensor equal the f32 entry points on the f32 tensor holding the same values, bit for bit."""
+    """fgcn_emb_fwd_tile with half_mask 2 writes the bfloat16 rounding of what mask 0 writes (same gram partials); fgcn_emb_dx_tile /
+    fgcn_emb_wgrad_tile with half_mask 1 on that tensor equal the f32 calls on the f32 tensor holding the same values, bit for bit."""
     from fusion_gcn_amd import ops
     x = gpu(rnd(B, T, V, cin, seed=61))
     w3 = ops.pack_split3(gpu(rnd(1, cin, 6 * ic, seed=62, scale=cin ** -0.5)))
@@ -565,7 +565,7 @@ def test_embedding_kernels_with_a_bfloat16_emb(V, T, cin, ic, B):
     assert torch.equal(gw2, gw3) and torch.equal(gb2, gb3)
 
 
-# ---- half-precision ACTIVATION storage (include/fgcn.h, the typed `_t` entry points; paths.half_activations) ---------------------------
+# ---- half-precision ACTIVATION storage (include/fgcn.h, half_mask input bits too; paths.half_activations) ---------------------------
 # A bfloat16 INPUT of a kernel must give the bits of the float32 call on the same values; a bfloat16 OUTPUT must be the round-to-nearest-even
 # of the float32 call's output, with BatchNorm sums of the float32 values.
 def h16(*shape, seed=0, scale=1.0):
@@ -574,7 +574,7 @@ def h16(*shape, seed=0, scale=1.0):
 
 @pytest.mark.parametrize("rows,C,res", [(1000, 64, 0), (777, 128, 1), (2048, 256, 2), (50, 8, 1), (600, 64, 2), (1000, 12, 1), (500, 20, 2)])   # (C % 8 != 0: the four-wide typed kernels)
 def test_batchnorm_passes_with_bfloat16_operands(rows, C, res):
-    """fgcn_bn_act_t / fgcn_bn_act_pool_t / fgcn_bn_act_bwd_reduce_t / fgcn_bn_act_bwd_apply_t with a, the shortcut and the incoming
+    """fgcn_bn_act / fgcn_bn_act_pool / fgcn_bn_act_bwd_reduce / fgcn_bn_act_bwd_apply with a, the shortcut and the incoming
     gradient as bfloat16 tensors, in every combination the block produces, against the float32 entry points on the same values."""
     from fusion_gcn_amd import ops
     a16, b16, d16 = h16(rows, C, seed=1), h16(rows, C, seed=2), h16(rows, C, seed=3)
@@ -608,7 +608,7 @@ def test_batchnorm_passes_with_bfloat16_operands(rows, C, res):
 @pytest.mark.parametrize("B,T,V,C,N,kt,s", [(2, 20, 25, 64, 64, 9, 1), (3, 13, 18, 256, 256, 9, 1), (2, 30, 27, 64, 128, 5, 1), (1, 9, 32, 128, 64, 3, 1),
                                             (2, 21, 25, 128, 128, 9, 2), (8, 40, 25, 128, 128, 9, 1), (16, 64, 25, 64, 64, 9, 1)])
 def test_halo_conv_writes_bfloat16(B, T, V, C, N, kt, s):
-    """fgcn_tconv_halo_t with mask 3: the output is the rounding of the float32 output of fgcn_tconv_halo_h, the BatchNorm moments are
+    """fgcn_tconv_halo with half_mask 3: the output is the rounding of the float32 output of half_mask 1, the BatchNorm moments are
     those of the float32 values, bit for bit (forward with statistics; data gradient, also through the frame views of a strided conv)."""
     from fusion_gcn_amd import ops
     pad = (kt - 1) // 2
@@ -637,8 +637,8 @@ def test_halo_conv_writes_bfloat16(B, T, V, C, N, kt, s):
 
 @pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 256, 256, 2), (32, 5, 128, 64, 1), (22, 40, 64, 64, 3)])
 def test_spatial_tile_kernels_on_bfloat16_activations(V, T, cin, cout, B):
-    """fgcn_spatial_fwd_tile_t (x in, y out), fgcn_spatial_wgrad_tile_t (x, dy), fgcn_spatial_bwd_tile_t (dy, x, dx, gated addends) against
-    the float32 / `_h` forms on the same values: equal inputs give equal bits, a bfloat16 output is the rounded float32 output."""
+    """fgcn_spatial_fwd_tile (x in, y out), fgcn_spatial_wgrad_tile (x, dy), fgcn_spatial_bwd_tile (dy, x, dx, gated addends) against
+    the float32 / bfloat16-dy forms on the same values: equal inputs give equal bits, a bfloat16 output is the rounded float32 output."""
     from fusion_gcn_amd import ops
     x16, a = h16(B, T, V, cin, seed=41), gpu(rnd(B, 3, V, V, seed=42, scale=0.3))
     x32 = x16.float()
@@ -672,7 +672,7 @@ def test_spatial_tile_kernels_on_bfloat16_activations(V, T, cin, cout, B):
 
 @pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 128, 32, 2), (27, 9, 64, 32, 1), (18, 10, 128, 64, 2), (22, 31, 256, 64, 1)])
 def test_embedding_kernels_on_bfloat16_activations(V, T, cin, ic, B):
-    """fgcn_emb_fwd_tile_t (x in), fgcn_emb_dx_tile_t (dx read-modify-written as bfloat16), fgcn_emb_wgrad_tile_t (x in) against the `_h`
+    """fgcn_emb_fwd_tile (x in), fgcn_emb_dx_tile (dx read-modify-written as bfloat16), fgcn_emb_wgrad_tile (x in) against the bfloat16-emb
     forms on the same values."""
     from fusion_gcn_amd import ops
     x16 = h16(B, T, V, cin, seed=61)
@@ -708,7 +708,7 @@ def test_embedding_kernels_on_bfloat16_activations(V, T, cin, ic, B):
 @pytest.mark.parametrize("B,T,V,K,N,s", [(2, 20, 25, 64, 128, 1), (2, 21, 25, 64, 128, 2), (3, 10, 18, 128, 256, 2), (2, 9, 27, 4, 64, 1), (2, 40, 25, 128, 64, 1),
                                          (1, 300, 25, 256, 128, 1)])
 def test_row_gemms_on_bfloat16_activations(B, T, V, K, N, s):
-    """fgcn_rows_gemm_t / fgcn_pw_gemm_t (the shortcut convolutions of the blocks that change width or stride): a bfloat16 input gives the bits
+    """fgcn_rows_gemm / fgcn_pw_gemm with a half_mask (the shortcut convolutions of the blocks that change width or stride): a bfloat16 input gives the bits
     of the float32 call on the same values, a bfloat16 output is the rounded float32 output with the float32 BatchNorm sums; also the
     accumulating data-gradient form from a bfloat16 gradient."""
     from fusion_gcn_amd import ops
@@ -751,8 +751,8 @@ def test_row_gemms_on_bfloat16_activations(B, T, V, K, N, s):
 @pytest.mark.parametrize("B,T,V,cin,cout,s", [(2, 20, 25, 64, 128, 1), (2, 21, 25, 64, 128, 2), (2, 12, 18, 128, 256, 2), (1, 30, 27, 128, 64, 1)])
 def test_shortcut_branch_backward_on_bfloat16_tensors(B, T, V, cin, cout, s):
     """The backward of the blocks that change width or stride under half-precision activation storage: the shortcut BatchNorm's gradient as a
-    bfloat16 tensor (fgcn_bn_act_bwd_apply_t, bit 4), the 1x1 weight gradient from bfloat16 operands (fgcn_pw_wgrad_h), and the fused spatial
-    backward reading a bfloat16 x while it accumulates into a float32 dx (fgcn_spatial_bwd_tile_t, mask 3) -- against the float32 forms."""
+    bfloat16 tensor (fgcn_bn_act_bwd_apply, half_mask bit 4), the 1x1 weight gradient from bfloat16 operands (fgcn_pw_wgrad, half_mask 3), and the fused spatial
+    backward reading a bfloat16 x while it accumulates into a float32 dx (fgcn_spatial_bwd_tile, half_mask 3) -- against the float32 forms."""
     from fusion_gcn_amd import ops
     Tp = (T - 1) // s + 1
     rows, C = B * Tp * V, cout

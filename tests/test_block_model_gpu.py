@@ -584,7 +584,7 @@ def test_batchnorm_backward_from_a_per_group_gradient(G, R, C, res_mode):
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,T,V,C,group", [(4, 11, 25, 64, 2), (6, 7, 20, 128, 3), (2, 40, 25, 256, 1)])
 def test_spatial_backward_tile_with_a_per_group_addend(B, T, V, C, group):
-    """fgcn_spatial_bwd_tile_g: the first gated addend as one row per group of samples = the launch with its (B, T, V, Cin) broadcast, bit for bit."""
+    """fgcn_spatial_bwd_tile with extra1_group > 0: the first gated addend as one row per group of samples = the launch with its (B, T, V, Cin) broadcast, bit for bit."""
     from fusion_gcn_amd import ops
     dev = torch.device("cuda:0")
     torch.manual_seed(7 + C)
