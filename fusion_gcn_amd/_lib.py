@@ -65,7 +65,7 @@ class ReduceItem(C.Structure):
 
 REDUCE_MAX_ITEMS = 8        # FGCN_REDUCE_MAX_ITEMS
 
-_I, _LL, _F, _P = C.c_int, C.c_longlong, C.c_float, C.c_void_p
+_I, _LL, _F, _D, _P = C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/fgcn.h one to one.  The fifteen kernels that take bfloat16 activation tensors carry `half_mask`
 # (an int) immediately before the stream (include/fgcn.h, "storage types and half_mask")
@@ -176,6 +176,9 @@ SIGNATURES = {
     "fgcn_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_optim_step": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _LL, _P]),
+    "fgcn_grad_norm_tiles": (_I, [_LL]),
+    "fgcn_optim_guard_bytes": (_LL, []),
+    "fgcn_optim_step_guarded": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _D, _I, _P, _I, _P, _P]),
     "fgcn_classify_state_bytes": (_LL, [_I]),
     "fgcn_classify_update": (_I, [_P, _P, _P, _P, _P, _LL, _LL, _I, _I, _I, _I, _P]),
 }
@@ -183,6 +186,10 @@ SIGNATURES = {
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)
 CLS_EXAMPLES, CLS_TOP1, CLS_TOPK, CLS_IGNORED, CLS_INVALID, CLS_DROPPED, CLS_LOSS_ITEMS, CLS_LOSS_SUM, CLS_WORDS = range(9)
 CLS_MAX_CLASSES = 1024      # FGCN_CLS_MAX_CLASSES
+# enum fgcn_guard_word: the 8-byte words of the guarded optimizer step's state (include/fgcn.h)
+(GUARD_STEP, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM, GUARD_COEF, GUARD_APPLY, GUARD_FIRST_STEP, GUARD_STEP_SIZE, GUARD_BC2_SQRT,
+ GUARD_WORDS) = range(10)
+GRAD_NORM_MAX_TILES = 512   # FGCN_GRAD_NORM_MAX_TILES
 
 _lib = None
 

@@ -5,6 +5,10 @@
 // lives in one contiguous float32 buffer (fusion_gcn_amd/optim.py; the gradients already do, dp.FlatGradients), and one
 // launch applies torch's update formulas element by element -- the data-parallel 1/world average rides along as
 // `grad_scale`.  Pure HBM stream: 16-byte loads / stores, 28 B per parameter (Adam).
+//
+// The guarded form (fgcn_optim_step_guarded) puts two launches in front of it: the float64 sum of squares of the scaled gradient
+// (one more 4 B per parameter read) and a one-workgroup decision -- clip coefficient, apply / skip, step count and Adam's bias
+// corrections -- written into a caller-owned guard state that the update then reads.  The host reads nothing back.
 #include <cmath>
 
 #include "fgcn_common.hpp"
@@ -21,11 +25,22 @@ struct OptimP {
     float beta1, beta2, eps, step_size, bc2_sqrt;      // Adam / AdamW
     float momentum, dampening;                         // SGD
     int nesterov, first_step;
+    const unsigned long long* guard;                   // GUARDED: enum fgcn_guard_word, written by optim_guard_decide_kernel
 };
 
+__device__ __forceinline__ double guard_f64(const unsigned long long* w, int word) { return __builtin_bit_cast(double, w[word]); }
+
 // kind 0: SGD (torch/optim/sgd.py), 1: Adam (L2 weight decay folded into the gradient), 2: AdamW (decoupled decay)
-template <int KIND>
+// GUARDED: the step's scalars come from the guard state of the launch before (uniform loads), nothing is stored when it says skip
+template <int KIND, bool GUARDED>
 __global__ __launch_bounds__(256) void optim_step_kernel(OptimP q) {
+    if (GUARDED) {
+        if (q.guard[FGCN_GUARD_APPLY] == 0) return;
+        q.grad_scale = (float)((double)q.grad_scale * guard_f64(q.guard, FGCN_GUARD_COEF));
+        q.first_step = (int)q.guard[FGCN_GUARD_FIRST_STEP];
+        q.step_size = (float)guard_f64(q.guard, FGCN_GUARD_STEP_SIZE);
+        q.bc2_sqrt = (float)guard_f64(q.guard, FGCN_GUARD_BC2_SQRT);
+    }
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < q.n4; i += (long long)gridDim.x * blockDim.x) {
         f32x4 p = *reinterpret_cast<const f32x4*>(q.p + i * 4);
         f32x4 g = *reinterpret_cast<const f32x4*>(q.g + i * 4) * q.grad_scale;
@@ -57,44 +72,177 @@ __global__ __launch_bounds__(256) void optim_step_kernel(OptimP q) {
     }
 }
 
+// ---- the guard: sum of squares of the scaled gradient, then the decision ---------------------------------------------------------
+constexpr int GN_THREADS = 256;
+constexpr int GN_UNROLL = 4;                                   // 16-byte groups per thread and chunk
+constexpr long long GN_CHUNK4 = (long long)GN_THREADS * GN_UNROLL;  // 16-byte groups per chunk (4096 floats)
+
+// Workgroup w takes the chunks w, w + gridDim.x, ...; inside a chunk thread t takes the groups t, t + 256, ...: which thread adds
+// which element depends on the element's index and the grid alone, and the grid on n alone (fgcn_grad_norm_tiles).  The thread sums
+// are combined by a butterfly inside the wave and in wave order across the workgroup.  float64 throughout.
+__global__ __launch_bounds__(GN_THREADS) void grad_sqsum_kernel(const float* g, long long n4, float grad_scale, double* partials) {
+    const double sc = (double)grad_scale;
+    const long long chunks = (n4 + GN_CHUNK4 - 1) / GN_CHUNK4;
+    double acc = 0.0;
+    for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const long long base = c * GN_CHUNK4 + threadIdx.x;
+        f32x4 x[GN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GN_UNROLL; ++u) {
+            const long long i = base + (long long)u * GN_THREADS;
+            x[u] = i < n4 ? *reinterpret_cast<const f32x4*>(g + i * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < GN_UNROLL; ++u) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)x[u][e] * sc;
+                acc = fma(d, d, acc);
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+    __shared__ double wave_sum[GN_THREADS / 64];
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = wave_sum[0];
+#pragma unroll
+        for (int w = 1; w < GN_THREADS / 64; ++w) s += wave_sum[w];
+        partials[blockIdx.x] = s;
+    }
+}
+
+struct GuardP {
+    const double* partials;
+    unsigned long long* guard;
+    int n_partials, skip_nonfinite, adam;
+    double max_norm, lr, beta1, beta2;
+};
+
+// One workgroup: the partials go through LDS so that their loads overlap, thread 0 adds them in index order and decides.
+__global__ __launch_bounds__(GN_THREADS) void optim_guard_decide_kernel(GuardP q) {
+    __shared__ double part[FGCN_GRAD_NORM_MAX_TILES];
+    for (int i = threadIdx.x; i < q.n_partials; i += GN_THREADS) part[i] = q.partials[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (int i = 0; i < q.n_partials; ++i) sum += part[i];
+    const double norm = sqrt(sum);
+    double coef = 1.0;
+    if (q.max_norm > 0.0) {
+        const double c = q.max_norm / (norm + 1e-6);
+        coef = c < 1.0 ? c : (c != c ? c : 1.0);              // torch.clamp(c, max=1.0): a NaN stays a NaN
+    }
+    const bool apply = isfinite(norm) || !q.skip_nonfinite;
+    unsigned long long* w = q.guard;
+    w[FGCN_GUARD_NORM] = __builtin_bit_cast(unsigned long long, norm);
+    w[FGCN_GUARD_COEF] = __builtin_bit_cast(unsigned long long, coef);
+    w[FGCN_GUARD_APPLY] = apply ? 1ull : 0ull;
+    if (!apply) {
+        w[FGCN_GUARD_SKIPPED] += 1ull;
+        return;
+    }
+    const unsigned long long step = w[FGCN_GUARD_STEP] + 1ull;
+    w[FGCN_GUARD_STEP] = step;
+    if (coef < 1.0) w[FGCN_GUARD_CLIPPED] += 1ull;
+    w[FGCN_GUARD_FIRST_STEP] = step == 1ull ? 1ull : 0ull;
+    if (q.adam) {                                             // the bias corrections in double, as fgcn_optim_step's host code
+        const double bc1 = 1.0 - pow(q.beta1, (double)step), bc2 = 1.0 - pow(q.beta2, (double)step);
+        w[FGCN_GUARD_STEP_SIZE] = __builtin_bit_cast(unsigned long long, q.lr / bc1);
+        w[FGCN_GUARD_BC2_SQRT] = __builtin_bit_cast(unsigned long long, sqrt(bc2));
+    }
+}
+
 }  // namespace fgcn
 
 using namespace fgcn;
 
-extern "C" int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                               float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
-                               float momentum, float dampening, int nesterov, long long step, void* stream) {
-    FGCN_REQUIRE(params && grads && n > 0, FGCN_E_BADARG, "optim_step: null pointer or empty buffer");
+// Everything both entry points check and fill in; `step` is the host-side count of the unguarded call, NULL for the guarded one
+// (whose count lives in the guard state).
+static int optim_prepare(OptimP& q, const char* who, float* params, const float* grads, float* state1, float* state2, long long n,
+                         int kind, float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
+                         float momentum, float dampening, int nesterov, const long long* step) {
+    FGCN_REQUIRE(params && grads && n > 0, FGCN_E_BADARG, "%s: null pointer or empty buffer", who);
     FGCN_REQUIRE(n % 4 == 0 && aligned16(params) && aligned16(grads), FGCN_E_ALIGN,
-                 "optim_step: buffers must be 16-byte aligned and a multiple of 4 floats long (n=%lld)", n);
-    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ADAMW, FGCN_E_BADARG, "optim_step: kind %d", kind);
-    FGCN_REQUIRE(step >= 1, FGCN_E_BADARG, "optim_step: step counts from 1 (got %lld)", step);
-    FGCN_REQUIRE(lr >= 0.f && weight_decay >= 0.f, FGCN_E_BADARG, "optim_step: negative lr / weight_decay");
-    OptimP q{};
+                 "%s: buffers must be 16-byte aligned and a multiple of 4 floats long (n=%lld)", who, n);
+    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ADAMW, FGCN_E_BADARG, "%s: kind %d", who, kind);
+    FGCN_REQUIRE(!step || *step >= 1, FGCN_E_BADARG, "%s: step counts from 1 (got %lld)", who, step ? *step : 0ll);
+    FGCN_REQUIRE(lr >= 0.f && weight_decay >= 0.f, FGCN_E_BADARG, "%s: negative lr / weight_decay", who);
+    q = OptimP{};
     q.p = params; q.g = grads; q.m = state1; q.v = state2; q.n4 = n / 4;
     q.lr = lr; q.wd = weight_decay; q.grad_scale = grad_scale;
     if (kind == FGCN_OPT_SGD) {
         FGCN_REQUIRE(momentum >= 0.f && (momentum == 0.f || (state1 && aligned16(state1))), FGCN_E_BADARG,
-                     "optim_step: SGD with momentum needs the momentum buffer");
+                     "%s: SGD with momentum needs the momentum buffer", who);
         FGCN_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), FGCN_E_BADARG,
-                     "optim_step: Nesterov momentum requires a momentum and zero dampening");
-        q.momentum = momentum; q.dampening = dampening; q.nesterov = nesterov; q.first_step = step == 1;
+                     "%s: Nesterov momentum requires a momentum and zero dampening", who);
+        q.momentum = momentum; q.dampening = dampening; q.nesterov = nesterov; q.first_step = step && *step == 1;
     } else {
         FGCN_REQUIRE(state1 && state2 && aligned16(state1) && aligned16(state2), FGCN_E_BADARG,
-                     "optim_step: Adam needs exp_avg and exp_avg_sq");
+                     "%s: Adam needs exp_avg and exp_avg_sq", who);
         FGCN_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, FGCN_E_BADARG,
-                     "optim_step: betas / eps out of range");
-        // the bias corrections in double, as torch's Python scalars
-        const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
+                     "%s: betas / eps out of range", who);
         q.beta1 = beta1; q.beta2 = beta2; q.eps = eps;
-        q.step_size = (float)((double)lr / bc1);
-        q.bc2_sqrt = (float)std::sqrt(bc2);
+        if (step) {      // the bias corrections in double, as torch's Python scalars
+            const double bc1 = 1.0 - std::pow((double)beta1, (double)*step), bc2 = 1.0 - std::pow((double)beta2, (double)*step);
+            q.step_size = (float)((double)lr / bc1);
+            q.bc2_sqrt = (float)std::sqrt(bc2);
+        }
     }
+    return FGCN_OK;
+}
+
+template <bool GUARDED>
+static void optim_launch(const OptimP& q, int kind, hipStream_t s) {
     const long long blocks = cdiv(q.n4, 256);
     dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
-    hipStream_t s = (hipStream_t)stream;
-    if (kind == FGCN_OPT_SGD) hipLaunchKernelGGL((optim_step_kernel<0>), grid, dim3(256), 0, s, q);
-    else if (kind == FGCN_OPT_ADAM) hipLaunchKernelGGL((optim_step_kernel<1>), grid, dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((optim_step_kernel<2>), grid, dim3(256), 0, s, q);
+    if (kind == FGCN_OPT_SGD) hipLaunchKernelGGL((optim_step_kernel<0, GUARDED>), grid, dim3(256), 0, s, q);
+    else if (kind == FGCN_OPT_ADAM) hipLaunchKernelGGL((optim_step_kernel<1, GUARDED>), grid, dim3(256), 0, s, q);
+    else hipLaunchKernelGGL((optim_step_kernel<2, GUARDED>), grid, dim3(256), 0, s, q);
+}
+
+extern "C" int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
+                               float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
+                               float momentum, float dampening, int nesterov, long long step, void* stream) {
+    OptimP q;
+    const int rc = optim_prepare(q, "optim_step", params, grads, state1, state2, n, kind, lr, weight_decay, grad_scale, beta1, beta2,
+                                 eps, momentum, dampening, nesterov, &step);
+    if (rc != FGCN_OK) return rc;
+    optim_launch<false>(q, kind, (hipStream_t)stream);
     return launch_status("optim_step");
+}
+
+extern "C" int fgcn_grad_norm_tiles(long long n) {
+    const long long t = cdiv(cdiv(n, 4), GN_CHUNK4);
+    return (int)(t < 1 ? 1 : t < FGCN_GRAD_NORM_MAX_TILES ? t : FGCN_GRAD_NORM_MAX_TILES);
+}
+
+extern "C" long long fgcn_optim_guard_bytes(void) { return 8ll * FGCN_GUARD_WORDS; }
+
+extern "C" int fgcn_optim_step_guarded(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
+                                       float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
+                                       float momentum, float dampening, int nesterov, double max_norm, int skip_nonfinite,
+                                       double* partials, int n_partials, void* guard, void* stream) {
+    OptimP q;
+    const int rc = optim_prepare(q, "optim_step_guarded", params, grads, state1, state2, n, kind, lr, weight_decay, grad_scale, beta1,
+                                 beta2, eps, momentum, dampening, nesterov, nullptr);
+    if (rc != FGCN_OK) return rc;
+    FGCN_REQUIRE(partials && guard, FGCN_E_BADARG, "optim_step_guarded: null partials / guard state");
+    FGCN_REQUIRE(((uintptr_t)guard & 7) == 0 && ((uintptr_t)partials & 7) == 0, FGCN_E_ALIGN,
+                 "optim_step_guarded: guard state and partials must be 8-byte aligned");
+    FGCN_REQUIRE(n_partials == fgcn_grad_norm_tiles(n), FGCN_E_BADARG, "optim_step_guarded: n_partials must be %d (got %d)",
+                 fgcn_grad_norm_tiles(n), n_partials);
+    FGCN_REQUIRE(max_norm >= 0.0, FGCN_E_BADARG, "optim_step_guarded: max_norm must be a number >= 0 (0: no clipping)");
+    q.guard = static_cast<const unsigned long long*>(guard);
+    GuardP d{};
+    d.partials = partials; d.guard = static_cast<unsigned long long*>(guard); d.n_partials = n_partials;
+    d.skip_nonfinite = skip_nonfinite != 0; d.adam = kind != FGCN_OPT_SGD;
+    d.max_norm = max_norm; d.lr = (double)lr; d.beta1 = (double)beta1; d.beta2 = (double)beta2;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(grad_sqsum_kernel, dim3((unsigned)n_partials), dim3(GN_THREADS), 0, s, grads, q.n4, grad_scale, partials);
+    hipLaunchKernelGGL(optim_guard_decide_kernel, dim3(1), dim3(GN_THREADS), 0, s, d);
+    optim_launch<true>(q, kind, s);
+    return launch_status("optim_step_guarded");
 }

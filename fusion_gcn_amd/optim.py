@@ -9,10 +9,17 @@ unchanged) -- but re-homes every trainable parameter into ONE contiguous float32
 the data-parallel exchange (``dp.FlatGradients``), and applies the update with a single libfgcn launch
 (``fgcn_optim_step``, include/fgcn.h) whose arithmetic follows torch's formulas operation by operation.
 
+``max_grad_norm=`` / ``skip_nonfinite=`` put a guard in front of that launch that is decided on the device
+(``fgcn_optim_step_guarded``): clipping by the global gradient norm (``torch.nn.utils.clip_grad_norm_`` before ``step()``) and
+the skip of a step whose gradients are not finite, which the reference gets from ``GradScaler.step`` in its
+``MixedPrecisionStep`` (torch_src/session/procedures/step.py:55-78) -- without a host read per step.
+
 No fallback: without libfgcn.so / off gfx950 ``step()`` raises ``FgcnError``.
 """
 from __future__ import annotations
 
+import math
+import numbers
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -32,11 +39,28 @@ class FlatOptimizer(torch.optim.Optimizer):
     ``grads``: an existing ``FlatGradients`` over the same parameters (the data-parallel buffer) to share.
     ``allow_unused``: a trainable parameter without a gradient in a step counts as a zero gradient instead of an error
     (forwarded to the FlatGradients this optimizer creates).
+
+    The guard (both off by default: the plain launch, a host-side step count).  They are attributes of the optimizer, not entries
+    of ``param_groups``: the state dict keeps torch's layout.
+    ``max_grad_norm``: clip by the global norm of the gradient the update applies (``grad_scale`` included), that is
+    ``g *= min(1, max_grad_norm / (norm + 1e-6))`` before weight decay is added -- ``clip_grad_norm_`` followed by ``step()``,
+    with the norm and the coefficient in float64 (gradients of 1e30 have a finite norm and are clipped; torch's float32 norm
+    overflows there).  May be reassigned between steps.
+    ``skip_nonfinite``: a step whose gradient norm is inf or NaN leaves the parameters, the moments and the step count
+    untouched and counts in ``skipped_steps``.
+    The norm, the decision, the step count and Adam's bias corrections are computed on the device; ``step()`` makes no
+    synchronising call.  ``grad_norm`` / ``clip_coef`` are 0-dim float64 device tensors (views of the guard state; reading
+    the attribute never waits for the device).  ``steps``, ``skipped_steps`` and ``clipped_steps`` read device counters and
+    DO wait for the device.  An optimizer that took the guarded path once keeps taking it (its step count lives on the device).
+    Data-parallel runs: ``Step.run_optimizer_step`` all-reduces before it calls ``step()``, so every rank sees the same averaged
+    buffer, computes the same bits from it (the sum has a fixed order) and takes the same decision.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], name: str = "ADAM", lr: float = 1e-3, *,
-                 grads: Optional[FlatGradients] = None, allow_unused: bool = False, **optimizer_args):
+                 grads: Optional[FlatGradients] = None, allow_unused: bool = False, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False, **optimizer_args):
         kind = name.upper()
+        _check_max_grad_norm(max_grad_norm)
         if kind not in KINDS:
             raise ValueError("Unsupported optimizer: " + kind + " (SGD | ADAM | ADAMW)")
         if optimizer_args.get("amsgrad") or optimizer_args.get("maximize"):
@@ -74,8 +98,54 @@ class FlatOptimizer(torch.optim.Optimizer):
         need1 = kind != "SGD" or defaults["momentum"] != 0
         self.state1 = torch.zeros_like(self.flat) if need1 else None       # momentum buffer / exp_avg
         self.state2 = torch.zeros_like(self.flat) if kind != "SGD" else None   # exp_avg_sq
-        self.steps = 0
+        self._steps = 0           # the host-side count of the unguarded path
         self.grad_scale = 1.0     # set to 1/world when the flat gradients hold an un-averaged all-reduce sum
+        # the guard's state (enum fgcn_guard_word) and the partial sums of the norm: allocated once, zero = reset
+        self._guard = torch.zeros(_lib.GUARD_WORDS, dtype=torch.int64, device=self.flat.device)
+        self._partials = torch.zeros(_lib.GRAD_NORM_MAX_TILES, dtype=torch.float64, device=self.flat.device)
+        self.grad_norm = self._guard.view(torch.float64)[_lib.GUARD_NORM]
+        self.clip_coef = self._guard.view(torch.float64)[_lib.GUARD_COEF]
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._max_grad_norm = max_grad_norm
+        self._guarded = max_grad_norm is not None or self.skip_nonfinite
+
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value: Optional[float]) -> None:
+        _check_max_grad_norm(value)
+        self._max_grad_norm = value
+        if value is not None:
+            self._enter_guarded()
+
+    def _enter_guarded(self) -> None:
+        """The step count moves to the device (one fill, no wait) and stays there."""
+        if not self._guarded:
+            self._guard[_lib.GUARD_STEP].fill_(self._steps)
+            self._guarded = True
+
+    @property
+    def steps(self) -> int:
+        """Updates applied so far.  On the guarded path this reads the device counter: it waits for the device."""
+        return int(self._guard[_lib.GUARD_STEP].item()) if self._guarded else self._steps
+
+    @steps.setter
+    def steps(self, value: int) -> None:
+        self._steps = int(value)
+        if self._guarded:
+            self._guard[_lib.GUARD_STEP].fill_(int(value))
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps the guard skipped (gradient norm not finite).  Reads a device counter: it waits for the device."""
+        return int(self._guard[_lib.GUARD_SKIPPED].item())
+
+    @property
+    def clipped_steps(self) -> int:
+        """Applied steps whose clip coefficient was below 1.  Reads a device counter: it waits for the device."""
+        return int(self._guard[_lib.GUARD_CLIPPED].item())
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         if set_to_none:
@@ -95,16 +165,25 @@ class FlatOptimizer(torch.optim.Optimizer):
         lib = _lib.load()
         if not self.flat.is_cuda:
             raise _lib.FgcnError("FlatOptimizer.step needs the parameters on an MI355X (no CPU fallback)")
-        self.steps += 1
+        if self.skip_nonfinite:
+            self._enter_guarded()
         b1, b2 = g.get("betas", (0.0, 0.0))
         s1 = self.state1.data_ptr() if self.state1 is not None else None
         s2 = self.state2.data_ptr() if self.state2 is not None else None
-        rc = lib.fgcn_optim_step(self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, self.flat.numel(),
-                                 KINDS[self.kind], float(g["lr"]), float(g["weight_decay"]), float(self.grad_scale),
-                                 float(b1), float(b2), float(g.get("eps", 0.0)), float(g.get("momentum", 0.0)),
-                                 float(g.get("dampening", 0.0)), int(bool(g.get("nesterov", False))), self.steps,
-                                 torch.cuda.current_stream(self.flat.device).cuda_stream)
-        _lib.check(rc, "fgcn_optim_step")
+        n = self.flat.numel()
+        common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n,
+                  KINDS[self.kind], float(g["lr"]), float(g["weight_decay"]), float(self.grad_scale),
+                  float(b1), float(b2), float(g.get("eps", 0.0)), float(g.get("momentum", 0.0)),
+                  float(g.get("dampening", 0.0)), int(bool(g.get("nesterov", False))))
+        stream = torch.cuda.current_stream(self.flat.device).cuda_stream
+        if self._guarded:         # norm -> decision -> update, stream-ordered; the step count is the device's
+            rc = lib.fgcn_optim_step_guarded(*common, float(self._max_grad_norm or 0.0), int(self.skip_nonfinite),
+                                             self._partials.data_ptr(), lib.fgcn_grad_norm_tiles(n), self._guard.data_ptr(), stream)
+            _lib.check(rc, "fgcn_optim_step_guarded")
+        else:
+            self._steps += 1
+            rc = lib.fgcn_optim_step(*common, self._steps, stream)
+            _lib.check(rc, "fgcn_optim_step")
         # the kernel wrote through raw pointers: tell autograd (and everything keyed on tensor versions, like the blocks'
         # cache of packed weights) that every parameter changed in place -- metadata only, no launches
         for p in self.params:
@@ -132,16 +211,18 @@ class FlatOptimizer(torch.optim.Optimizer):
         return [where[id(p)] for p in self.params]
 
     def state_dict(self) -> Dict:
-        """Same layout as the torch optimizer of that name: {"state": {i: {...}}, "param_groups": [...]}."""
+        """Same layout as the torch optimizer of that name: {"state": {i: {...}}, "param_groups": [...]}.  ``step`` is the count of
+        APPLIED updates (on the guarded path the device counter: skipped steps do not count, as in torch after GradScaler.step)."""
         state = {}
-        if self.steps:
+        steps = self.steps
+        if steps:
             s1 = self._views(self.state1) if self.state1 is not None else None
             s2 = self._views(self.state2) if self.state2 is not None else None
             for i, slot in enumerate(self._slots()):      # torch's layout: state index = position in param_groups[0]["params"]
                 if self.kind == "SGD":
                     state[slot] = {"momentum_buffer": s1[i].clone() if s1 is not None else None}
                 else:
-                    state[slot] = {"step": torch.tensor(float(self.steps)), "exp_avg": s1[i].clone(), "exp_avg_sq": s2[i].clone()}
+                    state[slot] = {"step": torch.tensor(float(steps)), "exp_avg": s1[i].clone(), "exp_avg_sq": s2[i].clone()}
         group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
         group["params"] = list(range(len(self.param_groups[0]["params"])))
         return {"state": state, "param_groups": [group]}
@@ -152,7 +233,7 @@ class FlatOptimizer(torch.optim.Optimizer):
             if k != "params":
                 self.param_groups[0][k] = v
         st = sd.get("state", {})
-        self.steps = 0
+        steps = 0
         if st:
             s1 = self._views(self.state1) if self.state1 is not None else None
             s2 = self._views(self.state2) if self.state2 is not None else None
@@ -162,13 +243,22 @@ class FlatOptimizer(torch.optim.Optimizer):
                     if self.kind == "SGD":
                         if s1 is not None and e.get("momentum_buffer") is not None:
                             s1[i].copy_(e["momentum_buffer"])
-                            self.steps = max(self.steps, 1)
+                            steps = max(steps, 1)
                     else:
                         s1[i].copy_(e["exp_avg"])
                         s2[i].copy_(e["exp_avg_sq"])
-                        self.steps = int(e["step"])
+                        steps = int(e["step"])
+        self.steps = steps          # (guarded: written to the device counter)
+
+
+def _check_max_grad_norm(value) -> None:
+    if value is None:
+        return
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or math.isnan(value) or value <= 0:
+        raise ValueError(f"max_grad_norm must be a positive number or None (got {value!r})")
 
 
 def create_optimizer(name: str, model: torch.nn.Module, lr: float, **optimizer_args) -> FlatOptimizer:
-    """Signature of the reference's session_helper.create_optimizer (torch_src/session_helper.py:80-84)."""
+    """Signature of the reference's session_helper.create_optimizer (torch_src/session_helper.py:80-84); ``max_grad_norm`` and
+    ``skip_nonfinite`` travel in ``optimizer_args`` like every other option of the config."""
     return FlatOptimizer(model.parameters(), name, lr, **optimizer_args)

@@ -45,7 +45,9 @@ class Step(abc.ABC):
     def run_optimizer_step(self, optimizer):
         """``optimizer.step()`` -- after ONE all-reduce (mean) of the flat gradient buffer when a process group with more than one
         rank is active: ``data.ClipBatches`` shards every batch per rank, so without the exchange the replicas would drift apart
-        silently.  The buffer is the optimizer's own (``optim.FlatOptimizer.grads``) or one built lazily over its parameters."""
+        silently.  The buffer is the optimizer's own (``optim.FlatOptimizer.grads``) or one built lazily over its parameters.
+        A ``FlatOptimizer`` with ``max_grad_norm`` / ``skip_nonfinite`` decides inside ``step()``, that is after the exchange, on the
+        averaged buffer: every rank computes the same bits from it (the norm has a fixed summation order) and takes the same decision."""
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             grads = getattr(optimizer, "grads", None)
             if not isinstance(grads, FlatGradients):

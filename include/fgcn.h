@@ -700,6 +700,47 @@ int fgcn_optim_step(float* params, const float* grads, float* state1, float* sta
                     float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
                     float momentum, float dampening, int nesterov, long long step, void* stream);
 
+/* The same update behind a guard that is decided on the device: clip by the global gradient norm (torch.nn.utils.clip_grad_norm_
+ * in front of optimizer.step()) and skip a step whose gradients are not finite (what GradScaler.step does in the reference's
+ * MixedPrecisionStep, torch_src/session/procedures/step.py:55-78).  Three stream-ordered launches, nothing is read back:
+ *   1. partials[w] = sum over workgroup w's elements of ((double)grad_scale * grads[i])^2, float64, plain stores.  Elements are
+ *      assigned to threads and workgroups by index alone and every sum has a fixed order: the same buffer gives the same bits on
+ *      every call.  n_partials must be fgcn_grad_norm_tiles(n) (>= 1, monotone in n, at most FGCN_GRAD_NORM_MAX_TILES).  The square of
+ *      a float32 fits a float64 exactly, so no finite input overflows the sum (1e30 per element has a finite norm here).
+ *   2. one workgroup adds the partials in index order and writes the decision into `guard` (below):
+ *        norm  = sqrt(sum)                                                                   (float64)
+ *        coef  = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1       (clip_grad_norm_'s formula in float64; NaN propagates)
+ *        apply = isfinite(norm) || !skip_nonfinite
+ *      apply:  ++STEP; ++CLIPPED when coef < 1; Adam's step_size = lr / (1 - beta1^STEP) and sqrt(1 - beta2^STEP) in float64 from
+ *              the NEW device-side step count (fgcn_optim_step computes the same on the host); SGD's first step is STEP == 1.
+ *      !apply: ++SKIPPED; STEP and CLIPPED keep their values.  NORM, COEF and APPLY are written on every call.
+ *   3. the update of fgcn_optim_step (the same kernel template) with g = (float)(grad_scale * coef) * grads -- scaled before
+ *      weight decay is added, which is where clip_grad_norm_ sits relative to optimizer.step() -- and step_size / bc2_sqrt /
+ *      first step taken from `guard`; it stores nothing when APPLY is 0: params, state1 and state2 keep their bits.
+ * guard: fgcn_optim_guard_bytes() bytes, 8-byte aligned, FGCN_GUARD_WORDS words of 8 bytes indexed by the enum below; the caller
+ * zeroes it to reset (STEP = 0: the next applied step is the first); the library allocates nothing and keeps no state.
+ * max_norm == 0 switches clipping off; negative or NaN: FGCN_E_BADARG.  FGCN_E_BADARG also for a null partials / guard and a wrong
+ * n_partials; FGCN_E_ALIGN for a guard or partials not 8-byte aligned; everything else as fgcn_optim_step. */
+enum fgcn_guard_word {
+    FGCN_GUARD_STEP = 0,       /* int64: updates applied */
+    FGCN_GUARD_SKIPPED = 1,    /* int64: calls that applied nothing (norm not finite, skip_nonfinite set) */
+    FGCN_GUARD_CLIPPED = 2,    /* int64: applied updates with coef < 1 */
+    FGCN_GUARD_NORM = 3,       /* float64: the last call's norm of grad_scale * grads */
+    FGCN_GUARD_COEF = 4,       /* float64: the last call's clip coefficient */
+    FGCN_GUARD_APPLY = 5,      /* int64 0 / 1: the last call's decision -- this and the next three are what launch 3 reads */
+    FGCN_GUARD_FIRST_STEP = 6, /* int64 0 / 1: STEP == 1 (SGD: the momentum buffer starts as the gradient) */
+    FGCN_GUARD_STEP_SIZE = 7,  /* float64: lr / (1 - beta1^STEP) (Adam / AdamW) */
+    FGCN_GUARD_BC2_SQRT = 8,   /* float64: sqrt(1 - beta2^STEP) (Adam / AdamW) */
+    FGCN_GUARD_WORDS = 9
+};
+#define FGCN_GRAD_NORM_MAX_TILES 512
+int fgcn_grad_norm_tiles(long long n);      /* partial sums launch 1 writes for a buffer of n floats */
+long long fgcn_optim_guard_bytes(void);
+int fgcn_optim_step_guarded(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
+                            float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
+                            float momentum, float dampening, int nesterov, double max_norm, int skip_nonfinite,
+                            double* partials, int n_partials, void* guard, void* stream);
+
 /* ---- MS-G3D data movement ------------------------------------------------------------------
  * (3 x 1) temporal max pooling with padding 1 and stride `stride` (nn.MaxPool2d((3,1), (stride,1), (1,0)) of
  * MultiScale_TemporalConv's pooling branch, models/msg3d/ms_tcn.py:72-78):
