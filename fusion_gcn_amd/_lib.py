@@ -133,7 +133,7 @@ SIGNATURES = {
     "fgcn_joint_gram_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(GramItem), _I, _P]),
     "fgcn_adj_softmax_fwd_wide": (_I, [_P, _I, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "fgcn_adj_softmax_bwd_wide": (_I, [_P, _I, _F, _P, _P, _P, _I, _I, _I, _P]),
-    "fgcn_bn_finalize": (_I, [_P, _I, _LL, _P, _P, _P, _P, _F, _F, _P, _I, _P]),
+    "fgcn_bn_finalize": (_I, [_P, _I, _LL, _P, _P, _P, _P, _F, _F, _P, _I, _P, _I, _LL, _P]),
     "fgcn_bn_eval_coeffs": (_I, [_P, _P, _P, _P, _F, _P, _I, _P]),
     "fgcn_bn_act": (_I, [_P] * 6 + [_LL, _I, _I, _I, _I, _P]),
     "fgcn_tconv_halo_bn_relu": (_I, [_P] * 7 + [_I] * 10 + [_P]),
@@ -166,12 +166,12 @@ SIGNATURES = {
     "fgcn_pw_gemm_tiles": (_I, [_LL]),
     "fgcn_pw_gemm": (_I, [_P] * 5 + [_LL] + [_I] * 5 + [_P, _I, _P]),
     "fgcn_data_bn_tiles": (_I, [_I, _I]),
-    "fgcn_data_bn_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "fgcn_data_bn_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_data_bn_apply": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_data_bn_bwd_reduce": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_data_bn_bwd_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_patch_input_slabs": (_I, [_I, _I, _I, _I, _I]),
-    "fgcn_patch_input_fwd": (_I, [_P] * 8 + [_I] * 10 + [_P]),
+    "fgcn_patch_input_fwd": (_I, [_P] * 8 + [_I] * 11 + [_P]),
     "fgcn_patch_input_bwd": (_I, [_P] * 10 + [_I] * 10 + [_P]),
     "fgcn_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -824,7 +824,8 @@ class DataBNFunction(torch.autograd.Function):
         x = x.contiguous()
         N, M, T, V, C = x.shape
         if train:
-            vec = ops.bn_finalize(ops.data_bn_stats(x), N * T, weight, bias, running_mean, running_var, momentum, eps)
+            vec = ops.bn_finalize(ops.data_bn_stats(x, centered=True), N * T, weight, bias, running_mean, running_var, momentum, eps,
+                                  pivot=x)
         else:
             vec = ops.bn_eval_coeffs(weight, bias, running_mean, running_var, eps)
         ctx.save_for_backward(x, vec)
@@ -862,10 +863,10 @@ class PatchInputFunction(torch.autograd.Function):
                 fusion: str):
         s = None if s is None else s.contiguous()
         p = p.contiguous()
-        z, part = ops.patch_input_fwd(s, p, w1, b1, w2, b2, V=V, fusion=fusion, stats=train)
+        z, part = ops.patch_input_fwd(s, p, w1, b1, w2, b2, V=V, fusion=fusion, stats=train, centered=True)
         N, T, C = z.shape[0], z.shape[2], z.shape[4]
         if train:
-            vec = ops.bn_finalize(part, N * T, weight, bias, running_mean, running_var, momentum, eps)
+            vec = ops.bn_finalize(part, N * T, weight, bias, running_mean, running_var, momentum, eps, pivot=z)
         else:
             vec = ops.bn_eval_coeffs(weight, bias, running_mean, running_var, eps)
         ctx.save_for_backward(z, vec, s, p, w1, b1, w2)

@@ -14,21 +14,30 @@ constexpr int ELEM_MAX_TILES = 1024;    // partial rows of the reduction kernels
 // block = 8 channels x 128 partial-groups (C/8 workgroups, 4 loads in flight per thread: the 7500-tile partial arrays
 // of the headline shape were a 48 us serial walk with 32 groups on C/32 workgroups); double accumulation of the float
 // tile sums, fixed summation order.
+// PIVOT (data_bn's input stage, fgcn_head.hip): a tile has four rows -- the plain sums of x and x^2 as ever, then the sums of (x - p)
+// and (x - p)^2 about p[c] = pivot[(c / pivot_inner) * pivot_outer + c % pivot_inner].  A channel whose offset is no larger than its
+// spread (mean^2 <= var) takes the plain sums, which are exact enough there, so a well-centred input gets bit for bit the statistics
+// it always got; any other channel takes mean = p + a / n, var = b / n - (a / n)^2 from the centred rows, which do not lose var to
+// mean^2.  Without PIVOT the arithmetic is what it always was.
+template <bool PIVOT>
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* partials, int P, long long count,
                                                            const float* gamma, const float* beta, float* rmean,
-                                                           float* rvar, float momentum, float eps, float* out, int C) {
+                                                           float* rvar, float momentum, float eps, float* out, int C,
+                                                           const float* pivot, int pivot_inner, long long pivot_outer) {
+    constexpr int R = PIVOT ? 4 : 2;                     // rows per tile
     __shared__ double s1[128][9], s2[128][9];
+    __shared__ double s3[PIVOT ? 128 : 1][9], s4[PIVOT ? 128 : 1][9];
     const int cl = threadIdx.x & 7, g = threadIdx.x >> 3;
     const int c = blockIdx.x * 8 + cl;
-    double a = 0.0, b = 0.0;
+    double a = 0.0, b = 0.0, ac = 0.0, bc = 0.0;
     if (c < C) {
         int i = g;
         for (; i + 896 < P; i += 1024) {                 // eight row groups (sixteen loads) in flight: the walk is latency-bound
             float x0[8], x1[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                x0[u] = partials[((long long)(i + 128 * u) * 2 + 0) * C + c];
-                x1[u] = partials[((long long)(i + 128 * u) * 2 + 1) * C + c];
+                x0[u] = partials[((long long)(i + 128 * u) * R + 0) * C + c];
+                x1[u] = partials[((long long)(i + 128 * u) * R + 1) * C + c];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -40,8 +49,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* partials
             float x0[4], x1[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                x0[u] = partials[((long long)(i + 128 * u) * 2 + 0) * C + c];
-                x1[u] = partials[((long long)(i + 128 * u) * 2 + 1) * C + c];
+                x0[u] = partials[((long long)(i + 128 * u) * R + 0) * C + c];
+                x1[u] = partials[((long long)(i + 128 * u) * R + 1) * C + c];
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -50,12 +59,22 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* partials
             }
         }
         for (; i < P; i += 128) {
-            a += (double)partials[((long long)i * 2 + 0) * C + c];
-            b += (double)partials[((long long)i * 2 + 1) * C + c];
+            a += (double)partials[((long long)i * R + 0) * C + c];
+            b += (double)partials[((long long)i * R + 1) * C + c];
+        }
+        if (PIVOT) {
+            for (i = g; i < P; i += 128) {
+                ac += (double)partials[((long long)i * R + 2) * C + c];
+                bc += (double)partials[((long long)i * R + 3) * C + c];
+            }
         }
     }
     s1[g][cl] = a;
     s2[g][cl] = b;
+    if (PIVOT) {
+        s3[g][cl] = ac;
+        s4[g][cl] = bc;
+    }
     __syncthreads();
     // the 128 group sums of a channel: a fixed tree (seven steps) instead of one thread's walk over 127 dependent LDS reads (~4 us of a ~19 us
     // launch that runs 26 times per step, and whose time does not shrink with the batch)
@@ -82,9 +101,22 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* partials
             b += s2[i][cl];
         }
 #endif
-        const double mean = a / (double)count;
+        double mean = a / (double)count;
         double var = b / (double)count - mean * mean;
         if (var < 0.0) var = 0.0;
+        if (PIVOT) {
+            for (int i = 1; i < 128; ++i) {
+                ac += s3[i][cl];
+                bc += s4[i][cl];
+            }
+            const double off = ac / (double)count;
+            double var_c = bc / (double)count - off * off;
+            if (var_c < 0.0) var_c = 0.0;
+            if (!(mean * mean <= var_c)) {
+                mean = (double)pivot[(long long)(c / pivot_inner) * pivot_outer + c % pivot_inner] + off;
+                var = var_c;
+            }
+        }
         const float rstd = (float)(1.0 / sqrt(var + (double)eps));
         const float scale = gamma[c] * rstd;
         out[0 * C + c] = (float)mean;
@@ -686,11 +718,19 @@ static unsigned stream_blocks(long long n4) {
 
 extern "C" int fgcn_bn_finalize(const float* partials, int n_partials, long long count, const float* gamma,
                                 const float* beta, float* running_mean, float* running_var, float momentum, float eps,
-                                float* out_vec, int C, void* stream) {
+                                float* out_vec, int C, const float* pivot, int pivot_inner, long long pivot_outer,
+                                void* stream) {
     FGCN_REQUIRE(partials && gamma && beta && out_vec && n_partials > 0 && count > 0 && C > 0, FGCN_E_BADARG,
                  "bn_finalize: bad argument");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)cdiv(C, 8)), dim3(1024), 0, (hipStream_t)stream, partials,
-                       n_partials, count, gamma, beta, running_mean, running_var, momentum, eps, out_vec, C);
+    FGCN_REQUIRE(!pivot || (pivot_inner > 0 && pivot_outer >= pivot_inner), FGCN_E_BADARG,
+                 "bn_finalize: a pivot needs pivot_inner > 0 and pivot_outer >= pivot_inner (got %d, %lld)", pivot_inner, pivot_outer);
+    if (pivot)
+        hipLaunchKernelGGL(bn_finalize_kernel<true>, dim3((unsigned)cdiv(C, 8)), dim3(1024), 0, (hipStream_t)stream, partials,
+                           n_partials, count, gamma, beta, running_mean, running_var, momentum, eps, out_vec, C, pivot, pivot_inner,
+                           pivot_outer);
+    else
+        hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3((unsigned)cdiv(C, 8)), dim3(1024), 0, (hipStream_t)stream, partials,
+                           n_partials, count, gamma, beta, running_mean, running_var, momentum, eps, out_vec, C, nullptr, 1, 0ll);
     return launch_status("bn_finalize");
 }
 

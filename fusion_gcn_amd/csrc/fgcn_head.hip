@@ -12,22 +12,37 @@ namespace fgcn {
 
 constexpr int DBN_T_CHUNK = 32;     // frames per tile: N * ceil(T / 32) tiles (640 at the headline shape)
 
-// partials[tile][0][ch] = sum x, [tile][1][ch] = sum x^2 over the tile's frames of clip n; thread <-> channel, so consecutive
-// threads of one body m read consecutive floats of a frame row
-__global__ __launch_bounds__(256) void data_bn_stats_kernel(const float* x, float* partials, int M, int T, int VC, int chunks) {
+// partials[tile][0][ch] = sum x, [tile][1][ch] = sum x^2 over the tile's frames of clip n.  `centered`: a tile has four rows, and
+// [tile][2][ch] = sum (x - p), [tile][3][ch] = sum (x - p)^2 about p[ch] = x[n = 0][m][t = 0][v][c], a sample of the channel itself
+// (data, not a statistic: every tile reads it from the input, no launch or host read in front), so those sums carry the channel's
+// spread and not its offset -- raw sensor units (metres, pixels, gravity) enter here, and a float32 sum of x^2 loses var to mean^2;
+// fgcn_bn_finalize chooses per channel (pivot = x, inner = V*C, outer = T*V*C).  The differences are exact in double and the <= 32
+// terms of a tile are summed in double: the one rounding per tile is the float32 store, and a constant channel gives exact zeros
+// about its pivot.  thread <-> channel, so consecutive threads of one body m read consecutive floats of a frame row
+__global__ __launch_bounds__(256) void data_bn_stats_kernel(const float* x, float* partials, int M, int T, int VC, int chunks,
+                                                            int centered) {
     const int n = blockIdx.x / chunks, t0 = (blockIdx.x % chunks) * DBN_T_CHUNK;
-    const int t1 = min(t0 + DBN_T_CHUNK, T), MVC = M * VC;
+    const int t1 = min(t0 + DBN_T_CHUNK, T), MVC = M * VC, R = centered ? 4 : 2;
     for (int ch = threadIdx.x; ch < MVC; ch += blockDim.x) {
         const int m = ch / VC, vc = ch - m * VC;
+        const double pivot = centered ? (double)x[(long long)m * T * VC + vc] : 0.0;
         const float* p = x + ((long long)(n * M + m) * T + t0) * VC + vc;
         float s1 = 0.f, s2 = 0.f;
+        double c1 = 0.0, c2 = 0.0;
         for (int t = t0; t < t1; ++t, p += VC) {
             const float v = *p;
             s1 += v;
             s2 += v * v;
+            const double d = (double)v - pivot;
+            c1 += d;
+            c2 += d * d;
         }
-        partials[((long long)blockIdx.x * 2 + 0) * MVC + ch] = s1;
-        partials[((long long)blockIdx.x * 2 + 1) * MVC + ch] = s2;
+        partials[((long long)blockIdx.x * R + 0) * MVC + ch] = s1;
+        partials[((long long)blockIdx.x * R + 1) * MVC + ch] = s2;
+        if (centered) {
+            partials[((long long)blockIdx.x * R + 2) * MVC + ch] = (float)c1;
+            partials[((long long)blockIdx.x * R + 3) * MVC + ch] = (float)c2;
+        }
     }
 }
 
@@ -175,12 +190,12 @@ static int check_dbn(const char* what, int N, int M, int T, int V, int C, int Cp
     return FGCN_OK;
 }
 
-extern "C" int fgcn_data_bn_stats(const float* x, float* partials, int N, int M, int T, int V, int C, void* stream) {
+extern "C" int fgcn_data_bn_stats(const float* x, float* partials, int N, int M, int T, int V, int C, int centered, void* stream) {
     FGCN_REQUIRE(x && partials, FGCN_E_BADARG, "data_bn_stats: null pointer");
     if (int e = check_dbn("data_bn_stats", N, M, T, V, C, C)) return e;
     const int chunks = (int)cdiv(T, DBN_T_CHUNK);
     hipLaunchKernelGGL(data_bn_stats_kernel, dim3((unsigned)(N * chunks)), dim3(256), 0, (hipStream_t)stream, x, partials, M, T, V * C,
-                       chunks);
+                       chunks, centered);
     return launch_status("data_bn_stats");
 }
 

@@ -343,7 +343,7 @@ extern "C" int fgcn_patch_input_slabs(int N, int M, int T, int Vp, int H) {
 
 extern "C" int fgcn_patch_input_fwd(const float* s, const float* p, const float* w1, const float* b1, const float* w2, const float* b2,
                                     float* z, float* stat_partials, int N, int M, int T, int V, int Vp, int Cs, int P, int H, int Q,
-                                    int fusion, void* stream) {
+                                    int fusion, int stat_centered, void* stream) {
     FGCN_REQUIRE(z, FGCN_E_BADARG, "patch_input_fwd: null output");
     if (int e = check_patch("patch_input_fwd", s, p, w1, b1, w2, b2, N, M, T, V, Vp, Cs, P, H, Q, fusion, false)) return e;
     PatchArgs a = patch_args(s, p, w1, b1, w2, b2, N, M, T, V, Vp, Cs, P, H, Q, fusion);
@@ -355,7 +355,7 @@ extern "C" int fgcn_patch_input_fwd(const float* s, const float* p, const float*
     if (bf) hipLaunchKernelGGL(patch_input_fwd_kernel<true>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(patch_input_fwd_kernel<false>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     if (int e = launch_status("patch_input_fwd")) return e;
-    return stat_partials ? fgcn_data_bn_stats(z, stat_partials, N, M, T, V, a.C, stream) : FGCN_OK;
+    return stat_partials ? fgcn_data_bn_stats(z, stat_partials, N, M, T, V, a.C, stat_centered, stream) : FGCN_OK;
 }
 
 extern "C" int fgcn_patch_input_bwd(const float* dz, const float* s, const float* p, const float* w1, const float* b1, const float* w2,

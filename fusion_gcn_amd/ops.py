@@ -1002,14 +1002,25 @@ def adj_softmax_bwd(partial: torch.Tensor, scale: float, c_in: Optional[torch.Te
 
 # ---- BatchNorm / epilogues -------------------------------------------------------------------------------------------
 def bn_finalize(partials: torch.Tensor, count: int, gamma, beta, running_mean=None, running_var=None,
-                momentum: float = 0.1, eps: float = 1e-5) -> torch.Tensor:
-    """-> vec (4, C) = mean, rstd, scale, shift; updates running stats in place when given."""
+                momentum: float = 0.1, eps: float = 1e-5, pivot: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> vec (4, C) = mean, rstd, scale, shift; updates running stats in place when given.
+    ``pivot``: the (N, M, T, V, C) tensor ``data_bn_stats(..., centered=True)`` ran over -- those four-row partials also hold the sums
+    about the sample x[0, m, 0, v, c] of each channel, which a channel with an offset larger than its spread is finalised from;
+    two-row partials (every other producer's) take none."""
     ensure_device()
     _chk(partials, "bn_finalize.partials")
     C = partials.shape[-1]
+    inner = outer = 0
+    if pivot is not None:
+        _chk(pivot, "bn_finalize.pivot")
+        if pivot.dim() != 5 or pivot.shape[1] * pivot.shape[3] * pivot.shape[4] != C or partials.shape[1] != 4:
+            raise _lib.FgcnError(f"bn_finalize: pivot {tuple(pivot.shape)} is not an (N, M, T, V, C) tensor of {C} (m, v, c) channels, "
+                                 f"or the partials {tuple(partials.shape)} are not data_bn_stats(centered=True)'s")
+        inner, outer = pivot.shape[3] * pivot.shape[4], pivot.shape[2] * pivot.shape[3] * pivot.shape[4]
     vec = torch.empty((4, C), device=partials.device, dtype=torch.float32)
     check(_lib.load().fgcn_bn_finalize(_p(partials), partials.shape[0], count, _p(gamma), _p(beta), _p(running_mean),
-                                       _p(running_var), momentum, eps, _p(vec), C, _stream()), "fgcn_bn_finalize")
+                                       _p(running_var), momentum, eps, _p(vec), C, _p(pivot), inner, outer, _stream()),
+          "fgcn_bn_finalize")
     return vec
 
 
@@ -1187,14 +1198,16 @@ def group_mean(x: torch.Tensor) -> torch.Tensor:
 
 
 # ---- the two ends of the step: input BatchNorm and loss (fgcn_head.hip) ---------------------------------------------------------
-def data_bn_stats(x: torch.Tensor) -> torch.Tensor:
-    """x (N, M, T, V, C) -> BatchNorm partial sums (tiles, 2, M*V*C) of the (m, v, c) channels over (n, t)."""
+def data_bn_stats(x: torch.Tensor, centered: bool = False) -> torch.Tensor:
+    """x (N, M, T, V, C) -> BatchNorm partial sums (tiles, 2, M*V*C) of the (m, v, c) channels over (n, t): per tile (sum x, sum x^2);
+    with ``centered`` (tiles, 4, M*V*C): those two and the same sums of x - p about each channel's sample p = x[0, m, 0, v, c] (from
+    which the variance does not lose digits to the channel's offset): finalize them with ``bn_finalize(..., pivot=x)``."""
     ensure_device()
     _chk(x, "data_bn_stats.x")
     N, M, T, V, C = x.shape
     lib = _lib.load()
-    part = torch.empty((lib.fgcn_data_bn_tiles(N, T), 2, M * V * C), device=x.device, dtype=torch.float32)
-    check(lib.fgcn_data_bn_stats(_p(x), _p(part), N, M, T, V, C, _stream()), "fgcn_data_bn_stats")
+    part = torch.empty((lib.fgcn_data_bn_tiles(N, T), 4 if centered else 2, M * V * C), device=x.device, dtype=torch.float32)
+    check(lib.fgcn_data_bn_stats(_p(x), _p(part), N, M, T, V, C, int(centered), _stream()), "fgcn_data_bn_stats")
     return part
 
 
@@ -1247,9 +1260,10 @@ def _patch_dims(s: Optional[torch.Tensor], p: torch.Tensor, w1: Optional[torch.T
 
 
 def patch_input_fwd(s: Optional[torch.Tensor], p: torch.Tensor, w1: Optional[torch.Tensor], b1: Optional[torch.Tensor],
-                    w2: Optional[torch.Tensor], b2: Optional[torch.Tensor], *, V: int, fusion: str, stats: bool = True):
+                    w2: Optional[torch.Tensor], b2: Optional[torch.Tensor], *, V: int, fusion: str, stats: bool = True,
+                    centered: bool = False):
     """s (N, M, T, V, Cs) or None, p (N, M, T, Vp, P), reducer (w1, b1, w2, b2) or all None (identity) -> (z (N, M, T, V, C), data_bn
-    statistics partials of z (tiles, 2, M*V*C) or None)."""
+    statistics partials of z (tiles, 2 or 4, M*V*C) or None): what ``data_bn_stats(z, centered)`` gives."""
     ensure_device()
     N, M, T, Vp, P, Cs, H, Q = _patch_dims(s, p, w1, w2, V, fusion)
     for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")):
@@ -1258,9 +1272,10 @@ def patch_input_fwd(s: Optional[torch.Tensor], p: torch.Tensor, w1: Optional[tor
     C = Cs + Q if fusion == "concatenate" else Cs
     lib = _lib.load()
     z = torch.empty((N, M, T, V, C), device=p.device, dtype=torch.float32)
-    part = (torch.empty((lib.fgcn_data_bn_tiles(N, T), 2, M * V * C), device=p.device, dtype=torch.float32) if stats else None)
+    part = (torch.empty((lib.fgcn_data_bn_tiles(N, T), 4 if centered else 2, M * V * C), device=p.device, dtype=torch.float32)
+            if stats else None)
     check(lib.fgcn_patch_input_fwd(_p(s), _p(p), _p(w1), _p(b1), _p(w2), _p(b2), _p(z), _p(part), N, M, T, V, Vp, Cs, P, H, Q,
-                                   PATCH_FUSIONS[fusion], _stream()), "fgcn_patch_input_fwd")
+                                   PATCH_FUSIONS[fusion], int(centered), _stream()), "fgcn_patch_input_fwd")
     return z, part
 
 

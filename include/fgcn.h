@@ -489,10 +489,15 @@ int fgcn_adj_softmax_bwd_wide(const float* partial, int nchunk, float scale, con
 /* ---- BatchNorm / activation epilogues ------------------------------------------------------------------ */
 /* mean/var from row-tile partials -> scale = gamma*rstd, shift = beta - mean*scale, and the running-stat update
  * (momentum, unbiased variance) of nn.BatchNorm2d in train mode (agcn.py:44,78,83; torch defaults eps 1e-5, 0.1).
- * out_vec: float[4][C] = {mean, rstd, scale, shift}.  running_* may be NULL. */
+ * out_vec: float[4][C] = {mean, rstd, scale, shift}.  running_* may be NULL.
+ * pivot (may be NULL: partials float[n_partials][2][C], pivot_inner / pivot_outer ignored): the partials are
+ * fgcn_data_bn_stats(centered != 0)'s, float[n_partials][4][C] = per tile the sums of x, x^2, x - p and (x - p)^2 about the per-channel
+ * pivot p[c] = pivot[(c / pivot_inner) * pivot_outer + c % pivot_inner].  A channel whose offset is no larger than its spread
+ * (mean^2 <= var) is finalised from the first two rows, exactly as without a pivot; any other channel from the centred rows,
+ * mean = p + a / n, var = b / n - (a / n)^2, so its variance does not lose digits to its offset and a constant channel gets 0. */
 int fgcn_bn_finalize(const float* partials, int n_partials, long long count, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, float momentum, float eps,
-                     float* out_vec, int C, void* stream);
+                     float* out_vec, int C, const float* pivot, int pivot_inner, long long pivot_outer, void* stream);
 /* eval mode: scale/shift from running statistics; out_vec as above (mean = running_mean, rstd = 1/sqrt(var+eps)) */
 int fgcn_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                         float eps, float* out_vec, int C, void* stream);
@@ -778,12 +783,16 @@ int fgcn_pw_gemm(const void* in, void* out, const void* w3, const float* bias, f
  * `data_bn` = nn.BatchNorm1d(M*V*C) over the network input x (N, M, T, V, C) viewed as (N, M*V*C, T)
  * (torch_src/models/mmargcn/agcn.py:150,186-188; msg3d.py:93,152-154): channel ch = (m*V + v)*C + c, statistics over (n, t).
  *   stats:      partials float[fgcn_data_bn_tiles(N, T)][2][M*V*C] (sum x, sum x^2 per tile) -> fgcn_bn_finalize(count = N*T)
- *               gives vec float[4][M*V*C] and updates the running statistics;
+ *               gives vec float[4][M*V*C] and updates the running statistics.  centered != 0 (what block.data_bn runs): partials
+ *               float[tiles][4][M*V*C], rows 2 and 3 = the sums of x - p and (x - p)^2 about the channel's pivot
+ *               p[ch] = x[0][m][0][v][c], a sample of the channel -- raw sensor units enter here, and sums about a sample carry
+ *               the channel's spread, not its offset -> fgcn_bn_finalize(count = N*T, pivot = x, pivot_inner = V*C,
+ *               pivot_outer = T*V*C);
  *   apply:      out (N*M, T, V, Cp) = x * scale[ch] + shift[ch], channels [C, Cp) zero -- the blocks' input layout, written directly;
  *   bwd_reduce: partials float[tiles][2][M*V*C] = (sum dout, sum dout * xhat) -> fgcn_reduce_sum -> (d beta, d gamma);
  *   bwd_apply:  dx (N, M, T, V, C) = scale * (dout - sum0/m - xhat * sum1/m), m = N*T (train) | scale * dout (eval). */
 int fgcn_data_bn_tiles(int N, int T);
-int fgcn_data_bn_stats(const float* x, float* partials, int N, int M, int T, int V, int C, void* stream);
+int fgcn_data_bn_stats(const float* x, float* partials, int N, int M, int T, int V, int C, int centered, void* stream);
 int fgcn_data_bn_apply(const float* x, const float* vec, float* out, int N, int M, int T, int V, int C, int Cp, void* stream);
 int fgcn_data_bn_bwd_reduce(const float* dout, const float* x, const float* vec, float* partials, int N, int M, int T, int V,
                             int C, int Cp, void* stream);
@@ -797,8 +806,9 @@ int fgcn_data_bn_bwd_apply(const float* dout, const float* x, const float* vec, 
  *   s  (N, M, T, V, Cs) skeleton rows, or NULL with Cs = 0 (concatenate only);  p (N, M, T, Vp, P) patch rows, Vp <= V;
  *   w1 (H, P), b1 (H), w2 (Q, H), b2 (Q): the two nn.Linear in their own layout, or w1 = b1 = w2 = b2 = NULL: the identity (Q = P);
  *   fusion: 0 concatenate z = [s | q] (C = Cs + Q), 1 sum s + q, 2 product s * q, 3 average (s + q) / 2 (1..3: C = Cs = Q);
- *   z  (N, M, T, V, C): the fused network input, q = 0 for v >= Vp;  stat_partials (may be NULL): what fgcn_data_bn_stats(z) writes,
- *      float[fgcn_data_bn_tiles(N, T)][2][M*V*C] (it is that kernel, run over z) -> fgcn_bn_finalize / fgcn_data_bn_apply unchanged.
+ *   z  (N, M, T, V, C): the fused network input, q = 0 for v >= Vp;  stat_partials (may be NULL): what
+ *      fgcn_data_bn_stats(z, ..., stat_centered) writes, float[fgcn_data_bn_tiles(N, T)][2 or 4][M*V*C] (it is that kernel, run over z)
+ *      -> fgcn_bn_finalize (stat_centered: with pivot = z) / fgcn_data_bn_apply unchanged.
  * The hidden (rows, H) tensor stays in registers.  Sizes with a reducer: P a multiple of 128 up to 1024, H a multiple of 32 up to 1024,
  * 1 <= Q <= 32; others are FGCN_E_BADARG.  Math mode: FGCN_MATH_BF16 rounds every operand to bfloat16 once; every other mode (and
  * product form) multiplies exact float32 operands on v_mfma_f32_32x32x2_f32.
@@ -807,7 +817,8 @@ int fgcn_data_bn_bwd_apply(const float* dout, const float* x, const float* vec, 
  *      recomputed from p; s is read for the product's derivative; s and p get no gradient (data).  Identity reducer: nothing to do. */
 int fgcn_patch_input_slabs(int N, int M, int T, int Vp, int H);
 int fgcn_patch_input_fwd(const float* s, const float* p, const float* w1, const float* b1, const float* w2, const float* b2, float* z,
-                         float* stat_partials, int N, int M, int T, int V, int Vp, int Cs, int P, int H, int Q, int fusion, void* stream);
+                         float* stat_partials, int N, int M, int T, int V, int Vp, int Cs, int P, int H, int Q, int fusion,
+                         int stat_centered, void* stream);
 int fgcn_patch_input_bwd(const float* dz, const float* s, const float* p, const float* w1, const float* b1, const float* w2, float* pw1,
                          float* pb1, float* pw2, float* pb2, int N, int M, int T, int V, int Vp, int Cs, int P, int H, int Q, int fusion,
                          void* stream);

@@ -62,6 +62,10 @@ def test_host_side_validation(lib):
     assert lib.fgcn_bn_act_bwd_reduce(p16, 0, p16, None, p16, p16, None, None, p16, 7, 1000, 64, 0, 1, 0, None) == -1   # needs 16 tiles
     assert lib.fgcn_elem_tiles(1000) == 16 and lib.fgcn_elem_tiles(10 ** 7) == 1024 and lib.fgcn_rows_gemm_tiles(129) == 2
     assert lib.fgcn_spatial_tiles(128, 300) == 128 * 10
+    # bn finalize: a pivot (the centred partials of fgcn_data_bn_stats) comes with its geometry
+    assert lib.fgcn_bn_finalize(p16, 1, 10, p16, p16, None, None, 0.1, 1e-5, p16, 8, p16, 0, 0, None) == -1
+    assert b"pivot" in lib.fgcn_last_error()
+    assert lib.fgcn_bn_finalize(p16, 1, 10, p16, p16, None, None, 0.1, 1e-5, p16, 8, p16, 8, 4, None) == -1
     # half_mask (half-precision activation storage): a mask the kernel is not built for, and bfloat16 tensors outside math mode bf16
     halo = (p16, p16, p16, None, None, 1, 4, 25, 32, 32, 32, 32, 4, 1, 0, 4, 4, 1, 0, 9, 1, -4)      # ... up to tc; then accumulate, 8 pointers
     assert lib.fgcn_bn_act(p16, p16, None, None, p16, None, 16, 8, 0, 1, 8, None) == -1                  # bit 3 does not exist
