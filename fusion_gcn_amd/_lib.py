@@ -65,6 +65,16 @@ class ReduceItem(C.Structure):
 
 REDUCE_MAX_ITEMS = 8        # FGCN_REDUCE_MAX_ITEMS
 
+
+class OptimGroup(C.Structure):
+    """fgcn_optim_group: the scalars of one parameter group of the grouped optimizer step."""
+    _fields_ = [("lr", C.c_float), ("weight_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int)]
+
+
+OPT_MAX_GROUPS = 8          # FGCN_OPT_MAX_GROUPS
+OPT_TILE4 = 1024            # FGCN_OPT_TILE4: 16-byte groups per row of the tile table, at most
+
 _I, _LL, _F, _D, _P = C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/fgcn.h one to one.  The fifteen kernels that take bfloat16 activation tensors carry `half_mask`
@@ -179,6 +189,8 @@ SIGNATURES = {
     "fgcn_grad_norm_tiles": (_I, [_LL]),
     "fgcn_optim_guard_bytes": (_LL, []),
     "fgcn_optim_step_guarded": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _D, _I, _P, _I, _P, _P]),
+    "fgcn_optim_step_groups": (_I, [_P, _P, _P, _P, _LL, _I, C.POINTER(OptimGroup), _I, _P, _I, _F, _LL, _P]),
+    "fgcn_optim_step_groups_guarded": (_I, [_P, _P, _P, _P, _LL, _I, C.POINTER(OptimGroup), _I, _P, _I, _F, _D, _I, _P, _I, _P, _P, _P]),
     "fgcn_classify_state_bytes": (_LL, [_I]),
     "fgcn_classify_update": (_I, [_P, _P, _P, _P, _P, _LL, _LL, _I, _I, _I, _I, _P]),
 }

@@ -14,13 +14,19 @@ the data-parallel exchange (``dp.FlatGradients``), and applies the update with a
 the skip of a step whose gradients are not finite, which the reference gets from ``GradScaler.step`` in its
 ``MixedPrecisionStep`` (torch_src/session/procedures/step.py:55-78) -- without a host read per step.
 
+Parameter groups (a list of dicts, as every ``torch.optim.Optimizer`` takes; ``create_optimizer(..., param_groups=[{"match": regex,
+...}])`` from a config) keep all of that: still one update launch (``fgcn_optim_step_groups``), which group an element belongs to
+comes from a tile table built and uploaded once at construction, the groups' scalars travel by value with every launch.
+
 No fallback: without libfgcn.so / off gfx950 ``step()`` raises ``FgcnError``.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import numbers
-from typing import Dict, Iterable, Optional
+import re
+from typing import Dict, Iterable, List, Optional
 
 import torch
 
@@ -28,20 +34,27 @@ from . import _lib
 from .dp import FlatGradients
 
 KINDS = {"SGD": 0, "ADAM": 1, "ADAMW": 2}     # FGCN_OPT_* (include/fgcn.h); names as in session_helper.available_optimizers
+MAX_GROUPS = _lib.OPT_MAX_GROUPS              # FGCN_OPT_MAX_GROUPS
 
 
 class FlatOptimizer(torch.optim.Optimizer):
     """``FlatOptimizer(model.parameters(), "ADAM", lr, weight_decay=0.01)`` == ``create_optimizer("ADAM", model, lr, ...)``.
 
     Supported ``optimizer_args`` (torch names and defaults): SGD ``momentum, dampening, weight_decay, nesterov``;
-    ADAM / ADAMW ``betas, eps, weight_decay`` (AdamW's default decay is 0.01).  ``amsgrad`` / ``maximize`` and more than
-    one parameter group are not built (the reference uses neither) and raise.
-    ``grads``: an existing ``FlatGradients`` over the same parameters (the data-parallel buffer) to share.
+    ADAM / ADAMW ``betas, eps, weight_decay`` (AdamW's default decay is 0.01).  ``amsgrad`` / ``maximize`` are not built (the
+    reference does not use them) and raise.
+    ``params``: an iterable of parameters, or torch's list of group dicts -- ``{"params": [...], "lr": ..., "weight_decay": ...}`` with
+    any of the kind's scalars above as overrides; one kind for all groups, at most ``MAX_GROUPS`` (8) of them.  The groups are final:
+    ``add_param_group`` on a built optimizer raises (it would have to re-home parameters into live flat buffers).  The order of the
+    flat buffers is the order of the ``FlatGradients`` in use -- the concatenation of the groups for the optimizer's own, the model's
+    order for a shared one, where the groups interleave; ``_group_of`` maps every tensor to its group.
+    ``grads``: an existing ``FlatGradients`` over the trainable parameters of all groups (the data-parallel buffer) to share.
     ``allow_unused``: a trainable parameter without a gradient in a step counts as a zero gradient instead of an error
     (forwarded to the FlatGradients this optimizer creates).
 
     The guard (both off by default: the plain launch, a host-side step count).  They are attributes of the optimizer, not entries
-    of ``param_groups``: the state dict keeps torch's layout.
+    of ``param_groups``: the state dict keeps torch's layout.  With several groups the norm is still the global one over all of them
+    (``clip_grad_norm_(model.parameters())``), a skipped step skips every group, and there is one step count.
     ``max_grad_norm``: clip by the global norm of the gradient the update applies (``grad_scale`` included), that is
     ``g *= min(1, max_grad_norm / (norm + 1e-6))`` before weight decay is added -- ``clip_grad_norm_`` followed by ``step()``,
     with the norm and the coefficient in float64 (gradients of 1e30 have a finite norm and are clipped; torch's float32 norm
@@ -74,19 +87,34 @@ class FlatOptimizer(torch.optim.Optimizer):
         if unknown:
             raise TypeError(f"{kind}: unexpected optimizer_args {sorted(unknown)}")
         defaults.update({k: v for k, v in optimizer_args.items() if k in defaults})
-        if lr < 0 or defaults["weight_decay"] < 0:
-            raise ValueError("negative lr / weight_decay")
-        if kind == "SGD" and defaults["nesterov"] and (defaults["momentum"] <= 0 or defaults["dampening"] != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        _check_group(kind, defaults)
         params = list(params)
         if params and isinstance(params[0], dict):
-            raise NotImplementedError("FlatOptimizer takes one parameter group (as the reference's create_optimizer)")
-        super().__init__(params, defaults)
+            if len(params) > MAX_GROUPS:
+                raise ValueError(f"FlatOptimizer takes at most {MAX_GROUPS} parameter groups (FGCN_OPT_MAX_GROUPS), got {len(params)}")
+            for i, group in enumerate(params):
+                if group.get("amsgrad") or group.get("maximize"):
+                    raise NotImplementedError("amsgrad / maximize are not built")
+                unknown = set(group) - set(defaults) - {"params", "amsgrad", "maximize"}
+                if unknown:
+                    raise TypeError(f"{kind}: unexpected optimizer_args {sorted(unknown)} in parameter group {i}")
+            params = [{k: v for k, v in group.items() if k not in ("amsgrad", "maximize")} for group in params]
+        self._built = False
+        super().__init__(params, defaults)      # (calls add_param_group once per group; a parameter in two groups is torch's error)
+        for group in self.param_groups:
+            _check_group(kind, group)
+        self._built = True
         self.kind = kind
-        self.grads = grads if grads is not None else FlatGradients(self.param_groups[0]["params"], allow_unused=allow_unused)
-        self.params = self.grads.params                      # trainable parameters, in order
-        if grads is not None and [id(p) for p in self.params] != [id(p) for p in self.param_groups[0]["params"] if p.requires_grad]:
-            raise ValueError("the shared FlatGradients must cover the same parameters in the same order")
+        every = [p for group in self.param_groups for p in group["params"]]
+        self.grads = grads if grads is not None else FlatGradients(every, allow_unused=allow_unused)
+        self.params = self.grads.params                      # trainable parameters, in the order of the flat buffers
+        if len(self.param_groups) == 1:
+            if grads is not None and [id(p) for p in self.params] != [id(p) for p in every if p.requires_grad]:
+                raise ValueError("the shared FlatGradients must cover the same parameters in the same order")
+        elif grads is not None and sorted(id(p) for p in self.params) != sorted(id(p) for p in every if p.requires_grad):
+            raise ValueError("the shared FlatGradients must cover exactly the trainable parameters of all groups")
+        group_index = {id(p): i for i, group in enumerate(self.param_groups) for p in group["params"]}
+        self._group_of: List[int] = [group_index[id(p)] for p in self.params]       # per tensor of the flat buffers
         # one contiguous home for the parameter values, laid out like the gradient buffer (16-byte aligned views)
         self.flat = torch.zeros_like(self.grads.flat)
         with torch.no_grad():
@@ -95,7 +123,7 @@ class FlatOptimizer(torch.optim.Optimizer):
                 home = self.flat[off:off + p.numel()].view_as(p)
                 home.copy_(p)
                 p.data = home
-        need1 = kind != "SGD" or defaults["momentum"] != 0
+        need1 = kind != "SGD" or any(group["momentum"] != 0 for group in self.param_groups)
         self.state1 = torch.zeros_like(self.flat) if need1 else None       # momentum buffer / exp_avg
         self.state2 = torch.zeros_like(self.flat) if kind != "SGD" else None   # exp_avg_sq
         self._steps = 0           # the host-side count of the unguarded path
@@ -108,6 +136,30 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.skip_nonfinite = bool(skip_nonfinite)
         self._max_grad_norm = max_grad_norm
         self._guarded = max_grad_norm is not None or self.skip_nonfinite
+        # several groups: the element-to-group table and the per-group step sizes of the guarded form, built and uploaded ONCE
+        self._tiles = self._sched = None
+        if len(self.param_groups) > 1:
+            self._tiles = torch.tensor(self.tile_table(), dtype=torch.int32).to(self.flat.device)
+            self._sched = torch.zeros(2 * MAX_GROUPS, dtype=torch.float64, device=self.flat.device)
+
+    def add_param_group(self, param_group) -> None:
+        if getattr(self, "_built", False):
+            raise NotImplementedError("FlatOptimizer must be built with its final parameter groups: add_param_group on a built "
+                                      "optimizer would re-home parameters into live flat buffers, which is not built")
+        super().add_param_group(param_group)
+
+    def tile_table(self, tile4: int = _lib.OPT_TILE4) -> List[List[int]]:
+        """Rows ``[start4, count4, group]`` of fgcn_optim_step_groups' table (units: 16-byte groups of the flat buffers): runs of
+        consecutive tensors of one group, cut into rows of at most ``tile4``.  A tensor's last 16-byte group carries its <= 3 floats
+        of alignment padding, so the rows cover the buffers exactly once."""
+        runs: List[List[int]] = []
+        for p, v, gi in zip(self.params, self.grads.views, self._group_of):
+            start4, count4 = v.storage_offset() // 4, (p.numel() + 3) // 4
+            if runs and runs[-1][2] == gi and runs[-1][0] + runs[-1][1] == start4:
+                runs[-1][1] += count4
+            else:
+                runs.append([start4, count4, gi])
+        return [[s + o, min(tile4, c - o), gi] for s, c, gi in runs for o in range(0, c, tile4)]
 
     @property
     def max_grad_norm(self) -> Optional[float]:
@@ -161,29 +213,41 @@ class FlatOptimizer(torch.optim.Optimizer):
                 loss = closure()
         self._check_homes()
         self.grads.gather()                   # p.grad -> the flat buffer (no copy when they already are views of it)
-        g = self.param_groups[0]
         lib = _lib.load()
         if not self.flat.is_cuda:
             raise _lib.FgcnError("FlatOptimizer.step needs the parameters on an MI355X (no CPU fallback)")
         if self.skip_nonfinite:
             self._enter_guarded()
-        b1, b2 = g.get("betas", (0.0, 0.0))
         s1 = self.state1.data_ptr() if self.state1 is not None else None
         s2 = self.state2.data_ptr() if self.state2 is not None else None
         n = self.flat.numel()
-        common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n,
-                  KINDS[self.kind], float(g["lr"]), float(g["weight_decay"]), float(self.grad_scale),
-                  float(b1), float(b2), float(g.get("eps", 0.0)), float(g.get("momentum", 0.0)),
-                  float(g.get("dampening", 0.0)), int(bool(g.get("nesterov", False))))
         stream = torch.cuda.current_stream(self.flat.device).cuda_stream
-        if self._guarded:         # norm -> decision -> update, stream-ordered; the step count is the device's
-            rc = lib.fgcn_optim_step_guarded(*common, float(self._max_grad_norm or 0.0), int(self.skip_nonfinite),
-                                             self._partials.data_ptr(), lib.fgcn_grad_norm_tiles(n), self._guard.data_ptr(), stream)
-            _lib.check(rc, "fgcn_optim_step_guarded")
+        guard = (float(self._max_grad_norm or 0.0), int(self.skip_nonfinite), self._partials.data_ptr(), lib.fgcn_grad_norm_tiles(n),
+                 self._guard.data_ptr()) if self._guarded else None
+        if len(self.param_groups) > 1:     # one launch over the tile table; the groups' scalars by value
+            groups = (_lib.OptimGroup * len(self.param_groups))(*[_group_scalars(g) for g in self.param_groups])
+            common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n, KINDS[self.kind], groups, len(groups),
+                      self._tiles.data_ptr(), self._tiles.shape[0], float(self.grad_scale))
+            if self._guarded:
+                _lib.check(lib.fgcn_optim_step_groups_guarded(*common, *guard, self._sched.data_ptr(), stream),
+                           "fgcn_optim_step_groups_guarded")
+            else:
+                self._steps += 1
+                _lib.check(lib.fgcn_optim_step_groups(*common, self._steps, stream), "fgcn_optim_step_groups")
         else:
-            self._steps += 1
-            rc = lib.fgcn_optim_step(*common, self._steps, stream)
-            _lib.check(rc, "fgcn_optim_step")
+            g = self.param_groups[0]
+            b1, b2 = g.get("betas", (0.0, 0.0))
+            common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n,
+                      KINDS[self.kind], float(g["lr"]), float(g["weight_decay"]), float(self.grad_scale),
+                      float(b1), float(b2), float(g.get("eps", 0.0)), float(g.get("momentum", 0.0)),
+                      float(g.get("dampening", 0.0)), int(bool(g.get("nesterov", False))))
+            if self._guarded:         # norm -> decision -> update, stream-ordered; the step count is the device's
+                rc = lib.fgcn_optim_step_guarded(*common, *guard, stream)
+                _lib.check(rc, "fgcn_optim_step_guarded")
+            else:
+                self._steps += 1
+                rc = lib.fgcn_optim_step(*common, self._steps, stream)
+                _lib.check(rc, "fgcn_optim_step")
         # the kernel wrote through raw pointers: tell autograd (and everything keyed on tensor versions, like the blocks'
         # cache of packed weights) that every parameter changed in place -- metadata only, no launches
         for p in self.params:
@@ -206,32 +270,45 @@ class FlatOptimizer(torch.optim.Optimizer):
         return [flat[v.storage_offset():v.storage_offset() + p.numel()].view_as(p) for p, v in zip(self.params, self.grads.views)]
 
     def _slots(self):
-        """Position of every trainable parameter in ``param_groups[0]["params"]`` (frozen parameters keep their slot, stateless)."""
-        where = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        """Position of every trainable parameter in the concatenation of the groups' ``"params"`` -- torch's state index (frozen
+        parameters keep their slot, stateless)."""
+        where = {id(p): i for i, p in enumerate(p for group in self.param_groups for p in group["params"])}
         return [where[id(p)] for p in self.params]
 
     def state_dict(self) -> Dict:
-        """Same layout as the torch optimizer of that name: {"state": {i: {...}}, "param_groups": [...]}.  ``step`` is the count of
-        APPLIED updates (on the guarded path the device counter: skipped steps do not count, as in torch after GradScaler.step)."""
+        """Same layout as the torch optimizer of that name over the same groups: {"state": {i: {...}}, "param_groups": [...]}, the
+        groups' ``"params"`` consecutive indices, the state keyed by them.  ``step`` is the count of APPLIED updates (on the guarded
+        path the device counter: skipped steps do not count, as in torch after GradScaler.step)."""
         state = {}
         steps = self.steps
         if steps:
             s1 = self._views(self.state1) if self.state1 is not None else None
             s2 = self._views(self.state2) if self.state2 is not None else None
-            for i, slot in enumerate(self._slots()):      # torch's layout: state index = position in param_groups[0]["params"]
+            for i, slot in enumerate(self._slots()):      # torch's layout: state index = position over all groups' "params"
                 if self.kind == "SGD":
-                    state[slot] = {"momentum_buffer": s1[i].clone() if s1 is not None else None}
+                    if s1 is None:
+                        state[slot] = {"momentum_buffer": None}
+                    elif self.param_groups[self._group_of[i]]["momentum"] != 0:      # (torch keeps no state without a momentum)
+                        state[slot] = {"momentum_buffer": s1[i].clone()}
                 else:
                     state[slot] = {"step": torch.tensor(float(steps)), "exp_avg": s1[i].clone(), "exp_avg_sq": s2[i].clone()}
-        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        group["params"] = list(range(len(self.param_groups[0]["params"])))
-        return {"state": state, "param_groups": [group]}
+        groups, first = [], 0
+        for g in self.param_groups:
+            group = {k: v for k, v in g.items() if k != "params"}
+            group["params"] = list(range(first, first + len(g["params"])))
+            first += len(g["params"])
+            groups.append(group)
+        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd: Dict) -> None:
-        group = sd["param_groups"][0]
-        for k, v in group.items():
-            if k != "params":
-                self.param_groups[0][k] = v
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        for mine, group in zip(self.param_groups, sd["param_groups"]):
+            if len(group["params"]) != len(mine["params"]):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+            for k, v in group.items():
+                if k != "params":
+                    mine[k] = v
         st = sd.get("state", {})
         steps = 0
         if st:
@@ -239,9 +316,9 @@ class FlatOptimizer(torch.optim.Optimizer):
             s2 = self._views(self.state2) if self.state2 is not None else None
             with torch.no_grad():
                 for i, slot in enumerate(self._slots()):
-                    e = st[slot] if slot in st else st[str(slot)]
+                    e = st[slot] if slot in st else st.get(str(slot))
                     if self.kind == "SGD":
-                        if s1 is not None and e.get("momentum_buffer") is not None:
+                        if s1 is not None and e is not None and e.get("momentum_buffer") is not None:
                             s1[i].copy_(e["momentum_buffer"])
                             steps = max(steps, 1)
                     else:
@@ -251,6 +328,20 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.steps = steps          # (guarded: written to the device counter)
 
 
+def _check_group(kind: str, group: Dict) -> None:
+    """The range checks of one group's scalars (the defaults are a group too)."""
+    if group["lr"] < 0 or group["weight_decay"] < 0:
+        raise ValueError("negative lr / weight_decay")
+    if kind == "SGD" and group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+
+def _group_scalars(g: Dict) -> _lib.OptimGroup:
+    b1, b2 = g.get("betas", (0.0, 0.0))
+    return _lib.OptimGroup(float(g["lr"]), float(g["weight_decay"]), float(b1), float(b2), float(g.get("eps", 0.0)),
+                           float(g.get("momentum", 0.0)), float(g.get("dampening", 0.0)), int(bool(g.get("nesterov", False))))
+
+
 def _check_max_grad_norm(value) -> None:
     if value is None:
         return
@@ -258,7 +349,31 @@ def _check_max_grad_norm(value) -> None:
         raise ValueError(f"max_grad_norm must be a positive number or None (got {value!r})")
 
 
+def groups_from_rules(model: torch.nn.Module, rules) -> List[Dict]:
+    """``param_groups=`` of a config -> torch's list of group dicts.  Every rule is ``{"match": regex, <overrides>}``; a parameter joins
+    the FIRST rule whose regex ``re.search``es its ``named_parameters()`` name, the unmatched ones form the first group with the
+    defaults.  A rule that matches nothing is an error (a typo would otherwise train with the defaults, silently)."""
+    rules = [dict(r) for r in rules]
+    for r in rules:
+        if "match" not in r:
+            raise ValueError(f"param_groups: a rule needs a \"match\" regex (got {r!r})")
+    rest, matched = [], [[] for _ in rules]
+    for name, p in model.named_parameters():
+        hit = next((i for i, r in enumerate(rules) if re.search(r["match"], name)), None)
+        (rest if hit is None else matched[hit]).append(p)
+    for r, ps in zip(rules, matched):
+        if not ps:
+            raise ValueError(f"param_groups: the rule {r['match']!r} matches no parameter of the model")
+    groups = [{"params": rest}] if rest else []
+    return groups + [dict({k: v for k, v in r.items() if k != "match"}, params=ps) for r, ps in zip(rules, matched)]
+
+
 def create_optimizer(name: str, model: torch.nn.Module, lr: float, **optimizer_args) -> FlatOptimizer:
     """Signature of the reference's session_helper.create_optimizer (torch_src/session_helper.py:80-84); ``max_grad_norm`` and
-    ``skip_nonfinite`` travel in ``optimizer_args`` like every other option of the config."""
-    return FlatOptimizer(model.parameters(), name, lr, **optimizer_args)
+    ``skip_nonfinite`` travel in ``optimizer_args`` like every other option of the config, and so does ``param_groups``: a list of
+    ``{"match": regex, <overrides>}`` rules (``groups_from_rules``), e.g.
+    ``[{"match": r"bn\\.|bias$|adj_b$", "weight_decay": 0.0}, {"match": r"^fc\\.", "lr": 0.01}]``."""
+    rules = optimizer_args.pop("param_groups", None)
+    if rules is None:
+        return FlatOptimizer(model.parameters(), name, lr, **optimizer_args)
+    return FlatOptimizer(groups_from_rules(model, rules), name, lr, **optimizer_args)

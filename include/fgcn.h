@@ -746,6 +746,42 @@ int fgcn_optim_step_guarded(float* params, const float* grads, float* state1, fl
                             float momentum, float dampening, int nesterov, double max_norm, int skip_nonfinite,
                             double* partials, int n_partials, void* guard, void* stream);
 
+/* The same two updates over several parameter groups (torch.optim's param_groups: one optimizer kind, per-group scalars), still ONE
+ * update launch.  Which group an element belongs to comes from a device-resident tile table the caller builds once:
+ *   tiles[3*t + 0] = start4   first 16-byte group (float4) of the tile inside the flat buffers
+ *   tiles[3*t + 1] = count4   16-byte groups in the tile, 1 .. FGCN_OPT_TILE4
+ *   tiles[3*t + 2] = group    0 .. ngroups-1
+ * all int (ntiles rows); one workgroup per tile.  A tile never holds values of two groups; the tiles together cover every 16-byte
+ * group of the buffers exactly once (the <= 3 padding floats behind a tensor ride in that tensor's last 16-byte group and keep their
+ * zeros).  The library cannot read the table on the host: a tile that reaches past n / 4 or names a group outside [0, ngroups) is
+ * ignored by the kernel, everything else about the table is the caller's contract.
+ * groups[g] travels by value in the kernel arguments (a new learning rate costs nothing).  Per element the arithmetic is that of
+ * fgcn_optim_step with groups[g]'s scalars, operation by operation: one group here, or equal groups, give the bits of the single-group
+ * call.  Adam's step size is (float)((double)lr_g / (1 - beta1_g^step)) and sqrt(1 - beta2_g^step) per group.  state1 may be NULL only
+ * when no SGD group has a momentum.
+ * Guarded form: the three launches of fgcn_optim_step_guarded -- the same norm kernel over the whole buffer (one global norm, the same
+ * bits), one decision for all groups, one step count -- and `group_sched`, a caller-owned device buffer of 2 * FGCN_OPT_MAX_GROUPS
+ * doubles, 8-byte aligned, that launch 2 fills with {lr_g / (1 - beta1_g^STEP), sqrt(1 - beta2_g^STEP)} per group for launch 3
+ * (the guard words STEP_SIZE / BC2_SQRT are left alone).
+ * FGCN_E_BADARG: ngroups outside [1, FGCN_OPT_MAX_GROUPS], a null groups / tiles / group_sched, ntiles < 1, n / 4 >= 2^31, a group's lr /
+ * weight_decay / betas / eps / momentum out of range or Nesterov without momentum or with dampening (the message names the group);
+ * FGCN_E_ALIGN: tiles not 4-byte, group_sched not 8-byte aligned; everything else as the single-group calls. */
+#define FGCN_OPT_MAX_GROUPS 8
+#define FGCN_OPT_TILE4 1024
+typedef struct fgcn_optim_group {
+    float lr, weight_decay;
+    float beta1, beta2, eps;       /* Adam / AdamW */
+    float momentum, dampening;     /* SGD */
+    int nesterov;
+} fgcn_optim_group;
+int fgcn_optim_step_groups(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
+                           const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
+                           long long step, void* stream);
+int fgcn_optim_step_groups_guarded(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
+                                   const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
+                                   double max_norm, int skip_nonfinite, double* partials, int n_partials, void* guard,
+                                   double* group_sched, void* stream);
+
 /* ---- MS-G3D data movement ------------------------------------------------------------------
  * (3 x 1) temporal max pooling with padding 1 and stride `stride` (nn.MaxPool2d((3,1), (stride,1), (1,0)) of
  * MultiScale_TemporalConv's pooling branch, models/msg3d/ms_tcn.py:72-78):
