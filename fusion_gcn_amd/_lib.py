@@ -185,6 +185,9 @@ SIGNATURES = {
     "fgcn_patch_input_bwd": (_I, [_P] * 10 + [_I] * 10 + [_P]),
     "fgcn_cross_entropy_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "fgcn_cross_entropy_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "fgcn_ce_workspace_bytes": (_LL, [_I]),
+    "fgcn_ce_fwd": (_I, [_P] * 9 + [_I, _I, _I, _I, _LL, _F, _I, _P]),
+    "fgcn_ce_bwd": (_I, [_P] * 8 + [_I, _I, _I, _I, _LL, _F, _I, _P]),
     "fgcn_optim_step": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _LL, _P]),
     "fgcn_grad_norm_tiles": (_I, [_LL]),
     "fgcn_optim_guard_bytes": (_LL, []),
@@ -198,6 +201,7 @@ SIGNATURES = {
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)
 CLS_EXAMPLES, CLS_TOP1, CLS_TOPK, CLS_IGNORED, CLS_INVALID, CLS_DROPPED, CLS_LOSS_ITEMS, CLS_LOSS_SUM, CLS_WORDS = range(9)
 CLS_MAX_CLASSES = 1024      # FGCN_CLS_MAX_CLASSES
+CE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}       # enum fgcn_ce_reduction
 # enum fgcn_guard_word: the 8-byte words of the guarded optimizer step's state (include/fgcn.h)
 (GUARD_STEP, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM, GUARD_COEF, GUARD_APPLY, GUARD_FIRST_STEP, GUARD_STEP_SIZE, GUARD_BC2_SQRT,
  GUARD_WORDS) = range(10)

@@ -941,4 +941,32 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return CrossEntropyFunction.apply(logits, labels)
 
 
+class CrossEntropyOptionsFunction(torch.autograd.Function):
+    """F.cross_entropy(logits, target, weight, ignore_index=, reduction=, label_smoothing=) with int64 labels or float32 class
+    probabilities (``fgcn_ce_fwd`` / ``_bwd``, include/fgcn.h): fixed-order sums each way; softmax is not stored when the logits need
+    no gradient.  The target and the weight get no gradient (data)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, reduction, label_smoothing, need):
+        loss, row_loss, row_scale, probs = ops.cross_entropy_opts_fwd(logits, target, weight, ignore_index=ignore_index,
+                                                                      reduction=reduction, label_smoothing=label_smoothing,
+                                                                      need_probs=need)
+        if need:
+            ctx.save_for_backward(probs, target, weight, row_scale, loss)
+        ctx.options = dict(ignore_index=ignore_index, reduction=reduction, label_smoothing=label_smoothing)
+        return row_loss if reduction == "none" else loss[0]
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        probs, target, weight, row_scale, loss = ctx.saved_tensors
+        d_loss = d_loss.contiguous().view(-1)
+        return ops.cross_entropy_opts_bwd(probs, target, weight, row_scale, loss, d_loss, **ctx.options), None, None, None, None, None, None
+
+
+def cross_entropy_options(logits: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, ignore_index: int = -100,
+                          reduction: str = "mean", label_smoothing: float = 0.0) -> torch.Tensor:
+    need = torch.is_grad_enabled() and logits.requires_grad          # (forward() itself always runs with grad mode off)
+    return CrossEntropyOptionsFunction.apply(logits, target, weight, ignore_index, reduction, label_smoothing, need)
+
+
 ops.bind_all_functions(globals())     # every Function's backward runs in its forward's library context (ops.Context)

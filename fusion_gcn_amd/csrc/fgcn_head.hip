@@ -171,6 +171,152 @@ __global__ __launch_bounds__(256) void cross_entropy_bwd_kernel(const float* pro
     }
 }
 
+// ---- CrossEntropyLoss with torch's arguments: weight, ignore_index, reduction, label_smoothing, class-probability targets ---------
+// (include/fgcn.h, fgcn_ce_fwd; the two kernels above are the plain path and stay as they are.)
+constexpr int CE_ROWS = 16;         // rows per workgroup: wave w takes rows 4 w .. 4 w + 3 of the group, one after the other
+
+// PROB selects WHAT is loaded as the target (labels[i] | target[i][c]), HAS_W whether weight[] is loaded at all: template
+// parameters, not branches around each load.  Per row i, lse = logsumexp(z_i):
+//   index targets:  keep = y != ignore_index;  y in [0, classes) (checked BEFORE weight[y] / z[y] are addressed):
+//                   row_loss = (1 - eps) w[y] (lse - z[y]) + eps/C sum_c w[c] (lse - z[c]),  row_scale = (1 - eps) w[y] + eps/C sum_c w[c],
+//                   denominator term w[y];  ignored: all three 0;  any other y: row_loss = row_scale = NaN, denominator term 0.
+//   probabilities:  t' = (1 - eps) t + eps/C;  row_loss = sum_c w[c] t'[c] (lse - z[c]),  row_scale = sum_c w[c] t'[c],  denominator term 1.
+// partials[block] = {sum row_loss, sum denominator terms} over the block's <= 16 rows in row order, in float64, by one thread.
+template <bool PROB, bool HAS_W>
+__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, const long long* labels, const float* target,
+                                                     const float* weight, float* probs, float* row_loss, float* row_scale,
+                                                     double* partials, int rows, int classes, int ld, int ld_t, long long ignore_index,
+                                                     float eps) {
+    __shared__ float sh_loss[CE_ROWS], sh_den[CE_ROWS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float smooth = eps / (float)classes, sharp = 1.f - eps;
+    for (int k = 0; k < CE_ROWS / 4; ++k) {
+        const int slot = wave * (CE_ROWS / 4) + k, i = blockIdx.x * CE_ROWS + slot;
+        float rl = 0.f, den = 0.f;                                   // a row past the end adds nothing
+        if (i < rows) {                                              // wave-uniform
+            const float* z = logits + (long long)i * ld;
+            float mx = -INFINITY;
+            for (int c = lane; c < classes; c += 64) mx = fmaxf(mx, z[c]);
+            mx = wmax(mx);
+            float s = 0.f;
+            for (int c = lane; c < classes; c += 64) s += expf(z[c] - mx);
+            s = wsum(s);
+            const float inv = 1.f / s, lse = mx + logf(s);
+            if (probs)
+                for (int c = lane; c < classes; c += 64) probs[(long long)i * classes + c] = expf(z[c] - mx) * inv;
+            float rs;
+            if constexpr (PROB) {
+                const float* t = target + (long long)i * ld_t;
+                float a = 0.f, b = 0.f;
+                for (int c = lane; c < classes; c += 64) {
+                    const float q = (HAS_W ? weight[c] : 1.f) * (sharp * t[c] + smooth);
+                    a += q * (lse - z[c]);
+                    b += q;
+                }
+                rl = wsum(a);
+                rs = wsum(b);
+                den = 1.f;
+            } else {
+                float a = 0.f, b = 0.f;                              // sum_c w[c] (lse - z[c]), sum_c w[c]: the smoothing term only
+                if (eps > 0.f) {
+                    for (int c = lane; c < classes; c += 64) {
+                        const float w = HAS_W ? weight[c] : 1.f;
+                        a += w * (lse - z[c]);
+                        b += w;
+                    }
+                    a = wsum(a);
+                    b = wsum(b);
+                }
+                const long long y = labels[i];
+                if (y == ignore_index) {
+                    rs = 0.f;
+                } else if (y >= 0 && y < classes) {
+                    const float wy = HAS_W ? weight[y] : 1.f;
+                    rl = sharp * wy * (lse - z[y]) + smooth * a;
+                    rs = sharp * wy + smooth * b;
+                    den = wy;
+                } else {
+                    rl = rs = NAN;
+                }
+            }
+            if (lane == 0) {
+                row_loss[i] = rl;
+                row_scale[i] = rs;
+            }
+        }
+        if (lane == 0) {
+            sh_loss[slot] = rl;
+            sh_den[slot] = den;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0, d = 0.0;
+        for (int r = 0; r < CE_ROWS; ++r) {
+            a += (double)sh_loss[r];
+            d += (double)sh_den[r];
+        }
+        partials[2 * blockIdx.x] = a;
+        partials[2 * blockIdx.x + 1] = d;
+    }
+}
+
+// One workgroup: the partials are staged through LDS 256 at a time and added by ONE thread in index order, in float64 -- the
+// order of the additions is the order of the rows, whatever order the workgroups of ce_fwd_kernel ran in.
+// loss[0] = mean ? sum / denominator (NaN for a zero denominator: every row ignored, every present weight zero) : sum; loss[1] = denominator.
+__global__ __launch_bounds__(256) void ce_finish_kernel(const double* partials, float* loss, int nparts, int mean) {
+    __shared__ double sh[2 * 256];
+    double a = 0.0, d = 0.0;
+    for (int p0 = 0; p0 < nparts; p0 += 256) {
+        const int n = min(256, nparts - p0);
+        if ((int)threadIdx.x < n) {
+            sh[2 * threadIdx.x] = partials[2 * (p0 + threadIdx.x)];
+            sh[2 * threadIdx.x + 1] = partials[2 * (p0 + threadIdx.x) + 1];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int p = 0; p < n; ++p) {
+                a += sh[2 * p];
+                d += sh[2 * p + 1];
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        loss[0] = mean ? (d != 0.0 ? (float)(a / d) : NAN) : (float)a;
+        loss[1] = (float)d;
+    }
+}
+
+// dlogits[i][c] = g_i (probs[i][c] row_scale[i] - a_ic), a_ic = w[c] q_ic (q: the smoothed one-hot | t'); g_i = dloss[0] / loss[1]
+// (mean; NaN for a zero denominator), dloss[0] (sum), dloss[i] (none).  An ignored row is written as 0 whatever g is; a label outside [0, classes) that is not
+// ignore_index has row_scale = NaN, hence a NaN row; columns [classes, ld_out) zero.
+template <bool PROB, bool HAS_W>
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* probs, const long long* labels, const float* target,
+                                                     const float* weight, const float* row_scale, const float* loss,
+                                                     const float* dloss, float* dlogits, int rows, int classes, int ld_t, int ld_out,
+                                                     long long ignore_index, float eps, int reduction) {
+    const float smooth = eps / (float)classes, sharp = 1.f - eps;
+    // (mean over a zero denominator: torch's gradient of a row that is not ignored is NaN -- 0/0 -- there, also where g * (...) would be inf)
+    const float g_all = reduction == FGCN_CE_MEAN ? (loss[1] != 0.f ? dloss[0] / loss[1] : NAN) : dloss[0];
+    const long long n = (long long)rows * ld_out;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const int i = (int)(e / ld_out), c = (int)(e - (long long)i * ld_out);
+        float d = 0.f;
+        if (c < classes) {
+            const float g = reduction == FGCN_CE_NONE ? dloss[i] : g_all;
+            const float w = HAS_W ? weight[c] : 1.f;
+            const float ps = probs[(long long)i * classes + c] * row_scale[i];
+            if constexpr (PROB) {
+                d = g * (ps - w * (sharp * target[(long long)i * ld_t + c] + smooth));
+            } else {
+                const long long y = labels[i];
+                if (y != ignore_index) d = g * (ps - w * ((c == y ? sharp : 0.f) + smooth));
+            }
+        }
+        dlogits[e] = d;
+    }
+}
+
 }  // namespace fgcn
 
 using namespace fgcn;
@@ -245,4 +391,50 @@ extern "C" int fgcn_cross_entropy_bwd(const float* probs, const long long* label
     hipLaunchKernelGGL(cross_entropy_bwd_kernel, dim3(stream_blocks((long long)rows * ld_out)), dim3(256), 0, (hipStream_t)stream, probs,
                        labels, loss, dloss, dlogits, rows, classes, ld_out);
     return launch_status("cross_entropy_bwd");
+}
+
+extern "C" long long fgcn_ce_workspace_bytes(int rows) { return rows > 0 ? cdiv(rows, CE_ROWS) * 2 * (long long)sizeof(double) : 0; }
+
+// the checks fgcn_ce_fwd and fgcn_ce_bwd share: one kind of target, the shape, eps in [0, 1] (a NaN fails the comparison), the reduction
+static int check_ce(const char* what, const long long* labels, const float* target, int rows, int classes, int ld_t, float eps,
+                    int reduction) {
+    FGCN_REQUIRE((labels != nullptr) != (target != nullptr), FGCN_E_BADARG, "%s: exactly one of labels / target", what);
+    FGCN_REQUIRE(rows > 0 && classes > 0 && (!target || ld_t >= classes), FGCN_E_BADARG, "%s: bad shape (rows=%d classes=%d ld_target=%d)",
+                 what, rows, classes, ld_t);
+    FGCN_REQUIRE(eps >= 0.f && eps <= 1.f, FGCN_E_BADARG, "%s: label_smoothing %g outside [0, 1]", what, (double)eps);
+    FGCN_REQUIRE(reduction == FGCN_CE_MEAN || reduction == FGCN_CE_SUM || reduction == FGCN_CE_NONE, FGCN_E_BADARG,
+                 "%s: unknown reduction %d", what, reduction);
+    return FGCN_OK;
+}
+
+extern "C" int fgcn_ce_fwd(const float* logits, const long long* labels, const float* target, const float* weight, float* probs,
+                           float* row_loss, float* row_scale, float* loss, void* workspace, int rows, int classes, int ld,
+                           int ld_target, long long ignore_index, float label_smoothing, int reduction, void* stream) {
+    FGCN_REQUIRE(logits && row_loss && row_scale && loss && workspace, FGCN_E_BADARG, "ce_fwd: null pointer");
+    if (int e = check_ce("ce_fwd", labels, target, rows, classes, ld_target, label_smoothing, reduction)) return e;
+    FGCN_REQUIRE(ld >= classes, FGCN_E_BADARG, "ce_fwd: ld=%d < classes=%d", ld, classes);
+    FGCN_REQUIRE((uintptr_t)workspace % 8 == 0, FGCN_E_ALIGN, "ce_fwd: workspace not 8-byte aligned");
+    const int nparts = (int)cdiv(rows, CE_ROWS);
+    auto kernel = target ? (weight ? ce_fwd_kernel<true, true> : ce_fwd_kernel<true, false>)
+                         : (weight ? ce_fwd_kernel<false, true> : ce_fwd_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream, logits, labels, target, weight, probs, row_loss,
+                       row_scale, (double*)workspace, rows, classes, ld, ld_target, ignore_index, label_smoothing);
+    if (int e = launch_status("ce_fwd")) return e;
+    hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, loss, nparts,
+                       (int)(reduction == FGCN_CE_MEAN));
+    return launch_status("ce_fwd (finish)");
+}
+
+extern "C" int fgcn_ce_bwd(const float* probs, const long long* labels, const float* target, const float* weight,
+                           const float* row_scale, const float* loss, const float* dloss, float* dlogits, int rows, int classes,
+                           int ld_target, int ld_out, long long ignore_index, float label_smoothing, int reduction, void* stream) {
+    FGCN_REQUIRE(probs && row_scale && loss && dloss && dlogits, FGCN_E_BADARG, "ce_bwd: null pointer");
+    if (int e = check_ce("ce_bwd", labels, target, rows, classes, ld_target, label_smoothing, reduction)) return e;
+    FGCN_REQUIRE(ld_out >= classes, FGCN_E_BADARG, "ce_bwd: ld_out=%d < classes=%d", ld_out, classes);
+    auto kernel = target ? (weight ? ce_bwd_kernel<true, true> : ce_bwd_kernel<true, false>)
+                         : (weight ? ce_bwd_kernel<false, true> : ce_bwd_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(stream_blocks((long long)rows * ld_out)), dim3(256), 0, (hipStream_t)stream, probs, labels, target,
+                       weight, row_scale, loss, dloss, dlogits, rows, classes, ld_target, ld_out, ignore_index, label_smoothing,
+                       reduction);
+    return launch_status("ce_bwd");
 }

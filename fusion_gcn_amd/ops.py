@@ -1330,6 +1330,74 @@ def cross_entropy_bwd(probs: torch.Tensor, labels: torch.Tensor, loss: torch.Ten
     return dl
 
 
+def _ce_target(what: str, rows: int, classes: int, target: torch.Tensor):
+    """(labels pointer, target pointer, target row stride) of an int64 (rows,) or float32 (rows, classes) target on the device."""
+    if target.dtype == torch.int64 and target.is_cuda and target.is_contiguous() and target.dim() == 1 and target.numel() == rows:
+        return target.data_ptr(), None, 0
+    if (target.dtype == torch.float32 and target.is_cuda and tuple(target.shape) == (rows, classes)
+            and (classes == 1 or target.stride(1) == 1) and (rows == 1 or target.stride(0) >= classes)):
+        return None, target.data_ptr(), target.stride(0) if rows > 1 else max(target.stride(0), classes)
+    raise _lib.FgcnError(f"{what}: the target is int64 labels (rows,) or float32 class probabilities (rows, classes) with contiguous "
+                         "classes, on the device")
+
+
+def _ce_weight(what: str, classes: int, weight: Optional[torch.Tensor]):
+    if weight is not None and not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous()
+                                   and tuple(weight.shape) == (classes,)):
+        raise _lib.FgcnError(f"{what}: weight must be a contiguous float32 device tensor of {classes} entries")
+    return None if weight is None else weight.data_ptr()
+
+
+def cross_entropy_opts_fwd(logits: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, *, ignore_index: int = -100,
+                           reduction: str = "mean", label_smoothing: float = 0.0, need_probs: bool = True):
+    """fgcn_ce_fwd: logits (rows, classes) float32 with unit column stride (any row stride); ``target`` int64 labels (rows,) or float32
+    class probabilities (rows, classes); ``weight`` float32 (classes,) or None -> (loss (2,) = {value, denominator}, row_loss (rows,),
+    row_scale (rows,), probs (rows, classes) or None without ``need_probs``)."""
+    ensure_device()
+    if logits.dim() != 2:
+        raise _lib.FgcnError("cross_entropy: logits (rows, classes)")
+    rows, classes = logits.shape
+    if not (logits.is_cuda and logits.dtype == torch.float32 and (classes == 1 or logits.stride(1) == 1)
+            and (rows == 1 or logits.stride(0) >= classes)):
+        raise _lib.FgcnError("cross_entropy: float32 logits (rows, classes) with contiguous classes on the device")
+    if reduction not in _lib.CE_REDUCTIONS:
+        raise _lib.FgcnError(f"cross_entropy: unknown reduction {reduction!r}")
+    labels_p, target_p, ld_t = _ce_target("cross_entropy", rows, classes, target)
+    weight_p = _ce_weight("cross_entropy", classes, weight)
+    lib = _lib.load()
+    f32 = dict(device=logits.device, dtype=torch.float32)
+    probs = torch.empty((rows, classes), **f32) if need_probs else None
+    row_loss, row_scale, loss = torch.empty(rows, **f32), torch.empty(rows, **f32), torch.empty(2, **f32)
+    work = torch.empty(lib.fgcn_ce_workspace_bytes(rows) // 8, device=logits.device, dtype=torch.float64)
+    ld = logits.stride(0) if rows > 1 else max(logits.stride(0), classes)        # a single row's stride is arbitrary
+    check(lib.fgcn_ce_fwd(logits.data_ptr(), labels_p, target_p, weight_p, _p(probs), _p(row_loss), _p(row_scale), _p(loss), _p(work),
+                          rows, classes, ld, ld_t, int(ignore_index), float(label_smoothing), _lib.CE_REDUCTIONS[reduction],
+                          _stream()), "fgcn_ce_fwd")
+    return loss, row_loss, row_scale, probs
+
+
+def cross_entropy_opts_bwd(probs: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor], row_scale: torch.Tensor,
+                           loss: torch.Tensor, dloss: torch.Tensor, *, ignore_index: int = -100, reduction: str = "mean",
+                           label_smoothing: float = 0.0) -> torch.Tensor:
+    """fgcn_ce_bwd with the arguments of the forward: ``dloss`` one float32 (mean, sum) or float32 (rows,) (none) -> dlogits
+    (rows, classes)."""
+    ensure_device()
+    rows, classes = probs.shape
+    if reduction not in _lib.CE_REDUCTIONS:
+        raise _lib.FgcnError(f"cross_entropy: unknown reduction {reduction!r}")
+    labels_p, target_p, ld_t = _ce_target("cross_entropy_bwd", rows, classes, target)
+    weight_p = _ce_weight("cross_entropy_bwd", classes, weight)
+    if not (dloss.is_cuda and dloss.dtype == torch.float32 and dloss.is_contiguous()
+            and dloss.numel() == (rows if reduction == "none" else 1)):
+        raise _lib.FgcnError("cross_entropy_bwd: dloss is one float32 (mean, sum) or a contiguous float32 (rows,) (none) on the device")
+    _chk(probs, "cross_entropy_bwd.probs")
+    dl = torch.empty((rows, classes), device=probs.device, dtype=torch.float32)
+    check(_lib.load().fgcn_ce_bwd(_p(probs), labels_p, target_p, weight_p, _p(row_scale), _p(loss), _p(dloss), _p(dl), rows, classes, ld_t,
+                                  classes, int(ignore_index), float(label_smoothing), _lib.CE_REDUCTIONS[reduction], _stream()),
+          "fgcn_ce_bwd")
+    return dl
+
+
 def classify_state_bytes(classes: int) -> int:
     """Size of the state buffer of ``classify_update`` (host-only query; 0 for a class count the kernel does not take)."""
     return int(_lib.load().fgcn_classify_state_bytes(classes))

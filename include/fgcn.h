@@ -867,6 +867,36 @@ int fgcn_cross_entropy_fwd(const float* logits, const long long* labels, float* 
                            int classes, int ld, void* stream);
 int fgcn_cross_entropy_bwd(const float* probs, const long long* labels, const float* loss, const float* dloss, float* dlogits,
                            int rows, int classes, int ld_out, void* stream);
+/* The same loss with torch.nn.CrossEntropyLoss's arguments (weight, ignore_index, reduction, label_smoothing, class-probability
+ * targets); the two calls above are the path of the default arguments and are untouched.  DESIGN.md section 8d.
+ *   logits (rows, classes) float32, row stride ld >= classes;  EXACTLY ONE of labels int64[rows] | target float32 (rows, classes)
+ *   class probabilities with row stride ld_target >= classes (ld_target is not read with labels);  weight float32[classes] or NULL
+ *   = all ones;  ignore_index applies to labels only (a value inside [0, classes) is legal);  label_smoothing eps in [0, 1].
+ * Per row i, lp = log_softmax(z_i), C = classes:
+ *   labels:  keep = (y != ignore_index);  row_loss = keep [(1 - eps) w[y] (-lp[y]) + eps/C sum_c w[c] (-lp[c])],
+ *            row_scale = keep [(1 - eps) w[y] + eps/C sum_c w[c]],  denominator = sum_i keep w[y_i] (it does not depend on eps).
+ *            A label outside [0, classes) that is not ignore_index: row_loss = row_scale = NaN (so are the mean and the sum, and
+ *            that row's gradient); no address is ever formed from a label before it is range-checked.
+ *   target:  t' = (1 - eps) t + eps/C;  row_loss = -sum_c w[c] t'[c] lp[c],  row_scale = sum_c w[c] t'[c],  denominator = rows.
+ * fwd writes row_loss float[rows] (the result of FGCN_CE_NONE), row_scale float[rows] (for the backward), probs float[rows][classes]
+ * = softmax (NULL when no backward follows) and loss float[2] = {value, denominator}: value = sum row_loss (FGCN_CE_SUM, FGCN_CE_NONE)
+ * or that sum / denominator (FGCN_CE_MEAN; NaN for a zero denominator, as in torch: every row ignored, every present weight zero).
+ * workspace: fgcn_ce_workspace_bytes(rows) bytes, 8-byte aligned, caller-owned (0 for rows <= 0): one float64 pair {sum row_loss,
+ * sum denominator} per workgroup of 16 rows (one wave per row), added in index order in float64 by a second one-workgroup launch --
+ * the order of the additions does not depend on the order the workgroups ran in: the same call leaves the same bits.
+ * bwd: dlogits (rows, ld_out) = g_i (probs[i][c] row_scale[i] - a_ic), a_ic = keep w[c] q_ic (q: the smoothed one-hot | t'),
+ *   g_i = dloss[0] / loss[1] (MEAN; NaN for a zero denominator, as torch's 0/0), dloss[0] (SUM), dloss[i] (NONE: dloss is float[rows]); an ignored row's gradient is exactly 0;
+ *   columns [classes, ld_out) zero.  It takes the labels / target / weight / ignore_index / label_smoothing / reduction of its fwd.
+ * FGCN_E_BADARG before any launch: a null required pointer (workspace included), both or neither of labels / target, rows <= 0,
+ * classes <= 0, ld / ld_target / ld_out < classes, eps outside [0, 1] or NaN, an unknown reduction; FGCN_E_ALIGN: workspace. */
+enum fgcn_ce_reduction { FGCN_CE_MEAN = 0, FGCN_CE_SUM = 1, FGCN_CE_NONE = 2 };
+long long fgcn_ce_workspace_bytes(int rows);
+int fgcn_ce_fwd(const float* logits, const long long* labels, const float* target, const float* weight, float* probs, float* row_loss,
+                float* row_scale, float* loss, void* workspace, int rows, int classes, int ld, int ld_target, long long ignore_index,
+                float label_smoothing, int reduction, void* stream);
+int fgcn_ce_bwd(const float* probs, const long long* labels, const float* target, const float* weight, const float* row_scale,
+                const float* loss, const float* dloss, float* dlogits, int rows, int classes, int ld_target, int ld_out,
+                long long ignore_index, float label_smoothing, int reduction, void* stream);
 
 /* Classification metrics accumulated on the device (metrics.py; reference torch_src/metrics.py Mean / MultiClassAccuracy /
  * TopKAccuracy / ConfusionMatrix / MisclassifiedSamplesList): ONE launch per batch adds everything those classes derive their values
