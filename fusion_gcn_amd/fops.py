@@ -454,8 +454,17 @@ class ParamForms:
             self.generation += 1
         return f.dst
 
-    def get_pair(self, name: str, suffixes: Tuple[str, str], make: Callable[[], Tuple[Form, Form]], device):
-        """Two forms built together (a matrix and its transpose) under ``name + suffix``."""
+    def get_pair(self, name: str, suffixes: Tuple[str, str], make: Callable[[], Tuple[Form, Form]], device,
+                 sources: Optional[Sequence[torch.Tensor]] = None):
+        """Two forms built together (a matrix and its transpose) under ``name + suffix``.  ``sources``: the tensors every segment of the
+        forms must read, in order -- for a source that is a plain attribute of its module (the constant adjacency stack), which can be
+        REPLACED by another tensor while the one the form holds stays alive, at its address and version."""
+        if sources is not None:
+            for key in (name + suffixes[0], name + suffixes[1]):
+                f = self.forms.get(key)
+                if f is not None and not (len(f.segs) == len(sources) and all(s.src is t for s, t in zip(f.segs, sources))):
+                    del self.forms[key]
+                    self.generation += 1
         a, b = self._current(name + suffixes[0]), self._current(name + suffixes[1])
         if a is None or b is None:
             a, b = make()
@@ -689,7 +698,8 @@ def node_mix_params(x: torch.Tensor, forms: ParamForms, name: str, a_const: torc
     padding (UTD-MHAD's 20 joints: every case), built with torch ops otherwise (NTU's 25 joints x 13 scales = 325 columns)."""
     if (a_const.shape[1] * num_scales) % 4:
         return node_mix(x, node_mix_matrix(a_const + a_res, num_scales), num_scales)
-    a_fm, a_fm_t = forms.get_pair(name, (".a", ".at"), lambda: node_mix_forms(a_const, a_res, num_scales), x.device)
+    a_fm, a_fm_t = forms.get_pair(name, (".a", ".at"), lambda: node_mix_forms(a_const, a_res, num_scales), x.device,
+                                  sources=(a_const, a_res))
     return _NodeMixParams.apply(x.contiguous(), a_fm, a_fm_t, a_res, num_scales)
 
 
