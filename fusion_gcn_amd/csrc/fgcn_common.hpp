@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/fgcn.h"
 
@@ -51,6 +52,41 @@ inline int launch_status(const char* what) {
     } while (0)
 
 inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+// The kernels address every tensor through a buffer descriptor with 32-bit byte offsets: a tensor, with the widest offset a lane adds
+// past its end, stays below 2 GiB (fusion_gcn_amd/routes.py fits32 is the Python copy of this limit).
+constexpr long long BUFFER_LIMIT = 0x7FFF0000ll;
+inline bool fits_buffer(long long bytes) { return bytes < BUFFER_LIMIT; }
+
+// ---- host: launching -------------------------------------------------------------------------------------
+// Launch of a kernel that may need more dynamic LDS than the default limit: the opt-in to `max_lds` bytes happens once per kernel
+// instantiation, in the initialiser of a function-local static (thread-safe by the language: the library is called from several threads).
+// It is not a stream operation, so it stays out of graph captures.  `max_lds` must be the same on every call for one kernel.
+template <auto Kernel, class Params>
+inline void launch_lds(dim3 grid, dim3 block, int max_lds, size_t lds, hipStream_t s, const Params& p) {
+    static const hipError_t opted =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    (void)opted;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, p);
+}
+
+// Run-time values -> template arguments: dispatch(f, one_of<1, 3>{np}, one_of<0, 1>{acc}, ...) calls
+// f(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, ...) with each selector's value (bools: 0 / 1).  The launchers pick a
+// kernel instantiation with it.  f returns whether it launched: a combination that is not built is cut inside f with `if constexpr` (so that
+// exactly the built ones are instantiated) and returns false.  dispatch returns f's answer, and false when a value is not in its list: a
+// launcher fails on false, so that no choice ends as a call that launched nothing and reports success.
+template <int... Vs>
+struct one_of {
+    int v;
+};
+template <class F>
+[[nodiscard]] inline bool dispatch(F&& f) {
+    return f();
+}
+template <class F, int... Vs, class... Rest>
+[[nodiscard]] inline bool dispatch(F&& f, one_of<Vs...> a, Rest... rest) {
+    return ((a.v == Vs && dispatch([&](auto... cs) { return f(std::integral_constant<int, Vs>{}, cs...); }, rest...)) || ...);
+}
 
 // Division of a row index by a run-time constant (joints per frame, rows per sample, frames) without the ~25-instruction sequence a
 // 32-bit integer division costs per lane: q = (n * m) >> p with m = ceil(2^p / d), p = 29 + ceil(log2 d) -- exact for every n < 2^29

@@ -752,10 +752,13 @@ static int check_elem(const char* what, long long rows, int C, int res_mode, con
     return FGCN_OK;
 }
 
+// the body of fgcn_bn_act and fgcn_bn_apply_ld; half_mask: bit 0 = a, bit 1 = b, bit 2 = out are bfloat16 tensors
 static int bn_act_impl(const float* a, const float* vec_a, const float* b, const float* vec_b, float* out,
-                       unsigned char* sign_mask, long long rows, int C, int res_mode, int relu, int ld_out, void* stream, bool o16 = false, int hm = 0) {
+                       unsigned char* sign_mask, long long rows, int C, int res_mode, int relu, int ld_out, void* stream, int half_mask) {
+    const bool o16 = half_mask & 4;
+    const int in16 = half_mask & 3;      // the bfloat16 inputs, as the kernels take them
     FGCN_REQUIRE(a && vec_a && out, FGCN_E_BADARG, "bn_act: null pointer");
-    FGCN_REQUIRE((!o16 && !hm) || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "bn_act: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(!half_mask || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "bn_act: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(!o16 || ld_out == C, FGCN_E_BADARG, "bn_act: a bfloat16 output is contiguous (ld_out == C)");
     if (int e = check_elem("bn_act", rows, C, res_mode, b, vec_b)) return e;
     FGCN_REQUIRE(aligned16(a) && aligned16(out) && aligned16(vec_a) && (!b || aligned16(b)), FGCN_E_ALIGN,
@@ -766,52 +769,27 @@ static int bn_act_impl(const float* a, const float* vec_a, const float* b, const
     FGCN_REQUIRE(!sign_mask || n4 % 2 == 0, FGCN_E_BADARG, "bn_act: a sign mask needs rows*C to be a multiple of 8");
     dim3 g(stream_blocks(n4)), blk(256);
     const int str = fgcn::stream_out(n4 * 16) ? 1 : 0;
-    if (hm && C % 8 == 0 && ld_out == C) {      // typed operands: eight elements per thread
+    if (in16 && C % 8 == 0 && ld_out == C) {      // typed operands: eight elements per thread
         const long long n8 = n4 / 2;
-        const int hm8 = hm | (o16 ? 4 : 0);
         dim3 g8(stream_blocks(n8));
-#define FGCN_BN_ACT8H(RES_, HM_)                                                                                                     \
-    do {                                                                                                                             \
-        if (sign_mask) hipLaunchKernelGGL((bn_act8_kernel<RES_, true, HM_>), g8, blk, 0, s, a, vec_a, b, vec_b, out, sign_mask, n8, C, relu, str); \
-        else hipLaunchKernelGGL((bn_act8_kernel<RES_, false, HM_>), g8, blk, 0, s, a, vec_a, b, vec_b, out, sign_mask, n8, C, relu, str);          \
-    } while (0)
-#define FGCN_BN_ACT8(RES_)                                                                                                           \
-    do switch (RES_ == 0 ? (hm8 & ~2) : hm8) {                                                                                       \
-        case 1: FGCN_BN_ACT8H(RES_, 1); break;                                                                                       \
-        case 2: FGCN_BN_ACT8H(RES_, 2); break;                                                                                       \
-        case 3: FGCN_BN_ACT8H(RES_, 3); break;                                                                                       \
-        case 4: FGCN_BN_ACT8H(RES_, 4); break;                                                                                       \
-        case 5: FGCN_BN_ACT8H(RES_, 5); break;                                                                                       \
-        case 6: FGCN_BN_ACT8H(RES_, 6); break;                                                                                       \
-        default: FGCN_BN_ACT8H(RES_, 7); break;                                                                                      \
-    } while (0)
-        if (res_mode == 0) FGCN_BN_ACT8(0);
-        else if (res_mode == 1) FGCN_BN_ACT8(1);
-        else FGCN_BN_ACT8(2);
-#undef FGCN_BN_ACT8
-#undef FGCN_BN_ACT8H
+        // (without a residual b is not read: its bit selects no kernel)
+        const bool built = dispatch(
+            [&](auto RES, auto M, auto HM) {
+                hipLaunchKernelGGL((bn_act8_kernel<RES, M == 1, HM>), g8, blk, 0, s, a, vec_a, b, vec_b, out, sign_mask, n8, C, relu, str);
+                return true;
+            },
+            one_of<0, 1, 2>{res_mode}, one_of<0, 1>{sign_mask != nullptr}, one_of<1, 2, 3, 4, 5, 6, 7>{res_mode == 0 ? (half_mask & ~2) : half_mask});
+        FGCN_REQUIRE(built, FGCN_E_BADARG, "bn_act: half_mask=%d names no bfloat16 operand that res_mode=%d reads", half_mask, res_mode);
         return launch_status("bn_act");
     }
-#define FGCN_BN_ACT4(RES_, M_, O_, TY_) \
-    hipLaunchKernelGGL((bn_act_kernel<RES_, M_, O_, TY_>), g, blk, 0, s, a, vec_a, b, vec_b, out, sign_mask, n4, C, relu, str, ld_out, hm)
-#define FGCN_BN_ACT3(RES_, M_, O_)                                                                                \
-    do {                                                                                                          \
-        if (hm) FGCN_BN_ACT4(RES_, M_, O_, true);                                                                 \
-        else FGCN_BN_ACT4(RES_, M_, O_, false);                                                                   \
-    } while (0)
-#define FGCN_BN_ACT(RES_)                                                                                         \
-    do {                                                                                                          \
-        if (o16 && sign_mask) FGCN_BN_ACT3(RES_, true, true);                                                     \
-        else if (o16) FGCN_BN_ACT3(RES_, false, true);                                                            \
-        else if (sign_mask) FGCN_BN_ACT3(RES_, true, false);                                                      \
-        else FGCN_BN_ACT3(RES_, false, false);                                                                    \
-    } while (0)
-    if (res_mode == 0) FGCN_BN_ACT(0);
-    else if (res_mode == 1) FGCN_BN_ACT(1);
-    else FGCN_BN_ACT(2);
-#undef FGCN_BN_ACT
-#undef FGCN_BN_ACT3
-#undef FGCN_BN_ACT4
+    const bool built = dispatch(
+        [&](auto RES, auto M, auto O, auto TY) {
+            hipLaunchKernelGGL((bn_act_kernel<RES, M == 1, O == 1, TY == 1>), g, blk, 0, s, a, vec_a, b, vec_b, out, sign_mask, n4, C, relu, str,
+                               ld_out, in16);
+            return true;
+        },
+        one_of<0, 1, 2>{res_mode}, one_of<0, 1>{sign_mask != nullptr}, one_of<0, 1>{o16}, one_of<0, 1>{in16 != 0});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "bn_act: no such kernel form (res_mode=%d)", res_mode);
     return launch_status("bn_act");
 }
 
@@ -825,13 +803,15 @@ static int reduce_block(int C, dim3* blk) {
     return 0;
 }
 
+// the body of fgcn_bn_act_bwd_reduce and fgcn_bn_bwd_reduce_ld; half_mask: bit 0 = dout, bit 1 = a, bit 2 = b are bfloat16 tensors
 static int bn_act_bwd_reduce_impl(const float* dout, const float* out, const unsigned char* sign_mask,
                                   const float* a, const float* vec_a, const float* b, const float* vec_b,
                                   float* partials, int n_tiles, long long rows, int C, int res_mode, int relu,
-                                  int ld_dout, void* stream, int grp_rows = 0, int hm = 0) {
+                                  int ld_dout, void* stream, int grp_rows, int half_mask) {
+    const bool dout16 = half_mask & 1;
     FGCN_REQUIRE(grp_rows >= 0 && (grp_rows == 0 || (rows % grp_rows == 0 && ld_dout == C)), FGCN_E_BADARG,
                  "bn_act_bwd_reduce: %lld rows are not whole groups of %d", rows, grp_rows);
-    FGCN_REQUIRE(!hm || (fgcn::math_mode() == FGCN_MATH_BF16 && !((hm & 1) && grp_rows) && (!relu || sign_mask)), FGCN_E_BADARG,
+    FGCN_REQUIRE(!half_mask || (fgcn::math_mode() == FGCN_MATH_BF16 && !(dout16 && grp_rows) && (!relu || sign_mask)), FGCN_E_BADARG,
                  "bn_act_bwd_reduce: bfloat16 tensors need math mode bf16, the sign image as the ReLU gate and a float32 per-group gradient");
     FGCN_REQUIRE(dout && a && vec_a && partials && (!relu || out || sign_mask), FGCN_E_BADARG,
                  "bn_act_bwd_reduce: null pointer");
@@ -840,51 +820,36 @@ static int bn_act_bwd_reduce_impl(const float* dout, const float* out, const uns
                  fgcn_elem_tiles(rows));
     dim3 blk;
     FGCN_REQUIRE(reduce_block(C, &blk) == 0, FGCN_E_BADARG, "bn_act_bwd_reduce: C=%d unsupported", C);
-    const size_t lds = (size_t)blk.y * 3 * blk.x * 4 * sizeof(float) * ((hm && (fgcn::tuning(26) & 1)) ? 2 : 1);
+    const size_t lds = (size_t)blk.y * 3 * blk.x * 4 * sizeof(float) * ((half_mask && (fgcn::tuning(26) & 1)) ? 2 : 1);
     FGCN_REQUIRE(lds <= 64 * 1024, FGCN_E_BADARG, "bn_act_bwd_reduce: C=%d needs too much LDS", C);
     const long long rpt = rows_per_tile_for(rows);
     hipStream_t s = (hipStream_t)stream;
     dim3 g((unsigned)n_tiles, (unsigned)cdiv(C, (int)blk.x * 4));
-    if (hm && C % 8 == 0 && ld_dout == C && blk.x % 2 == 0) {
+    const int res = res_mode == 2 ? 2 : 0;      // (only a residual BatchNorm adds sums of its own)
+    if (half_mask && C % 8 == 0 && ld_dout == C && blk.x % 2 == 0) {
         // typed operands: eight channels per thread, the same rows per thread as the four-wide kernel (same sums, bit for bit)
         const dim3 blk8(blk.x / 2, (fgcn::tuning(26) & 1) ? blk.y * 2 : blk.y);      // (key 26 bit 0, A/B: 256 threads -- other sums in the last bits)
-#define FGCN_BN_RED8(RES_, HM_) \
-    hipLaunchKernelGGL((bn_act_bwd_reduce8_kernel<RES_, HM_>), g, blk8, lds, s, dout, sign_mask, a, vec_a, b, vec_b, partials, rows, rpt, C, relu, grp_rows)
-        if (res_mode == 2) {
-            switch (hm) {
-                case 1: FGCN_BN_RED8(2, 1); break;
-                case 2: FGCN_BN_RED8(2, 2); break;
-                case 3: FGCN_BN_RED8(2, 3); break;
-                case 4: FGCN_BN_RED8(2, 4); break;
-                case 5: FGCN_BN_RED8(2, 5); break;
-                case 6: FGCN_BN_RED8(2, 6); break;
-                default: FGCN_BN_RED8(2, 7); break;
-            }
-        } else {
-            switch (hm & 3) {
-                case 1: FGCN_BN_RED8(0, 1); break;
-                case 2: FGCN_BN_RED8(0, 2); break;
-                default: FGCN_BN_RED8(0, 3); break;
-            }
-        }
-#undef FGCN_BN_RED8
+        // (without a residual BatchNorm b is not read: its bit selects no kernel)
+        const bool built = dispatch(
+            [&](auto RES, auto HM) {
+                constexpr bool built = RES == 2 || HM <= 3;
+                if constexpr (built)
+                    hipLaunchKernelGGL((bn_act_bwd_reduce8_kernel<RES, HM>), g, blk8, lds, s, dout, sign_mask, a, vec_a, b, vec_b, partials, rows,
+                                       rpt, C, relu, grp_rows);
+                return built;
+            },
+            one_of<0, 2>{res}, one_of<1, 2, 3, 4, 5, 6, 7>{res == 2 ? half_mask : (half_mask & 3)});
+        FGCN_REQUIRE(built, FGCN_E_BADARG, "bn_act_bwd_reduce: half_mask=%d names no bfloat16 operand that res_mode=%d reads", half_mask, res_mode);
         return launch_status("bn_act_bwd_reduce");
     }
-#define FGCN_BN_RED3(RES_, M_, TY_)                                                                                \
-    hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<RES_, M_, TY_>), g, blk, lds, s, dout, out, sign_mask, a, vec_a, b, vec_b, \
-                       partials, rows, rpt, C, relu, ld_dout, grp_rows, hm)
-#define FGCN_BN_RED(RES_, M_)                                                                                      \
-    do {                                                                                                           \
-        if (hm) FGCN_BN_RED3(RES_, M_, true);                                                                      \
-        else FGCN_BN_RED3(RES_, M_, false);                                                                        \
-    } while (0)
-    if (res_mode == 2) {
-        if (sign_mask) FGCN_BN_RED(2, true); else FGCN_BN_RED(2, false);
-    } else {
-        if (sign_mask) FGCN_BN_RED(0, true); else FGCN_BN_RED(0, false);
-    }
-#undef FGCN_BN_RED
-#undef FGCN_BN_RED3
+    const bool built = dispatch(
+        [&](auto RES, auto M, auto TY) {
+            hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<RES, M == 1, TY == 1>), g, blk, lds, s, dout, out, sign_mask, a, vec_a, b, vec_b,
+                               partials, rows, rpt, C, relu, ld_dout, grp_rows, half_mask);
+            return true;
+        },
+        one_of<0, 2>{res}, one_of<0, 1>{sign_mask != nullptr}, one_of<0, 1>{half_mask != 0});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "bn_act_bwd_reduce: no such kernel form (res_mode=%d)", res_mode);
     return launch_status("bn_act_bwd_reduce");
 }
 
@@ -892,10 +857,12 @@ static int bn_act_bwd_apply_impl(const float* dout, const float* out, const unsi
                                  const float* a, const float* vec_a, const float* b, const float* vec_b,
                                  const float* sums, float* da, float* db,
                                  long long rows, int C, int res_mode, int relu, int train, int db_accumulate,
-                                 int ld_dout, void* stream, int grp_rows = 0, bool o16 = false, int hm = 0, int db16 = 0) {
+                                 int ld_dout, void* stream, int grp_rows, int half_mask) {
+    const bool dout16 = half_mask & 1, da16 = half_mask & 8, db16 = half_mask & 16;
+    const int in16 = half_mask & 7;      // the bfloat16 inputs (dout, a, b), as the kernels take them
     FGCN_REQUIRE(grp_rows >= 0 && (grp_rows == 0 || (rows % grp_rows == 0 && ld_dout == C)), FGCN_E_BADARG,
                  "bn_act_bwd_apply: %lld rows are not whole groups of %d", rows, grp_rows);
-    FGCN_REQUIRE((!hm && !o16) || (fgcn::math_mode() == FGCN_MATH_BF16 && !((hm & 1) && grp_rows) && (!hm || !relu || sign_mask)), FGCN_E_BADARG,
+    FGCN_REQUIRE(!(in16 || da16) || (fgcn::math_mode() == FGCN_MATH_BF16 && !(dout16 && grp_rows) && (!in16 || !relu || sign_mask)), FGCN_E_BADARG,
                  "bn_act_bwd_apply: bfloat16 tensors need math mode bf16, the sign image as the ReLU gate and a float32 per-group gradient");
     FGCN_REQUIRE(dout && vec_a && da && (!relu || out || sign_mask) && (!train || (a && sums)), FGCN_E_BADARG,
                  "bn_act_bwd_apply: null pointer");
@@ -909,64 +876,33 @@ static int bn_act_bwd_apply_impl(const float* dout, const float* out, const unsi
     hipStream_t s = (hipStream_t)stream;
     dim3 g(stream_blocks(n4)), blk(256);
     const int str = fgcn::stream_out(n4 * 16) ? 1 : 0;
-    FGCN_REQUIRE(!db16 || (hm && C % 8 == 0 && ld_dout == C && !db_accumulate && db && (!relu || sign_mask)), FGCN_E_BADARG,
+    FGCN_REQUIRE(!db16 || (in16 && C % 8 == 0 && ld_dout == C && !db_accumulate && db && (!relu || sign_mask)), FGCN_E_BADARG,
                  "bn_act_bwd_apply: a bfloat16 db needs the eight-wide typed kernel (C %% 8 == 0) and no accumulation");
-    if (hm && C % 8 == 0 && ld_dout == C && (!relu || sign_mask)) {      // typed operands: eight elements per thread
+    const int rm = (res_mode == 0 || !db) ? 0 : res_mode;      // (no db: the residual branch takes no gradient)
+    if (in16 && C % 8 == 0 && ld_dout == C && (!relu || sign_mask)) {      // typed operands: eight elements per thread
         const long long n8 = n4 / 2;
-        const int hm8 = hm | (o16 ? 8 : 0);
         dim3 g8(stream_blocks(n8));
-        const int rm = (res_mode == 0 || !db) ? 0 : res_mode;
-#define FGCN_BN_APP8H(RES_, HM_)                                                                                                          \
-    do {                                                                                                                                  \
-        if (train) hipLaunchKernelGGL((bn_act_bwd_apply8_kernel<RES_, HM_, true>), g8, blk, 0, s, dout, sign_mask, a, vec_a, b, vec_b, sums, da, db, n8, C, \
-                                      relu, inv_m, db_accumulate, str, grp_rows, db16);                                                   \
-        else hipLaunchKernelGGL((bn_act_bwd_apply8_kernel<RES_, HM_, false>), g8, blk, 0, s, dout, sign_mask, a, vec_a, b, vec_b, sums, da, db, n8, C,      \
-                                relu, inv_m, db_accumulate, str, grp_rows, db16);                                                         \
-    } while (0)
-#define FGCN_BN_APP8(RES_)                                                                                                                \
-    do switch (RES_ == 2 ? hm8 : (hm8 & ~4)) {                                                                                            \
-        case 1: FGCN_BN_APP8H(RES_, 1); break;                                                                                            \
-        case 2: FGCN_BN_APP8H(RES_, 2); break;                                                                                            \
-        case 3: FGCN_BN_APP8H(RES_, 3); break;                                                                                            \
-        case 4: FGCN_BN_APP8H(RES_, 4); break;                                                                                            \
-        case 5: FGCN_BN_APP8H(RES_, 5); break;                                                                                            \
-        case 6: FGCN_BN_APP8H(RES_, 6); break;                                                                                            \
-        case 7: FGCN_BN_APP8H(RES_, 7); break;                                                                                            \
-        case 8: FGCN_BN_APP8H(RES_, 8); break;                                                                                            \
-        case 9: FGCN_BN_APP8H(RES_, 9); break;                                                                                            \
-        case 10: FGCN_BN_APP8H(RES_, 10); break;                                                                                          \
-        case 11: FGCN_BN_APP8H(RES_, 11); break;                                                                                          \
-        case 12: FGCN_BN_APP8H(RES_, 12); break;                                                                                          \
-        case 13: FGCN_BN_APP8H(RES_, 13); break;                                                                                          \
-        case 14: FGCN_BN_APP8H(RES_, 14); break;                                                                                          \
-        default: FGCN_BN_APP8H(RES_, 15); break;                                                                                          \
-    } while (0)
-        if (rm == 0) FGCN_BN_APP8(0);
-        else if (rm == 1) FGCN_BN_APP8(1);
-        else FGCN_BN_APP8(2);
-#undef FGCN_BN_APP8
-#undef FGCN_BN_APP8H
+        const int hm8 = half_mask & 15;      // dout, a, b, da
+        // (only a residual BatchNorm reads b: elsewhere its bit selects no kernel)
+        const bool built = dispatch(
+            [&](auto RES, auto HM, auto TRAIN) {
+                hipLaunchKernelGGL((bn_act_bwd_apply8_kernel<RES, HM, TRAIN == 1>), g8, blk, 0, s, dout, sign_mask, a, vec_a, b, vec_b, sums, da, db,
+                                   n8, C, relu, inv_m, db_accumulate, str, grp_rows, db16 ? 1 : 0);
+                return true;
+            },
+            one_of<0, 1, 2>{rm}, one_of<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>{rm == 2 ? hm8 : (hm8 & ~4)}, one_of<0, 1>{train != 0});
+        FGCN_REQUIRE(built, FGCN_E_BADARG, "bn_act_bwd_apply: half_mask=%d names no bfloat16 operand that res_mode=%d %s db reads", half_mask,
+                     res_mode, db ? "with" : "without");
         return launch_status("bn_act_bwd_apply");
     }
-#define FGCN_BN_APP4(RES_, M_, O_, TY_)                                                                            \
-    hipLaunchKernelGGL((bn_act_bwd_apply_kernel<RES_, M_, O_, TY_>), g, blk, 0, s, dout, out, sign_mask, a, vec_a, b, vec_b, sums, \
-                       da, db, n4, C, relu, train, inv_m, db_accumulate, str, ld_dout, grp_rows, hm)
-#define FGCN_BN_APP(RES_, M_)                                                                                      \
-    do {                                                                                                           \
-        if (o16 && hm) FGCN_BN_APP4(RES_, M_, true, true);                                                         \
-        else if (o16) FGCN_BN_APP4(RES_, M_, true, false);                                                         \
-        else if (hm) FGCN_BN_APP4(RES_, M_, false, true);                                                          \
-        else FGCN_BN_APP4(RES_, M_, false, false);                                                                 \
-    } while (0)
-    if (res_mode == 0 || !db) {
-        if (sign_mask) FGCN_BN_APP(0, true); else FGCN_BN_APP(0, false);
-    } else if (res_mode == 1) {
-        if (sign_mask) FGCN_BN_APP(1, true); else FGCN_BN_APP(1, false);
-    } else {
-        if (sign_mask) FGCN_BN_APP(2, true); else FGCN_BN_APP(2, false);
-    }
-#undef FGCN_BN_APP
-#undef FGCN_BN_APP4
+    const bool built = dispatch(
+        [&](auto RES, auto M, auto O, auto TY) {
+            hipLaunchKernelGGL((bn_act_bwd_apply_kernel<RES, M == 1, O == 1, TY == 1>), g, blk, 0, s, dout, out, sign_mask, a, vec_a, b, vec_b,
+                               sums, da, db, n4, C, relu, train, inv_m, db_accumulate, str, ld_dout, grp_rows, in16);
+            return true;
+        },
+        one_of<0, 1, 2>{rm}, one_of<0, 1>{sign_mask != nullptr}, one_of<0, 1>{da16}, one_of<0, 1>{in16 != 0});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "bn_act_bwd_apply: no such kernel form (res_mode=%d)", res_mode);
     return launch_status("bn_act_bwd_apply");
 }
 
@@ -1110,9 +1046,8 @@ extern "C" int fgcn_row_softmax_bwd(const float* da, const float* c, float* ds, 
 extern "C" int fgcn_bn_act(const void* a, const float* vec_a, const void* b, const float* vec_b, void* out, unsigned char* sign_mask,
                            long long rows, int C, int res_mode, int relu, int half_mask, void* stream) {
     FGCN_REQUIRE((half_mask & ~7) == 0, FGCN_E_BADARG, "bn_act: half_mask=%d", half_mask);
-    // bit 0 a, bit 1 b -> hm; bit 2 out -> o16
     return bn_act_impl(static_cast<const float*>(a), vec_a, static_cast<const float*>(b), vec_b, static_cast<float*>(out), sign_mask, rows, C,
-                       res_mode, relu, C, stream, (half_mask & 4) != 0, half_mask & 3);
+                       res_mode, relu, C, stream, half_mask);
 }
 // grp_rows > 0: the gradient of a POOLED output (fgcn_bn_act_pool) -- dout is float[rows / grp_rows][C], one row per group of grp_rows consecutive
 // rows (already divided by the group size), read in place of the rows x C broadcast of it
@@ -1120,7 +1055,6 @@ extern "C" int fgcn_bn_act_bwd_reduce(const void* dout, int grp_rows, const floa
                                       const float* vec_a, const void* b, const float* vec_b, float* partials, int n_tiles, long long rows,
                                       int C, int res_mode, int relu, int half_mask, void* stream) {
     FGCN_REQUIRE((half_mask & ~7) == 0 && grp_rows >= 0, FGCN_E_BADARG, "bn_act_bwd_reduce: half_mask=%d grp_rows=%d", half_mask, grp_rows);
-    // bit 0 dout, bit 1 a, bit 2 b -> hm
     return bn_act_bwd_reduce_impl(static_cast<const float*>(dout), out, sign_mask, static_cast<const float*>(a), vec_a, static_cast<const float*>(b),
                                   vec_b, partials, n_tiles, rows, C, res_mode, relu, C, stream, grp_rows, half_mask);
 }
@@ -1128,10 +1062,9 @@ extern "C" int fgcn_bn_act_bwd_apply(const void* dout, int grp_rows, const float
                                      const float* vec_a, const void* b, const float* vec_b, const float* sums, void* da, void* db,
                                      long long rows, int C, int res_mode, int relu, int train, int db_accumulate, int half_mask, void* stream) {
     FGCN_REQUIRE((half_mask & ~31) == 0 && grp_rows >= 0, FGCN_E_BADARG, "bn_act_bwd_apply: half_mask=%d grp_rows=%d", half_mask, grp_rows);
-    // bit 0 dout, bit 1 a, bit 2 b -> hm; bit 3 da -> o16; bit 4 db -> db16
     return bn_act_bwd_apply_impl(static_cast<const float*>(dout), out, sign_mask, static_cast<const float*>(a), vec_a, static_cast<const float*>(b),
                                  vec_b, sums, static_cast<float*>(da), static_cast<float*>(db), rows, C, res_mode, relu, train, db_accumulate, C, stream,
-                                 grp_rows, (half_mask & 8) != 0, half_mask & 7, (half_mask & 16) ? 1 : 0);
+                                 grp_rows, half_mask);
 }
 
 // fgcn_bn_act followed by fgcn_group_mean without the tensor between them (the last block of the model): see bn_act_pool_kernel
@@ -1141,10 +1074,11 @@ extern "C" int fgcn_bn_act_pool_splits(int groups, int grp_rows) {
     return splits;
 }
 
-static int bn_act_pool_impl(const float* a, const float* vec_a, const float* b, const float* vec_b, unsigned char* sign_mask,
-                            float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, void* stream, int hm) {
+extern "C" int fgcn_bn_act_pool(const void* a, const float* vec_a, const void* b, const float* vec_b, unsigned char* sign_mask,
+                                float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, int half_mask, void* stream) {
+    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "bn_act_pool: half_mask=%d", half_mask);      // bit 0 a, bit 1 b
     FGCN_REQUIRE(a && vec_a && sign_mask && partial && pooled, FGCN_E_BADARG, "bn_act_pool: null pointer");
-    FGCN_REQUIRE(!hm || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "bn_act_pool: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(!half_mask || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "bn_act_pool: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(groups > 0 && groups <= 65535 && grp_rows > 0 && C > 0 && C % 8 == 0, FGCN_E_BADARG,
                  "bn_act_pool: groups=%d grp_rows=%d C=%d (C must be a multiple of 8)", groups, grp_rows, C);
     if (int e = check_elem("bn_act_pool", (long long)groups * grp_rows, C, res_mode, b, vec_b)) return e;
@@ -1157,25 +1091,17 @@ static int bn_act_pool_impl(const float* a, const float* vec_a, const float* b, 
     const dim3 grid((unsigned)splits, (unsigned)groups, (unsigned)cdiv(C, cx * 4)), blk((unsigned)cx, (unsigned)ny);
     const size_t lds = (size_t)ny * cx * 4 * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define FGCN_BN_POOL(RES_)                                                                                                          \
-    do {                                                                                                                            \
-        if (hm) hipLaunchKernelGGL((bn_act_pool_kernel<RES_, true>), grid, blk, lds, s, a, vec_a, b, vec_b, sign_mask, partial, grp_rows, per, C, hm); \
-        else hipLaunchKernelGGL((bn_act_pool_kernel<RES_, false>), grid, blk, lds, s, a, vec_a, b, vec_b, sign_mask, partial, grp_rows, per, C, 0);    \
-    } while (0)
-    if (res_mode == 0) FGCN_BN_POOL(0);
-    else if (res_mode == 1) FGCN_BN_POOL(1);
-    else FGCN_BN_POOL(2);
-#undef FGCN_BN_POOL
+    const bool built = dispatch(
+        [&](auto RES, auto TY) {
+            hipLaunchKernelGGL((bn_act_pool_kernel<RES, TY == 1>), grid, blk, lds, s, static_cast<const float*>(a), vec_a,
+                               static_cast<const float*>(b), vec_b, sign_mask, partial, grp_rows, per, C, half_mask);
+            return true;
+        },
+        one_of<0, 1, 2>{res_mode}, one_of<0, 1>{half_mask != 0});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "bn_act_pool: no such kernel form (res_mode=%d)", res_mode);
     hipLaunchKernelGGL(group_mean_finish_kernel, dim3((unsigned)cdiv((long long)groups * C, 256)), dim3(256), 0, s, partial, pooled, groups,
                        C, splits, 1.f / (float)grp_rows);
     return launch_status("bn_act_pool");
-}
-
-extern "C" int fgcn_bn_act_pool(const void* a, const float* vec_a, const void* b, const float* vec_b, unsigned char* sign_mask,
-                                float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, int half_mask, void* stream) {
-    FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "bn_act_pool: half_mask=%d", half_mask);      // bit 0 a, bit 1 b -> hm
-    return bn_act_pool_impl(static_cast<const float*>(a), vec_a, static_cast<const float*>(b), vec_b, sign_mask, partial, pooled, groups,
-                            grp_rows, C, res_mode, stream, half_mask);
 }
 
 // The same three passes for a plain BatchNorm (no residual, no activation) whose RESULT is a channel window of a wider tensor -- one
@@ -1184,15 +1110,15 @@ extern "C" int fgcn_bn_act_pool(const void* a, const float* vec_a, const void* b
 // gradient (dout = window base, stride ld_dout) -- no torch.cat, no contiguous copies of its backward slices.
 extern "C" int fgcn_bn_apply_ld(const float* a, const float* vec_a, float* out, long long rows, int C, int ld_out, void* stream) {
     FGCN_REQUIRE(ld_out >= C && ld_out % 4 == 0, FGCN_E_ALIGN, "bn_apply_ld: ld_out=%d must cover C=%d and be a multiple of 4", ld_out, C);
-    return bn_act_impl(a, vec_a, nullptr, nullptr, out, nullptr, rows, C, 0, 0, ld_out, stream);
+    return bn_act_impl(a, vec_a, nullptr, nullptr, out, nullptr, rows, C, 0, 0, ld_out, stream, 0);
 }
 extern "C" int fgcn_bn_bwd_reduce_ld(const float* dout, int ld_dout, const float* a, const float* vec_a, float* partials, int n_tiles,
                                      long long rows, int C, void* stream) {
     FGCN_REQUIRE(ld_dout >= C && ld_dout % 4 == 0 && aligned16(dout), FGCN_E_ALIGN, "bn_bwd_reduce_ld: ld_dout=%d must cover C=%d, multiples of 4", ld_dout, C);
-    return bn_act_bwd_reduce_impl(dout, nullptr, nullptr, a, vec_a, nullptr, nullptr, partials, n_tiles, rows, C, 0, 0, ld_dout, stream);
+    return bn_act_bwd_reduce_impl(dout, nullptr, nullptr, a, vec_a, nullptr, nullptr, partials, n_tiles, rows, C, 0, 0, ld_dout, stream, 0, 0);
 }
 extern "C" int fgcn_bn_bwd_apply_ld(const float* dout, int ld_dout, const float* a, const float* vec_a, const float* sums, float* da,
                                     long long rows, int C, int train, void* stream) {
     FGCN_REQUIRE(ld_dout >= C && ld_dout % 4 == 0 && aligned16(dout), FGCN_E_ALIGN, "bn_bwd_apply_ld: ld_dout=%d must cover C=%d, multiples of 4", ld_dout, C);
-    return bn_act_bwd_apply_impl(dout, nullptr, nullptr, a, vec_a, nullptr, nullptr, sums, da, nullptr, rows, C, 0, 0, train, 0, ld_dout, stream);
+    return bn_act_bwd_apply_impl(dout, nullptr, nullptr, a, vec_a, nullptr, nullptr, sums, da, nullptr, rows, C, 0, 0, train, 0, ld_dout, stream, 0, 0);
 }

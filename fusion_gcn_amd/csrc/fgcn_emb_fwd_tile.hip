@@ -22,7 +22,7 @@
 // Every sum has a fixed order (bitwise reproducible).
 #include <algorithm>
 
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 namespace fgcn {
 
@@ -74,10 +74,10 @@ __global__ __launch_bounds__(256, 2) void emb_fwd_tile_kernel(EmbFwP p) {
     const int cbase = col_wg * CW;                                   // first embedding channel of the workgroup
     const int ch0 = cbase + wc * 16 * MU;                            // ... of this wave (+ 16 mu)
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, p.w_plane_bytes * NP, 0x00020000);
-    const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc((void*)p.emb, 0, p.e_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, (unsigned)p.Ce * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.w3, p.w_plane_bytes * NP);
+    const __amdgpu_buffer_rsrc_t re = buffer_rsrc(p.emb, p.e_bytes);
+    const __amdgpu_buffer_rsrc_t rb = buffer_rsrc(p.bias, (unsigned)p.Ce * 4u);
 
     // bias of this lane's channels: unit mu, channels ch0 + 16 mu + 4 g4 .. + 3
     f32x4 bv[MU];
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void emb_fwd_tile_kernel(EmbFwP p) {
     }
 
     // ---- the segment's partial matrices: lane (w = 16 wt + l15, g4), register r -> v = 16 vt + 4 g4 + r ----------------------------------
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)p.partial, 0, p.p_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = buffer_rsrc(p.partial, p.p_bytes);
 #pragma unroll
     for (int ks = 0; ks < NSUB; ++ks) {
         const int k = NSUB == 3 ? ks : col_wg;
@@ -294,23 +294,14 @@ extern "C" int fgcn_emb_fwd_tile_segments(int B, int T, int V, int ic) {
     return ef_geom(B, T, V, ic).nseg;
 }
 
-static int emb_fwd_tile_impl(const float* x, const void* w3, const float* bias, float* emb, float* partial, int B, int T, int V, int Cin,
-                             int ic, int ld_x, int ld_e, void* stream, int e16);
-
 // half_mask (math mode bf16): bit 0 = x is a bfloat16 tensor, bit 1 = emb is written as BFLOAT16 (ld_e in elements): its only readers,
 // fgcn_emb_dx_tile / fgcn_emb_wgrad_tile, copy instead of convert -- bit-identical results, half the bytes of the 1.5-activation-wide tensor
 extern "C" int fgcn_emb_fwd_tile(const void* x, const void* w3, const float* bias, void* emb, float* partial, int B, int T, int V, int Cin,
                                  int ic, int ld_x, int ld_e, int half_mask, void* stream) {
     FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "emb_fwd_tile: half_mask=%d", half_mask);
-    FGCN_REQUIRE(!(half_mask & 2) || emb, FGCN_E_BADARG, "emb_fwd_tile: null pointer (half_mask=%d names a bfloat16 emb)", half_mask);
-    // the kernel's selector has the bits the other way round: e16 bit 0 = emb, bit 1 = x
-    return emb_fwd_tile_impl(static_cast<const float*>(x), w3, bias, static_cast<float*>(emb), partial, B, T, V, Cin, ic, ld_x, ld_e, stream,
-                             ((half_mask & 2) ? 1 : 0) | ((half_mask & 1) ? 2 : 0));
-}
-
-static int emb_fwd_tile_impl(const float* x, const void* w3, const float* bias, float* emb, float* partial, int B, int T, int V, int Cin,
-                             int ic, int ld_x, int ld_e, void* stream, int e16) {      // e16: bit 0 = emb bfloat16, bit 1 = x bfloat16 (1 or 3)
-    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_fwd_tile: bfloat16 tensors need math mode bf16");
+    const bool x16 = half_mask & 1, e16 = half_mask & 2;
+    FGCN_REQUIRE(!e16 || emb, FGCN_E_BADARG, "emb_fwd_tile: null pointer (half_mask=%d names a bfloat16 emb)", half_mask);
+    FGCN_REQUIRE(!half_mask || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_fwd_tile: bfloat16 tensors need math mode bf16");
     // emb == NULL (inference: nothing reads the embeddings after the gram): the kernel's stores of emb go to an empty buffer descriptor and are
     // dropped by the hardware -- the 1.5-activation-wide tensor is never written
     const bool write_emb = emb != nullptr;
@@ -324,55 +315,29 @@ static int emb_fwd_tile_impl(const float* x, const void* w3, const float* bias, 
     FGCN_REQUIRE(ld_x % 4 == 0 && ld_e % 4 == 0 && ld_x >= Cin && ld_e >= Ce, FGCN_E_ALIGN, "emb_fwd_tile: row strides");
     FGCN_REQUIRE(aligned16(x) && aligned16(w3) && aligned16(emb) && aligned16(bias) && (reinterpret_cast<uintptr_t>(partial) & 3u) == 0, FGCN_E_ALIGN,
                  "emb_fwd_tile: 16-byte alignment");
-    const long long x_bytes = (long long)B * T * V * ld_x * ((e16 & 2) ? 2 : 4), e_bytes = (long long)B * T * V * ld_e * ((e16 & 1) ? 2 : 4);
+    const long long x_bytes = (long long)B * T * V * ld_x * (x16 ? 2 : 4), e_bytes = (long long)B * T * V * ld_e * (e16 ? 2 : 4);
     const long long plane = (long long)Cin * Ce * 2;
-    FGCN_REQUIRE(x_bytes < 0x7FFF0000ll && e_bytes < 0x7FFF0000ll && plane * 3 < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(x_bytes) && fits_buffer(e_bytes) && fits_buffer(plane * 3), FGCN_E_BADARG,
                  "emb_fwd_tile: tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     const EfGeom g = ef_geom(B, T, V, ic);
     EmbFwP p;
-    p.x = x; p.w3 = w3; p.bias = bias; p.emb = emb; p.partial = partial;
+    p.x = static_cast<const float*>(x); p.w3 = w3; p.bias = bias; p.emb = static_cast<float*>(emb); p.partial = partial;
     p.B = B; p.T = T; p.V = V; p.Cin = Cin; p.ic = ic; p.Ce = Ce; p.ld_x = ld_x; p.ld_e = ld_e;
     p.F = g.F; p.tiles_t = g.tiles_t; p.tps = g.tps; p.nseg = g.nseg; p.ncol = g.ncol;
     p.x_bytes = (unsigned)x_bytes; p.e_bytes = write_emb ? (unsigned)e_bytes : 0u; p.w_plane_bytes = (unsigned)plane;
     p.p_bytes = (unsigned)((long long)B * g.nseg * 3 * 1024 * 4);
     const dim3 grid((unsigned)(B * g.nseg * g.ncol));
-    hipStream_t s = (hipStream_t)stream;
     const int np = fgcn::math_mode() == FGCN_MATH_BF16 ? 1 : 3;
-#define FGCN_EF(NP_, MU_, IC_, NSUB_)                                                                                       \
-    do {                                                                                                                    \
-        static bool opted = false;   /* once per instantiation; not a stream operation (stays out of graph captures) */    \
-        constexpr int lds_ = ef_lds<NP_>(IC_);                                                                              \
-        if (!opted) {                                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_fwd_tile_kernel<NP_, MU_, IC_, NSUB_>),            \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                                    \
-            opted = true;                                                                                                   \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((emb_fwd_tile_kernel<NP_, MU_, IC_, NSUB_>), grid, dim3(256), lds_, s, p);                       \
-    } while (0)
-#define FGCN_EF16(MU_, IC_, NSUB_, H_)                                                                                      \
-    do {                                                                                                                    \
-        static bool opted16 = false;                                                                                        \
-        constexpr int lds_ = ef_lds<1>(IC_);                                                                                \
-        if (!opted16) {                                                                                                     \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_fwd_tile_kernel<1, MU_, IC_, NSUB_, H_>),          \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                                    \
-            opted16 = true;                                                                                                 \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((emb_fwd_tile_kernel<1, MU_, IC_, NSUB_, H_>), grid, dim3(256), lds_, s, p);                     \
-    } while (0)
-#define FGCN_EF_NP(MU_, IC_, NSUB_)                    \
-    do {                                               \
-        if (np == 3) FGCN_EF(3, MU_, IC_, NSUB_);      \
-        else if (e16 == 3) FGCN_EF16(MU_, IC_, NSUB_, 3); \
-        else if (e16 == 2) FGCN_EF16(MU_, IC_, NSUB_, 2); \
-        else if (e16 == 1) FGCN_EF16(MU_, IC_, NSUB_, 1); \
-        else FGCN_EF(1, MU_, IC_, NSUB_);              \
-    } while (0)
-    if (ic == 16) FGCN_EF_NP(3, 16, 3);
-    else if (ic == 32) FGCN_EF_NP(6, 32, 3);
-    else FGCN_EF_NP(4, 64, 1);
-#undef FGCN_EF_NP
-#undef FGCN_EF16
-#undef FGCN_EF
+    // the kernel's storage selector has the bits the other way round: bit 0 = emb, bit 1 = x (one-part kernel only)
+    const int h16 = (e16 ? 1 : 0) | (x16 ? 2 : 0);
+    const bool built = dispatch(
+        [&](auto NP, auto IC, auto H16) {
+            constexpr int MU = IC == 16 ? 3 : (IC == 32 ? 6 : 4), NSUB = IC == 64 ? 1 : 3, lds = ef_lds<NP>(IC);
+            constexpr bool built = NP == 1 || H16 == 0;
+            if constexpr (built) launch_lds<emb_fwd_tile_kernel<NP, MU, IC, NSUB, H16>>(grid, dim3(256), lds, lds, (hipStream_t)stream, p);
+            return built;
+        },
+        one_of<1, 3>{np}, one_of<16, 32, 64>{ic}, one_of<0, 1, 2, 3>{h16});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "emb_fwd_tile: no such kernel form (ic=%d half_mask=%d)", ic, half_mask);
     return launch_status("emb_fwd_tile");
 }

@@ -33,7 +33,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 // Timing probes (wrong results; tools/build_probe.py only).  dx kernel: bit 0 = no contraction MFMAs, 1 = no mixing (the image stays unwritten),
 // 16 = the emb values' bytes in a quarter of the requests, 17 = no in-register split of the emb values (16 + 17: what pre-split transposed
@@ -49,7 +49,6 @@
 namespace fgcn {
 
 constexpr unsigned ET_OOB = 0x80000000u;
-constexpr int ET_AHB = 80;              // bytes per [w] row of a split matrix plane (32 joints v x bf16 + 16 pad: conflict-free b128 reads)
 
 // split matrix planes of `nm` consecutive (subset, side) groups starting at group g_lo -> LDS [slot][part][w][v]: the plane of group g holds
 // M[v_in][w_out] at [w_out][v_in] -- g even (theta_k): M = dS_k^T, g odd (phi_k): M = dS_k
@@ -60,20 +59,13 @@ __device__ __forceinline__ void et_stage_planes(unsigned char* Ah, const float* 
         const int g = g_lo + m, k = g >> 1;
         float a = 0.f;
         if (g < 6 && v < V && w < V) a = (g & 1) ? src[(k * V + v) * V + w] : src[(k * V + w) * V + v];
-        unsigned ph, pm, pl;
-        split_bf16_pair(a, 0.f, ph, pm, pl);
-        unsigned short* d = reinterpret_cast<unsigned short*>(Ah + ((m * NP) * 32 + w) * ET_AHB) + v;
-        d[0] = (unsigned short)ph;
-        if constexpr (NP == 3) {
-            d[32 * ET_AHB / 2] = (unsigned short)pm;
-            d[2 * 32 * ET_AHB / 2] = (unsigned short)pl;
-        }
+        put_split<NP, NP>(Ah, m, w, v, a);
     }
 }
-// The same for all six groups ONCE per sample, into global memory in the LDS image's own layout [group][part][w][ET_AHB bytes]
+// The same for all six groups ONCE per sample, into global memory in the LDS image's own layout [group][part][w][AHB bytes]
 // (fgcn_emb_dx_tile's workspace): a workgroup of the dx kernel -- one per 128-row tile -- then copies 16-byte pieces instead of splitting
 // 24 values per thread (300 of its 1500 vector instructions per tile and 72 two-byte LDS writes; SQ counters, profiles/r05_pmc_emb_dx.txt).
-template <int NP> constexpr int et_planes_bytes() { return 6 * NP * 32 * ET_AHB; }
+template <int NP> constexpr int et_planes_bytes() { return 6 * NP * 32 * AHB; }
 template <int NP>
 __global__ __launch_bounds__(256) void emb_planes_kernel(const float* __restrict__ d_s, unsigned char* __restrict__ planes, int V) {
     const float* src = d_s + (long long)blockIdx.x * 3 * V * V;
@@ -82,17 +74,11 @@ __global__ __launch_bounds__(256) void emb_planes_kernel(const float* __restrict
         const int g = i >> 10, k = g >> 1, w = (i >> 5) & 31, v = i & 31;
         float a = 0.f;
         if (v < V && w < V) a = (g & 1) ? src[(k * V + v) * V + w] : src[(k * V + w) * V + v];
-        unsigned ph, pm, pl;
-        split_bf16_pair(a, 0.f, ph, pm, pl);
-        unsigned short* d = reinterpret_cast<unsigned short*>(dst + ((g * NP) * 32 + w) * ET_AHB) + v;
-        d[0] = (unsigned short)ph;
-        if constexpr (NP == 3) {
-            d[32 * ET_AHB / 2] = (unsigned short)pm;
-            d[2 * 32 * ET_AHB / 2] = (unsigned short)pl;
-        }
+        put_split<NP, NP>(dst, g, w, v, a);
+        unsigned short* d = reinterpret_cast<unsigned short*>(dst + ((g * NP) * 32 + w) * AHB) + v;
         if (v < 8) d[32] = 0;                                        // the 16 pad bytes of the row (copied, never read as operands)
         if constexpr (NP == 3) {
-            if (v < 8) d[32 * ET_AHB / 2 + 32] = 0, d[2 * 32 * ET_AHB / 2 + 32] = 0;
+            if (v < 8) d[32 * AHB / 2 + 32] = 0, d[2 * 32 * AHB / 2 + 32] = 0;
         }
     }
 }
@@ -101,7 +87,7 @@ template <int NP, int NTHREADS>
 __device__ __forceinline__ void et_copy_planes(unsigned char* Ah, const unsigned char* src, int tid) {
     constexpr int PIECES = et_planes_bytes<NP>() / 16, NE = (PIECES + NTHREADS - 1) / NTHREADS;
     static_assert(PIECES % 64 == 0, "whole waves");
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (unsigned)et_planes_bytes<NP>(), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(src, (unsigned)et_planes_bytes<NP>());
     u32x4v v[NE];
 #pragma unroll
     for (int e = 0; e < NE; ++e) v[e] = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)(tid + NTHREADS * e) * 16u, 0, 0);
@@ -129,7 +115,7 @@ struct EmbDxP {
 constexpr int ED_XS = 64;               // bytes per image row and part (32 channels x bf16), 32-byte blocks XOR-swizzled by row bit 2
 constexpr int ED_PLANE = 128 * ED_XS;   // one part of the image: one 32-channel pair x 128 rows
 constexpr int ED_NMAT = 6;              // matrix slots: all (subset, side) groups stay resident
-template <int NP> constexpr int ed_lds() { return NP * ED_PLANE + ED_NMAT * NP * 32 * ET_AHB; }
+template <int NP> constexpr int ed_lds() { return NP * ED_PLANE + ED_NMAT * NP * 32 * AHB; }
 
 // One chunk = one 32-channel pair of demb (the image of two pairs beside six resident matrices would not leave room for two workgroups
 // per CU; re-staging the matrices per chunk cost 16 prefetch registers and spilled).  MAXU: mixing units (frame, 16-channel half) of a
@@ -153,12 +139,12 @@ __global__ __launch_bounds__(256, 2) void emb_dx_tile_kernel(EmbDxP p) {
     auto swz = [](int r) -> unsigned { return (unsigned)(r & 4) << 3; };
     extern __shared__ __attribute__((aligned(16))) unsigned char ed_lds_raw[];
     unsigned char* Xh = ed_lds_raw;                                  // [NP parts][128 rows][64 B]
-    unsigned char* ahs = Xh + NP * ED_PLANE;                         // [6 groups][NP parts][32 w][ET_AHB]
+    unsigned char* ahs = Xh + NP * ED_PLANE;                         // [6 groups][NP parts][32 w][AHB]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g4 = lane >> 4;
     const int wr = wave >> 1, wc = wave & 1;
-    const int vid = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);    // XCD-aware order, column tile fastest
+    const int vid = xcd_tile(blockIdx.x, p.per_xcd);    // XCD-aware order, column tile fastest
     if (vid >= p.tiles_m * p.tiles_n) return;
     const int bm = vid / p.tiles_n, bn = vid - bm * p.tiles_n;
     const int n = bm / p.tiles_t, tf = bm - n * p.tiles_t;
@@ -168,9 +154,9 @@ __global__ __launch_bounds__(256, 2) void emb_dx_tile_kernel(EmbDxP p) {
     const int nrows = nf * V;
     const int n0 = bn * BN;
 
-    const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc((void*)p.emb, 0, p.e_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, p.w_plane_bytes * NP, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rdx = __builtin_amdgcn_make_buffer_rsrc((void*)p.dx, 0, p.dx_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t re = buffer_rsrc(p.emb, p.e_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.w3, p.w_plane_bytes * NP);
+    const __amdgpu_buffer_rsrc_t rdx = buffer_rsrc(p.dx, p.dx_bytes);
 
     // the six matrices of this sample, split once per workgroup
     if (!(FGCN_PROBE_EMB & 8)) et_copy_planes<NP, 64 * NW>(ahs, p.planes + (p.s_batched ? (long long)n * et_planes_bytes<NP>() : 0), tid);
@@ -192,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void emb_dx_tile_kernel(EmbDxP p) {
             for (int nu = 0; nu < NU; ++nu) {
                 if constexpr (OLD32)
                     acc[mt][nu][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                                   __builtin_amdgcn_make_buffer_rsrc((void*)p.dx_old, 0, p.old_bytes, 0x00020000),
+                                                                   buffer_rsrc(p.dx_old, p.old_bytes),
                                                                    lane_base * 2u + nu * 64, (unsigned)(mt * 16 + r) * dx_row_b * 2u, 0));
                 else if constexpr (ACC && DX16)
                     acc[mt][nu][r] = __builtin_bit_cast(float, (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(
@@ -220,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void emb_dx_tile_kernel(EmbDxP p) {
     // emb values of a unit: lane (c = l15, g4) <- emb[(f, v = 8 g4 + j)][partner channel + l15], j = 0 .. 7 (the A fragment of the mixing).
     // Per request: per-lane offset = the unit's row base | the joint's out-of-range bit (both fixed for the kernel), scalar offset = the
     // joint's rows + the chunk's partner channels; past the last chunk the requests go to an empty descriptor (zeros, no traffic).
-    const __amdgpu_buffer_rsrc_t re_none = __builtin_amdgcn_make_buffer_rsrc((void*)p.emb, 0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t re_none = buffer_rsrc(p.emb, 0);
     unsigned ubase[MAXU], jinv[8];
 #pragma unroll
     for (int i = 0; i < MAXU; ++i)
@@ -283,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void emb_dx_tile_kernel(EmbDxP p) {
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) {
                     if constexpr ((FGCN_PROBE_EMB & 32768) != 0) af[pl] = xs[i][pl] + (unsigned)(wt + 1);
-                    else af[pl] = *reinterpret_cast<const u32x4v*>(ahs + ((g[i] * NP + pl) * 32 + 16 * wt + l15) * ET_AHB + 16 * g4);
+                    else af[pl] = *reinterpret_cast<const u32x4v*>(ahs + ((g[i] * NP + pl) * 32 + 16 * wt + l15) * AHB + 16 * g4);
                 }
                 // demb_f^T (16 c x 16 w): lane (w = 16 wt + l15, g4) holds channels 4 g4 .. + 3 of the half
                 if constexpr ((FGCN_PROBE_EMB & 8192) != 0) m[i][wt] = __builtin_bit_cast(f32x4, xs[i][0] ^ af[0] ^ xs[i][NP - 1] ^ af[NP - 1]);
@@ -414,18 +400,7 @@ constexpr int EW_ROWS = 160;            // rows of an x plane: (F - 1) V + 32 <=
 // row stride of an x plane: the channels' bytes + 32 -- eight consecutive rows then start 32 bytes apart modulo 256 (a transposing read's
 // half wave touches 8 rows x 32 bytes)
 template <int NT> constexpr int ew_rs() { return NT * 32 + 32; }
-template <int NP, int NT, int NM> constexpr int ew_lds() { return NP * EW_ROWS * ew_rs<NT>() + NM * NP * 32 * ET_AHB; }
-
-__device__ __forceinline__ u32x2 ew_read_tr16(const unsigned char* p) {
-    using v4s = __attribute__((ext_vector_type(4))) short;
-    const v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
-    return __builtin_bit_cast(u32x2, v);
-}
-
-template <class Fn, int... S>
-__device__ __forceinline__ void ew_for_slots(Fn&& fn, std::integer_sequence<int, S...>) {
-    (fn(std::integral_constant<int, S>{}), ...);
-}
+template <int NP, int NT, int NM> constexpr int ew_lds() { return NP * EW_ROWS * ew_rs<NT>() + NM * NP * 32 * AHB; }
 
 // CT: 16-channel demb tiles of the workgroup (8: every wave walks all frames; 4: two waves per tile take alternate frames, added at the
 // end); NT: 16-channel tiles of x (4 or 8); NSLOT: frame slots of a wave per tile, compile time (straight-line code: exact request counts);
@@ -462,8 +437,8 @@ __global__ __launch_bounds__(512, 1) void emb_wgrad_tile_kernel(EmbWgP p) {
     const int V = p.V, F = p.F;
     const int t_lo = seg * p.tps, t_hi = min(t_lo + p.tps, p.gtiles);
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc((void*)p.emb, 0, p.e_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t re = buffer_rsrc(p.emb, p.e_bytes);
 
     f32x4 acc[NT];
 #pragma unroll
@@ -557,7 +532,7 @@ __global__ __launch_bounds__(512, 1) void emb_wgrad_tile_kernel(EmbWgP p) {
                     u32x4v af[NP];
 #pragma unroll
                     for (int pl = 0; pl < NP; ++pl)
-                        af[pl] = *reinterpret_cast<const u32x4v*>(Ah + ((ms * NP + pl) * 32 + 16 * wt + l15) * ET_AHB + 16 * g4);
+                        af[pl] = *reinterpret_cast<const u32x4v*>(Ah + ((ms * NP + pl) * 32 + 16 * wt + l15) * AHB + 16 * g4);
                     // demb_f (32 joints w x 16 channels): lane (c = l15, g4) holds joints w = 4 g4 + r (wt = 0) and 16 + 4 g4 + r (wt = 1)
                     if constexpr ((FGCN_PROBE_EMB & 512) != 0) m[wt] = __builtin_bit_cast(f32x4, af[0] ^ xs[0]);
                     else m[wt] = mfma_np_k32<NP>(af, xs, f32x4{0.f, 0.f, 0.f, 0.f});
@@ -573,8 +548,8 @@ __global__ __launch_bounds__(512, 1) void emb_wgrad_tile_kernel(EmbWgP p) {
                     for (int pl = 0; pl < NP; ++pl) {
                         if ((FGCN_PROBE_EMB & 4096) && nt > 0) break;
                         const unsigned char* base = Im + pl * PL + nt * 32 + 8 * c4;
-                        const u32x2 lo = ew_read_tr16(base + r_lo * RS);
-                        const u32x2 hi = ew_read_tr16(base + r_hi * RS);
+                        const u32x2 lo = lds_read_tr16(base + r_lo * RS);
+                        const u32x2 hi = lds_read_tr16(base + r_hi * RS);
                         df[pl] = u32x4v{lo[0], lo[1], hi[0], hi[1]};
                     }
                     if constexpr ((FGCN_PROBE_EMB & 256) != 0) acc[nt][0] += __builtin_bit_cast(float, a3[0][0] ^ df[0][0]);
@@ -582,8 +557,8 @@ __global__ __launch_bounds__(512, 1) void emb_wgrad_tile_kernel(EmbWgP p) {
                 }
             }
         };
-        if (active) ew_for_slots([&](auto s_tag) { slot(s_tag, std::true_type{}); }, std::make_integer_sequence<int, NSLOT>{});
-        else ew_for_slots([&](auto s_tag) { slot(s_tag, std::false_type{}); }, std::make_integer_sequence<int, NSLOT>{});
+        if (active) for_slots([&](auto s_tag) { slot(s_tag, std::true_type{}); }, std::make_integer_sequence<int, NSLOT>{});
+        else for_slots([&](auto s_tag) { slot(s_tag, std::false_type{}); }, std::make_integer_sequence<int, NSLOT>{});
         // the next tile's x rows (and its sample's matrix planes) replace this one's
         __syncthreads();                                             // this tile's fragment reads are done
         const int n1 = (g + 1) / p.tiles_t;
@@ -593,8 +568,8 @@ __global__ __launch_bounds__(512, 1) void emb_wgrad_tile_kernel(EmbWgP p) {
     }
 
     // ---- the workgroup's slabs: partial[seg][c][o], bias_partial[seg][c] ---------------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)p.partial, 0, p.p_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias_partial, 0, p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = buffer_rsrc(p.partial, p.p_bytes);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias_partial, 0, p.b_bytes, BUFFER_FLAGS);      // (see buffer_rsrc)
     float bs = bsum + __shfl_xor(bsum, 16);                          // the four joint groups of a channel, fixed order
     bs += __shfl_xor(bs, 32);
     if constexpr (FP == 2) {                                         // fixed order: frames of the even slots + frames of the odd slots
@@ -687,56 +662,6 @@ extern "C" long long fgcn_emb_dx_tile_workspace(int B, int d_s_batched) {
     return (d_s_batched ? (long long)B : 1ll) * per;
 }
 
-// one instantiation of the dx kernel (LDS opt-in once per instantiation; not a stream operation: stays out of graph captures); the bfloat16-emb
-// form exists for the one-part kernel
-template <int NP, int NT, int MU, bool ACC, int PD, int RS>
-static void ed_go(int e16, dim3 grid, hipStream_t s, const EmbDxP& p) {      // e16: 1 = emb bfloat16, 3 = emb and dx
-    if constexpr (NP == 1 && ACC) {
-        if (e16 == 7) {
-            static bool opted167 = false;
-            if (!opted167) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS, 7>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, ed_lds<NP>());
-                opted167 = true;
-            }
-            hipLaunchKernelGGL((emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS, 7>), grid, dim3(256), ed_lds<NP>(), s, p);
-            return;
-        }
-    }
-    if constexpr (NP == 1) {
-        if (e16 == 3) {
-            static bool opted163 = false;
-            if (!opted163) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS, 3>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, ed_lds<NP>());
-                opted163 = true;
-            }
-            hipLaunchKernelGGL((emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS, 3>), grid, dim3(256), ed_lds<NP>(), s, p);
-            return;
-        }
-        if (e16) {
-            static bool opted16 = false;
-            if (!opted16) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS, 1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, ed_lds<NP>());
-                opted16 = true;
-            }
-            hipLaunchKernelGGL((emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS, 1>), grid, dim3(256), ed_lds<NP>(), s, p);
-            return;
-        }
-    }
-    static bool opted = false;
-    if (!opted) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, ed_lds<NP>());
-        opted = true;
-    }
-    hipLaunchKernelGGL((emb_dx_tile_kernel<NP, NT, MU, ACC, PD, RS>), grid, dim3(256), ed_lds<NP>(), s, p);
-}
-
-static int emb_dx_tile_impl(const float* emb, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V, int ic, int Cx,
-                            int ld_e, int ld_dx, int d_s_batched, int accumulate, void* stream, int e16, const float* dx_old = nullptr);
-
 // half_mask (math mode bf16): bit 0 = emb is a BFLOAT16 tensor (as fgcn_emb_fwd_tile writes it: bit-identical to the f32-emb call on the same
 // values), bit 1 = dx is (masks 0, 1, 3); strides in elements.
 // dx_old (mask 3, accumulate): a float32 tensor laid out like dx that holds the values to add to -- dx itself is then only written
@@ -745,17 +670,11 @@ extern "C" int fgcn_emb_dx_tile(const void* emb, const float* d_s, const void* w
                                 int ic, int Cx, int ld_e, int ld_dx, int d_s_batched, int accumulate, const float* dx_old, int half_mask,
                                 void* stream) {
     FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "emb_dx_tile: half_mask=%d (0, 1 or 3)", half_mask);
+    const bool e16 = half_mask & 1, dx16 = half_mask & 2;
     FGCN_REQUIRE(!dx_old || (half_mask == 3 && accumulate && aligned16(dx_old)), FGCN_E_BADARG,
                  "emb_dx_tile: dx_old comes with a bfloat16 emb and dx and accumulation");
-    // e16: bit 0 emb, bit 1 dx, 7 = both with the addend read from dx_old
-    return emb_dx_tile_impl(static_cast<const float*>(emb), d_s, w3, static_cast<float*>(dx), workspace, B, T, V, ic, Cx, ld_e, ld_dx, d_s_batched,
-                            accumulate, stream, dx_old ? 7 : half_mask, dx_old);
-}
-
-static int emb_dx_tile_impl(const float* emb, const float* d_s, const void* w3, float* dx, void* workspace, int B, int T, int V, int ic, int Cx,
-                            int ld_e, int ld_dx, int d_s_batched, int accumulate, void* stream, int e16, const float* dx_old) {
     FGCN_REQUIRE(emb && d_s && w3 && dx && workspace, FGCN_E_BADARG, "emb_dx_tile: null pointer");
-    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_dx_tile: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(!half_mask || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_dx_tile: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(B > 0 && T > 0, FGCN_E_BADARG, "emb_dx_tile: bad sizes B=%d T=%d", B, T);
     FGCN_REQUIRE(emb_tile_mode_ok() && emb_tile_sizes_ok(V, ic, Cx), FGCN_E_BADARG,
                  "emb_dx_tile: needs math mode bf16x3 or bf16, 16 <= V <= %d, ic %% 16 == 0, Cx %% 64 == 0 (V=%d ic=%d Cx=%d, mode %d)", FGCN_MAX_V, V,
@@ -764,13 +683,13 @@ static int emb_dx_tile_impl(const float* emb, const float* d_s, const void* w3, 
     FGCN_REQUIRE(ld_e % 4 == 0 && ld_dx % 4 == 0 && ld_e >= Ce && ld_dx >= Cx, FGCN_E_ALIGN, "emb_dx_tile: row strides");
     FGCN_REQUIRE(aligned16(emb) && aligned16(w3) && aligned16(dx) && aligned16(workspace) && (reinterpret_cast<uintptr_t>(d_s) & 3u) == 0, FGCN_E_ALIGN,
                  "emb_dx_tile: 16-byte alignment");
-    const long long e_bytes = (long long)B * T * V * ld_e * (e16 ? 2 : 4), dx_bytes = (long long)B * T * V * ld_dx * ((e16 & 2) ? 2 : 4);
+    const long long e_bytes = (long long)B * T * V * ld_e * (e16 ? 2 : 4), dx_bytes = (long long)B * T * V * ld_dx * (dx16 ? 2 : 4);
     const long long plane = (long long)Ce * Cx * 2;
-    FGCN_REQUIRE(e_bytes < 0x7FFF0000ll && dx_bytes < 0x7FFF0000ll && plane * 3 < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(e_bytes) && fits_buffer(dx_bytes) && fits_buffer(plane * 3), FGCN_E_BADARG,
                  "emb_dx_tile: tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     const int np = fgcn::math_mode() == FGCN_MATH_BF16 ? 1 : 3;
     EmbDxP p;
-    p.emb = emb; p.planes = static_cast<const unsigned char*>(workspace); p.w3 = w3; p.dx = dx;
+    p.emb = static_cast<const float*>(emb); p.planes = static_cast<const unsigned char*>(workspace); p.w3 = w3; p.dx = static_cast<float*>(dx);
     p.dx_old = dx_old; p.old_bytes = dx_old ? (unsigned)(dx_bytes * 2) : 0u;
     p.B = B; p.T = T; p.V = V; p.ic = ic; p.Ce = Ce; p.Cout = Cx; p.ld_e = ld_e; p.ld_dx = ld_dx; p.s_batched = d_s_batched;
     p.ic_inv = (unsigned)(((1ull << 32) + (unsigned)ic - 1) / (unsigned)ic);
@@ -788,38 +707,20 @@ static int emb_dx_tile_impl(const float* emb, const float* d_s, const void* w3, 
     // the split matrix planes, once per sample
     if (np == 3) hipLaunchKernelGGL((emb_planes_kernel<3>), dim3(d_s_batched ? B : 1), dim3(256), 0, s, d_s, static_cast<unsigned char*>(workspace), V);
     else hipLaunchKernelGGL((emb_planes_kernel<1>), dim3(d_s_batched ? B : 1), dim3(256), 0, s, d_s, static_cast<unsigned char*>(workspace), V);
-    const bool big = 2 * p.F > 12;                                   // mixing units per wave and chunk: ceil(2 F / 4)
-#define FGCN_ED_GO6(NP_, NT_, MU_, ACC_, PD_, RS_) ed_go<NP_, NT_, MU_, ACC_, PD_, RS_>(e16, grid, s, p)
-    /* tuning key 18 = 1: 128-column tiles with a two-slot weight ring (default four; 64-column tiles always two) */
-#define FGCN_ED_GO4(NP_, NT_, MU_, ACC_)                                   \
-    do {                                                                   \
-        if (NT_ == 1) FGCN_ED_GO6(NP_, 1, MU_, ACC_, 1, 2);                \
-        else if (variant == 1) FGCN_ED_GO6(NP_, 2, MU_, ACC_, 1, 2);       \
-        else FGCN_ED_GO6(NP_, 2, MU_, ACC_, 1, 4);                         \
-    } while (0)
-#define FGCN_ED_GO3(NP_, NT_, MU_)                     \
-    do {                                               \
-        if (accumulate) FGCN_ED_GO4(NP_, NT_, MU_, true); \
-        else FGCN_ED_GO4(NP_, NT_, MU_, false);        \
-    } while (0)
-#define FGCN_ED_GO2(NP_, NT_)                  \
-    do {                                       \
-        if (big) FGCN_ED_GO3(NP_, NT_, 4);     \
-        else FGCN_ED_GO3(NP_, NT_, 3);         \
-    } while (0)
-#define FGCN_ED_GO(NP_)                        \
-    do {                                       \
-        if (narrow) FGCN_ED_GO2(NP_, 1);       \
-        else FGCN_ED_GO2(NP_, 2);              \
-    } while (0)
-    const int variant = fgcn::tuning(18);
-    if (np == 3) FGCN_ED_GO(3);
-    else FGCN_ED_GO(1);
-#undef FGCN_ED_GO
-#undef FGCN_ED_GO2
-#undef FGCN_ED_GO3
-#undef FGCN_ED_GO4
-#undef FGCN_ED_GO6
+    const int mu = 2 * p.F > 12 ? 4 : 3;                             // mixing units per wave and chunk: ceil(2 F / 4)
+    // weight ring: 64-column tiles always two slots; 128-column tiles four (tuning key 18 = 1: two)
+    const int ring = narrow || fgcn::tuning(18) == 1 ? 2 : 4;
+    // the kernel's storage selector (one-part kernel only): half_mask, or 7 = both bfloat16 with the addend read from dx_old
+    const int h16 = dx_old ? 7 : half_mask;
+    const bool built = dispatch(
+        [&](auto NP, auto NT, auto MU, auto ACC, auto RS, auto H16) {
+            constexpr bool built = (NT == 2 || RS == 2) && (NP == 1 || H16 == 0) && (ACC == 1 || H16 != 7);
+            if constexpr (built) launch_lds<emb_dx_tile_kernel<NP, NT, MU, ACC == 1, 1, RS, H16>>(grid, dim3(256), ed_lds<NP>(), ed_lds<NP>(), s, p);
+            return built;
+        },
+        one_of<1, 3>{np}, one_of<1, 2>{narrow ? 1 : 2}, one_of<3, 4>{mu}, one_of<0, 1>{accumulate != 0}, one_of<2, 4>{ring},
+        one_of<0, 1, 3, 7>{h16});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "emb_dx_tile: no such kernel form (half_mask=%d accumulate=%d)", half_mask, accumulate);
     return launch_status("emb_dx_tile");
 }
 
@@ -830,55 +731,13 @@ extern "C" int fgcn_emb_wgrad_tile_slabs(int B, int T, int V, int ic, int Cx) {
     return g.ok ? g.nseg : 0;
 }
 
-template <int NP, int CT, int NT, int NS, int NM, int PF>
-static void ew_go(int e16, dim3 grid, hipStream_t s, const EmbWgP& p) {      // e16: 1 = emb bfloat16, 3 = emb and x
-    constexpr int lds_ = ew_lds<NP, NT, NM>();
-    if constexpr (NP == 1) {
-        if (e16 == 3) {
-            static bool attr163 = false;
-            if (!attr163) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_wgrad_tile_kernel<NP, CT, NT, NS, NM, PF, 3>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_);
-                attr163 = true;
-            }
-            hipLaunchKernelGGL((emb_wgrad_tile_kernel<NP, CT, NT, NS, NM, PF, 3>), grid, dim3(512), lds_, s, p);
-            return;
-        }
-        if (e16) {
-            static bool attr16 = false;
-            if (!attr16) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_wgrad_tile_kernel<NP, CT, NT, NS, NM, PF, 1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_);
-                attr16 = true;
-            }
-            hipLaunchKernelGGL((emb_wgrad_tile_kernel<NP, CT, NT, NS, NM, PF, 1>), grid, dim3(512), lds_, s, p);
-            return;
-        }
-    }
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&emb_wgrad_tile_kernel<NP, CT, NT, NS, NM, PF>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_);
-        attr = true;
-    }
-    hipLaunchKernelGGL((emb_wgrad_tile_kernel<NP, CT, NT, NS, NM, PF>), grid, dim3(512), lds_, s, p);
-}
-
-static int emb_wgrad_tile_impl(const float* emb, const float* x, const float* d_s, float* partial, float* bias_partial, int B, int T,
-                               int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, void* stream, int e16);
-
 // half_mask (math mode bf16): bit 0 = emb is a BFLOAT16 tensor (as fgcn_emb_fwd_tile writes it), bit 1 = x is (masks 0, 1, 3); strides in elements
 extern "C" int fgcn_emb_wgrad_tile(const void* emb, const void* x, const float* d_s, float* partial, float* bias_partial, int B,
                                    int T, int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, int half_mask, void* stream) {
     FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "emb_wgrad_tile: half_mask=%d (0, 1 or 3)", half_mask);
-    return emb_wgrad_tile_impl(static_cast<const float*>(emb), static_cast<const float*>(x), d_s, partial, bias_partial, B, T, V, ic, Cx, ld_e, ld_x,
-                               d_s_batched, stream, half_mask);      // e16 = half_mask: bit 0 emb, bit 1 x
-}
-
-static int emb_wgrad_tile_impl(const float* emb, const float* x, const float* d_s, float* partial, float* bias_partial, int B, int T,
-                               int V, int ic, int Cx, int ld_e, int ld_x, int d_s_batched, void* stream, int e16) {
+    const bool e16 = half_mask & 1, x16 = half_mask & 2;
     FGCN_REQUIRE(emb && x && d_s && partial && bias_partial, FGCN_E_BADARG, "emb_wgrad_tile: null pointer");
-    FGCN_REQUIRE(!e16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_wgrad_tile: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(!half_mask || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "emb_wgrad_tile: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(B > 0 && T > 0, FGCN_E_BADARG, "emb_wgrad_tile: bad sizes B=%d T=%d", B, T);
     FGCN_REQUIRE(fgcn_emb_tile_available(V, ic, Cx), FGCN_E_BADARG,
                  "emb_wgrad_tile: V=%d ic=%d Cx=%d in math mode %d not supported (bf16x3 or bf16, 16 <= V <= %d, ic %% 16 == 0, Cx in 64s)", V, ic,
@@ -894,46 +753,27 @@ static int emb_wgrad_tile_impl(const float* emb, const float* x, const float* d_
     FGCN_REQUIRE((long long)g.nseg * Ce * Cx * 4 < (1ll << 31), FGCN_E_BADARG, "emb_wgrad_tile: partial slabs must be smaller than 2 GiB");
     const int np = fgcn::math_mode() == FGCN_MATH_BF16 ? 1 : 3;
     EmbWgP p;
-    p.emb = emb, p.x = x, p.d_s = d_s, p.partial = partial, p.bias_partial = bias_partial;
+    p.emb = static_cast<const float*>(emb), p.x = static_cast<const float*>(x), p.d_s = d_s, p.partial = partial, p.bias_partial = bias_partial;
     p.B = B, p.T = T, p.V = V, p.ic = ic, p.Ce = Ce, p.Cx = Cx, p.ld_e = ld_e, p.ld_x = ld_x, p.s_batched = d_s_batched;
     p.F = g.F, p.tiles_t = g.tiles_t, p.gtiles = g.gtiles, p.tps = g.tps, p.nseg = g.nseg, p.n_cg = g.n_cg, p.n_og = g.n_og;
-    p.e_bytes = (unsigned)(rows * ld_e * (e16 ? 2 : 4)), p.x_bytes = (unsigned)(rows * ld_x * (e16 == 3 ? 2 : 4));
+    p.e_bytes = (unsigned)(rows * ld_e * (e16 ? 2 : 4)), p.x_bytes = (unsigned)(rows * ld_x * (x16 ? 2 : 4));
     p.p_bytes = (unsigned)((long long)g.nseg * Ce * Cx * 4), p.b_bytes = (unsigned)((long long)g.nseg * Ce * 4);
-    hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(g.nseg * g.n_cg * g.n_og));
-#define FGCN_EW6(NP_, CT_, NT_, NS_, NM_, PF_) ew_go<NP_, CT_, NT_, NS_, NM_, PF_>(e16, grid, s, p)
-    /* tuning key 19: slots the emb values are requested ahead (0 = two, 1 = one) */
-#define FGCN_EW(NP_, CT_, NT_, NS_, NM_)                           \
-    do {                                                           \
-        if (pf1) FGCN_EW6(NP_, CT_, NT_, NS_, NM_, 1);             \
-        else FGCN_EW6(NP_, CT_, NT_, NS_, NM_, 2);                 \
-    } while (0)
-    const bool pf1 = fgcn::tuning(19) == 1;
+    const int pf = fgcn::tuning(19) == 1 ? 1 : 2;      // tuning key 19: slots the emb values are requested ahead (0 = two, 1 = one)
     // frame slots of a wave per tile: F frames over 8 / CT waves per channel tile, rounded up to even
     const int nslot = ((g.F + 8 / g.CT - 1) / (8 / g.CT) + 1) & ~1;
     FGCN_REQUIRE(nslot == (g.CT == 8 ? (g.F > 6 ? 8 : 6) : 4), FGCN_E_BADARG, "emb_wgrad_tile: %d frames per tile: no such kernel form", g.F);
-#define FGCN_EW_NP(CT_, NT_, NS_, NM_)                     \
-    do {                                                   \
-        if (np == 3) FGCN_EW(3, CT_, NT_, NS_, NM_);       \
-        else FGCN_EW(1, CT_, NT_, NS_, NM_);               \
-    } while (0)
-    if (g.NM == 6) {                                                 // ic = 16
-        if (nslot == 8) FGCN_EW_NP(8, 4, 8, 6);
-        else FGCN_EW_NP(8, 4, 6, 6);
-    } else if (g.CT == 8) {
-        if (g.NT == 8) {
-            if (nslot == 8) FGCN_EW_NP(8, 8, 8, 2);
-            else FGCN_EW_NP(8, 8, 6, 2);
-        } else {
-            if (nslot == 8) FGCN_EW_NP(8, 4, 8, 2);
-            else FGCN_EW_NP(8, 4, 6, 2);
-        }
-    } else {
-        if (g.NT == 8) FGCN_EW_NP(4, 8, 4, 2);
-        else FGCN_EW_NP(4, 4, 4, 2);
-    }
-#undef FGCN_EW_NP
-#undef FGCN_EW
-#undef FGCN_EW6
+    // built: ic = 16 (NM = 6) as 8 x 4 tiles; otherwise channel tiles of 8 (6 or 8 slots) or 4 (4 slots) by 4 or 8 output tiles
+    const int ct = g.NM == 6 || g.CT == 8 ? 8 : 4, nt = g.NM != 6 && g.NT == 8 ? 8 : 4, ns = ct == 4 ? 4 : (nslot == 8 ? 8 : 6);
+    const bool built = dispatch(
+        [&](auto NP, auto CT, auto NT, auto NS, auto NM, auto PF, auto H16) {
+            constexpr int lds = ew_lds<NP, NT, NM>();
+            constexpr bool built = (CT == 8) == (NS != 4) && (NM == 2 || (CT == 8 && NT == 4)) && (NP == 1 || H16 == 0);
+            if constexpr (built) launch_lds<emb_wgrad_tile_kernel<NP, CT, NT, NS, NM, PF, H16>>(grid, dim3(512), lds, lds, (hipStream_t)stream, p);
+            return built;
+        },
+        one_of<1, 3>{np}, one_of<4, 8>{ct}, one_of<4, 8>{nt}, one_of<4, 6, 8>{ns}, one_of<2, 6>{g.NM == 6 ? 6 : 2}, one_of<1, 2>{pf},
+        one_of<0, 1, 3>{half_mask});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "emb_wgrad_tile: no such kernel form (%d frame slots, half_mask=%d)", nslot, half_mask);
     return launch_status("emb_wgrad_tile");
 }

@@ -13,7 +13,7 @@
 // rows_wgrad: dW[tap][k][n] = sum_rows a[src(row,tap)][k] * g[row][n]: both operands are K(=row)-major, so
 //   A/B fragments are single LDS dwords with the channel on the lane.  64x64 output tile per workgroup
 //   (one 32x32 accumulator per wave), rows split across blockIdx.z into deterministic partial slabs.
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 #include <type_traits>
 
 namespace fgcn {
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256, (MT == 1 && !DB) ? 3 : 2) void rows_gemm_kerne
     // tile fastest, so the workgroups that re-read one A row tile run on one XCD (one L2).  Speed only.
     int bm, bn;
     if (p.per_xcd > 0) {
-        const int vid = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);
+        const int vid = xcd_tile(blockIdx.x, p.per_xcd);
         if (vid >= p.tiles_m * p.tiles_n) return;
         bm = vid / p.tiles_n;
         bn = vid - bm * p.tiles_n;
@@ -90,9 +90,8 @@ __global__ __launch_bounds__(256, (MT == 1 && !DB) ? 3 : 2) void rows_gemm_kerne
     const int n_first = (int)fastdiv((unsigned)m0, p.dTV);    // 32-bit decode: host guarantees M < 2^29
     const long long in_base = (long long)n_first * p.T_in * p.V * p.ld_in;
     const long long in_left = (p.in_elems - in_base) * IS;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const char*>(p.in) + in_base * IS), 0, (unsigned)(in_left < 0x7FFFFFFFll ? in_left : 0x7FFFFFFFll), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc((reinterpret_cast<const char*>(p.in) + in_base * IS), (unsigned)(in_left < 0x7FFFFFFFll ? in_left : 0x7FFFFFFFll));
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.w, p.w_bytes);
 
     // the A-tile rows this thread stages: r = (tid >> 3) + 32*i
     unsigned roff[AR];
@@ -196,10 +195,8 @@ __global__ __launch_bounds__(256, (MT == 1 && !DB) ? 3 : 2) void rows_gemm_kerne
     // The output buffer covers exactly this tile's rows that exist (rows >= M fall outside and are dropped).
     const long long rows_left = p.M - m0;
     const unsigned tile_rows = (unsigned)(rows_left < BM ? rows_left : BM);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<char*>(p.out) + m0 * p.ld_out * (OUT16 ? 2 : 4)), 0, tile_rows * (unsigned)p.ld_out * (OUT16 ? 2u : 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.bias ? p.bias : p.w), 0, p.bias ? (unsigned)p.N * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc((reinterpret_cast<char*>(p.out) + m0 * p.ld_out * (OUT16 ? 2 : 4)), tile_rows * (unsigned)p.ld_out * (OUT16 ? 2u : 4u));
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc((p.bias ? p.bias : p.w), p.bias ? (unsigned)p.N * 4u : 0u);
     float ssum[NT], ssq[NT];
     // One branch around the whole epilogue (an `if (p.accumulate)` around the loads inside the unrolled loops made hipcc drain vmcnt(0)
     // -- every earlier store's write acknowledgement -- at each join, on the plain path too).  Accumulating form: the old values of
@@ -354,8 +351,8 @@ __global__ __launch_bounds__(256) void rows_wgrad_kernel(WgradP p) {
     // (n, tg, v) of those rows are decoded once (32-bit) and advanced by 64 rows per stage with carries.
     // Loads are buffer loads: rows / channels that do not exist carry an out-of-range offset and read as zeros, so the
     // eight loads of a stage issue back to back with no branches.
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.g_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rg = buffer_rsrc(p.g, p.g_bytes);
     constexpr unsigned OOB = 0x80000000u;
     const bool kcol_ok = k0 + c4 < p.K, ncol_ok = n0 + c4 < p.N;
     const int dt = BR / p.V, dv = BR - dt * p.V;
@@ -659,9 +656,10 @@ static int check_tmap(const fgcn_tmap& m) {
 static int rows_gemm_launch(const float* in, float* out, const float* w, const float* bias, float* stat_partials,
                             int B, int T_in, int T_out, int V, int K, int N, int ld_in, int ld_out,
                             fgcn_tmap map, int accumulate, int batch, long long in_bs, long long out_bs, long long w_bs,
-                            void* stream, int inner = 1, long long in_bs2 = 0, long long out_bs2 = 0, long long w_bs2 = 0, int io = 0) {
+                            void* stream, int inner, long long in_bs2, long long out_bs2, long long w_bs2, int half_mask) {
+    const bool out16 = half_mask & 2;      // (bit 0: a bfloat16 input)
     FGCN_REQUIRE(in && out && w, FGCN_E_BADARG, "rows_gemm: null pointer");
-    FGCN_REQUIRE(io == 0 || (fgcn::math_mode() == FGCN_MATH_BF16 && batch == 1 && inner == 1 && !((io & 2) && accumulate)), FGCN_E_BADARG,
+    FGCN_REQUIRE(half_mask == 0 || (fgcn::math_mode() == FGCN_MATH_BF16 && batch == 1 && inner == 1 && !(out16 && accumulate)), FGCN_E_BADARG,
                  "rows_gemm: bfloat16 tensors need math mode bf16, a single problem and (for a bfloat16 output) no accumulation");
     FGCN_REQUIRE(batch >= 1 && inner >= 1 && (long long)batch * inner <= 65535 && in_bs % 4 == 0 && out_bs % 4 == 0 && w_bs % 4 == 0 &&
                      in_bs2 % 4 == 0 && out_bs2 % 4 == 0 && w_bs2 % 4 == 0,
@@ -725,9 +723,9 @@ static int rows_gemm_launch(const float* in, float* out, const float* w, const f
     const bool bf = fgcn::math_mode() == FGCN_MATH_BF16;
 #define FGCN_LAUNCH(MT_, NT_, DB_)                                                                         \
     do {                                                                                                   \
-        if (bf && io == 3) hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, true, 3>), grid, dim3(256), 0, s, p);      \
-        else if (bf && io == 2) hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, true, 2>), grid, dim3(256), 0, s, p); \
-        else if (bf && io == 1) hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, true, 1>), grid, dim3(256), 0, s, p); \
+        if (bf && half_mask == 3) hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, true, 3>), grid, dim3(256), 0, s, p);      \
+        else if (bf && half_mask == 2) hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, true, 2>), grid, dim3(256), 0, s, p); \
+        else if (bf && half_mask == 1) hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, true, 1>), grid, dim3(256), 0, s, p); \
         else if (bf) hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, true>), grid, dim3(256), 0, s, p); \
         else hipLaunchKernelGGL((rows_gemm_kernel<MT_, NT_, DB_, false>), grid, dim3(256), 0, s, p);       \
     } while (0)
@@ -753,7 +751,7 @@ extern "C" int fgcn_rows_gemm(const void* in, void* out, const float* w, const f
                               fgcn_tmap map, int accumulate, int half_mask, void* stream) {
     FGCN_REQUIRE((half_mask & ~3) == 0, FGCN_E_BADARG, "rows_gemm: half_mask=%d", half_mask);
     return rows_gemm_launch(static_cast<const float*>(in), static_cast<float*>(out), w, bias, stat_partials, B, T_in, T_out, V, K, N, ld_in, ld_out,
-                            map, accumulate, 1, 0, 0, 0, stream, 1, 0, 0, 0, half_mask);      // io = half_mask: bit 0 in, bit 1 out
+                            map, accumulate, 1, 0, 0, 0, stream, 1, 0, 0, 0, half_mask);
 }
 
 extern "C" int fgcn_rows_gemm_batched(const float* in, float* out, const float* w, int batch, long long in_bstride,
@@ -762,7 +760,7 @@ extern "C" int fgcn_rows_gemm_batched(const float* in, float* out, const float* 
     FGCN_REQUIRE(rows > 0, FGCN_E_BADARG, "rows_gemm_batched: rows=%d", rows);
     const fgcn_tmap pointwise{1, 1, 0, 0, 1};
     return rows_gemm_launch(in, out, w, nullptr, nullptr, 1, rows, rows, 1, K, N, ld_in, ld_out, pointwise, accumulate, batch,
-                            in_bstride, out_bstride, w_bstride, stream);
+                            in_bstride, out_bstride, w_bstride, stream, 1, 0, 0, 0, 0);
 }
 
 extern "C" int fgcn_rows_gemm_batched2(const float* in, float* out, const float* w, int batch, long long in_bstride,
@@ -772,7 +770,7 @@ extern "C" int fgcn_rows_gemm_batched2(const float* in, float* out, const float*
     FGCN_REQUIRE(rows > 0, FGCN_E_BADARG, "rows_gemm_batched2: rows=%d", rows);
     const fgcn_tmap pointwise{1, 1, 0, 0, 1};
     return rows_gemm_launch(in, out, w, nullptr, nullptr, 1, rows, rows, 1, K, N, ld_in, ld_out, pointwise, accumulate, batch,
-                            in_bstride, out_bstride, w_bstride, stream, inner, in_bstride2, out_bstride2, w_bstride2);
+                            in_bstride, out_bstride, w_bstride, stream, inner, in_bstride2, out_bstride2, w_bstride2, 0);
 }
 
 extern "C" int fgcn_rows_wgrad(const float* a, const float* g, float* partial,
@@ -792,7 +790,7 @@ extern "C" int fgcn_rows_wgrad(const float* a, const float* g, float* partial,
     p.M = (long long)B * T_g * V;
     FGCN_REQUIRE(p.M < (1ll << 31) - 4096, FGCN_E_BADARG, "rows_wgrad: too many rows (32-bit row indices)");
     const long long a_bytes = (long long)B * T_a * V * ld_a * 4, g_bytes = p.M * ld_g * 4;
-    FGCN_REQUIRE(a_bytes < 0x7FFF0000ll && g_bytes < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(a_bytes) && fits_buffer(g_bytes), FGCN_E_BADARG,
                  "rows_wgrad: operands must be smaller than 2 GiB (32-bit buffer offsets)");
     p.a_bytes = (unsigned)a_bytes; p.g_bytes = (unsigned)g_bytes;
     p.rows_per_split = cdiv(cdiv(p.M, nsplit), 64) * 64;

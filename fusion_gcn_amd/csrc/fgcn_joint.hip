@@ -6,7 +6,7 @@
 // at a time, the joint index sits on the MFMA row/K dimension and 32 channels on the lanes, so global loads and
 // stores are 128-byte contiguous per half-wave.  These ops are HBM-bound (each activation element feeds one
 // 32x32x2 step); the fused spatial kernel (fgcn_spatial.hip) removes them from the forward pass.
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 // joint_dagg reads every operand tile exactly once: its tile loads carry the non-temporal hint (-6 % per launch in kbench, -0.03 .. -0.2 ms on the step;
 // the same hint on joint_gram's and joint_mix_vec's loads, whose rows are read by several subsets / waves, cost 20-50 %: profiles/r03_ab_store_nt.txt)
 #ifndef FGCN_DAGG_LDAUX
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void joint_mix_kernel(MixP p) {
     const int ksteps = (V + 1) >> 1;
     // branch-free buffer loads (lanes / joints that do not take part read zeros through an out-of-range offset), issued
     // one (item, term) step ahead of the MFMA chain that consumes them
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc(p.in, p.in_bytes);
     constexpr unsigned OOB = 0x80000000u;
     auto issue = [&](int t, int it, int tr, float (&bv)[16]) {
         const fgcn_mix_item& item = p.items[it < p.n_items ? it : 0];
@@ -164,8 +164,8 @@ __global__ __launch_bounds__(256) void joint_mix_vec_kernel(MixVP p) {
     }
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, p.out_bytes);
     constexpr unsigned OOB = 0x80000000u;
     const bool lane_ok = VW * l31 < p.nch;  // all items of a launch have the same width (checked on the host)
     unsigned koff[16], uoff[16];
@@ -277,8 +277,8 @@ __global__ __launch_bounds__(256, 3) void joint_gram3_kernel(GramP p) {
     const int V = p.V;
     const bool row_ok = l31 < V;
     const int vv = row_ok ? l31 : 0;
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.in1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in2, 0, p.in2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = buffer_rsrc(p.in1, p.in1_bytes);
+    const __amdgpu_buffer_rsrc_t r2 = buffer_rsrc(p.in2, p.in2_bytes);
     constexpr unsigned OOB = 0x80000000u;
     int ic1[3], ic2[3];
 #pragma unroll
@@ -342,8 +342,8 @@ __global__ __launch_bounds__(256, 3) void joint_gram_kernel(GramP p) {
 
     // Branch-free buffer loads (absent joints / channels read as zeros through an out-of-range offset).  Widths are
     // multiples of 4 (host check).
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.in1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in2, 0, p.in2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = buffer_rsrc(p.in1, p.in1_bytes);
+    const __amdgpu_buffer_rsrc_t r2 = buffer_rsrc(p.in2, p.in2_bytes);
     constexpr unsigned OOB = 0x80000000u;
     // item descriptors in scalar registers (dynamic indexing of the kernel-argument array went through vector memory
     // and a full vmcnt(0) drain in front of every prefetch)
@@ -493,11 +493,10 @@ __global__ __launch_bounds__(256, MB) void joint_dagg_kernel(DaggP p) {
     __syncthreads();
 
     constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)p.dagg, 0, p.d_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rd = buffer_rsrc(p.dagg, p.d_bytes);
     // dx rows of this workgroup's frames: offsets relative to frame t0 (no tensor-size limit on dx)
-    const __amdgpu_buffer_rsrc_t rdx = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.dx + ((long long)n * p.T + t0) * V * p.ld_dx), 0, (unsigned)((t1 - t0) * V * p.ld_dx) * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rdx = buffer_rsrc((p.dx + ((long long)n * p.T + t0) * V * p.ld_dx), (unsigned)((t1 - t0) * V * p.ld_dx) * 4u);
 
     // gated addends: resources over this workgroup's frames (element index relative to frame t0; C % 8 == 0 keeps the sign
     // image byte-aligned at every frame)
@@ -505,8 +504,8 @@ __global__ __launch_bounds__(256, MB) void joint_dagg_kernel(DaggP p) {
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
         const long long e0 = ((long long)n * p.T + t0) * V * C;
-        re[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.e[i] + e0), 0, (unsigned)((t1 - t0) * V * C) * 4u, 0x00020000);
-        rm[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.m[i] + (e0 >> 3)), 0, (unsigned)((t1 - t0) * V * C) >> 3, 0x00020000);
+        re[i] = buffer_rsrc((p.e[i] + e0), (unsigned)((t1 - t0) * V * C) * 4u);
+        rm[i] = buffer_rsrc((p.m[i] + (e0 >> 3)), (unsigned)((t1 - t0) * V * C) >> 3);
     }
 
     // staging: lane -> (row = lane / 8 + 8 * pass, 16-byte group lane % 8); all 32 rows are written (absent joints and
@@ -713,7 +712,6 @@ struct SWgradP {
 };
 
 constexpr int YTS = 68;   // dy tile row stride (64 channels + 4)
-constexpr int SW_AHB = 80; // MM == 2: bytes per [w] row of a split A^ plane (32 joints x bf16 + 16 pad: conflict-free b128 reads)
 
 // MM: 0 = exact f32 MFMAs; 1 = FGCN_MATH_BF16 (operands rounded once, one bf16 MFMA per product group); 2 = FGCN_MATH_BF16X3: the
 // weight-gradient contraction from exact three-way bf16 splits (six v_mfma_f32_32x32x16_bf16 per 16 joints, 384 cycles instead of
@@ -725,9 +723,9 @@ __global__ __launch_bounds__(256, 2) void spatial_wgrad_kernel(SWgradP p) {
     constexpr bool BF = MM == 1;
     extern __shared__ __attribute__((aligned(16))) float wsm[];
     float* img = wsm;                                  // [3][kk = in joint v][i = out joint w] = A^_k[v][w]
-    // MM == 2: instead, the three bf16 parts of A^_k as planes [subset][part][w][SW_AHB bytes] (v contiguous: one ds_read_b128 = the 8
+    // MM == 2: instead, the three bf16 parts of A^_k as planes [subset][part][w][AHB bytes] (v contiguous: one ds_read_b128 = the 8
     // joints of a lane's fragment of the split joint mixing)
-    constexpr int IMG_FLOATS = MM == 2 ? 9 * 32 * SW_AHB / 4 : 3 * IMG;
+    constexpr int IMG_FLOATS = MM == 2 ? 9 * 32 * AHB / 4 : 3 * IMG;
     unsigned char* ahs = reinterpret_cast<unsigned char*>(wsm);
     float* tiles = wsm + IMG_FLOATS;                   // [4 waves][32 * DTS + 32 * YTS]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -742,16 +740,10 @@ __global__ __launch_bounds__(256, 2) void spatial_wgrad_kernel(SWgradP p) {
     float* yt = xt + 32 * DTS;
 
     const float* msrc = p.mats + (p.mats_batched ? (long long)n * NS * V * V : 0);
-    for (int e = tid; e < 3 * IMG; e += 256) {
+    for (int e = tid; e < 3 * IMG; e += 256) {      // (its own loop: stage_adjacency_planes changes this kernel's scalar registers)
         if constexpr (MM == 2) {
             const int k = e >> 10, w = (e >> 5) & 31, v = e & 31;
-            const float a = (k < NS && v < V && w < V) ? msrc[(k * V + v) * V + w] : 0.f;
-            unsigned ph, pm, pl;
-            split_bf16_pair(a, 0.f, ph, pm, pl);
-            unsigned short* d = reinterpret_cast<unsigned short*>(ahs + ((k * 3) * 32 + w) * SW_AHB) + v;
-            d[0] = (unsigned short)ph;
-            d[32 * SW_AHB / 2] = (unsigned short)pm;
-            d[2 * 32 * SW_AHB / 2] = (unsigned short)pl;
+            put_split<3>(ahs, k, w, v, (k < NS && v < V && w < V) ? msrc[(k * V + v) * V + w] : 0.f);
         } else {
             const int k = e >> 10, v = (e >> 5) & 31, w = e & 31;
             img[e] = (k < NS && v < V && w < V) ? msrc[(k * V + v) * V + w] : 0.f;
@@ -760,8 +752,8 @@ __global__ __launch_bounds__(256, 2) void spatial_wgrad_kernel(SWgradP p) {
     __syncthreads();
 
     constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(p.dy, p.dy_bytes);
     const int cw = min(32, p.Cin - c0), ow = min(64, p.Cout - o0);
 
     f32x16 accw[3][2];
@@ -820,7 +812,7 @@ __global__ __launch_bounds__(256, 2) void spatial_wgrad_kernel(SWgradP p) {
                         u32x4v af[3];
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            af[pl] = *reinterpret_cast<const u32x4v*>(ahs + ((k * 3 + pl) * 32 + l31) * SW_AHB + 16 * h + 32 * s2);
+                            af[pl] = *reinterpret_cast<const u32x4v*>(ahs + ((k * 3 + pl) * 32 + l31) * AHB + 16 * h + 32 * s2);
                         agg = mfma_x3_k16(af, xf3[s2], agg);
                     }
                 } else {
@@ -862,7 +854,7 @@ __global__ __launch_bounds__(256, 2) void spatial_wgrad_kernel(SWgradP p) {
         }
     }
     // cross-wave sum (fixed order) and the slab: partial[slab][k * Cin + c0 + c][o0 + o]
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)p.partial, 0, p.p_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = buffer_rsrc(p.partial, p.p_bytes);
     const unsigned slab = (unsigned)(n * gridDim.y + chunk);
     float* red = tiles;
 #pragma unroll
@@ -980,7 +972,7 @@ extern "C" int fgcn_joint_mix(const float* in, float* out, const float* mats, in
                  "joint_mix: channel counts exceed row strides");
     FGCN_REQUIRE(B <= 65535, FGCN_E_BADARG, "joint_mix: B too large for grid.y");
     const long long mix_in_bytes = (long long)B * T * V * ld_in * 4;
-    FGCN_REQUIRE(mix_in_bytes < 0x7FFF0000ll, FGCN_E_BADARG, "joint_mix: input must be smaller than 2 GiB");
+    FGCN_REQUIRE(fits_buffer(mix_in_bytes), FGCN_E_BADARG, "joint_mix: input must be smaller than 2 GiB");
     MixP p;
     p.in_bytes = (unsigned)mix_in_bytes;
     p.in = in; p.out = out; p.mats = mats;
@@ -1013,7 +1005,7 @@ extern "C" int fgcn_joint_gram(const float* in1, const float* in2, float* partia
                  "joint_gram: strides/pointers must be 16-byte aligned");
     FGCN_REQUIRE(B <= 65535, FGCN_E_BADARG, "joint_gram: B too large for grid.y");
     const long long b1 = (long long)B * T * V * ld1 * 4, b2 = (long long)B * T * V * ld2 * 4;
-    FGCN_REQUIRE(b1 < 0x7FFF0000ll && b2 < 0x7FFF0000ll, FGCN_E_BADARG, "joint_gram: operands must be smaller than 2 GiB");
+    FGCN_REQUIRE(fits_buffer(b1) && fits_buffer(b2), FGCN_E_BADARG, "joint_gram: operands must be smaller than 2 GiB");
     GramP p;
     p.in1_bytes = (unsigned)b1; p.in2_bytes = (unsigned)b2;
     p.in1 = in1; p.in2 = in2; p.partial = partial;
@@ -1075,7 +1067,7 @@ extern "C" int fgcn_joint_mix_vec(const float* in, float* out, const float* mats
     FGCN_REQUIRE(ld_in % 4 == 0 && ld_out % 4 == 0 && aligned16(in) && aligned16(out), FGCN_E_ALIGN,
                  "joint_mix_vec: 16-byte alignment");
     const long long in_bytes = (long long)B * T * V * ld_in * 4, out_bytes = (long long)B * T * V * ld_out * 4;
-    FGCN_REQUIRE(in_bytes < 0x7FFF0000ll && out_bytes < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(in_bytes) && fits_buffer(out_bytes), FGCN_E_BADARG,
                  "joint_mix_vec: tensors must be smaller than 2 GiB");
     MixVP p;
     p.in_bytes = (unsigned)in_bytes; p.out_bytes = (unsigned)out_bytes;
@@ -1133,7 +1125,7 @@ extern "C" int fgcn_joint_dagg(const float* x, const float* dagg, const float* m
     FGCN_REQUIRE(x && dagg && mats && dx && partial, FGCN_E_BADARG, "joint_dagg: null pointer");
     const int n_extra = extra1 ? (extra2 ? 2 : 1) : 0;
     FGCN_REQUIRE((!extra1 || mask1) && (!extra2 || (mask2 && extra1)), FGCN_E_BADARG, "joint_dagg: a gated addend needs its sign image");
-    FGCN_REQUIRE(n_extra == 0 || (C % 8 == 0 && (long long)B * T * V * C * 4 < 0x7FFF0000ll), FGCN_E_BADARG,
+    FGCN_REQUIRE(n_extra == 0 || (C % 8 == 0 && fits_buffer((long long)B * T * V * C * 4)), FGCN_E_BADARG,
                  "joint_dagg: gated addends need C %% 8 == 0 (C=%d) and tensors below 2 GiB", C);
     FGCN_REQUIRE(B > 0 && B <= 65535 && T > 0 && V > 0 && V <= FGCN_MAX_V && C > 0 && t_chunk > 0, FGCN_E_BADARG,
                  "joint_dagg: bad sizes B=%d T=%d V=%d C=%d", B, T, V, C);
@@ -1142,7 +1134,7 @@ extern "C" int fgcn_joint_dagg(const float* x, const float* dagg, const float* m
                      aligned16(x) && aligned16(dagg),
                  FGCN_E_ALIGN, "joint_dagg: C and the row strides must be multiples of 4 and cover the channels");
     const long long xb = (long long)B * T * V * ld_x * 4, db = (long long)B * T * V * ld_dagg * 4;
-    FGCN_REQUIRE(xb < 0x7FFF0000ll && db < 0x7FFF0000ll && (long long)t_chunk * V * ld_dx * 4 < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(xb) && fits_buffer(db) && fits_buffer((long long)t_chunk * V * ld_dx * 4), FGCN_E_BADARG,
                  "joint_dagg: x and dagg must be smaller than 2 GiB");
     DaggP p;
     p.x = x; p.dagg = dagg; p.mats = mats; p.dx = dx; p.partial = partial;
@@ -1211,7 +1203,7 @@ extern "C" int fgcn_spatial_wgrad(const float* x, const float* dy, const float* 
     const int nchunk = fgcn_spatial_wgrad_chunks(B, T, Cin, Cout);
     const long long xb = (long long)B * T * V * ld_x * 4, yb = (long long)B * T * V * ld_dy * 4;
     const long long pb = (long long)B * nchunk * n_subsets * Cin * Cout * 4;
-    FGCN_REQUIRE(xb < 0x7FFF0000ll && yb < 0x7FFF0000ll && pb < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(xb) && fits_buffer(yb) && fits_buffer(pb), FGCN_E_BADARG,
                  "spatial_wgrad: tensors must be smaller than 2 GiB");
     SWgradP p;
     p.x = x; p.dy = dy; p.mats = mats; p.partial = partial;
@@ -1220,36 +1212,19 @@ extern "C" int fgcn_spatial_wgrad(const float* x, const float* dy, const float* 
     p.x_bytes = (unsigned)xb; p.dy_bytes = (unsigned)yb; p.p_bytes = (unsigned)pb;
     const bool x3m = fgcn::math_mode() == FGCN_MATH_BF16X3 && !(fgcn::tuning(6) & 512);
     // 65,536 bytes (76,288 with the split A^ planes of the bf16x3 form): two workgroups per CU
-    const size_t lds = (size_t)((x3m ? 9 * 32 * SW_AHB / 4 : 3 * IMG) + 4 * (32 * DTS + 32 * YTS)) * sizeof(float);
+    const size_t lds = (size_t)((x3m ? 9 * 32 * AHB / 4 : 3 * IMG) + 4 * (32 * DTS + 32 * YTS)) * sizeof(float);
     dim3 grid((unsigned)(cdiv(Cin, 32) * p.tiles_o), (unsigned)nchunk, (unsigned)B);
     hipStream_t s = (hipStream_t)stream;
-    const bool bf = fgcn::math_mode() == FGCN_MATH_BF16;
-    const bool x3 = fgcn::math_mode() == FGCN_MATH_BF16X3 && !(fgcn::tuning(6) & 512);   // key 6 bit 9: the exact-f32 form (A/B control)
     const int ks = (V + 3) / 4 * 2;
-    static bool lds_opt_in = false;   // once per process; not a stream operation (stays out of graph captures)
-#define FGCN_SW(KS_)                                                                                                   \
-    do {                                                                                                               \
-        if (bf) hipLaunchKernelGGL((spatial_wgrad_kernel<KS_, 1>), grid, dim3(256), lds, s, p);                        \
-        else if (x3) hipLaunchKernelGGL((spatial_wgrad_kernel<KS_, 2>), grid, dim3(256), lds, s, p);                   \
-        else hipLaunchKernelGGL((spatial_wgrad_kernel<KS_, 0>), grid, dim3(256), lds, s, p);                           \
-    } while (0)
-    const int max_lds = (int)((9 * 32 * SW_AHB / 4 + 4 * (32 * DTS + 32 * YTS)) * sizeof(float));   // the larger (bf16x3) form
-#define FGCN_SW_ATTR(KS_)                                                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_wgrad_kernel<KS_, 0>),                          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_wgrad_kernel<KS_, 2>),                          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);                                   \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_wgrad_kernel<KS_, 1>),                          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)
-    if (!lds_opt_in) {
-        FGCN_SW_ATTR(10); FGCN_SW_ATTR(12); FGCN_SW_ATTR(14); FGCN_SW_ATTR(16);
-        lds_opt_in = true;
-    }
-    if (ks <= 10) FGCN_SW(10);
-    else if (ks <= 12) FGCN_SW(12);
-    else if (ks <= 14) FGCN_SW(14);
-    else FGCN_SW(16);
-#undef FGCN_SW
-#undef FGCN_SW_ATTR
+    constexpr int max_lds = (int)((9 * 32 * AHB / 4 + 4 * (32 * DTS + 32 * YTS)) * sizeof(float));   // the larger (bf16x3) form
+    // MM: 1 = bf16, 2 = bf16x3 (x3m; tuning key 6 bit 9 selects the exact-f32 form instead, an A/B control), 0 = f32
+    const bool built = dispatch(
+        [&](auto KS, auto MM) {
+            launch_lds<spatial_wgrad_kernel<KS, MM>>(grid, dim3(256), max_lds, lds, s, p);
+            return true;
+        },
+        one_of<10, 12, 14, 16>{ks <= 10 ? 10 : (ks <= 12 ? 12 : (ks <= 14 ? 14 : 16))},
+        one_of<0, 1, 2>{fgcn::math_mode() == FGCN_MATH_BF16 ? 1 : (x3m ? 2 : 0)});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "spatial_wgrad: no such kernel form");
     return launch_status("spatial_wgrad");
 }

@@ -5,7 +5,7 @@
 // The 32-joint kernels (fgcn_joint.hip) put the joint index on one 32-wide MFMA dimension; here a 64-joint matrix is a 2 x 2 grid of
 // 32 x 32 MFMA blocks.  The graph sizes up to 32 joints never reach this file: the host picks it only for V > FGCN_MAX_V.
 // Same formulas, same operand precision (f32 products, f32 accumulation) in every math mode, like the 32-joint forms.
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 namespace fgcn {
 
@@ -47,8 +47,8 @@ __global__ __launch_bounds__(256) void joint_mix_wide_kernel(MixWP p) {
     }
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, p.out_bytes);
     constexpr unsigned OOB = 0x80000000u;
 
     for (int t = t0 + wave; t < t1; t += 4) {
@@ -118,8 +118,8 @@ __global__ __launch_bounds__(256, 2) void joint_gram_wide_kernel(GramWP p) {
     const int V = p.V;
     const int c1 = __builtin_amdgcn_readfirstlane(p.items[it].c1), c2 = __builtin_amdgcn_readfirstlane(p.items[it].c2);
     const int width = __builtin_amdgcn_readfirstlane(p.items[it].width);
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in1, 0, p.in1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.in2, 0, p.in2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = buffer_rsrc(p.in1, p.in1_bytes);
+    const __amdgpu_buffer_rsrc_t r2 = buffer_rsrc(p.in2, p.in2_bytes);
     constexpr unsigned OOB = 0x80000000u;
     f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
     const int nq = (width + 7) >> 3;
@@ -283,7 +283,7 @@ extern "C" int fgcn_joint_mix_wide(const float* in, float* out, const float* mat
                  "joint_mix_wide: n_mats=%d n_items=%d out of range", n_mats, n_items);
     FGCN_REQUIRE(ld_in > 0 && ld_out > 0 && aligned16(in) && aligned16(out), FGCN_E_ALIGN, "joint_mix_wide: 16-byte alignment");
     const long long in_bytes = (long long)B * T * V * ld_in * 4, out_bytes = (long long)B * T * V * ld_out * 4;
-    FGCN_REQUIRE(in_bytes < 0x7FFF0000ll && out_bytes < 0x7FFF0000ll, FGCN_E_BADARG, "joint_mix_wide: tensors must be smaller than 2 GiB");
+    FGCN_REQUIRE(fits_buffer(in_bytes) && fits_buffer(out_bytes), FGCN_E_BADARG, "joint_mix_wide: tensors must be smaller than 2 GiB");
     MixWP p;
     p.in = in; p.out = out; p.mats = mats;
     p.in_bytes = (unsigned)in_bytes; p.out_bytes = (unsigned)out_bytes;
@@ -329,7 +329,7 @@ extern "C" int fgcn_joint_gram_wide(const float* in1, const float* in2, float* p
     FGCN_REQUIRE(ld1 % 4 == 0 && ld2 % 4 == 0 && aligned16(in1) && aligned16(in2), FGCN_E_ALIGN,
                  "joint_gram_wide: strides/pointers must be 16-byte aligned");
     const long long b1 = (long long)B * T * V * ld1 * 4, b2 = (long long)B * T * V * ld2 * 4;
-    FGCN_REQUIRE(b1 < 0x7FFF0000ll && b2 < 0x7FFF0000ll, FGCN_E_BADARG, "joint_gram_wide: operands must be smaller than 2 GiB");
+    FGCN_REQUIRE(fits_buffer(b1) && fits_buffer(b2), FGCN_E_BADARG, "joint_gram_wide: operands must be smaller than 2 GiB");
     GramWP p;
     p.in1 = in1; p.in2 = in2; p.partial = partial;
     p.in1_bytes = (unsigned)b1; p.in2_bytes = (unsigned)b2;

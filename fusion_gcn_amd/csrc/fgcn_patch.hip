@@ -313,20 +313,7 @@ static PatchArgs patch_args(const float* s, const float* p, const float* w1, con
     return a;
 }
 
-static void patch_lds_opt_in() {
-    static bool done = false;     // once per process; not a stream operation (stays out of graph captures)
-    if (done) return;
-    const int max_lds = 160 * 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_input_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              max_lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_input_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              max_lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_input_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              max_lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_input_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              max_lds);
-    done = true;
-}
+constexpr int PI_MAX_LDS = 160 * 1024;
 
 static int patch_bps(long long R, int H) {
     const long long nblocks = cdiv(R, PI_ROWS);
@@ -351,9 +338,8 @@ extern "C" int fgcn_patch_input_fwd(const float* s, const float* p, const float*
     const bool bf = w1 && math_mode() == FGCN_MATH_BF16;
     const unsigned grid = (unsigned)(a.nblocks + cdiv(a.pad_rows, 256));
     const size_t lds = w1 ? patch_lds(P, false) : 0;
-    patch_lds_opt_in();
-    if (bf) hipLaunchKernelGGL(patch_input_fwd_kernel<true>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(patch_input_fwd_kernel<false>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+    if (bf) launch_lds<patch_input_fwd_kernel<true>>(dim3(grid), dim3(256), PI_MAX_LDS, lds, (hipStream_t)stream, a);
+    else launch_lds<patch_input_fwd_kernel<false>>(dim3(grid), dim3(256), PI_MAX_LDS, lds, (hipStream_t)stream, a);
     if (int e = launch_status("patch_input_fwd")) return e;
     return stat_partials ? fgcn_data_bn_stats(z, stat_partials, N, M, T, V, a.C, stat_centered, stream) : FGCN_OK;
 }
@@ -367,10 +353,9 @@ extern "C" int fgcn_patch_input_bwd(const float* dz, const float* s, const float
     a.dz = dz, a.pw1 = pw1, a.pb1 = pb1, a.pw2 = pw2, a.pb2 = pb2;
     a.bps = patch_bps(a.R, H);
     const dim3 grid((unsigned)(H / 32), (unsigned)cdiv(a.nblocks, a.bps));
-    patch_lds_opt_in();
     if (math_mode() == FGCN_MATH_BF16)
-        hipLaunchKernelGGL(patch_input_bwd_kernel<true>, grid, dim3(256), patch_lds(P, true), (hipStream_t)stream, a);
+        launch_lds<patch_input_bwd_kernel<true>>(grid, dim3(256), PI_MAX_LDS, patch_lds(P, true), (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(patch_input_bwd_kernel<false>, grid, dim3(256), patch_lds(P, true), (hipStream_t)stream, a);
+        launch_lds<patch_input_bwd_kernel<false>>(grid, dim3(256), PI_MAX_LDS, patch_lds(P, true), (hipStream_t)stream, a);
     return launch_status("patch_input_bwd");
 }

@@ -15,7 +15,7 @@
 //        chunk's largest magnitude (wave maxima through four LDS words ahead of the barrier that exists anyway); the accumulators are
 //        rescaled (a power of two: exact) whenever the scale moves, and the epilogue multiplies 2^-ea 2^-ew back out.
 //   NT = 1 / 2: 64 / 128 output columns per tile.
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 // Timing probes (wrong results; tools/probes builds only): bit 0 = no output stores, bit 1 = no MFMAs, bit 2 = the image is deposited
 // once per workgroup (later chunks skip the split + LDS writes), bit 3 = no input fetches after the first, bit 4 = weight fragments
@@ -75,16 +75,14 @@ __global__ __launch_bounds__(256, 2) void pw_x3_kernel(PwP p) {
     const int l15 = lane & 15, g4 = lane >> 4;
     const int wr = wave >> 1, wc = wave & 1;
 
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const unsigned char*>(p.w3) + (NP == 2 ? 16 : 0)), 0, p.w_plane_bytes * NP, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc((reinterpret_cast<const unsigned char*>(p.w3) + (NP == 2 ? 16 : 0)), p.w_plane_bytes * NP);
     constexpr int EA_NONE = 1000;                                    // "no scale yet" (every chunk so far was all zeros)
     const int ew = NP == 2 ? min(scale_exp_for(*reinterpret_cast<const unsigned*>(p.w3)), 126) : 0;
     float* smax = reinterpret_cast<float*>(Xh + NP * plane);         // NP == 2: the four waves' chunk maxima
     int ea = EA_NONE, abound = 0;
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void*)(p.bias ? (const void*)p.bias : p.w3), 0,
-                                                                           p.bias ? (unsigned)p.N * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc((p.bias ? (const void*)p.bias : p.w3), p.bias ? (unsigned)p.N * 4u : 0u);
 
     // this workgroup's tiles: ids go round-robin over the 8 XCDs, so workgroup b works inside XCD (b & 7)'s share of the virtual tile
     // list [x * per_xcd, (x + 1) * per_xcd) (column tile fastest), taking every wg_per_xcd-th tile from its local index on
@@ -384,33 +382,25 @@ extern "C" int fgcn_pw_gemm_available(void) {
     return (mm == FGCN_MATH_BF16X3 || mm == FGCN_MATH_BF16) ? 1 : 0;
 }
 
-static int pw_gemm_impl(const float* in, float* out, const void* w3, const float* bias, float* stat_partials, long long rows,
-                        int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, void* stream_, int io);
-
 // half_mask (math mode bf16, half-precision activation storage): bit 0 = `in` is a bfloat16 tensor, bit 1 = `out` is (not with
 // accumulation); strides in elements; stat_partials: the moments of the float32 results
 extern "C" int fgcn_pw_gemm(const void* in, void* out, const void* w3, const float* bias, float* stat_partials, long long rows,
                             int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, int half_mask, void* stream_) {
     FGCN_REQUIRE((half_mask & ~3) == 0 && !((half_mask & 2) && accumulate), FGCN_E_BADARG, "pw_gemm: half_mask=%d (a bfloat16 output: no accumulation)",
                  half_mask);
-    return pw_gemm_impl(static_cast<const float*>(in), static_cast<float*>(out), w3, bias, stat_partials, rows, K, N, ld_in, ld_out, accumulate,
-                        in_amax, stream_, half_mask);      // io = half_mask: bit 0 in, bit 1 out
-}
-
-static int pw_gemm_impl(const float* in, float* out, const void* w3, const float* bias, float* stat_partials, long long rows,
-                        int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, void* stream_, int io) {
+    const bool in16 = half_mask & 1, out16 = half_mask & 2;
     FGCN_REQUIRE(in && out && w3 && rows > 0, FGCN_E_BADARG, "pw_gemm: null pointer or no rows");
-    FGCN_REQUIRE(io == 0 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "pw_gemm: bfloat16 tensors need math mode bf16");
+    FGCN_REQUIRE(half_mask == 0 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "pw_gemm: bfloat16 tensors need math mode bf16");
     FGCN_REQUIRE(fgcn_pw_gemm_available(), FGCN_E_BADARG, "pw_gemm: a split-bf16 math mode (bf16x3 / bf16) only");
     FGCN_REQUIRE(K > 0 && K % 32 == 0 && N > 0 && N % 4 == 0 && ld_in % 4 == 0 && ld_out % 4 == 0 && ld_in >= K && ld_out >= N,
                  FGCN_E_ALIGN, "pw_gemm: K must be a multiple of 32, N and the row strides multiples of 4 (K=%d N=%d ld_in=%d ld_out=%d)", K,
                  N, ld_in, ld_out);
     FGCN_REQUIRE(aligned16(in) && aligned16(w3) && aligned16(out), FGCN_E_ALIGN, "pw_gemm: 16-byte alignment");
-    const long long in_bytes = rows * ld_in * ((io & 1) ? 2 : 4), out_bytes = rows * ld_out * ((io & 2) ? 2 : 4), plane = (long long)K * N * 2;
-    FGCN_REQUIRE(in_bytes < 0x7FFF0000ll && out_bytes < 0x7FFF0000ll && plane * 3 < 0x7FFF0000ll, FGCN_E_BADARG,
+    const long long in_bytes = rows * ld_in * (in16 ? 2 : 4), out_bytes = rows * ld_out * (out16 ? 2 : 4), plane = (long long)K * N * 2;
+    FGCN_REQUIRE(fits_buffer(in_bytes) && fits_buffer(out_bytes) && fits_buffer(plane * 3), FGCN_E_BADARG,
                  "pw_gemm: tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     PwP p;
-    p.in = in; p.out = out; p.w3 = w3; p.bias = bias; p.stats = stat_partials;
+    p.in = static_cast<const float*>(in); p.out = static_cast<float*>(out); p.w3 = w3; p.bias = bias; p.stats = stat_partials;
     p.M = rows;
     p.in_bytes = (unsigned)in_bytes; p.out_bytes = (unsigned)out_bytes; p.w_plane_bytes = (unsigned)plane;
     p.K = K; p.N = N; p.ld_in = ld_in; p.ld_out = ld_out; p.accumulate = accumulate;
@@ -430,37 +420,18 @@ static int pw_gemm_impl(const float* in, float* out, const void* w3, const float
     const bool one = fgcn::math_mode() == FGCN_MATH_BF16, two = fgcn::f16x2_products();
     const size_t lds = (size_t)128 * 128 * (one ? 1 : (two ? 2 : 3)) + 16;
     hipStream_t s = (hipStream_t)stream_;
-    const bool stream = !(io & 2) && fgcn::stream_out(rows * (long long)N * 4);
-#define FGCN_PW_LAUNCH(NT_, NP_)                                                                                         \
-    do {                                                                                                                 \
-        if (accumulate) hipLaunchKernelGGL((pw_x3_kernel<NT_, NP_, true>), grid, dim3(256), lds, s, p);                  \
-        else if (stream) hipLaunchKernelGGL((pw_x3_kernel<NT_, NP_, false, true>), grid, dim3(256), lds, s, p);         \
-        else hipLaunchKernelGGL((pw_x3_kernel<NT_, NP_, false>), grid, dim3(256), lds, s, p);                            \
-    } while (0)
-#define FGCN_PW_LAUNCH_T(NT_)       /* one part, typed tensors */                                                        \
-    do {                                                                                                                 \
-        if (accumulate) hipLaunchKernelGGL((pw_x3_kernel<NT_, 1, true, false, 1>), grid, dim3(256), lds, s, p);          \
-        else if (io == 1 && stream) hipLaunchKernelGGL((pw_x3_kernel<NT_, 1, false, true, 1>), grid, dim3(256), lds, s, p); \
-        else if (io == 1) hipLaunchKernelGGL((pw_x3_kernel<NT_, 1, false, false, 1>), grid, dim3(256), lds, s, p);       \
-        else if (io == 2) hipLaunchKernelGGL((pw_x3_kernel<NT_, 1, false, false, 2>), grid, dim3(256), lds, s, p);       \
-        else hipLaunchKernelGGL((pw_x3_kernel<NT_, 1, false, false, 3>), grid, dim3(256), lds, s, p);                    \
-    } while (0)
-    if (io) {
-        FGCN_REQUIRE(one && !(accumulate && io != 1), FGCN_E_BADARG, "pw_gemm: an accumulating call takes a bfloat16 input only");
-        if (narrow) FGCN_PW_LAUNCH_T(1);
-        else FGCN_PW_LAUNCH_T(2);
-        return launch_status("pw_gemm");
-    }
-    if (narrow) {
-        if (one) FGCN_PW_LAUNCH(1, 1);
-        else if (two) FGCN_PW_LAUNCH(1, 2);
-        else FGCN_PW_LAUNCH(1, 3);
-    } else {
-        if (one) FGCN_PW_LAUNCH(2, 1);
-        else if (two) FGCN_PW_LAUNCH(2, 2);
-        else FGCN_PW_LAUNCH(2, 3);
-    }
-#undef FGCN_PW_LAUNCH
-#undef FGCN_PW_LAUNCH_T
+    const bool str = !accumulate && !out16 && fgcn::stream_out(rows * (long long)N * 4);
+    FGCN_REQUIRE(!half_mask || (one && !(accumulate && half_mask != 1)), FGCN_E_BADARG, "pw_gemm: an accumulating call takes a bfloat16 input only");
+    // built: accumulating or streamed stores, not both; typed tensors (IO = half_mask) for the one-part kernel, a bfloat16 output through
+    // the plain stores only
+    const bool built = dispatch(
+        [&](auto NT, auto NP, auto ACC, auto STR, auto IO) {
+            constexpr bool built = !(ACC == 1 && STR == 1) && (IO == 0 || NP == 1) && (IO < 2 || (ACC == 0 && STR == 0));
+            if constexpr (built) hipLaunchKernelGGL((pw_x3_kernel<NT, NP, ACC == 1, STR == 1, IO>), grid, dim3(256), lds, s, p);
+            return built;
+        },
+        one_of<1, 2>{narrow ? 1 : 2}, one_of<1, 2, 3>{one ? 1 : (two ? 2 : 3)}, one_of<0, 1>{accumulate != 0}, one_of<0, 1>{str},
+        one_of<0, 1, 2, 3>{half_mask});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "pw_gemm: no such kernel form (half_mask=%d accumulate=%d)", half_mask, accumulate);
     return launch_status("pw_gemm");
 }

@@ -22,7 +22,7 @@
 //           steps per value instead of 5.
 // The joint axis sits on 25 of the 32 MFMA columns (78 % of the f32 MFMA rate is the ceiling of this mapping);
 // A^_k's zero padding makes the 7 idle columns exact zeros, so they drop out of stores and statistics.
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 // Timing probes of spatial_fwd_x3_kernel (wrong results; tools/build_probe.py only): bit 0 = no output stores, bit 1 = no step-1 MFMAs,
 // bit 2 = no step-2 MFMAs, bit 3 = the weight fragments are loaded once
@@ -83,13 +83,12 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
     const int t0 = blockIdx.x * p.t_chunk;
     const int t1 = min(t0 + p.t_chunk, p.T);
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.wd, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.wd, p.w_bytes);
     // output rows of this workgroup's frames [t0, t1): offsets relative to frame t0 (no tensor-size limit); stores are
     // branch-free buffer stores (absent joints / channels carry the out-of-range offset and are dropped) -- guarded
     // global stores made hipcc drain vmcnt(0), i.e. the next frame's x prefetch, in front of every row store
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.y + ((long long)n * p.T + t0) * V * p.ld_y), 0, (unsigned)((t1 - t0) * V * p.ld_y) * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = buffer_rsrc((p.y + ((long long)n * p.T + t0) * V * p.ld_y), (unsigned)((t1 - t0) * V * p.ld_y) * 4u);
 
     const float* asrc = p.a_hat + (p.a_batched ? (long long)n * NS * V * V : 0);
     for (int i = tid; i < 3 * 32 * 32; i += 256) {
@@ -315,7 +314,6 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
 //   * a workgroup covers 64 output columns (blockIdx.z = column block; agg is re-formed per block -- at 384 cycles per tile
 //     and subset that is cheaper than the registers a wider block would need for two frames).
 // Same accumulator-as-operand chain, weight format (fgcn_pack_split3, acc_order), epilogue and statistics as above.
-constexpr int AHB = 80;    // bytes per [w] row of a split A^ plane (32 joints x bf16 + 16 pad: conflict-free b128 reads)
 
 // NP = 3: three bf16 parts per operand, six products (FGCN_PRODUCTS_BF16X3).  NP = 2: two f16 parts, three products
 // (FGCN_PRODUCTS_F16X2, fgcn_common.hpp) with power-of-two block scales, all of them wave-private because the waves of this kernel are
@@ -339,7 +337,7 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
     const int l31 = lane & 31, h = lane >> 5;
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     if (p.per_xcd > 0) {
-        const int vid = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);
+        const int vid = xcd_tile(blockIdx.x, p.per_xcd);
         if (vid >= p.nchunk * p.B * p.ncol) return;
         bz = vid % p.ncol;
         const int rest = vid / p.ncol;
@@ -351,11 +349,9 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
     const int t0 = bx * p.t_chunk;
     const int t1 = min(t0 + p.t_chunk, p.T);
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const unsigned char*>(p.wd) + (NP == 2 ? 16 : 0)), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.y + ((long long)n * p.T + t0) * V * p.ld_y), 0, (unsigned)((t1 - t0) * V * p.ld_y) * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc((reinterpret_cast<const unsigned char*>(p.wd) + (NP == 2 ? 16 : 0)), p.w_bytes);
+    const __amdgpu_buffer_rsrc_t ry = buffer_rsrc((p.y + ((long long)n * p.T + t0) * V * p.ld_y), (unsigned)((t1 - t0) * V * p.ld_y) * 4u);
 
     const float* asrc = p.a_hat + (p.a_batched ? (long long)n * NS * V * V : 0);
     int eA = 0;                                                       // NP == 2: scale of this sample's A^ images
@@ -674,38 +670,29 @@ static int spatial_t_chunk(int B, int T) {
 extern "C" int fgcn_spatial_tiles(int B, int T) { return (int)(B * cdiv(T, spatial_t_chunk(B, T))); }
 
 template <int CI, int CO>
-static void launch_spatial(const SpatialP& p, hipStream_t s) {
-    const size_t lds = (((3 * 32 * AHS + 3) & ~3) + 4 * 2 * CO * 32 + 4 * 32 * TTS + CO * 32) * sizeof(float);
+static bool launch_spatial(const SpatialP& p, hipStream_t s) {      // returns whether it launched, as dispatch does
+    constexpr size_t lds = (((3 * 32 * AHS + 3) & ~3) + 4 * 2 * CO * 32 + 4 * 32 * TTS + CO * 32) * sizeof(float);
     dim3 grid((unsigned)cdiv(p.T, p.t_chunk), (unsigned)p.B, (unsigned)cdiv(p.Cout, CO * 32));
-    static bool lds_opt_in = false;  // once per instantiation (not a stream operation: keep it out of graph captures)
-    if (!lds_opt_in && lds > 48 * 1024) {  // gfx950 has 160 KiB of LDS per CU; opt in beyond the default dynamic limit
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_fwd_kernel<CI, CO, 0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_fwd_kernel<CI, CO, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_fwd_kernel<CI, CO, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        lds_opt_in = true;
-    }
     const int mm = fgcn::math_mode();
-    if (mm == FGCN_MATH_BF16X3 && p.Cin % 32 == 0)      // (narrower inputs: the exact f32 kernel, f32 pack_k4 weights)
-        hipLaunchKernelGGL((spatial_fwd_kernel<CI, CO, 2>), grid, dim3(256), lds, s, p);
-    else if (mm == FGCN_MATH_BF16)
-        hipLaunchKernelGGL((spatial_fwd_kernel<CI, CO, 1>), grid, dim3(256), lds, s, p);
-    else
-        hipLaunchKernelGGL((spatial_fwd_kernel<CI, CO, 0>), grid, dim3(256), lds, s, p);
+    // (BF16X3 on inputs narrower than 32 channels: the exact f32 kernel, f32 pack_k4 weights)
+    return dispatch(
+        [&](auto MM) {
+            // gfx950 has 160 KiB of LDS per CU; only the forms beyond the default dynamic limit opt in
+            if constexpr (lds > 48 * 1024) launch_lds<spatial_fwd_kernel<CI, CO, MM>>(grid, dim3(256), (int)lds, lds, s, p);
+            else hipLaunchKernelGGL((spatial_fwd_kernel<CI, CO, MM>), grid, dim3(256), lds, s, p);
+            return true;
+        },
+        one_of<0, 1, 2>{mm == FGCN_MATH_BF16X3 && p.Cin % 32 == 0 ? 2 : (mm == FGCN_MATH_BF16 ? 1 : 0)});
 }
 
 template <int CI>
 static int dispatch_out(int co, const SpatialP& p, hipStream_t s) {
     switch (co) {
-        case 1: launch_spatial<CI, 1>(p, s); return 0;
-        case 2: launch_spatial<CI, 2>(p, s); return 0;
-        case 4: launch_spatial<CI, 4>(p, s); return 0;
-        case 8:
-            if (fgcn::math_mode() == FGCN_MATH_BF16X3 && p.Cin % 32 == 0) launch_spatial<CI, 4>(p, s);   // two column blocks
-            else launch_spatial<CI, 8>(p, s);
-            return 0;
+        case 1: return launch_spatial<CI, 1>(p, s) ? 0 : -1;
+        case 2: return launch_spatial<CI, 2>(p, s) ? 0 : -1;
+        case 4: return launch_spatial<CI, 4>(p, s) ? 0 : -1;
+        case 8:      // (bf16x3: two column blocks)
+            return (fgcn::math_mode() == FGCN_MATH_BF16X3 && p.Cin % 32 == 0 ? launch_spatial<CI, 4>(p, s) : launch_spatial<CI, 8>(p, s)) ? 0 : -1;
     }
     return -1;
 }
@@ -728,7 +715,7 @@ extern "C" int fgcn_spatial_fwd(const float* x, const float* a_hat, const float*
     const bool split = fgcn::math_mode() == FGCN_MATH_BF16X3 && Cin % 32 == 0;   // wd: fgcn_pack_split3(acc_order) form
     const long long x_bytes = (long long)B * T * V * ld_x * 4;
     const long long w_bytes = (long long)n_subsets * Cin * Cout * (split ? (fgcn::f16x2_products() ? 4 : 6) : 4);
-    FGCN_REQUIRE(x_bytes < 0x7FFF0000ll, FGCN_E_BADARG, "spatial_fwd: x must be smaller than 2 GiB (32-bit buffer offsets)");
+    FGCN_REQUIRE(fits_buffer(x_bytes), FGCN_E_BADARG, "spatial_fwd: x must be smaller than 2 GiB (32-bit buffer offsets)");
     FGCN_REQUIRE(aligned16(x) || true, FGCN_E_ALIGN, "spatial_fwd: alignment");
     SpatialP p{x, a_hat, wd, bias_sum, y, stat_partials, B, T, V, Cin, Cout, ld_x, ld_y, n_subsets, a_hat_batched,
                spatial_t_chunk(B, T), (unsigned)x_bytes, (unsigned)w_bytes,

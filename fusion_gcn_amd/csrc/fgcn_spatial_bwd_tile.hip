@@ -29,7 +29,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 // Timing probes (wrong results; tools/build_probe.py only): bit 0 = no gram MFMAs, bit 1 = no mix MFMAs, bit 2 = no MFMAs in the
 // contraction steps, bit 3 = x rows / old dx values not requested, bit 4 = the dY rows requested for the first step only,
@@ -69,16 +69,9 @@ struct SpBwdP {
 constexpr int SB_ROWS = 144;            // 128 tile rows + the rows a 32-joint fragment of the last frame reaches past them (V = 16: 143)
 constexpr int SB_XS = 64;               // bytes per image row and part (32 channels x bf16), 32-byte blocks XOR-swizzled by row bit 2
 constexpr int SB_PL = SB_ROWS * SB_XS;  // one plane
-constexpr int SB_AHB = 80;              // bytes per [v] row of a split A^ plane (32 joints w x bf16 + 16 pad)
 constexpr int SB_IM = 3 * SB_PL;        // staging planes [3] first, then the image [3 subsets][3 parts]
 constexpr int SB_AH = SB_IM + 9 * SB_PL;
-constexpr int SB_LDS = SB_AH + 9 * 32 * SB_AHB;   // 133632 bytes
-
-__device__ __forceinline__ u32x2 sb_read_tr16(const unsigned char* p) {
-    using v4s = __attribute__((ext_vector_type(4))) short;
-    const v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
-    return __builtin_bit_cast(u32x2, v);
-}
+constexpr int SB_LDS = SB_AH + 9 * 32 * AHB;   // 133632 bytes
 
 // MAXS: mix units per wave and half (the host's table: two for four to six frames per tile, up to four for seven / eight)
 // NE: gated addends of dx (0 or 2; 2 only without accumulation)
@@ -110,33 +103,21 @@ __global__ __launch_bounds__(512, 1) void spatial_bwd_tile_x3_kernel(SpBwdP p) {
     const int V = p.V, F = p.F, Cin = p.Cin, N3 = 3 * p.Cin;
     const int tile_lo = seg * p.tps, tile_hi = min(tile_lo + p.tps, p.tiles_t);
 
-    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, p.w_plane_bytes * NP, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rdx = __builtin_amdgcn_make_buffer_rsrc((void*)p.dx, 0, p.dx_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rdy = buffer_rsrc(p.dy, p.dy_bytes);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.w3, p.w_plane_bytes * NP);
+    const __amdgpu_buffer_rsrc_t rdx = buffer_rsrc(p.dx, p.dx_bytes);
     __amdgpu_buffer_rsrc_t rge[2], rgm[2];
     const unsigned e0_row = p.e0_grp ? (unsigned)(n / p.e0_grp) * (unsigned)p.Cin : 0u;      // element offset of this sample's group row in e[0]
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        rge[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(NE ? (const void*)p.e[i] : (const void*)p.dx), 0,
-                                                   NE ? ((i == 0 && p.e0_grp) ? p.e0_bytes : p.e_bytes) : 0u, 0x00020000);
-        rgm[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(NE ? (const void*)p.m[i] : (const void*)p.dx), 0, NE ? p.m_bytes : 0u, 0x00020000);
+        rge[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(NE ? (const void*)p.e[i] : (const void*)p.dx), 0,      // (see buffer_rsrc)
+                                                   NE ? ((i == 0 && p.e0_grp) ? p.e0_bytes : p.e_bytes) : 0u, BUFFER_FLAGS);
+        rgm[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(NE ? (const void*)p.m[i] : (const void*)p.dx), 0, NE ? p.m_bytes : 0u, BUFFER_FLAGS);
     }
 
     // A^_k of this sample, split once per workgroup: planes [subset][part][v][w] bf16 (one ds_read_b128 = 8 joints w of row v)
-    const float* asrc = p.a_hat + (p.a_batched ? (long long)n * 3 * V * V : 0);
-    for (int i = tid; i < 3 * 32 * 32; i += 512) {
-        const int k = i >> 10, v = (i >> 5) & 31, w = i & 31;
-        const float a = (v < V && w < V) ? asrc[(k * V + v) * V + w] : 0.f;
-        unsigned ph, pm, pl;
-        split_bf16_pair(a, 0.f, ph, pm, pl);
-        unsigned short* d = reinterpret_cast<unsigned short*>(Ah + ((k * LP) * 32 + v) * SB_AHB) + w;
-        d[0] = (unsigned short)ph;
-        if constexpr (NP == 3) {
-            d[32 * SB_AHB / 2] = (unsigned short)pm;
-            d[2 * 32 * SB_AHB / 2] = (unsigned short)pl;
-        }
-    }
+    stage_adjacency_planes<NP, 512, true>(Ah, p.a_hat + (p.a_batched ? (long long)n * 3 * V * V : 0), V, tid);
     // rows 128 .. 143 of every staging / image plane are never written again: zero them (a fragment of the last frame reads them)
     for (int i = tid; i < 12 * 256; i += 512) {
         const int pl = i >> 8, o = i & 255;
@@ -448,7 +429,7 @@ __global__ __launch_bounds__(512, 1) void spatial_bwd_tile_x3_kernel(SpBwdP p) {
                     for (int vt = 0; vt < 2; ++vt)
 #pragma unroll
                         for (int pl = 0; pl < NP; ++pl)
-                            af[vt][pl] = *reinterpret_cast<const u32x4v*>(Ah + ((k * LP + pl) * 32 + 16 * vt + l15) * SB_AHB + 16 * g4);
+                            af[vt][pl] = *reinterpret_cast<const u32x4v*>(Ah + ((k * LP + pl) * 32 + 16 * vt + l15) * AHB + 16 * g4);
 #pragma unroll
                     for (int s = 0; s < MAXS; ++s) {
                         if (!(sok[s] && sf[s] < nf)) continue;       // wave-uniform
@@ -460,8 +441,8 @@ __global__ __launch_bounds__(512, 1) void spatial_bwd_tile_x3_kernel(SpBwdP p) {
 #pragma unroll
                         for (int pl = 0; pl < NP; ++pl) {
                             const unsigned char* base = Im + (k * LP + pl) * SB_PL;
-                            const u32x2 lo = sb_read_tr16(base + r_lo * SB_XS + (cb ^ swz(r_lo)));
-                            const u32x2 hi = sb_read_tr16(base + r_hi * SB_XS + (cb ^ swz(r_hi)));
+                            const u32x2 lo = lds_read_tr16(base + r_lo * SB_XS + (cb ^ swz(r_lo)));
+                            const u32x2 hi = lds_read_tr16(base + r_hi * SB_XS + (cb ^ swz(r_hi)));
                             df[pl] = u32x4v{lo[0], lo[1], hi[0], hi[1]};
                         }
 #pragma unroll
@@ -533,11 +514,6 @@ extern "C" int fgcn_spatial_bwd_tile_segments(int B, int T, int V) {
     return (int)cdiv(tiles_t, tps);
 }
 
-static int spatial_bwd_tile_launch(const float* dy, const float* x, const float* a_hat, const void* w3, float* dx, float* partial,
-                                   int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched,
-                                   int accumulate, const float* extra1, const unsigned char* mask1, const float* extra2,
-                                   const unsigned char* mask2, int extra1_group, void* stream, int dy16 = 0);
-
 // extra1_group > 0: the first gated addend is given per GROUP of `extra1_group` consecutive samples, extra1 = float[B / extra1_group][Cin]
 // (not accumulating).  half_mask (math mode bf16; strides in elements): bit 0 = dy is a BFLOAT16 tensor (bit-identical to the f32-dy call on
 // the tensor fgcn_bn_act_bwd_apply would have written), bit 1 = x is, bit 2 = dx AND the gated addends are (a per-group extra1 stays float32);
@@ -550,17 +526,9 @@ extern "C" int fgcn_spatial_bwd_tile(const void* dy, const void* x, const float*
                  half_mask);
     FGCN_REQUIRE(extra1_group >= 0 && (extra1_group == 0 || (extra1 && B % extra1_group == 0 && !accumulate)), FGCN_E_BADARG,
                  "spatial_bwd_tile: %d samples are not whole groups of %d", B, extra1_group);
-    return spatial_bwd_tile_launch(static_cast<const float*>(dy), static_cast<const float*>(x), a_hat, w3, static_cast<float*>(dx), partial, B, T, V,
-                                   Cin, Cout, ld_dy, ld_x, ld_dx, a_hat_batched, accumulate, static_cast<const float*>(extra1), mask1,
-                                   static_cast<const float*>(extra2), mask2, extra1_group, stream, half_mask);      // dy16 = half_mask
-}
-
-static int spatial_bwd_tile_launch(const float* dy, const float* x, const float* a_hat, const void* w3, float* dx, float* partial,
-                                   int B, int T, int V, int Cin, int Cout, int ld_dy, int ld_x, int ld_dx, int a_hat_batched,
-                                   int accumulate, const float* extra1, const unsigned char* mask1, const float* extra2,
-                                   const unsigned char* mask2, int extra1_group, void* stream, int dy16) {      // dy16: the entry point's half_mask (0, 1, 3, 7)
+    const bool dy16 = half_mask & 1, x16 = half_mask & 2, dx16 = half_mask & 4;
     const bool gated = extra1 != nullptr;
-    FGCN_REQUIRE(!dy16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_bwd_tile: a bfloat16 dy needs math mode bf16");
+    FGCN_REQUIRE(!half_mask || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_bwd_tile: a bfloat16 dy needs math mode bf16");
     FGCN_REQUIRE(!gated || (mask1 && extra2 && mask2 && !accumulate && ld_x == Cin && Cin % 8 == 0), FGCN_E_BADARG,
                  "spatial_bwd_tile: gated addends come in pairs with their sign images, without accumulation, on contiguous (B, T, V, Cin) tensors");
     FGCN_REQUIRE(!gated || (aligned16(extra1) && aligned16(extra2)), FGCN_E_ALIGN, "spatial_bwd_tile: 16-byte aligned addends");
@@ -573,13 +541,13 @@ static int spatial_bwd_tile_launch(const float* dy, const float* x, const float*
                  "spatial_bwd_tile: row strides");
     FGCN_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(w3) && aligned16(dx), FGCN_E_ALIGN, "spatial_bwd_tile: 16-byte alignment");
     const long long rows = (long long)B * T * V;
-    const int abytes = (dy16 & 4) ? 2 : 4;
-    const long long dy_bytes = rows * ld_dy * (dy16 ? 2 : 4), x_bytes = rows * ld_x * ((dy16 & 2) ? 2 : 4), dx_bytes = rows * ld_dx * abytes;
+    const int abytes = dx16 ? 2 : 4;
+    const long long dy_bytes = rows * ld_dy * (dy16 ? 2 : 4), x_bytes = rows * ld_x * (x16 ? 2 : 4), dx_bytes = rows * ld_dx * abytes;
     const long long plane = (long long)3 * Cin * Cout * 2;
-    FGCN_REQUIRE(dy_bytes < 0x7FFF0000ll && x_bytes < 0x7FFF0000ll && dx_bytes < 0x7FFF0000ll && plane * 3 < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(dy_bytes) && fits_buffer(x_bytes) && fits_buffer(dx_bytes) && fits_buffer(plane * 3), FGCN_E_BADARG,
                  "spatial_bwd_tile: tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     SpBwdP p;
-    p.dy = dy; p.x = x; p.a_hat = a_hat; p.w3 = w3; p.dx = dx; p.partial = partial;
+    p.dy = static_cast<const float*>(dy); p.x = static_cast<const float*>(x); p.a_hat = a_hat; p.w3 = w3; p.dx = static_cast<float*>(dx); p.partial = partial;
     p.B = B; p.T = T; p.V = V; p.Cin = Cin; p.Cout = Cout; p.ld_dy = ld_dy; p.ld_x = ld_x; p.ld_dx = ld_dx; p.a_batched = a_hat_batched;
     p.F = 128 / V;
     p.tiles_t = (int)cdiv(T, p.F);
@@ -587,7 +555,7 @@ static int spatial_bwd_tile_launch(const float* dy, const float* x, const float*
     p.tps = (int)cdiv(p.tiles_t, p.nseg);
     FGCN_REQUIRE((long long)B * p.nseg < (1ll << 30), FGCN_E_BADARG, "spatial_bwd_tile: too many workgroups");
     p.dy_bytes = (unsigned)dy_bytes; p.x_bytes = (unsigned)x_bytes; p.dx_bytes = (unsigned)dx_bytes; p.w_plane_bytes = (unsigned)plane;
-    p.e[0] = extra1; p.e[1] = extra2; p.m[0] = mask1; p.m[1] = mask2; p.e_bytes = (unsigned)(rows * Cin * abytes);
+    p.e[0] = static_cast<const float*>(extra1); p.e[1] = static_cast<const float*>(extra2); p.m[0] = mask1; p.m[1] = mask2; p.e_bytes = (unsigned)(rows * Cin * abytes);
     p.m_bytes = (unsigned)(rows * Cin / 8);
     p.e0_grp = extra1_group;
     p.e0_bytes = extra1_group ? (unsigned)((long long)(B / extra1_group) * Cin * 4) : 0u;
@@ -611,49 +579,22 @@ static int spatial_bwd_tile_launch(const float* dy, const float* x, const float*
         }
     }
     const dim3 grid((unsigned)(B * p.nseg));
-    hipStream_t s = (hipStream_t)stream;
-    const bool one_part = fgcn::math_mode() == FGCN_MATH_BF16;     // operands rounded to bfloat16 once
-#define FGCN_SB_GO4(ACC_, MS_, NE_, NP_, I16_)                                                                         \
-    do {                                                                                                                \
-        static bool opted = false;   /* once per instantiation; not a stream operation (stays out of graph captures) */ \
-        if (!opted) {                                                                                                   \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_bwd_tile_x3_kernel<ACC_, MS_, NE_, NP_, I16_>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_LDS);                         \
-            opted = true;                                                                                               \
-        }                                                                                                               \
-        hipLaunchKernelGGL((spatial_bwd_tile_x3_kernel<ACC_, MS_, NE_, NP_, I16_>), grid, dim3(512), SB_LDS, s, p);     \
-    } while (0)
-#define FGCN_SB_GO3(ACC_, MS_, NE_)                                                                                    \
-    do {                                                                                                                \
-        if (one_part && dy16 == 7) FGCN_SB_GO4(ACC_, MS_, NE_, 1, 7);                                                   \
-        else if (one_part && dy16 == 3) FGCN_SB_GO4(ACC_, MS_, NE_, 1, 3);                                              \
-        else if (one_part && dy16) FGCN_SB_GO4(ACC_, MS_, NE_, 1, 1);                                                   \
-        else if (one_part) FGCN_SB_GO4(ACC_, MS_, NE_, 1, 0);                                                           \
-        else FGCN_SB_GO4(ACC_, MS_, NE_, 3, 0);                                                                         \
-    } while (0)
-#define FGCN_SB_GO(ACC_, MS_)                                                                                          \
-    do {                                                                                                                \
-        if (gated) FGCN_SB_GO3(false, MS_, 2);                                                                          \
-        else FGCN_SB_GO3(ACC_, MS_, 0);                                                                                 \
-    } while (0)
     int max_units = 0;
     for (int w = 0; w < 8; ++w) {
         int c = 0;
         for (int u = 0; u < 2 * p.F; ++u) c += p.mix_wave[u] == w ? 1 : 0;
         max_units = std::max(max_units, c);
     }
-    if (max_units <= 2) {
-        if (accumulate) FGCN_SB_GO(true, 2);
-        else FGCN_SB_GO(false, 2);
-    } else if (max_units <= 3) {
-        if (accumulate) FGCN_SB_GO(true, 3);
-        else FGCN_SB_GO(false, 3);
-    } else {
-        if (accumulate) FGCN_SB_GO(true, 4);
-        else FGCN_SB_GO(false, 4);
-    }
-#undef FGCN_SB_GO
-#undef FGCN_SB_GO3
-#undef FGCN_SB_GO4
+    // ACC: dx is added to; NE: gated addends (never with accumulation); one bf16 part: operands rounded to bfloat16 once, and only that
+    // kernel takes bfloat16 tensors (IN16 = half_mask)
+    const bool built = dispatch(
+        [&](auto ACC, auto MS, auto NE, auto NP, auto IN16) {
+            constexpr bool built = (ACC == 0 || NE == 0) && (NP == 1 || IN16 == 0);
+            if constexpr (built) launch_lds<spatial_bwd_tile_x3_kernel<ACC == 1, MS, NE, NP, IN16>>(grid, dim3(512), (int)SB_LDS, SB_LDS, (hipStream_t)stream, p);
+            return built;
+        },
+        one_of<0, 1>{accumulate && !gated}, one_of<2, 3, 4>{max_units <= 2 ? 2 : (max_units <= 3 ? 3 : 4)}, one_of<0, 2>{gated ? 2 : 0},
+        one_of<1, 3>{fgcn::math_mode() == FGCN_MATH_BF16 ? 1 : 3}, one_of<0, 1, 3, 7>{half_mask});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "spatial_bwd_tile: no such kernel form (half_mask=%d)", half_mask);
     return launch_status("spatial_bwd_tile");
 }

@@ -19,7 +19,7 @@
 //   aggregation units of a chunk = (pair, frame): 2 F units, dealt round-robin to the four waves; a unit is 2 x 6 MFMAs
 //   (v_mfma_f32_32x32x16_bf16: agg^T (32 c x 32 w) = X_t^T . A^_k), its x rows are requested one chunk ahead and parked in registers.
 // Rows of the image beyond the tile's F V rows are never written and never stored (each output row depends on its own image row only).
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 // Timing probes (wrong results; tools/build_probe.py only): bit 0 = the image is staged for the first chunk only, bit 1 = no feature
 // MFMAs, bit 2 = x is fetched for the first chunk only, bit 3 = no aggregation MFMAs / splits (the image receives x's split instead)
@@ -52,7 +52,6 @@ struct SpTileP {
     unsigned res_bytes;
 };
 
-constexpr int ST_AHB = 80;              // bytes per [w] row of a split A^ plane (32 joints x bf16 + 16 pad: conflict-free b128 reads)
 constexpr int ST_XS = 64;               // bytes per image row and part (32 channels x bf16), 32-byte blocks XOR-swizzled by row bit 2
 constexpr int ST_PLANE = 256 * ST_XS;   // one part of the image: two pairs x 128 rows
 
@@ -72,13 +71,13 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
     auto swz = [](int r) -> unsigned { return (unsigned)(r & 4) << 3; };
     extern __shared__ __attribute__((aligned(16))) float smem_st[];
     unsigned char* Xh = reinterpret_cast<unsigned char*>(smem_st);   // [3 parts][2 pairs x 128 rows][64 B]
-    unsigned char* ahs = Xh + LP * ST_PLANE;                         // [3 subsets][3 parts][32 w][ST_AHB]
+    unsigned char* ahs = Xh + LP * ST_PLANE;                         // [3 subsets][3 parts][32 w][AHB]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g4 = lane >> 4, l31 = lane & 31, h = lane >> 5;
     const int wr = wave >> 1, wc = wave & 1;
     // XCD-aware order, column tile fastest: the column tiles of a row tile (same x rows, same A^) run back to back on one XCD
-    const int vid = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);
+    const int vid = xcd_tile(blockIdx.x, p.per_xcd);
     if (vid >= p.tiles_m * p.tiles_n) return;
     const int bm = vid / p.tiles_n, bn = vid - bm * p.tiles_n;
     const int n = bm / p.tiles_t, tf = bm - n * p.tiles_t;
@@ -88,8 +87,8 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
     const int nrows = nf * V;
     const int n0 = bn * BN;
 
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, p.w_plane_bytes * NP, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.w3, p.w_plane_bytes * NP);
 
     // A^_k of this sample, split once per workgroup: [subset][part][w][v] bf16 (one ds_read_b128 = the 8 joints of a lane's fragment).
     // All twelve requests of a thread are in flight at once (branch-free buffer loads; absent joints carry the out-of-range offset): as a
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
     // the embedding-backward kernel 22 % of its time, profiles/r05_kbench_emb_bwd_variants.txt).
     {
         const float* asrc = p.a_hat + (p.a_batched ? (long long)n * 3 * V * V : 0);
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)asrc, 0, (unsigned)(3 * V * V) * 4u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(asrc, (unsigned)(3 * V * V) * 4u);
         float av[12];
 #pragma unroll
         for (int e = 0; e < 12; ++e) {
@@ -109,14 +108,7 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
         for (int e = 0; e < 12; ++e) {
             const int i = tid + 256 * e;
             const int k = e >> 2, w = (i >> 5) & 31, v = i & 31;
-            unsigned ph, pm, pl;
-            split_bf16_pair(av[e], 0.f, ph, pm, pl);
-            unsigned short* d = reinterpret_cast<unsigned short*>(ahs + ((k * LP) * 32 + w) * ST_AHB) + v;
-            d[0] = (unsigned short)ph;
-            if constexpr (NP == 3) {
-                d[32 * ST_AHB / 2] = (unsigned short)pm;
-                d[2 * 32 * ST_AHB / 2] = (unsigned short)pl;
-            }
+            put_split<NP>(ahs, k, w, v, av[e]);
         }
     }
 
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
             }
         }
     };
-    const unsigned char* af_lane = ahs + l31 * ST_AHB + 16 * h;      // + (k * NP + part) * 32 * ST_AHB + 32 * s2
+    const unsigned char* af_lane = ahs + l31 * AHB + 16 * h;      // + (k * NP + part) * 32 * AHB + 32 * s2
     auto stage_units = [&](int c, float (&xr)[MAXU][16]) {
         const bool same_ci = (2 * c + 1) % 3 != 0;
         u32x4v xs[2][NP];                                            // the split x rows of the current frame (kept across a shared pair)
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
                 u32x4v af[NP];
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl)
-                    af[pl] = *reinterpret_cast<const u32x4v*>(af_lane + (k * LP + pl) * 32 * ST_AHB + 32 * s2);
+                    af[pl] = *reinterpret_cast<const u32x4v*>(af_lane + (k * LP + pl) * 32 * AHB + 32 * s2);
                 agg = mfma_np_k16<NP>(xs[s2], af, agg);                  // agg^T (32 c x 32 w): lane = joint w, register r = channel acc_row(r)
             }
             // this lane's joint w = l31 of frame uf: image row uq * 128 + uf * V + w, channels 8 g + 4 h + (0..3) per register group
@@ -263,9 +255,8 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
 
     // ---- epilogue: bias, branch-free buffer stores, BatchNorm partial sums (accumulator register r of lane (col l15, g4) = row
     // 4 g4 + r of its 16 x 16 tile); rows beyond the tile's frames carry the out-of-range offset ----------------------------------
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void*)(p.bias ? (const void*)p.bias : p.w3), 0,
-                                                                           p.bias ? (unsigned)p.Cout * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc((p.bias ? (const void*)p.bias : p.w3), p.bias ? (unsigned)p.Cout * 4u : 0u);
     const long long m0 = ((long long)n * p.T + t0) * V;
     float ssum[NU], ssq[NU], bv[NU];
     unsigned coff[NU];
@@ -284,11 +275,9 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
     if constexpr (FEP) {
         // G = relu((acc + bias) * scale + shift + res * rscale + rshift): per-column constants first, the shortcut values of a row tile
         // requested one row tile ahead of its stores (two register sets)
-        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)p.ep_vec, 0, (unsigned)p.Cout * 16u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rrv = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ep_rvec ? p.ep_rvec : p.ep_vec), 0,
-                                                                             p.ep_rvec ? (unsigned)p.Cout * 16u : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ep_res ? (const void*)p.ep_res : (const void*)p.y), 0,
-                                                                              p.ep_res ? p.res_bytes : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rv = buffer_rsrc(p.ep_vec, (unsigned)p.Cout * 16u);
+        const __amdgpu_buffer_rsrc_t rrv = buffer_rsrc((p.ep_rvec ? p.ep_rvec : p.ep_vec), p.ep_rvec ? (unsigned)p.Cout * 16u : 0u);
+        const __amdgpu_buffer_rsrc_t rres = buffer_rsrc((p.ep_res ? (const void*)p.ep_res : (const void*)p.y), p.ep_res ? p.res_bytes : 0u);
         float esc[NU], esh[NU], rsc[NU], rsh[NU];
         const float res_unit = p.ep_rvec ? 0.f : 1.f;
 #pragma unroll
@@ -410,37 +399,14 @@ extern "C" int fgcn_spatial_fwd_tile_tiles(int B, int T, int V) {
     return V >= 16 && V <= FGCN_MAX_V ? (int)(B * cdiv(T, sp_tile_frames(V))) : 0;
 }
 
+// the body of fgcn_spatial_fwd_tile and fgcn_spatial_fwd_tile_bn_relu (ep_vec: the inference output stage)
 static int spatial_fwd_tile_impl(const float* x, const float* a_hat, const void* w3, const float* bias_sum, float* y,
                                  float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
-                                 int a_hat_batched, void* stream, const float* ep_vec, const float* ep_res, int ld_res, const float* ep_rvec, int io = 0);
-
-// half_mask (math mode bf16, half-precision activation storage): bit 0 = x is a bfloat16 tensor, bit 1 = y is (masks 0, 2, 3);
-// ld_x / ld_y in elements; stat_partials: the moments of the float32 accumulators
-extern "C" int fgcn_spatial_fwd_tile(const void* x, const float* a_hat, const void* w3, const float* bias_sum, void* y,
-                                     float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
-                                     int a_hat_batched, int half_mask, void* stream) {
-    FGCN_REQUIRE(half_mask == 0 || half_mask == 2 || half_mask == 3, FGCN_E_BADARG, "spatial_fwd_tile: half_mask=%d (0, 2 or 3)", half_mask);
-    return spatial_fwd_tile_impl(static_cast<const float*>(x), a_hat, w3, bias_sum, static_cast<float*>(y), stat_partials, B, T, V, Cin, Cout, ld_x,
-                                 ld_y, a_hat_batched, stream, nullptr, nullptr, 0, nullptr, half_mask);      // io = half_mask: bit 0 x, bit 1 y
-}
-
-// Inference form of north-star kernel 1: aggregation + 1x1 feature contraction + (eval-mode) BatchNorm + shortcut + ReLU in ONE kernel --
-// g = relu(BN(sum_k conv_d[k](x . A^_k)) + shortcut), agcn.py:103-115 with the BatchNorm's running statistics folded into a per-channel
-// scale / shift (bn_vec = fgcn_bn_eval_coeffs).  res: the shortcut operand (x for an identity block, the down conv's output with its own
-// res_vec) or NULL; rows of ld_res floats.  No pre-BatchNorm tensor is written and nothing is kept for a backward.
-extern "C" int fgcn_spatial_fwd_tile_bn_relu(const float* x, const float* a_hat, const void* w3, const float* bias_sum, float* g,
-                                             const float* bn_vec, const float* res, int ld_res, const float* res_vec,
-                                             int B, int T, int V, int Cin, int Cout, int ld_x, int ld_g, int a_hat_batched, void* stream) {
-    FGCN_REQUIRE(bn_vec && aligned16(bn_vec) && (!res || (ld_res >= Cout && ld_res % 4 == 0)) && (!res_vec || res), FGCN_E_BADARG,
-                 "spatial_fwd_tile_bn_relu: the BatchNorm vector is required; a shortcut needs ld_res >= Cout, its BatchNorm needs the shortcut");
-    return spatial_fwd_tile_impl(x, a_hat, w3, bias_sum, g, nullptr, B, T, V, Cin, Cout, ld_x, ld_g, a_hat_batched, stream, bn_vec, res, ld_res, res_vec);
-}
-
-static int spatial_fwd_tile_impl(const float* x, const float* a_hat, const void* w3, const float* bias_sum, float* y,
-                                 float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
-                                 int a_hat_batched, void* stream, const float* ep_vec, const float* ep_res, int ld_res, const float* ep_rvec, int io) {
+                                 int a_hat_batched, void* stream, const float* ep_vec, const float* ep_res, int ld_res, const float* ep_rvec,
+                                 int half_mask) {
+    const bool x16 = half_mask & 1, y16 = half_mask & 2;
     FGCN_REQUIRE(x && a_hat && w3 && y, FGCN_E_BADARG, "spatial_fwd_tile: null pointer");
-    FGCN_REQUIRE(io == 0 || ((io == 2 || io == 3) && fgcn::math_mode() == FGCN_MATH_BF16 && !ep_vec), FGCN_E_BADARG,
+    FGCN_REQUIRE(half_mask == 0 || ((half_mask == 2 || half_mask == 3) && fgcn::math_mode() == FGCN_MATH_BF16 && !ep_vec), FGCN_E_BADARG,
                  "spatial_fwd_tile: bfloat16 tensors (half_mask 2 or 3) need math mode bf16 and the training form");
     FGCN_REQUIRE(B > 0 && T > 0 && Cin > 0 && Cout > 0, FGCN_E_BADARG, "spatial_fwd_tile: bad sizes B=%d T=%d Cin=%d Cout=%d", B, T, Cin, Cout);
     FGCN_REQUIRE(fgcn_spatial_fwd_tile_available(V, Cin, Cout), FGCN_E_BADARG,
@@ -448,9 +414,9 @@ static int spatial_fwd_tile_impl(const float* x, const float* a_hat, const void*
                  FGCN_MAX_V, V, Cin, Cout);
     FGCN_REQUIRE(ld_x % 4 == 0 && ld_y % 4 == 0 && ld_x >= Cin && ld_y >= Cout, FGCN_E_ALIGN, "spatial_fwd_tile: row strides");
     FGCN_REQUIRE(aligned16(x) && aligned16(w3) && aligned16(y), FGCN_E_ALIGN, "spatial_fwd_tile: 16-byte alignment");
-    const long long x_bytes = (long long)B * T * V * ld_x * ((io & 1) ? 2 : 4), y_bytes = (long long)B * T * V * ld_y * ((io & 2) ? 2 : 4);
+    const long long x_bytes = (long long)B * T * V * ld_x * (x16 ? 2 : 4), y_bytes = (long long)B * T * V * ld_y * (y16 ? 2 : 4);
     const long long plane = (long long)3 * Cin * Cout * 2;
-    FGCN_REQUIRE(x_bytes < 0x7FFF0000ll && y_bytes < 0x7FFF0000ll && plane * 3 < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(x_bytes) && fits_buffer(y_bytes) && fits_buffer(plane * 3), FGCN_E_BADARG,
                  "spatial_fwd_tile: tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     SpTileP p;
     p.x = x; p.a_hat = a_hat; p.w3 = w3; p.bias = bias_sum; p.y = y; p.stats = stat_partials;
@@ -466,58 +432,44 @@ static int spatial_fwd_tile_impl(const float* x, const float* a_hat, const void*
     p.x_bytes = (unsigned)x_bytes; p.y_bytes = (unsigned)y_bytes; p.w_plane_bytes = (unsigned)plane;
     const bool fep = ep_vec != nullptr;
     const long long res_bytes = ep_res ? (long long)B * T * V * ld_res * 4 : 0;
-    FGCN_REQUIRE(res_bytes < 0x7FFF0000ll, FGCN_E_BADARG, "spatial_fwd_tile: the shortcut tensor must be smaller than 2 GiB");
+    FGCN_REQUIRE(fits_buffer(res_bytes), FGCN_E_BADARG, "spatial_fwd_tile: the shortcut tensor must be smaller than 2 GiB");
     p.ep_vec = ep_vec; p.ep_res = ep_res; p.ep_rvec = ep_rvec; p.ld_res = ld_res; p.res_bytes = (unsigned)res_bytes;
-    const size_t lds = (size_t)3 * ST_PLANE + 9 * 32 * ST_AHB;
+    constexpr size_t lds = (size_t)3 * ST_PLANE + 9 * 32 * AHB;
     const dim3 grid((unsigned)(p.per_xcd * 8));
     hipStream_t s = (hipStream_t)stream;
     const bool four = 2 * p.F > 12;                                  // aggregation units per wave and chunk: ceil(2 F / 4)
-    const bool str = !(io & 2) ? fgcn::stream_out(y_bytes) : ((fgcn::tuning(25) & 2) && fgcn::stream_out(y_bytes));   // (a bfloat16 y: 32-byte pieces, stored plainly; key 25 bit 1: streamed)
-#define FGCN_ST_GO6(NT_, MU_, STR_, NP_, FEP_, IO_)                                                                 \
-    do {                                                                                                            \
-        static bool opted = false;   /* once per instantiation; not a stream operation (stays out of graph captures) */ \
-        if (!opted) {                                                                                               \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_tile_x3_kernel<NT_, MU_, STR_, NP_, FEP_, IO_>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
-            opted = true;                                                                                           \
-        }                                                                                                           \
-        hipLaunchKernelGGL((spatial_tile_x3_kernel<NT_, MU_, STR_, NP_, FEP_, IO_>), grid, dim3(256), lds, s, p);   \
-    } while (0)
-#define FGCN_ST_GO5(NT_, MU_, STR_, NP_, FEP_)                                                                      \
-    do {                                                                                                            \
-        if constexpr (NP_ == 1 && !FEP_) {                                                                          \
-            if (io == 3) { FGCN_ST_GO6(NT_, MU_, STR_, 1, false, 3); break; }                                       \
-            if (io == 2) { FGCN_ST_GO6(NT_, MU_, STR_, 1, false, 2); break; }                                       \
-        }                                                                                                           \
-        FGCN_ST_GO6(NT_, MU_, STR_, NP_, FEP_, 0);                                                                  \
-    } while (0)
-#define FGCN_ST_GO4(NT_, MU_, STR_, NP_)                \
-    do {                                                \
-        if (fep) FGCN_ST_GO5(NT_, MU_, STR_, NP_, true); \
-        else FGCN_ST_GO5(NT_, MU_, STR_, NP_, false);   \
-    } while (0)
-    const bool one_part = fgcn::math_mode() == FGCN_MATH_BF16;     // operands rounded to bfloat16 once
-#define FGCN_ST_GO3(NT_, MU_, STR_)                     \
-    do {                                                \
-        if (one_part) FGCN_ST_GO4(NT_, MU_, STR_, 1);   \
-        else FGCN_ST_GO4(NT_, MU_, STR_, 3);            \
-    } while (0)
-#define FGCN_ST_GO(NT_, MU_)                                                                                        \
-    do {                                                                                                            \
-        if (str) FGCN_ST_GO3(NT_, MU_, true);                                                                       \
-        else FGCN_ST_GO3(NT_, MU_, false);                                                                          \
-    } while (0)
-    if (narrow) {
-        if (four) FGCN_ST_GO(1, 4);
-        else FGCN_ST_GO(1, 3);
-    } else {
-        if (four) FGCN_ST_GO(2, 4);
-        else FGCN_ST_GO(2, 3);
-    }
-#undef FGCN_ST_GO
-#undef FGCN_ST_GO3
-#undef FGCN_ST_GO4
-#undef FGCN_ST_GO5
-#undef FGCN_ST_GO6
+    const bool str = !y16 ? fgcn::stream_out(y_bytes) : ((fgcn::tuning(25) & 2) && fgcn::stream_out(y_bytes));   // (a bfloat16 y: 32-byte pieces, stored plainly; key 25 bit 1: streamed)
+    // one bf16 part: operands rounded to bfloat16 once; only that kernel's training form takes bfloat16 tensors (IO = half_mask)
+    const bool built = dispatch(
+        [&](auto NT, auto MU, auto STR, auto NP, auto FEP, auto IO) {
+            constexpr bool built = IO == 0 || (NP == 1 && FEP == 0);
+            if constexpr (built) launch_lds<spatial_tile_x3_kernel<NT, MU, STR == 1, NP, FEP == 1, IO>>(grid, dim3(256), (int)lds, lds, s, p);
+            return built;
+        },
+        one_of<1, 2>{narrow ? 1 : 2}, one_of<3, 4>{four ? 4 : 3}, one_of<0, 1>{str}, one_of<1, 3>{fgcn::math_mode() == FGCN_MATH_BF16 ? 1 : 3},
+        one_of<0, 1>{fep}, one_of<0, 2, 3>{half_mask});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "spatial_fwd_tile: no such kernel form (half_mask=%d)", half_mask);
     return launch_status("spatial_fwd_tile");
+}
+
+// half_mask (math mode bf16, half-precision activation storage): bit 0 = x is a bfloat16 tensor, bit 1 = y is (masks 0, 2, 3);
+// ld_x / ld_y in elements; stat_partials: the moments of the float32 accumulators
+extern "C" int fgcn_spatial_fwd_tile(const void* x, const float* a_hat, const void* w3, const float* bias_sum, void* y,
+                                     float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
+                                     int a_hat_batched, int half_mask, void* stream) {
+    FGCN_REQUIRE(half_mask == 0 || half_mask == 2 || half_mask == 3, FGCN_E_BADARG, "spatial_fwd_tile: half_mask=%d (0, 2 or 3)", half_mask);
+    return spatial_fwd_tile_impl(static_cast<const float*>(x), a_hat, w3, bias_sum, static_cast<float*>(y), stat_partials, B, T, V, Cin, Cout, ld_x,
+                                 ld_y, a_hat_batched, stream, nullptr, nullptr, 0, nullptr, half_mask);
+}
+
+// Inference form of north-star kernel 1: aggregation + 1x1 feature contraction + (eval-mode) BatchNorm + shortcut + ReLU in ONE kernel --
+// g = relu(BN(sum_k conv_d[k](x . A^_k)) + shortcut), agcn.py:103-115 with the BatchNorm's running statistics folded into a per-channel
+// scale / shift (bn_vec = fgcn_bn_eval_coeffs).  res: the shortcut operand (x for an identity block, the down conv's output with its own
+// res_vec) or NULL; rows of ld_res floats.  No pre-BatchNorm tensor is written and nothing is kept for a backward.
+extern "C" int fgcn_spatial_fwd_tile_bn_relu(const float* x, const float* a_hat, const void* w3, const float* bias_sum, float* g,
+                                             const float* bn_vec, const float* res, int ld_res, const float* res_vec,
+                                             int B, int T, int V, int Cin, int Cout, int ld_x, int ld_g, int a_hat_batched, void* stream) {
+    FGCN_REQUIRE(bn_vec && aligned16(bn_vec) && (!res || (ld_res >= Cout && ld_res % 4 == 0)) && (!res_vec || res), FGCN_E_BADARG,
+                 "spatial_fwd_tile_bn_relu: the BatchNorm vector is required; a shortcut needs ld_res >= Cout, its BatchNorm needs the shortcut");
+    return spatial_fwd_tile_impl(x, a_hat, w3, bias_sum, g, nullptr, B, T, V, Cin, Cout, ld_x, ld_g, a_hat_batched, stream, bn_vec, res, ld_res, res_vec, 0);
 }

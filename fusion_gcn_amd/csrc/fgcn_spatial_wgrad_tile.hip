@@ -25,7 +25,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 // Timing probes (wrong results; tools/build_probe.py only): bit 0 = no contraction MFMAs, bit 1 = no mixing MFMAs, bit 2 = x values requested
 // for the first slot only, bit 3 = dY rows requested for the first tile only, bit 4 = no deposit of the dY tile (first tile only),
@@ -51,22 +51,10 @@ struct SwTileP {
 };
 
 constexpr int SWT_ROWS = 160;           // rows of a dY plane: (F - 1) V + 32 <= 160
-constexpr int SWT_AHB = 80;             // bytes per [w] row of a split A^ plane (32 joints v x bf16 + 16 pad)
 // row stride of a dY plane: the channels' bytes + 32 -- eight consecutive rows then start 32 bytes apart modulo 256, which is what a
 // transposing read's half wave touches (8 rows x 32 bytes)
 template <int NT> constexpr int swt_rs() { return NT * 32 + 32; }
-template <int NT> constexpr int swt_lds() { return 3 * SWT_ROWS * swt_rs<NT>() + 9 * 32 * SWT_AHB; }
-
-__device__ __forceinline__ u32x2 swt_read_tr16(const unsigned char* p) {
-    using v4s = __attribute__((ext_vector_type(4))) short;
-    const v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
-    return __builtin_bit_cast(u32x2, v);
-}
-
-template <class Fn, int... S>
-__device__ __forceinline__ void swt_for_slots(Fn&& fn, std::integer_sequence<int, S...>) {
-    (fn(std::integral_constant<int, S>{}), ...);
-}
+template <int NT> constexpr int swt_lds() { return 3 * SWT_ROWS * swt_rs<NT>() + 9 * 32 * AHB; }
 
 // CT: 16-channel input tiles of the workgroup (8: every wave walks all frames; 4: two waves per tile take alternate frames and their
 // accumulators are added at the end); NT: 16-channel output tiles (4 or 8); NSLOT: frame slots of a wave per tile (ceil(F / FP) rounded up to
@@ -104,8 +92,8 @@ __global__ __launch_bounds__(512, 1) void spatial_wgrad_tile_x3_kernel(SwTileP p
     const int V = p.V, F = p.F;
     const int g_lo = seg * p.tps, g_hi = min(g_lo + p.tps, p.gtiles);
 
-    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rdy = buffer_rsrc(p.dy, p.dy_bytes);
+    const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(p.x, p.x_bytes);
 
     f32x4 acc[3][NT];
 #pragma unroll
@@ -149,19 +137,7 @@ __global__ __launch_bounds__(512, 1) void spatial_wgrad_tile_x3_kernel(SwTileP p
     // the A^ planes of sample n -> LDS (between two barriers): A^_k split once, planes [subset][part][w][v] bf16 (one ds_read_b128 = the 8
     // joints v of a lane's fragment)
     auto planes = [&](int n) {
-        const float* asrc = p.a_hat + (p.a_batched ? (long long)n * 3 * V * V : 0);
-        for (int i = tid; i < 3 * 32 * 32; i += 512) {
-            const int k = i >> 10, w = (i >> 5) & 31, v = i & 31;
-            const float a = (v < V && w < V) ? asrc[(k * V + v) * V + w] : 0.f;
-            unsigned ph, pm, pl;
-            split_bf16_pair(a, 0.f, ph, pm, pl);
-            unsigned short* d = reinterpret_cast<unsigned short*>(Ah + ((k * LP) * 32 + w) * SWT_AHB) + v;
-            d[0] = (unsigned short)ph;
-            if constexpr (NP == 3) {
-                d[32 * SWT_AHB / 2] = (unsigned short)pm;
-                d[2 * 32 * SWT_AHB / 2] = (unsigned short)pl;
-            }
-        }
+        stage_adjacency_planes<NP, 512, false>(Ah, p.a_hat + (p.a_batched ? (long long)n * 3 * V * V : 0), V, tid);
     };
     auto deposit = [&]() {
 #pragma unroll
@@ -215,7 +191,7 @@ __global__ __launch_bounds__(512, 1) void spatial_wgrad_tile_x3_kernel(SwTileP p
                     u32x4v af[NP];
 #pragma unroll
                     for (int pl = 0; pl < NP; ++pl)
-                        af[pl] = *reinterpret_cast<const u32x4v*>(Ah + ((k * LP + pl) * 32 + 16 * wt + l15) * SWT_AHB + 16 * g4);
+                        af[pl] = *reinterpret_cast<const u32x4v*>(Ah + ((k * LP + pl) * 32 + 16 * wt + l15) * AHB + 16 * g4);
                     if constexpr ((FGCN_PROBE_SW & 2) != 0) m[wt] = __builtin_bit_cast(f32x4, af[0] ^ xs[0] ^ af[NP - 1] ^ xs[NP - 1]);
                     else m[wt] = mfma_np_k32<NP>(af, xs, f32x4{0.f, 0.f, 0.f, 0.f});
                 }
@@ -233,8 +209,8 @@ __global__ __launch_bounds__(512, 1) void spatial_wgrad_tile_x3_kernel(SwTileP p
                 for (int pl = 0; pl < NP; ++pl) {
                     if ((FGCN_PROBE_SW & 32) && nt > 0) break;
                     const unsigned char* base = Im + pl * PL + nt * 32 + 8 * c4;
-                    const u32x2 lo = swt_read_tr16(base + r_lo * RS);
-                    const u32x2 hi = swt_read_tr16(base + r_hi * RS);
+                    const u32x2 lo = lds_read_tr16(base + r_lo * RS);
+                    const u32x2 hi = lds_read_tr16(base + r_hi * RS);
                     df[pl] = u32x4v{lo[0], lo[1], hi[0], hi[1]};
                 }
 #pragma unroll
@@ -244,7 +220,7 @@ __global__ __launch_bounds__(512, 1) void spatial_wgrad_tile_x3_kernel(SwTileP p
                 }
             }
         };
-        swt_for_slots(slot, std::make_integer_sequence<int, NSLOT>{});
+        for_slots(slot, std::make_integer_sequence<int, NSLOT>{});
         // the next tile's dY rows (and its sample's A^ planes) replace this one's
         __syncthreads();                                             // this tile's fragment reads are done
         const int n1 = (g + 1) / p.tiles_t;
@@ -254,7 +230,7 @@ __global__ __launch_bounds__(512, 1) void spatial_wgrad_tile_x3_kernel(SwTileP p
     }
 
     // ---- the workgroup's slab: partial[seg][k Cin + c][o] -------------------------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)p.partial, 0, p.p_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = buffer_rsrc(p.partial, p.p_bytes);
     if constexpr (FP == 2) {                                         // fixed order: frames of the even slots + frames of the odd slots
         __syncthreads();
         float* red = reinterpret_cast<float*>(sw_lds);               // [ct][k][nt][r][lane]
@@ -331,23 +307,14 @@ extern "C" int fgcn_spatial_wgrad_tile_slabs(int B, int T, int V, int Cin, int C
     return swt_geom(B, T, V, Cin, Cout).nseg;
 }
 
-static int spatial_wgrad_tile_launch(const float* x, const float* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
-                                     int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream, int dy16);
-
 // half_mask (math mode bf16; strides in elements): bit 0 = x is a BFLOAT16 tensor, bit 1 = dy is (masks 0, 2, 3: a bfloat16 x comes with a
 // bfloat16 dy); a bfloat16 dy alone is bit-identical to the call on the f32 tensor fgcn_bn_act_bwd_apply would have written
 extern "C" int fgcn_spatial_wgrad_tile(const void* x, const void* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
                                        int Cout, int ld_x, int ld_dy, int a_hat_batched, int half_mask, void* stream) {
     FGCN_REQUIRE(half_mask == 0 || half_mask == 2 || half_mask == 3, FGCN_E_BADARG, "spatial_wgrad_tile: half_mask=%d (0, 2 or 3)", half_mask);
-    // the kernel's selector counts from dy: dy16 1 = dy bfloat16, 3 = dy and x
-    return spatial_wgrad_tile_launch(static_cast<const float*>(x), static_cast<const float*>(dy), a_hat, partial, B, T, V, Cin, Cout, ld_x, ld_dy,
-                                     a_hat_batched, stream, half_mask == 3 ? 3 : (half_mask == 2 ? 1 : 0));
-}
-
-static int spatial_wgrad_tile_launch(const float* x, const float* dy, const float* a_hat, float* partial, int B, int T, int V, int Cin,
-                                     int Cout, int ld_x, int ld_dy, int a_hat_batched, void* stream, int dy16) {   // dy16: 1 = dy bfloat16, 3 = dy and x
+    const bool x16 = half_mask & 1, dy16 = half_mask & 2;
     FGCN_REQUIRE(x && dy && a_hat && partial, FGCN_E_BADARG, "spatial_wgrad_tile: null pointer");
-    FGCN_REQUIRE(!dy16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_wgrad_tile: a bfloat16 dy needs math mode bf16");
+    FGCN_REQUIRE(!half_mask || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "spatial_wgrad_tile: a bfloat16 dy needs math mode bf16");
     FGCN_REQUIRE(fgcn_spatial_wgrad_tile_available(V, Cin, Cout), FGCN_E_BADARG,
                  "spatial_wgrad_tile: V=%d Cin=%d Cout=%d in math mode %d not supported (split-bf16 mode, 16 <= V <= %d, channels in 64s)", V,
                  Cin, Cout, fgcn::math_mode(), FGCN_MAX_V);
@@ -361,48 +328,27 @@ static int spatial_wgrad_tile_launch(const float* x, const float* dy, const floa
     const SwtGeom g = swt_geom(B, T, V, Cin, Cout);
     FGCN_REQUIRE((long long)g.nseg * 3 * Cin * Cout * 4 < (1ll << 31), FGCN_E_BADARG, "spatial_wgrad_tile: partial slabs must be smaller than 2 GiB");
     SwTileP p;
-    p.x = x, p.dy = dy, p.a_hat = a_hat, p.partial = partial;
+    p.x = static_cast<const float*>(x), p.dy = static_cast<const float*>(dy), p.a_hat = a_hat, p.partial = partial;
     p.B = B, p.T = T, p.V = V, p.Cin = Cin, p.Cout = Cout, p.ld_x = ld_x, p.ld_dy = ld_dy, p.a_batched = a_hat_batched;
     p.F = g.F, p.tiles_t = g.tiles_t, p.gtiles = g.gtiles, p.tps = g.tps, p.nseg = g.nseg, p.n_cg = g.n_cg, p.n_og = g.n_og;
-    p.x_bytes = (unsigned)(rows * ld_x * ((dy16 & 2) ? 2 : 4)), p.dy_bytes = (unsigned)(rows * ld_dy * (dy16 ? 2 : 4));
+    p.x_bytes = (unsigned)(rows * ld_x * (x16 ? 2 : 4)), p.dy_bytes = (unsigned)(rows * ld_dy * (dy16 ? 2 : 4));
     p.p_bytes = (unsigned)((long long)g.nseg * 3 * Cin * Cout * 4);
-    hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(g.nseg * g.n_cg * g.n_og));
-#define FGCN_SWT4(CT_, NT_, NS_, NP_, I16_)                                                                                      \
-    do {                                                                                                                          \
-        static bool attr = false;                                                                                                 \
-        if (!attr) {                                                                                                              \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_wgrad_tile_x3_kernel<CT_, NT_, NS_, NP_, I16_>),   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, swt_lds<NT_>());                                \
-            attr = true;                                                                                                          \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((spatial_wgrad_tile_x3_kernel<CT_, NT_, NS_, NP_, I16_>), grid, dim3(512), swt_lds<NT_>(), s, p);     \
-    } while (0)
-    const bool one_part = fgcn::math_mode() == FGCN_MATH_BF16;     // operands rounded to bfloat16 once
-#define FGCN_SWT(CT_, NT_, NS_)                                    \
-    do {                                                           \
-        if (one_part && dy16 == 3) FGCN_SWT4(CT_, NT_, NS_, 1, 3); \
-        else if (one_part && dy16) FGCN_SWT4(CT_, NT_, NS_, 1, 1); \
-        else if (one_part) FGCN_SWT4(CT_, NT_, NS_, 1, 0);         \
-        else FGCN_SWT4(CT_, NT_, NS_, 3, 0);                       \
-    } while (0)
+    const int np = fgcn::math_mode() == FGCN_MATH_BF16 ? 1 : 3;     // one part: operands rounded to bfloat16 once
     // frame slots of a wave per tile: F frames over 8 / CT waves per channel tile, rounded up to even
-    const int nslot = ((g.F + 8 / g.CT - 1) / (8 / g.CT) + 1) & ~1;
-#define FGCN_SWT_NT(CT_, NS_)                  \
-    do {                                       \
-        if (g.NT == 8) FGCN_SWT(CT_, 8, NS_);  \
-        else FGCN_SWT(CT_, 4, NS_);            \
-    } while (0)
     // (5 .. 8 frames per tile for 16 .. 32 joints: 6 or 8 slots with one wave per channel tile, 4 with two)
+    const int nslot = ((g.F + 8 / g.CT - 1) / (8 / g.CT) + 1) & ~1;
     FGCN_REQUIRE(nslot == (g.CT == 8 ? (g.F > 6 ? 8 : 6) : 4), FGCN_E_BADARG, "spatial_wgrad_tile: %d frames per tile: no such kernel form", g.F);
-    if (g.CT == 8) {
-        if (nslot == 8) FGCN_SWT_NT(8, 8);
-        else FGCN_SWT_NT(8, 6);
-    } else {
-        FGCN_SWT_NT(4, 4);
-    }
-#undef FGCN_SWT_NT
-#undef FGCN_SWT
-#undef FGCN_SWT4
+    // the kernel's storage selector counts from dy (one-part kernel only): 1 = dy bfloat16, 3 = dy and x
+    const int in16 = x16 ? 3 : (dy16 ? 1 : 0);
+    const bool built = dispatch(
+        [&](auto CT, auto NT, auto NS, auto NP, auto IN16) {
+            constexpr bool built = (CT == 8) == (NS != 4) && (NP == 1 || IN16 == 0);
+            if constexpr (built) launch_lds<spatial_wgrad_tile_x3_kernel<CT, NT, NS, NP, IN16>>(grid, dim3(512), swt_lds<NT>(), swt_lds<NT>(), (hipStream_t)stream, p);
+            return built;
+        },
+        one_of<4, 8>{g.CT == 8 ? 8 : 4}, one_of<4, 8>{g.NT == 8 ? 8 : 4}, one_of<4, 6, 8>{g.CT == 8 ? nslot : 4}, one_of<1, 3>{np},
+        one_of<0, 1, 3>{in16});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "spatial_wgrad_tile: no such kernel form (%d frame slots, half_mask=%d)", nslot, half_mask);
     return launch_status("spatial_wgrad_tile");
 }

@@ -18,7 +18,7 @@
 //
 // Arithmetic: float32 FMAs in ascending column order in EVERY math mode -- two launches agree bit for bit and the math mode changes
 // nothing (the rule of the joint kernels).
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 namespace fgcn {
 
@@ -46,14 +46,13 @@ __global__ __launch_bounds__(256) void graph_spmm_kernel(SpmmP p, const int* __r
     const int row0 = (int)blockIdx.z * p.V;                                // first row of this sample (B * V < 2^29: host check)
     const int n0 = (int)blockIdx.x * SPMM_RUN;
 
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(RES ? p.b : p.in), 0, RES ? p.b_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc((void*)(MASK ? (void*)p.mask : (void*)p.out), 0,
-                                                                        MASK ? p.mask_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rb = buffer_rsrc((RES ? p.b : p.in), RES ? p.b_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rm = buffer_rsrc((MASK ? (void*)p.mask : (void*)p.out), MASK ? p.mask_bytes : 0u);
     f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sh = {0.f, 0.f, 0.f, 0.f};
     if constexpr (RES == 2) {
-        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)p.vec_b, 0, (unsigned)p.C * 16u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rv = buffer_rsrc(p.vec_b, (unsigned)p.C * 16u);
         sc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, lane_off, (unsigned)p.C * 8u, 0));
         sh = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, lane_off, (unsigned)p.C * 12u, 0));
     }

@@ -18,7 +18,7 @@
 //   (row, tap) with a select on the A fragment.
 // Strided convolutions run as two stride-1 passes over the even / odd frames ("virtual frames" with a stride and
 // offset on the input or output side), so no tap is ever multiplied with a structurally-zero row.
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 #include <type_traits>
 
 namespace fgcn {
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, MINB) void conv_halo_kernel(HaloP p) {
     // image) meet in one L2.  Speed only.
     int bm, bn;
     if (p.per_xcd > 0) {
-        const int vid = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);
+        const int vid = xcd_tile(blockIdx.x, p.per_xcd);
         if (vid >= p.tiles_m * p.tiles_n) return;
         bm = vid / p.tiles_n;
         bn = vid - bm * p.tiles_n;
@@ -112,8 +112,8 @@ __global__ __launch_bounds__(256, MINB) void conv_halo_kernel(HaloP p) {
     const int V = p.V, TvV = p.Tv * p.V;
     const unsigned k4b = (tid & 7) * 16;            // byte offset of this thread's 4 channels inside a 32-chunk
 
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.w4, p.w_bytes);
 
     // this lane's output row (for the per-tap frame mask)
     const long long mrow = m0 + wave * 32 + l31;
@@ -232,9 +232,8 @@ __global__ __launch_bounds__(256, MINB) void conv_halo_kernel(HaloP p) {
     // Branch-free buffer stores (rows / channels / frames that do not exist carry the out-of-range offset and are
     // dropped): guarded global stores made hipcc wait for vmcnt(0) after every single store.
     constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.bias ? p.bias : p.w4), 0, p.bias ? (unsigned)p.N * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc((p.bias ? p.bias : p.w4), p.bias ? (unsigned)p.N * 4u : 0u);
     float ssum[NT], ssq[NT], bv[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -400,7 +399,7 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
     // (shared halo rows) run back to back on ONE XCD and find each other's rows in its L2 instead of fetching them again
     int bm = blockIdx.x, bn = blockIdx.y;
     if (p.per_xcd > 0) {
-        const int vid = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);
+        const int vid = xcd_tile(blockIdx.x, p.per_xcd);
         if (vid >= p.tiles_m * p.tiles_n) return;
         bm = vid / p.tiles_n;
         bn = vid - bm * p.tiles_n;
@@ -412,9 +411,8 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
     const int V = p.V, TvV = p.Tv * p.V;
     const unsigned k4b = (tid % TPR) * 16;
 
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const unsigned char*>(p.w4) + (NP == 2 ? 16 : 0)), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc((reinterpret_cast<const unsigned char*>(p.w4) + (NP == 2 ? 16 : 0)), p.w_bytes);
     // NP == 2 (f16x2 products, fgcn_common.hpp): block scaling.  The staged chunk (tile + halo rows x KC channels) is scaled by 2^ea as it
     // is split, ea from its largest magnitude (wave maxima through four LDS words); the accumulators are rescaled (a power of two:
     // exact) whenever the scale moves, and the epilogue multiplies 2^-ea 2^-ew back out (ew: the packed form's scale, header word of
@@ -518,17 +516,15 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
                 }
                 stage[i] = buf_load4(rin, src_off[i], (unsigned)kc * 4);
                 if constexpr (FIN)
-                    stage2[i] = buf_load4(__builtin_amdgcn_make_buffer_rsrc((void*)p.fin_res, 0, p.in_bytes, 0x00020000), src_off[i],
+                    stage2[i] = buf_load4(buffer_rsrc(p.fin_res, p.in_bytes), src_off[i],
                                           (unsigned)kc * 4);
             }
     };
     auto deposit = [&](int kc, int lo = 0, int hi = 64) {   // split the staged rows into the three bf16 planes
         const float a_scale = (NP == 2 && ea != EA_NONE) ? exp2i(ea) : 1.f;
         f32x4 fsc = {0.f, 0.f, 0.f, 0.f}, fsh = fsc;
-        const __amdgpu_buffer_rsrc_t rgo = __builtin_amdgcn_make_buffer_rsrc((void*)(FIN ? (void*)p.fin_out : (void*)p.out), 0,
-                                                                             FIN ? p.in_bytes : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rgm = __builtin_amdgcn_make_buffer_rsrc((void*)(FIN ? (void*)p.fin_mask : (void*)p.out), 0,
-                                                                             FIN ? p.in_bytes >> 5 : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rgo = buffer_rsrc((FIN ? (void*)p.fin_out : (void*)p.out), FIN ? p.in_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t rgm = buffer_rsrc((FIN ? (void*)p.fin_mask : (void*)p.out), FIN ? p.in_bytes >> 5 : 0u);
         const int own0 = -p.dmin * V;                // image row of the tile's first own (non-halo) row
         if constexpr (FIN) {
             fsc = *reinterpret_cast<const f32x4*>(p.fin_vec + 2 * p.K + kc + (tid % TPR) * 4);
@@ -673,18 +669,15 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
     // accumulator register r of lane (col l15, g4) = row 4 g4 + r of the 16 x 16 tile
     __builtin_amdgcn_sched_barrier(0);                    // (epilogue loads hoisted into the last MFMA step spilled registers)
     const bool plain_out = p.out_s == 1 && p.out_o == 0 && p.T_out_full == p.Tv && p.Th_out == p.Tv;
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.bias ? p.bias : p.w4), 0, p.bias ? (unsigned)p.N * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc((p.bias ? p.bias : p.w4), p.bias ? (unsigned)p.N * 4u : 0u);
     float ssum[NU], ssq[NU], bv[NU];
     unsigned coff[NU];
     const float un_a = (NP == 2 && ea != EA_NONE) ? exp2i(-ea) : 1.f, un_w = NP == 2 ? exp2i(-ew) : 1.f;
     constexpr bool bnb = EPI == 2;                        // BatchNorm-backward sums instead of the forward moments
-    const __amdgpu_buffer_rsrc_t rba = __builtin_amdgcn_make_buffer_rsrc((void*)(bnb ? p.bn_a : p.out), 0, p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbm = __builtin_amdgcn_make_buffer_rsrc((void*)(bnb ? (const void*)p.bn_mask : (const void*)p.out), 0,
-                                                                         p.out_bytes >> 5, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbv = __builtin_amdgcn_make_buffer_rsrc((void*)(bnb ? p.bn_vec : p.w4), 0,
-                                                                         bnb ? (unsigned)p.N * 8u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rba = buffer_rsrc((bnb ? p.bn_a : p.out), p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rbm = buffer_rsrc((bnb ? (const void*)p.bn_mask : (const void*)p.out), p.out_bytes >> 5);
+    const __amdgpu_buffer_rsrc_t rbv = buffer_rsrc((bnb ? p.bn_vec : p.w4), bnb ? (unsigned)p.N * 8u : 0u);
     float bmean[NU], brstd[NU];
 #pragma unroll
     for (int nu = 0; nu < NU; ++nu) {
@@ -731,14 +724,12 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
     };
     constexpr bool fep = EPI == 4;                        // inference output stage (HaloP::ep_*)
     constexpr bool ldacc = EPI == 3 || fep;               // per-element operand of the epilogue: out's old values / the shortcut values
-    const __amdgpu_buffer_rsrc_t rold = fep ? __builtin_amdgcn_make_buffer_rsrc((void*)(p.ep_res ? (const void*)p.ep_res : (const void*)p.out), 0,
-                                                                                p.ep_res ? p.out_bytes : 0u, 0x00020000)
+    const __amdgpu_buffer_rsrc_t rold = fep ? buffer_rsrc((p.ep_res ? (const void*)p.ep_res : (const void*)p.out), p.ep_res ? p.out_bytes : 0u)
                                             : rout;
     float esc[NU], esh[NU], rsc[NU], rsh[NU];
     if constexpr (fep) {
-        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)p.ep_vec, 0, (unsigned)p.N * 16u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rrv = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ep_rvec ? p.ep_rvec : p.ep_vec), 0,
-                                                                             p.ep_rvec ? (unsigned)p.N * 16u : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rv = buffer_rsrc(p.ep_vec, (unsigned)p.N * 16u);
+        const __amdgpu_buffer_rsrc_t rrv = buffer_rsrc((p.ep_rvec ? p.ep_rvec : p.ep_vec), p.ep_rvec ? (unsigned)p.N * 16u : 0u);
         const float res_unit = p.ep_rvec ? 0.f : 1.f;     // (branch-free: an empty descriptor returns 0, the scalar addend makes the scale 1)
 #pragma unroll
         for (int nu = 0; nu < NU; ++nu) {
@@ -872,52 +863,29 @@ extern "C" int fgcn_tconv_halo_tiles(int B, int Th_out, int Th_in, int V) {
     return (int)cdiv((long long)B * Tv * V, halo_tile_rows(V));
 }
 
-// one instantiation of the split kernel (LDS opt-in once per instantiation: not a stream operation, stays out of graph captures); the
-// bfloat16-input form exists for the one-part tap kernel only
-template <int NT, int KC, int NP, int EPI, bool FIN, int WR, bool STR>
-static void halo_k32_launch(int in16, dim3 grid, size_t lds, hipStream_t s, const HaloP& p) {
-    constexpr int max_lds = 32 * HALO_MAX_STAGE * XSB * 3;
-    if constexpr (NP == 1 && !FIN && KC == 32 && EPI == 0) {
-        if (in16 == 2) {             // bfloat16 in and out (the launcher has checked that this is the form it dispatches to)
-            static bool opted162 = false;
-            if (!opted162) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_x3k32_kernel<NT, KC, NP, EPI, FIN, WR, STR, 2>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-                opted162 = true;
-            }
-            hipLaunchKernelGGL((conv_halo_x3k32_kernel<NT, KC, NP, EPI, FIN, WR, STR, 2>), grid, dim3(256), lds, s, p);
-            return;
-        }
-    }
-    if constexpr (NP == 1 && !FIN && KC == 32 && EPI != 4) {
-        if (in16) {
-            static bool opted16 = false;
-            if (!opted16) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_x3k32_kernel<NT, KC, NP, EPI, FIN, WR, STR, 1>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-                opted16 = true;
-            }
-            hipLaunchKernelGGL((conv_halo_x3k32_kernel<NT, KC, NP, EPI, FIN, WR, STR, 1>), grid, dim3(256), lds, s, p);
-            return;
-        }
-    }
-    static bool opted = false;
-    if (!opted) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_x3k32_kernel<NT, KC, NP, EPI, FIN, WR, STR>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-        opted = true;
-    }
-    hipLaunchKernelGGL((conv_halo_x3k32_kernel<NT, KC, NP, EPI, FIN, WR, STR>), grid, dim3(256), lds, s, p);
+// The instantiations of the split kernel that are built (H16: 1 = bfloat16 input, 2 = bfloat16 input and output -- the one-part tap kernel
+// only, the output through the plain store epilogue): the fused input stage and the 1x1 form on the 2 x 2 wave arrangement (WR = 2) with the
+// store epilogues; the 4 x 1 arrangement (WR = 4) over 64 columns with every epilogue, over 128 with the store epilogues; the inference
+// stage (EPI 4) not for the f16x2 products (NP = 2); streamed stores not in the accumulating epilogue (EPI 3)
+constexpr bool halo_k32_built(int NT, int KC, int NP, int EPI, bool FIN, int WR, bool STR, int H16) {
+    if ((STR && EPI == 3) || (EPI == 4 && NP == 2)) return false;
+    if (H16 && !(NP == 1 && !FIN && KC == 32 && EPI != 4 && (H16 == 1 || EPI == 0))) return false;
+    if (FIN) return NT <= 2 && KC == 32 && NP != 2 && EPI == 0 && WR == 2;
+    if (KC == 64) return NT <= 2 && WR == 2 && (EPI == 0 || EPI == 3);
+    if (WR == 2) return NT <= 2;
+    return NT == 2 || (NT == 4 && (EPI == 0 || EPI == 3));
 }
 
+// the body of fgcn_tconv_halo and fgcn_tconv_halo_bn_relu (ep_vec: the inference output stage); half_mask as for fgcn_tconv_halo
 static int tconv_halo_impl(const float* in, float* out, const float* w4, const float* bias, float* stat_partials,
                            int B, int Th, int V, int K, int N, int ld_in, int ld_out,
                            int T_in_full, int in_s, int in_o, int Th_in,
                            int T_out_full, int out_s, int out_o,
                            int taps, int tb, int tc, int accumulate, const float* bn_a, const unsigned char* bn_mask,
                            const float* bn_vec, const float* fin_vec, const float* fin_res, float* fin_out,
-                           unsigned char* fin_mask, unsigned* in_amax, void* stream, int in16, const float* ep_vec = nullptr,
-                           const float* ep_res = nullptr, const float* ep_rvec = nullptr) {
+                           unsigned char* fin_mask, unsigned* in_amax, void* stream, int half_mask, const float* ep_vec,
+                           const float* ep_res, const float* ep_rvec) {
+    const bool in16 = half_mask & 1, out16 = half_mask & 2;
     FGCN_REQUIRE(in && out && w4, FGCN_E_BADARG, "tconv_halo: null pointer");
     const bool fep = ep_vec != nullptr;
     FGCN_REQUIRE(!fep || ((fgcn::math_mode() == FGCN_MATH_BF16X3 || fgcn::math_mode() == FGCN_MATH_BF16) && !fgcn::f16x2_products() && !in16 &&
@@ -927,8 +895,8 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
                  "plain output view, no statistics / accumulation / fused input stage");
     FGCN_REQUIRE(!in16 || (fgcn::math_mode() == FGCN_MATH_BF16 && !(fin_vec || fin_res || fin_out || fin_mask) && !(taps == 1 && K % 64 == 0)),
                  FGCN_E_BADARG, "tconv_halo: a bfloat16 input needs math mode bf16, the tap form and no fused input stage");
-    // (in16 == 2: the output is bfloat16 too -- the plain store epilogue, with or without the forward moments)
-    FGCN_REQUIRE(in16 != 2 || (!accumulate && !bn_a && !fep && ld_out % 2 == 0), FGCN_E_BADARG,
+    // (a bfloat16 output: the plain store epilogue, with or without the forward moments)
+    FGCN_REQUIRE(!out16 || (!accumulate && !bn_a && !fep && ld_out % 2 == 0), FGCN_E_BADARG,
                  "tconv_halo: a bfloat16 output is written by the plain store epilogue (no accumulation, no BatchNorm-backward sums)");
     const bool fin = fin_vec || fin_res || fin_out || fin_mask;
     FGCN_REQUIRE(!fin || !fgcn::f16x2_products(), FGCN_E_BADARG, "tconv_halo: the fused input stage is not built for the f16x2 products");
@@ -958,8 +926,8 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
     const long long in_bytes = (long long)B * T_in_full * V * ld_in * (in16 ? 2 : 4);
     const bool two = fgcn::f16x2_products();                                                // FGCN_PACK_SPLIT2H weights: two f16 parts
     const long long w_bytes = (long long)taps * K * N * (mm != FGCN_MATH_F32 ? (two ? 4 : 6) : 4);   // split form in both bf16 modes
-    const long long out_bytes = (long long)B * T_out_full * V * ld_out * (in16 == 2 ? 2 : 4);
-    FGCN_REQUIRE(in_bytes < 0x7FFF0000ll && w_bytes < 0x7FFF0000ll && out_bytes < 0x7FFF0000ll, FGCN_E_BADARG,
+    const long long out_bytes = (long long)B * T_out_full * V * ld_out * (out16 ? 2 : 4);
+    FGCN_REQUIRE(fits_buffer(in_bytes) && fits_buffer(w_bytes) && fits_buffer(out_bytes), FGCN_E_BADARG,
                  "tconv_halo: tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     HaloP p;
     p.in = in; p.out = out; p.w4 = w4; p.bias = bias; p.stats = stat_partials;
@@ -1001,18 +969,8 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
     const long long tiles = cdiv(p.Mv, bmr);
     FGCN_REQUIRE(p.Mv < (1ll << 31) - 4096, FGCN_E_BADARG, "tconv_halo: too many rows (32-bit row indices)");
     hipStream_t s = (hipStream_t)stream;
-    static bool lds_opt_in = false;  // once per process (not a stream operation: keep it out of graph captures)
-    if (!lds_opt_in) {               // V > 25 needs more than the default dynamic-LDS limit (gfx950: 160 KiB per CU)
-        const int max_lds = 32 * HALO_MAX_STAGE * XSB * 3;   // the larger of the two image forms
-#define FGCN_HALO_ATTR(NT_, MB_)                                                                            \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<NT_, MB_, 0>),              \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);                       \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<NT_, MB_, 1>),              \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)
-        FGCN_HALO_ATTR(2, 2); FGCN_HALO_ATTR(2, 3); FGCN_HALO_ATTR(4, 2); FGCN_HALO_ATTR(4, 3);
-#undef FGCN_HALO_ATTR
-        lds_opt_in = true;
-    }
+    // V > 25 needs more than the default dynamic-LDS limit (gfx950: 160 KiB per CU); the larger of the two image forms
+    constexpr int max_lds = 32 * HALO_MAX_STAGE * XSB * 3;
     const bool three = fgcn::tuning(4) == 0;   // 3 workgroups per CU measured faster (64 channels: 0.73 -> 0.63 ms)
     p.tiles_m = (int)tiles;
     p.tiles_n = (int)cdiv(N, N <= 64 ? 64 : 128);
@@ -1035,90 +993,37 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
         FGCN_REQUIRE(!(bn_a && accumulate), FGCN_E_BADARG, "tconv_halo: BatchNorm-backward sums of an accumulating call are not built");
         const int epi = fep ? 4 : (bn_a ? 2 : (accumulate ? 3 : 0));     // epilogue form (compile time, see the kernel)
         // the bytes this call writes (a bfloat16 output: 32-byte pieces, stored plainly unless tuning key 25 bit 0 asks for streamed stores)
-        const bool stream_k = in16 != 2 ? fgcn::stream_out((long long)B * Th * V * N * 4) : ((fgcn::tuning(25) & 1) && fgcn::stream_out((long long)B * Th * V * N * 2));
-#define FGCN_K32_GO7(NT_, KC_, NP_, EPI_, FIN_, WR_, STR_) halo_k32_launch<NT_, KC_, NP_, EPI_, FIN_, WR_, STR_>(in16, grid, lds_k, s, p)
-#define FGCN_K32_GO6(NT_, KC_, NP_, EPI_, FIN_, WR_)                                                                     \
-    do {                                                                                                                 \
-        if (EPI_ != 3 && stream_k) FGCN_K32_GO7(NT_, KC_, NP_, EPI_, FIN_, WR_, (EPI_ != 3));                            \
-        else FGCN_K32_GO7(NT_, KC_, NP_, EPI_, FIN_, WR_, false);                                                        \
-    } while (0)
-#define FGCN_K32_GO(NT_, KC_, NP_, EPI_, FIN_) FGCN_K32_GO6(NT_, KC_, NP_, EPI_, FIN_, 2)
-#define FGCN_K32_WIDE_NP(EPI_)                                                                                           \
-    do {                                                                                                                 \
-        if (one) FGCN_K32_GO6(2, 32, 1, EPI_, false, 4);                                                                 \
-        else if (two) FGCN_K32_GO6(2, 32, 2, EPI_, false, 4);                                                            \
-        else FGCN_K32_GO6(2, 32, 3, EPI_, false, 4);                                                                     \
-    } while (0)
-#define FGCN_K32_NP(NT_, KC_, EPI_)                                                                                      \
-    do {                                                                                                                 \
-        if (one) FGCN_K32_GO(NT_, KC_, 1, EPI_, false);                                                                  \
-        else if (two) FGCN_K32_GO(NT_, KC_, 2, EPI_, false);                                                             \
-        else FGCN_K32_GO(NT_, KC_, 3, EPI_, false);                                                                      \
-    } while (0)
-#define FGCN_K32_NP13(NT_, KC_, EPI_)      /* (the inference stage: three bf16 parts or one -- not the f16x2 products) */ \
-    do {                                                                                                                 \
-        if (one) FGCN_K32_GO(NT_, KC_, 1, EPI_, false);                                                                  \
-        else FGCN_K32_GO(NT_, KC_, 3, EPI_, false);                                                                      \
-    } while (0)
-#define FGCN_K32_LAUNCH(NT_, KC_)                                                                                        \
-    do {                                                                                                                 \
-        if (epi == 0) FGCN_K32_NP(NT_, KC_, 0);                                                                          \
-        else if (epi == 3) FGCN_K32_NP(NT_, KC_, 3);                                                                     \
-        else if (epi == 4 && KC_ == 32) FGCN_K32_NP13(NT_, 32, 4);                                                       \
-        else if (epi == 2 && KC_ == 32) FGCN_K32_NP(NT_, 32, 2);                                                         \
-        else return fgcn::fail(FGCN_E_BADARG, "tconv_halo: BatchNorm-backward sums are built for the tap kernel only"); \
-    } while (0)
-        if (fin) {
-            FGCN_REQUIRE(!pw, FGCN_E_BADARG, "tconv_halo: the fused input stage runs on the 128-row tap tile (V <= 32)");
-            if (N <= 64) {
-                if (one) FGCN_K32_GO(1, 32, 1, 0, true);
-                else FGCN_K32_GO(1, 32, 3, 0, true);
-            } else {
-                if (one) FGCN_K32_GO(2, 32, 1, 0, true);
-                else FGCN_K32_GO(2, 32, 3, 0, true);
-            }
-        } else if (pw) {
-            if (N <= 64) FGCN_K32_LAUNCH(1, 64);
-            else FGCN_K32_LAUNCH(2, 64);
-        } else {
-            if (wide_rows && epi == 4) {                 // (N <= 64: the 128-column 4 x 1 form is excluded for this epilogue above)
-                if (one) FGCN_K32_GO6(2, 32, 1, 4, false, 4); else FGCN_K32_GO6(2, 32, 3, 4, false, 4);
-            } else if (wide_rows && N > 64) {
-                if (epi == 0) { if (one) FGCN_K32_GO6(4, 32, 1, 0, false, 4); else if (two) FGCN_K32_GO6(4, 32, 2, 0, false, 4); else FGCN_K32_GO6(4, 32, 3, 0, false, 4); }
-                else { if (one) FGCN_K32_GO6(4, 32, 1, 3, false, 4); else if (two) FGCN_K32_GO6(4, 32, 2, 3, false, 4); else FGCN_K32_GO6(4, 32, 3, 3, false, 4); }
-            } else if (wide_rows) {
-                if (epi == 0) FGCN_K32_WIDE_NP(0);
-                else if (epi == 3) FGCN_K32_WIDE_NP(3);
-                else FGCN_K32_WIDE_NP(2);
-            } else if (N <= 64) FGCN_K32_LAUNCH(1, 32);
-            else FGCN_K32_LAUNCH(2, 32);
-        }
-#undef FGCN_K32_LAUNCH
-#undef FGCN_K32_NP13
-#undef FGCN_K32_NP
-#undef FGCN_K32_GO
-#undef FGCN_K32_GO6
-#undef FGCN_K32_GO7
-#undef FGCN_K32_WIDE_NP
+        const bool stream_k = !out16 ? fgcn::stream_out((long long)B * Th * V * N * 4) : ((fgcn::tuning(25) & 1) && fgcn::stream_out((long long)B * Th * V * N * 2));
+        FGCN_REQUIRE(!fin || !pw, FGCN_E_BADARG, "tconv_halo: the fused input stage runs on the 128-row tap tile (V <= 32)");
+        FGCN_REQUIRE(!pw || epi == 0 || epi == 3, FGCN_E_BADARG, "tconv_halo: BatchNorm-backward sums are built for the tap kernel only");
+        // column tiles of a workgroup in 64s; the 4 x 1 wave arrangement (wide_rows, a four-slot weight ring): one 128-column tile = 4, else 2
+        // (N <= 64 for the inference stage: the 128-column 4 x 1 form is excluded for that epilogue above)
+        const int nt = !wide_rows ? (N <= 64 ? 1 : 2) : (epi != 4 && N > 64 ? 4 : 2);
+        const int h16 = !(one && !fin && !pw && epi != 4) ? 0 : (out16 && epi == 0 ? 2 : (in16 ? 1 : 0));
+        const int kc = pw ? 64 : 32, wr = wide_rows ? 4 : 2;
+        const bool str = epi != 3 && stream_k;
+        const bool built = dispatch(
+            [&](auto NT, auto KC, auto NP, auto EPI, auto FIN, auto WR, auto STR, auto H16) {
+                constexpr bool built = halo_k32_built(NT, KC, NP, EPI, FIN == 1, WR, STR == 1, H16);
+                if constexpr (built) launch_lds<conv_halo_x3k32_kernel<NT, KC, NP, EPI, FIN == 1, WR, STR == 1, H16>>(grid, dim3(256), max_lds, lds_k, s, p);
+                return built;
+            },
+            one_of<1, 2, 4>{nt}, one_of<32, 64>{kc}, one_of<1, 2, 3>{np}, one_of<0, 2, 3, 4>{epi}, one_of<0, 1>{fin}, one_of<2, 4>{wr},
+            one_of<0, 1>{str}, one_of<0, 1, 2>{h16});
+        FGCN_REQUIRE(built, FGCN_E_BADARG, "tconv_halo: no such kernel form");
         return launch_status("tconv_halo");
     }
     if ((fgcn::tuning(5) & 2) && tiles * p.tiles_n < (1ll << 30)) {   // measured neutral: off
         p.per_xcd = (int)cdiv(tiles * p.tiles_n, 8);
         grid = dim3((unsigned)(p.per_xcd * 8));
     }
-#define FGCN_HALO_LAUNCH(NT_, MB_)                                                                           \
-    do {                                                                                                     \
-        if (mm == FGCN_MATH_BF16) hipLaunchKernelGGL((conv_halo_kernel<NT_, MB_, 1>), grid, dim3(256), lds, s, p); \
-        else hipLaunchKernelGGL((conv_halo_kernel<NT_, MB_, 0>), grid, dim3(256), lds, s, p);                \
-    } while (0)
-    if (N <= 64) {
-        if (three) FGCN_HALO_LAUNCH(2, 3);
-        else FGCN_HALO_LAUNCH(2, 2);
-    } else {
-        if (three) FGCN_HALO_LAUNCH(4, 3);
-        else FGCN_HALO_LAUNCH(4, 2);
-    }
-#undef FGCN_HALO_LAUNCH
+    const bool built = dispatch(
+        [&](auto NT, auto MB, auto BF) {
+            launch_lds<conv_halo_kernel<NT, MB, BF>>(grid, dim3(256), max_lds, lds, s, p);
+            return true;
+        },
+        one_of<2, 4>{N <= 64 ? 2 : 4}, one_of<2, 3>{three ? 3 : 2}, one_of<0, 1>{mm == FGCN_MATH_BF16});
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "tconv_halo: no such kernel form");
     return launch_status("tconv_halo");
 }
 
@@ -1134,10 +1039,9 @@ extern "C" int fgcn_tconv_halo(const void* in, void* out, const float* w4, const
                                const float* bn_vec, const float* fin_vec, const float* fin_res, float* fin_out,
                                unsigned char* fin_mask, unsigned* in_amax, int half_mask, void* stream) {
     FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "tconv_halo: half_mask=%d (0, 1 or 3)", half_mask);
-    const int in16 = half_mask == 3 ? 2 : half_mask;      // 0 float32, 1 bfloat16 in, 2 bfloat16 in and out
     return tconv_halo_impl(static_cast<const float*>(in), static_cast<float*>(out), w4, bias, stat_partials, B, Th, V, K, N, ld_in, ld_out, T_in_full,
                            in_s, in_o, Th_in, T_out_full, out_s, out_o, taps, tb, tc, accumulate, bn_a, bn_mask, bn_vec, fin_vec, fin_res, fin_out,
-                           fin_mask, in_amax, stream, in16);
+                           fin_mask, in_amax, stream, half_mask, nullptr, nullptr, nullptr);
 }
 
 // North-star kernel 2 as the north star states it, for INFERENCE: the (taps x 1) temporal convolution (stride 1) with the block's output
@@ -1151,5 +1055,5 @@ extern "C" int fgcn_tconv_halo_bn_relu(const float* in, float* out, const float*
                                        int taps, int tb, int tc, void* stream) {
     FGCN_REQUIRE(bn_vec, FGCN_E_BADARG, "tconv_halo_bn_relu: the BatchNorm vector is required");
     return tconv_halo_impl(in, out, w4, bias, nullptr, B, T, V, K, N, ld_in, ld_out, T, 1, 0, T, T, 1, 0, taps, tb, tc, 0, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, stream, false, bn_vec, res, res_vec);
+                           nullptr, nullptr, nullptr, nullptr, nullptr, stream, 0, bn_vec, res, res_vec);
 }

@@ -11,7 +11,7 @@
 //   * strided convolutions are two calls over the even / odd frames of a (`a_s`, `a_o`: frame view), each tap lands
 //     in its own slab (`tap0`, `tap_step`), so no structurally-zero taps are computed.
 // Output: deterministic partial slabs [nslab][taps_total][K][N], summed by reduce_sum.
-#include "fgcn_common.hpp"
+#include "fgcn_tile.hpp"
 
 namespace fgcn {
 
@@ -76,8 +76,8 @@ __global__ __launch_bounds__(256, 2) void tconv_wgrad_kernel(TWgradP p) {
     const int sbeg = blockIdx.y * p.stages_per_split;
     const int send = min(sbeg + p.stages_per_split, p.total_stages);
 
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.g_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rg = buffer_rsrc(p.g, p.g_bytes);
 
     // per-lane part of the source addresses of a piece: a: row lane/8, channels (lane%8)*4;  g: row lane/(TN/4)
     const int a_lr = lane >> 3, akc = k0 + (lane & 7) * 4;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void tconv_wgrad_kernel(TWgradP p) {
     }
 
     // ---- partial slabs: [slab = split * NPART + part][tap][k][n] ------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)p.partial, 0, p.p_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = buffer_rsrc(p.partial, p.p_bytes);
     const int slab = blockIdx.y * NPART + part;
     const int ncol = n0 + nsub * 32 + l31;
 #pragma unroll
@@ -198,12 +198,6 @@ constexpr int X3_APASS = 6;              // passes of 64 rows: window <= 128 + 8
 // bytes apart modulo 256 = one transposed read touches every bank once.
 constexpr int x3_rows(int tn, int wv = 8) { return 32 * (wv / (tn / 32)); }   // 8 waves: 64 (TN 128) / 128 (TN 64); 4 waves: half
 constexpr int x3_sg(int tn) { return tn == 64 ? 160 : tn * 2 + 64; }   // (64 columns: 32 bytes of padding -- the circular window fits beside 128 g rows)
-
-__device__ __forceinline__ u32x2 lds_read_tr16(const unsigned char* p) {
-    using v4s = __attribute__((ext_vector_type(4))) short;
-    const v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
-    return __builtin_bit_cast(u32x2, v);
-}
 
 // CH (1x1 convolutions, fgcn_pw_wgrad): accumulator j = in-channel chunk j instead of tap j -- the "window" is then NTAP
 // images of the stage's rows, one per 32-channel chunk (window row chunk * X3_R + r), and the fragment of accumulator j
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void tconv_wgrad_x3_kerne
     const int nsub = wave % NSUBS, part = wave / NSUBS;
     int bx = blockIdx.x, by = blockIdx.y;
     if (p.per_xcd > 0) {
-        const int vid = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);
+        const int vid = xcd_tile(blockIdx.x, p.per_xcd);
         if (vid >= p.tiles_xy * p.n_split) return;
         by = vid / p.tiles_xy;
         bx = vid - by * p.tiles_xy;
@@ -263,8 +257,8 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void tconv_wgrad_x3_kerne
     const int sbeg = by * p.stages_per_split;
     const int send = min(sbeg + p.stages_per_split, p.total_stages);
 
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.g_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rg = buffer_rsrc(p.g, p.g_bytes);
     const bool strided = p.a_s != 1 || p.a_o != 0;
     int ea = 0, eg = 0;
     if constexpr (NP == 2) {
@@ -449,7 +443,7 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void tconv_wgrad_x3_kerne
     }
 
     // ---- partial slabs: [slab = split * NPARTS + part][tap][k][n] -----------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)p.partial, 0, p.p_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = buffer_rsrc(p.partial, p.p_bytes);
     const int slab = by * NPARTS + part;
     const float un_a = exp2i(-ea), un_g = exp2i(-eg);               // (NP == 2; 1 otherwise)
 #pragma unroll
@@ -511,97 +505,40 @@ extern "C" int fgcn_pw_wgrad_slabs(int N, int nsplit) { return nsplit * twgrad_p
 extern "C" int fgcn_tconv_wgrad_resident(int N) { return twgrad_use_x3(N, 0) && twgrad_x3_waves(N, 0) == 8 ? 256 : 512; }
 extern "C" int fgcn_pw_wgrad_resident(int N) { return twgrad_use_x3(N, 1) && twgrad_x3_waves(N, 1) == 8 ? 256 : 512; }
 
+// (the launch_twgrad* functions return whether they launched, as dispatch does)
 template <int NTAP>
-static void launch_twgrad(const TWgradP& p, int N, dim3 grid, size_t lds, hipStream_t s) {
-    static bool opt_in = false;   // once per instantiation; not a stream operation (stays out of graph captures)
-    if (!opt_in) {
-        const int max_lds = 160 * 1024;
-#define FGCN_TW_ATTR(TN_, BF_)                                                                      \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_wgrad_kernel<NTAP, TN_, BF_>),  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)
-        FGCN_TW_ATTR(64, 0); FGCN_TW_ATTR(64, 1); FGCN_TW_ATTR(64, 2); FGCN_TW_ATTR(128, 0); FGCN_TW_ATTR(128, 1);
-        FGCN_TW_ATTR(128, 2);
-#undef FGCN_TW_ATTR
-        opt_in = true;
-    }
+static bool launch_twgrad(const TWgradP& p, int N, dim3 grid, size_t lds, hipStream_t s) {
     const int mm = fgcn::math_mode();
-#define FGCN_TW_LAUNCH(TN_)                                                                                   \
-    do {                                                                                                      \
-        if (mm == FGCN_MATH_BF16X3) hipLaunchKernelGGL((tconv_wgrad_kernel<NTAP, TN_, 2>), grid, dim3(256), lds, s, p); \
-        else if (mm == FGCN_MATH_BF16) hipLaunchKernelGGL((tconv_wgrad_kernel<NTAP, TN_, 1>), grid, dim3(256), lds, s, p); \
-        else hipLaunchKernelGGL((tconv_wgrad_kernel<NTAP, TN_, 0>), grid, dim3(256), lds, s, p);              \
-    } while (0)
-    if (N <= 64) FGCN_TW_LAUNCH(64);
-    else FGCN_TW_LAUNCH(128);
-#undef FGCN_TW_LAUNCH
+    return dispatch(
+        [&](auto TN, auto BF) {
+            launch_lds<tconv_wgrad_kernel<NTAP, TN, BF>>(grid, dim3(256), 160 * 1024, lds, s, p);
+            return true;
+        },
+        one_of<64, 128>{N <= 64 ? 64 : 128}, one_of<0, 1, 2>{mm == FGCN_MATH_BF16X3 ? 2 : (mm == FGCN_MATH_BF16 ? 1 : 0)});
 }
 
-// one instantiation of the split kernel; the bfloat16-input form exists for the one-part kernel in tap mode
-template <int NTAP, int TN, bool CH, int NP, int WV, bool RING>
-static void twx_go(const TWgradP& p, dim3 grid, size_t lds, hipStream_t s) {
-    if constexpr (NP == 1) {
-        if (p.in16) {
-            static bool opted16 = false;
-            if (!opted16) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_wgrad_x3_kernel<NTAP, TN, CH, NP, WV, RING, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                opted16 = true;
-            }
-            hipLaunchKernelGGL((tconv_wgrad_x3_kernel<NTAP, TN, CH, NP, WV, RING, true>), grid, dim3(64 * WV), lds, s, p);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((tconv_wgrad_x3_kernel<NTAP, TN, CH, NP, WV, RING>), grid, dim3(64 * WV), lds, s, p);
-}
-
+// The split kernel: 1 bf16 part (math mode bf16), 2 f16 parts (f16x2 products) or 3 bf16 parts; 4 or 8 waves; the circular-window form
+// exists for the tap mode only, the bfloat16-input form for the one-part kernel; chunk mode with more than 3 chunks has no 64-column form
+// (the launcher's chunk counts never ask for it).
 template <int NTAP, bool CH>
-static void launch_twgrad_x3(const TWgradP& p, int N, dim3 grid, size_t lds, hipStream_t s) {
+static bool launch_twgrad_x3(const TWgradP& p, int N, dim3 grid, size_t lds, hipStream_t s) {
     static_assert(!CH || NTAP <= 6, "chunk mode: at most 6 (128 columns) / 3 (64 columns) chunks fit the staging passes");
-    constexpr bool RG = !CH;                          // the circular-window form exists for the tap mode only
-    static bool opt_in = false;
-    if (!opt_in) {
-#define FGCN_TWX_ATTR1(TN_, NP_, WV_, RING_)                                                                          \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_wgrad_x3_kernel<NTAP, TN_, CH, NP_, WV_, RING_>), \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-#define FGCN_TWX_ATTR(TN_)                                                                                            \
-    FGCN_TWX_ATTR1(TN_, 3, 8, false); FGCN_TWX_ATTR1(TN_, 1, 8, false); FGCN_TWX_ATTR1(TN_, 3, 4, false);            \
-    FGCN_TWX_ATTR1(TN_, 1, 4, false); FGCN_TWX_ATTR1(TN_, 3, 8, RG); FGCN_TWX_ATTR1(TN_, 1, 8, RG);                  \
-    FGCN_TWX_ATTR1(TN_, 3, 4, RG); FGCN_TWX_ATTR1(TN_, 1, 4, RG);                                                    \
-    FGCN_TWX_ATTR1(TN_, 2, 8, false); FGCN_TWX_ATTR1(TN_, 2, 4, false); FGCN_TWX_ATTR1(TN_, 2, 8, RG); FGCN_TWX_ATTR1(TN_, 2, 4, RG)
-        FGCN_TWX_ATTR(128);
-        if constexpr (!CH || NTAP <= 3) { FGCN_TWX_ATTR(64); }
-#undef FGCN_TWX_ATTR
-#undef FGCN_TWX_ATTR1
-        opt_in = true;
-    }
     const bool one = fgcn::math_mode() == FGCN_MATH_BF16;
     const bool two = !one && p.a_amax && p.g_amax;                // f16x2 products (twgrad_launch cleared the pointers otherwise)
-    const bool half = twgrad_x3_waves(N, CH ? 1 : 0) == 4;
-    const bool ring = RG && p.ring_rows > 0;
-#define FGCN_TWX_GO(TN_, NP_, WV_, RING_) twx_go<NTAP, TN_, CH, NP_, WV_, RING_>(p, grid, lds, s)
-#define FGCN_TWX_LAUNCH(TN_)                                                                                    \
-    do {                                                                                                        \
-        if (ring) {                                                                                             \
-            if (half) { if (one) FGCN_TWX_GO(TN_, 1, 4, RG); else if (two) FGCN_TWX_GO(TN_, 2, 4, RG); else FGCN_TWX_GO(TN_, 3, 4, RG); } \
-            else { if (one) FGCN_TWX_GO(TN_, 1, 8, RG); else if (two) FGCN_TWX_GO(TN_, 2, 8, RG); else FGCN_TWX_GO(TN_, 3, 8, RG); }      \
-        } else {                                                                                                \
-            if (half) { if (one) FGCN_TWX_GO(TN_, 1, 4, false); else if (two) FGCN_TWX_GO(TN_, 2, 4, false); else FGCN_TWX_GO(TN_, 3, 4, false); } \
-            else { if (one) FGCN_TWX_GO(TN_, 1, 8, false); else if (two) FGCN_TWX_GO(TN_, 2, 8, false); else FGCN_TWX_GO(TN_, 3, 8, false); }      \
-        }                                                                                                       \
-    } while (0)
-    if (N <= 64) {
-        if constexpr (!CH || NTAP <= 3) FGCN_TWX_LAUNCH(64);
-    } else {
-        FGCN_TWX_LAUNCH(128);
-    }
-#undef FGCN_TWX_LAUNCH
-#undef FGCN_TWX_GO
+    return dispatch(
+        [&](auto TN, auto NP, auto WV, auto RING, auto IN16) {
+            constexpr bool built = (TN == 128 || !CH || NTAP <= 3) && (RING == 0 || !CH) && (IN16 == 0 || NP == 1);
+            if constexpr (built) launch_lds<tconv_wgrad_x3_kernel<NTAP, TN, CH, NP, WV, RING == 1, IN16 == 1>>(grid, dim3(64 * WV), 160 * 1024, lds, s, p);
+            return built;
+        },
+        one_of<64, 128>{N <= 64 ? 64 : 128}, one_of<1, 2, 3>{one ? 1 : (two ? 2 : 3)}, one_of<4, 8>{twgrad_x3_waves(N, CH ? 1 : 0)},
+        one_of<0, 1>{!CH && p.ring_rows > 0}, one_of<0, 1>{one && p.in16});
 }
 
 static int twgrad_launch(const float* a, const float* g, float* partial, int B, int T_g, int V, int K, int N,
                          int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int Th_a, int nacc, int chunk_mode,
                          int shift0, int tap0, int tap_step, int taps_total, int nsplit, const unsigned* a_amax,
-                         const unsigned* g_amax, void* stream, const char* what, bool in16 = false) {
+                         const unsigned* g_amax, void* stream, const char* what, bool in16) {
     FGCN_REQUIRE(a && g && partial, FGCN_E_BADARG, "%s: null pointer", what);
     FGCN_REQUIRE(!in16 || fgcn::math_mode() == FGCN_MATH_BF16, FGCN_E_BADARG, "%s: bfloat16 inputs need math mode bf16", what);
     FGCN_REQUIRE(B > 0 && T_g > 0 && V > 0 && V <= FGCN_MAX_V && K > 0 && N > 0 && nsplit > 0 && nsplit <= 65535,
@@ -615,7 +552,7 @@ static int twgrad_launch(const float* a, const float* g, float* partial, int B, 
     const int parts = twgrad_parts(N, chunk_mode);
     const bool x3 = twgrad_use_x3(N, chunk_mode);
     const long long p_bytes = (long long)nsplit * parts * taps_total * K * N * 4;
-    FGCN_REQUIRE(a_bytes < 0x7FFF0000ll && g_bytes < 0x7FFF0000ll && p_bytes < 0x7FFF0000ll, FGCN_E_BADARG,
+    FGCN_REQUIRE(fits_buffer(a_bytes) && fits_buffer(g_bytes) && fits_buffer(p_bytes), FGCN_E_BADARG,
                  "%s: tensors must be smaller than 2 GiB (32-bit buffer offsets)", what);
     TWgradP p;
     p.a = a; p.g = g; p.partial = partial;
@@ -658,40 +595,44 @@ static int twgrad_launch(const float* a, const float* g, float* partial, int B, 
         grid = dim3((unsigned)(p.per_xcd * 8));
     }
     hipStream_t s = (hipStream_t)stream;
+    bool built = false;
     if (x3 && chunk_mode) {
         switch (nacc) {
-            case 6: launch_twgrad_x3<6, true>(p, N, grid, lds, s); break;
-            case 5: launch_twgrad_x3<5, true>(p, N, grid, lds, s); break;
-            case 4: launch_twgrad_x3<4, true>(p, N, grid, lds, s); break;
-            case 3: launch_twgrad_x3<3, true>(p, N, grid, lds, s); break;
-            case 2: launch_twgrad_x3<2, true>(p, N, grid, lds, s); break;
-            case 1: launch_twgrad_x3<1, true>(p, N, grid, lds, s); break;
+            case 6: built = launch_twgrad_x3<6, true>(p, N, grid, lds, s); break;
+            case 5: built = launch_twgrad_x3<5, true>(p, N, grid, lds, s); break;
+            case 4: built = launch_twgrad_x3<4, true>(p, N, grid, lds, s); break;
+            case 3: built = launch_twgrad_x3<3, true>(p, N, grid, lds, s); break;
+            case 2: built = launch_twgrad_x3<2, true>(p, N, grid, lds, s); break;
+            case 1: built = launch_twgrad_x3<1, true>(p, N, grid, lds, s); break;
             default: return fgcn::fail(FGCN_E_BADARG, "%s: %d chunks per pass not instantiated", what, nacc);
         }
+        FGCN_REQUIRE(built, FGCN_E_BADARG, "%s: no such kernel form (N=%d, %d per pass)", what, N, nacc);
         return launch_status(what);
     }
     if (x3) {
         switch (nacc) {
-            case 9: launch_twgrad_x3<9, false>(p, N, grid, lds, s); break;
-            case 5: launch_twgrad_x3<5, false>(p, N, grid, lds, s); break;
-            case 4: launch_twgrad_x3<4, false>(p, N, grid, lds, s); break;
-            case 3: launch_twgrad_x3<3, false>(p, N, grid, lds, s); break;
-            case 2: launch_twgrad_x3<2, false>(p, N, grid, lds, s); break;
-            case 1: launch_twgrad_x3<1, false>(p, N, grid, lds, s); break;
+            case 9: built = launch_twgrad_x3<9, false>(p, N, grid, lds, s); break;
+            case 5: built = launch_twgrad_x3<5, false>(p, N, grid, lds, s); break;
+            case 4: built = launch_twgrad_x3<4, false>(p, N, grid, lds, s); break;
+            case 3: built = launch_twgrad_x3<3, false>(p, N, grid, lds, s); break;
+            case 2: built = launch_twgrad_x3<2, false>(p, N, grid, lds, s); break;
+            case 1: built = launch_twgrad_x3<1, false>(p, N, grid, lds, s); break;
             default: return fgcn::fail(FGCN_E_BADARG, "%s: %d taps per pass not instantiated", what, nacc);
         }
+        FGCN_REQUIRE(built, FGCN_E_BADARG, "%s: no such kernel form (N=%d, %d per pass)", what, N, nacc);
         return launch_status(what);
     }
     switch (nacc) {
-        case 9: launch_twgrad<9>(p, N, grid, lds, s); break;
-        case 6: launch_twgrad<6>(p, N, grid, lds, s); break;
-        case 5: launch_twgrad<5>(p, N, grid, lds, s); break;
-        case 4: launch_twgrad<4>(p, N, grid, lds, s); break;
-        case 3: launch_twgrad<3>(p, N, grid, lds, s); break;
-        case 2: launch_twgrad<2>(p, N, grid, lds, s); break;
-        case 1: launch_twgrad<1>(p, N, grid, lds, s); break;
+        case 9: built = launch_twgrad<9>(p, N, grid, lds, s); break;
+        case 6: built = launch_twgrad<6>(p, N, grid, lds, s); break;
+        case 5: built = launch_twgrad<5>(p, N, grid, lds, s); break;
+        case 4: built = launch_twgrad<4>(p, N, grid, lds, s); break;
+        case 3: built = launch_twgrad<3>(p, N, grid, lds, s); break;
+        case 2: built = launch_twgrad<2>(p, N, grid, lds, s); break;
+        case 1: built = launch_twgrad<1>(p, N, grid, lds, s); break;
         default: return fgcn::fail(FGCN_E_BADARG, "%s: %d accumulators per wave not instantiated (1-6, 9)", what, nacc);
     }
+    FGCN_REQUIRE(built, FGCN_E_BADARG, "%s: no such kernel form (N=%d, %d per pass)", what, N, nacc);
     return launch_status(what);
 }
 

@@ -19,7 +19,7 @@ SPATIAL_FWD_MAX_C = 256
 
 def fits32(elements: int) -> bool:
     """Whether a float32 tensor of this many elements is addressable with the 32-bit byte offsets of the tile kernels."""
-    return elements * 4 < 0x7FFF0000
+    return elements * 4 < 0x7FFF0000      # BUFFER_LIMIT of csrc/fgcn_common.hpp (fits_buffer)
 
 
 def pw_min_k(rows: int, mode: Optional[str] = None, o=None) -> int:

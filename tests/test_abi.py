@@ -58,6 +58,11 @@ def test_host_side_validation(lib):
     # spatial kernel: more than 256 channels
     assert lib.fgcn_spatial_fwd(p16, p16, p16, None, p16, None, 1, 1, 25, 512, 64, 512, 64, 3, 1, None) == -1
     assert lib.fgcn_spatial_fwd(p16, p16, p16, None, p16, None, 1, 1, 25, 3, 64, 4, 64, 3, 1, None) == -2   # Cin % 4
+    # the fused BatchNorm + activation without its input, its vector or its output (both entry points of the shared body)
+    for args in ((None, p16, None, None, p16), (p16, None, None, None, p16), (p16, p16, None, None, None)):
+        assert lib.fgcn_bn_act(*args, None, 16, 8, 0, 1, 0, None) == -1
+        assert b"null pointer" in lib.fgcn_last_error()
+    assert lib.fgcn_bn_apply_ld(None, p16, p16, 16, 8, 8, None) == -1 and b"null pointer" in lib.fgcn_last_error()
     # bn reduce with a wrong tile count
     assert lib.fgcn_bn_act_bwd_reduce(p16, 0, p16, None, p16, p16, None, None, p16, 7, 1000, 64, 0, 1, 0, None) == -1   # needs 16 tiles
     assert lib.fgcn_elem_tiles(1000) == 16 and lib.fgcn_elem_tiles(10 ** 7) == 1024 and lib.fgcn_rows_gemm_tiles(129) == 2
@@ -94,6 +99,11 @@ def test_host_side_validation(lib):
         assert b"no accumulation" in lib.fgcn_last_error()
         assert lib.fgcn_bn_act_bwd_reduce(p16, 4, None, p16, p16, p16, None, None, p16, 1, 16, 8, 0, 1, 1, None) == -1   # a bfloat16 per-group dout
         assert b"float32 per-group gradient" in lib.fgcn_last_error()
+        # a mask whose only bit names an operand the call does not read selects no typed kernel: refused, not run as the all-bfloat16 form
+        assert lib.fgcn_bn_act(p16, p16, None, None, p16, None, 16, 8, 0, 1, 2, None) == -1                  # b without a residual
+        assert b"half_mask" in lib.fgcn_last_error()
+        assert lib.fgcn_bn_act_bwd_apply(p16, 0, None, p16, p16, p16, None, None, p16, p16, None, 16, 8, 2, 1, 1, 0, 4, None) == -1   # b without db
+        assert b"half_mask" in lib.fgcn_last_error()
     finally:
         lib.fgcn_set_math_mode(mode)
 

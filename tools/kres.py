@@ -20,6 +20,24 @@ def demangle(name):
     return subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
 
 
+def device_asm(src, flags=FLAGS):
+    """The gfx950 assembly of one HIP source, as lines."""
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run([HIPCC, *flags, "-S", "--cuda-device-only", src, "-o", f"{tmp}/o.s"], capture_output=True, text=True)
+        if r.returncode:
+            sys.exit(r.stderr)
+        return open(f"{tmp}/o.s").read().split("\n")
+
+
+def kernels(lines):
+    """{mangled name: the lines from the kernel's label to its .Lfunc_end} (the first s_endpgm may be an early exit)."""
+    out = {}
+    for si in (i for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)):
+        ei = next(i for i in range(si, len(lines)) if lines[i].startswith(".Lfunc_end"))
+        out[lines[si].split(":")[0]] = lines[si:ei]
+    return out
+
+
 def main():
     stem = sys.argv[1]
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
@@ -34,19 +52,11 @@ def main():
                r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)")
         for m in re.finditer(pat, r.stderr, re.S):
             res[m.group(1)] = m.groups()[1:]
-        r = subprocess.run([HIPCC, *FLAGS, "-S", "--cuda-device-only", src, "-o", f"{tmp}/o.s"],
-                           capture_output=True, text=True)
-        if r.returncode:
-            sys.exit(r.stderr)
-        lines = open(f"{tmp}/o.s").read().split("\n")
-    starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)]
-    for si in starts:
-        mangled = lines[si].split(":")[0]
+    for mangled, text in kernels(device_asm(src)).items():
         name = demangle(mangled)
         if flt and flt not in name:
             continue
-        ei = next(i for i in range(si, len(lines)) if lines[i].startswith(".Lfunc_end"))    # (the first s_endpgm may be an early exit)
-        body = [l for l in lines[si:ei] if l.startswith("\t") and not l.startswith("\t.") and not l.startswith("\t;")]
+        body = [l for l in text if l.startswith("\t") and not l.startswith("\t.") and not l.startswith("\t;")]
         cnt = lambda p: sum(1 for l in body if re.search(p, l))
         v, a, scr, occ, lds = res.get(mangled, ("?",) * 5)
         print(f"{name[:76]:76s} vgpr={v:>3} agpr={a:>3} scratch={scr:>3} occ={occ} lds={lds:>6} | instr={len(body):5d} "
