@@ -196,6 +196,10 @@ SIGNATURES = {
     "fgcn_optim_step_groups_guarded": (_I, [_P, _P, _P, _P, _LL, _I, C.POINTER(OptimGroup), _I, _P, _I, _F, _D, _I, _P, _I, _P, _P, _P]),
     "fgcn_classify_state_bytes": (_LL, [_I]),
     "fgcn_classify_update": (_I, [_P, _P, _P, _P, _P, _LL, _LL, _I, _I, _I, _I, _P]),
+    "fgcn_philox4x32_10": (_I, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "fgcn_dropout_fwd": (_I, [_P, _P, _P, _LL, _F, C.c_ulonglong, C.c_uint, _P, _P]),
+    "fgcn_dropout_bwd": (_I, [_P, _P, _P, _LL, _F, _P]),
+    "fgcn_rng_advance": (_I, [_P, _P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

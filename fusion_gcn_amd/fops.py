@@ -788,4 +788,70 @@ def joined_vector(forms: ParamForms, name: str, params: Sequence[torch.Tensor]) 
     return _JoinedVector.apply(packed, *params)
 
 
+# ---- dropout with masks from libfgcn's counter-based generator --------------------------------------------
+class _Dropout(torch.autograd.Function):
+    """y = x / (1 - p) where kept (``FusedDropout.draw``: fgcn_dropout_fwd, then fgcn_rng_advance); the backward reads the kept-bit image."""
+
+    @staticmethod
+    def forward(ctx, x, state, p: float):
+        y, mask = state.draw(x, p)
+        ctx.p = p
+        ctx.save_for_backward(mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_out):
+        mask, = ctx.saved_tensors
+        return ops.dropout_bwd(d_out.contiguous(), mask, ctx.p), None, None
+
+
+def dropout(x: torch.Tensor, state: "FusedDropout", p: float, training: bool) -> torch.Tensor:
+    """Differentiable dropout of a float32 device tensor (numel % 4 == 0) whose masks come from ``state`` = (seed, site, device-side
+    step counter): a pure function of those and the element index, so two runs from one state agree bit for bit and a recorded
+    step draws new masks per replay.  Not training, or p == 0: ``x`` itself, nothing is launched.  p == 1: zeros, as torch's."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    if not training or p == 0.0:
+        return x
+    if p == 1.0:
+        return x * 0.0
+    return _Dropout.apply(x.contiguous(), state, float(p))
+
+
+class FusedDropout(torch.nn.Dropout):
+    """``nn.Dropout`` on libfgcn's generator.  It stays an ``nn.Dropout`` (what GraphStep looks for to know that a recorded step is
+    not comparable with an eager one) and adds no state-dict key: the step counter is a NON-persistent one-word uint64 buffer -- it
+    moves with the module, GraphStep rolls it back with the other buffers after its warm-up, and a checkpoint carries neither it
+    nor the seed (as the reference's carries no generator state).
+
+    ``seed``: drawn from torch's default CPU generator on the first training forward (so ``torch.manual_seed`` fixes it), or set by
+    ``reseed``.  ``site``: a second stream selector under one seed.  ``keep_mask``: the kept-bit image of the last training forward
+    (bit i & 7 of byte i >> 3 of the flat tensor), a side output for tests and tools."""
+
+    def __init__(self, p: float = 0.5):
+        super().__init__(p, inplace=False)
+        self.register_buffer("step", torch.zeros(1, dtype=torch.uint64), persistent=False)
+        self.seed: Optional[int] = None
+        self.site = 0
+        self.keep_mask: Optional[torch.Tensor] = None
+
+    def reseed(self, seed: int, site: int = 0) -> None:
+        """Set the seed (and site) explicitly and start counting steps from zero again."""
+        self.seed, self.site = int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF
+        with torch.no_grad():
+            self.step.view(torch.int64).zero_()
+
+    def draw(self, x: torch.Tensor, p: Optional[float] = None):
+        """One training-mode application without autograd: -> (y, keep_mask); the step counter advances behind it."""
+        if self.seed is None:            # (a host-side draw: never part of a capture's device work)
+            self.seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+        y, mask = ops.dropout_fwd(x, self.p if p is None else p, self.seed, self.site, self.step)
+        ops.rng_advance(self.step)
+        self.keep_mask = mask
+        return y, mask
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return dropout(x, self, self.p, self.training)
+
+
 ops.bind_all_functions(globals())     # every Function's backward runs in its forward's library context (ops.Context)

@@ -16,6 +16,11 @@ static adjacency has 8 .. 30 non-zeros per row, its CSR form is built once from 
 transpose, no padding) and the residual + ReLU + sign image are the gather's epilogue; the data gradient is the same kernel over adj^T's
 CSR form.  Parameters, buffers and state-dict keys are those of the dense route.
 
+With ``dropout > 0`` the layer computes the reference's ``relu(dropout(conv(x) . adj^T) + residual(x))`` in training: ``self.dropout`` is a
+``fops.FusedDropout`` (masks from libfgcn's counter-based generator; no state-dict key), applied to the node-major
+``(B, V, O)`` aggregate -- on the dense route between the transpose back and ``fgcn_bn_act``; on the sparse route the gather runs without its
+epilogue and the dense route's ``fgcn_bn_act`` call follows the dropout.  In eval mode, and without dropout, the calls are the ones above.
+
 ``AGCNGraphConvolution`` (:56-113: per-sample V x V attention) reuses the same pieces with per-sample matrices as the GEMM
 weight and a row softmax on the transposed scores (``fgcn_row_softmax_*``); see ``_AgcnConv1dFunction``.
 """
@@ -30,6 +35,7 @@ import torch.nn as nn
 
 from ... import ops
 from ...block import pw_gemm
+from ...fops import FusedDropout
 
 
 def _r(c: int, m: int) -> int:
@@ -81,6 +87,7 @@ class _GraphConv1dFunction(torch.autograd.Function):
         O, Fin = weight.shape[0], weight.shape[1]
         dev = x.device
         sparse = mod.takes_sparse_route()
+        drop = mod.dropout if (train and mod.dropout is not None and mod.dropout.p > 0) else None
         with torch.no_grad():
             w = torch.zeros((1, Fp, O), device=dev, dtype=torch.float32)
             w[0, :Fin] = weight.view(O, Fin).t()
@@ -89,14 +96,20 @@ class _GraphConv1dFunction(torch.autograd.Function):
             W["w_s3"] = _split_form(mod, "w", w)        # split form of the current products (bf16x3 / f16x2)
         support = torch.empty((B, V, O), device=dev, dtype=torch.float32)
         pw_gemm(_rows4(x), W, "w", _rows4(support), K=Fp, N=O, bias=bias)
-        main = None
-        if not sparse:
+        main = keep = None
+        if sparse and drop is not None:
+            # dropout sits between the aggregation and the residual: the gather runs without its epilogue, then the dense route's epilogue pass
+            main = ops.graph_spmm(support, mod._csr_forms()["adj"])
+        elif not sparse:
             A = mod._adjacency_forms()
             Vp = A["Vp"]
             sup_fm = ops.transpose(support, Vp)                               # (B, O, Vp), zero padding columns
             out_fm = torch.empty((B, O, Vp), device=dev, dtype=torch.float32)
             pw_gemm(_rows4(sup_fm), A, "adjT", _rows4(out_fm), K=Vp, N=Vp)
             main = ops.transpose_into(out_fm, V)                              # (B, V, O)
+        if main is not None:
+            if drop is not None:
+                main, keep = drop.draw(main)                                  # the mask index is that of the node-major (B, V, O) tensor
             vec_id = _identity_vec(O, dev)
         r = vec_r = None
         if mod.res_kind == "conv":
@@ -113,7 +126,7 @@ class _GraphConv1dFunction(torch.autograd.Function):
                      else ops.bn_eval_coeffs(res_g, res_beta, bn.running_mean, bn.running_var))
             if train:
                 bn.num_batches_tracked += 1
-        if sparse:
+        if main is None:
             # the aggregation as a gather over adj's CSR form with the residual and the ReLU in its epilogue: no transposes, no bn_act pass
             # (mask None when O % 8 != 0: the backward then gates from `out`)
             csr = mod._csr_forms()["adj"]
@@ -127,12 +140,13 @@ class _GraphConv1dFunction(torch.autograd.Function):
             out, mask = ops.bn_act(r, vec_r, main, None, relu=True, sign_mask=True)   # relu(BN(r) + main)
         ctx.sparse = sparse
         ctx.mod, ctx.train, ctx.W = mod, train, W
-        ctx.save_for_backward(x, out, mask, r, vec_r, weight, res_w)
+        ctx.drop_p = drop.p if drop is not None else 0.0
+        ctx.save_for_backward(x, out, mask, r, vec_r, weight, res_w, keep)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        x, out, mask, r, vec_r, weight, res_w = ctx.saved_tensors
+        x, out, mask, r, vec_r, weight, res_w, keep = ctx.saved_tensors
         mod, train, W = ctx.mod, ctx.train, ctx.W
         B, V, Fp = x.shape
         O, Fin = weight.shape[0], weight.shape[1]
@@ -158,6 +172,8 @@ class _GraphConv1dFunction(torch.autograd.Function):
             if "wr_s3" in W and O % 32 == 0:
                 Wt["wr_t_s3"] = _split_form(mod, "wr_t", Wt["wr_t"])
             pw_gemm(_rows4(dr), Wt, "wr_t", _rows4(dx), K=O, N=Fp)
+        if keep is not None:
+            ops.dropout_bwd(d_main, keep, ctx.drop_p, out=d_main)
         # main path: d_support = d_main . adj  (feature-major; sparse route: node-major gather), then the conv's data and weight gradients
         if ctx.sparse:
             d_support = ops.graph_spmm(d_main, mod._csr_forms()["adjT"])      # a gather over adj^T's rows: no atomics, no transposes
@@ -203,9 +219,8 @@ class STGCNGraphConvolution(nn.Module):
         if adj.is_sparse:
             adj = adj.to_dense()
         self.register_buffer("adj", adj.to(torch.float32))
-        self.dropout = nn.Dropout(dropout) if dropout > 0 else None
-        if dropout > 0:
-            raise NotImplementedError("dropout inside the fused graph convolution is not built (reference default: 0)")
+        # the reference's nn.Dropout on conv(x) . adj^T (graph_convolution.py:45-51), with masks from libfgcn's generator
+        self.dropout = FusedDropout(dropout) if dropout > 0 else None
         if not residual:
             self.res_kind, self.residual = "none", None
         elif in_features == out_features:

@@ -60,7 +60,9 @@ class SpatialTemporal_MS_GCN(nn.Module):
         if self.A_scales.device != x.device:
             self.A_scales = self.A_scales.to(x.device)
         agg = fops.node_mix_params(x, self._forms, "A", self.A_scales, self.A_res, self.num_scales)
-        conv, bn, _ = self.mlp.layers
+        *drop, conv, bn, _ = self.mlp.layers
+        if drop:                                                            # MLP(dropout=): a FusedDropout in front of the conv
+            agg = drop[0](agg)
         y, part = fops.conv_params(agg, self._forms, "mlp", [conv.weight], [conv.bias], stats=bn.training, zero_bias_grad=bn.training,
                                    scales=self.num_scales)
         return fops.bn_act(y, part, bn, relu=is_relu(self.act))            # linear MLP, no residual, then the block's activation

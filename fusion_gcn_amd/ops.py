@@ -1876,3 +1876,50 @@ def col_moments(x: torch.Tensor) -> torch.Tensor:
     check(lib.fgcn_bn_act_bwd_reduce(_p(x), 0, None, None, _p(x), _p(vec), None, None, _p(partials), tiles, rows, C, 0, 0, 0, _stream()),
           "fgcn_bn_act_bwd_reduce")
     return partials[:, :2].contiguous()
+
+
+# ---- dropout from the counter-based generator (fgcn_dropout_fwd / _bwd, fgcn_rng_advance) -----------------------
+def _chk_step(step: torch.Tensor, name: str) -> None:
+    if not isinstance(step, torch.Tensor) or not step.is_cuda or step.dtype != torch.uint64 or step.numel() != 1:
+        raise _lib.FgcnError(f"{name}: expected a one-word uint64 CUDA tensor (the step counter), got "
+                             f"{getattr(step, 'dtype', type(step))} {getattr(step, 'device', '')}")
+
+
+def dropout_fwd(x: torch.Tensor, p: float, seed: int, site: int, step: torch.Tensor):
+    """-> (y, keep_mask): y = x / (1 - p) where kept, 0 elsewhere; element i is kept iff word i & 3 of Philox4x32-10 at counter
+    (i >> 2, site, step) under the key ``seed`` is >= p * 2^32 (include/fgcn.h).  keep_mask: the kept bits as a uint8 image,
+    ceil(numel / 8) bytes in ``bn_act``'s sign-image layout.  ``step``: a one-word uint64 device tensor, read and left as it is
+    (``rng_advance`` bumps it).  x: contiguous float32 on the device, numel % 4 == 0; 0 <= p < 1."""
+    ensure_device()
+    _chk(x, "dropout_fwd.x")
+    _chk_step(step, "dropout_fwd.step")
+    n = x.numel()
+    y = torch.empty_like(x)
+    mask = torch.empty((n + 7) // 8, device=x.device, dtype=torch.uint8)
+    check(_lib.load().fgcn_dropout_fwd(_p(x), _p(y), _p(mask), n, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF,
+                                       step.data_ptr(), _stream()), "fgcn_dropout_fwd")
+    return y, mask
+
+
+def dropout_bwd(dy: torch.Tensor, keep_mask: torch.Tensor, p: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx = dy / (1 - p) where ``keep_mask`` (``dropout_fwd``'s image) has the element's bit, 0 elsewhere.  ``out`` may be ``dy`` itself."""
+    ensure_device()
+    _chk(dy, "dropout_bwd.dy")
+    n = dy.numel()
+    if not keep_mask.is_cuda or keep_mask.dtype != torch.uint8 or not keep_mask.is_contiguous() or keep_mask.numel() != (n + 7) // 8:
+        raise _lib.FgcnError(f"dropout_bwd.keep_mask: expected {(n + 7) // 8} contiguous uint8 on the device, got {keep_mask.dtype} "
+                             f"{keep_mask.device} numel={keep_mask.numel()}")
+    if out is None:
+        out = torch.empty_like(dy)
+    _chk(out, "dropout_bwd.out")
+    if out.numel() != n:
+        raise _lib.FgcnError(f"dropout_bwd.out: {out.numel()} elements for a gradient of {n}")
+    check(_lib.load().fgcn_dropout_bwd(_p(dy), _p(keep_mask), _p(out), n, float(p), _stream()), "fgcn_dropout_bwd")
+    return out
+
+
+def rng_advance(step: torch.Tensor) -> None:
+    """step += 1 on the device, stream-ordered behind whatever read it."""
+    ensure_device()
+    _chk_step(step, "rng_advance.step")
+    check(_lib.load().fgcn_rng_advance(step.data_ptr(), _stream()), "fgcn_rng_advance")

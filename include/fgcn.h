@@ -941,6 +941,34 @@ long long fgcn_classify_state_bytes(int classes);   /* 0 for classes outside [1,
 int fgcn_classify_update(const float* logits, const long long* labels, const float* loss, void* state, int* pred_out,
                          long long pred_offset, long long pred_capacity, int rows, int classes, int ld, int k, void* stream);
 
+/* Dropout with masks from a counter-based generator (fops.dropout / FusedDropout: the IMU graph convolution's and the MS-G3D MLP's
+ * `dropout=`).  The masks are a pure function of (seed, site, *step, element index): a test recomputes them on
+ * the host bit for bit, two runs from one state draw the same masks, and a recorded HIP graph draws new ones on every replay
+ * without the host, because the step counter is a word in device memory.
+ *
+ * Philox4x32-10 (Salmon et al., SC'11): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, ten
+ * rounds; one round maps (c0, c1, c2, c3), (k0, k1) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)) and the key
+ * is bumped after each round.  fgcn_philox4x32_10 is the HOST copy of the function the kernel calls (no device is touched);
+ * ctr = key = 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.  FGCN_E_BADARG: a null pointer.
+ *
+ * fgcn_dropout_fwd, float32 x -> y, n elements: element i belongs to group g = i >> 2 and uses word i & 3 of
+ *     philox(ctr = {(unsigned)g, site, lo32(*step), hi32(*step)}, key = {lo32(seed), hi32(seed)});
+ * it is kept iff word >= thr, thr = (unsigned)((double)p * 4294967296.0); y[i] = kept ? x[i] * s : 0.0f with
+ * s = 1.0f / (1.0f - p) formed in float32 on the host.  keep_mask (ceil(n / 8) bytes) receives bit i & 7 of byte i >> 3 = kept,
+ * unused tail bits zero: the bit layout of fgcn_bn_act's sign image.  `step` is a device pointer to one 8-byte word that the call
+ * reads and does not change.  FGCN_E_BADARG before any launch: n <= 0, n % 4 != 0, n >= 2^34, p < 0, p >= 1 or not finite, a null
+ * pointer, x / y not 16-byte aligned (step: 8-byte).  Float32 storage only.
+ *
+ * fgcn_dropout_bwd: dx[i] = kept ? dy[i] * s : 0.0f from the bit image; dx == dy (in place) is allowed.  Same refusals.
+ *
+ * fgcn_rng_advance: *step += 1 by one lane, in a launch of its own: stream-ordered behind the forward that read the word, so no
+ * workgroup of that forward sees the new value, and the pair captures into a HIP graph as a straight line. */
+int fgcn_philox4x32_10(const unsigned ctr[4], const unsigned key[2], unsigned out[4]);
+int fgcn_dropout_fwd(const float* x, float* y, unsigned char* keep_mask, long long n, float p, unsigned long long seed, unsigned site,
+                     const unsigned long long* step, void* stream);
+int fgcn_dropout_bwd(const float* dy, const unsigned char* keep_mask, float* dx, long long n, float p, void* stream);
+int fgcn_rng_advance(unsigned long long* step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
