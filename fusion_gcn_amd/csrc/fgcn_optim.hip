@@ -22,19 +22,29 @@ namespace fgcn {
 struct OptimP {
     float* p;
     const float* g;
-    float* m;     // SGD: momentum buffer; Adam: exp_avg
+    float* m;     // SGD: momentum buffer; Adam: exp_avg; ASGD: ax, the averaged iterate
     float* v;     // Adam: exp_avg_sq
     long long n4;
     float lr, wd, grad_scale;
     float beta1, beta2, eps, step_size, bc2_sqrt;      // Adam / AdamW
-    float momentum, dampening;                         // SGD
+    float momentum, dampening;                         // SGD; ASGD: the step's eta, mu
     int nesterov, first_step;
+    float c0;                                          // ASGD: 1 - lambd * eta (asgd_decay), set by the kernel
     const unsigned long long* guard;                   // GUARDED: enum fgcn_guard_word, written by optim_guard_decide_kernel
 };
 
 __device__ __forceinline__ double guard_f64(const unsigned long long* w, int word) { return __builtin_bit_cast(double, w[word]); }
 
-// kind 0: SGD (torch/optim/sgd.py), 1: Adam (L2 weight decay folded into the gradient), 2: AdamW (decoupled decay)
+// ASGD's decay factor as torch's Python scalars give it: the product and the difference each rounded to double, then to float32
+// (beta1 carries lambd, momentum eta).  Wave-uniform.
+__device__ __forceinline__ float asgd_decay(float lambd, float eta) {
+#pragma clang fp contract(off)
+    const double prod = (double)lambd * (double)eta;
+    return (float)(1.0 - prod);
+}
+
+// kind 0: SGD (torch/optim/sgd.py), 1: Adam (L2 weight decay folded into the gradient), 2: AdamW (decoupled decay),
+// 3: ASGD (torch/optim/asgd.py, _single_tensor_asgd: decay, step, then the running average ax in state1)
 // One 16-byte group i of the flat buffers with the scalars of q (wave-uniform).
 template <int KIND>
 __device__ __forceinline__ void optim_update4(const OptimP& q, long long i) {
@@ -49,6 +59,18 @@ __device__ __forceinline__ void optim_update4(const OptimP& q, long long i) {
             g = q.nesterov ? g + buf * q.momentum : buf;
         }
         p -= g * q.lr;
+    } else if (KIND == 3) {
+#pragma clang fp contract(off)
+        const float eta = q.momentum, mu = q.dampening;
+        f32x4 ax = p;
+        if (mu != 1.f) ax = *reinterpret_cast<const f32x4*>(q.m + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (q.wd != 0.f) g[e] = __builtin_fmaf(p[e], q.wd, g[e]);      // grad.add(param, alpha=wd): p before the decay
+            p[e] = __builtin_fmaf(-eta, g[e], p[e] * q.c0);                 // param.mul_(c0); param.add_(grad, alpha=-eta)
+            ax[e] = mu == 1.f ? p[e] : ax[e] + (p[e] - ax[e]) * mu;         // ax.copy_(param) / ax.add_(param.sub(ax).mul_(mu))
+        }
+        *reinterpret_cast<f32x4*>(q.m + i * 4) = ax;
     } else {
         if (KIND == 1 && q.wd != 0.f) g += p * q.wd;
         if (KIND == 2) p *= 1.f - q.lr * q.wd;
@@ -77,6 +99,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(OptimP q) {
         q.step_size = (float)guard_f64(q.guard, FGCN_GUARD_STEP_SIZE);
         q.bc2_sqrt = (float)guard_f64(q.guard, FGCN_GUARD_BC2_SQRT);
     }
+    if (KIND == 3) q.c0 = asgd_decay(q.beta1, q.momentum);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < q.n4; i += (long long)gridDim.x * blockDim.x)
         optim_update4<KIND>(q, i);
 }
@@ -88,6 +111,7 @@ struct OptimGroupsP {
     OptimP base;                                       // buffers, n4, grad_scale, first_step (unguarded), guard
     const int* tiles;
     const double* sched;                               // GUARDED: {step_size, bc2_sqrt} per group, written by the decision launch
+                                                       // (ASGD: {eta_use, mu_use, eta_next, mu_next} per group)
     int ngroups;
     fgcn_optim_group grp[FGCN_OPT_MAX_GROUPS];
     float step_size[FGCN_OPT_MAX_GROUPS], bc2_sqrt[FGCN_OPT_MAX_GROUPS];      // unguarded Adam: from the host-side step count
@@ -109,9 +133,15 @@ __global__ __launch_bounds__(256) void optim_step_groups_kernel(OptimGroupsP a) 
         if (q.guard[FGCN_GUARD_APPLY] == 0) return;
         q.grad_scale = (float)((double)q.grad_scale * guard_f64(q.guard, FGCN_GUARD_COEF));
         q.first_step = (int)q.guard[FGCN_GUARD_FIRST_STEP];
-        q.step_size = (float)a.sched[2 * gi];
-        q.bc2_sqrt = (float)a.sched[2 * gi + 1];
+        if (KIND == 3) {
+            q.momentum = (float)a.sched[4 * gi];
+            q.dampening = (float)a.sched[4 * gi + 1];
+        } else {
+            q.step_size = (float)a.sched[2 * gi];
+            q.bc2_sqrt = (float)a.sched[2 * gi + 1];
+        }
     }
+    if (KIND == 3) q.c0 = asgd_decay(q.beta1, q.momentum);
     for (int j = threadIdx.x; j < count4; j += 256) optim_update4<KIND>(q, (long long)start4 + j);
 }
 
@@ -222,6 +252,30 @@ __global__ __launch_bounds__(GN_THREADS) void optim_guard_decide_groups_kernel(G
     }
 }
 
+// ASGD's decision: the values torch computed after the step before become this step's, and the next step's come from the new STEP and
+// the groups' current lr (torch/optim/asgd.py: new_eta, new_mu, each rounded through float32).  Nothing moves when the step is skipped.
+struct GuardAsgdP {
+    GuardP d;                                                 // (d.lr / d.beta1 / d.beta2 unused, d.adam 0)
+    double* sched;                                            // {eta_use, mu_use, eta_next, mu_next} per group
+    int ngroups;
+    double lr[FGCN_OPT_MAX_GROUPS], lambd[FGCN_OPT_MAX_GROUPS], alpha[FGCN_OPT_MAX_GROUPS], t0[FGCN_OPT_MAX_GROUPS];
+};
+
+__global__ __launch_bounds__(GN_THREADS) void optim_guard_decide_asgd_kernel(GuardAsgdP a) {
+    const unsigned long long step = guard_decide(a.d);
+    if (!step) return;
+    const double t = (double)step;
+    for (int g = 0; g < a.ngroups; ++g) {
+#pragma clang fp contract(off)
+        double* s = a.sched + 4 * g;
+        s[0] = s[2];
+        s[1] = s[3];
+        const double over = t - a.t0[g];
+        s[2] = (double)(float)(a.lr[g] / pow(1.0 + a.lambd[g] * a.lr[g] * t, a.alpha[g]));
+        s[3] = (double)(float)(1.0 / (over > 1.0 ? over : 1.0));
+    }
+}
+
 }  // namespace fgcn
 
 using namespace fgcn;
@@ -234,7 +288,7 @@ static int optim_prepare(OptimP& q, const char* who, float* params, const float*
     FGCN_REQUIRE(params && grads && n > 0, FGCN_E_BADARG, "%s: null pointer or empty buffer", who);
     FGCN_REQUIRE(n % 4 == 0 && aligned16(params) && aligned16(grads), FGCN_E_ALIGN,
                  "%s: buffers must be 16-byte aligned and a multiple of 4 floats long (n=%lld)", who, n);
-    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ADAMW, FGCN_E_BADARG, "%s: kind %d", who, kind);
+    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ASGD, FGCN_E_BADARG, "%s: kind %d", who, kind);
     FGCN_REQUIRE(!step || *step >= 1, FGCN_E_BADARG, "%s: step counts from 1 (got %lld)", who, step ? *step : 0ll);
     FGCN_REQUIRE(lr >= 0.f && weight_decay >= 0.f, FGCN_E_BADARG, "%s: negative lr / weight_decay", who);
     q = OptimP{};
@@ -246,6 +300,14 @@ static int optim_prepare(OptimP& q, const char* who, float* params, const float*
         FGCN_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), FGCN_E_BADARG,
                      "%s: Nesterov momentum requires a momentum and zero dampening", who);
         q.momentum = momentum; q.dampening = dampening; q.nesterov = nesterov; q.first_step = step && *step == 1;
+    } else if (kind == FGCN_OPT_ASGD) {      // beta1, beta2, eps carry lambd, alpha, t0; momentum, dampening the step's eta, mu
+        FGCN_REQUIRE(state1 && aligned16(state1), FGCN_E_BADARG, "%s: kind 3 (ASGD) needs ax, the averaged iterate, in state1", who);
+        FGCN_REQUIRE(!state2, FGCN_E_BADARG, "%s: kind 3 (ASGD) keeps one state buffer: state2 must be NULL", who);
+        FGCN_REQUIRE(beta1 >= 0.f && std::isfinite(beta2) && std::isfinite(eps), FGCN_E_BADARG,
+                     "%s: ASGD: negative lambd or alpha / t0 not finite", who);
+        FGCN_REQUIRE(momentum >= 0.f && dampening > 0.f && dampening <= 1.f, FGCN_E_BADARG,
+                     "%s: ASGD: eta must be >= 0 and mu in (0, 1] (got %g, %g)", who, (double)momentum, (double)dampening);
+        q.beta1 = beta1; q.momentum = momentum; q.dampening = dampening;
     } else {
         FGCN_REQUIRE(state1 && state2 && aligned16(state1) && aligned16(state2), FGCN_E_BADARG,
                      "%s: Adam needs exp_avg and exp_avg_sq", who);
@@ -267,7 +329,8 @@ static void optim_launch(const OptimP& q, int kind, hipStream_t s) {
     dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
     if (kind == FGCN_OPT_SGD) hipLaunchKernelGGL((optim_step_kernel<0, GUARDED>), grid, dim3(256), 0, s, q);
     else if (kind == FGCN_OPT_ADAM) hipLaunchKernelGGL((optim_step_kernel<1, GUARDED>), grid, dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((optim_step_kernel<2, GUARDED>), grid, dim3(256), 0, s, q);
+    else if (kind == FGCN_OPT_ADAMW) hipLaunchKernelGGL((optim_step_kernel<2, GUARDED>), grid, dim3(256), 0, s, q);
+    else hipLaunchKernelGGL((optim_step_kernel<3, false>), grid, dim3(256), 0, s, q);      // (ASGD has no single-group guarded form)
 }
 
 extern "C" int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
@@ -299,7 +362,7 @@ static int guard_prepare(GuardP& d, const char* who, long long n, int kind, doub
     FGCN_REQUIRE(max_norm >= 0.0, FGCN_E_BADARG, "%s: max_norm must be a number >= 0 (0: no clipping)", who);
     d = GuardP{};
     d.partials = partials; d.guard = static_cast<unsigned long long*>(guard); d.n_partials = n_partials;
-    d.skip_nonfinite = skip_nonfinite != 0; d.adam = kind != FGCN_OPT_SGD;
+    d.skip_nonfinite = skip_nonfinite != 0; d.adam = kind == FGCN_OPT_ADAM || kind == FGCN_OPT_ADAMW;
     d.max_norm = max_norm;
     return FGCN_OK;
 }
@@ -308,6 +371,8 @@ extern "C" int fgcn_optim_step_guarded(float* params, const float* grads, float*
                                        float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
                                        float momentum, float dampening, int nesterov, double max_norm, int skip_nonfinite,
                                        double* partials, int n_partials, void* guard, void* stream) {
+    FGCN_REQUIRE(kind != FGCN_OPT_ASGD, FGCN_E_BADARG,
+                 "optim_step_guarded: kind 3 (ASGD) keeps eta / mu in group_sched: call fgcn_optim_step_groups_guarded with one group");
     OptimP q;
     int rc = optim_prepare(q, "optim_step_guarded", params, grads, state1, state2, n, kind, lr, weight_decay, grad_scale, beta1,
                            beta2, eps, momentum, dampening, nesterov, nullptr);
@@ -334,7 +399,7 @@ static int optim_groups_prepare(OptimGroupsP& a, const char* who, float* params,
     FGCN_REQUIRE(n % 4 == 0 && aligned16(params) && aligned16(grads), FGCN_E_ALIGN,
                  "%s: buffers must be 16-byte aligned and a multiple of 4 floats long (n=%lld)", who, n);
     FGCN_REQUIRE(n / 4 <= 0x7fffffffll, FGCN_E_BADARG, "%s: the tile table indexes 16-byte groups with an int (n=%lld)", who, n);
-    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ADAMW, FGCN_E_BADARG, "%s: kind %d", who, kind);
+    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ASGD, FGCN_E_BADARG, "%s: kind %d", who, kind);
     FGCN_REQUIRE(!step || *step >= 1, FGCN_E_BADARG, "%s: step counts from 1 (got %lld)", who, step ? *step : 0ll);
     FGCN_REQUIRE(ngroups >= 1 && ngroups <= FGCN_OPT_MAX_GROUPS, FGCN_E_BADARG, "%s: 1 to %d parameter groups (got %d)", who,
                  FGCN_OPT_MAX_GROUPS, ngroups);
@@ -346,7 +411,10 @@ static int optim_groups_prepare(OptimGroupsP& a, const char* who, float* params,
     q.p = params; q.g = grads; q.m = state1; q.v = state2; q.n4 = n / 4; q.grad_scale = grad_scale;
     q.first_step = kind == FGCN_OPT_SGD && step && *step == 1;
     a.tiles = tiles; a.ngroups = ngroups;
-    if (kind != FGCN_OPT_SGD)
+    if (kind == FGCN_OPT_ASGD) {
+        FGCN_REQUIRE(state1 && aligned16(state1), FGCN_E_BADARG, "%s: kind 3 (ASGD) needs ax, the averaged iterate, in state1", who);
+        FGCN_REQUIRE(!state2, FGCN_E_BADARG, "%s: kind 3 (ASGD) keeps one state buffer: state2 must be NULL", who);
+    } else if (kind != FGCN_OPT_SGD)
         FGCN_REQUIRE(state1 && state2 && aligned16(state1) && aligned16(state2), FGCN_E_BADARG, "%s: Adam needs exp_avg and exp_avg_sq",
                      who);
     for (int g = 0; g < ngroups; ++g) {
@@ -357,6 +425,13 @@ static int optim_groups_prepare(OptimGroupsP& a, const char* who, float* params,
                          "%s: group %d: SGD with momentum needs the momentum buffer", who, g);
             FGCN_REQUIRE(!h.nesterov || (h.momentum > 0.f && h.dampening == 0.f), FGCN_E_BADARG,
                          "%s: group %d: Nesterov momentum requires a momentum and zero dampening", who, g);
+        } else if (kind == FGCN_OPT_ASGD) {      // beta1, beta2, eps carry lambd, alpha, t0
+            FGCN_REQUIRE(h.beta1 >= 0.f && std::isfinite(h.beta2) && std::isfinite(h.eps), FGCN_E_BADARG,
+                         "%s: group %d: ASGD: negative lambd or alpha / t0 not finite", who, g);
+            // momentum, dampening carry the step's eta, mu on the unguarded path (the guarded one reads group_sched)
+            FGCN_REQUIRE(!step || (h.momentum >= 0.f && h.dampening > 0.f && h.dampening <= 1.f), FGCN_E_BADARG,
+                         "%s: group %d: ASGD: eta must be >= 0 and mu in (0, 1] (got %g, %g)", who, g, (double)h.momentum,
+                         (double)h.dampening);
         } else {
             FGCN_REQUIRE(h.beta1 >= 0.f && h.beta1 < 1.f && h.beta2 >= 0.f && h.beta2 < 1.f && h.eps >= 0.f, FGCN_E_BADARG,
                          "%s: group %d: betas / eps out of range", who, g);
@@ -376,7 +451,8 @@ static void optim_groups_launch(const OptimGroupsP& a, int kind, int ntiles, hip
     const dim3 grid((unsigned)ntiles);
     if (kind == FGCN_OPT_SGD) hipLaunchKernelGGL((optim_step_groups_kernel<0, GUARDED>), grid, dim3(256), 0, s, a);
     else if (kind == FGCN_OPT_ADAM) hipLaunchKernelGGL((optim_step_groups_kernel<1, GUARDED>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((optim_step_groups_kernel<2, GUARDED>), grid, dim3(256), 0, s, a);
+    else if (kind == FGCN_OPT_ADAMW) hipLaunchKernelGGL((optim_step_groups_kernel<2, GUARDED>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((optim_step_groups_kernel<3, GUARDED>), grid, dim3(256), 0, s, a);
 }
 
 extern "C" int fgcn_optim_step_groups(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
@@ -411,7 +487,16 @@ extern "C" int fgcn_optim_step_groups_guarded(float* params, const float* grads,
     }
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(grad_sqsum_kernel, dim3((unsigned)n_partials), dim3(GN_THREADS), 0, s, grads, a.base.n4, grad_scale, partials);
-    hipLaunchKernelGGL(optim_guard_decide_groups_kernel, dim3(1), dim3(GN_THREADS), 0, s, d);
+    if (kind == FGCN_OPT_ASGD) {
+        GuardAsgdP e{};
+        e.d = d.d; e.sched = group_sched; e.ngroups = ngroups;
+        for (int g = 0; g < ngroups; ++g) {
+            e.lr[g] = (double)groups[g].lr; e.lambd[g] = (double)groups[g].beta1;
+            e.alpha[g] = (double)groups[g].beta2; e.t0[g] = (double)groups[g].eps;
+        }
+        hipLaunchKernelGGL(optim_guard_decide_asgd_kernel, dim3(1), dim3(GN_THREADS), 0, s, e);
+    } else
+        hipLaunchKernelGGL(optim_guard_decide_groups_kernel, dim3(1), dim3(GN_THREADS), 0, s, d);
     optim_groups_launch<true>(a, kind, ntiles, s);
     return launch_status("optim_step_groups_guarded");
 }

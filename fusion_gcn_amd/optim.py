@@ -1,6 +1,6 @@
 """The step after the hot path: one fused parameter update over flat buffers.
 
-The reference builds ``torch.optim.{SGD, Adam, AdamW}(model.parameters(), lr, **optimizer_args)`` and an optional
+The reference builds ``torch.optim.{SGD, ASGD, Adam, AdamW}(model.parameters(), lr, **optimizer_args)`` and an optional
 ``torch.optim.lr_scheduler`` over it (torch_src/session_helper.py:48-89; ADAM + weight_decay 0.01 + ``cawr`` in
 config/utd-mhad/skeleton/agcn.yaml:15-22) and calls ``optimizer.step()`` after every batch (session/session.py:176-183):
 one small launch chain per parameter tensor, 274 tensors.  ``FlatOptimizer`` keeps that interface -- it *is* a
@@ -18,22 +18,27 @@ Parameter groups (a list of dicts, as every ``torch.optim.Optimizer`` takes; ``c
 ...}])`` from a config) keep all of that: still one update launch (``fgcn_optim_step_groups``), which group an element belongs to
 comes from a tile table built and uploaded once at construction, the groups' scalars travel by value with every launch.
 
+ASGD (``torch.optim.ASGD``) keeps its product, the averaged iterate ``ax``, in ``state1``; ``FlatOptimizer.averaged()`` evaluates the
+model with it.  Its step size ``eta`` and averaging weight ``mu`` are state, computed AFTER a step from that step's ``lr`` and used in
+the next one: on the host on the plain path, on the device (``group_sched``) on the guarded one.
+
 No fallback: without libfgcn.so / off gfx950 ``step()`` raises ``FgcnError``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import numbers
 import re
-from typing import Dict, Iterable, List, Optional
+from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
 from . import _lib
 from .dp import FlatGradients
 
-KINDS = {"SGD": 0, "ADAM": 1, "ADAMW": 2}     # FGCN_OPT_* (include/fgcn.h); names as in session_helper.available_optimizers
+KINDS = {"SGD": 0, "ADAM": 1, "ADAMW": 2, "ASGD": 3}     # FGCN_OPT_* (include/fgcn.h); names as in session_helper.available_optimizers
 MAX_GROUPS = _lib.OPT_MAX_GROUPS              # FGCN_OPT_MAX_GROUPS
 
 
@@ -41,8 +46,8 @@ class FlatOptimizer(torch.optim.Optimizer):
     """``FlatOptimizer(model.parameters(), "ADAM", lr, weight_decay=0.01)`` == ``create_optimizer("ADAM", model, lr, ...)``.
 
     Supported ``optimizer_args`` (torch names and defaults): SGD ``momentum, dampening, weight_decay, nesterov``;
-    ADAM / ADAMW ``betas, eps, weight_decay`` (AdamW's default decay is 0.01).  ``amsgrad`` / ``maximize`` are not built (the
-    reference does not use them) and raise.
+    ADAM / ADAMW ``betas, eps, weight_decay`` (AdamW's default decay is 0.01); ASGD ``lambd, alpha, t0, weight_decay``.
+    ``amsgrad`` / ``maximize`` are not built (the reference does not use them) and raise.
     ``params``: an iterable of parameters, or torch's list of group dicts -- ``{"params": [...], "lr": ..., "weight_decay": ...}`` with
     any of the kind's scalars above as overrides; one kind for all groups, at most ``MAX_GROUPS`` (8) of them.  The groups are final:
     ``add_param_group`` on a built optimizer raises (it would have to re-home parameters into live flat buffers).  The order of the
@@ -75,12 +80,14 @@ class FlatOptimizer(torch.optim.Optimizer):
         kind = name.upper()
         _check_max_grad_norm(max_grad_norm)
         if kind not in KINDS:
-            raise ValueError("Unsupported optimizer: " + kind + " (SGD | ADAM | ADAMW)")
+            raise ValueError("Unsupported optimizer: " + kind + " (SGD | ASGD | ADAM | ADAMW)")
         if optimizer_args.get("amsgrad") or optimizer_args.get("maximize"):
             raise NotImplementedError("amsgrad / maximize are not built")
         defaults = dict(lr=lr, weight_decay=0.01 if kind == "ADAMW" else 0.0)
         if kind == "SGD":
             defaults.update(momentum=0.0, dampening=0.0, nesterov=False)
+        elif kind == "ASGD":
+            defaults.update(lambd=1e-4, alpha=0.75, t0=1e6)
         else:
             defaults.update(betas=(0.9, 0.999), eps=1e-8)
         unknown = set(optimizer_args) - set(defaults) - {"amsgrad", "maximize"}
@@ -124,8 +131,8 @@ class FlatOptimizer(torch.optim.Optimizer):
                 home.copy_(p)
                 p.data = home
         need1 = kind != "SGD" or any(group["momentum"] != 0 for group in self.param_groups)
-        self.state1 = torch.zeros_like(self.flat) if need1 else None       # momentum buffer / exp_avg
-        self.state2 = torch.zeros_like(self.flat) if kind != "SGD" else None   # exp_avg_sq
+        self.state1 = torch.zeros_like(self.flat) if need1 else None       # momentum buffer / exp_avg / ASGD's ax
+        self.state2 = torch.zeros_like(self.flat) if kind in ("ADAM", "ADAMW") else None   # exp_avg_sq
         self._steps = 0           # the host-side count of the unguarded path
         self.grad_scale = 1.0     # set to 1/world when the flat gradients hold an un-averaged all-reduce sum
         # the guard's state (enum fgcn_guard_word) and the partial sums of the norm: allocated once, zero = reset
@@ -138,9 +145,14 @@ class FlatOptimizer(torch.optim.Optimizer):
         self._guarded = max_grad_norm is not None or self.skip_nonfinite
         # several groups: the element-to-group table and the per-group step sizes of the guarded form, built and uploaded ONCE
         self._tiles = self._sched = None
-        if len(self.param_groups) > 1:
+        if len(self.param_groups) > 1 or kind == "ASGD":       # (ASGD's guarded form is the grouped call, also for one group)
             self._tiles = torch.tensor(self.tile_table(), dtype=torch.int32).to(self.flat.device)
-            self._sched = torch.zeros(2 * MAX_GROUPS, dtype=torch.float64, device=self.flat.device)
+            self._sched = torch.zeros((4 if kind == "ASGD" else 2) * MAX_GROUPS, dtype=torch.float64, device=self.flat.device)
+        # ASGD: (eta, mu) of the NEXT step per group, float32 values; None until the first step takes eta = lr.  On the guarded path
+        # they live in _sched ({eta_use, mu_use, eta_next, mu_next} per group), written once when the path is entered
+        self._eta_mu: Optional[List[Tuple[float, float]]] = None
+        self._sched_seeded = False
+        self._averaging = False
 
     def add_param_group(self, param_group) -> None:
         if getattr(self, "_built", False):
@@ -177,6 +189,8 @@ class FlatOptimizer(torch.optim.Optimizer):
         if not self._guarded:
             self._guard[_lib.GUARD_STEP].fill_(self._steps)
             self._guarded = True
+            if self.kind == "ASGD":
+                self._write_sched()
 
     @property
     def steps(self) -> int:
@@ -199,6 +213,51 @@ class FlatOptimizer(torch.optim.Optimizer):
         """Applied steps whose clip coefficient was below 1.  Reads a device counter: it waits for the device."""
         return int(self._guard[_lib.GUARD_CLIPPED].item())
 
+    # ---- ASGD: eta / mu and the averaged iterate ------------------------------------------------------------------------------
+    def _write_sched(self) -> None:
+        """The host's (eta, mu) -- or (lr, 1) before the first step -- into group_sched's ``next`` pair (and ``use``, which the decision
+        launch overwrites before the update reads it).  One small copy, stream-ordered."""
+        pairs = self._eta_mu or [(_f32(g["lr"]), 1.0) for g in self.param_groups]
+        rows = [[eta, mu, eta, mu] for eta, mu in pairs] + [[0.0] * 4] * (MAX_GROUPS - len(pairs))
+        self._sched.copy_(torch.tensor(rows, dtype=torch.float64).reshape(-1))
+        self._sched_seeded = True
+
+    def _read_eta_mu(self) -> List[Tuple[float, float]]:
+        """(eta, mu) the next step will use, per group.  On the guarded path this reads the device: it waits for it."""
+        if self._guarded and self._sched_seeded:
+            rows = self._sched.view(MAX_GROUPS, 4)[:len(self.param_groups), 2:].cpu().tolist()
+            return [(eta, mu) for eta, mu in rows]
+        return list(self._eta_mu or [(_f32(g["lr"]), 1.0) for g in self.param_groups])
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """``with optimizer.averaged(): session.validate_epoch(...)`` -- evaluate with ASGD's averaged iterate ``ax`` (torch keeps it in
+        the optimizer state and offers no way to use it).  Inside the context every trainable parameter aliases its view of ``ax``
+        instead of its home in ``flat``: a swap of ``p.data``, no copy and no launch; the tensor versions are bumped on entry and on
+        exit, so the blocks' packed-weight caches refresh both ways.  ``step()`` inside raises ``RuntimeError``; so does entering before
+        the first applied step (``ax`` is still zeros; on the guarded path this check reads the device counter), ``TypeError`` for
+        another kind.  Only parameters are averaged: BatchNorm running statistics are buffers, ASGD keeps no average of them, and the
+        model evaluates with the statistics of the last iterate."""
+        if self.kind != "ASGD":
+            raise TypeError(f"averaged() is ASGD's averaged iterate; this optimizer is {self.kind}")
+        if self._averaging:
+            raise RuntimeError("averaged() is already active")
+        if self.steps == 0:
+            raise RuntimeError("averaged() before the first applied step: ax is still zeros")
+        self._check_homes()
+        homes = [p.data for p in self.params]
+        self._averaging = True
+        try:
+            for p, ax in zip(self.params, self._views(self.state1)):
+                p.data = ax
+                torch.autograd.graph.increment_version(p)
+            yield self
+        finally:
+            for p, home in zip(self.params, homes):
+                p.data = home
+                torch.autograd.graph.increment_version(p)
+            self._averaging = False
+
     def zero_grad(self, set_to_none: bool = True) -> None:
         if set_to_none:
             self.grads.zero()
@@ -211,6 +270,8 @@ class FlatOptimizer(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._averaging:
+            raise RuntimeError("FlatOptimizer.step inside averaged(): the parameters alias ax, the averaged iterate")
         self._check_homes()
         self.grads.gather()                   # p.grad -> the flat buffer (no copy when they already are views of it)
         lib = _lib.load()
@@ -224,8 +285,15 @@ class FlatOptimizer(torch.optim.Optimizer):
         stream = torch.cuda.current_stream(self.flat.device).cuda_stream
         guard = (float(self._max_grad_norm or 0.0), int(self.skip_nonfinite), self._partials.data_ptr(), lib.fgcn_grad_norm_tiles(n),
                  self._guard.data_ptr()) if self._guarded else None
-        if len(self.param_groups) > 1:     # one launch over the tile table; the groups' scalars by value
-            groups = (_lib.OptimGroup * len(self.param_groups))(*[_group_scalars(g) for g in self.param_groups])
+        asgd = self.kind == "ASGD"
+        if asgd and self._guarded:
+            if not self._sched_seeded:         # (built guarded: eta = the lr of the first step() call)
+                self._write_sched()
+        elif asgd and self._eta_mu is None:
+            self._eta_mu = [(_f32(g["lr"]), 1.0) for g in self.param_groups]
+        if len(self.param_groups) > 1 or (asgd and self._guarded):     # one launch over the tile table; the groups' scalars by value
+            pairs = self._eta_mu if asgd and not self._guarded else [None] * len(self.param_groups)
+            groups = (_lib.OptimGroup * len(self.param_groups))(*[_group_scalars(g, em) for g, em in zip(self.param_groups, pairs)])
             common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n, KINDS[self.kind], groups, len(groups),
                       self._tiles.data_ptr(), self._tiles.shape[0], float(self.grad_scale))
             if self._guarded:
@@ -236,11 +304,10 @@ class FlatOptimizer(torch.optim.Optimizer):
                 _lib.check(lib.fgcn_optim_step_groups(*common, self._steps, stream), "fgcn_optim_step_groups")
         else:
             g = self.param_groups[0]
-            b1, b2 = g.get("betas", (0.0, 0.0))
+            h = _group_scalars(g, self._eta_mu[0] if asgd else None)
             common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n,
-                      KINDS[self.kind], float(g["lr"]), float(g["weight_decay"]), float(self.grad_scale),
-                      float(b1), float(b2), float(g.get("eps", 0.0)), float(g.get("momentum", 0.0)),
-                      float(g.get("dampening", 0.0)), int(bool(g.get("nesterov", False))))
+                      KINDS[self.kind], h.lr, h.weight_decay, float(self.grad_scale),
+                      h.beta1, h.beta2, h.eps, h.momentum, h.dampening, h.nesterov)
             if self._guarded:         # norm -> decision -> update, stream-ordered; the step count is the device's
                 rc = lib.fgcn_optim_step_guarded(*common, *guard, stream)
                 _lib.check(rc, "fgcn_optim_step_guarded")
@@ -248,6 +315,8 @@ class FlatOptimizer(torch.optim.Optimizer):
                 self._steps += 1
                 rc = lib.fgcn_optim_step(*common, self._steps, stream)
                 _lib.check(rc, "fgcn_optim_step")
+        if asgd and not self._guarded:     # torch computes the next step's eta / mu after the update, from this step's lr
+            self._eta_mu = [_asgd_next(g, self._steps) for g in self.param_groups]
         # the kernel wrote through raw pointers: tell autograd (and everything keyed on tensor versions, like the blocks'
         # cache of packed weights) that every parameter changed in place -- metadata only, no launches
         for p in self.params:
@@ -284,8 +353,13 @@ class FlatOptimizer(torch.optim.Optimizer):
         if steps:
             s1 = self._views(self.state1) if self.state1 is not None else None
             s2 = self._views(self.state2) if self.state2 is not None else None
+            eta_mu = self._read_eta_mu() if self.kind == "ASGD" else None
             for i, slot in enumerate(self._slots()):      # torch's layout: state index = position over all groups' "params"
-                if self.kind == "SGD":
+                if self.kind == "ASGD":
+                    eta, mu = eta_mu[self._group_of[i]]
+                    state[slot] = {"step": torch.tensor(float(steps)), "eta": torch.tensor(eta), "mu": torch.tensor(mu),
+                                   "ax": s1[i].clone()}
+                elif self.kind == "SGD":
                     if s1 is None:
                         state[slot] = {"momentum_buffer": None}
                     elif self.param_groups[self._group_of[i]]["momentum"] != 0:      # (torch keeps no state without a momentum)
@@ -311,13 +385,18 @@ class FlatOptimizer(torch.optim.Optimizer):
                     mine[k] = v
         st = sd.get("state", {})
         steps = 0
+        eta_mu: Dict[int, Tuple[float, float]] = {}
         if st:
             s1 = self._views(self.state1) if self.state1 is not None else None
             s2 = self._views(self.state2) if self.state2 is not None else None
             with torch.no_grad():
                 for i, slot in enumerate(self._slots()):
                     e = st[slot] if slot in st else st.get(str(slot))
-                    if self.kind == "SGD":
+                    if self.kind == "ASGD":
+                        s1[i].copy_(e["ax"])
+                        steps = int(e["step"])
+                        eta_mu.setdefault(self._group_of[i], (_f32(float(e["eta"])), _f32(float(e["mu"]))))
+                    elif self.kind == "SGD":
                         if s1 is not None and e is not None and e.get("momentum_buffer") is not None:
                             s1[i].copy_(e["momentum_buffer"])
                             steps = max(steps, 1)
@@ -326,6 +405,10 @@ class FlatOptimizer(torch.optim.Optimizer):
                         s2[i].copy_(e["exp_avg_sq"])
                         steps = int(e["step"])
         self.steps = steps          # (guarded: written to the device counter)
+        if self.kind == "ASGD":     # a group without trainable tensors has no entry: what torch would have computed for it
+            self._eta_mu = [eta_mu.get(i, _asgd_next(g, steps)) for i, g in enumerate(self.param_groups)] if steps else None
+            if self._guarded:
+                self._write_sched()
 
 
 def _check_group(kind: str, group: Dict) -> None:
@@ -334,9 +417,27 @@ def _check_group(kind: str, group: Dict) -> None:
         raise ValueError("negative lr / weight_decay")
     if kind == "SGD" and group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
         raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+    if kind == "ASGD" and not (group["lambd"] >= 0 and math.isfinite(group["alpha"]) and math.isfinite(group["t0"])):
+        raise ValueError("ASGD: lambd must be >= 0, alpha and t0 finite")
 
 
-def _group_scalars(g: Dict) -> _lib.OptimGroup:
+def _f32(x: float) -> float:
+    """x rounded through float32, as a value stored in one of torch's float32 state tensors."""
+    return ctypes.c_float(x).value
+
+
+def _asgd_next(g: Dict, step: int) -> Tuple[float, float]:
+    """(eta, mu) for the step after the one that made the count ``step``, from that step's lr: torch/optim/asgd.py's new_eta / new_mu,
+    Python doubles rounded through float32."""
+    lr, step = float(g["lr"]), float(step)
+    return _f32(lr / ((1 + g["lambd"] * lr * step) ** g["alpha"])), _f32(1 / max(1, step - g["t0"]))
+
+
+def _group_scalars(g: Dict, eta_mu: Optional[Tuple[float, float]] = None) -> _lib.OptimGroup:
+    if "lambd" in g:      # ASGD: lambd, alpha, t0 in the slots beta1, beta2, eps; the step's eta, mu in momentum, dampening
+        eta, mu = eta_mu or (0.0, 0.0)       # (the guarded form reads them from group_sched)
+        return _lib.OptimGroup(float(g["lr"]), float(g["weight_decay"]), float(g["lambd"]), float(g["alpha"]), float(g["t0"]),
+                               eta, mu, 0)
     b1, b2 = g.get("betas", (0.0, 0.0))
     return _lib.OptimGroup(float(g["lr"]), float(g["weight_decay"]), float(b1), float(b2), float(g.get("eps", 0.0)),
                            float(g.get("momentum", 0.0)), float(g.get("dampening", 0.0)), int(bool(g.get("nesterov", False))))

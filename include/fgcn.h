@@ -696,11 +696,31 @@ int fgcn_row_softmax_bwd(const float* da, const float* c, float* ds, long long r
  *   FGCN_OPT_ADAM   g += wd*p;  m += (g-m)(1-beta1);  v = beta2*v + (1-beta2) g*g;
  *                   p -= lr/(1-beta1^step) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)   (state1 = exp_avg, state2 = exp_avg_sq)
  *   FGCN_OPT_ADAMW  p *= 1 - lr*wd first, g untouched, then the same moments and update.
+ *   FGCN_OPT_ASGD   g += wd*p;  p *= (float)(1 - (double)lambd*eta);  p += -eta*g;  ax = mu == 1 ? p : ax + (p - ax)*mu
+ *                   (torch 2.10's _single_tensor_asgd, non-capturable path; state1 = ax, the averaged iterate; state2 must be NULL)
  * g is read as grad_scale * grads (the 1/world of the data-parallel average).  params, grads, state*: float[n], 16-byte
- * aligned, n % 4 == 0 (padding elements must hold zeros in all buffers); step counts from 1.  amsgrad / maximize: not built. */
+ * aligned, n % 4 == 0 (padding elements must hold zeros in all buffers); step counts from 1.  amsgrad / maximize: not built.
+ *
+ * ASGD's scalars.  eta and mu are float32 STATE of a parameter group, not functions of the current lr: torch computes them after a
+ * step, from that step's lr, and uses them in the next one (an LR scheduler shows up one step late in eta):
+ *   first step: eta = (float)lr, mu = 1;
+ *   after the step that made the count STEP:  eta = (float)(lr / pow(1 + lambd*lr*STEP, alpha)),  mu = (float)(1 / max(1, STEP - t0)),
+ *   both in double arithmetic.
+ * Unguarded forms (fgcn_optim_step, fgcn_optim_step_groups): the slots beta1, beta2, eps carry lambd, alpha, t0 and the slots
+ * momentum, dampening carry the CURRENT eta, mu (the fields of fgcn_optim_group likewise); the caller owns that state and computes the
+ * next values after the call.  lr and `step` are not used by the update itself.
+ * Guarded form, fgcn_optim_step_groups_guarded only: eta / mu live on the device in the caller-owned group_sched, which for this kind
+ * is 4 * FGCN_OPT_MAX_GROUPS doubles, {eta_use, mu_use, eta_next, mu_next} per group.  The caller initialises eta_next = lr_g,
+ * mu_next = 1 once (zeroing is NOT a reset for this kind).  Launch 2, when the step applies, copies next -> use and then computes the
+ * new next from the new STEP and the group's current lr; when it does not apply all four values keep their bits.  Launch 3 reads use;
+ * the momentum / dampening slots are ignored.  fgcn_optim_step_guarded has no group_sched argument and returns FGCN_E_BADARG for this
+ * kind: call fgcn_optim_step_groups_guarded with one group and a one-group tile table.
+ * FGCN_E_BADARG for ASGD: a null state1, a non-null state2, lambd < 0, alpha or t0 not finite, and on the unguarded forms an eta < 0 or
+ * a mu outside (0, 1] (the grouped forms name the group). */
 #define FGCN_OPT_SGD 0
 #define FGCN_OPT_ADAM 1
 #define FGCN_OPT_ADAMW 2
+#define FGCN_OPT_ASGD 3
 int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
                     float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
                     float momentum, float dampening, int nesterov, long long step, void* stream);
@@ -762,7 +782,8 @@ int fgcn_optim_step_guarded(float* params, const float* grads, float* state1, fl
  * Guarded form: the three launches of fgcn_optim_step_guarded -- the same norm kernel over the whole buffer (one global norm, the same
  * bits), one decision for all groups, one step count -- and `group_sched`, a caller-owned device buffer of 2 * FGCN_OPT_MAX_GROUPS
  * doubles, 8-byte aligned, that launch 2 fills with {lr_g / (1 - beta1_g^STEP), sqrt(1 - beta2_g^STEP)} per group for launch 3
- * (the guard words STEP_SIZE / BC2_SQRT are left alone).
+ * (the guard words STEP_SIZE / BC2_SQRT are left alone).  FGCN_OPT_ASGD: group_sched holds 4 doubles per group and carries state
+ * between calls (see "ASGD's scalars" above).
  * FGCN_E_BADARG: ngroups outside [1, FGCN_OPT_MAX_GROUPS], a null groups / tiles / group_sched, ntiles < 1, n / 4 >= 2^31, a group's lr /
  * weight_decay / betas / eps / momentum out of range or Nesterov without momentum or with dampening (the message names the group);
  * FGCN_E_ALIGN: tiles not 4-byte, group_sched not 8-byte aligned; everything else as the single-group calls. */
@@ -770,8 +791,8 @@ int fgcn_optim_step_guarded(float* params, const float* grads, float* state1, fl
 #define FGCN_OPT_TILE4 1024
 typedef struct fgcn_optim_group {
     float lr, weight_decay;
-    float beta1, beta2, eps;       /* Adam / AdamW */
-    float momentum, dampening;     /* SGD */
+    float beta1, beta2, eps;       /* Adam / AdamW; ASGD: lambd, alpha, t0 */
+    float momentum, dampening;     /* SGD; ASGD (unguarded): the step's eta, mu */
     int nesterov;
 } fgcn_optim_group;
 int fgcn_optim_step_groups(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
