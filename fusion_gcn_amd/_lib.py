@@ -67,9 +67,15 @@ REDUCE_MAX_ITEMS = 8        # FGCN_REDUCE_MAX_ITEMS
 
 
 class OptimGroup(C.Structure):
-    """fgcn_optim_group: the scalars of one parameter group of the grouped optimizer step."""
+    """fgcn_optim_group: the scalars of one parameter group of the optimizer step."""
     _fields_ = [("lr", C.c_float), ("weight_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int)]
+
+
+class OptimGuard(C.Structure):
+    """fgcn_optim_guard: the guard of the optimizer step (clip by global norm, skip non-finite steps) and its device state."""
+    _fields_ = [("max_norm", C.c_double), ("skip_nonfinite", C.c_int), ("n_partials", C.c_int), ("partials", C.c_void_p),
+                ("state", C.c_void_p), ("group_sched", C.c_void_p)]
 
 
 OPT_MAX_GROUPS = 8          # FGCN_OPT_MAX_GROUPS
@@ -188,12 +194,9 @@ SIGNATURES = {
     "fgcn_ce_workspace_bytes": (_LL, [_I]),
     "fgcn_ce_fwd": (_I, [_P] * 9 + [_I, _I, _I, _I, _LL, _F, _I, _P]),
     "fgcn_ce_bwd": (_I, [_P] * 8 + [_I, _I, _I, _I, _LL, _F, _I, _P]),
-    "fgcn_optim_step": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _LL, _P]),
+    "fgcn_optim_step": (_I, [_P, _P, _P, _P, _LL, _I, C.POINTER(OptimGroup), _I, _P, _I, _F, _LL, C.POINTER(OptimGuard), _P]),
     "fgcn_grad_norm_tiles": (_I, [_LL]),
     "fgcn_optim_guard_bytes": (_LL, []),
-    "fgcn_optim_step_guarded": (_I, [_P, _P, _P, _P, _LL, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _D, _I, _P, _I, _P, _P]),
-    "fgcn_optim_step_groups": (_I, [_P, _P, _P, _P, _LL, _I, C.POINTER(OptimGroup), _I, _P, _I, _F, _LL, _P]),
-    "fgcn_optim_step_groups_guarded": (_I, [_P, _P, _P, _P, _LL, _I, C.POINTER(OptimGroup), _I, _P, _I, _F, _D, _I, _P, _I, _P, _P, _P]),
     "fgcn_classify_state_bytes": (_LL, [_I]),
     "fgcn_classify_update": (_I, [_P, _P, _P, _P, _P, _LL, _LL, _I, _I, _I, _I, _P]),
     "fgcn_philox4x32_10": (_I, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
@@ -207,8 +210,7 @@ CLS_EXAMPLES, CLS_TOP1, CLS_TOPK, CLS_IGNORED, CLS_INVALID, CLS_DROPPED, CLS_LOS
 CLS_MAX_CLASSES = 1024      # FGCN_CLS_MAX_CLASSES
 CE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}       # enum fgcn_ce_reduction
 # enum fgcn_guard_word: the 8-byte words of the guarded optimizer step's state (include/fgcn.h)
-(GUARD_STEP, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM, GUARD_COEF, GUARD_APPLY, GUARD_FIRST_STEP, GUARD_STEP_SIZE, GUARD_BC2_SQRT,
- GUARD_WORDS) = range(10)
+GUARD_STEP, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM, GUARD_COEF, GUARD_APPLY, GUARD_FIRST_STEP, GUARD_WORDS = range(8)
 GRAD_NORM_MAX_TILES = 512   # FGCN_GRAD_NORM_MAX_TILES
 
 _lib = None

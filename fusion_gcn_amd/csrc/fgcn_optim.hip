@@ -6,13 +6,13 @@
 // launch applies torch's update formulas element by element -- the data-parallel 1/world average rides along as
 // `grad_scale`.  Pure HBM stream: 16-byte loads / stores, 28 B per parameter (Adam).
 //
-// The guarded form (fgcn_optim_step_guarded) puts two launches in front of it: the float64 sum of squares of the scaled gradient
-// (one more 4 B per parameter read) and a one-workgroup decision -- clip coefficient, apply / skip, step count and Adam's bias
-// corrections -- written into a caller-owned guard state that the update then reads.  The host reads nothing back.
+// With a guard (fgcn_optim_guard) two launches go in front of it: the float64 sum of squares of the scaled gradient (one more 4 B
+// per parameter read) and a one-workgroup decision -- clip coefficient, apply / skip, step count and every group's step sizes --
+// written into caller-owned device state that the update then reads.  The host reads nothing back.
 //
-// The grouped forms (fgcn_optim_step_groups, fgcn_optim_step_groups_guarded: torch.optim's param_groups) keep the launch counts: the
-// update is still one launch, one workgroup per row of a device-resident tile table (start4, count4, group), the group's scalars
-// selected from a by-value array in the kernel arguments.  The formulas exist once (optim_update4, guard_decide).
+// One entry point, fgcn_optim_step: the update is one workgroup per row of a device-resident tile table (start4, count4, group), the
+// group's scalars (torch.optim's param_groups) selected from a by-value array in the kernel arguments.  One group is a table whose
+// rows all name group 0.  The formulas exist once (optim_update4, guard_decide).
 #include <cmath>
 
 #include "fgcn_common.hpp"
@@ -89,24 +89,10 @@ __device__ __forceinline__ void optim_update4(const OptimP& q, long long i) {
     *reinterpret_cast<f32x4*>(q.p + i * 4) = p;
 }
 
-// GUARDED: the step's scalars come from the guard state of the launch before (uniform loads), nothing is stored when it says skip
-template <int KIND, bool GUARDED>
-__global__ __launch_bounds__(256) void optim_step_kernel(OptimP q) {
-    if (GUARDED) {
-        if (q.guard[FGCN_GUARD_APPLY] == 0) return;
-        q.grad_scale = (float)((double)q.grad_scale * guard_f64(q.guard, FGCN_GUARD_COEF));
-        q.first_step = (int)q.guard[FGCN_GUARD_FIRST_STEP];
-        q.step_size = (float)guard_f64(q.guard, FGCN_GUARD_STEP_SIZE);
-        q.bc2_sqrt = (float)guard_f64(q.guard, FGCN_GUARD_BC2_SQRT);
-    }
-    if (KIND == 3) q.c0 = asgd_decay(q.beta1, q.momentum);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < q.n4; i += (long long)gridDim.x * blockDim.x)
-        optim_update4<KIND>(q, i);
-}
-
-// The grouped update: workgroup t takes row t of the tile table (start4, count4, group) -- all int, read with uniform loads -- and
+// The update: workgroup t takes row t of the tile table (start4, count4, group) -- all int, read with uniform loads -- and
 // runs optim_update4 over its 16-byte groups with that group's scalars.  A row that names no group or reaches past the buffers does
-// nothing (the host cannot see the table).
+// nothing (the host cannot see the table).  GUARDED: the step's scalars come from the state of the launch before (uniform loads),
+// nothing is stored when it says skip.
 struct OptimGroupsP {
     OptimP base;                                       // buffers, n4, grad_scale, first_step (unguarded), guard
     const int* tiles;
@@ -190,8 +176,10 @@ __global__ __launch_bounds__(GN_THREADS) void grad_sqsum_kernel(const float* g, 
 struct GuardP {
     const double* partials;
     unsigned long long* guard;
-    int n_partials, skip_nonfinite, adam;
-    double max_norm, lr, beta1, beta2;
+    double* sched;                                            // group_sched
+    int n_partials, skip_nonfinite, kind, ngroups;
+    double max_norm;
+    fgcn_optim_group grp[FGCN_OPT_MAX_GROUPS];
 };
 
 // One workgroup: the partials go through LDS so that their loads overlap, thread 0 adds them in index order and decides.  Returns
@@ -225,124 +213,34 @@ __device__ __forceinline__ unsigned long long guard_decide(const GuardP& q) {
     return step;
 }
 
+// The decision, then every group's scalars of an applied step into `sched`, in double as torch's Python scalars: lane i of thread 0's
+// wave computes entry i.  Adam / AdamW: the step size and sqrt(1 - beta2^STEP) from the new STEP, two entries per group.  ASGD, one lane
+// per group: the values torch computed after the step before become this step's, and the next step's come from the new STEP and the
+// group's current lr (torch/optim/asgd.py: new_eta, new_mu, each rounded through float32; beta1, beta2, eps carry lambd, alpha, t0).
+// Nothing moves when the step is skipped.
 __global__ __launch_bounds__(GN_THREADS) void optim_guard_decide_kernel(GuardP q) {
-    const unsigned long long step = guard_decide(q);
-    if (step && q.adam) {                                     // the bias corrections in double, as fgcn_optim_step's host code
-        const double bc1 = 1.0 - pow(q.beta1, (double)step), bc2 = 1.0 - pow(q.beta2, (double)step);
-        q.guard[FGCN_GUARD_STEP_SIZE] = __builtin_bit_cast(unsigned long long, q.lr / bc1);
-        q.guard[FGCN_GUARD_BC2_SQRT] = __builtin_bit_cast(unsigned long long, sqrt(bc2));
-    }
-}
-
-// The same decision for the grouped update: every group's step size and sqrt(1 - beta2^STEP) go to `sched` instead of the guard words.
-struct GuardGroupsP {
-    GuardP d;                                                 // (d.lr / d.beta1 / d.beta2 unused)
-    double* sched;
-    int ngroups;
-    double lr[FGCN_OPT_MAX_GROUPS], beta1[FGCN_OPT_MAX_GROUPS], beta2[FGCN_OPT_MAX_GROUPS];
-};
-
-__global__ __launch_bounds__(GN_THREADS) void optim_guard_decide_groups_kernel(GuardGroupsP a) {
-    const unsigned long long step = guard_decide(a.d);
-    if (!step || !a.d.adam) return;
-    for (int g = 0; g < a.ngroups; ++g) {
-        const double bc1 = 1.0 - pow(a.beta1[g], (double)step), bc2 = 1.0 - pow(a.beta2[g], (double)step);
-        a.sched[2 * g] = a.lr[g] / bc1;
-        a.sched[2 * g + 1] = sqrt(bc2);
-    }
-}
-
-// ASGD's decision: the values torch computed after the step before become this step's, and the next step's come from the new STEP and
-// the groups' current lr (torch/optim/asgd.py: new_eta, new_mu, each rounded through float32).  Nothing moves when the step is skipped.
-struct GuardAsgdP {
-    GuardP d;                                                 // (d.lr / d.beta1 / d.beta2 unused, d.adam 0)
-    double* sched;                                            // {eta_use, mu_use, eta_next, mu_next} per group
-    int ngroups;
-    double lr[FGCN_OPT_MAX_GROUPS], lambd[FGCN_OPT_MAX_GROUPS], alpha[FGCN_OPT_MAX_GROUPS], t0[FGCN_OPT_MAX_GROUPS];
-};
-
-__global__ __launch_bounds__(GN_THREADS) void optim_guard_decide_asgd_kernel(GuardAsgdP a) {
-    const unsigned long long step = guard_decide(a.d);
-    if (!step) return;
-    const double t = (double)step;
-    for (int g = 0; g < a.ngroups; ++g) {
 #pragma clang fp contract(off)
-        double* s = a.sched + 4 * g;
+    const unsigned long long step = __shfl(guard_decide(q), 0);
+    const bool asgd = q.kind == FGCN_OPT_ASGD;
+    const int per = asgd ? 1 : 2, i = threadIdx.x;
+    if (!step || q.kind == FGCN_OPT_SGD || i >= per * q.ngroups) return;
+    const fgcn_optim_group& h = q.grp[i / per];
+    const double t = (double)step, lr = (double)h.lr, b1 = (double)h.beta1, b2 = (double)h.beta2;
+    const double pw = pow(asgd ? 1.0 + b1 * lr * t : i & 1 ? b2 : b1, asgd ? b2 : t);
+    if (asgd) {
+        double* s = q.sched + 4 * i;
         s[0] = s[2];
         s[1] = s[3];
-        const double over = t - a.t0[g];
-        s[2] = (double)(float)(a.lr[g] / pow(1.0 + a.lambd[g] * a.lr[g] * t, a.alpha[g]));
+        const double over = t - (double)h.eps;
+        s[2] = (double)(float)(lr / pw);
         s[3] = (double)(float)(1.0 / (over > 1.0 ? over : 1.0));
-    }
+    } else
+        q.sched[i] = i & 1 ? sqrt(1.0 - pw) : lr / (1.0 - pw);
 }
 
 }  // namespace fgcn
 
 using namespace fgcn;
-
-// Everything both entry points check and fill in; `step` is the host-side count of the unguarded call, NULL for the guarded one
-// (whose count lives in the guard state).
-static int optim_prepare(OptimP& q, const char* who, float* params, const float* grads, float* state1, float* state2, long long n,
-                         int kind, float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
-                         float momentum, float dampening, int nesterov, const long long* step) {
-    FGCN_REQUIRE(params && grads && n > 0, FGCN_E_BADARG, "%s: null pointer or empty buffer", who);
-    FGCN_REQUIRE(n % 4 == 0 && aligned16(params) && aligned16(grads), FGCN_E_ALIGN,
-                 "%s: buffers must be 16-byte aligned and a multiple of 4 floats long (n=%lld)", who, n);
-    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ASGD, FGCN_E_BADARG, "%s: kind %d", who, kind);
-    FGCN_REQUIRE(!step || *step >= 1, FGCN_E_BADARG, "%s: step counts from 1 (got %lld)", who, step ? *step : 0ll);
-    FGCN_REQUIRE(lr >= 0.f && weight_decay >= 0.f, FGCN_E_BADARG, "%s: negative lr / weight_decay", who);
-    q = OptimP{};
-    q.p = params; q.g = grads; q.m = state1; q.v = state2; q.n4 = n / 4;
-    q.lr = lr; q.wd = weight_decay; q.grad_scale = grad_scale;
-    if (kind == FGCN_OPT_SGD) {
-        FGCN_REQUIRE(momentum >= 0.f && (momentum == 0.f || (state1 && aligned16(state1))), FGCN_E_BADARG,
-                     "%s: SGD with momentum needs the momentum buffer", who);
-        FGCN_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), FGCN_E_BADARG,
-                     "%s: Nesterov momentum requires a momentum and zero dampening", who);
-        q.momentum = momentum; q.dampening = dampening; q.nesterov = nesterov; q.first_step = step && *step == 1;
-    } else if (kind == FGCN_OPT_ASGD) {      // beta1, beta2, eps carry lambd, alpha, t0; momentum, dampening the step's eta, mu
-        FGCN_REQUIRE(state1 && aligned16(state1), FGCN_E_BADARG, "%s: kind 3 (ASGD) needs ax, the averaged iterate, in state1", who);
-        FGCN_REQUIRE(!state2, FGCN_E_BADARG, "%s: kind 3 (ASGD) keeps one state buffer: state2 must be NULL", who);
-        FGCN_REQUIRE(beta1 >= 0.f && std::isfinite(beta2) && std::isfinite(eps), FGCN_E_BADARG,
-                     "%s: ASGD: negative lambd or alpha / t0 not finite", who);
-        FGCN_REQUIRE(momentum >= 0.f && dampening > 0.f && dampening <= 1.f, FGCN_E_BADARG,
-                     "%s: ASGD: eta must be >= 0 and mu in (0, 1] (got %g, %g)", who, (double)momentum, (double)dampening);
-        q.beta1 = beta1; q.momentum = momentum; q.dampening = dampening;
-    } else {
-        FGCN_REQUIRE(state1 && state2 && aligned16(state1) && aligned16(state2), FGCN_E_BADARG,
-                     "%s: Adam needs exp_avg and exp_avg_sq", who);
-        FGCN_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, FGCN_E_BADARG,
-                     "%s: betas / eps out of range", who);
-        q.beta1 = beta1; q.beta2 = beta2; q.eps = eps;
-        if (step) {      // the bias corrections in double, as torch's Python scalars
-            const double bc1 = 1.0 - std::pow((double)beta1, (double)*step), bc2 = 1.0 - std::pow((double)beta2, (double)*step);
-            q.step_size = (float)((double)lr / bc1);
-            q.bc2_sqrt = (float)std::sqrt(bc2);
-        }
-    }
-    return FGCN_OK;
-}
-
-template <bool GUARDED>
-static void optim_launch(const OptimP& q, int kind, hipStream_t s) {
-    const long long blocks = cdiv(q.n4, 256);
-    dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
-    if (kind == FGCN_OPT_SGD) hipLaunchKernelGGL((optim_step_kernel<0, GUARDED>), grid, dim3(256), 0, s, q);
-    else if (kind == FGCN_OPT_ADAM) hipLaunchKernelGGL((optim_step_kernel<1, GUARDED>), grid, dim3(256), 0, s, q);
-    else if (kind == FGCN_OPT_ADAMW) hipLaunchKernelGGL((optim_step_kernel<2, GUARDED>), grid, dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((optim_step_kernel<3, false>), grid, dim3(256), 0, s, q);      // (ASGD has no single-group guarded form)
-}
-
-extern "C" int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                               float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
-                               float momentum, float dampening, int nesterov, long long step, void* stream) {
-    OptimP q;
-    const int rc = optim_prepare(q, "optim_step", params, grads, state1, state2, n, kind, lr, weight_decay, grad_scale, beta1, beta2,
-                                 eps, momentum, dampening, nesterov, &step);
-    if (rc != FGCN_OK) return rc;
-    optim_launch<false>(q, kind, (hipStream_t)stream);
-    return launch_status("optim_step");
-}
 
 extern "C" int fgcn_grad_norm_tiles(long long n) {
     const long long t = cdiv(cdiv(n, 4), GN_CHUNK4);
@@ -351,103 +249,82 @@ extern "C" int fgcn_grad_norm_tiles(long long n) {
 
 extern "C" long long fgcn_optim_guard_bytes(void) { return 8ll * FGCN_GUARD_WORDS; }
 
-// What both guarded entry points check and fill in for the decision launch.
-static int guard_prepare(GuardP& d, const char* who, long long n, int kind, double max_norm, int skip_nonfinite, double* partials,
-                         int n_partials, void* guard) {
-    FGCN_REQUIRE(partials && guard, FGCN_E_BADARG, "%s: null partials / guard state", who);
-    FGCN_REQUIRE(((uintptr_t)guard & 7) == 0 && ((uintptr_t)partials & 7) == 0, FGCN_E_ALIGN,
-                 "%s: guard state and partials must be 8-byte aligned", who);
-    FGCN_REQUIRE(n_partials == fgcn_grad_norm_tiles(n), FGCN_E_BADARG, "%s: n_partials must be %d (got %d)", who,
-                 fgcn_grad_norm_tiles(n), n_partials);
-    FGCN_REQUIRE(max_norm >= 0.0, FGCN_E_BADARG, "%s: max_norm must be a number >= 0 (0: no clipping)", who);
-    d = GuardP{};
-    d.partials = partials; d.guard = static_cast<unsigned long long*>(guard); d.n_partials = n_partials;
-    d.skip_nonfinite = skip_nonfinite != 0; d.adam = kind == FGCN_OPT_ADAM || kind == FGCN_OPT_ADAMW;
-    d.max_norm = max_norm;
-    return FGCN_OK;
-}
-
-extern "C" int fgcn_optim_step_guarded(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                                       float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
-                                       float momentum, float dampening, int nesterov, double max_norm, int skip_nonfinite,
-                                       double* partials, int n_partials, void* guard, void* stream) {
-    FGCN_REQUIRE(kind != FGCN_OPT_ASGD, FGCN_E_BADARG,
-                 "optim_step_guarded: kind 3 (ASGD) keeps eta / mu in group_sched: call fgcn_optim_step_groups_guarded with one group");
-    OptimP q;
-    int rc = optim_prepare(q, "optim_step_guarded", params, grads, state1, state2, n, kind, lr, weight_decay, grad_scale, beta1,
-                           beta2, eps, momentum, dampening, nesterov, nullptr);
-    if (rc != FGCN_OK) return rc;
-    GuardP d;
-    rc = guard_prepare(d, "optim_step_guarded", n, kind, max_norm, skip_nonfinite, partials, n_partials, guard);
-    if (rc != FGCN_OK) return rc;
-    q.guard = d.guard;
-    d.lr = (double)lr; d.beta1 = (double)beta1; d.beta2 = (double)beta2;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(grad_sqsum_kernel, dim3((unsigned)n_partials), dim3(GN_THREADS), 0, s, grads, q.n4, grad_scale, partials);
-    hipLaunchKernelGGL(optim_guard_decide_kernel, dim3(1), dim3(GN_THREADS), 0, s, d);
-    optim_launch<true>(q, kind, s);
-    return launch_status("optim_step_guarded");
-}
-
-// ---- several parameter groups ----------------------------------------------------------------------------------------------------
-// Everything both grouped entry points check and fill in: the buffers as optim_prepare, then every group's ranges (the message names
-// the group).  `step` as in optim_prepare.
-static int optim_groups_prepare(OptimGroupsP& a, const char* who, float* params, const float* grads, float* state1, float* state2,
-                                long long n, int kind, const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles,
-                                float grad_scale, const long long* step) {
-    FGCN_REQUIRE(params && grads && n > 0, FGCN_E_BADARG, "%s: null pointer or empty buffer", who);
+// Everything the call checks and fills in: the buffers, every group's ranges (the message names the group), then the guard.  `step` is
+// the host-side count without a guard; with one the count lives in the guard state.
+static int optim_prepare(OptimGroupsP& a, GuardP& d, float* params, const float* grads, float* state1, float* state2, long long n,
+                         int kind, const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
+                         long long step, const fgcn_optim_guard* guard) {
+    FGCN_REQUIRE(params && grads && n > 0, FGCN_E_BADARG, "optim_step: null pointer or empty buffer");
     FGCN_REQUIRE(n % 4 == 0 && aligned16(params) && aligned16(grads), FGCN_E_ALIGN,
-                 "%s: buffers must be 16-byte aligned and a multiple of 4 floats long (n=%lld)", who, n);
-    FGCN_REQUIRE(n / 4 <= 0x7fffffffll, FGCN_E_BADARG, "%s: the tile table indexes 16-byte groups with an int (n=%lld)", who, n);
-    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ASGD, FGCN_E_BADARG, "%s: kind %d", who, kind);
-    FGCN_REQUIRE(!step || *step >= 1, FGCN_E_BADARG, "%s: step counts from 1 (got %lld)", who, step ? *step : 0ll);
-    FGCN_REQUIRE(ngroups >= 1 && ngroups <= FGCN_OPT_MAX_GROUPS, FGCN_E_BADARG, "%s: 1 to %d parameter groups (got %d)", who,
+                 "optim_step: buffers must be 16-byte aligned and a multiple of 4 floats long (n=%lld)", n);
+    FGCN_REQUIRE(n / 4 <= 0x7fffffffll, FGCN_E_BADARG, "optim_step: the tile table indexes 16-byte groups with an int (n=%lld)", n);
+    FGCN_REQUIRE(kind >= FGCN_OPT_SGD && kind <= FGCN_OPT_ASGD, FGCN_E_BADARG, "optim_step: kind %d", kind);
+    FGCN_REQUIRE(guard || step >= 1, FGCN_E_BADARG, "optim_step: step counts from 1 (got %lld)", step);
+    FGCN_REQUIRE(!guard || step == 0, FGCN_E_BADARG, "optim_step: with a guard the count lives in its state: step must be 0 (got %lld)",
+                 step);
+    FGCN_REQUIRE(ngroups >= 1 && ngroups <= FGCN_OPT_MAX_GROUPS, FGCN_E_BADARG, "optim_step: 1 to %d parameter groups (got %d)",
                  FGCN_OPT_MAX_GROUPS, ngroups);
-    FGCN_REQUIRE(groups, FGCN_E_BADARG, "%s: null groups", who);
-    FGCN_REQUIRE(tiles && ntiles >= 1, FGCN_E_BADARG, "%s: null or empty tile table", who);
-    FGCN_REQUIRE(((uintptr_t)tiles & 3) == 0, FGCN_E_ALIGN, "%s: the tile table must be 4-byte aligned", who);
+    FGCN_REQUIRE(groups, FGCN_E_BADARG, "optim_step: null groups");
+    FGCN_REQUIRE(tiles && ntiles >= 1, FGCN_E_BADARG, "optim_step: null or empty tile table");
+    FGCN_REQUIRE(((uintptr_t)tiles & 3) == 0, FGCN_E_ALIGN, "optim_step: the tile table must be 4-byte aligned");
     a = OptimGroupsP{};
     OptimP& q = a.base;
     q.p = params; q.g = grads; q.m = state1; q.v = state2; q.n4 = n / 4; q.grad_scale = grad_scale;
-    q.first_step = kind == FGCN_OPT_SGD && step && *step == 1;
+    q.first_step = kind == FGCN_OPT_SGD && step == 1;
     a.tiles = tiles; a.ngroups = ngroups;
     if (kind == FGCN_OPT_ASGD) {
-        FGCN_REQUIRE(state1 && aligned16(state1), FGCN_E_BADARG, "%s: kind 3 (ASGD) needs ax, the averaged iterate, in state1", who);
-        FGCN_REQUIRE(!state2, FGCN_E_BADARG, "%s: kind 3 (ASGD) keeps one state buffer: state2 must be NULL", who);
+        FGCN_REQUIRE(state1 && aligned16(state1), FGCN_E_BADARG, "optim_step: kind 3 (ASGD) needs ax, the averaged iterate, in state1");
+        FGCN_REQUIRE(!state2, FGCN_E_BADARG, "optim_step: kind 3 (ASGD) keeps one state buffer: state2 must be NULL");
     } else if (kind != FGCN_OPT_SGD)
-        FGCN_REQUIRE(state1 && state2 && aligned16(state1) && aligned16(state2), FGCN_E_BADARG, "%s: Adam needs exp_avg and exp_avg_sq",
-                     who);
+        FGCN_REQUIRE(state1 && state2 && aligned16(state1) && aligned16(state2), FGCN_E_BADARG,
+                     "optim_step: Adam needs exp_avg and exp_avg_sq");
     for (int g = 0; g < ngroups; ++g) {
         const fgcn_optim_group& h = groups[g];
-        FGCN_REQUIRE(h.lr >= 0.f && h.weight_decay >= 0.f, FGCN_E_BADARG, "%s: group %d: negative lr / weight_decay", who, g);
+        FGCN_REQUIRE(h.lr >= 0.f && h.weight_decay >= 0.f, FGCN_E_BADARG, "optim_step: group %d: negative lr / weight_decay", g);
         if (kind == FGCN_OPT_SGD) {
             FGCN_REQUIRE(h.momentum >= 0.f && (h.momentum == 0.f || (state1 && aligned16(state1))), FGCN_E_BADARG,
-                         "%s: group %d: SGD with momentum needs the momentum buffer", who, g);
+                         "optim_step: group %d: SGD with momentum needs the momentum buffer", g);
             FGCN_REQUIRE(!h.nesterov || (h.momentum > 0.f && h.dampening == 0.f), FGCN_E_BADARG,
-                         "%s: group %d: Nesterov momentum requires a momentum and zero dampening", who, g);
+                         "optim_step: group %d: Nesterov momentum requires a momentum and zero dampening", g);
         } else if (kind == FGCN_OPT_ASGD) {      // beta1, beta2, eps carry lambd, alpha, t0
             FGCN_REQUIRE(h.beta1 >= 0.f && std::isfinite(h.beta2) && std::isfinite(h.eps), FGCN_E_BADARG,
-                         "%s: group %d: ASGD: negative lambd or alpha / t0 not finite", who, g);
-            // momentum, dampening carry the step's eta, mu on the unguarded path (the guarded one reads group_sched)
-            FGCN_REQUIRE(!step || (h.momentum >= 0.f && h.dampening > 0.f && h.dampening <= 1.f), FGCN_E_BADARG,
-                         "%s: group %d: ASGD: eta must be >= 0 and mu in (0, 1] (got %g, %g)", who, g, (double)h.momentum,
+                         "optim_step: group %d: ASGD: negative lambd or alpha / t0 not finite", g);
+            // momentum, dampening carry the step's eta, mu without a guard (with one the update reads group_sched)
+            FGCN_REQUIRE(guard || (h.momentum >= 0.f && h.dampening > 0.f && h.dampening <= 1.f), FGCN_E_BADARG,
+                         "optim_step: group %d: ASGD: eta must be >= 0 and mu in (0, 1] (got %g, %g)", g, (double)h.momentum,
                          (double)h.dampening);
         } else {
             FGCN_REQUIRE(h.beta1 >= 0.f && h.beta1 < 1.f && h.beta2 >= 0.f && h.beta2 < 1.f && h.eps >= 0.f, FGCN_E_BADARG,
-                         "%s: group %d: betas / eps out of range", who, g);
-            if (step) {      // the bias corrections in double, as torch's Python scalars
-                const double bc1 = 1.0 - std::pow((double)h.beta1, (double)*step), bc2 = 1.0 - std::pow((double)h.beta2, (double)*step);
+                         "optim_step: group %d: betas / eps out of range", g);
+            if (!guard) {      // the bias corrections in double, as torch's Python scalars
+                const double bc1 = 1.0 - std::pow((double)h.beta1, (double)step), bc2 = 1.0 - std::pow((double)h.beta2, (double)step);
                 a.step_size[g] = (float)((double)h.lr / bc1);
                 a.bc2_sqrt[g] = (float)std::sqrt(bc2);
             }
         }
         a.grp[g] = h;
     }
+    if (!guard) return FGCN_OK;
+    FGCN_REQUIRE(guard->partials && guard->state, FGCN_E_BADARG, "optim_step: null partials / guard state");
+    FGCN_REQUIRE(((uintptr_t)guard->state & 7) == 0 && ((uintptr_t)guard->partials & 7) == 0, FGCN_E_ALIGN,
+                 "optim_step: guard state and partials must be 8-byte aligned");
+    FGCN_REQUIRE(guard->n_partials == fgcn_grad_norm_tiles(n), FGCN_E_BADARG, "optim_step: n_partials must be %d (got %d)",
+                 fgcn_grad_norm_tiles(n), guard->n_partials);
+    FGCN_REQUIRE(guard->max_norm >= 0.0, FGCN_E_BADARG, "optim_step: max_norm must be a number >= 0 (0: no clipping)");
+    FGCN_REQUIRE(guard->group_sched, FGCN_E_BADARG, "optim_step: null group_sched");
+    FGCN_REQUIRE(((uintptr_t)guard->group_sched & 7) == 0, FGCN_E_ALIGN, "optim_step: group_sched must be 8-byte aligned");
+    d = GuardP{};
+    d.partials = guard->partials; d.guard = static_cast<unsigned long long*>(guard->state); d.sched = guard->group_sched;
+    d.n_partials = guard->n_partials; d.skip_nonfinite = guard->skip_nonfinite != 0; d.kind = kind; d.ngroups = ngroups;
+    d.max_norm = guard->max_norm;
+    for (int g = 0; g < ngroups; ++g) d.grp[g] = groups[g];
+    q.guard = d.guard;
+    a.sched = d.sched;
     return FGCN_OK;
 }
 
 template <bool GUARDED>
-static void optim_groups_launch(const OptimGroupsP& a, int kind, int ntiles, hipStream_t s) {
+static void optim_launch(const OptimGroupsP& a, int kind, int ntiles, hipStream_t s) {
     const dim3 grid((unsigned)ntiles);
     if (kind == FGCN_OPT_SGD) hipLaunchKernelGGL((optim_step_groups_kernel<0, GUARDED>), grid, dim3(256), 0, s, a);
     else if (kind == FGCN_OPT_ADAM) hipLaunchKernelGGL((optim_step_groups_kernel<1, GUARDED>), grid, dim3(256), 0, s, a);
@@ -455,48 +332,20 @@ static void optim_groups_launch(const OptimGroupsP& a, int kind, int ntiles, hip
     else hipLaunchKernelGGL((optim_step_groups_kernel<3, GUARDED>), grid, dim3(256), 0, s, a);
 }
 
-extern "C" int fgcn_optim_step_groups(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                                      const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
-                                      long long step, void* stream) {
+extern "C" int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
+                               const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
+                               long long step, const fgcn_optim_guard* guard, void* stream) {
     OptimGroupsP a;
-    const int rc = optim_groups_prepare(a, "optim_step_groups", params, grads, state1, state2, n, kind, groups, ngroups, tiles, ntiles,
-                                        grad_scale, &step);
+    GuardP d;
+    const int rc = optim_prepare(a, d, params, grads, state1, state2, n, kind, groups, ngroups, tiles, ntiles, grad_scale, step, guard);
     if (rc != FGCN_OK) return rc;
-    optim_groups_launch<false>(a, kind, ntiles, (hipStream_t)stream);
-    return launch_status("optim_step_groups");
-}
-
-extern "C" int fgcn_optim_step_groups_guarded(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                                              const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles,
-                                              float grad_scale, double max_norm, int skip_nonfinite, double* partials, int n_partials,
-                                              void* guard, double* group_sched, void* stream) {
-    OptimGroupsP a;
-    int rc = optim_groups_prepare(a, "optim_step_groups_guarded", params, grads, state1, state2, n, kind, groups, ngroups, tiles,
-                                  ntiles, grad_scale, nullptr);
-    if (rc != FGCN_OK) return rc;
-    GuardGroupsP d{};
-    rc = guard_prepare(d.d, "optim_step_groups_guarded", n, kind, max_norm, skip_nonfinite, partials, n_partials, guard);
-    if (rc != FGCN_OK) return rc;
-    FGCN_REQUIRE(group_sched, FGCN_E_BADARG, "optim_step_groups_guarded: null group_sched");
-    FGCN_REQUIRE(((uintptr_t)group_sched & 7) == 0, FGCN_E_ALIGN, "optim_step_groups_guarded: group_sched must be 8-byte aligned");
-    a.base.guard = d.d.guard;
-    a.sched = group_sched;
-    d.sched = group_sched; d.ngroups = ngroups;
-    for (int g = 0; g < ngroups; ++g) {
-        d.lr[g] = (double)groups[g].lr; d.beta1[g] = (double)groups[g].beta1; d.beta2[g] = (double)groups[g].beta2;
-    }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(grad_sqsum_kernel, dim3((unsigned)n_partials), dim3(GN_THREADS), 0, s, grads, a.base.n4, grad_scale, partials);
-    if (kind == FGCN_OPT_ASGD) {
-        GuardAsgdP e{};
-        e.d = d.d; e.sched = group_sched; e.ngroups = ngroups;
-        for (int g = 0; g < ngroups; ++g) {
-            e.lr[g] = (double)groups[g].lr; e.lambd[g] = (double)groups[g].beta1;
-            e.alpha[g] = (double)groups[g].beta2; e.t0[g] = (double)groups[g].eps;
-        }
-        hipLaunchKernelGGL(optim_guard_decide_asgd_kernel, dim3(1), dim3(GN_THREADS), 0, s, e);
+    if (guard) {      // norm -> decision -> update, stream-ordered
+        hipLaunchKernelGGL(grad_sqsum_kernel, dim3((unsigned)guard->n_partials), dim3(GN_THREADS), 0, s, grads, a.base.n4, grad_scale,
+                           guard->partials);
+        hipLaunchKernelGGL(optim_guard_decide_kernel, dim3(1), dim3(GN_THREADS), 0, s, d);
+        optim_launch<true>(a, kind, ntiles, s);
     } else
-        hipLaunchKernelGGL(optim_guard_decide_groups_kernel, dim3(1), dim3(GN_THREADS), 0, s, d);
-    optim_groups_launch<true>(a, kind, ntiles, s);
-    return launch_status("optim_step_groups_guarded");
+        optim_launch<false>(a, kind, ntiles, s);
+    return launch_status("optim_step");
 }

@@ -9,14 +9,15 @@ unchanged) -- but re-homes every trainable parameter into ONE contiguous float32
 the data-parallel exchange (``dp.FlatGradients``), and applies the update with a single libfgcn launch
 (``fgcn_optim_step``, include/fgcn.h) whose arithmetic follows torch's formulas operation by operation.
 
-``max_grad_norm=`` / ``skip_nonfinite=`` put a guard in front of that launch that is decided on the device
-(``fgcn_optim_step_guarded``): clipping by the global gradient norm (``torch.nn.utils.clip_grad_norm_`` before ``step()``) and
+``max_grad_norm=`` / ``skip_nonfinite=`` put a guard in front of that launch that is decided on the device (the call's
+``fgcn_optim_guard``): clipping by the global gradient norm (``torch.nn.utils.clip_grad_norm_`` before ``step()``) and
 the skip of a step whose gradients are not finite, which the reference gets from ``GradScaler.step`` in its
 ``MixedPrecisionStep`` (torch_src/session/procedures/step.py:55-78) -- without a host read per step.
 
 Parameter groups (a list of dicts, as every ``torch.optim.Optimizer`` takes; ``create_optimizer(..., param_groups=[{"match": regex,
-...}])`` from a config) keep all of that: still one update launch (``fgcn_optim_step_groups``), which group an element belongs to
-comes from a tile table built and uploaded once at construction, the groups' scalars travel by value with every launch.
+...}])`` from a config) keep all of that: the same call and still one update launch, which group an element belongs to comes from a
+tile table built and uploaded once at construction (one group: every row names group 0), the groups' scalars travel by value with
+every launch.
 
 ASGD (``torch.optim.ASGD``) keeps its product, the averaged iterate ``ax``, in ``state1``; ``FlatOptimizer.averaged()`` evaluates the
 model with it.  Its step size ``eta`` and averaging weight ``mu`` are state, computed AFTER a step from that step's ``lr`` and used in
@@ -143,11 +144,9 @@ class FlatOptimizer(torch.optim.Optimizer):
         self.skip_nonfinite = bool(skip_nonfinite)
         self._max_grad_norm = max_grad_norm
         self._guarded = max_grad_norm is not None or self.skip_nonfinite
-        # several groups: the element-to-group table and the per-group step sizes of the guarded form, built and uploaded ONCE
-        self._tiles = self._sched = None
-        if len(self.param_groups) > 1 or kind == "ASGD":       # (ASGD's guarded form is the grouped call, also for one group)
-            self._tiles = torch.tensor(self.tile_table(), dtype=torch.int32).to(self.flat.device)
-            self._sched = torch.zeros((4 if kind == "ASGD" else 2) * MAX_GROUPS, dtype=torch.float64, device=self.flat.device)
+        # the element-to-group table and the per-group step sizes of the guarded form, built and uploaded ONCE
+        self._tiles = torch.tensor(self.tile_table(), dtype=torch.int32).to(self.flat.device)
+        self._sched = torch.zeros((4 if kind == "ASGD" else 2) * MAX_GROUPS, dtype=torch.float64, device=self.flat.device)
         # ASGD: (eta, mu) of the NEXT step per group, float32 values; None until the first step takes eta = lr.  On the guarded path
         # they live in _sched ({eta_use, mu_use, eta_next, mu_next} per group), written once when the path is entered
         self._eta_mu: Optional[List[Tuple[float, float]]] = None
@@ -161,7 +160,7 @@ class FlatOptimizer(torch.optim.Optimizer):
         super().add_param_group(param_group)
 
     def tile_table(self, tile4: int = _lib.OPT_TILE4) -> List[List[int]]:
-        """Rows ``[start4, count4, group]`` of fgcn_optim_step_groups' table (units: 16-byte groups of the flat buffers): runs of
+        """Rows ``[start4, count4, group]`` of fgcn_optim_step's table (units: 16-byte groups of the flat buffers): runs of
         consecutive tensors of one group, cut into rows of at most ``tile4``.  A tensor's last 16-byte group carries its <= 3 floats
         of alignment padding, so the rows cover the buffers exactly once."""
         runs: List[List[int]] = []
@@ -282,39 +281,25 @@ class FlatOptimizer(torch.optim.Optimizer):
         s1 = self.state1.data_ptr() if self.state1 is not None else None
         s2 = self.state2.data_ptr() if self.state2 is not None else None
         n = self.flat.numel()
-        stream = torch.cuda.current_stream(self.flat.device).cuda_stream
-        guard = (float(self._max_grad_norm or 0.0), int(self.skip_nonfinite), self._partials.data_ptr(), lib.fgcn_grad_norm_tiles(n),
-                 self._guard.data_ptr()) if self._guarded else None
         asgd = self.kind == "ASGD"
         if asgd and self._guarded:
             if not self._sched_seeded:         # (built guarded: eta = the lr of the first step() call)
                 self._write_sched()
         elif asgd and self._eta_mu is None:
             self._eta_mu = [(_f32(g["lr"]), 1.0) for g in self.param_groups]
-        if len(self.param_groups) > 1 or (asgd and self._guarded):     # one launch over the tile table; the groups' scalars by value
-            pairs = self._eta_mu if asgd and not self._guarded else [None] * len(self.param_groups)
-            groups = (_lib.OptimGroup * len(self.param_groups))(*[_group_scalars(g, em) for g, em in zip(self.param_groups, pairs)])
-            common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n, KINDS[self.kind], groups, len(groups),
-                      self._tiles.data_ptr(), self._tiles.shape[0], float(self.grad_scale))
-            if self._guarded:
-                _lib.check(lib.fgcn_optim_step_groups_guarded(*common, *guard, self._sched.data_ptr(), stream),
-                           "fgcn_optim_step_groups_guarded")
-            else:
-                self._steps += 1
-                _lib.check(lib.fgcn_optim_step_groups(*common, self._steps, stream), "fgcn_optim_step_groups")
+        pairs = self._eta_mu if asgd and not self._guarded else [None] * len(self.param_groups)
+        groups = (_lib.OptimGroup * len(self.param_groups))(*[_group_scalars(g, em) for g, em in zip(self.param_groups, pairs)])
+        guard = None
+        if self._guarded:         # norm -> decision -> update, stream-ordered; the step count is the device's
+            guard = _lib.OptimGuard(float(self._max_grad_norm or 0.0), int(self.skip_nonfinite), lib.fgcn_grad_norm_tiles(n),
+                                    self._partials.data_ptr(), self._guard.data_ptr(), self._sched.data_ptr())
         else:
-            g = self.param_groups[0]
-            h = _group_scalars(g, self._eta_mu[0] if asgd else None)
-            common = (self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n,
-                      KINDS[self.kind], h.lr, h.weight_decay, float(self.grad_scale),
-                      h.beta1, h.beta2, h.eps, h.momentum, h.dampening, h.nesterov)
-            if self._guarded:         # norm -> decision -> update, stream-ordered; the step count is the device's
-                rc = lib.fgcn_optim_step_guarded(*common, *guard, stream)
-                _lib.check(rc, "fgcn_optim_step_guarded")
-            else:
-                self._steps += 1
-                rc = lib.fgcn_optim_step(*common, self._steps, stream)
-                _lib.check(rc, "fgcn_optim_step")
+            self._steps += 1
+        # one launch over the tile table; the groups' scalars by value
+        rc = lib.fgcn_optim_step(self.flat.data_ptr(), self.grads.flat.data_ptr(), s1, s2, n, KINDS[self.kind], groups, len(groups),
+                                 self._tiles.data_ptr(), self._tiles.shape[0], float(self.grad_scale),
+                                 0 if self._guarded else self._steps, guard, torch.cuda.current_stream(self.flat.device).cuda_stream)
+        _lib.check(rc, "fgcn_optim_step")
         if asgd and not self._guarded:     # torch computes the next step's eta / mu after the update, from this step's lr
             self._eta_mu = [_asgd_next(g, self._steps) for g in self.param_groups]
         # the kernel wrote through raw pointers: tell autograd (and everything keyed on tensor versions, like the blocks'

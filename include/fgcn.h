@@ -689,7 +689,7 @@ int fgcn_row_softmax_fwd(const float* st, const float* adj_t, float* c_out, floa
 int fgcn_row_softmax_bwd(const float* da, const float* c, float* ds, long long rows, int V, int ld, float scale, void* stream);
 
 /* ---- the step after the path: parameter update over flat buffers ------------------- */
-/* One launch applies torch.optim's update to every trainable value of the model (reference: create_optimizer,
+/* fgcn_optim_step: one launch applies torch.optim's update to every trainable value of the model (reference: create_optimizer,
  * torch_src/session_helper.py:80-84, optimizer.step() in session/session.py:176-183):
  *   FGCN_OPT_SGD    d = g + wd*p;  buf = first step ? d : momentum*buf + (1-dampening)*d;  d = nesterov ? d + momentum*buf : buf;
  *                   p -= lr*d                                                        (state1 = buf, NULL when momentum == 0)
@@ -701,107 +701,97 @@ int fgcn_row_softmax_bwd(const float* da, const float* c, float* ds, long long r
  * g is read as grad_scale * grads (the 1/world of the data-parallel average).  params, grads, state*: float[n], 16-byte
  * aligned, n % 4 == 0 (padding elements must hold zeros in all buffers); step counts from 1.  amsgrad / maximize: not built.
  *
+ * Limit: n / 4 < 2^31 (a 34 GB parameter buffer): the tile table addresses 16-byte groups with an int.
+ *
+ * Parameter groups and the tile table.  The scalars come per group (torch.optim's param_groups: one optimizer kind, per-group scalars;
+ * groups[g] travels by value in the kernel arguments, a new learning rate costs nothing), and which group an element belongs to comes
+ * from a device-resident tile table the caller builds once:
+ *   tiles[3*t + 0] = start4   first 16-byte group (float4) of the tile inside the flat buffers
+ *   tiles[3*t + 1] = count4   16-byte groups in the tile, 1 .. FGCN_OPT_TILE4
+ *   tiles[3*t + 2] = group    0 .. ngroups-1
+ * all int (ntiles rows); one workgroup per tile.  A tile never holds values of two groups; the tiles together cover every 16-byte
+ * group of the buffers exactly once (the <= 3 padding floats behind a tensor ride in that tensor's last 16-byte group and keep their
+ * zeros).  The table is always given: one group is ngroups == 1 and a table whose rows all name group 0.  How the rows cut the buffer
+ * does not change a bit of the result.  The library cannot read the table on the host: a tile that reaches past n / 4 or names a group
+ * outside [0, ngroups) is ignored by the kernel, everything else about the table is the caller's contract.
+ * Adam's step size is (float)((double)lr_g / (1 - beta1_g^step)) and sqrt(1 - beta2_g^step) per group.  state1 may be NULL only when no
+ * SGD group has a momentum.
+ *
+ * The guard (guard != NULL; NULL: the plain update above, `step` >= 1 the host-side count) is decided on the device: clip by the
+ * global gradient norm (torch.nn.utils.clip_grad_norm_ in front of optimizer.step()) and skip a step whose gradients are not finite
+ * (what GradScaler.step does in the reference's MixedPrecisionStep, torch_src/session/procedures/step.py:55-78).  The step count lives
+ * in guard->state and `step` must be 0.  Three stream-ordered launches, nothing is read back:
+ *   1. partials[w] = sum over workgroup w's elements of ((double)grad_scale * grads[i])^2, float64, plain stores.  Elements are
+ *      assigned to threads and workgroups by index alone and every sum has a fixed order: the same buffer gives the same bits on
+ *      every call.  n_partials must be fgcn_grad_norm_tiles(n) (>= 1, monotone in n, at most FGCN_GRAD_NORM_MAX_TILES).  The square of
+ *      a float32 fits a float64 exactly, so no finite input overflows the sum (1e30 per element has a finite norm here).
+ *   2. one workgroup adds the partials in index order and writes the decision into `state`, one decision and one count for all groups:
+ *        norm  = sqrt(sum)                                                                   (float64)
+ *        coef  = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1       (clip_grad_norm_'s formula in float64; NaN propagates)
+ *        apply = isfinite(norm) || !skip_nonfinite
+ *      apply:  ++STEP; ++CLIPPED when coef < 1; SGD's first step is STEP == 1; Adam / AdamW: group_sched[2g], [2g + 1] =
+ *              lr_g / (1 - beta1_g^STEP), sqrt(1 - beta2_g^STEP) in float64 from the NEW device-side step count (what the plain
+ *              update computes on the host); ASGD: see below.
+ *      !apply: ++SKIPPED; STEP, CLIPPED and group_sched keep their values.  NORM, COEF and APPLY are written on every call.
+ *   3. the update with g = (float)(grad_scale * coef) * grads -- scaled before weight decay is added, which is where clip_grad_norm_
+ *      sits relative to optimizer.step() -- and the step's scalars taken from `state` and `group_sched`; it stores nothing when APPLY
+ *      is 0: params, state1 and state2 keep their bits.
+ * state: fgcn_optim_guard_bytes() bytes, 8-byte aligned, FGCN_GUARD_WORDS words of 8 bytes indexed by the enum below; the caller
+ * zeroes it to reset (STEP = 0: the next applied step is the first).  group_sched: 2 (ASGD: 4) * FGCN_OPT_MAX_GROUPS doubles, 8-byte
+ * aligned.  All of it is caller-owned device memory; the library allocates nothing and keeps no state.
+ *
  * ASGD's scalars.  eta and mu are float32 STATE of a parameter group, not functions of the current lr: torch computes them after a
  * step, from that step's lr, and uses them in the next one (an LR scheduler shows up one step late in eta):
  *   first step: eta = (float)lr, mu = 1;
  *   after the step that made the count STEP:  eta = (float)(lr / pow(1 + lambd*lr*STEP, alpha)),  mu = (float)(1 / max(1, STEP - t0)),
  *   both in double arithmetic.
- * Unguarded forms (fgcn_optim_step, fgcn_optim_step_groups): the slots beta1, beta2, eps carry lambd, alpha, t0 and the slots
- * momentum, dampening carry the CURRENT eta, mu (the fields of fgcn_optim_group likewise); the caller owns that state and computes the
- * next values after the call.  lr and `step` are not used by the update itself.
- * Guarded form, fgcn_optim_step_groups_guarded only: eta / mu live on the device in the caller-owned group_sched, which for this kind
- * is 4 * FGCN_OPT_MAX_GROUPS doubles, {eta_use, mu_use, eta_next, mu_next} per group.  The caller initialises eta_next = lr_g,
+ * The fields beta1, beta2, eps of fgcn_optim_group carry lambd, alpha, t0.  Without a guard momentum, dampening carry the CURRENT
+ * eta, mu; the caller owns that state and computes the next values after the call (lr and `step` are not used by the update itself).
+ * With a guard eta / mu live in group_sched, {eta_use, mu_use, eta_next, mu_next} per group.  The caller initialises eta_next = lr_g,
  * mu_next = 1 once (zeroing is NOT a reset for this kind).  Launch 2, when the step applies, copies next -> use and then computes the
- * new next from the new STEP and the group's current lr; when it does not apply all four values keep their bits.  Launch 3 reads use;
- * the momentum / dampening slots are ignored.  fgcn_optim_step_guarded has no group_sched argument and returns FGCN_E_BADARG for this
- * kind: call fgcn_optim_step_groups_guarded with one group and a one-group tile table.
- * FGCN_E_BADARG for ASGD: a null state1, a non-null state2, lambd < 0, alpha or t0 not finite, and on the unguarded forms an eta < 0 or
- * a mu outside (0, 1] (the grouped forms name the group). */
+ * new next from the new STEP and the group's current lr; launch 3 reads use; the momentum / dampening fields are ignored.
+ *
+ * FGCN_E_BADARG: a null or empty buffer, n / 4 >= 2^31, an unknown kind, step < 1 without a guard or != 0 with one, ngroups outside
+ * [1, FGCN_OPT_MAX_GROUPS], a null groups / tiles, ntiles < 1, a missing state buffer (ASGD: also a non-null state2), a group's lr /
+ * weight_decay / betas / eps / momentum out of range, Nesterov without momentum or with dampening, ASGD's lambd < 0, alpha or t0 not
+ * finite and without a guard an eta < 0 or a mu outside (0, 1] (the message names the group); a null partials / state / group_sched,
+ * a wrong n_partials, max_norm negative or NaN (0 switches clipping off).  FGCN_E_ALIGN: buffers not 16-byte aligned or n % 4 != 0,
+ * tiles not 4-byte, partials / state / group_sched not 8-byte aligned.  Every check precedes the first launch. */
 #define FGCN_OPT_SGD 0
 #define FGCN_OPT_ADAM 1
 #define FGCN_OPT_ADAMW 2
 #define FGCN_OPT_ASGD 3
-int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                    float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
-                    float momentum, float dampening, int nesterov, long long step, void* stream);
-
-/* The same update behind a guard that is decided on the device: clip by the global gradient norm (torch.nn.utils.clip_grad_norm_
- * in front of optimizer.step()) and skip a step whose gradients are not finite (what GradScaler.step does in the reference's
- * MixedPrecisionStep, torch_src/session/procedures/step.py:55-78).  Three stream-ordered launches, nothing is read back:
- *   1. partials[w] = sum over workgroup w's elements of ((double)grad_scale * grads[i])^2, float64, plain stores.  Elements are
- *      assigned to threads and workgroups by index alone and every sum has a fixed order: the same buffer gives the same bits on
- *      every call.  n_partials must be fgcn_grad_norm_tiles(n) (>= 1, monotone in n, at most FGCN_GRAD_NORM_MAX_TILES).  The square of
- *      a float32 fits a float64 exactly, so no finite input overflows the sum (1e30 per element has a finite norm here).
- *   2. one workgroup adds the partials in index order and writes the decision into `guard` (below):
- *        norm  = sqrt(sum)                                                                   (float64)
- *        coef  = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1       (clip_grad_norm_'s formula in float64; NaN propagates)
- *        apply = isfinite(norm) || !skip_nonfinite
- *      apply:  ++STEP; ++CLIPPED when coef < 1; Adam's step_size = lr / (1 - beta1^STEP) and sqrt(1 - beta2^STEP) in float64 from
- *              the NEW device-side step count (fgcn_optim_step computes the same on the host); SGD's first step is STEP == 1.
- *      !apply: ++SKIPPED; STEP and CLIPPED keep their values.  NORM, COEF and APPLY are written on every call.
- *   3. the update of fgcn_optim_step (the same kernel template) with g = (float)(grad_scale * coef) * grads -- scaled before
- *      weight decay is added, which is where clip_grad_norm_ sits relative to optimizer.step() -- and step_size / bc2_sqrt /
- *      first step taken from `guard`; it stores nothing when APPLY is 0: params, state1 and state2 keep their bits.
- * guard: fgcn_optim_guard_bytes() bytes, 8-byte aligned, FGCN_GUARD_WORDS words of 8 bytes indexed by the enum below; the caller
- * zeroes it to reset (STEP = 0: the next applied step is the first); the library allocates nothing and keeps no state.
- * max_norm == 0 switches clipping off; negative or NaN: FGCN_E_BADARG.  FGCN_E_BADARG also for a null partials / guard and a wrong
- * n_partials; FGCN_E_ALIGN for a guard or partials not 8-byte aligned; everything else as fgcn_optim_step. */
+#define FGCN_OPT_MAX_GROUPS 8
+#define FGCN_OPT_TILE4 1024
+#define FGCN_GRAD_NORM_MAX_TILES 512
+typedef struct fgcn_optim_group {
+    float lr, weight_decay;
+    float beta1, beta2, eps;       /* Adam / AdamW; ASGD: lambd, alpha, t0 */
+    float momentum, dampening;     /* SGD; ASGD (no guard): the step's eta, mu */
+    int nesterov;
+} fgcn_optim_group;
 enum fgcn_guard_word {
     FGCN_GUARD_STEP = 0,       /* int64: updates applied */
     FGCN_GUARD_SKIPPED = 1,    /* int64: calls that applied nothing (norm not finite, skip_nonfinite set) */
     FGCN_GUARD_CLIPPED = 2,    /* int64: applied updates with coef < 1 */
     FGCN_GUARD_NORM = 3,       /* float64: the last call's norm of grad_scale * grads */
     FGCN_GUARD_COEF = 4,       /* float64: the last call's clip coefficient */
-    FGCN_GUARD_APPLY = 5,      /* int64 0 / 1: the last call's decision -- this and the next three are what launch 3 reads */
+    FGCN_GUARD_APPLY = 5,      /* int64 0 / 1: the last call's decision -- this and the next one are what launch 3 reads */
     FGCN_GUARD_FIRST_STEP = 6, /* int64 0 / 1: STEP == 1 (SGD: the momentum buffer starts as the gradient) */
-    FGCN_GUARD_STEP_SIZE = 7,  /* float64: lr / (1 - beta1^STEP) (Adam / AdamW) */
-    FGCN_GUARD_BC2_SQRT = 8,   /* float64: sqrt(1 - beta2^STEP) (Adam / AdamW) */
-    FGCN_GUARD_WORDS = 9
+    FGCN_GUARD_WORDS = 7
 };
-#define FGCN_GRAD_NORM_MAX_TILES 512
+typedef struct fgcn_optim_guard {   /* NULL in the call: the plain update */
+    double max_norm;                /* 0: no clipping */
+    int skip_nonfinite, n_partials; /* n_partials == fgcn_grad_norm_tiles(n) */
+    double* partials;
+    void* state;                    /* fgcn_optim_guard_bytes() bytes, the words of enum fgcn_guard_word */
+    double* group_sched;            /* 2 (Adam/AdamW) or 4 (ASGD) doubles per group, FGCN_OPT_MAX_GROUPS groups */
+} fgcn_optim_guard;
 int fgcn_grad_norm_tiles(long long n);      /* partial sums launch 1 writes for a buffer of n floats */
 long long fgcn_optim_guard_bytes(void);
-int fgcn_optim_step_guarded(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                            float lr, float weight_decay, float grad_scale, float beta1, float beta2, float eps,
-                            float momentum, float dampening, int nesterov, double max_norm, int skip_nonfinite,
-                            double* partials, int n_partials, void* guard, void* stream);
-
-/* The same two updates over several parameter groups (torch.optim's param_groups: one optimizer kind, per-group scalars), still ONE
- * update launch.  Which group an element belongs to comes from a device-resident tile table the caller builds once:
- *   tiles[3*t + 0] = start4   first 16-byte group (float4) of the tile inside the flat buffers
- *   tiles[3*t + 1] = count4   16-byte groups in the tile, 1 .. FGCN_OPT_TILE4
- *   tiles[3*t + 2] = group    0 .. ngroups-1
- * all int (ntiles rows); one workgroup per tile.  A tile never holds values of two groups; the tiles together cover every 16-byte
- * group of the buffers exactly once (the <= 3 padding floats behind a tensor ride in that tensor's last 16-byte group and keep their
- * zeros).  The library cannot read the table on the host: a tile that reaches past n / 4 or names a group outside [0, ngroups) is
- * ignored by the kernel, everything else about the table is the caller's contract.
- * groups[g] travels by value in the kernel arguments (a new learning rate costs nothing).  Per element the arithmetic is that of
- * fgcn_optim_step with groups[g]'s scalars, operation by operation: one group here, or equal groups, give the bits of the single-group
- * call.  Adam's step size is (float)((double)lr_g / (1 - beta1_g^step)) and sqrt(1 - beta2_g^step) per group.  state1 may be NULL only
- * when no SGD group has a momentum.
- * Guarded form: the three launches of fgcn_optim_step_guarded -- the same norm kernel over the whole buffer (one global norm, the same
- * bits), one decision for all groups, one step count -- and `group_sched`, a caller-owned device buffer of 2 * FGCN_OPT_MAX_GROUPS
- * doubles, 8-byte aligned, that launch 2 fills with {lr_g / (1 - beta1_g^STEP), sqrt(1 - beta2_g^STEP)} per group for launch 3
- * (the guard words STEP_SIZE / BC2_SQRT are left alone).  FGCN_OPT_ASGD: group_sched holds 4 doubles per group and carries state
- * between calls (see "ASGD's scalars" above).
- * FGCN_E_BADARG: ngroups outside [1, FGCN_OPT_MAX_GROUPS], a null groups / tiles / group_sched, ntiles < 1, n / 4 >= 2^31, a group's lr /
- * weight_decay / betas / eps / momentum out of range or Nesterov without momentum or with dampening (the message names the group);
- * FGCN_E_ALIGN: tiles not 4-byte, group_sched not 8-byte aligned; everything else as the single-group calls. */
-#define FGCN_OPT_MAX_GROUPS 8
-#define FGCN_OPT_TILE4 1024
-typedef struct fgcn_optim_group {
-    float lr, weight_decay;
-    float beta1, beta2, eps;       /* Adam / AdamW; ASGD: lambd, alpha, t0 */
-    float momentum, dampening;     /* SGD; ASGD (unguarded): the step's eta, mu */
-    int nesterov;
-} fgcn_optim_group;
-int fgcn_optim_step_groups(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                           const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
-                           long long step, void* stream);
-int fgcn_optim_step_groups_guarded(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
-                                   const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
-                                   double max_norm, int skip_nonfinite, double* partials, int n_partials, void* guard,
-                                   double* group_sched, void* stream);
+int fgcn_optim_step(float* params, const float* grads, float* state1, float* state2, long long n, int kind,
+                    const fgcn_optim_group* groups, int ngroups, const int* tiles, int ntiles, float grad_scale,
+                    long long step, const fgcn_optim_guard* guard, void* stream);
 
 /* ---- MS-G3D data movement ------------------------------------------------------------------
  * (3 x 1) temporal max pooling with padding 1 and stride `stride` (nn.MaxPool2d((3,1), (stride,1), (1,0)) of

@@ -46,7 +46,7 @@ def test_asgd_is_built_with_torchs_names_and_defaults():
     assert (g["lr"], g["lambd"], g["alpha"], g["t0"], g["weight_decay"]) == (0.05, 1e-4, 0.75, 1e6, 0)
     for p, b in zip(m.parameters(), before):
         assert torch.equal(p, b) and p.data_ptr() % 16 == 0
-    # state1 is ax, there is no state2; the guarded form is the grouped call, so the one-group table exists
+    # state1 is ax, there is no state2; every row of the one-group table names group 0
     assert opt.state1 is not None and opt.state1.shape == opt.flat.shape and opt.state2 is None
     assert opt._tiles.dtype == torch.int32 and opt._tiles.shape[1] == 3 and opt._sched.numel() == 4 * _lib.OPT_MAX_GROUPS
     assert opt._tiles.tolist() == opt.tile_table() and all(r[2] == 0 for r in opt.tile_table())
@@ -188,35 +188,30 @@ def test_host_side_eta_mu_recurrence_is_torchs(args):
 
 
 def test_asgd_entry_points_validate_on_the_host(lib):
-    """FGCN_OPT_ASGD is declared; the single-group guarded call refuses it and names the grouped call; the ranges are checked before
-    any HIP call (host pointers here: nothing is launched)."""
+    """FGCN_OPT_ASGD is declared; the ranges are checked before any HIP call (host pointers here: nothing is launched), for one group
+    and for two, plain and with a guard."""
     import os
     import re
 
     from conftest import ROOT
     text = open(os.path.join(ROOT, "include", "fgcn.h")).read()
     assert re.search(r"#define FGCN_OPT_ASGD 3\b", text)
-    assert _lib.GUARD_WORDS == 9 and lib.fgcn_optim_guard_bytes() == 72
+    assert _lib.GUARD_WORDS == 7 and lib.fgcn_optim_guard_bytes() == 56
     buf = (C.c_double * 128)()
     p16 = (C.addressof(buf) + 15) // 16 * 16
     n, err = 16, lib.fgcn_last_error
     asgd = dict(lr=0.1, weight_decay=0.0, beta1=1e-4, beta2=0.75, eps=1e6, momentum=0.1, dampening=1.0, nesterov=0)
 
-    def single(guarded, s1=p16, s2=None, **o):
-        a = dict(asgd, **o)
-        head = (p16, p16, s1, s2, n, 3, a["lr"], a["weight_decay"], 1.0, a["beta1"], a["beta2"], a["eps"], a["momentum"], a["dampening"], 0)
-        if guarded:
-            return lib.fgcn_optim_step_guarded(*head, 1.0, 1, p16, lib.fgcn_grad_norm_tiles(n), p16, None)
-        return lib.fgcn_optim_step(*head, 1, None)
-
     def grouped(guarded, s1=p16, s2=None, overrides=({}, {})):
         groups = (_lib.OptimGroup * len(overrides))(*[_lib.OptimGroup(**dict(asgd, **o)) for o in overrides])
         head = (p16, p16, s1, s2, n, 3, groups, len(groups), p16, 1, 1.0)
         if guarded:
-            return lib.fgcn_optim_step_groups_guarded(*head, 1.0, 1, p16, lib.fgcn_grad_norm_tiles(n), p16, p16, None)
-        return lib.fgcn_optim_step_groups(*head, 1, None)
+            return lib.fgcn_optim_step(*head, 0, _lib.OptimGuard(1.0, 1, lib.fgcn_grad_norm_tiles(n), p16, p16, p16), None)
+        return lib.fgcn_optim_step(*head, 1, None, None)
 
-    assert single(True) == -1 and b"ASGD" in err() and b"fgcn_optim_step_groups_guarded" in err()
+    def single(guarded, s1=p16, s2=None, **o):
+        return grouped(guarded, s1, s2, overrides=(o,))
+
     assert single(False, beta1=-1e-4) == -1 and b"lambd" in err()
     assert single(False, s1=None) == -1 and b"state1" in err()
     assert single(False, s2=p16) == -1 and b"state2 must be NULL" in err()

@@ -179,33 +179,65 @@ def test_two_groups_match_torch_asgd_over_the_same_groups(guarded):
 
 
 def test_one_group_through_the_grouped_call_is_the_single_group_call():
-    """include/fgcn.h: one group through fgcn_optim_step_groups gives the bits of fgcn_optim_step -- for both branches of the average."""
+    """include/fgcn.h: how the rows of the tile table cut the buffer does not change a bit of the result.  One group, 2085 16-byte groups,
+    three tables -- full rows and a short one, rows of 250 (a quarter of a workgroup's 1024), unequal rows from 1 up -- for ASGD in both
+    branches of the average and for ADAM, each plain and behind a guard whose clip bites."""
     from fusion_gcn_amd import _lib
     lib = _lib.load()
-    n = 4 * 2500                                              # ten table rows of 250 16-byte groups: more than one workgroup
+    n = 4 * 2085
+    cuts = ([1024, 1024, 37], [250] * 8 + [85], [1, 1023, 512, 549])
     g = torch.Generator().manual_seed(11)
     p0, grad, ax0 = (torch.randn(n, generator=g).to(DEV) for _ in range(3))
-    tiles = torch.tensor([[s, 250, 0] for s in range(0, n // 4, 250)], dtype=torch.int32).to(DEV)
+    v0 = torch.rand(n, generator=g).to(DEV)                   # ADAM's exp_avg_sq
     stream = torch.cuda.current_stream(DEV).cuda_stream
-    for eta, mu in ((0.05, 1.0), (0.0371, 0.25)):
-        pa, pb, axa, axb = p0.clone(), p0.clone(), ax0.clone(), ax0.clone()
-        rc = lib.fgcn_optim_step(pa.data_ptr(), grad.data_ptr(), axa.data_ptr(), None, n, 3, 0.05, 0.01, 0.5, 0.05, 0.5, 2.0, eta, mu, 0,
-                                 3, stream)
+
+    def run(kind, scalars, counts, guarded):
+        """One call with the count going from 2 to 3 and grad_scale 0.5 -> (params, state1[, state2][, guard state, group_sched])."""
+        assert sum(counts) == n // 4
+        tiles = torch.tensor([[sum(counts[:i]), c, 0] for i, c in enumerate(counts)], dtype=torch.int32).to(DEV)
+        out = [p0.clone(), ax0.clone()] + ([v0.clone()] if kind == 1 else [])
+        groups = (_lib.OptimGroup * 1)(_lib.OptimGroup(*scalars))
+        guard = None
+        if guarded:
+            state = torch.zeros(_lib.GUARD_WORDS, dtype=torch.int64, device=DEV)
+            state[_lib.GUARD_STEP] = 2
+            partials = torch.zeros(_lib.GRAD_NORM_MAX_TILES, dtype=torch.float64, device=DEV)
+            sched = torch.zeros((4 if kind == 3 else 2) * _lib.OPT_MAX_GROUPS, dtype=torch.float64)
+            if kind == 3:
+                sched[:4] = torch.tensor([scalars[5], scalars[6]] * 2, dtype=torch.float32).double()      # eta, mu: use and next
+            sched = sched.to(DEV)
+            guard = _lib.OptimGuard(1.0, 1, lib.fgcn_grad_norm_tiles(n), partials.data_ptr(), state.data_ptr(), sched.data_ptr())
+            out += [state, sched]
+        rc = lib.fgcn_optim_step(out[0].data_ptr(), grad.data_ptr(), out[1].data_ptr(), out[2].data_ptr() if kind == 1 else None, n, kind,
+                                 groups, 1, tiles.data_ptr(), tiles.shape[0], 0.5, 0 if guarded else 3, guard, stream)
         _lib.check(rc, "fgcn_optim_step")
-        groups = (_lib.OptimGroup * 1)(_lib.OptimGroup(0.05, 0.01, 0.05, 0.5, 2.0, eta, mu, 0))
-        rc = lib.fgcn_optim_step_groups(pb.data_ptr(), grad.data_ptr(), axb.data_ptr(), None, n, 3, groups, 1, tiles.data_ptr(),
-                                        tiles.shape[0], 0.5, 3, stream)
-        _lib.check(rc, "fgcn_optim_step_groups")
         torch.cuda.synchronize()
-        assert torch.equal(pa, pb) and torch.equal(axa, axb)
-        assert not torch.equal(pa, p0) and (torch.equal(axa, pa) if mu == 1.0 else not torch.equal(axa, pa))
-        # and it is torch's arithmetic: one tensor, the same scalars
-        pr = p0.cpu().clone().requires_grad_()
-        pr.grad = grad.cpu() * 0.5
-        ref = torch.optim.ASGD([pr], 0.05, lambd=0.05, alpha=0.5, t0=2.0, weight_decay=0.01)
-        ref.state[pr].update(step=torch.tensor(2.0), eta=torch.tensor(eta), mu=torch.tensor(mu), ax=ax0.cpu().clone())
-        ref.step()
-        assert rel(pa, pr) < TOL and rel(axa, ref.state[pr]["ax"]) < TOL
+        if guarded:                                           # the norm of 0.5 * grad is about 45: the clip to 1 bites
+            assert int(state[_lib.GUARD_STEP]) == 3 and int(state[_lib.GUARD_CLIPPED]) == 1
+            assert 0.0 < float(state.view(torch.float64)[_lib.GUARD_COEF]) < 0.1
+        return out
+
+    asgd = [(0.05, 0.01, 0.05, 0.5, 2.0, eta, mu, 0) for eta, mu in ((0.05, 1.0), (0.0371, 0.25))]
+    adam = (0.05, 0.01, 0.9, 0.999, 1e-8, 0.0, 0.0, 0)
+    for kind, scalars in ((3, asgd[0]), (3, asgd[1]), (1, adam)):
+        for guarded in (False, True):
+            first, *others = [run(kind, scalars, counts, guarded) for counts in cuts]
+            for other in others:
+                assert len(other) == len(first) and all(torch.equal(a, b) for a, b in zip(first, other)), (kind, scalars, guarded)
+            pa, axa = first[0], first[1]
+            assert not torch.equal(pa, p0) and not torch.equal(axa, ax0)
+            if kind == 3:
+                mu = scalars[6]
+                assert torch.equal(axa, pa) if mu == 1.0 else not torch.equal(axa, pa)
+            if kind == 3 and not guarded:
+                # and it is torch's arithmetic: one tensor, the same scalars
+                eta, mu = scalars[5], scalars[6]
+                pr = p0.cpu().clone().requires_grad_()
+                pr.grad = grad.cpu() * 0.5
+                ref = torch.optim.ASGD([pr], 0.05, lambd=0.05, alpha=0.5, t0=2.0, weight_decay=0.01)
+                ref.state[pr].update(step=torch.tensor(2.0), eta=torch.tensor(eta), mu=torch.tensor(mu), ax=ax0.cpu().clone())
+                ref.step()
+                assert rel(pa, pr) < TOL and rel(axa, ref.state[pr]["ax"]) < TOL
 
 
 def test_two_optimizers_from_one_state_agree_bit_for_bit():
@@ -312,15 +344,15 @@ def test_c_abi_refuses_what_the_header_says():
     lib = _lib.load()
     n = 64
     p, grad, ax = (torch.zeros(n, device=DEV) for _ in range(3))
-    partials, guard = torch.zeros(_lib.GRAD_NORM_MAX_TILES, dtype=torch.float64, device=DEV), torch.zeros(_lib.GUARD_WORDS, dtype=torch.int64, device=DEV)
-    head = (p.data_ptr(), grad.data_ptr(), ax.data_ptr(), None, n, 3, 0.1, 0.0, 1.0)
-    rc = lib.fgcn_optim_step_guarded(*head, 1e-4, 0.75, 1e6, 0.1, 1.0, 0, 1.0, 1, partials.data_ptr(), lib.fgcn_grad_norm_tiles(n),
-                                     guard.data_ptr(), None)
-    assert rc == -1 and b"fgcn_optim_step_groups_guarded" in lib.fgcn_last_error()
-    assert lib.fgcn_optim_step(*head, -1e-4, 0.75, 1e6, 0.1, 1.0, 0, 1, None) == -1 and b"lambd" in lib.fgcn_last_error()
-    head = (p.data_ptr(), grad.data_ptr(), None, None, n, 3, 0.1, 0.0, 1.0)
-    assert lib.fgcn_optim_step(*head, 1e-4, 0.75, 1e6, 0.1, 1.0, 0, 1, None) == -1 and b"state1" in lib.fgcn_last_error()
+    tiles = torch.tensor([[0, n // 4, 0]], dtype=torch.int32).to(DEV)
+
+    def call(state1, lambd):
+        groups = (_lib.OptimGroup * 1)(_lib.OptimGroup(0.1, 0.0, lambd, 0.75, 1e6, 0.1, 1.0, 0))
+        return lib.fgcn_optim_step(p.data_ptr(), grad.data_ptr(), state1, None, n, 3, groups, 1, tiles.data_ptr(), 1, 1.0, 1, None, None)
+
+    assert call(ax.data_ptr(), -1e-4) == -1 and b"lambd" in lib.fgcn_last_error()
+    assert call(None, 1e-4) == -1 and b"state1" in lib.fgcn_last_error()
     with pytest.raises(_lib.FgcnError, match="state1"):
         _lib.check(-1, "fgcn_optim_step")
     torch.cuda.synchronize()
-    assert float(p.abs().sum()) == 0.0 and int(guard.abs().sum()) == 0
+    assert float(p.abs().sum()) == 0.0

@@ -1,6 +1,6 @@
 """Parameter groups of FlatOptimizer (a list of dicts, as every torch.optim.Optimizer takes): what can be checked without a GPU -- the
 construction and its errors, torch's state-dict layout, the element-to-group tile table the grouped kernel walks, the groups a config
-spells with ``param_groups=``, and the host-side validation of fgcn_optim_step_groups / fgcn_optim_step_groups_guarded (it precedes
+spells with ``param_groups=``, and the host-side validation of fgcn_optim_step, plain and with a guard (it precedes
 every HIP call).  The arithmetic is checked on the device in tests/test_optim_groups_gpu.py.
 
 The model is chosen so that the flat buffers hold: tensor sizes that are no multiple of 4 (4690, 67, 335, 5: padding), a 1-element
@@ -81,9 +81,9 @@ def test_construction_with_2_3_and_8_groups_and_the_limit():
     sched = torch.optim.lr_scheduler.LambdaLR(opt, [lambda e: 0.5 ** e, lambda e: 1.0, lambda e: 1.0 / (1 + e)])
     sched.step()
     assert [g["lr"] for g in opt.param_groups] == pytest.approx([0.05, 0.01, 0.05])
-    # one group given as a list of one dict is the single-group path (no table)
+    # one group given as a list of one dict: the same call, every row of its table names group 0
     one = FlatOptimizer([dict(params=list(group_model().parameters()), lr=0.3)], "SGD", 0.1)
-    assert one._tiles is None and one.param_groups[0]["lr"] == 0.3
+    assert one._tiles.tolist() == one.tile_table() and all(r[2] == 0 for r in one.tile_table()) and one.param_groups[0]["lr"] == 0.3
 
 
 def test_per_group_validation_errors():
@@ -280,15 +280,16 @@ def test_create_optimizer_builds_groups_from_a_config():
 
 def test_new_entry_points_are_declared_and_bound(lib):
     text = open(os.path.join(ROOT, "include", "fgcn.h")).read()
-    for name in ("fgcn_optim_step_groups", "fgcn_optim_step_groups_guarded"):
-        assert re.search(rf"\bint {name}\(", text) and name in _lib.SIGNATURES and hasattr(lib, name)
+    assert re.search(r"\bint fgcn_optim_step\(", text) and "fgcn_optim_step" in _lib.SIGNATURES and hasattr(lib, "fgcn_optim_step")
+    assert [n for n in _lib.SIGNATURES if n.startswith("fgcn_optim_step")] == ["fgcn_optim_step"]       # the one call
     assert re.search(r"#define FGCN_OPT_MAX_GROUPS 8\b", text) and f"#define FGCN_OPT_TILE4 {_lib.OPT_TILE4}\n" in text
-    assert C.sizeof(_lib.OptimGroup) == 32
-    fields = re.search(r"typedef struct fgcn_optim_group \{(.*?)\}", text, re.S).group(1)
-    fields = re.sub(r"/\*.*?\*/", "", fields)
-    assert re.findall(r"\b(\w+)\s*[,;]", fields) == [f[0] for f in _lib.OptimGroup._fields_]
-    # the existing ABI stays: the guard state keeps its nine words
-    assert _lib.GUARD_WORDS == 9 and lib.fgcn_optim_guard_bytes() == 72
+    for name, mirror, size in (("fgcn_optim_group", _lib.OptimGroup, 32), ("fgcn_optim_guard", _lib.OptimGuard, 40)):
+        assert C.sizeof(mirror) == size
+        fields = re.search(rf"typedef struct {name} \{{(.*?)\}}", text, re.S).group(1)
+        fields = re.sub(r"/\*.*?\*/", "", fields)
+        assert re.findall(r"\b(\w+)\s*[,;]", fields) == [f[0] for f in mirror._fields_]
+    # the guard state: seven words (the Adam step sizes live in group_sched)
+    assert re.search(r"FGCN_GUARD_WORDS = 7\b", text) and _lib.GUARD_WORDS == 7 and lib.fgcn_optim_guard_bytes() == 56
 
 
 def test_grouped_steps_validate_on_the_host(lib):
@@ -300,15 +301,16 @@ def test_grouped_steps_validate_on_the_host(lib):
     def groups_of(*overrides):
         return (_lib.OptimGroup * max(1, len(overrides)))(*[_lib.OptimGroup(**dict(adam, **o)) for o in overrides])
 
-    def call(guarded, params=p16, grads=p16, s1=p16, s2=p16, n=n, kind=1, groups=None, ngroups=None, tiles=p16, ntiles=1, step=1,
+    def call(guarded, params=p16, grads=p16, s1=p16, s2=p16, n=n, kind=1, groups=None, ngroups=None, tiles=p16, ntiles=1, step=None,
              max_norm=1.0, partials=p16, n_partials=None, guard=p16, sched=p16):
         groups = groups_of({}, {}) if groups is None else groups
         ngroups = len(groups) if ngroups is None else ngroups
         head = (params, grads, s1, s2, n, kind, groups, ngroups, tiles, ntiles, 1.0)
         if not guarded:
-            return lib.fgcn_optim_step_groups(*head, step, None)
+            return lib.fgcn_optim_step(*head, 1 if step is None else step, None, None)
         n_partials = lib.fgcn_grad_norm_tiles(n) if n_partials is None else n_partials
-        return lib.fgcn_optim_step_groups_guarded(*head, max_norm, 1, partials, n_partials, guard, sched, None)
+        return lib.fgcn_optim_step(*head, 0 if step is None else step, _lib.OptimGuard(max_norm, 1, n_partials, partials, guard, sched),
+                                   None)
 
     for guarded in (False, True):
         err = lib.fgcn_last_error
@@ -339,7 +341,8 @@ def test_grouped_steps_validate_on_the_host(lib):
         assert call(guarded, groups=groups_of({}, dict(momentum=-0.5)), **sgd) == -1
         assert call(guarded, groups=groups_of({}, dict(momentum=0.9)), s1=None, **sgd) == -1 and b"needs the momentum buffer" in err()
     assert call(False, step=0) == -1 and b"step counts from 1" in lib.fgcn_last_error()
-    # the guard's own arguments, as fgcn_optim_step_guarded
+    # the guard's own arguments
+    assert call(True, step=1) == -1 and b"step must be 0" in lib.fgcn_last_error()
     assert call(True, guard=p16 + 4) == -2 and b"8-byte aligned" in lib.fgcn_last_error()
     assert call(True, partials=p16 + 4) == -2
     assert call(True, partials=None) == -1 and b"null partials" in lib.fgcn_last_error()
@@ -349,7 +352,7 @@ def test_grouped_steps_validate_on_the_host(lib):
     assert call(True, sched=None) == -1 and b"null group_sched" in lib.fgcn_last_error()
     assert call(True, sched=p16 + 4) == -2 and b"group_sched must be 8-byte aligned" in lib.fgcn_last_error()
     with pytest.raises(_lib.FgcnError, match="group 1"):
-        _lib.check(call(False, groups=groups_of({}, dict(lr=-1.0))), "fgcn_optim_step_groups")
+        _lib.check(call(False, groups=groups_of({}, dict(lr=-1.0))), "fgcn_optim_step")
 
 
 def test_grouped_step_fails_loudly_without_a_gpu():

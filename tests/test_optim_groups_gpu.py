@@ -1,4 +1,4 @@
-"""Parameter groups of the fused optimizer step on the device (fgcn_optim_step_groups, fgcn_optim_step_groups_guarded).
+"""Parameter groups of the fused optimizer step on the device (fgcn_optim_step over several groups, plain and with a guard).
 
 Oracles: the single-group FlatOptimizer, bit for bit (the grouped kernel runs the same per-element arithmetic with a group's scalars,
 so equal groups ARE the single group and every group IS its own optimizer: no tolerance applies); torch's own optimizer objects over

@@ -1,5 +1,5 @@
 """The guard of the fused optimizer step (clip by global norm, skip non-finite steps): what can be checked without a GPU -- the
-options of FlatOptimizer / create_optimizer, the host-side validation of fgcn_optim_step_guarded (it precedes every HIP call) and
+options of FlatOptimizer / create_optimizer, the host-side validation of fgcn_optim_step's guard (it precedes every HIP call) and
 the partial-count query.  The arithmetic is checked on the device in tests/test_optim_guard_gpu.py."""
 import ctypes as C
 
@@ -92,17 +92,24 @@ def test_guarded_step_validates_on_the_host(lib):
     p16 = (p + 15) // 16 * 16
     n = 16
 
-    def call(params=p16, grads=p16, s1=p16, s2=p16, n=n, kind=1, lr=0.1, max_norm=1.0, partials=p16, n_partials=None, guard=p16):
+    tiles = (C.c_int * 3)(0, n // 4, 0)
+
+    def call(params=p16, grads=p16, s1=p16, s2=p16, n=n, kind=1, lr=0.1, max_norm=1.0, partials=p16, n_partials=None, guard=p16,
+             sched=p16, step=0):
         n_partials = lib.fgcn_grad_norm_tiles(n) if n_partials is None else n_partials
-        return lib.fgcn_optim_step_guarded(params, grads, s1, s2, n, kind, lr, 0.0, 1.0, 0.9, 0.999, 1e-8, 0.0, 0.0, 0, max_norm, 1,
-                                           partials, n_partials, guard, None)
+        group = (_lib.OptimGroup * 1)(_lib.OptimGroup(lr, 0.0, 0.9, 0.999, 1e-8, 0.0, 0.0, 0))
+        return lib.fgcn_optim_step(params, grads, s1, s2, n, kind, group, 1, tiles, 1, 1.0, step,
+                                   _lib.OptimGuard(max_norm, 1, n_partials, partials, guard, sched), None)
 
     assert call(guard=p16 + 4) == -2 and b"8-byte aligned" in lib.fgcn_last_error()           # misaligned state
     assert call(partials=p16 + 4) == -2
     assert call(n=18) == -2 and b"multiple of 4" in lib.fgcn_last_error()                     # n % 4 != 0
     assert call(grads=p16 + 8) == -2                                                          # buffers 16-byte aligned
     assert call(partials=None) == -1 and b"null partials" in lib.fgcn_last_error()            # null partial buffer
-    assert call(guard=None) == -1
+    assert call(guard=None) == -1 and b"null partials / guard state" in lib.fgcn_last_error()
+    assert call(sched=None) == -1 and b"null group_sched" in lib.fgcn_last_error()
+    assert call(sched=p16 + 4) == -2 and b"group_sched must be 8-byte aligned" in lib.fgcn_last_error()
+    assert call(step=1) == -1 and b"step must be 0" in lib.fgcn_last_error()                  # the count lives in the guard state
     assert call(params=None) == -1 and b"null pointer" in lib.fgcn_last_error()
     assert call(n_partials=2) == -1 and b"n_partials must be 1" in lib.fgcn_last_error()      # wrong partial count
     assert call(n=8192, n_partials=1) == -1 and b"n_partials must be 2" in lib.fgcn_last_error()
@@ -112,7 +119,7 @@ def test_guarded_step_validates_on_the_host(lib):
     assert call(s2=None) == -1 and b"Adam needs" in lib.fgcn_last_error()
     assert call(lr=-0.1) == -1
     with pytest.raises(_lib.FgcnError, match="max_norm"):
-        _lib.check(call(max_norm=-2.0), "fgcn_optim_step_guarded")
+        _lib.check(call(max_norm=-2.0), "fgcn_optim_step")
 
 
 def test_guarded_step_fails_loudly_without_a_gpu():

@@ -1,4 +1,4 @@
-"""The guard of the fused optimizer step on the device (fgcn_optim_step_guarded, FlatOptimizer(max_grad_norm=, skip_nonfinite=)).
+"""The guard of the fused optimizer step on the device (fgcn_optim_step with an fgcn_optim_guard, FlatOptimizer(max_grad_norm=, skip_nonfinite=)).
 
 Oracles: the float64 norm ``g.double().pow(2).sum().sqrt()`` on the CPU; torch's own ``clip_grad_norm_`` + optimizer objects on the
 CPU (tolerance 2e-6 relative, the one of tests/test_optim.py: the clip adds one float32 multiplication per element); and for the skip
@@ -46,10 +46,14 @@ def _raw_norm(lib, g, max_norm=1.0, grad_scale=1.0):
     tiles = lib.fgcn_grad_norm_tiles(n)
     partials = torch.full((tiles + 1,), -7.0, dtype=torch.float64, device=DEV)        # one guard element behind the last partial
     guard = torch.zeros(_lib.GUARD_WORDS, dtype=torch.int64, device=DEV)
-    rc = lib.fgcn_optim_step_guarded(p.data_ptr(), g.data_ptr(), None, None, n, 0, 0.0, 0.0, grad_scale, 0.0, 0.0, 0.0, 0.0, 0.0, 0,
-                                     max_norm, 1, partials.data_ptr(), tiles, guard.data_ptr(),
-                                     torch.cuda.current_stream(DEV).cuda_stream)
-    _lib.check(rc, "fgcn_optim_step_guarded")
+    sched = torch.zeros(2 * _lib.OPT_MAX_GROUPS, dtype=torch.float64, device=DEV)
+    rows = torch.arange(0, n // 4, _lib.OPT_TILE4, dtype=torch.int32)
+    table = torch.stack([rows, (n // 4 - rows).clamp(max=_lib.OPT_TILE4), torch.zeros_like(rows)], dim=1).contiguous().to(DEV)
+    group = (_lib.OptimGroup * 1)(_lib.OptimGroup(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0))
+    rc = lib.fgcn_optim_step(p.data_ptr(), g.data_ptr(), None, None, n, 0, group, 1, table.data_ptr(), table.shape[0], grad_scale, 0,
+                             _lib.OptimGuard(max_norm, 1, tiles, partials.data_ptr(), guard.data_ptr(), sched.data_ptr()),
+                             torch.cuda.current_stream(DEV).cuda_stream)
+    _lib.check(rc, "fgcn_optim_step")
     torch.cuda.synchronize()
     assert float(partials[tiles]) == -7.0 and float(p.abs().max()) == 0.0
     return guard.cpu(), partials[:tiles].cpu()
