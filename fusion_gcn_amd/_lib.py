@@ -203,6 +203,8 @@ SIGNATURES = {
     "fgcn_dropout_fwd": (_I, [_P, _P, _P, _LL, _F, C.c_ulonglong, C.c_uint, _P, _P]),
     "fgcn_dropout_bwd": (_I, [_P, _P, _P, _LL, _F, _P]),
     "fgcn_rng_advance": (_I, [_P, _P]),
+    "fgcn_clip_augment": (_I, [_P] * 6 + [_I] * 7 + [C.POINTER(C.c_float), _F, _F, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
+    "fgcn_augment_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, C.POINTER(C.c_float), _F, _F, C.POINTER(C.c_float)]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

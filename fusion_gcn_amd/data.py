@@ -18,17 +18,22 @@ the same ``(features, labels, indices)`` triples, already on the device, in one 
   * streaming: rows are gathered from the memory map into one of two pinned host buffers and copied on a side HIP stream
     while the previous step computes (double buffering; the consumer waits on an event, never on the host).
 Data-parallel ranks take contiguous shards of every global batch (``dp.shard_batch``), all ranks shuffling with the same
-seed.  torch is plumbing here (pinned memory, streams, index_select); nothing on this path calls the HIP kernels.
+seed.  torch is plumbing here (pinned memory, streams, index_select); without augmentation nothing on this path calls the HIP kernels.
+
+Augmentation (ours; the reference has none): ``ClipBatches(..., augment=Augment(...))`` replaces the row gather of each modality by one
+``fgcn_clip_augment`` call -- random rotation and scale of the joints, a random temporal window resampled to the clip's length -- whose
+random numbers are keyed by (seed, epoch, global sample index): DESIGN.md section 8f.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Iterator, Optional, Sequence, Tuple, Union
+from typing import Dict, Iterable, Iterator, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import numpy.lib.format
 import torch
 
+from ._lib import FgcnError
 from .dp import shard_batch
 
 HEADER_BYTES = 128      # data_writer.py:19: np.memmap(out_path, dtype, "w+", 128, shape)
@@ -149,17 +154,62 @@ class MultiModalDataset(torch.utils.data.Dataset):
 Features = Union[torch.Tensor, Dict[str, torch.Tensor]]
 
 
+class Augment:
+    """What ``ClipBatches(augment=...)`` does to every clip it hands out (include/fgcn.h).
+
+    ``max_angle``: the largest rotation about x, y, z in radians (each angle uniform in +-max_angle); ``scale``: the size factor is
+    uniform in 1 +- scale; ``min_window``: the shortest temporal window as a fraction of the recording (the window's length is uniform in
+    [min_window, 1], its start uniform in what is left), resampled to the clip's T frames by linear interpolation.  The temporal part
+    applies to every modality, and all modalities of a sample take the same part of the recording; the spatial part to the joints of
+    ``(M, T, V, 3)`` arrays.  ``joints = (lo, hi)`` restricts it to joints ``[lo, hi)`` (the appended sensor joints of a
+    skeleton_imu_enhanced array hold sensor axes, not positions); None = all joints of an array with three coordinates.
+    ``valid_frames``: feature id -> the number of valid frames of each sample (the window is taken from those; default: all T).
+    ``only``: the feature ids to augment (default: all); the others are gathered unchanged.  ``site`` separates two uses of one seed."""
+
+    def __init__(self, max_angle: Sequence[float] = (0.3, 0.3, 0.3), scale: float = 0.1, min_window: float = 0.5,
+                 joints: Optional[Tuple[int, int]] = None, valid_frames: Optional[Mapping[str, Sequence[int]]] = None, site: int = 0,
+                 only: Optional[Iterable[str]] = None):
+        self.max_angle = tuple(float(a) for a in max_angle)
+        if len(self.max_angle) != 3 or not all(np.isfinite(self.max_angle)):
+            raise ValueError(f"max_angle: three finite angles (x, y, z), got {max_angle!r}")
+        if not 0.0 <= scale < 1.0:
+            raise ValueError(f"scale={scale} outside [0, 1)")
+        if not 0.0 < min_window <= 1.0:
+            raise ValueError(f"min_window={min_window} outside (0, 1]")
+        if joints is not None and not 0 <= joints[0] <= joints[1]:
+            raise ValueError(f"joints={joints!r}: expected (lo, hi) with 0 <= lo <= hi")
+        self.scale, self.min_window, self.site = float(scale), float(min_window), int(site)
+        self.joints = None if joints is None else (int(joints[0]), int(joints[1]))
+        self.valid_frames = dict(valid_frames or {})
+        self.only = None if only is None else frozenset(only)
+
+    def applies_to(self, feature_id: str) -> bool:
+        return self.only is None or feature_id in self.only
+
+    def joint_range(self, sample_shape: Sequence[int]) -> Optional[Tuple[int, int]]:
+        """The joints of a sample of this shape that are rotated and scaled; None: the modality has no spatial part."""
+        if len(sample_shape) != 4 or sample_shape[3] != 3:
+            return None
+        lo, hi = self.joints or (0, sample_shape[2])
+        if hi > sample_shape[2]:
+            raise ValueError(f"joints={self.joints!r} for an array of {sample_shape[2]} joints")
+        return (lo, hi) if hi > lo else None
+
+
 class ClipBatches:
     """Iterate one epoch of ``(features, labels, indices)`` device batches over a ``MultiModalDataset``.
 
     ``batch_size`` is the global batch (the reference's config value); rank r of ``world`` receives clips
     ``[r*bs/world, (r+1)*bs/world)`` of each global batch.  ``shuffle`` permutes with ``seed + epoch`` (``set_epoch``), the
     same permutation on every rank.  ``resident``: True / False, or None = upload the split when it takes at most
-    ``resident_budget`` bytes.  Features come out float32, labels int64 (session.py:171-174)."""
+    ``resident_budget`` bytes.  Features come out float32, labels int64 (session.py:171-174).  ``augment``: None = the stored clips as
+    they are; an ``Augment`` = every clip of the modalities it names transformed on the device as it is gathered, a pure function of
+    (``seed``, the epoch ``set_epoch`` set, the clip's index in the data set) -- labels and ``indices`` are untouched, and the parameter
+    tables of the last batch are kept in ``last_params`` (feature id -> (clips, 12) tensor)."""
 
     def __init__(self, dataset: MultiModalDataset, batch_size: int, *, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
-                 resident: Optional[bool] = None, resident_budget: int = 64 << 30):
+                 resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None):
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
@@ -175,10 +225,33 @@ class ClipBatches:
         self.resident = nbytes <= resident_budget if resident is None else bool(resident)
         self.labels = torch.from_numpy(np.asarray(dataset.labels_data).astype(np.int64))
         on_gpu = self.device.type == "cuda"
+        self.augment, self.last_params = augment, {}
+        self.aug_keys = [k for k in self.keys if augment is not None and augment.applies_to(k)]
+        if augment is not None:
+            if not on_gpu:
+                raise FgcnError("ClipBatches(augment=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
+            for k in self.aug_keys:
+                if len(self.arrays[k].shape) not in (3, 5):
+                    raise FgcnError(f"augment: feature {k!r} has shape {self.arrays[k].shape}; expected (samples, M, T, V, C) or "
+                                    f"(samples, T, S) -- leave it out with Augment(only=...)")
+                augment.joint_range(self.arrays[k].shape[1:])         # (a joint range the array does not have: refused here, not mid-epoch)
+            unknown = (set(augment.valid_frames) | set(augment.only or ())) - set(self.keys)
+            if unknown:
+                raise ValueError(f"augment names features the data set does not have: {sorted(unknown)}")
+            self.valid = {}
+            for k in self.aug_keys:
+                if k in augment.valid_frames:
+                    v = np.asarray(augment.valid_frames[k])
+                    T = self.arrays[k].shape[-2] if len(self.arrays[k].shape) == 3 else self.arrays[k].shape[2]
+                    if v.shape != (n,) or v.min() < 1 or v.max() > T:
+                        raise ValueError(f"valid_frames[{k!r}]: expected {n} frame counts in [1, {T}]")
+                    self.valid[k] = torch.from_numpy(v.astype(np.int32))
         if self.resident:
             self.dev_feat = {k: torch.from_numpy(np.array(a[:n], dtype=np.float32)).to(self.device)
                              for k, a in self.arrays.items()}
             self.dev_labels = self.labels.to(self.device)
+            if augment is not None:
+                self.dev_valid = {k: v.to(self.device) for k, v in self.valid.items()}
         else:
             per = batch_size // world
             mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=on_gpu)      # noqa: E731
@@ -190,6 +263,15 @@ class ClipBatches:
             self.copy_stream = torch.cuda.Stream(self.device) if on_gpu else None
             self.copied = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
             self.consumed = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
+            if augment is not None:
+                # per slot: the augmented batch (what the consumer receives; the uploaded rows are the kernel's source), the clips' ids, and
+                # the valid frames of the slot's rows, staged and copied with the rows
+                self.aug_out = [{k: torch.empty_like(self.dev[s][k]) for k in self.aug_keys} for s in range(2)]
+                self.host_ids = [mk((per,), torch.int64) for _ in range(2)]
+                self.dev_ids = [torch.empty((per,), dtype=torch.int64, device=self.device) for _ in range(2)]
+                self.host_valid = [{k: mk((per,), torch.int32) for k in self.valid} for _ in range(2)]
+                self.dev_valid = [{k: torch.empty((per,), dtype=torch.int32, device=self.device) for k in self.valid} for _ in range(2)]
+                self.slot_rows = torch.arange(per, dtype=torch.int64, device=self.device)
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -220,6 +302,16 @@ class ClipBatches:
                     continue
             yield glob[shard_batch(len(glob), self.rank, self.world)]
 
+    def _augment(self, k: str, src: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, valid: Optional[torch.Tensor],
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Rows ``rows`` of ``src`` (the clips ``ids`` of the data set), augmented for this epoch, on the current stream."""
+        from . import ops
+        a = self.augment
+        out, params = ops.clip_augment(src, rows, ids, seed=self.seed, epoch=self.epoch, site=a.site, max_angle=a.max_angle, scale=a.scale,
+                                       min_window=a.min_window, joints=a.joint_range(src.shape[1:]), valid=valid, out=out)
+        self.last_params[k] = params
+        return out
+
     def _out(self, feats: Dict[str, torch.Tensor]) -> Features:
         return feats[self.keys[0]] if len(self.keys) == 1 else feats
 
@@ -227,7 +319,12 @@ class ClipBatches:
         if self.resident:
             for idx in self._shards():
                 di = idx.to(self.device)
-                yield self._out({k: v.index_select(0, di) for k, v in self.dev_feat.items()}), self.dev_labels.index_select(0, di), idx
+                if self.augment is None:
+                    feats = {k: v.index_select(0, di) for k, v in self.dev_feat.items()}
+                else:
+                    feats = {k: self._augment(k, v, di, di, self.dev_valid.get(k)) if k in self.aug_keys else v.index_select(0, di)
+                             for k, v in self.dev_feat.items()}
+                yield self._out(feats), self.dev_labels.index_select(0, di), idx
             return
         on_gpu = self.device.type == "cuda"
 
@@ -242,12 +339,20 @@ class ClipBatches:
                 rows = np.asarray(a[order], dtype=np.float32)
                 self.host[slot][k][:m].copy_(torch.from_numpy(rows[back]))
             self.host_lab[slot][:m].copy_(self.labels[idx])
+            if self.augment is not None:
+                self.host_ids[slot][:m].copy_(idx)
+                for k, v in self.valid.items():
+                    self.host_valid[slot][k][:m].copy_(v[idx])
             if on_gpu:
                 self.copy_stream.wait_event(self.consumed[slot])      # the consumer of the device slot's last batch is done
                 with torch.cuda.stream(self.copy_stream):
                     for k in self.keys:
                         self.dev[slot][k][:m].copy_(self.host[slot][k][:m], non_blocking=True)
                     self.dev_lab[slot][:m].copy_(self.host_lab[slot][:m], non_blocking=True)
+                    if self.augment is not None:
+                        self.dev_ids[slot][:m].copy_(self.host_ids[slot][:m], non_blocking=True)
+                        for k in self.valid:
+                            self.dev_valid[slot][k][:m].copy_(self.host_valid[slot][k][:m], non_blocking=True)
                     self.copied[slot].record(self.copy_stream)
             else:
                 for k in self.keys:
@@ -267,6 +372,10 @@ class ClipBatches:
             if on_gpu:
                 torch.cuda.current_stream(self.device).wait_event(self.copied[slot])
             feats = {k: self.dev[slot][k][:m] for k in self.keys}
+            for k in self.aug_keys:
+                # on the consumer's stream, behind the copy: the slot's rows are the source, `consumed` below covers kernel and consumer
+                feats[k] = self._augment(k, self.dev[slot][k][:m], self.slot_rows[:m], self.dev_ids[slot][:m],
+                                         self.dev_valid[slot][k][:m] if k in self.valid else None, out=self.aug_out[slot][k][:m])
             yield self._out(feats), self.dev_lab[slot][:m], idx
             if on_gpu:
                 self.consumed[slot].record(torch.cuda.current_stream(self.device))

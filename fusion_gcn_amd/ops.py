@@ -1923,3 +1923,61 @@ def rng_advance(step: torch.Tensor) -> None:
     ensure_device()
     _chk_step(step, "rng_advance.step")
     check(_lib.load().fgcn_rng_advance(step.data_ptr(), _stream()), "fgcn_rng_advance")
+
+
+# ---- augmentation of clips as the batch is gathered (fgcn_clip_augment / fgcn_augment_params) -------------------
+def _augment_scalars(max_angle, scale: float, min_window: float):
+    if len(max_angle) != 3:
+        raise _lib.FgcnError(f"augment: max_angle needs three angles (x, y, z), got {max_angle!r}")
+    return (ctypes.c_float * 3)(*[float(a) for a in max_angle]), float(scale), float(min_window)
+
+
+def augment_params(sample: int, site: int, epoch: int, seed: int, max_angle=(0.0, 0.0, 0.0), scale: float = 0.0,
+                   min_window: float = 1.0) -> list:
+    """The table row of one sample on the HOST (no device is touched): [A row-major (9), o, r, 0], by the function the kernel calls."""
+    ang, scale, min_window = _augment_scalars(max_angle, scale, min_window)
+    out = (ctypes.c_float * 12)()
+    check(_lib.load().fgcn_augment_params(int(sample) & 0xFFFFFFFF, int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, ang, scale, min_window, out), "fgcn_augment_params")
+    return list(out)
+
+
+def clip_augment(src: torch.Tensor, idx: torch.Tensor, sample_ids: torch.Tensor, *, seed: int, epoch: int, site: int = 0,
+                 max_angle=(0.0, 0.0, 0.0), scale: float = 0.0, min_window: float = 1.0, joints: Optional[Tuple[int, int]] = None,
+                 valid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """-> (out, params): out[k] = source row ``idx[k]`` of ``src``, resampled in time and (joints ``[lo, hi)`` of a skeleton with three
+    coordinates) rotated and scaled with the random numbers of sample ``sample_ids[k]`` in ``epoch`` (include/fgcn.h); params (b, 12):
+    the rows' matrix, offset and window.  src: (rows, M, T, V, C) or (rows, T, S) contiguous float32 on the device; idx, sample_ids: (b)
+    int64 -- on the device, where ``idx`` is trusted to hold rows of ``src``, or on the host, where it is checked and uploaded; valid:
+    None or (rows) int32 on the device, the valid frames of each SOURCE row; joints: None = no spatial part."""
+    ensure_device()
+    _chk(src, "clip_augment.src")
+    if src.dim() == 5:
+        outer, T, inner, C = src.shape[1], src.shape[2], src.shape[3] * src.shape[4], src.shape[4]
+    elif src.dim() == 3:
+        outer, T, inner, C = 1, src.shape[1], src.shape[2], src.shape[2]
+    else:
+        raise _lib.FgcnError(f"clip_augment.src: expected (rows, M, T, V, C) or (rows, T, S), got {tuple(src.shape)}")
+    b = idx.numel()
+    for t, name in ((idx, "idx"), (sample_ids, "sample_ids")):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != b:
+            raise _lib.FgcnError(f"clip_augment.{name}: expected ({b},) int64, got {tuple(t.shape)} {t.dtype}")
+    if not idx.is_cuda:
+        if b and (int(idx.min()) < 0 or int(idx.max()) >= src.shape[0]):
+            raise _lib.FgcnError(f"clip_augment.idx: rows outside [0, {src.shape[0]})")
+    idx, sample_ids = idx.to(src.device).contiguous(), sample_ids.to(src.device).contiguous()
+    if valid is not None and (not valid.is_cuda or valid.dtype != torch.int32 or not valid.is_contiguous() or valid.numel() != src.shape[0]):
+        raise _lib.FgcnError(f"clip_augment.valid: expected {src.shape[0]} contiguous int32 on the device, got {valid.dtype} {valid.device} "
+                             f"numel={valid.numel()}")
+    if out is None:
+        out = torch.empty((b, *src.shape[1:]), device=src.device, dtype=torch.float32)
+    _chk(out, "clip_augment.out")
+    if tuple(out.shape) != (b, *src.shape[1:]):
+        raise _lib.FgcnError(f"clip_augment.out: {tuple(out.shape)} for a batch of {(b, *src.shape[1:])}")
+    lo, hi = (0, 0) if joints is None else (int(joints[0]), int(joints[1]))
+    ang, scale, min_window = _augment_scalars(max_angle, scale, min_window)
+    params = torch.empty((b, 12), device=src.device, dtype=torch.float32)
+    check(_lib.load().fgcn_clip_augment(_p(src), idx.data_ptr(), sample_ids.data_ptr(), _p(valid), _p(out), _p(params),
+                                        b, outer, T, inner, C, lo, hi, ang, scale, min_window, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, _stream()), "fgcn_clip_augment")
+    return out, params

@@ -980,6 +980,47 @@ int fgcn_dropout_fwd(const float* x, float* y, unsigned char* keep_mask, long lo
 int fgcn_dropout_bwd(const float* dy, const unsigned char* keep_mask, float* dx, long long n, float p, void* stream);
 int fgcn_rng_advance(unsigned long long* step, void* stream);
 
+/* Augmentation of clips as the batch is gathered (data.ClipBatches(augment=...)).  Row k of `out` is source row
+ * idx[k] of `src`, resampled in time and -- joints with three coordinates -- rotated and scaled, with random numbers that are a pure
+ * function of (seed, site, epoch, sample_ids[k]): the same bits in any batch order, on any number of ranks, on the resident and the
+ * streaming path, and in a second run.  A sample is (outer, T, inner) float32: a skeleton (M, T, V, C) is (M, T, V * C), an inertial
+ * signal (T, S) is (1, T, S), patch features (M, T, V, F) are (M, T, V * F).
+ *
+ * Random words: two Philox blocks per sample, philox(ctr = {(unsigned)sample, site, epoch, j}, key = {lo32(seed), hi32(seed)}), j = 0, 1.
+ * A word w gives the uniform u = (float)(w >> 8) * 2^-24, exact in float32, in [0, 1).  All arithmetic below is float32, every product
+ * and sum rounded on its own unless an fma is named.
+ *
+ * Parameters (the table row of the sample, 12 floats): with u0..u3 the words of block 0 and u4, u5 words 0, 1 of block 1,
+ *     theta_a = (2 u_a - 1) * max_angle[a], a = x, y, z (2u - 1 is exact);   s = 1 + (2 u3 - 1) * scale;
+ *     A = s * Rz(theta_z) * Ry(theta_y) * Rx(theta_x), each entry formed as s * (the sum of its one or two products of sinf / cosf values);
+ *     r = min_window + u4 * (1 - min_window);   o = u5 * (1 - r), formed as u5 * ((1 - u4) * (1 - min_window)) (1 - u4 is exact);
+ *     row = {A row-major (9), o, r, 0}.
+ * Zero angles and scale and min_window = 1 give exactly the identity matrix, o = 0 and r = 1.
+ *
+ * Temporal part, all of `inner`: v = valid[idx[k]] (valid == NULL: T; a value outside [1, T] is clamped into it), output frame t reads
+ *     pos = (o + r * t / (T - 1)) * (v - 1), formed as fma(r * t, (v - 1) / (T - 1), o * (v - 1)) (the quotient counts as 0 for T == 1);
+ *     f0 = floor(pos) clamped to [0, v - 1], f1 = min(f0 + 1, v - 1), w = pos - f0, y = fma(w, x[f1] - x[f0], x[f0]).
+ * Spatial part, after the interpolation, joints [joint_lo, joint_hi) of a sample with C == 3 (inner = V * 3):
+ *     y'_c = fma(A[c][2], y_2, fma(A[c][1], y_1, A[c][0] * y_0)).  No translation: a zero joint stays zero.
+ * Identity: with zero angles and scale, min_window = 1 and valid == NULL (or T), pos == t and w == 0 exactly and `out` equals the gathered
+ * rows (x[f0] + 0 * (x[f0] - x[f0]), then 1 * y_0 + 0 * y_1 + 0 * y_2).
+ *
+ * fgcn_clip_augment: src (rows, outer, T, inner), idx / sample_ids (b) 8-byte integers on the device (idx may repeat and need not be sorted;
+ * every idx[k] must be a row of src -- the caller's duty; the streaming path passes idx = 0..b-1 and the real ids), valid NULL or 4-byte
+ * integers indexed by SOURCE row, out (b, outer, T, inner), params (b, 12) receives the table.  Two launches: one lane per row forms the
+ * table, then one lane per (row, outer, frame, joint) -- per element when no joint is rotated -- reads it back.  Rows need 4-byte alignment only.
+ * FGCN_E_BADARG before any launch: a null pointer (valid excepted); b, outer, T or inner <= 0; C <= 0 or inner % C != 0; a joint range
+ * outside 0 <= joint_lo <= joint_hi <= inner / C; joint_hi > joint_lo with C != 3; min_window outside (0, 1]; scale outside [0, 1); an
+ * angle that is not finite; out == src.
+ *
+ * fgcn_augment_params: the HOST copy of the table row (no device is touched), computed by the function the kernel calls; the device's row
+ * differs from it by the two sinf / cosf implementations alone.  The same refusals for its arguments. */
+int fgcn_clip_augment(const float* src, const long long* idx, const long long* sample_ids, const int* valid, float* out, float* params, int b,
+                      int outer, int T, int inner, int C, int joint_lo, int joint_hi, const float max_angle[3], float scale, float min_window,
+                      unsigned long long seed, unsigned site, unsigned epoch, void* stream);
+int fgcn_augment_params(unsigned sample, unsigned site, unsigned epoch, unsigned long long seed, const float max_angle[3], float scale,
+                        float min_window, float out12[12]);
+
 #ifdef __cplusplus
 }
 #endif
