@@ -205,6 +205,7 @@ SIGNATURES = {
     "fgcn_rng_advance": (_I, [_P, _P]),
     "fgcn_clip_augment": (_I, [_P] * 6 + [_I] * 7 + [C.POINTER(C.c_float), _F, _F, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "fgcn_augment_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, C.POINTER(C.c_float), _F, _F, C.POINTER(C.c_float)]),
+    "fgcn_clip_normalize": (_I, [_P] * 5 + [_I] * 10 + [_P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)
@@ -214,6 +215,7 @@ CE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}       # enum fgcn_ce_reduction
 # enum fgcn_guard_word: the 8-byte words of the guarded optimizer step's state (include/fgcn.h)
 GUARD_STEP, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM, GUARD_COEF, GUARD_APPLY, GUARD_FIRST_STEP, GUARD_WORDS = range(8)
 GRAD_NORM_MAX_TILES = 512   # FGCN_GRAD_NORM_MAX_TILES
+NORMALIZE_MAX_T = 4096      # FGCN_NORMALIZE_MAX_T
 
 _lib = None
 

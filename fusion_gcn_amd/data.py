@@ -23,6 +23,11 @@ seed.  torch is plumbing here (pinned memory, streams, index_select); without au
 Augmentation (ours; the reference has none): ``ClipBatches(..., augment=Augment(...))`` replaces the row gather of each modality by one
 ``fgcn_clip_augment`` call -- random rotation and scale of the joints, a random temporal window resampled to the clip's length -- whose
 random numbers are keyed by (seed, epoch, global sample index): DESIGN.md section 8f.
+
+Normalisation (reference: util/preprocessing/skeleton.py:normalize_skeleton, an offline per-clip loop): ``ClipBatches(...,
+normalize=Normalize(...))`` takes RAW skeleton clips -- null frames padded, the centre joint of the first body at the origin, spine to z,
+shoulders to x -- with ``fgcn_clip_normalize``: once at upload on the resident path, per batch behind the copy on the streaming path, and
+before the augmentation where both are given: DESIGN.md section 8g.
 """
 from __future__ import annotations
 
@@ -196,6 +201,59 @@ class Augment:
         return (lo, hi) if hi > lo else None
 
 
+class Normalize:
+    """What ``ClipBatches(normalize=...)`` does to every raw skeleton clip (include/fgcn.h): the reference's
+    ``normalize_skeleton(skeleton, origin_joint, z_axis_joints, x_axis_joints)``.
+
+    ``origin_joint``: the joint of the first body that is moved to the origin; ``z_axis_joints`` / ``x_axis_joints``: the pair of joints
+    whose bone is turned to the z / x axis (None: no such pass; a pair needs three coordinates).  ``only``: the feature ids to normalise
+    (default: all); the others are handed out as stored."""
+
+    def __init__(self, origin_joint: int, z_axis_joints: Optional[Sequence[int]] = None, x_axis_joints: Optional[Sequence[int]] = None,
+                 only: Optional[Iterable[str]] = None):
+        if isinstance(origin_joint, bool) or not isinstance(origin_joint, (int, np.integer)) or origin_joint < 0:
+            raise ValueError(f"origin_joint={origin_joint!r}: expected a joint number >= 0")
+        self.origin_joint = int(origin_joint)
+        self.z_axis_joints, self.x_axis_joints = self._pair(z_axis_joints, "z_axis_joints"), self._pair(x_axis_joints, "x_axis_joints")
+        self.only = None if only is None else frozenset(only)
+
+    @staticmethod
+    def _pair(pair, name: str) -> Optional[Tuple[int, int]]:
+        if pair is None:
+            return None
+        pair = tuple(pair)
+        if len(pair) != 2 or any(isinstance(j, bool) or not isinstance(j, (int, np.integer)) or j < 0 for j in pair) or pair[0] == pair[1]:
+            raise ValueError(f"{name}={pair!r}: expected two different joint numbers >= 0")
+        return int(pair[0]), int(pair[1])
+
+    @classmethod
+    def for_dataset(cls, name: str, only: Optional[Iterable[str]] = None) -> "Normalize":
+        """The reference's joint numbers for a data set (``"utd_mhad"``, ``"mmact"``, ``"ntu_rgb_d"``; its constants module holds them)."""
+        from .util.dynamic_import import import_dataset_constants
+        got = import_dataset_constants(name, ["skeleton_center_joint", "skeleton_z_joints", "skeleton_x_joints"])
+        if len(got) != 3:
+            raise ValueError(f"data set {name!r} has no skeleton normalisation constants")
+        return cls(*got, only=only)
+
+    def applies_to(self, feature_id: str) -> bool:
+        return self.only is None or feature_id in self.only
+
+    def check_shape(self, feature_id: str, shape: Sequence[int]) -> None:
+        """Refuses an array (samples, M, T, V, C) this normalisation cannot take -- at construction, not mid-epoch."""
+        if len(shape) != 5:
+            raise FgcnError(f"normalize: feature {feature_id!r} has shape {tuple(shape)}; expected (samples, M, T, V, C) -- leave it out "
+                            f"with Normalize(only=...)")
+        V, C = shape[3], shape[4]
+        pairs = [p for p in (self.z_axis_joints, self.x_axis_joints) if p is not None]
+        if C not in (2, 3) or (pairs and C != 3):
+            raise FgcnError(f"normalize: feature {feature_id!r} has {C} coordinates; expected 2 or 3, and 3 with an axis pair")
+        if max([self.origin_joint] + [j for p in pairs for j in p]) >= V:
+            raise FgcnError(f"normalize: feature {feature_id!r} has {V} joints; the joint numbers {self.origin_joint}, {pairs} need more")
+
+
+NORMALIZE_CHUNK = 2048      # clips per fgcn_clip_normalize call when a resident split is normalised at upload
+
+
 class ClipBatches:
     """Iterate one epoch of ``(features, labels, indices)`` device batches over a ``MultiModalDataset``.
 
@@ -205,11 +263,15 @@ class ClipBatches:
     ``resident_budget`` bytes.  Features come out float32, labels int64 (session.py:171-174).  ``augment``: None = the stored clips as
     they are; an ``Augment`` = every clip of the modalities it names transformed on the device as it is gathered, a pure function of
     (``seed``, the epoch ``set_epoch`` set, the clip's index in the data set) -- labels and ``indices`` are untouched, and the parameter
-    tables of the last batch are kept in ``last_params`` (feature id -> (clips, 12) tensor)."""
+    tables of the last batch are kept in ``last_params`` (feature id -> (clips, 12) tensor).  ``normalize``: None = the stored clips are
+    taken as they are; a ``Normalize`` = the (samples, M, T, V, C) arrays it names hold RAW skeletons and are normalised on the device
+    -- a resident split once, at construction; a streamed batch behind its copy -- before any augmentation; ``last_plan`` (feature id ->
+    (frame_map, params)) keeps the tables of the last call."""
 
     def __init__(self, dataset: MultiModalDataset, batch_size: int, *, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
-                 resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None):
+                 resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None,
+                 normalize: Optional[Normalize] = None):
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
@@ -246,9 +308,24 @@ class ClipBatches:
                     if v.shape != (n,) or v.min() < 1 or v.max() > T:
                         raise ValueError(f"valid_frames[{k!r}]: expected {n} frame counts in [1, {T}]")
                     self.valid[k] = torch.from_numpy(v.astype(np.int32))
+        self.normalize, self.last_plan = normalize, {}
+        self.norm_keys = [k for k in self.keys if normalize is not None and normalize.applies_to(k)]
+        if normalize is not None:
+            if not on_gpu:
+                raise FgcnError("ClipBatches(normalize=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
+            unknown = set(normalize.only or ()) - set(self.keys)
+            if unknown:
+                raise ValueError(f"normalize names features the data set does not have: {sorted(unknown)}")
+            for k in self.norm_keys:
+                normalize.check_shape(k, self.arrays[k].shape)
         if self.resident:
             self.dev_feat = {k: torch.from_numpy(np.array(a[:n], dtype=np.float32)).to(self.device)
                              for k, a in self.arrays.items()}
+            for k in self.norm_keys:                        # once, at upload: nothing is done per batch
+                raw, self.dev_feat[k] = self.dev_feat[k], torch.empty_like(self.dev_feat[k])
+                for lo in range(0, n, NORMALIZE_CHUNK):
+                    rows = torch.arange(lo, min(lo + NORMALIZE_CHUNK, n), dtype=torch.int64, device=self.device)
+                    self._normalize(k, raw, rows, out=self.dev_feat[k][lo:lo + len(rows)])
             self.dev_labels = self.labels.to(self.device)
             if augment is not None:
                 self.dev_valid = {k: v.to(self.device) for k, v in self.valid.items()}
@@ -263,6 +340,11 @@ class ClipBatches:
             self.copy_stream = torch.cuda.Stream(self.device) if on_gpu else None
             self.copied = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
             self.consumed = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
+            if augment is not None or normalize is not None:
+                self.slot_rows = torch.arange(per, dtype=torch.int64, device=self.device)
+            if normalize is not None:
+                # per slot: the normalised batch (the uploaded rows are the kernel's source); the slot's `consumed` event covers it
+                self.norm_out = [{k: torch.empty_like(self.dev[s][k]) for k in self.norm_keys} for s in range(2)]
             if augment is not None:
                 # per slot: the augmented batch (what the consumer receives; the uploaded rows are the kernel's source), the clips' ids, and
                 # the valid frames of the slot's rows, staged and copied with the rows
@@ -271,7 +353,6 @@ class ClipBatches:
                 self.dev_ids = [torch.empty((per,), dtype=torch.int64, device=self.device) for _ in range(2)]
                 self.host_valid = [{k: mk((per,), torch.int32) for k in self.valid} for _ in range(2)]
                 self.dev_valid = [{k: torch.empty((per,), dtype=torch.int32, device=self.device) for k in self.valid} for _ in range(2)]
-                self.slot_rows = torch.arange(per, dtype=torch.int64, device=self.device)
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -310,6 +391,15 @@ class ClipBatches:
         out, params = ops.clip_augment(src, rows, ids, seed=self.seed, epoch=self.epoch, site=a.site, max_angle=a.max_angle, scale=a.scale,
                                        min_window=a.min_window, joints=a.joint_range(src.shape[1:]), valid=valid, out=out)
         self.last_params[k] = params
+        return out
+
+    def _normalize(self, k: str, src: torch.Tensor, rows: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """Rows ``rows`` of the raw clips ``src``, normalised into ``out``, on the current stream."""
+        from . import ops
+        z = self.normalize
+        out, frame_map, params = ops.clip_normalize(src, rows, origin_joint=z.origin_joint, z_axis_joints=z.z_axis_joints,
+                                                    x_axis_joints=z.x_axis_joints, out=out)
+        self.last_plan[k] = (frame_map, params)
         return out
 
     def _out(self, feats: Dict[str, torch.Tensor]) -> Features:
@@ -372,9 +462,12 @@ class ClipBatches:
             if on_gpu:
                 torch.cuda.current_stream(self.device).wait_event(self.copied[slot])
             feats = {k: self.dev[slot][k][:m] for k in self.keys}
-            for k in self.aug_keys:
+            for k in self.norm_keys:
                 # on the consumer's stream, behind the copy: the slot's rows are the source, `consumed` below covers kernel and consumer
-                feats[k] = self._augment(k, self.dev[slot][k][:m], self.slot_rows[:m], self.dev_ids[slot][:m],
+                feats[k] = self._normalize(k, self.dev[slot][k][:m], self.slot_rows[:m], out=self.norm_out[slot][k][:m])
+            for k in self.aug_keys:
+                # the same for the augmentation, which reads the normalised rows where there are any
+                feats[k] = self._augment(k, feats[k], self.slot_rows[:m], self.dev_ids[slot][:m],
                                          self.dev_valid[slot][k][:m] if k in self.valid else None, out=self.aug_out[slot][k][:m])
             yield self._out(feats), self.dev_lab[slot][:m], idx
             if on_gpu:

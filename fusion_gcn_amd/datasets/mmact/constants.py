@@ -20,6 +20,12 @@ _parent = {0: 1, 2: 1, 5: 1, 8: 1, 11: 1,
 skeleton_edges = edges_from_parents(_parent)
 center_joint = 1
 
+# normalize_skeleton's arguments (reference datasets/mmact/constants.py:20): the neck at the origin; the joints are two-dimensional
+# image coordinates, so nothing is rotated
+skeleton_center_joint = 1
+skeleton_z_joints = None
+skeleton_x_joints = None
+
 num_joints = len(skeleton_joints)
 num_classes = 35
 num_subjects = 20

@@ -21,6 +21,12 @@ _parent = {0: 1, 1: 20, 2: 20, 3: 2, 4: 20, 5: 4, 6: 5, 7: 6,
 skeleton_edges = edges_from_parents(_parent)
 center_joint = 20
 
+# normalize_skeleton's arguments (reference datasets/ntu_rgb_d/preprocess_data.py:67): spine_center at the origin, spine_base ->
+# spine_center to z, the shoulders to x
+skeleton_center_joint = 1
+skeleton_z_joints = (0, 1)
+skeleton_x_joints = (4, 8)
+
 num_joints = len(skeleton_joints)
 num_classes = 60
 num_subjects = 40

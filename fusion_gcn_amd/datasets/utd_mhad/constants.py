@@ -2,7 +2,8 @@
 
 Restates the tables the model layer reads from the reference's
 datasets/utd_mhad/constants.py:63-112 (skeleton_joints, skeleton_edges oriented towards the
-shoulder centre, center_joint, num_joints, num_classes).  Preprocessing constants are out of scope.
+shoulder centre, center_joint, num_joints, num_classes) and, for data.Normalize.for_dataset, the joint numbers its skeleton
+normalisation uses (constants.py:26-28).
 """
 from .._skeleton import edges_from_parents
 
@@ -20,6 +21,11 @@ _parent = {0: 1, 2: 1, 4: 1, 8: 1, 3: 2, 12: 3, 16: 3,
            13: 12, 14: 13, 15: 14, 17: 16, 18: 17, 19: 18}
 skeleton_edges = edges_from_parents(_parent)
 center_joint = 1
+
+# normalize_skeleton's arguments for the Kinect v1 skeleton: spine at the origin, hip_center -> spine to z, the shoulders to x
+skeleton_center_joint = 2
+skeleton_z_joints = (3, 2)
+skeleton_x_joints = (4, 8)
 
 num_joints = len(skeleton_joints)
 num_classes = 27

@@ -1981,3 +1981,46 @@ def clip_augment(src: torch.Tensor, idx: torch.Tensor, sample_ids: torch.Tensor,
                                         b, outer, T, inner, C, lo, hi, ang, scale, min_window, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                         int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, _stream()), "fgcn_clip_augment")
     return out, params
+
+
+# ---- normalisation of raw skeleton clips as the batch is gathered (fgcn_clip_normalize) --------------------------
+def _joint_pair(pair, name: str) -> Tuple[int, int]:
+    if pair is None:
+        return -1, -1
+    if len(pair) != 2 or int(pair[0]) < 0 or int(pair[1]) < 0:
+        raise _lib.FgcnError(f"clip_normalize.{name}: two joint numbers >= 0 or None, got {pair!r}")
+    return int(pair[0]), int(pair[1])
+
+
+def clip_normalize(src: torch.Tensor, idx: torch.Tensor, *, origin_joint: int, z_axis_joints: Optional[Tuple[int, int]] = None,
+                   x_axis_joints: Optional[Tuple[int, int]] = None, out: Optional[torch.Tensor] = None):
+    """-> (out, frame_map, params): out[k] = source row ``idx[k]`` of ``src`` normalised as the reference's ``normalize_skeleton`` does
+    (include/fgcn.h): null frames padded, joint ``origin_joint`` of body 0 at the origin, the bone ``z_axis_joints`` turned to the z axis
+    and ``x_axis_joints`` to the x axis (None: no such pass; pairs need three coordinates).  frame_map (b, M, T) int32: the source frame of
+    every output frame; params (b, 12) float64: R row-major, z applied, x applied, valid bodies.  src: (rows, M, T, V, C) contiguous
+    float32 on the device, C = 2 or 3; idx: (b) int64 -- on the device, where it is trusted to hold rows of ``src``, or on the host,
+    where it is checked and uploaded."""
+    ensure_device()
+    _chk(src, "clip_normalize.src")
+    if src.dim() != 5:
+        raise _lib.FgcnError(f"clip_normalize.src: expected (rows, M, T, V, C), got {tuple(src.shape)}")
+    M, T, V, C = src.shape[1:]
+    b = idx.numel()
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise _lib.FgcnError(f"clip_normalize.idx: expected ({b},) int64, got {tuple(idx.shape)} {idx.dtype}")
+    if not idx.is_cuda:
+        if b and (int(idx.min()) < 0 or int(idx.max()) >= src.shape[0]):
+            raise _lib.FgcnError(f"clip_normalize.idx: rows outside [0, {src.shape[0]})")
+    idx = idx.to(src.device).contiguous()
+    z0, z1 = _joint_pair(z_axis_joints, "z_axis_joints")
+    x0, x1 = _joint_pair(x_axis_joints, "x_axis_joints")
+    if out is None:
+        out = torch.empty((b, M, T, V, C), device=src.device, dtype=torch.float32)
+    _chk(out, "clip_normalize.out")
+    if tuple(out.shape) != (b, M, T, V, C):
+        raise _lib.FgcnError(f"clip_normalize.out: {tuple(out.shape)} for a batch of {(b, M, T, V, C)}")
+    frame_map = torch.empty((b, M, T), device=src.device, dtype=torch.int32)
+    params = torch.empty((b, 12), device=src.device, dtype=torch.float64)
+    check(_lib.load().fgcn_clip_normalize(_p(src), idx.data_ptr(), _p(out), _p(frame_map), _p(params), b, M, T, V, C, int(origin_joint),
+                                          z0, z1, x0, x1, _stream()), "fgcn_clip_normalize")
+    return out, frame_map, params

@@ -1021,6 +1021,40 @@ int fgcn_clip_augment(const float* src, const long long* idx, const long long* s
 int fgcn_augment_params(unsigned sample, unsigned site, unsigned epoch, unsigned long long seed, const float max_angle[3], float scale,
                         float min_window, float out12[12]);
 
+/* Normalisation of raw skeleton clips as the batch is gathered (data.ClipBatches(normalize=...)): the reference's
+ * normalize_skeleton(skeleton, origin_joint, z_axis_joints, x_axis_joints) (util/preprocessing/skeleton.py) on source row idx[k].  A clip
+ * is (M, T, V, C) float32, C = 2 or 3; the result is a pure function of the clip and the joint numbers.
+ *
+ * Definitions.  A frame of a body is NULL when all its V * C values are zero (-0 counts as zero, a NaN as a value); a body is INVALID when
+ * all its frames are null; a joint of a frame is MISSING when its C values are zero.  (The reference tests sum() == 0 instead: the two
+ * differ only where non-zero values cancel exactly, and there this definition is the one that holds.)
+ *
+ * Stage 1, the frame map of every body (pad_null_frames): output frame t is source frame map[t].  If frame 0 is null, base = the non-null
+ * frames in order and f = their number; otherwise f = the last non-null frame + 1 and base = 0 .. f-1 (null frames inside [0, f) stay).
+ * map[t] = base[t] for t < f, base[(t - f) mod f] for t >= f.  An invalid body has the identity map and comes out as zeros.
+ * Stage 2 (move_skeleton_origin): centre[t] = joint `origin` of body 0 at ITS mapped frame t (zero when body 0 is invalid or the joint
+ * is missing there); every joint becomes x - centre[t], a missing joint stays zero.
+ * Stage 3 (parallelize_joints_to_axis, twice; C == 3): the pass for the pair (j0, j1) and a unit axis takes bone = p[j1] - p[j0] from body
+ * 0, output frame 0, of the clip as it stands -- after stage 2 for the z pass (z0, z1) -> (0, 0, 1), after the z pass for the x pass
+ * (x0, x1) -> (1, 0, 0).  The pass is skipped if sum|bone| < 1e-6; with k = bone x axis and theta = acos(bone . axis / |bone|) it is
+ * skipped if sum|k| < 1e-6 or |theta| < 1e-6 (so a bone antiparallel to the axis is left alone, as in the reference); otherwise every
+ * joint is multiplied by the Rodrigues matrix I + sin(theta) K + (1 - cos(theta)) K^2 of k / |k|.  The argument of acos is clamped to
+ * [-1, 1]: the reference would return NaN where a rounding takes it outside.
+ * Arithmetic: float64 from the float32 input throughout -- the centred coordinates, both matrices, their product R = R_x R_z, and
+ * R (x - centre) -- and ONE rounding to float32 at the store.  With no rotation applied the stored value is float32(x - centre).
+ *
+ * fgcn_clip_normalize: src (rows, M, T, V, C), idx (b) 8-byte integers on the device (they may repeat and need not be sorted; every idx[k]
+ * must be a row of src -- the caller's duty), out (b, M, T, V, C), frame_map (b, M, T) 4-byte integers and params (b, 12) float64 receive
+ * the tables: params[0..8] = R row-major, [9] = 1.0 if the z rotation was applied, [10] the same for x, [11] the number of valid bodies.
+ * z0 < 0: no z pair; x0 < 0: no x pair.  Two launches: one workgroup per clip forms its tables, then one lane per (clip, body, frame,
+ * joint) gathers through them (a frame number read back is clamped into [0, T)).  Rows need 4-byte alignment only.
+ * FGCN_E_BADARG before any launch: a null pointer; b, M, T or V <= 0; V > 64; C not 2 or 3; T > FGCN_NORMALIZE_MAX_T; origin outside
+ * [0, V); a pair whose joints are outside [0, V) or equal; a pair with C != 3; out == src (the gather reads other frames); b * M >= 2^31
+ * (one grid does not hold more bodies). */
+#define FGCN_NORMALIZE_MAX_T 4096
+int fgcn_clip_normalize(const float* src, const long long* idx, float* out, int* frame_map, double* params, int b, int M, int T, int V, int C,
+                        int origin, int z0, int z1, int x0, int x1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
