@@ -16,6 +16,7 @@ from typing import Dict, Iterator, List, Tuple
 import numpy as np
 import torch
 
+import guarded
 from conftest import rel_l2
 
 ALL_MODES = ("f32", "bf16x3", "f16x2", "bf16")
@@ -235,7 +236,9 @@ def poison(device) -> None:
 
 
 class BlockRun:
-    """One case's module on the device; ``run`` = one poisoned forward + backward under an entry's options, with the plan really used captured"""
+    """One case's module on the device; ``run`` = one poisoned forward + backward under an entry's options, with the plan really used captured.
+    The run is made on guarded allocations (tests/guarded.py) and ends with the check of their margins: a route that stores outside a tensor
+    the host layer allocated fails the entry.  ``poison`` stays: it reaches what autograd allocates in C++, the guard does not."""
 
     def __init__(self, case: Case, device):
         self.case, self.device = case, device
@@ -244,10 +247,19 @@ class BlockRun:
         ora = oracle_case(case, "train")
         xc = ora["x"].float().permute(0, 2, 3, 1)
         pad = self.blk.cfg.cx - case.cin
-        self.x_cl = (torch.nn.functional.pad(xc, (0, pad)) if pad else xc).contiguous().to(device)      # (the three lines of forward_nchw)
-        self.probe_cl = ora["probe"].float().permute(0, 2, 3, 1).contiguous().to(device)
+        self.x_host = (torch.nn.functional.pad(xc, (0, pad)) if pad else xc).contiguous()      # (the three lines of forward_nchw)
+        self.probe_host = ora["probe"].float().permute(0, 2, 3, 1).contiguous()
 
-    def run(self, entry: Entry, phase: str, inject=None) -> dict:
+    def run(self, entry: Entry, phase: str, inject=None, guard: bool = True) -> dict:
+        """``guard=False``: the same run on the allocator's own tensors (for the test that the guard changes no bit)"""
+        if not guard:
+            return self._run(entry, phase, inject)
+        with guarded.Guard() as g:
+            res = self._run(entry, phase, inject)
+            g.check()
+        return res
+
+    def _run(self, entry: Entry, phase: str, inject) -> dict:
         from fusion_gcn_amd import block, ops
         from oracle import relu_masks as RM
         blk, dev = self.blk, self.device
@@ -266,14 +278,16 @@ class BlockRun:
         try:
             with ops.context(entry.plan.mode) as ctx:
                 ctx.paths = entry.options.copy()
+                x_cl = guarded.put(self.x_host, torch.bfloat16 if entry.half else None, device=dev)       # NaN on both sides of the inputs too
+                probe_cl = guarded.put(self.probe_host, device=dev)
                 poison(dev)
-                xg = (self.x_cl.bfloat16() if entry.half else self.x_cl.clone()).requires_grad_(True)
+                xg = x_cl.requires_grad_(True)
                 out = blk(xg, out_half=entry.half)          # the module itself: the forward hook sees the STBlockFunction node
                 signs = taps.sign_images()[0]
                 if inject is not None:
                     taps.inject([inject])
                 poison(dev)
-                (out.float() * self.probe_cl).sum().backward()
+                (out.float() * probe_cl).sum().backward()
                 torch.cuda.synchronize()
         finally:
             block.plan_block = real

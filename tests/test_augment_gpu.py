@@ -12,7 +12,11 @@ import torch.nn.functional as F
 import augment_ref as A
 from test_data import write_split
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 
 ROWS, IDX, VALID = 7, [5, 0, 5, 3], [13, 1, 2, 7, 13, 12, 5]
@@ -27,7 +31,7 @@ def _src(*shape, seed=1):
 def _run(src, idx=IDX, ids=IDS, valid=VALID, joints=None, **kw):
     from fusion_gcn_amd import ops
     v = None if valid is None else torch.tensor(valid, dtype=torch.int32, device=DEV)
-    out, table = ops.clip_augment(src.to(DEV), torch.tensor(idx), torch.tensor(ids), joints=joints, valid=v, **{**KW, **kw})
+    out, table = ops.clip_augment(guarded.to(src, DEV), torch.tensor(idx), torch.tensor(ids), joints=joints, valid=v, **{**KW, **kw})
     torch.cuda.synchronize()
     return out.cpu(), table.cpu()
 
@@ -140,15 +144,15 @@ def test_more_than_one_workgroup_and_wrapper_refusals():
     idx = torch.randint(0, 9, (600,), generator=g)
     ids = torch.arange(600) * 7
     valid = torch.randint(1, 6, (9,), generator=g)
-    out, table = ops.clip_augment(src.to(DEV), idx, ids, joints=(1, 3), valid=valid.to(torch.int32).to(DEV), **KW)
+    out, table = ops.clip_augment(guarded.to(src, DEV), idx, ids, joints=(1, 3), valid=guarded.to(valid.to(torch.int32), DEV), **KW)
     want = A.transform(src.numpy(), idx.numpy(), table.cpu().numpy(), valid.numpy(), (1, 3))
     assert float(np.abs(out.cpu().double().numpy() - want).max()) <= _tolerance(5, src)
     _check_table(table.cpu(), ids=ids.tolist())
     with pytest.raises(_lib.FgcnError, match="rows outside"):
-        ops.clip_augment(src.to(DEV), torch.tensor([9]), torch.tensor([0]), **KW)
+        ops.clip_augment(guarded.to(src, DEV), torch.tensor([9]), torch.tensor([0]), **KW)
     with pytest.raises(_lib.FgcnError, match="valid"):
-        ops.clip_augment(src.to(DEV), idx, ids, valid=valid.to(DEV), **KW)           # int64 frame counts
-    on_dev = src.to(DEV)
+        ops.clip_augment(guarded.to(src, DEV), idx, ids, valid=guarded.to(valid, DEV), **KW)           # int64 frame counts
+    on_dev = guarded.to(src, DEV)
     with pytest.raises(_lib.FgcnError, match="alias"):
         ops.clip_augment(on_dev, torch.arange(9), torch.arange(9), out=on_dev, **KW)
 
@@ -261,7 +265,7 @@ def test_graph_step_training_on_augmented_batches_repeats_bit_for_bit(tmp_path):
     def run():
         model = Model(shape, classes, Graph(utd.skeleton_edges, center_joint=utd.center_joint), num_layers=2)
         filler.fill_state_dict(model.state_dict())
-        model = model.to(DEV).train()
+        model = guarded.to(model, DEV).train()
         opt = FlatOptimizer(model.parameters(), "SGD", 0.01, momentum=0.9)
         step = GraphStep(verify=True)
         batches = ClipBatches(ds, 4, shuffle=True, seed=3, device=DEV, resident=False, augment=Augment())

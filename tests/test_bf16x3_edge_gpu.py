@@ -16,7 +16,11 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 RATIO = 2.0
 
 
@@ -35,7 +39,7 @@ def f32(x):
 
 
 def gpu(x):
-    return x.float().to(dev()).contiguous()
+    return guarded.put(x.float(), device=dev())
 
 
 def pow2(shape, lo, hi, seed):

@@ -15,7 +15,11 @@ from oracle import agcn_oracle as O
 from oracle import filler, graph_oracle
 from oracle import relu_masks as RM
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 
 
 def dev():
@@ -121,7 +125,7 @@ def test_block_forward_backward_vs_oracle(name, cin, cout, stride, residual, V, 
     blk = SpatialTemporalConv(cin, cout, adj, stride=stride, residual=residual, fused_spatial=fused)
     fill_module(blk, "l0.")
     sd = oracle_sd(blk, "l0.")
-    blk = blk.to(dev())
+    blk = guarded.to(blk, dev())
     x = torch.from_numpy(filler.bellish(f"x.blk.{name}", (B, cin, T, V))).double()      # oracle layout (B, C, T, V)
     Tp = (T - 1) // stride + 1
     probe = torch.from_numpy(filler.uniform(f"probe.blk.{name}", (B, cout, Tp, V), -1, 1)).double()
@@ -139,7 +143,7 @@ def test_block_forward_backward_vs_oracle(name, cin, cout, stride, residual, V, 
 
     # ---- HIP path ------------------------------------------------------------------------------------------------
     blk.train()
-    xg = x.float().to(dev()).requires_grad_(True)
+    xg = guarded.to(x.float(), dev()).requires_grad_(True)
     out_g = blk.forward_nchw(xg)
     assert out_g.shape == out_o.shape
     fwd_err = rel_l2(out_g.detach().cpu().numpy(), out_o.detach().numpy())
@@ -147,7 +151,7 @@ def test_block_forward_backward_vs_oracle(name, cin, cout, stride, residual, V, 
     c_err = rel_l2(torch.stack(blk.gcn1.adj_c, 1).cpu().numpy(), torch.stack(adj_c, 1).detach().numpy())
     assert c_err < 1e-5, c_err
     flips = int(((out_g.detach().cpu() > 0) != (out_o.detach() > 0)).sum())
-    (out_g * probe.float().to(dev())).sum().backward()
+    (out_g * guarded.to(probe.float(), dev())).sum().backward()
     tol = 2e-4 if flips == 0 else 5e-3
     dx_err = rel_l2(xg.grad.cpu().numpy(), grads_o[0].numpy())
     assert dx_err < tol, (dx_err, flips)
@@ -166,7 +170,7 @@ def test_block_forward_backward_vs_oracle(name, cin, cout, stride, residual, V, 
     blk.eval()
     sd_eval = oracle_sd(blk, "l0.")
     with torch.no_grad():
-        out_e = blk.forward_nchw(x.float().to(dev()))
+        out_e = blk.forward_nchw(guarded.to(x.float(), dev()))
     want_e, _ = O.st_block(x, sd_eval, "l0", stride, residual, False)
     assert rel_l2(out_e.cpu().numpy(), want_e.numpy()) < 2e-5
 
@@ -192,7 +196,7 @@ def test_block_random_shapes_vs_oracle(seed):
     blk = SpatialTemporalConv(cin, cout, adj, stride=stride, residual=residual)
     fill_module(blk, "l0.")
     sd = oracle_sd(blk, "l0.")
-    blk = blk.to(dev()).train()
+    blk = guarded.to(blk, dev()).train()
     x = torch.from_numpy(filler.bellish(f"x.rnd.{seed}", (B, cin, T, V))).double()
     Tp = (T - 1) // stride + 1
     probe = torch.from_numpy(filler.uniform(f"probe.rnd.{seed}", (B, cout, Tp, V), -1, 1)).double()
@@ -204,12 +208,12 @@ def test_block_random_shapes_vs_oracle(seed):
     out_o, _ = O.st_block(xo, live, "l0", stride, residual, True, O.Stats())
     grads_o = torch.autograd.grad((out_o * probe).sum(), [xo] + list(params.values()), allow_unused=True)
     want = {k[3:]: g.numpy() for k, g in zip(params.keys(), grads_o[1:]) if g is not None}
-    xg = x.float().to(dev()).requires_grad_(True)
+    xg = guarded.to(x.float(), dev()).requires_grad_(True)
     out_g = blk.forward_nchw(xg)
     fwd_err = rel_l2(out_g.detach().cpu().numpy(), out_o.detach().numpy())
     assert fwd_err < 2e-5, (fwd_err, V, T, B)
     flips = int(((out_g.detach().cpu() > 0) != (out_o.detach() > 0)).sum())
-    (out_g * probe.float().to(dev())).sum().backward()
+    (out_g * guarded.to(probe.float(), dev())).sum().backward()
     tol = 2e-4 if flips == 0 else 5e-3
     dx_err = rel_l2(xg.grad.cpu().numpy(), grads_o[0].numpy())
     assert dx_err < tol, (dx_err, flips, V, T, B)
@@ -231,7 +235,7 @@ def test_block_with_other_temporal_kernels_vs_oracle(kt, stride, T):
     blk.tcn1 = TemporalConv(cout, cout, kernel_size=kt, stride=stride)
     fill_module(blk, "l0.")
     sd = oracle_sd(blk, "l0.")
-    blk = blk.to(dev()).train()
+    blk = guarded.to(blk, dev()).train()
     x = torch.from_numpy(filler.bellish(f"x.kt.{kt}.{stride}.{T}", (B, cin, T, V))).double()
     Tp = (T - 1) // stride + 1
     # gradients on a scale where an unscaled f16 split would lose them (2^-20) and one where it would overflow (2^18)
@@ -246,11 +250,11 @@ def test_block_with_other_temporal_kernels_vs_oracle(kt, stride, T):
         grads_o = torch.autograd.grad((out_o * probe).sum(), [xo] + list(params.values()), allow_unused=True)
         want = {k[3:]: g.numpy() for k, g in zip(params.keys(), grads_o[1:]) if g is not None}
         blk.zero_grad()
-        xg = x.float().to(dev()).requires_grad_(True)
+        xg = guarded.to(x.float(), dev()).requires_grad_(True)
         out_g = blk.forward_nchw(xg)
         assert rel_l2(out_g.detach().cpu().numpy(), out_o.detach().numpy()) < 2e-5
         flips = int(((out_g.detach().cpu() > 0) != (out_o.detach() > 0)).sum())
-        (out_g * probe.float().to(dev())).sum().backward()
+        (out_g * guarded.to(probe.float(), dev())).sum().backward()
         tol = 2e-4 if flips == 0 else 5e-3
         assert rel_l2(xg.grad.cpu().numpy(), grads_o[0].numpy()) < tol, (scale, flips)
         got = {n: p.grad.detach().cpu().numpy() for n, p in blk.named_parameters()}
@@ -264,7 +268,7 @@ def test_static_adjacency_block_is_stgcn_special_case():
     blk = SpatialTemporalConv(64, 64, adj, static_adjacency=True)
     fill_module(blk, "l0.")
     sd = oracle_sd(blk, "l0.")
-    blk = blk.to(dev()).train()
+    blk = guarded.to(blk, dev()).train()
     x = torch.from_numpy(filler.bellish("x.stgcn", (2, 64, 10, 25))).double()
     params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.endswith(("adj_b", "conv_d.1.weight"))}
     live = dict(sd)
@@ -272,7 +276,7 @@ def test_static_adjacency_block_is_stgcn_special_case():
     xo = x.clone().requires_grad_(True)
     out_o, _ = O.st_block(xo, live, "l0", 1, True, True, None, static_adjacency=True)
     g_o = torch.autograd.grad(out_o.square().sum(), [xo] + list(params.values()))
-    xg = x.float().to(dev()).requires_grad_(True)
+    xg = guarded.to(x.float(), dev()).requires_grad_(True)
     out_g = blk.forward_nchw(xg)
     assert rel_l2(out_g.detach().cpu().numpy(), out_o.detach().numpy()) < 2e-5
     out_g.square().sum().backward()
@@ -305,17 +309,17 @@ def test_full_model_vs_golden_and_oracle(golden, tag, shape, classes, gname):
     ref = golden("model.npz")
     model, x, labels = _model_case(tag, shape, classes, gname)
     sd = oracle_sd(model)
-    model = model.to(dev())
+    model = guarded.to(model, dev())
     # eval-mode logits vs the reference
     model.eval()
     with torch.no_grad():
-        lg = model(x.float().to(dev()))
+        lg = model(guarded.to(x.float(), dev()))
     e_eval = rel_l2(lg.cpu().numpy(), ref[f"{tag}.eval.logits"])
     assert e_eval < 1e-4, e_eval
     # train step
     model.train()
-    logits = model(x.float().to(dev()))
-    loss = torch.nn.functional.cross_entropy(logits, labels.to(dev()))
+    logits = model(guarded.to(x.float(), dev()))
+    loss = torch.nn.functional.cross_entropy(logits, guarded.to(labels, dev()))
     loss.backward()
     e_train = rel_l2(logits.detach().cpu().numpy(), ref[f"{tag}.train.logits"])
     assert e_train < 1e-4, e_train
@@ -327,7 +331,7 @@ def test_full_model_vs_golden_and_oracle(golden, tag, shape, classes, gname):
             assert rel_l2(model.state_dict()[k].cpu().numpy(), v.numpy()) < 1e-4, k
     # gradients: flip-accounted against the float64 oracle, per-parameter norms against the reference's own
     model.zero_grad(set_to_none=True)
-    check_gradients_with_flip_accounting(model, x.float().to(dev()), labels.to(dev()), x.double(), labels, sd, ref, tag)
+    check_gradients_with_flip_accounting(model, guarded.to(x.float(), dev()), guarded.to(labels, dev()), x.double(), labels, sd, ref, tag)
 
 
 def test_agcn_spelling_and_mmargcn_mode(golden):
@@ -341,8 +345,8 @@ def test_agcn_spelling_and_mmargcn_mode(golden):
     mm = import_model("mmargcn")({"skeleton": (1, 20, 22, 3)}, 27, g, mode="skeleton_imu_spatial_fusion",
                                  num_imu_joints=2, imu_enhanced_mode="append_center")
     filler.fill_state_dict(mm.state_dict(), rename=lambda k: k.replace("_model.agcn.", ""))
-    mm = mm.to(dev())
-    x = torch.from_numpy(filler.skeleton_input("x.mm22", (2, 1, 20, 22, 3))).float().to(dev())
+    mm = guarded.to(mm, dev())
+    x = guarded.to(torch.from_numpy(filler.skeleton_input("x.mm22", (2, 1, 20, 22, 3))).float(), dev())
     mm.eval()
     with torch.no_grad():
         assert rel_l2(mm(x).cpu().numpy(), ref["mm22.eval.logits"]) < 1e-4
@@ -353,8 +357,8 @@ def test_agcn_spelling_and_mmargcn_mode(golden):
     agcn = import_model("agcn")({"skeleton": (1, 100, 20, 3)}, 27, g)
     inv = {O.agcn_key(k): k for k in O.new_state_dict((1, 100, 20, 3), 27, adj_for(20))}
     filler.fill_state_dict(agcn.state_dict(), rename=lambda k: inv[k])
-    agcn = agcn.to(dev()).eval()
-    xx = torch.from_numpy(filler.skeleton_input("x.cfg1", (2, 1, 100, 20, 3))).float().to(dev())
+    agcn = guarded.to(agcn, dev()).eval()
+    xx = guarded.to(torch.from_numpy(filler.skeleton_input("x.cfg1", (2, 1, 100, 20, 3))).float(), dev())
     with torch.no_grad():
         assert rel_l2(agcn(xx).cpu().numpy(), ref_m["cfg1.eval.logits"]) < 1e-4
 
@@ -383,9 +387,9 @@ def test_other_baseline_shapes_vs_reference(golden, tag, dataset, shape, classes
         model = Model(shape[1:], classes, g)
         strip = ""
     filler.fill_state_dict(model.state_dict(), rename=lambda k: k.replace(strip, "") if strip else k)
-    model = model.to(dev())
-    x = torch.from_numpy(filler.skeleton_input(f"x.{tag}", shape, empty_second_body=True)).float().to(dev())
-    labels = torch.from_numpy(ref[f"{tag}.labels"]).to(dev())
+    model = guarded.to(model, dev())
+    x = guarded.to(torch.from_numpy(filler.skeleton_input(f"x.{tag}", shape, empty_second_body=True)).float(), dev())
+    labels = guarded.to(torch.from_numpy(ref[f"{tag}.labels"]), dev())
     model.eval()
     with torch.no_grad():
         assert rel_l2(model(x).cpu().numpy(), ref[f"{tag}.eval.logits"]) < 1e-4
@@ -423,7 +427,7 @@ def test_size_independent_properties_at_headline_shape(joints):
         model = import_model("mmargcn")({"skeleton": (2, 300, joints, 3)}, classes, Graph(c.skeleton_edges, center_joint=c.center_joint),
                                         mode="skeleton_imu_spatial_fusion", num_imu_joints=n_imu, imu_enhanced_mode="append_center")
         filler.fill_state_dict(model.state_dict(), rename=lambda k: k.replace("_model.agcn.", ""))
-    model = model.to(dev()).eval()
+    model = guarded.to(model, dev()).eval()
     x = torch.randn(8, 2, 300, joints, 3, device=dev())
     with torch.no_grad():
         full = model(x)
@@ -462,7 +466,7 @@ def test_streamed_output_stores_change_no_bit(fgcn_math_mode):
     with ops.math_mode(fgcn_math_mode):
         model = Model((2, 64, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=20))
         fill_module(model)
-        model = model.to(dev()).train()
+        model = guarded.to(model, dev()).train()
         x = torch.randn(3, 2, 64, 25, 3, device=dev())
         labels = torch.arange(3, device=dev()) % 60
         runs = {}
@@ -509,7 +513,7 @@ def test_pool_and_classifier_kernels_and_graph_replay():
     from fusion_gcn_amd.datasets.ntu_rgb_d import constants as ntu
     from fusion_gcn_amd.models.mmargcn.agcn import Model
     from fusion_gcn_amd.util import Graph
-    model = Model((2, 300, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint)).to(dev).train()
+    model = guarded.to(Model((2, 300, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint)), dev).train()
     x = torch.randn(8, 2, 300, 25, 3, device=dev)
     y = torch.randint(0, 60, (8,), device=dev)
 
@@ -617,7 +621,7 @@ def test_model_with_and_without_the_pooling_epilogue(fgcn_math):
     from fusion_gcn_amd.util import Graph
     dev = torch.device("cuda:0")
     torch.manual_seed(5)
-    model = Model((2, 40, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint)).to(dev).train()
+    model = guarded.to(Model((2, 40, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint)), dev).train()
     with torch.no_grad():
         for m in model.modules():                       # (the reference's 1e-6 BatchNorm gain would silence the graph convolutions)
             if hasattr(m, "gcn1"):
@@ -664,8 +668,8 @@ def test_dropout_between_blocks_and_second_backward():
     remap = {k: v for k, v in drop.state_dict().items()}
     plain.load_state_dict({k.replace(f"l{int(k.split('.')[0][1:])}.", f"l{int(k.split('.')[0][1:]) // 2}.", 1) if k.startswith("l") else k: v
                            for k, v in remap.items()})
-    drop, plain = drop.to(dev()), plain.to(dev())
-    x = torch.from_numpy(filler.skeleton_input("x.drop", shape)).float().to(dev())
+    drop, plain = guarded.to(drop, dev()), guarded.to(plain, dev())
+    x = guarded.to(torch.from_numpy(filler.skeleton_input("x.drop", shape)).float(), dev())
     drop.eval(), plain.eval()
     with torch.no_grad():
         assert torch.equal(drop(x), plain(x))
@@ -692,7 +696,7 @@ def test_inference_runs_the_fused_output_stages(fgcn_math):
     from fusion_gcn_amd.util import Graph
     dev = torch.device("cuda:0")
     torch.manual_seed(7)
-    model = Model((2, 40, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint)).to(dev)
+    model = guarded.to(Model((2, 40, 25, 3), 60, Graph(ntu.skeleton_edges, center_joint=ntu.center_joint)), dev)
     with torch.no_grad():
         for m in model.modules():
             if hasattr(m, "gcn1"):

@@ -17,8 +17,12 @@ that it leaves no route out).  Per entry, here:
     statistics and batch counters are bit-unchanged;
   * f32 / bf16x3 / f16x2: a second poisoned forward + backward is bit-identical in output, dx and every gradient.
 
+Every run is made on guarded allocations (tests/guarded.py: NaN in front of and behind every tensor the host layer creates and the inputs x and probe,
+the margins verified after the backward), so each entry also carries the check that no route stores outside its tensors or lets a load past an
+extent reach a result; ``test_the_guard_changes_no_bit`` fixes that the guard only moves tensors.
+
 All failures of a case's entries are collected and raised once.  One model-level leg runs the pooled last block and the block-to-block hand-off
-under non-default option sets."""
+under non-default option sets, under the same guard."""
 import functools
 import math
 
@@ -27,6 +31,7 @@ import pytest
 import torch
 
 import block_routes as R
+import guarded
 from oracle import filler
 from oracle import relu_masks as RM
 
@@ -109,6 +114,27 @@ def test_every_route_of_the_block_vs_oracle(fgcn_math, phase, case):
     assert not fails, "\n".join(fails)
 
 
+@pytest.mark.parametrize("fgcn_math", ["bf16x3", "bf16"], indirect=True)
+def test_the_guard_changes_no_bit(fgcn_math):
+    """identity64, train, default options: the run on guarded allocations and the run on the allocator's own tensors (poisoned both) give the
+    same bits in the output, dx and every parameter gradient -- the guard moves tensors (512-byte aligned, as the allocator's are) and selects
+    no other kernel form"""
+    case = next(c for c in R.CASES if c.name == "identity64")
+    entry = next(e for e in R.matrix(fgcn_math, "train") if e.case == case and e.option_name == "default" and not e.half)
+    run = R.BlockRun(case, dev())
+    with_guard = run.run(entry, "train")
+    without = run.run(entry, "train", guard=False)
+    assert with_guard["plans"] == without["plans"] == [entry.plan]
+    assert torch.isfinite(with_guard["out"]).all() and with_guard["out_dtype"] == without["out_dtype"]
+    assert torch.equal(with_guard["out"], without["out"])
+    assert torch.equal(with_guard["dx"], without["dx"])
+    assert set(with_guard["grads"]) == set(without["grads"]) and len(with_guard["grads"]) > 10
+    for k, g in with_guard["grads"].items():
+        assert torch.equal(g, without["grads"][k]), k
+    if without["adj_c"] is not None:
+        assert torch.equal(with_guard["adj_c"], without["adj_c"])
+
+
 # ---- model level: the pooled last block and the block-to-block hand-off under non-default routes ----------------------------------------------
 # name -> (FGCN_PATHS spec, what the ten plans of the step must show: the option set really took effect)
 MODEL_SETS = {
@@ -162,10 +188,11 @@ def test_model_under_non_default_routes_vs_oracle(fgcn_math, name):
         return plans[-1]
     block.plan_block = spy
     try:
-        with ops.context(fgcn_math) as ctx:
+        with ops.context(fgcn_math) as ctx, guarded.Guard() as guard:
             ctx.paths.update_from(spec)
             R.poison(dev())
-            rep = RM.gradient_parity_report(model, x.float().to(dev()), labels.to(dev()), oracle=oracle)
+            rep = RM.gradient_parity_report(model, guard.put(x.float()), labels.to(dev()), oracle=oracle)
+            guard.check()
     finally:
         block.plan_block = real
     print(f"[{fgcn_math} model | {name}] logits {rep['logits_err']:.2e} flips {rep['flips']} of {rep['decisions']} grad {rep['err_plain']:.2e} / "

@@ -16,7 +16,11 @@ import torch
 
 from conftest import rel_l2
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 
 DEV = "cuda:0"
 EPS = 1e-5
@@ -99,7 +103,7 @@ def _kernel_step(stage, bn, probe, train, dims):
     assert out.shape == (N * M, T, V, (C + 3) // 4 * 4) and float(out[..., C:].abs().sum()) == 0.0
     pad = torch.zeros(out.shape, dtype=torch.float32)
     pad[..., :C] = probe.reshape(N * M, T, V, C)
-    (out * pad.to(DEV)).sum().backward()
+    (out * guarded.to(pad, DEV)).sum().backward()
     torch.cuda.synchronize()
     q = {"out": _by_channel(out[..., :C].detach().cpu(), dims), "rstd": rstd,
          "running_mean": bn.running_mean.double().cpu().numpy(), "running_var": bn.running_var.double().cpu().numpy(),
@@ -160,8 +164,8 @@ def _input_stage_contract(dims, stage_of, seed, has_dx=True):
     x32 = _make_input(dims, seed)
     probe = torch.randn(N, M, T, V, C, generator=torch.Generator().manual_seed(seed + 1)).double()     # float32 values
     names = ["out", "running_mean", "running_var", "rstd", "dgamma", "dbeta"] + (["dx"] if has_dx else [])
-    bn64, bn32, mine, twin = (_fresh_bn(ch, seed + 2, torch.float64), _fresh_bn(ch, seed + 2), _fresh_bn(ch, seed + 2).to(DEV),
-                              _fresh_bn(ch, seed + 2).to(DEV))
+    bn64, bn32, mine, twin = (_fresh_bn(ch, seed + 2, torch.float64), _fresh_bn(ch, seed + 2), guarded.to(_fresh_bn(ch, seed + 2), DEV),
+                              guarded.to(_fresh_bn(ch, seed + 2), DEV))
     stage = stage_of(x32)
     bad = []
     for train in (True, False):
@@ -181,7 +185,7 @@ def _data_bn_stage(x32):
     from fusion_gcn_amd.block import data_bn
 
     def stage(bn):
-        leaf = x32.to(DEV).requires_grad_(True)
+        leaf = guarded.to(x32, DEV).requires_grad_(True)
         return data_bn(leaf, bn), leaf
     return stage
 
@@ -217,7 +221,7 @@ def test_patch_input_statistics_are_flat_in_the_offset():
     assert ops.paths().get("patch_input_fused", ops.get_math_mode())
 
     def stage_of(z32):
-        s, p = z32[..., :Cs].contiguous().to(DEV), z32[..., Cs:].contiguous().to(DEV)
+        s, p = guarded.to(z32[..., :Cs].contiguous(), DEV), guarded.to(z32[..., Cs:].contiguous(), DEV)
 
         def stage(bn):
             return patch_input(s, p, None, bn, V, "concatenate"), None
@@ -231,8 +235,8 @@ def test_data_bn_under_graph_capture_gives_eager_bits():
     from fusion_gcn_amd.block import data_bn
     dims = (3, 2, 37, 25, 3)
     ch = dims[1] * dims[3] * dims[4]
-    x = _make_input(dims, seed=5).to(DEV)
-    eager, warm, captured = (_fresh_bn(ch, 9).to(DEV).train() for _ in range(3))
+    x = guarded.to(_make_input(dims, seed=5), DEV)
+    eager, warm, captured = (guarded.to(_fresh_bn(ch, 9), DEV).train() for _ in range(3))
     with torch.no_grad():
         want = data_bn(x, eager)
         side = torch.cuda.Stream()
@@ -257,7 +261,7 @@ DRIVES = (("none", 0.0), ("bias", 3.0), ("bias", 30.0), ("data", 3.0), ("data", 
 
 
 def _gpu(t):
-    return t.float().to(DEV).contiguous()
+    return guarded.put(t.float(), device=DEV)
 
 
 def _nonneg(shape, q, gen):

@@ -15,7 +15,11 @@ import torch.nn.functional as F
 import dropout_ref as R
 from conftest import rel_l2
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 MODES = pytest.mark.parametrize("fgcn_math", ["f32", "bf16x3", "f16x2"], indirect=True)
 WG = 256 * 8                 # elements one workgroup of the dropout kernels covers
@@ -46,11 +50,11 @@ def test_kernels_match_the_numpy_generator_bit_for_bit(n, p):
     from fusion_gcn_amd import ops
     seed = 0x9E3779B97F4A7C15
     x, dy = R.rnd(n, seed=n).float(), R.rnd(n, seed=n + 1).float()
-    xg, dyg = x.to(DEV), dy.to(DEV)
+    xg, dyg = guarded.to(x, DEV), guarded.to(dy, DEV)
     s = R.scale(p)
     for site in (0, 7):
         for step in (0, 2 ** 32 + 5):
-            word = torch.tensor([step], dtype=torch.uint64).to(DEV)
+            word = guarded.to(torch.tensor([step], dtype=torch.uint64), DEV)
             y, mask = ops.dropout_fwd(xg, p, seed, site, word)
             kept = R.keep(n, p, seed, site, step)
             assert mask.dtype == torch.uint8 and np.array_equal(mask.cpu().numpy(), R.pack(kept)), (site, step)
@@ -66,11 +70,11 @@ def test_kernels_match_the_numpy_generator_bit_for_bit(n, p):
 
 def test_ops_check_their_arguments_like_their_neighbours():
     from fusion_gcn_amd import _lib, ops
-    x, word = torch.zeros(16, device=DEV), torch.zeros(1, dtype=torch.uint64).to(DEV)
+    x, word = torch.zeros(16, device=DEV), guarded.to(torch.zeros(1, dtype=torch.uint64), DEV)
     for bad in (x.double(), x.cpu(), torch.zeros(4, 8, device=DEV)[:, ::2]):
         with pytest.raises(_lib.FgcnError):
             ops.dropout_fwd(bad, 0.5, 1, 0, word)
-    for bad in (word.cpu(), torch.zeros(1, dtype=torch.int64, device=DEV), torch.zeros(2, dtype=torch.uint64).to(DEV)):
+    for bad in (word.cpu(), torch.zeros(1, dtype=torch.int64, device=DEV), guarded.to(torch.zeros(2, dtype=torch.uint64), DEV)):
         with pytest.raises(_lib.FgcnError):
             ops.dropout_fwd(x, 0.5, 1, 0, bad)
         with pytest.raises(_lib.FgcnError):
@@ -86,12 +90,12 @@ def test_ops_check_their_arguments_like_their_neighbours():
 # ---- the step counter ----------------------------------------------------------------------------------------------------------------
 def test_two_calls_draw_the_masks_of_two_consecutive_steps():
     from fusion_gcn_amd import fops
-    drop = fops.FusedDropout(0.5).to(DEV)
+    drop = guarded.to(fops.FusedDropout(0.5), DEV)
     drop.reseed(11, site=2)
     start = 2 ** 32 - 1                                                    # the second step carries into the high half of the word
     _set_word(drop.step, start)
     n = WG + 12
-    x = R.rnd(n, seed=3).float().to(DEV).requires_grad_(True)
+    x = guarded.to(R.rnd(n, seed=3).float(), DEV).requires_grad_(True)
     outs = []
     for k in range(2):
         y = fops.dropout(x, drop, drop.p, True)
@@ -109,9 +113,9 @@ def test_two_calls_draw_the_masks_of_two_consecutive_steps():
 
 def test_a_captured_forward_and_advance_draw_new_masks_on_every_replay():
     from fusion_gcn_amd import fops
-    drop = fops.FusedDropout(0.3).to(DEV)
+    drop = guarded.to(fops.FusedDropout(0.3), DEV)
     n = 3 * WG + 20
-    x = R.rnd(n, seed=4).float().to(DEV)
+    x = guarded.to(R.rnd(n, seed=4).float(), DEV)
     drop.reseed(13)
     drop.draw(x)                                                           # eager warm-up: the library and the device check are loaded
     drop.reseed(13)
@@ -145,12 +149,12 @@ def _gc_layer(kind, sparse, dropout):
     layer = STGCNGraphConvolution(fin, o, R.ring_adjacency().float(), residual=residual, sparse=sparse, dropout=dropout)
     missing = layer.load_state_dict({k: v.float() for k, v in R.gc_case(kind)["params"].items()}, strict=False)
     assert not missing.unexpected_keys
-    return layer.to(DEV)
+    return guarded.to(layer, DEV)
 
 
 def _gc_input(kind):
     x = R.gc_case(kind)["x"].float()
-    return F.pad(x, (0, (-x.shape[-1]) % 4)).contiguous().to(DEV).requires_grad_(True)        # node-major, channels padded to 4
+    return guarded.to(F.pad(x, (0, (-x.shape[-1]) % 4)).contiguous(), DEV).requires_grad_(True)        # node-major, channels padded to 4
 
 
 @MODES
@@ -170,7 +174,7 @@ def test_graph_convolution_with_dropout_matches_float64(kind, sparse, fgcn_math)
     assert np.array_equal(kept.reshape(-1), R.keep(n, R.GC_P, R.GC_SEED, 0, 0)) and _word(layer.dropout.step) == 1
     ref = _cached(("gc", kind), lambda: R.gc_reference(kind, kept))
     assert R.off_the_kink(ref["pre"], kept if kind == "none" else None) >= 1e-4               # no ReLU flip can hide
-    (out * case["probe"].float().to(DEV)).sum().backward()
+    (out * guarded.to(case["probe"].float(), DEV)).sum().backward()
     named = dict(layer.named_parameters())
     errors = {"forward": rel_l2(out.detach().cpu().numpy(), ref["out"].numpy()),
               "dx": rel_l2(xg.grad[..., :fin].cpu().numpy(), ref["gx"].numpy())}
@@ -198,7 +202,7 @@ def _mlp(dropout):
     p = R.mlp_case()["params"]
     mlp.load_state_dict({f"layers.{i}.weight": p["weight"].float(), f"layers.{i}.bias": p["bias"].float(),
                          f"layers.{i + 1}.weight": p["gamma"].float(), f"layers.{i + 1}.bias": p["beta"].float()}, strict=False)
-    return mlp.to(DEV)
+    return guarded.to(mlp, DEV)
 
 
 @MODES
@@ -207,14 +211,14 @@ def test_mlp_with_dropout_matches_float64(fgcn_math):
     mlp = _mlp(R.MLP_P).train()
     drop, conv, bn, _ = mlp.layers
     drop.reseed(R.MLP_SEED)
-    xg = case["x"].float().to(DEV).requires_grad_(True)
+    xg = guarded.to(case["x"].float(), DEV).requires_grad_(True)
     out = mlp(xg)
     n = xg.numel()
     kept = R.unpack(drop.keep_mask.cpu().numpy(), n).reshape(R.MLP_SHAPE)
     assert np.array_equal(kept.reshape(-1), R.keep(n, R.MLP_P, R.MLP_SEED, 0, 0)) and _word(drop.step) == 1
     ref = _cached("mlp", lambda: R.mlp_reference(kept))
     assert R.off_the_kink(ref["pre"]) >= 1e-4
-    (out * case["probe"].float().to(DEV)).sum().backward()
+    (out * guarded.to(case["probe"].float(), DEV)).sum().backward()
     errors = {"forward": rel_l2(out.detach().cpu().numpy(), ref["out"].numpy()), "dx": rel_l2(xg.grad.cpu().numpy(), ref["gx"].numpy()),
               "weight": rel_l2(conv.weight.grad.cpu().numpy(), ref["grads"]["weight"].numpy()),
               "gamma": rel_l2(bn.weight.grad.cpu().numpy(), ref["grads"]["gamma"].numpy()),
@@ -243,12 +247,12 @@ def test_multi_scale_graph_conv_with_dropout_matches_float64(fgcn_math):
     mod.load_state_dict({"A_res": p["A_res"].float(), "mlp.layers.1.weight": p["weight"].float(), "mlp.layers.1.bias": p["bias"].float(),
                          "mlp.layers.2.weight": p["gamma"].float(), "mlp.layers.2.bias": p["beta"].float()}, strict=False)
     a_powers = mod.A_powers.double().clone()
-    mod = mod.to(DEV).train()
+    mod = guarded.to(mod, DEV).train()
     drop, conv, bn, _ = mod.mlp.layers
     drop.reseed(R.GCN_SEED)
     seen = []
     hook = drop.register_forward_hook(lambda m, args, result: seen.append(result.detach()))
-    xg = F.pad(case["x"].float(), (0, 1)).contiguous().to(DEV).requires_grad_(True)
+    xg = guarded.to(F.pad(case["x"].float(), (0, 1)).contiguous(), DEV).requires_grad_(True)
     out = mod(xg)
     hook.remove()
     n = b * t * v * R.GCN_SCALES * (c + 1)
@@ -259,7 +263,7 @@ def test_multi_scale_graph_conv_with_dropout_matches_float64(fgcn_math):
     ref = _cached("msgcn", lambda: R.msgcn_reference(a_powers, kept))
     assert R.off_the_kink(ref["pre"]) >= 1e-4
     assert rel_l2(seen[0].cpu().numpy(), ref["dropped"].numpy()) < 2e-5
-    (out * case["probe"].float().to(DEV)).sum().backward()
+    (out * guarded.to(case["probe"].float(), DEV)).sum().backward()
     errors = {"forward": rel_l2(out.detach().cpu().numpy(), ref["out"].numpy()),
               "dx": rel_l2(xg.grad[..., :c].cpu().numpy(), ref["gx"].numpy()),
               "A_res": rel_l2(mod.A_res.grad.cpu().numpy(), ref["grads"]["A_res"].numpy()),
@@ -276,14 +280,14 @@ def test_multi_scale_graph_conv_with_dropout_matches_float64(fgcn_math):
 def _gcn(nodes, features, classes, **kw):
     from fusion_gcn_amd.models.mmargcn.gcn import GCN
     torch.manual_seed(3)
-    model = GCN(R.ring_adjacency(nodes).float(), (features, nodes), classes, dropout=0.3, gc_model="stgcn", **kw).to(DEV).train()
+    model = guarded.to(GCN(R.ring_adjacency(nodes).float(), (features, nodes), classes, dropout=0.3, gc_model="stgcn", **kw), DEV).train()
     for m in _fused(model):
         m.reseed(1)
     return model
 
 
 def test_two_models_from_one_seed_take_bit_identical_steps():
-    batches = [(R.rnd(4, 1, 24, seed=40 + i).float().to(DEV), torch.tensor([0, 3, 1, 4], device=DEV).roll(i)) for i in range(2)]
+    batches = [(guarded.to(R.rnd(4, 1, 24, seed=40 + i).float(), DEV), torch.tensor([0, 3, 1, 4], device=DEV).roll(i)) for i in range(2)]
 
     def run():
         model = _gcn(24, 1, 5, num_layers=3, inner_feature_dim=16)
@@ -309,7 +313,7 @@ def test_graph_step_draws_a_new_mask_per_replay_and_counts_real_steps_only():
     model = _gcn(16, 3, 4, num_layers=4, inner_feature_dim=8)          # 16 nodes: the smallest graph of tests/test_imu_gcn.py
     drops = _fused(model)
     assert len(drops) == 3
-    x, y = R.rnd(4, 3, 16, seed=50).float().to(DEV), torch.tensor([0, 1, 2, 3], device=DEV)
+    x, y = guarded.to(R.rnd(4, 3, 16, seed=50).float(), DEV), torch.tensor([0, 1, 2, 3], device=DEV)
     step = GraphStep()
     masks, losses = [], []
     for _ in range(3):
@@ -338,15 +342,15 @@ def test_late_fusion_with_dropout_trains_and_evaluates_like_the_model_without():
     shapes = {"skeleton": (1, 16, 20, 3), "inertial": (8, 6)}
     graph = Graph(utd.skeleton_edges, center_joint=utd.center_joint)
     torch.manual_seed(5)
-    model = Model(shapes, 27, graph, mode="skeleton_imu_gcn_late_fusion", dropout=0.2, **kw).to(DEV).train()
-    x = {"skeleton": R.rnd(3, *shapes["skeleton"], seed=60).float().to(DEV), "inertial": R.rnd(3, *shapes["inertial"], seed=61).float().to(DEV)}
+    model = guarded.to(Model(shapes, 27, graph, mode="skeleton_imu_gcn_late_fusion", dropout=0.2, **kw), DEV).train()
+    x = {"skeleton": guarded.to(R.rnd(3, *shapes["skeleton"], seed=60).float(), DEV), "inertial": guarded.to(R.rnd(3, *shapes["inertial"], seed=61).float(), DEV)}
     y = torch.tensor([1, 26, 7], device=DEV)
     loss = F.cross_entropy(model(x), y)
     loss.backward()
     assert bool(torch.isfinite(loss)) and all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in model.parameters())
     assert all(_word(m.step) == 1 for m in _fused(model)) and _fused(model)
     # the same values in a dropout=0 model: the skeleton branch's nn.Dropout modules took every other l<i> slot (l0, l2, ... -> l0, l1, ...)
-    plain = Model(shapes, 27, graph, mode="skeleton_imu_gcn_late_fusion", **kw).to(DEV)
+    plain = guarded.to(Model(shapes, 27, graph, mode="skeleton_imu_gcn_late_fusion", **kw), DEV)
 
     def renumber(k):
         parts = k.split(".")

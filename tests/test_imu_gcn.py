@@ -15,6 +15,12 @@ from conftest import rel_l2
 from oracle import filler
 from oracle import imu_gcn_oracle as O
 
+import guarded
+from guarded import guarded_gpu_tests  # noqa: F401  (the fixture)
+
+# the tests marked gpu run on guarded allocations, margins verified at teardown (tests/guarded.py); the host tests as they are
+pytestmark = pytest.mark.usefixtures("guarded_gpu_tests")
+
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "imu_gcn.npz"))
 CASES = {
     "value48": ((8, 6), 7, 3, dict(gc_model="stgcn", graph_node_format="node_per_value", num_layers=5, inner_feature_dim=16)),
@@ -119,14 +125,14 @@ def test_hip_imu_gcn_matches_the_oracle(tag):
     x, y = inputs(tag, shape, batch, classes)
     ref_eval = O.imu_gcn_forward(x, sd, train=False, **fmt(kw))
     ref_logits, ref_loss, ref_grads = O.loss_and_grads(x, y, sd, **fmt(kw))
-    model = model.to(dev)
+    model = guarded.to(model, dev)
     model.eval()
     with torch.no_grad():
-        got_eval = model(x.float().to(dev)).cpu().double()
+        got_eval = model(guarded.to(x.float(), dev)).cpu().double()
     assert rel_l2(got_eval.numpy(), ref_eval.numpy()) < 2e-5
     model.train()
-    logits = model(x.float().to(dev))
-    loss = F.cross_entropy(logits, y.to(dev))
+    logits = model(guarded.to(x.float(), dev))
+    loss = F.cross_entropy(logits, guarded.to(y, dev))
     loss.backward()
     assert rel_l2(logits.detach().cpu().double().numpy(), ref_logits.numpy()) < 2e-5
     assert abs(float(loss.detach()) - float(ref_loss)) < 2e-5 * max(1.0, abs(float(ref_loss)))
@@ -228,14 +234,14 @@ def test_hip_late_fusion_matches_the_oracle(gc_model):
     x, y = late_inputs()
     ref_logits, ref_loss, ref_grads = late_loss_and_grads(x, y, sd)
     ref_eval = late_oracle(x, sd, train=False).detach()
-    model = model.to(dev)
-    xg = {k: v.float().to(dev) for k, v in x.items()}
+    model = guarded.to(model, dev)
+    xg = {k: guarded.to(v.float(), dev) for k, v in x.items()}
     model.eval()
     with torch.no_grad():
         assert rel_l2(model(xg).cpu().double().numpy(), ref_eval.numpy()) < 5e-5
     model.train()
     logits = model(xg)
-    loss = F.cross_entropy(logits, y.to(dev))
+    loss = F.cross_entropy(logits, guarded.to(y, dev))
     loss.backward()
     assert rel_l2(logits.detach().cpu().double().numpy(), ref_logits.numpy()) < 5e-5
     assert abs(float(loss.detach()) - float(ref_loss)) < 1e-4
@@ -286,8 +292,8 @@ def test_channel_fusion_oracle_matches_the_reference():
 def test_hip_channel_fusion_matches_the_reference():
     dev = torch.device("cuda:0")
     model, sd, x = chan_build()
-    model = model.to(dev)
-    xg = {k: v.float().to(dev) for k, v in x.items()}
+    model = guarded.to(model, dev)
+    xg = {k: guarded.to(v.float(), dev) for k, v in x.items()}
     model.eval()
     with torch.no_grad():
         assert rel_l2(model(xg).cpu().double().numpy(), chan_oracle(x, sd, False).detach().numpy()) < 5e-5

@@ -15,7 +15,11 @@ from conftest import rel_l2
 from oracle import imu_gcn_oracle as O
 from test_imu_gcn import CASES, GOLD, build, fmt, inputs, late_build, late_inputs, late_loss_and_grads, late_oracle
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 U = 2.0 ** -24
 MODES = ("f32", "bf16x3", "f16x2")
 
@@ -45,18 +49,18 @@ def check_forms(adj, B, C, seed, ld_extra=0, forms=("plain", "relu", "identity",
     from fusion_gcn_amd import ops
     V = adj.shape[0]
     g = torch.Generator().manual_seed(seed)
-    wide = torch.randn(B, V, C + ld_extra, generator=g).to(dev())
+    wide = guarded.to(torch.randn(B, V, C + ld_extra, generator=g), dev())
     x = wide[..., :C]                                                       # row stride C + ld_extra
-    b = torch.randn(B, V, C, generator=g).to(dev())
+    b = guarded.to(torch.randn(B, V, C, generator=g), dev())
     vec = torch.zeros(4, C)
     vec[2], vec[3] = torch.randn(C, generator=g), torch.randn(C, generator=g)
-    vec = vec.to(dev())
-    csr = ops.csr_from_dense(adj.to(dev()))
-    a64 = adj.double().to(dev())
+    vec = guarded.to(vec, dev())
+    csr = ops.csr_from_dense(guarded.to(adj, dev()))
+    a64 = guarded.to(adj.double(), dev())
     x64, b64 = x.double(), b.double()
     prod = torch.matmul(a64, x64)                                           # float64 dense product adj @ in[b]
     mag = torch.matmul(a64.abs(), x64.abs())
-    n_row = (adj != 0).sum(1).double().to(dev()).view(1, V, 1)
+    n_row = guarded.to((adj != 0).sum(1).double(), dev()).view(1, V, 1)
     worst = {}
     for form in forms:
         kw, want, s = {}, prod, mag
@@ -110,9 +114,9 @@ def test_kernel_is_deterministic_and_ignores_the_math_mode():
     g = torch.Generator().manual_seed(5)
     for adj, C in ((config_adj(True, 2), 512), (random_adj(240, 9), 36)):
         V = adj.shape[0]
-        x, b = torch.randn(3, V, C, generator=g).to(dev()), torch.randn(3, V, C, generator=g).to(dev())
-        vec = torch.randn(4, C, generator=g).to(dev())
-        csr = ops.csr_from_dense(adj.to(dev()))
+        x, b = guarded.to(torch.randn(3, V, C, generator=g), dev()), guarded.to(torch.randn(3, V, C, generator=g), dev())
+        vec = guarded.to(torch.randn(4, C, generator=g), dev())
+        csr = ops.csr_from_dense(guarded.to(adj, dev()))
         first = ops.graph_spmm(x, csr, relu=True, b=b, vec_b=vec)
         assert torch.equal(ops.graph_spmm(x, csr, relu=True, b=b, vec_b=vec), first)          # two launches: the same bits
         for m in ("f32", "bf16x3", "f16x2", "bf16"):
@@ -126,11 +130,11 @@ def test_transposed_form_is_the_data_gradient(which):
     adj = {"config": lambda: config_adj(), "config_inter2": lambda: config_adj(True, 2), "random240": lambda: random_adj(240, 2),
            "random48": lambda: random_adj(48, 4)}[which]()
     V, B, C = adj.shape[0], 3, 64
-    d = torch.randn(B, V, C, generator=torch.Generator().manual_seed(11)).to(dev())
-    got = ops.graph_spmm(d, ops.csr_from_dense(adj.to(dev()), transpose=True))
-    at = adj.t().double().to(dev())
+    d = guarded.to(torch.randn(B, V, C, generator=torch.Generator().manual_seed(11)), dev())
+    got = ops.graph_spmm(d, ops.csr_from_dense(guarded.to(adj, dev()), transpose=True))
+    at = guarded.to(adj.t().double(), dev())
     want, mag = torch.matmul(at, d.double()), torch.matmul(at.abs(), d.double().abs())
-    n_row = (adj.t() != 0).sum(1).double().to(dev()).view(1, V, 1)
+    n_row = guarded.to((adj.t() != 0).sum(1).double(), dev()).view(1, V, 1)
     assert bool(((got.double() - want).abs() <= 2 * (n_row + 1) * U * mag).all())
 
 
@@ -158,15 +162,15 @@ def test_sparse_model_matches_the_oracle(tag, mode):
     x, y = inputs(tag, shape, batch, classes)
     ref_eval = O.imu_gcn_forward(x, sd, train=False, **fmt(kw))
     ref_logits, ref_loss, ref_grads = O.loss_and_grads(x, y, sd, **fmt(kw))
-    model = model.to(dev())
+    model = guarded.to(model, dev())
     with ops.math_mode(mode):
         model.eval()
         with torch.no_grad():
-            got_eval = model(x.float().to(dev())).cpu().double()
+            got_eval = model(guarded.to(x.float(), dev())).cpu().double()
         assert rel_l2(got_eval.numpy(), ref_eval.numpy()) < 2e-5
         model.train()
-        logits = model(x.float().to(dev()))
-        loss = F.cross_entropy(logits, y.to(dev()))
+        logits = model(guarded.to(x.float(), dev()))
+        loss = F.cross_entropy(logits, guarded.to(y, dev()))
         loss.backward()
     assert rel_l2(logits.detach().cpu().double().numpy(), ref_logits.numpy()) < 2e-5
     assert abs(float(loss.detach()) - float(ref_loss)) < 2e-5 * max(1.0, abs(float(ref_loss)))
@@ -198,9 +202,9 @@ def test_sparse_model_bf16_contract(tag):
     from fusion_gcn_amd import ops
     shape, classes, batch, kw = stgcn_case(tag)
     model, _ = build(tag, shape, classes, dict(kw, sparse=True))
-    model = model.to(dev()).train()
+    model = guarded.to(model, dev()).train()
     x, y = inputs(tag, shape, batch, classes)
-    x, y = x.float().to(dev()), y.to(dev())
+    x, y = guarded.to(x.float(), dev()), guarded.to(y, dev())
 
     def run():
         for p in model.parameters():
@@ -241,11 +245,11 @@ def test_route(monkeypatch, mode):
     x, y = inputs("value240", shape, batch, classes)
     for sparse in (True, False):
         model, _ = build("value240", shape, classes, dict(kw, sparse=True) if sparse else kw)
-        model = model.to(dev()).train()
+        model = guarded.to(model, dev()).train()
         layers = sum(isinstance(m, STGCNGraphConvolution) for m in model.modules())
         with monkeypatch.context() as mp, ops.math_mode(mode):
             c = Counter(mp, ops, ("transpose", "transpose_into", "graph_spmm"))
-            F.cross_entropy(model(x.float().to(dev())), y.to(dev())).backward()
+            F.cross_entropy(model(guarded.to(x.float(), dev())), guarded.to(y, dev())).backward()
             torch.cuda.synchronize()
         want = (0, 0, 2 * layers) if sparse else (2 * layers, 2 * layers, 0)
         assert (c.n["transpose"], c.n["transpose_into"], c.n["graph_spmm"]) == want, (sparse, c.n)
@@ -257,10 +261,10 @@ def test_auto_route_through_path_options(monkeypatch):
     from fusion_gcn_amd import ops
     shape, classes, batch, kw = stgcn_case("value240")
     x, y = inputs("value240", shape, batch, classes)
-    x, y = x.float().to(dev()), y.to(dev())
+    x, y = guarded.to(x.float(), dev()), guarded.to(y, dev())
     dense, _ = build("value240", shape, classes, kw)
     sparse, _ = build("value240", shape, classes, dict(kw, sparse=True))
-    dense, sparse = dense.to(dev()).train(), sparse.to(dev()).train()
+    dense, sparse = guarded.to(dense, dev()).train(), guarded.to(sparse, dev()).train()
     want = sparse(x).detach()
     for ppm, calls in ((50_000, True), (10, False)):
         with ops.context() as ctx, monkeypatch.context() as mp:
@@ -291,15 +295,15 @@ def test_sparse_late_fusion_matches_the_oracle(mode):
     x, y = late_inputs()
     ref_logits, ref_loss, ref_grads = late_loss_and_grads(x, y, sd)
     ref_eval = late_oracle(x, sd, train=False).detach()
-    model = model.to(dev())
-    xg = {k: v.float().to(dev()) for k, v in x.items()}
+    model = guarded.to(model, dev())
+    xg = {k: guarded.to(v.float(), dev()) for k, v in x.items()}
     with ops.math_mode(mode):
         model.eval()
         with torch.no_grad():
             assert rel_l2(model(xg).cpu().double().numpy(), ref_eval.numpy()) < 5e-5
         model.train()
         logits = model(xg)
-        loss = F.cross_entropy(logits, y.to(dev()))
+        loss = F.cross_entropy(logits, guarded.to(y, dev()))
         loss.backward()
     assert rel_l2(logits.detach().cpu().double().numpy(), ref_logits.numpy()) < 5e-5
     assert abs(float(loss.detach()) - float(ref_loss)) < 1e-4
@@ -324,9 +328,9 @@ def test_sparse_model_in_a_recorded_step(mode):
     from fusion_gcn_amd.session.procedures import DefaultStep, GraphStep
     shape, classes, batch, kw = stgcn_case("value240")
     model, _ = build("value240", shape, classes, dict(kw, sparse=True))
-    model = model.to(dev()).train()
+    model = guarded.to(model, dev()).train()
     x, y = inputs("value240", shape, batch, classes)
-    x, y = x.float().to(dev()), y.to(dev())
+    x, y = guarded.to(x.float(), dev()), guarded.to(y, dev())
     layers = [m for m in model.modules() if isinstance(m, STGCNGraphConvolution)]
 
     def run(step):
@@ -362,7 +366,7 @@ def test_sparse_model_in_a_recorded_step(mode):
     # model.to(...): every parameter and buffer gets a new home
     for p in model.parameters():          # (Module.to converts a held .grad in place -- here a view of the step's flat buffer: drop them first)
         p.grad = None
-    model.to("cpu").to(dev())
+    guarded.to(model.to("cpu"), dev())
     same(run(step), eager2)
     assert all(m._csr_cache[0][1] == m.adj.data_ptr() for m in layers)
 
@@ -374,7 +378,7 @@ def test_sparse_model_inference(tag):
     model, sd = build(tag, shape, classes, dict(kw, sparse=True))
     x, _ = inputs(tag, shape, batch, classes)
     want = O.imu_gcn_forward(x, sd, train=False, **fmt(kw))
-    model = model.to(dev()).eval()
+    model = guarded.to(model, dev()).eval()
     with torch.no_grad():
-        got = model(x.float().to(dev()))
+        got = model(guarded.to(x.float(), dev()))
     assert not got.requires_grad and rel_l2(got.cpu().double().numpy(), want.numpy()) < 2e-5

@@ -7,7 +7,11 @@ import torch
 
 from conftest import rel_l2
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 
 FWD_TOL = 3e-6
 RED_TOL = 2e-5
@@ -23,7 +27,7 @@ def rnd(*shape, seed=0, scale=1.0):
 
 
 def to_gpu(t):
-    return t.float().to(dev()).contiguous()
+    return guarded.put(t.float(), device=dev())
 
 
 def ref_rows_conv(x, w, tmap, T_out, bias=None):
@@ -441,13 +445,14 @@ def test_joint_mix_aggregation_and_its_transpose(V, cin):
 @pytest.mark.parametrize("V,cin", [(25, 64), (18, 128), (27, 256), (22, 192), (25, 4), (20, 32), (32, 64), (5, 8)])
 def test_joint_mix_channel_groups(V, cin, order, monkeypatch):
     """The channel-group kernel (1 or 2 channels per lane; every k-step template) gives the same agg / dx as the
-    einsum, with and without accumulation, and never writes outside its rows (canary row stride)."""
+    einsum, with and without accumulation, and never writes outside its tensors: ``agg`` and ``dx`` are guarded allocations (to_gpu ->
+    guarded.put) with 256 KiB of 0xFF on both sides, and the module's ``guarded_allocations`` fixture verifies those margins at teardown."""
     from fusion_gcn_amd import block, ops
     monkeypatch.setattr(ops.paths(), "mix_vw_order", order)      # (a per-context path option: fusion_gcn_amd/paths.py)
     B, T = 3, 9
     x, a = rnd(B, T, V, cin, seed=70), rnd(B, 3, V, V, seed=71, scale=0.3)
     want = torch.einsum("btvc,bkvw->btwkc", x, a).reshape(B, T, V, 3 * cin)
-    agg = torch.full((B, T, V, 3 * cin), 7.0, device=dev())
+    agg = to_gpu(torch.full((B, T, V, 3 * cin), 7.0))
     block.mix_agg(to_gpu(x), agg, to_gpu(a), cin)
     assert rel_l2(agg.cpu().numpy(), want.numpy()) < FWD_TOL
     dagg, base = rnd(B, T, V, 3 * cin, seed=72), rnd(B, T, V, cin, seed=73)
@@ -691,7 +696,7 @@ def test_spatial_backward_tile_form(V, T, cin, cout, B):
     assert rel_l2(dx.cpu().numpy(), torch.einsum("btwkc,kvw->btvc", dagg, a[0]).numpy()) < FWD_TOL
     # the ReLU-gated gradients of the block's two identity shortcuts (agcn.py:114,135) as the mix accumulators' start: dx = mix +
     # sum_i e_i * [bit of mask_i], the sign images from the real bn_act kernel
-    ident = torch.stack([torch.zeros(cin), torch.ones(cin), torch.ones(cin), torch.zeros(cin)]).float().to(dev())
+    ident = guarded.to(torch.stack([torch.zeros(cin), torch.ones(cin), torch.ones(cin), torch.zeros(cin)]).float(), dev())
     want_gated, gated = want_dx.clone(), []
     for i in range(2):
         e, pre = rnd(B, T, V, cin, seed=320 + i), rnd(B, T, V, cin, seed=330 + i)
@@ -953,7 +958,7 @@ def test_joint_dagg_adds_the_gated_shortcut_gradients(V, T, C, B, n_gated):
     dagg, base = rnd(B, T, V, 3 * C, seed=97), rnd(B, T, V, C, seed=98)
     want = torch.einsum("btwkc,bkvw->btvc", dagg.reshape(B, T, V, 3, C), a)
     gated = []
-    ident = torch.stack([torch.zeros(C), torch.ones(C), torch.ones(C), torch.zeros(C)]).float().to(dev())   # mean 0, rstd/scale 1, shift 0
+    ident = guarded.to(torch.stack([torch.zeros(C), torch.ones(C), torch.ones(C), torch.zeros(C)]).float(), dev())   # mean 0, rstd/scale 1, shift 0
     for i in range(n_gated):
         e, pre = rnd(B, T, V, C, seed=100 + i), rnd(B, T, V, C, seed=110 + i)
         out, mask = ops.bn_act(to_gpu(pre), ident, relu=True, sign_mask=True)
@@ -1072,7 +1077,7 @@ def test_batchnorm_epilogue_forward_backward(C, res_mode):
     assert rel_l2(sums[0].cpu().numpy(), dp.sum(0).numpy()) < RED_TOL
     assert rel_l2(sums[1].cpu().numpy(), (dp * a_hat).sum(0).numpy()) < RED_TOL
     if (rows * C) % 8 == 0:          # gate from the bit image: bit-identical to the gate from the tensor
-        bits = torch.from_numpy(np.packbits((out_want.detach().numpy().reshape(-1) > 0), bitorder="little")).to(dev())
+        bits = guarded.to(torch.from_numpy(np.packbits((out_want.detach().numpy().reshape(-1) > 0), bitorder="little")), dev())
         da2, db2, sums2 = ops.bn_act_bwd(to_gpu(dout), None, ag, vec_a, bg, vec_b, res_mode=res_mode, relu=True,
                                          train=True, sign_mask=bits)
         assert torch.equal(da2, da) and torch.equal(sums2, sums) and (db is None or torch.equal(db2, db))
@@ -1113,12 +1118,12 @@ def test_data_bn_matches_batchnorm1d(N, M, T, V, C, train):
         ref.running_mean.uniform_(-0.3, 0.3), ref.running_var.uniform_(0.5, 2.0)
     mine = torch.nn.BatchNorm1d(ch)
     mine.load_state_dict({k: (v.float() if v.is_floating_point() else v) for k, v in ref.state_dict().items()})
-    mine = mine.to(dev())
+    mine = guarded.to(mine, dev())
     ref.train(train), mine.train(train)
     x = (torch.randn(N, M, T, V, C, dtype=torch.float64) * 2 + 0.3)
     xr = x.clone().requires_grad_(True)
     h = ref(xr.permute(0, 1, 3, 4, 2).contiguous().view(N, ch, T)).view(N, M, V, C, T).permute(0, 1, 4, 2, 3).reshape(N * M, T, V, C)
-    xm = x.float().to(dev()).requires_grad_(True)
+    xm = guarded.to(x.float(), dev()).requires_grad_(True)
     got = data_bn(xm, mine)
     Cp = (C + 3) // 4 * 4
     assert got.shape == (N * M, T, V, Cp)
@@ -1126,7 +1131,7 @@ def test_data_bn_matches_batchnorm1d(N, M, T, V, C, train):
     assert float(got[..., C:].abs().max()) == 0.0 if Cp > C else True
     probe = torch.randn(N * M, T, V, Cp, dtype=torch.float64)
     (h * probe[..., :C]).sum().backward()
-    (got * probe.float().to(dev())).sum().backward()
+    (got * guarded.to(probe.float(), dev())).sum().backward()
     assert rel_l2(mine.weight.grad.cpu().numpy(), ref.weight.grad.numpy()) < 1e-5
     assert rel_l2(mine.bias.grad.cpu().numpy(), ref.bias.grad.numpy()) < 1e-5
     assert rel_l2(xm.grad.cpu().numpy(), xr.grad.numpy()) < 2e-5
@@ -1135,7 +1140,7 @@ def test_data_bn_matches_batchnorm1d(N, M, T, V, C, train):
     assert int(mine.num_batches_tracked) == int(ref.num_batches_tracked)
     # fixed-order sums: a second run gives the same bits
     mine.zero_grad()
-    xm2 = x.float().to(dev()).requires_grad_(True)
+    xm2 = guarded.to(x.float(), dev()).requires_grad_(True)
     got2 = data_bn(xm2, mine) if not train else None
     if got2 is not None:
         assert torch.equal(got2, got)
@@ -1157,20 +1162,20 @@ def test_cross_entropy_matches_torch(rows, classes):
     zr = z[:, :classes].clone().requires_grad_(True)
     want = F.cross_entropy(zr, y)
     (want * 1.7).backward()
-    base = z.float().to(dev()).requires_grad_(True)
+    base = guarded.to(z.float(), dev()).requires_grad_(True)
     loss_fn = CrossEntropyLoss()
-    got = loss_fn(base[:, :classes], y.to(dev()))
+    got = loss_fn(base[:, :classes], guarded.to(y, dev()))
     (got * 1.7).backward()
     assert abs(float(got) - float(want)) < 2e-6 * max(1.0, abs(float(want)))
     assert rel_l2(base.grad[:, :classes].cpu().numpy(), zr.grad.numpy()) < 2e-6
     assert float(base.grad[:, classes:].abs().max()) == 0.0 if npad > classes else True
-    again = loss_fn(base.detach()[:, :classes], y.to(dev()))
+    again = loss_fn(base.detach()[:, :classes], guarded.to(y, dev()))
     assert torch.equal(again, got.detach())
     # a label outside [0, classes) that is not ignore_index (torch: a device assert) fails loudly: NaN loss and gradients
     bad = y.clone()
     bad[0] = classes + 3
-    z2 = z.float().to(dev()).requires_grad_(True)
-    lb = loss_fn(z2[:, :classes], bad.to(dev()))
+    z2 = guarded.to(z.float(), dev()).requires_grad_(True)
+    lb = loss_fn(z2[:, :classes], guarded.to(bad, dev()))
     lb.backward()
     assert torch.isnan(lb) and torch.isnan(z2.grad[0, :classes]).all()
 

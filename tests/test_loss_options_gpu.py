@@ -11,7 +11,11 @@ import torch.nn.functional as F
 
 from conftest import rel_l2
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 REDUCTIONS = ("mean", "sum", "none")
 # 16 rows per workgroup: (1000, 3) runs on 63 workgroups with 8 rows in the last, (517, 1030) on 33 with 5 in the last
@@ -61,10 +65,10 @@ def reference(z, target, classes, weight, ignore_index, reduction, eps, up):
 
 def run(z, target, classes, weight, ignore_index, reduction, eps, up):
     from fusion_gcn_amd.loss import CrossEntropyLoss
-    base = z.float().to(DEV).requires_grad_(True)
-    loss_fn = CrossEntropyLoss(None if weight is None else weight.float(), ignore_index, reduction, eps).to(DEV)
+    base = guarded.to(z.float(), DEV).requires_grad_(True)
+    loss_fn = guarded.to(CrossEntropyLoss(None if weight is None else weight.float(), ignore_index, reduction, eps), DEV)
     got = loss_fn(base[:, :classes], target)
-    (got * (up.float().to(DEV) if reduction == "none" else 1.7)).sum().backward()
+    (got * (guarded.to(up.float(), DEV) if reduction == "none" else 1.7)).sum().backward()
     torch.cuda.synchronize()
     return got.detach().cpu(), base.grad.cpu()
 
@@ -91,7 +95,7 @@ def test_index_targets_match_torch(rows, classes, name, reduction):
     z, y, w, _, up = inputs(rows, classes, ignore_index)
     w = w if use_w else None
     want, want_grad = reference(z, y, classes, w, ignore_index, reduction, eps, up)
-    got, grad = run(z, y.to(DEV), classes, w, ignore_index, reduction, eps, up)
+    got, grad = run(z, guarded.to(y, DEV), classes, w, ignore_index, reduction, eps, up)
     compare(got, grad, want, want_grad, classes, reduction)
     ignored = (y == ignore_index).nonzero().flatten()
     assert ignored.numel() >= min(2, rows - 1)
@@ -106,7 +110,7 @@ def test_probability_targets_match_torch(rows, classes, use_w, eps, reduction):
     w = w if use_w else None
     assert abs(float(t[0].sum()) - 0.6) < 1e-6 and abs(float(t[1].sum()) - 1.0) < 1e-6
     want, want_grad = reference(z, t[:, :classes], classes, w, -100, reduction, eps, up)
-    got, grad = run(z, t.float().to(DEV)[:, :classes], classes, w, -100, reduction, eps, up)       # a window: its own row stride
+    got, grad = run(z, guarded.to(t.float(), DEV)[:, :classes], classes, w, -100, reduction, eps, up)       # a window: its own row stride
     compare(got, grad, want, want_grad, classes, reduction)
 
 
@@ -120,7 +124,7 @@ def test_every_row_ignored_and_zero_weights(reduction):
                            (torch.tensor([classes // 2] * (rows - 1) + [-100]), w, 0.0),           # every present class at weight 0
                            (torch.tensor([classes // 2] * (rows - 1) + [-100]), w, 0.1)):
         want, want_grad = reference(z, y, classes, weight, -100, reduction, eps, up)
-        got, grad = run(z, y.to(DEV), classes, weight, -100, reduction, eps, up)
+        got, grad = run(z, guarded.to(y, DEV), classes, weight, -100, reduction, eps, up)
         assert torch.equal(torch.isnan(got), torch.isnan(want)) and torch.equal(torch.isnan(grad[:, :classes]), torch.isnan(want_grad))
         if reduction == "mean":
             assert torch.isnan(got)
@@ -144,7 +148,7 @@ def test_invalid_label_is_nan_in_its_row(reduction):
     for bad_label in (classes, -1, 2 ** 40):
         bad = y.clone()
         bad[5] = bad_label
-        got, grad = run(z, bad.to(DEV), classes, w, -100, reduction, 0.1, up)
+        got, grad = run(z, guarded.to(bad, DEV), classes, w, -100, reduction, 0.1, up)
         other = torch.arange(rows) != 5
         assert torch.isnan(grad[5, :classes]).all() and not torch.isnan(grad[other]).any() and float(grad[:, classes:].abs().max()) == 0.0
         if reduction == "none":
@@ -162,10 +166,10 @@ def test_default_arguments_are_the_plain_path(rows, classes):
     from fusion_gcn_amd import block
     from fusion_gcn_amd.loss import CrossEntropyLoss, cross_entropy
     z, y, _, _, _ = inputs(rows, classes)
-    y = y.to(DEV)
+    y = guarded.to(y, DEV)
 
     def both(fn):
-        base = z.float().to(DEV).requires_grad_(True)
+        base = guarded.to(z.float(), DEV).requires_grad_(True)
         loss = fn(base[:, :classes], y)
         (loss * 1.7).backward()
         return loss.detach(), base.grad
@@ -175,7 +179,7 @@ def test_default_arguments_are_the_plain_path(rows, classes):
                lambda a, b: cross_entropy(a, b, None, -100, "mean", 0.0)):
         got, grad = both(fn)
         assert torch.equal(got, want) and torch.equal(grad, want_grad)
-    got, grad = both(CrossEntropyLoss(weight=torch.ones(classes)).to(DEV))
+    got, grad = both(guarded.to(CrossEntropyLoss(weight=torch.ones(classes)), DEV))
     assert close(float(got), float(want)) and rel_l2(grad.cpu().numpy(), want_grad.cpu().numpy()) < 2e-6
     assert float(grad[:, classes:].abs().max()) == 0.0
 
@@ -185,7 +189,7 @@ def test_two_runs_leave_the_same_bits():
     from fusion_gcn_amd import ops
     rows, classes = 517, 1030
     z, y, w, _, _ = inputs(rows, classes)
-    zd, yd, wd = z.float().to(DEV)[:, :classes], y.to(DEV), w.float().to(DEV)
+    zd, yd, wd = guarded.to(z.float(), DEV)[:, :classes], guarded.to(y, DEV), guarded.to(w.float(), DEV)
     runs = []
     for _ in range(2):
         loss, row_loss, row_scale, probs = ops.cross_entropy_opts_fwd(zd, yd, wd, label_smoothing=0.1)
@@ -203,10 +207,10 @@ def test_forward_without_autograd_returns_the_same_bits():
     from fusion_gcn_amd.loss import CrossEntropyLoss
     rows, classes = 64, 60
     z, y, w, _, _ = inputs(rows, classes)
-    yd = y.to(DEV)
+    yd = guarded.to(y, DEV)
     for reduction in REDUCTIONS:
-        loss_fn = CrossEntropyLoss(w.float(), reduction=reduction, label_smoothing=0.1).to(DEV)
-        base = z.float().to(DEV).requires_grad_(True)
+        loss_fn = guarded.to(CrossEntropyLoss(w.float(), reduction=reduction, label_smoothing=0.1), DEV)
+        base = guarded.to(z.float(), DEV).requires_grad_(True)
         with_grad = loss_fn(base[:, :classes], yd)
         assert with_grad.requires_grad
         with torch.no_grad():
@@ -227,15 +231,15 @@ def test_graph_step_replays_a_loss_with_options():
     shape, classes, clips = (1, 16, 20, 3), 27, 4
     model = Model(shape, classes, Graph(utd.skeleton_edges, center_joint=utd.center_joint), num_layers=2)
     filler.fill_state_dict(model.state_dict())
-    model = model.to(DEV).train()
+    model = guarded.to(model, DEV).train()
     twin = copy.deepcopy(model)
     g = torch.Generator().manual_seed(11)
-    x = torch.randn(clips, *shape, generator=g).to(DEV)
+    x = guarded.to(torch.randn(clips, *shape, generator=g), DEV)
     w = balanced_class_weights(torch.randint(0, classes, (200,), generator=g), classes) + 0.05
-    loss_fn = CrossEntropyLoss(weight=w, label_smoothing=0.1).to(DEV)
+    loss_fn = guarded.to(CrossEntropyLoss(weight=w, label_smoothing=0.1), DEV)
     step = GraphStep()
     for k in range(3):
-        y = torch.randint(0, classes, (clips,), generator=g).to(DEV)
+        y = guarded.to(torch.randint(0, classes, (clips,), generator=g), DEV)
         model.zero_grad()
         _, loss = step.forward(model, loss_fn, x, y)
         step.backward(loss)

@@ -12,7 +12,11 @@ import metrics_golden as MG
 from fusion_gcn_amd import _lib
 from fusion_gcn_amd import metrics as M
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 GUARD = 0x5A5A5A5A5A5A5A5A
 
@@ -24,7 +28,7 @@ def d():
 
 def _dev(batch):
     z, y, loss, idx = batch
-    return torch.from_numpy(z).to(DEV), torch.from_numpy(y).to(DEV), torch.tensor(float(loss), dtype=torch.float32).to(DEV), torch.from_numpy(idx)
+    return guarded.to(torch.from_numpy(z), DEV), guarded.to(torch.from_numpy(y), DEV), guarded.to(torch.tensor(float(loss), dtype=torch.float32), DEV), torch.from_numpy(idx)
 
 
 def _feed(container, d, s, step):
@@ -169,14 +173,14 @@ def _agcn(shape, classes):
     from fusion_gcn_amd.util import Graph
     model = Model(shape, classes, Graph(utd.skeleton_edges, center_joint=utd.center_joint))
     filler.fill_state_dict(model.state_dict())
-    return model.to(DEV)
+    return guarded.to(model, DEV)
 
 
 def _batches(sizes, shape, classes, seed=5):
     g = torch.Generator().manual_seed(seed)
     out, first = [], 0
     for n in sizes:
-        out.append((torch.randn(n, *shape, generator=g).to(DEV), torch.randint(0, classes, (n,), generator=g).to(DEV), first + torch.arange(n)))
+        out.append((guarded.to(torch.randn(n, *shape, generator=g), DEV), guarded.to(torch.randint(0, classes, (n,), generator=g), DEV), first + torch.arange(n)))
         first += n
     return out
 

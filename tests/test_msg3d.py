@@ -14,6 +14,12 @@ from conftest import rel_l2
 from oracle import filler
 from oracle import msg3d_oracle as O
 
+import guarded
+from guarded import guarded_gpu_tests  # noqa: F401  (the fixture)
+
+# the tests marked gpu run on guarded allocations, margins verified at teardown (tests/guarded.py); the host tests as they are
+pytestmark = pytest.mark.usefixtures("guarded_gpu_tests")
+
 CASES = {"utd": ((2, 1, 16, 20, 3), 27), "ntu": ((2, 2, 12, 25, 3), 60)}
 # conv biases in front of a train-mode BatchNorm: analytically zero gradient (compared absolutely)
 ZERO_GRAD = (".0.bias", ".conv.bias", "out_conv.bias")
@@ -108,10 +114,10 @@ def test_temporal_max_pool_kernel(B, T, V, C, stride):
     want = F.max_pool2d(x_ref, kernel_size=(3, 1), stride=(stride, 1), padding=(1, 0))
     probe = rnd(*want.shape, seed=2)
     (gx,) = torch.autograd.grad((want * probe).sum(), x_ref)
-    xg = x.to(dev()).requires_grad_(True)
+    xg = guarded.to(x, dev()).requires_grad_(True)
     got = fops.maxpool3(xg, stride)
     assert torch.equal(got.detach().cpu().double(), want.detach().permute(0, 2, 3, 1))
-    (got * probe.permute(0, 2, 3, 1).float().to(dev())).sum().backward()
+    (got * guarded.to(probe.permute(0, 2, 3, 1).float(), dev())).sum().backward()
     assert rel_l2(xg.grad.cpu().numpy(), gx.permute(0, 2, 3, 1).numpy()) < 1e-6
 
 
@@ -125,10 +131,10 @@ def test_unfold_windows_kernel(B, T, V, C, window, stride, dilation):
     want = O.unfold_windows(x_ref, window, stride, dilation)                      # (B, C, T', window * V)
     probe = rnd(*want.shape, seed=4)
     (gx,) = torch.autograd.grad((want * probe).sum(), x_ref)
-    xg = x.float().to(dev()).requires_grad_(True)
+    xg = guarded.to(x.float(), dev()).requires_grad_(True)
     got = fops.unfold_windows(xg, window, stride, dilation)
     assert torch.equal(got.detach().cpu().double(), want.detach().permute(0, 2, 3, 1).float().double())
-    (got * probe.permute(0, 2, 3, 1).float().to(dev())).sum().backward()
+    (got * guarded.to(probe.permute(0, 2, 3, 1).float(), dev())).sum().backward()
     assert rel_l2(xg.grad.cpu().numpy(), gx.permute(0, 2, 3, 1).numpy()) < 1e-6
 
 
@@ -143,10 +149,10 @@ def test_node_mix_aggregation(B, T, V, C, S, fgcn_math):
     want = O.aggregate(xr.permute(0, 3, 1, 2), ar, S).permute(0, 2, 3, 1)         # (B, T, V, S*C)
     probe = rnd(*want.shape, seed=7)
     gx, ga = torch.autograd.grad((want * probe).sum(), (xr, ar))
-    xg, ag = x.float().to(dev()).requires_grad_(True), a.float().to(dev()).requires_grad_(True)
+    xg, ag = guarded.to(x.float(), dev()).requires_grad_(True), guarded.to(a.float(), dev()).requires_grad_(True)
     got = fops.node_mix(xg, fops.node_mix_matrix(ag, S), S)
     assert rel_l2(got.detach().cpu().numpy(), want.detach().numpy()) < 3e-6
-    (got * probe.float().to(dev())).sum().backward()
+    (got * guarded.to(probe.float(), dev())).sum().backward()
     assert rel_l2(xg.grad.cpu().numpy(), gx.numpy()) < 3e-6
     assert rel_l2(ag.grad.cpu().numpy(), ga.numpy()) < 2e-5
 
@@ -157,7 +163,7 @@ def _gpu_model(tag):
     model = Model({"skeleton": shape[1:]}, classes, _graph(tag))
     filler.fill_state_dict(model.state_dict())
     sd = {k: (v.detach().double().clone() if v.is_floating_point() else v.detach().clone()) for k, v in model.state_dict().items()}
-    return model.to(dev()), sd
+    return guarded.to(model, dev()), sd
 
 
 @pytest.mark.gpu
@@ -172,10 +178,10 @@ def test_hip_model_matches_the_reference_and_the_oracle(golden, tag, fgcn_math):
     a = ref[f"{tag}.a_binary"]
     model.eval()
     with torch.no_grad():
-        e_eval = rel_l2(model(x.float().to(dev())).cpu().numpy(), ref[f"{tag}.eval.logits"])
+        e_eval = rel_l2(model(guarded.to(x.float(), dev())).cpu().numpy(), ref[f"{tag}.eval.logits"])
     model.train()
-    logits = model(x.float().to(dev()))
-    loss = F.cross_entropy(logits, labels.to(dev()))
+    logits = model(guarded.to(x.float(), dev()))
+    loss = F.cross_entropy(logits, guarded.to(labels, dev()))
     loss.backward()
     e_train = rel_l2(logits.detach().cpu().numpy(), ref[f"{tag}.train.logits"])
     d_loss = abs(float(loss.detach()) - float(ref[f"{tag}.train.loss"]))
@@ -206,8 +212,8 @@ def test_msg3d_resolves_through_import_model_and_loads_reference_shaped_checkpoi
     a, b = Model({"skeleton": shape[1:]}, classes, _graph("utd")), Model({"skeleton": shape[1:]}, classes, _graph("utd"))
     filler.fill_state_dict(a.state_dict())
     b.load_state_dict(a.state_dict())
-    a, b = a.to(dev()).eval(), b.to(dev()).eval()
-    x = torch.from_numpy(filler.skeleton_input("x.msg3d.utd", shape)).float().to(dev())
+    a, b = guarded.to(a, dev()).eval(), guarded.to(b, dev()).eval()
+    x = guarded.to(torch.from_numpy(filler.skeleton_input("x.msg3d.utd", shape)).float(), dev())
     with torch.no_grad():
         assert torch.equal(a(x), b(x))
 
@@ -228,13 +234,13 @@ def test_conv_rows_matches_conv2d(B, T, V, K, N, kt, stride, dil, fgcn_math):
     want = F.conv2d(xr, wr, br, stride=(stride, 1), padding=(pad, 0), dilation=(dil, 1))
     probe = rnd(*want.shape, seed=14)
     gx, gw, gb = torch.autograd.grad((want * probe).sum(), (xr, wr, br))
-    xg = x.float().to(dev()).requires_grad_(True)
-    wg, bg = w.float().to(dev()).requires_grad_(True), b.float().to(dev()).requires_grad_(True)
+    xg = guarded.to(x.float(), dev()).requires_grad_(True)
+    wg, bg = guarded.to(w.float(), dev()).requires_grad_(True), guarded.to(b.float(), dev()).requires_grad_(True)
     got, part = fops.conv_rows(xg, wg[..., 0].permute(2, 1, 0), bg, tmap=temporal_map(kt, stride, dil), T_out=out_frames(T, stride), stats=True)
     assert rel_l2(got.detach().cpu().numpy(), want.detach().permute(0, 2, 3, 1).numpy()) < 3e-6
     flat = want.detach().permute(0, 2, 3, 1).reshape(-1, N)
     assert rel_l2(part.double().sum(0)[0].cpu().numpy(), flat.sum(0).numpy()) < 2e-5          # BatchNorm partial sums of the epilogue
-    (got * probe.permute(0, 2, 3, 1).float().to(dev())).sum().backward()
+    (got * guarded.to(probe.permute(0, 2, 3, 1).float(), dev())).sum().backward()
     assert rel_l2(xg.grad.cpu().numpy(), gx.permute(0, 2, 3, 1).numpy()) < 3e-6
     assert rel_l2(wg.grad.cpu().numpy(), gw.numpy()) < 2e-5
     assert rel_l2(bg.grad.cpu().numpy(), gb.numpy()) < 2e-5
@@ -250,7 +256,7 @@ def test_multi_scale_temporal_block_matches_the_oracle(stride, cin, cout, fgcn_m
     blk = MultiScale_TemporalConv(cin, cout, stride=stride)
     filler.fill_state_dict(blk.state_dict(), prefix="tcn1.")
     sd = {"tcn1." + k: (v.detach().double().clone() if v.is_floating_point() else v.detach().clone()) for k, v in blk.state_dict().items()}
-    blk = blk.to(dev()).train()
+    blk = guarded.to(blk, dev()).train()
     x = torch.from_numpy(filler.bellish("x.mstcn", (B, cin, T, V)))
     params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if v.is_floating_point() and not k.endswith(("running_mean", "running_var"))}
     live = dict(sd)
@@ -260,11 +266,11 @@ def test_multi_scale_temporal_block_matches_the_oracle(stride, cin, cout, fgcn_m
     want = O.ms_tcn(xo, live, "tcn1", stride, True, stats)
     probe = rnd(*want.shape, seed=21)
     grads = torch.autograd.grad((want * probe).sum(), [xo] + list(params.values()), allow_unused=True)
-    xg = x.float().permute(0, 2, 3, 1).contiguous().to(dev()).requires_grad_(True)
+    xg = guarded.to(x.float().permute(0, 2, 3, 1).contiguous(), dev()).requires_grad_(True)
     got = blk(xg)
     assert rel_l2(got.detach().cpu().numpy(), want.detach().permute(0, 2, 3, 1).numpy()) < 2e-5
     flips = int(((got.detach().cpu() > 0) != (want.detach().permute(0, 2, 3, 1) > 0)).sum())
-    (got * probe.permute(0, 2, 3, 1).float().to(dev())).sum().backward()
+    (got * guarded.to(probe.permute(0, 2, 3, 1).float(), dev())).sum().backward()
     tol = 2e-4 if flips == 0 else 5e-3
     assert rel_l2(xg.grad.cpu().numpy(), grads[0].permute(0, 2, 3, 1).numpy()) < tol, flips
     scale = max(float(g.abs().max()) for g in grads[1:] if g is not None)
@@ -287,9 +293,9 @@ def test_standalone_module_repacks_its_weights_after_an_in_place_update(fgcn_mat
     B, T, V, cin, cout = 2, 10, 20, 96, 96
     blk = MultiScale_TemporalConv(cin, cout, stride=1)
     filler.fill_state_dict(blk.state_dict(), prefix="tcn1.")
-    blk = blk.to(dev()).train()
+    blk = guarded.to(blk, dev()).train()
     x = torch.from_numpy(filler.bellish("x.mstcn.stale", (B, cin, T, V)))
-    xg = x.float().permute(0, 2, 3, 1).contiguous().to(dev())
+    xg = guarded.to(x.float().permute(0, 2, 3, 1).contiguous(), dev())
 
     def oracle():
         sd = {"tcn1." + k: (v.detach().double().cpu().clone() if v.is_floating_point() else v.detach().cpu().clone())
@@ -373,7 +379,7 @@ def _device_input(x):
     xl = _cl(x).float()
     if x.shape[1] == 3:
         xl = torch.nn.functional.pad(xl, (0, 1))
-    return xl.contiguous().to(dev()).requires_grad_(True)
+    return guarded.put(xl, device=dev()).requires_grad_(True)
 
 
 def _finish(ref, want, probe, xo, params, stats, **more):
@@ -524,7 +530,7 @@ def _assert_one_batch_tracked(mod):
 
 
 def _backward(got, ref):
-    (got * _cl(ref["probe"]).float().to(dev())).sum().backward()
+    (got * guarded.to(_cl(ref["probe"]).float(), dev())).sum().backward()
 
 
 @pytest.mark.parametrize("kind,case", [("gcn", c) for c in GCN_CASES] + [("stgcn", c) for c in G3D_CASES])
@@ -554,7 +560,7 @@ def test_multi_scale_graph_conv_matches_the_oracle(tag, cin, cout, fgcn_math):
     MASK_EPS of zero, so no ReLU decision of float32 enters and every gradient keeps the tight bound."""
     ref = _gcn_reference(tag, cin, cout)
     assert ref["masked"] <= MASK_CAP
-    mod = _new_gcn(tag, cin, cout).to(dev()).train()
+    mod = guarded.to(_new_gcn(tag, cin, cout), dev()).train()
     xg = _device_input(ref["x"])
     got = mod(xg)
     assert ("A.a" in mod._forms.forms) == (tag == "utd")                   # the route the case is there for
@@ -571,7 +577,7 @@ def test_spatial_temporal_graph_conv_matches_the_oracle(tag, cin, cout, window, 
     forms route; ntu: 125 nodes, 750 columns, the torch route; (5, 1, 4): whole windows of padding."""
     ref = _stgcn_reference(tag, cin, cout, window, stride, T)
     assert ref["masked"] <= MASK_CAP
-    mod = _new_g3d(tag, cin, cout, window, stride).gcn3d.to(dev()).train()
+    mod = guarded.to(_new_g3d(tag, cin, cout, window, stride).gcn3d, dev()).train()
     xg = _device_input(ref["x"])
     got = mod(xg)
     _backward(got, ref)
@@ -604,7 +610,7 @@ def test_g3d_pathway_matches_the_oracle(tag, cin, cout, window, stride, T, fgcn_
     BatchNorm) vs O.ms_g3d.  The ReLU is inside: its decisions are compared with the oracle's hidden tensor through a forward hook; the
     tight gradient bound when none differs, 5e-3 otherwise, and never more than 1e-4 of them may differ."""
     ref = _g3d_reference(tag, cin, cout, window, stride, T)
-    mod = _new_g3d(tag, cin, cout, window, stride).to(dev()).train()
+    mod = guarded.to(_new_g3d(tag, cin, cout, window, stride), dev()).train()
     xg = _device_input(ref["x"])
     got, flips, total = _run_with_flips(mod, [mod], [ref["hidden"]], xg)
     _backward(got, ref)
@@ -629,10 +635,10 @@ def test_add_act_equals_torch_including_the_ties(shape, relu, fgcn_math):
     want = torch.relu(ar + br) if relu else ar + br
     probe = rnd(*shape, seed=42).float()
     ga, gb = torch.autograd.grad((want * probe).sum(), (ar, br))
-    ag, bg = a.to(dev()).requires_grad_(True), b.to(dev()).requires_grad_(True)
+    ag, bg = guarded.to(a, dev()).requires_grad_(True), guarded.to(b, dev()).requires_grad_(True)
     got = fops.add_act(ag, bg, relu=relu)
     assert torch.equal(got.detach().cpu(), want.detach())
-    (got * probe.to(dev())).sum().backward()
+    (got * guarded.to(probe, dev())).sum().backward()
     assert torch.equal(ag.grad.cpu(), ga) and torch.equal(bg.grad.cpu(), gb)
     if relu:
         assert not ag.grad.cpu()[a + b == 0].any()
@@ -667,7 +673,7 @@ def test_multi_window_g3d_matches_the_sum_of_the_oracles_pathways(fgcn_math):
     ref = _multi_window_reference(tag, cin, cout, stride, T)
     mod = MultiWindow_MS_G3D(cin, cout, _a_binary(tag), G3D_SCALES, window_stride=stride)
     mod.load_state_dict(ref["module"])
-    mod = mod.to(dev()).train()
+    mod = guarded.to(mod, dev()).train()
     xg = _device_input(ref["x"])
     got, flips, total = _run_with_flips(mod, list(mod.gcn3d), ref["hidden"], xg)
     _backward(got, ref)
@@ -692,7 +698,7 @@ def test_graph_conv_in_eval_mode_matches_the_oracle(fgcn_math):
     statistics (the masked probe again), which the forward must leave bit for bit as they were, like num_batches_tracked."""
     ref = _gcn_reference("utd", 96, 96, False)
     assert ref["masked"] <= MASK_CAP and not ref["stats"]
-    mod = _new_gcn("utd", 96, 96).to(dev()).eval()
+    mod = guarded.to(_new_gcn("utd", 96, 96), dev()).eval()
     before = _buffers(mod)
     xg = _device_input(ref["x"])
     got = mod(xg)
@@ -707,7 +713,7 @@ def test_g3d_pathway_in_eval_mode_matches_the_oracle(fgcn_math):
     case = ("utd", 96, 192, 3, 2, 11)
     ref = _g3d_reference(*case, False)
     assert not ref["stats"]
-    mod = _new_g3d(*case[:5]).to(dev()).eval()
+    mod = guarded.to(_new_g3d(*case[:5]), dev()).eval()
     before = _buffers(mod)
     xg = _device_input(ref["x"])
     got, flips, total = _run_with_flips(mod, [mod], [ref["hidden"]], xg)
@@ -732,9 +738,9 @@ def test_standalone_graph_conv_repacks_its_matrix_after_an_update(kind, fgcn_mat
         from fusion_gcn_amd.models.msg3d.ms_gtcn import SpatialTemporal_MS_GCN
         blk, S, nodes, const = SpatialTemporal_MS_GCN(C, C, _a_binary("utd"), G3D_SCALES, 3), G3D_SCALES, 3 * V, "A_scales"
     filler.fill_state_dict(blk.state_dict(), prefix="stale.")
-    blk = blk.to(dev()).train()
+    blk = guarded.to(blk, dev()).train()
     x = torch.from_numpy(filler.bellish(f"x.{kind}.stale", (BATCH, C, T, nodes)))
-    xg = _cl(x).float().contiguous().to(dev())
+    xg = guarded.to(_cl(x).float().contiguous(), dev())
 
     def oracle():
         sd = _state64(blk, "p.")
@@ -781,11 +787,11 @@ def test_bn_act_gates_from_the_output_when_there_is_no_sign_image(fgcn_math):
     bn = torch.nn.BatchNorm2d(C)
     with torch.no_grad():
         bn.weight.copy_(gamma), bn.bias.copy_(beta)
-    bn = bn.to(dev()).train()
-    xg, wg = x.float().to(dev()).requires_grad_(True), w.float().to(dev()).requires_grad_(True)
-    y, part = fops.conv_rows(xg, wg.t().unsqueeze(0), b.float().to(dev()), stats=True)
+    bn = guarded.to(bn, dev()).train()
+    xg, wg = guarded.to(x.float(), dev()).requires_grad_(True), guarded.to(w.float(), dev()).requires_grad_(True)
+    y, part = fops.conv_rows(xg, wg.t().unsqueeze(0), guarded.to(b.float(), dev()), stats=True)
     got = fops.bn_act(y, part, bn, relu=True)
-    (got * _cl(probe).float().to(dev())).sum().backward()
+    (got * guarded.to(_cl(probe).float(), dev())).sum().backward()
     errs = [rel_l2(got.detach().cpu().numpy(), _cl(torch.relu(u)).detach().numpy())]
     errs += [rel_l2(g.grad.cpu().numpy(), want.numpy()) for g, want in zip((xg, wg, bn.weight, bn.bias), wants)]
     print(f"[msg3d bn_act without a sign image {fgcn_math}] forward {errs[0]:.2e}, gradients of x, w, gamma, beta " + ", ".join(f"{e:.2e}" for e in errs[1:]))

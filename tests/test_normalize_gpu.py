@@ -12,7 +12,11 @@ import torch
 import normalize_ref as N
 from test_normalize import CASES
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 
 
@@ -22,7 +26,7 @@ def _kw(origin, zp, xp):
 
 def _run(src, idx, **kw):
     from fusion_gcn_amd import ops
-    out, frame_map, params = ops.clip_normalize(torch.as_tensor(src).to(DEV), torch.as_tensor(idx, dtype=torch.int64), **kw)
+    out, frame_map, params = ops.clip_normalize(guarded.to(torch.as_tensor(src), DEV), torch.as_tensor(idx, dtype=torch.int64), **kw)
     torch.cuda.synchronize()
     return out.cpu().numpy(), frame_map.cpu().numpy(), params.cpu().numpy()
 
@@ -170,7 +174,7 @@ def test_clip_batches_resident_and_streaming_deliver_the_normalised_rows(raw_dat
     from fusion_gcn_amd import ops
     from fusion_gcn_amd.data import Normalize
     ds, clips, inertial = raw_dataset
-    want, _, _ = ops.clip_normalize(torch.from_numpy(clips).to(DEV), torch.arange(10), **KW7)
+    want, _, _ = ops.clip_normalize(guarded.to(torch.from_numpy(clips), DEV), torch.arange(10), **KW7)
     want = want.cpu()
     (res_it, res), (str_it, stream) = _epoch(ds, resident=True), _epoch(ds, resident=False)
     assert res_it.resident and not str_it.resident and [len(b[2]) for b in res] == [4, 4, 2]
@@ -190,7 +194,7 @@ def test_augmentation_reads_the_normalised_clips(raw_dataset, resident):
     from fusion_gcn_amd import ops
     from fusion_gcn_amd.data import Augment, ClipBatches
     ds, clips, _ = raw_dataset
-    normalised, _, _ = ops.clip_normalize(torch.from_numpy(clips).to(DEV), torch.arange(10), **KW7)
+    normalised, _, _ = ops.clip_normalize(guarded.to(torch.from_numpy(clips), DEV), torch.arange(10), **KW7)
     aug = Augment(only=["skeleton"])
     it = ClipBatches(ds, BS, shuffle=True, seed=5, device=DEV, resident=resident, normalize=_norm(), augment=aug)
     it.set_epoch(2)
@@ -199,7 +203,7 @@ def test_augmentation_reads_the_normalised_clips(raw_dataset, resident):
         want, table = ops.clip_augment(normalised, idx, idx, seed=5, epoch=2, site=aug.site, max_angle=aug.max_angle, scale=aug.scale,
                                        min_window=aug.min_window, joints=(0, 7))
         assert torch.equal(feats["skeleton"].view(torch.int32), want.view(torch.int32)) and torch.equal(it.last_params["skeleton"], table)
-        assert not torch.equal(feats["skeleton"], normalised[idx.to(DEV)])
+        assert not torch.equal(feats["skeleton"], normalised[guarded.to(idx, DEV)])
         seen += len(idx)
     assert seen == 10
 

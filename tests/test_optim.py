@@ -9,6 +9,12 @@ import pytest
 import torch
 import torch.nn as nn
 
+import guarded
+from guarded import guarded_gpu_tests  # noqa: F401  (the fixture)
+
+# the tests marked gpu run on guarded allocations, margins verified at teardown (tests/guarded.py); the host tests as they are
+pytestmark = pytest.mark.usefixtures("guarded_gpu_tests")
+
 
 def small_model(seed=0):
     torch.manual_seed(seed)
@@ -68,7 +74,7 @@ def test_fused_update_matches_torch_optim(name, args):
     from fusion_gcn_amd.optim import FlatOptimizer
     dev = torch.device("cuda:0")
     ref_model = small_model(3)
-    model = copy.deepcopy(ref_model).to(dev)
+    model = guarded.to(copy.deepcopy(ref_model), dev)
     ref = TORCH[name](ref_model.parameters(), 0.05, **args)
     opt = FlatOptimizer(model.parameters(), name, 0.05, **args)
     sched_r = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(ref, T_0=3)
@@ -80,7 +86,7 @@ def test_fused_update_matches_torch_optim(name, args):
         for pr, po in zip(ref_model.parameters(), model.parameters()):
             grad = torch.randn(pr.shape, generator=g) * (1.0 + it)
             pr.grad = grad.clone()
-            po.grad = grad.to(dev)
+            po.grad = guarded.to(grad, dev)
         ref.step()
         opt.step()
         sched_r.step()
@@ -104,7 +110,7 @@ def test_fused_update_matches_torch_optim(name, args):
     sd = opt.state_dict()
     other = TORCH[name](copy.deepcopy(ref_model).parameters(), 0.05, **args)
     other.load_state_dict(sd)
-    opt2 = FlatOptimizer(copy.deepcopy(ref_model).to(dev).parameters(), name, 0.05, **args)
+    opt2 = FlatOptimizer(guarded.to(copy.deepcopy(ref_model), dev).parameters(), name, 0.05, **args)
     opt2.load_state_dict(ref.state_dict())
     if name != "SGD":
         assert opt2.steps == 6 and opt.steps == 7
@@ -116,12 +122,12 @@ def test_fused_update_matches_torch_optim(name, args):
 def test_grad_scale_is_the_data_parallel_average():
     from fusion_gcn_amd.optim import FlatOptimizer
     dev = torch.device("cuda:0")
-    a, b = small_model(5).to(dev), small_model(5).to(dev)
+    a, b = guarded.to(small_model(5), dev), guarded.to(small_model(5), dev)
     oa, ob = FlatOptimizer(a.parameters(), "ADAM", 0.01, weight_decay=0.01), FlatOptimizer(b.parameters(), "ADAM", 0.01, weight_decay=0.01)
     ob.grad_scale = 0.25
     g = torch.Generator().manual_seed(1)
     for pa, pb in zip(a.parameters(), b.parameters()):
-        grad = torch.randn(pa.shape, generator=g).to(dev)
+        grad = guarded.to(torch.randn(pa.shape, generator=g), dev)
         pa.grad, pb.grad = grad.clone(), grad * 4.0
     oa.step(), ob.step()
     for pa, pb in zip(a.parameters(), b.parameters()):

@@ -12,7 +12,13 @@ import torch.nn.functional as F
 
 from test_optim_asgd import ARGS, small_model, two_groups
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+to_device = guarded.to           # (tests here take a parameter named ``guarded``)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 TOL = 2e-6
 LR = 0.05
@@ -32,7 +38,7 @@ def pair(args, seed=3, groups=None, **guard):
     """(CPU model, torch.optim.ASGD), (device model, FlatOptimizer) from one state, each under a CosineAnnealingWarmRestarts(T_0=3)."""
     from fusion_gcn_amd.optim import FlatOptimizer
     ref_model = small_model(seed)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = to_device(copy.deepcopy(ref_model), DEV)
     ref = torch.optim.ASGD(groups(ref_model) if groups else ref_model.parameters(), LR, **args)
     opt = FlatOptimizer(groups(model) if groups else model.parameters(), "ASGD", LR, **args, **guard)
     sched = [torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(o, T_0=3) for o in (ref, opt)]
@@ -47,7 +53,7 @@ def ours(model, args=None, seed=3, groups=None, **guard):
 
 def feed(model, grads, dev=None):
     for p, g in zip(model.parameters(), grads):
-        p.grad = g.clone() if dev is None else g.to(dev)
+        p.grad = g.clone() if dev is None else to_device(g, dev)
 
 
 def assert_matches_torch(ref_model, ref, model, opt, what):
@@ -97,7 +103,7 @@ def test_guard_that_never_clips_is_the_plain_update():
     first = {}
     for name, args in zip(("defaults", "t0_wd", "t0_lambd_alpha_wd"), ARGS):
         base = small_model(3)
-        ma, mb = copy.deepcopy(base).to(DEV), copy.deepcopy(base).to(DEV)
+        ma, mb = to_device(copy.deepcopy(base), DEV), to_device(copy.deepcopy(base), DEV)
         (oa, sa), (ob, sb) = ours(ma, args), ours(mb, args, max_grad_norm=1e30)
         first[name] = None
         for it, grads in enumerate(gradients(base, 8)):
@@ -187,14 +193,14 @@ def test_one_group_through_the_grouped_call_is_the_single_group_call():
     n = 4 * 2085
     cuts = ([1024, 1024, 37], [250] * 8 + [85], [1, 1023, 512, 549])
     g = torch.Generator().manual_seed(11)
-    p0, grad, ax0 = (torch.randn(n, generator=g).to(DEV) for _ in range(3))
-    v0 = torch.rand(n, generator=g).to(DEV)                   # ADAM's exp_avg_sq
+    p0, grad, ax0 = (to_device(torch.randn(n, generator=g), DEV) for _ in range(3))
+    v0 = to_device(torch.rand(n, generator=g), DEV)                   # ADAM's exp_avg_sq
     stream = torch.cuda.current_stream(DEV).cuda_stream
 
     def run(kind, scalars, counts, guarded):
         """One call with the count going from 2 to 3 and grad_scale 0.5 -> (params, state1[, state2][, guard state, group_sched])."""
         assert sum(counts) == n // 4
-        tiles = torch.tensor([[sum(counts[:i]), c, 0] for i, c in enumerate(counts)], dtype=torch.int32).to(DEV)
+        tiles = to_device(torch.tensor([[sum(counts[:i]), c, 0] for i, c in enumerate(counts)], dtype=torch.int32), DEV)
         out = [p0.clone(), ax0.clone()] + ([v0.clone()] if kind == 1 else [])
         groups = (_lib.OptimGroup * 1)(_lib.OptimGroup(*scalars))
         guard = None
@@ -205,7 +211,7 @@ def test_one_group_through_the_grouped_call_is_the_single_group_call():
             sched = torch.zeros((4 if kind == 3 else 2) * _lib.OPT_MAX_GROUPS, dtype=torch.float64)
             if kind == 3:
                 sched[:4] = torch.tensor([scalars[5], scalars[6]] * 2, dtype=torch.float32).double()      # eta, mu: use and next
-            sched = sched.to(DEV)
+            sched = to_device(sched, DEV)
             guard = _lib.OptimGuard(1.0, 1, lib.fgcn_grad_norm_tiles(n), partials.data_ptr(), state.data_ptr(), sched.data_ptr())
             out += [state, sched]
         rc = lib.fgcn_optim_step(out[0].data_ptr(), grad.data_ptr(), out[1].data_ptr(), out[2].data_ptr() if kind == 1 else None, n, kind,
@@ -242,7 +248,7 @@ def test_one_group_through_the_grouped_call_is_the_single_group_call():
 
 def test_two_optimizers_from_one_state_agree_bit_for_bit():
     base = small_model(3)
-    ma, mb = copy.deepcopy(base).to(DEV), copy.deepcopy(base).to(DEV)
+    ma, mb = to_device(copy.deepcopy(base), DEV), to_device(copy.deepcopy(base), DEV)
     (oa, sa), (ob, sb) = ours(ma, ARGS[2]), ours(mb, ARGS[2])
     for grads in gradients(base, 5):
         feed(ma, grads, DEV), feed(mb, grads, DEV)
@@ -275,7 +281,7 @@ def test_state_dict_loads_into_torch_asgd_and_back(guarded):
             assert torch.equal(got[i][k].cpu(), mine["state"][i][k].cpu()), (i, k)
         assert float(got[i]["step"]) == 6.0 and got[i]["eta"].dtype == torch.float32
     # torch's into a fresh one of ours (on the guarded path the load writes group_sched) and out again
-    model2 = copy.deepcopy(ref_model).to(DEV)
+    model2 = to_device(copy.deepcopy(ref_model), DEV)
     opt2 = FlatOptimizer(model2.parameters(), "ASGD", LR, **args, **guard)
     theirs = ref.state_dict()
     opt2.load_state_dict(theirs)
@@ -304,10 +310,10 @@ def test_averaged_evaluates_the_model_with_ax():
     shape, classes = (1, 24, 20, 3), 27
     model = Model(shape, classes, Graph(utd.skeleton_edges, center_joint=utd.center_joint))
     filler.fill_state_dict(model.state_dict())
-    model = model.to(DEV).train()
+    model = to_device(model, DEV).train()
     opt = FlatOptimizer(model.parameters(), "ASGD", 0.01, t0=0)
     g = torch.Generator().manual_seed(5)
-    x, y = torch.randn(4, *shape, generator=g).to(DEV), torch.randint(0, classes, (4,), generator=g).to(DEV)
+    x, y = to_device(torch.randn(4, *shape, generator=g), DEV), to_device(torch.randint(0, classes, (4,), generator=g), DEV)
     with pytest.raises(RuntimeError, match="before the first applied step"):
         with opt.averaged():
             pass
@@ -344,7 +350,7 @@ def test_c_abi_refuses_what_the_header_says():
     lib = _lib.load()
     n = 64
     p, grad, ax = (torch.zeros(n, device=DEV) for _ in range(3))
-    tiles = torch.tensor([[0, n // 4, 0]], dtype=torch.int32).to(DEV)
+    tiles = to_device(torch.tensor([[0, n // 4, 0]], dtype=torch.int32), DEV)
 
     def call(state1, lambd):
         groups = (_lib.OptimGroup * 1)(_lib.OptimGroup(0.1, 0.0, lambd, 0.75, 1e6, 0.1, 1.0, 0))

@@ -17,7 +17,13 @@ import torch.nn as nn
 
 from test_optim_groups import CASES, TORCH, group_model, three_groups
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+to_device = guarded.to           # (tests here take a parameter named ``guarded``)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 SCHEDULES = [lambda e: 0.9 ** e, lambda e: 1.0 / (1 + e), lambda e: 1.0 if e < 3 else 0.5]     # one per group
 
@@ -65,7 +71,7 @@ def _bits(t):
 def test_equal_groups_are_the_single_group_bit_for_bit(kind, args, _overrides, max_norm):
     from fusion_gcn_amd.optim import FlatOptimizer
     base = group_model(3)
-    ma, mb = copy.deepcopy(base).to(DEV), copy.deepcopy(base).to(DEV)
+    ma, mb = to_device(copy.deepcopy(base), DEV), to_device(copy.deepcopy(base), DEV)
     single = FlatOptimizer(ma.parameters(), kind, 0.05, max_grad_norm=max_norm, **args)
     grouped = _shared(mb, ({}, {}, {}), kind, max_grad_norm=max_norm, **args)
     scheds = [torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(o, T_0=3) for o in (single, grouped)]
@@ -106,7 +112,7 @@ def test_each_group_is_its_own_optimizer_bit_for_bit(kind, args, overrides):
     betas / momentum against one single-group FlatOptimizer per group, over copies of just that group's parameters."""
     from fusion_gcn_amd.optim import FlatOptimizer
     base = group_model(3)
-    model = copy.deepcopy(base).to(DEV)
+    model = to_device(copy.deepcopy(base), DEV)
     opt = _shared(model, overrides, kind, **args)
     sched = torch.optim.lr_scheduler.LambdaLR(opt, SCHEDULES)
     where = {id(p): i for i, p in enumerate(model.parameters())}
@@ -148,7 +154,7 @@ def test_each_group_is_its_own_optimizer_bit_for_bit(kind, args, overrides):
 def test_grouped_update_matches_torch_optim(kind, args, overrides):
     from fusion_gcn_amd.optim import FlatOptimizer
     ref_model = group_model(3)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = to_device(copy.deepcopy(ref_model), DEV)
     ref = TORCH[kind](three_groups(ref_model, overrides), 0.05, **args)
     opt = FlatOptimizer(three_groups(model, overrides), kind, 0.05, **args)      # its own buffers: the concatenation of the groups
     assert opt._group_of == [0, 0, 0, 1, 1, 1, 1, 2, 2, 2]
@@ -180,7 +186,7 @@ def test_grouped_update_matches_torch_optim(kind, args, overrides):
     sd = opt.state_dict()
     other = TORCH[kind](three_groups(copy.deepcopy(ref_model), overrides), 0.05, **args)
     other.load_state_dict(sd)
-    opt2 = FlatOptimizer(three_groups(copy.deepcopy(ref_model).to(DEV), overrides), kind, 0.05, **args)
+    opt2 = FlatOptimizer(three_groups(to_device(copy.deepcopy(ref_model), DEV), overrides), kind, 0.05, **args)
     opt2.load_state_dict(ref.state_dict())
     if kind != "SGD":
         assert opt2.steps == 6 and opt.steps == 7
@@ -192,7 +198,7 @@ def test_grouped_update_matches_torch_optim(kind, args, overrides):
 @pytest.mark.parametrize("kind,args,overrides", CASES)
 def test_clipped_grouped_update_matches_clip_grad_norm_and_torch_optim(kind, args, overrides):
     ref_model = group_model(3)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = to_device(copy.deepcopy(ref_model), DEV)
     steps = _grad_steps(ref_model)
     norms = [math.sqrt(sum(float(t.double().pow(2).sum()) for t in grads)) for grads in steps]
     max_norm = norms[2]
@@ -230,7 +236,7 @@ def test_clipped_grouped_update_matches_clip_grad_norm_and_torch_optim(kind, arg
 @pytest.mark.parametrize("kind,args,overrides", CASES)
 def test_nonfinite_gradient_in_one_group_skips_every_group(kind, args, overrides, bad):
     ref_model = group_model(3)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = to_device(copy.deepcopy(ref_model), DEV)
     ref = TORCH[kind](three_groups(ref_model, overrides), 0.05, **args)
     opt = _shared(model, overrides, kind, skip_nonfinite=True, **args)
     steps = _grad_steps(ref_model, steps=4)
@@ -269,7 +275,7 @@ def test_nonfinite_gradient_in_one_group_skips_every_group(kind, args, overrides
 # ---- 6. step-level properties ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("guarded", [False, True])
 def test_grouped_step_never_waits_for_the_device(guarded):
-    model = group_model(3).to(DEV)
+    model = to_device(group_model(3), DEV)
     kw = dict(max_grad_norm=1.0, skip_nonfinite=True) if guarded else {}
     opt = _shared(model, CASES[1][2], "ADAM", weight_decay=0.01, **kw)
     tiles = opt._tiles.clone()
@@ -324,7 +330,7 @@ def test_groups_over_a_shared_buffer_train_the_same_under_graph_step():
             return ""
 
     def train(graph):
-        model = copy.deepcopy(base).to(DEV).train()
+        model = to_device(copy.deepcopy(base), DEV).train()
         grads = FlatGradients(model.parameters())
         opt = FlatOptimizer(groups_from_rules(model, rules), "SGD", 0.01, momentum=0.9, weight_decay=1e-4, grads=grads)
         assert len(opt.param_groups) == 3 and len(set(opt._group_of[:8])) > 1           # interleaved in the model's order
@@ -341,5 +347,5 @@ def test_groups_over_a_shared_buffer_train_the_same_under_graph_step():
     graph, keep_g = train(True)
     assert_same_training(graph, eager, keep_g, keep_e)
     # (biases in front of a train-mode BatchNorm have a zero gradient and, in their group, no decay: they stay)
-    moved = [float((a - b.to(DEV)).abs().max()) > 0 for a, b in zip(eager.parameters(), base.parameters())]
+    moved = [float((a - to_device(b, DEV)).abs().max()) > 0 for a, b in zip(eager.parameters(), base.parameters())]
     assert sum(moved) > len(moved) // 2 and moved[-2]

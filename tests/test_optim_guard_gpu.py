@@ -12,7 +12,11 @@ import torch
 from fusion_gcn_amd import _lib
 from test_optim import CASES, TORCH, small_model
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 DEV = torch.device("cuda:0")
 
 
@@ -48,7 +52,7 @@ def _raw_norm(lib, g, max_norm=1.0, grad_scale=1.0):
     guard = torch.zeros(_lib.GUARD_WORDS, dtype=torch.int64, device=DEV)
     sched = torch.zeros(2 * _lib.OPT_MAX_GROUPS, dtype=torch.float64, device=DEV)
     rows = torch.arange(0, n // 4, _lib.OPT_TILE4, dtype=torch.int32)
-    table = torch.stack([rows, (n // 4 - rows).clamp(max=_lib.OPT_TILE4), torch.zeros_like(rows)], dim=1).contiguous().to(DEV)
+    table = guarded.to(torch.stack([rows, (n // 4 - rows).clamp(max=_lib.OPT_TILE4), torch.zeros_like(rows)], dim=1).contiguous(), DEV)
     group = (_lib.OptimGroup * 1)(_lib.OptimGroup(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0))
     rc = lib.fgcn_optim_step(p.data_ptr(), g.data_ptr(), None, None, n, 0, group, 1, table.data_ptr(), table.shape[0], grad_scale, 0,
                              _lib.OptimGuard(max_norm, 1, tiles, partials.data_ptr(), guard.data_ptr(), sched.data_ptr()),
@@ -68,7 +72,7 @@ def test_norm_against_float64(which):
     g_cpu = (torch.randn(n, generator=gen).double() * torch.pow(torch.tensor(10.0, dtype=torch.float64), expo)).float()
     assert bool(torch.isfinite(g_cpu).all())
     want = float(g_cpu.double().pow(2).sum().sqrt())
-    g = g_cpu.to(DEV)
+    g = guarded.to(g_cpu, DEV)
     guard, partials = _raw_norm(lib, g)
     got = float(guard.view(torch.float64)[_lib.GUARD_NORM])
     err = abs(got - want) / want
@@ -119,7 +123,7 @@ def _rel(po, pr):
 def test_clipped_update_matches_clip_grad_norm_and_torch_optim(name, args):
     from fusion_gcn_amd.optim import FlatOptimizer
     ref_model = small_model(3)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = guarded.to(copy.deepcopy(ref_model), DEV)
     g = torch.Generator().manual_seed(7)
     steps = [[torch.randn(p.shape, generator=g) * (1.0 + it) for p in ref_model.parameters()] for it in range(6)]
     norms = [math.sqrt(sum(float(t.double().pow(2).sum()) for t in grads)) for grads in steps]
@@ -135,7 +139,7 @@ def test_clipped_update_matches_clip_grad_norm_and_torch_optim(name, args):
         opt.zero_grad()
         for pr, po, grad in zip(ref_model.parameters(), model.parameters(), grads):
             pr.grad = grad.clone()
-            po.grad = grad.to(DEV)
+            po.grad = guarded.to(grad, DEV)
         torch.nn.utils.clip_grad_norm_(list(ref_model.parameters()), max_norm)
         ref.step()
         opt.step()
@@ -163,7 +167,7 @@ def _good_step(ref, opt, ref_model, model, gen, max_norm):
     for pr, po in zip(ref_model.parameters(), model.parameters()):
         grad = torch.randn(pr.shape, generator=gen)
         pr.grad = grad.clone()
-        po.grad = grad.to(DEV)
+        po.grad = guarded.to(grad, DEV)
     if max_norm is not None:
         torch.nn.utils.clip_grad_norm_(list(ref_model.parameters()), max_norm)
     ref.step()
@@ -177,7 +181,7 @@ def _bad_step(opt, model, gen, bad):
         grad = torch.randn(po.shape, generator=gen)
         if i == len(params) - 2:
             grad.view(-1)[-1] = bad
-        po.grad = grad.to(DEV)
+        po.grad = guarded.to(grad, DEV)
     before = [t.clone() if t is not None else None for t in (opt.flat, opt.state1, opt.state2)]
     opt.step()
     for now, was in zip((opt.flat, opt.state1, opt.state2), before):
@@ -192,7 +196,7 @@ def _bad_step(opt, model, gen, bad):
 def test_nonfinite_step_is_skipped_bit_for_bit(name, args, max_norm, bad):
     from fusion_gcn_amd.optim import FlatOptimizer
     ref_model = small_model(3)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = guarded.to(copy.deepcopy(ref_model), DEV)
     ref = TORCH[name](ref_model.parameters(), 0.05, **args)
     opt = FlatOptimizer(model.parameters(), name, 0.05, max_grad_norm=max_norm, skip_nonfinite=True, **args)
     gen, gen_bad = torch.Generator().manual_seed(7), torch.Generator().manual_seed(8)
@@ -217,7 +221,7 @@ def test_skipped_first_step_leaves_the_momentum_buffer_uninitialised(max_norm):
     from fusion_gcn_amd.optim import FlatOptimizer
     args = dict(momentum=0.8, dampening=0.1)
     ref_model = small_model(3)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = guarded.to(copy.deepcopy(ref_model), DEV)
     ref = torch.optim.SGD(ref_model.parameters(), 0.05, **args)
     opt = FlatOptimizer(model.parameters(), "SGD", 0.05, max_grad_norm=max_norm, skip_nonfinite=True, **args)
     _bad_step(opt, model, torch.Generator().manual_seed(8), float("nan"))
@@ -233,7 +237,7 @@ def test_skipped_first_step_leaves_the_momentum_buffer_uninitialised(max_norm):
 def test_nonfinite_norm_without_skip_propagates_like_torch():
     """max_grad_norm set, skip_nonfinite off: clip_grad_norm_(error_if_nonfinite=False) -- the coefficient is NaN and propagates."""
     from fusion_gcn_amd.optim import FlatOptimizer
-    model = small_model(3).to(DEV)
+    model = guarded.to(small_model(3), DEV)
     opt = FlatOptimizer(model.parameters(), "ADAM", 0.05, max_grad_norm=1.0)
     for i, po in enumerate(model.parameters()):
         po.grad = torch.ones_like(po)
@@ -248,13 +252,13 @@ def test_nonfinite_norm_without_skip_propagates_like_torch():
 # ---- 4. grad_scale ---------------------------------------------------------------------------------------------------------------------
 def test_grad_scale_is_the_data_parallel_average_under_the_clip():
     from fusion_gcn_amd.optim import FlatOptimizer
-    a, b = small_model(5).to(DEV), small_model(5).to(DEV)
+    a, b = guarded.to(small_model(5), DEV), guarded.to(small_model(5), DEV)
     oa = FlatOptimizer(a.parameters(), "ADAM", 0.01, weight_decay=0.01, max_grad_norm=0.5)
     ob = FlatOptimizer(b.parameters(), "ADAM", 0.01, weight_decay=0.01, max_grad_norm=0.5)
     ob.grad_scale = 0.25
     g = torch.Generator().manual_seed(1)
     for pa, pb in zip(a.parameters(), b.parameters()):
-        grad = torch.randn(pa.shape, generator=g).to(DEV)
+        grad = guarded.to(torch.randn(pa.shape, generator=g), DEV)
         pa.grad, pb.grad = grad.clone(), grad * 4.0
     oa.step(), ob.step()
     assert oa.clipped_steps == 1 and ob.clipped_steps == 1
@@ -267,7 +271,7 @@ def test_grad_scale_is_the_data_parallel_average_under_the_clip():
 # ---- 5. no device wait -----------------------------------------------------------------------------------------------------------------
 def test_guarded_step_never_waits_for_the_device():
     from fusion_gcn_amd.optim import FlatOptimizer
-    model = small_model(3).to(DEV)
+    model = guarded.to(small_model(3), DEV)
     opt = FlatOptimizer(model.parameters(), "ADAM", 0.05, max_grad_norm=1.0, skip_nonfinite=True)
     for po in model.parameters():
         po.grad = torch.ones_like(po)
@@ -302,7 +306,7 @@ def test_guarded_step_never_waits_for_the_device():
 def test_checkpoint_counts_applied_steps_only():
     from fusion_gcn_amd.optim import FlatOptimizer
     ref_model = small_model(3)
-    model = copy.deepcopy(ref_model).to(DEV)
+    model = guarded.to(copy.deepcopy(ref_model), DEV)
     ref = torch.optim.Adam(ref_model.parameters(), 0.05, weight_decay=0.01)
     opt = FlatOptimizer(model.parameters(), "ADAM", 0.05, weight_decay=0.01, skip_nonfinite=True)
     gen = torch.Generator().manual_seed(7)
@@ -317,7 +321,7 @@ def test_checkpoint_counts_applied_steps_only():
     assert all(float(e["step"]) == 3.0 for e in other.state_dict()["state"].values())
     assert torch.allclose(other.state_dict()["state"][0]["exp_avg"], ref.state_dict()["state"][0]["exp_avg"], rtol=1e-5, atol=1e-8)
     # torch's state into a guarded optimizer: the device counter is set and the next update uses it
-    model2 = copy.deepcopy(ref_model).to(DEV)
+    model2 = guarded.to(copy.deepcopy(ref_model), DEV)
     opt2 = FlatOptimizer(model2.parameters(), "ADAM", 0.05, weight_decay=0.01, skip_nonfinite=True)
     opt2.load_state_dict(ref.state_dict())
     assert int(opt2._guard[_lib.GUARD_STEP]) == 3 and opt2.steps == 3
@@ -349,7 +353,7 @@ def test_overflowing_batch_through_the_session(session_case, skip):
     from fusion_gcn_amd.session.procedures import DefaultBatchProcessor, DefaultStep
     from fusion_gcn_amd.session.session import Session
     base, data = session_case
-    model = copy.deepcopy(base).to(DEV)
+    model = guarded.to(copy.deepcopy(base), DEV)
     opt = create_optimizer("ADAM", model, 1e-3, weight_decay=0.01, skip_nonfinite=skip)
     calls = []
 

@@ -8,7 +8,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 
 VARIANTS = [("first", 3, 64, 1, "none", True), ("identity64", 64, 64, 1, "identity", False), ("down_s2", 64, 128, 2, "conv", True),
             ("identity256", 256, 256, 1, "identity", False), ("down_s2_256", 128, 256, 2, "conv", True)]
@@ -29,7 +33,7 @@ def _params(cfg, seed):
             shape = (cfg.cout, cfg.cout, 9, 1) if n.endswith("weight") else (cfg.cout,)
         else:                                      # conv_d, down.0, residual.conv
             shape = (cfg.cout, cfg.cin, 1, 1) if n.endswith("weight") else (cfg.cout,)
-        P[n] = torch.randn(shape, generator=g).cuda()
+        P[n] = guarded.to(torch.randn(shape, generator=g), "cuda")
     return P
 
 
@@ -125,8 +129,8 @@ def test_model_refreshes_all_blocks_in_one_launch_and_tracks_parameter_versions(
     shape = (2, 1, 16, 20, 3)
     model = Model(shape[1:], 27, Graph(utd.skeleton_edges, center_joint=utd.center_joint))
     filler.fill_state_dict(model.state_dict())
-    model = model.to(dev).eval()
-    x = torch.from_numpy(filler.skeleton_input("x.pack", shape)).float().to(dev)
+    model = guarded.to(model, dev).eval()
+    x = guarded.to(torch.from_numpy(filler.skeleton_input("x.pack", shape)).float(), dev)
     with torch.no_grad():
         a = model(x).clone()
         assert getattr(model, "_pack_plan", None) is None       # first forward: the blocks built their forms lazily
@@ -143,7 +147,7 @@ def test_model_refreshes_all_blocks_in_one_launch_and_tracks_parameter_versions(
         d = model(x).clone()
         assert torch.equal(c, d) and model._pack_plan[1] is plan
     # the same weights through freshly built forms give the same logits
-    fresh = Model(shape[1:], 27, Graph(utd.skeleton_edges, center_joint=utd.center_joint)).to(dev).eval()
+    fresh = guarded.to(Model(shape[1:], 27, Graph(utd.skeleton_edges, center_joint=utd.center_joint)), dev).eval()
     fresh.load_state_dict(model.state_dict())
     with torch.no_grad():
         assert torch.equal(fresh(x), c)

@@ -21,7 +21,11 @@ from fusion_gcn_amd.util import Graph
 from oracle import agcn_oracle as O
 from oracle import relu_masks as RM
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 
 FWD_TOL, RED_TOL = 3e-6, 2e-5          # tests/test_kernels_gpu.py
 DEV = "cuda:0"
@@ -62,7 +66,7 @@ def _ref_stats(z):
 
 
 def _dev(t):
-    return None if t is None else t.float().to(DEV).contiguous()
+    return None if t is None else guarded.put(t.float(), device=DEV)
 
 
 MATH = ["f32", "bf16x3", "f16x2", "bf16"]
@@ -186,7 +190,7 @@ def _oracle(model, x, y, train=True):
 
 
 def _to_dev(x):
-    return {k: v.to(DEV) for k, v in x.items()} if "skeleton" in x else x["rgb"].to(DEV)
+    return {k: guarded.to(v, DEV) for k, v in x.items()} if "skeleton" in x else guarded.to(x["rgb"], DEV)
 
 
 # the patch-only modes have no reducer and no skeleton: data_bn is their input stage on either setting of patch_input_fused
@@ -210,10 +214,10 @@ def test_identity_reducer_mode_matches_the_float64_composition(mode):
 def _parity(mode, fused, math_mode, model):
     x, y = _inputs(mode)
     ora = _oracle(model, x, y)
-    model = model.to(DEV).train()
+    model = guarded.to(model, DEV).train()
     with ops.context(math_mode) as ctx:
         ctx.paths.patch_input_fused = fused
-        rep = RM.gradient_parity_report(model, _to_dev(x), y.to(DEV), oracle=ora)
+        rep = RM.gradient_parity_report(model, _to_dev(x), guarded.to(y, DEV), oracle=ora)
     print(f"[{mode} fused={fused} {math_mode}] logits {rep['logits_err']:.2e} | flips {rep['flips']} of {rep['decisions']} | "
           f"grad {rep['err_plain']:.2e} / {rep['err_injected']:.2e}")
     assert rep["logits_err"] < 1e-5 and rep["loss_err"] < 1e-5, rep
@@ -240,7 +244,7 @@ def test_eval_mode_uses_running_statistics(mode):
     else:
         z = x["rgb"].double()
     want = O.model_forward(z, agcn_sd, train=False)
-    model = model.to(DEV).eval()
+    model = guarded.to(model, DEV).eval()
     with torch.no_grad():
         got = model(_to_dev(x))
     assert rel_l2(got.cpu().numpy(), want.numpy()) < 1e-5
@@ -252,7 +256,7 @@ def test_fused_and_composed_input_stage_agree(mode, train):
     """paths.patch_input_fused on and off: the same network input, running statistics and reducer gradients (the A/B routes).
     Compared at the input stage itself: past it, the blocks' ReLU decisions turn float32 rounding differences into flips."""
     from fusion_gcn_amd.block import patch_input
-    base = _model(mode).to(DEV).train(train)
+    base = guarded.to(_model(mode), DEV).train(train)
     x, _ = _inputs(mode)
     xd = _to_dev(x)
     gen = torch.Generator().manual_seed(2)
@@ -263,7 +267,7 @@ def test_fused_and_composed_input_stage_agree(mode, train):
             ctx.paths.patch_input_fused = fused
             h = patch_input(xd["skeleton"], xd["rgb"], model.patch_feature_dim_reducer, model.agcn.data_bn, model.num_joints,
                             model.fusion_type)
-            g = torch.randn(h.shape, generator=gen).to(DEV) if not out else out[True][3]
+            g = guarded.to(torch.randn(h.shape, generator=gen), DEV) if not out else out[True][3]
             (h * g).sum().backward()
         bn = model.agcn.data_bn
         out[fused] = (h.detach().cpu(), [p.grad.cpu() for p in model.patch_feature_dim_reducer.parameters()],
@@ -279,9 +283,9 @@ def test_fused_and_composed_input_stage_agree(mode, train):
 def test_graph_step_replays_the_eager_step_and_adam_updates(mode):
     from fusion_gcn_amd.optim import FlatOptimizer
     from fusion_gcn_amd.session.procedures import GraphStep
-    model = _model(mode).to(DEV).train()
+    model = guarded.to(_model(mode), DEV).train()
     x, y = _inputs(mode)
-    xd, yd = _to_dev(x), y.to(DEV)
+    xd, yd = _to_dev(x), guarded.to(y, DEV)
     eager = copy.deepcopy(model)
     step = GraphStep(verify=True)
     opt = FlatOptimizer(model.parameters(), "ADAM", 1e-3, weight_decay=0.01, grads=None)
@@ -314,14 +318,14 @@ def test_clip_batches_feed_skeleton_rgb_early_fusion(tmp_path):
                 w.collect_next(s)
     np.save(os.path.join(tmp_path, "train_labels.npy"), rng.integers(0, CLASSES, n))
     ds = MultiModalDataset([(str(tmp_path), NumpyDatasetLoader())], "train")
-    model = _model("skeleton_rgb_patch_features_early_fusion").to(DEV).train()
+    model = guarded.to(_model("skeleton_rgb_patch_features_early_fusion"), DEV).train()
     seen = 0
     for feats, labels, idx in ClipBatches(ds, 3, device=DEV):
         assert set(feats) == {"skeleton", "rgb"}
         loss = F.cross_entropy(model(feats), labels)
         loss.backward()
         assert torch.isfinite(loss)
-        direct = {k: torch.from_numpy(arrays[k][idx.cpu().numpy()]).to(DEV) for k in arrays}
+        direct = {k: guarded.to(torch.from_numpy(arrays[k][idx.cpu().numpy()]), DEV) for k in arrays}
         assert torch.equal(feats["rgb"], direct["rgb"]) and torch.equal(feats["skeleton"], direct["skeleton"])
         seen += labels.numel()
     assert seen == n

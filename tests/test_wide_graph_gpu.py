@@ -12,7 +12,11 @@ from conftest import rel_l2
 from oracle import agcn_oracle as O
 from oracle import filler, graph_oracle
 
-pytestmark = pytest.mark.gpu
+import guarded
+from guarded import guarded_allocations  # noqa: F401  (the fixture)
+
+# every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
 ALL_MODES = ["f32", "bf16x3", "f16x2", "bf16"]
 
 
@@ -57,12 +61,12 @@ def test_joint_mix_wide(V, T, B):
         return out
     for acc in (False, True):
         out0 = rnd(B, T, V, C_out, seed=7) if acc else torch.zeros(B, T, V, C_out, dtype=torch.float64)
-        out = out0.float().to(dev())
-        ops.joint_mix_wide(x.float().to(dev()), out, mats.float().to(dev()), spec, accumulate=acc)
+        out = guarded.to(out0.float(), dev())
+        ops.joint_mix_wide(guarded.to(x.float(), dev()), out, guarded.to(mats.float(), dev()), spec, accumulate=acc)
         assert rel_l2(out.cpu().numpy(), want(out0).numpy()) < 2e-6, acc
     # one shared set of matrices (static adjacency)
     out = torch.zeros(B, T, V, C_out, device=dev())
-    ops.joint_mix_wide(x.float().to(dev()), out, mats[:1].float().to(dev()), spec[:1])
+    ops.joint_mix_wide(guarded.to(x.float(), dev()), out, guarded.to(mats[:1].float(), dev()), spec[:1])
     ref = torch.einsum("vu,btvc->btuc", mats[0, 0], x[..., :32])
     assert rel_l2(out[..., :32].cpu().numpy(), ref.numpy()) < 2e-6
     assert float(out[..., 32:].abs().max()) == 0.0
@@ -74,7 +78,7 @@ def test_joint_gram_and_column_softmax_wide(V, T, B, ic):
     from fusion_gcn_amd import ops
     emb = rnd(B, T, V, 6 * ic, seed=V + ic)
     items = [(2 * k * ic, (2 * k + 1) * ic, ic) for k in range(3)]
-    part = ops.joint_gram(emb.float().to(dev()), emb.float().to(dev()), items)
+    part = ops.joint_gram(guarded.to(emb.float(), dev()), guarded.to(emb.float(), dev()), items)
     assert tuple(part.shape[2:]) == (3, 64, 64)
     S = torch.stack([torch.einsum("btvc,btwc->bvw", emb[..., a:a + w], emb[..., b:b + w]) for a, b, w in items], 1)
     got = part.double().sum(1).cpu()
@@ -83,15 +87,15 @@ def test_joint_gram_and_column_softmax_wide(V, T, B, ic):
         assert float(got[..., V:, :].abs().max()) == 0.0 and float(got[..., :, V:].abs().max()) == 0.0
     adj_a, adj_b = rnd(3, V, V, seed=1), rnd(3, V, V, seed=2)
     scale = 1.0 / (ic * T)
-    c, a_hat = ops.adj_softmax_fwd(part, scale, adj_a.float().to(dev()), B, adj_b=adj_b.float().to(dev()))
+    c, a_hat = ops.adj_softmax_fwd(part, scale, guarded.to(adj_a.float(), dev()), B, adj_b=guarded.to(adj_b.float(), dev()))
     C = torch.softmax(S * scale, dim=-2)
     assert rel_l2(c.cpu().numpy(), C.numpy()) < 2e-6
     assert rel_l2(a_hat.cpu().numpy(), (C + adj_a + adj_b).numpy()) < 2e-6
-    _, a_static = ops.adj_softmax_fwd(None, 1.0, adj_a.float().to(dev()), 1, use_softmax=False, adj_b=adj_b.float().to(dev()))
+    _, a_static = ops.adj_softmax_fwd(None, 1.0, guarded.to(adj_a.float(), dev()), 1, use_softmax=False, adj_b=guarded.to(adj_b.float(), dev()))
     assert rel_l2(a_static.cpu().numpy(), (adj_a + adj_b)[None].numpy()) < 1e-7
     # backward: the gram of x against dagg gives dA^; dS = scale C (dC - colsum(C dC))
     x, dagg = rnd(B, T, V, 8, seed=3), rnd(B, T, V, 24, seed=4)
-    part_b = ops.joint_gram(x.float().to(dev()), dagg.float().to(dev()), [(0, 8 * k, 8) for k in range(3)])
+    part_b = ops.joint_gram(guarded.to(x.float(), dev()), guarded.to(dagg.float(), dev()), [(0, 8 * k, 8) for k in range(3)])
     d_a_hat, d_s = ops.adj_softmax_bwd(part_b, scale, c, V)
     dC = torch.stack([torch.einsum("btvc,btwc->bvw", x, dagg[..., 8 * k:8 * k + 8]) for k in range(3)], 1)
     Cg = c.double().cpu()
@@ -110,27 +114,27 @@ def test_row_kernels_do_not_depend_on_the_joint_count(V, T, B, K, N, kt, s):
     Tp = (T - 1) // s + 1
     pad = (kt - 1) // 2
     ref = F.conv2d(x.permute(0, 3, 1, 2), w, stride=(s, 1), padding=(pad, 0)).permute(0, 2, 3, 1)
-    wk = w[..., 0].permute(2, 1, 0).contiguous().float().to(dev())            # (taps, K, N)
+    wk = guarded.to(w[..., 0].permute(2, 1, 0).contiguous().float(), dev())            # (taps, K, N)
     u = torch.empty(B, Tp, V, N, device=dev())
-    ops.rows_gemm(x.float().to(dev()), wk, u, K=K, N=N, tmap=ops.conv_tmap(kt, s))
+    ops.rows_gemm(guarded.to(x.float(), dev()), wk, u, K=K, N=N, tmap=ops.conv_tmap(kt, s))
     assert rel_l2(u.cpu().numpy(), ref.numpy()) < 2e-6
     du = rnd(B, Tp, V, N, seed=13)
     xr = x.clone().requires_grad_(True)
     wr = w.clone().requires_grad_(True)
     (F.conv2d(xr.permute(0, 3, 1, 2), wr, stride=(s, 1), padding=(pad, 0)).permute(0, 2, 3, 1) * du).sum().backward()
     dg = torch.empty(B, T, V, K, device=dev())
-    ops.rows_gemm(du.float().to(dev()), w[..., 0].permute(2, 0, 1).contiguous().float().to(dev()), dg, K=N, N=K,
+    ops.rows_gemm(guarded.to(du.float(), dev()), guarded.to(w[..., 0].permute(2, 0, 1).contiguous().float(), dev()), dg, K=N, N=K,
                   tmap=ops.conv_dgrad_tmap(kt, s))
     assert rel_l2(dg.cpu().numpy(), xr.grad.numpy()) < 2e-6
-    gw = ops.tconv_wgrad(x.float().to(dev()), du.float().to(dev()), taps=kt, stride=s, all_taps=False, conv_param=(1, K))
+    gw = ops.tconv_wgrad(guarded.to(x.float(), dev()), guarded.to(du.float(), dev()), taps=kt, stride=s, all_taps=False, conv_param=(1, K))
     assert rel_l2(gw.cpu().numpy(), wr.grad.numpy()) < 2e-6
     # BatchNorm (statistics, finalize) + identity shortcut + ReLU over V joints per frame
     a, r = rnd(B, Tp, V, N, seed=14), rnd(B, Tp, V, N, seed=15)
     part = torch.empty(B, Tp, V, N, device=dev())
-    stats = ops.rows_gemm(a.float().to(dev()), torch.eye(N, device=dev())[None].contiguous(), part, K=N, N=N, stats=True)
-    gamma, beta = rnd(N, seed=16).float().to(dev()), rnd(N, seed=17).float().to(dev())
+    stats = ops.rows_gemm(guarded.to(a.float(), dev()), torch.eye(N, device=dev())[None].contiguous(), part, K=N, N=N, stats=True)
+    gamma, beta = guarded.to(rnd(N, seed=16).float(), dev()), guarded.to(rnd(N, seed=17).float(), dev())
     vec = ops.bn_finalize(stats, B * Tp * V, gamma, beta)
-    o, _ = ops.bn_act(part, vec, r.float().to(dev()), None, relu=True, sign_mask=True)
+    o, _ = ops.bn_act(part, vec, guarded.to(r.float(), dev()), None, relu=True, sign_mask=True)
     mean, var = a.mean((0, 1, 2)), a.var((0, 1, 2), unbiased=False)
     want = torch.relu((a - mean) / torch.sqrt(var + 1e-5) * gamma.double().cpu() + beta.double().cpu() + r)
     assert rel_l2(o.cpu().numpy(), want.numpy()) < 2e-5
@@ -159,10 +163,10 @@ def _block_case(name, cin, cout, stride, residual, V, T, static, adj, B=2, seed_
     out_o, adj_c = O.st_block(xo, live, "l0", stride, residual, True, stats, static_adjacency=static)
     grads_o = torch.autograd.grad((out_o * probe).sum(), [xo] + list(params.values()), allow_unused=True)
     want = {k[3:]: g.numpy() for k, g in zip(params.keys(), grads_o[1:]) if g is not None}
-    blk = blk.to(dev()).train()
-    xg = x.float().to(dev()).requires_grad_(True)
+    blk = guarded.to(blk, dev()).train()
+    xg = guarded.to(x.float(), dev()).requires_grad_(True)
     out_g = blk.forward_nchw(xg)
-    (out_g * probe.float().to(dev())).sum().backward()
+    (out_g * guarded.to(probe.float(), dev())).sum().backward()
     got = {n: p.grad.detach().cpu().numpy() for n, p in blk.named_parameters()}
     return blk, x, sd, stats, out_o, adj_c, grads_o[0], want, out_g, xg.grad, got
 
@@ -212,7 +216,7 @@ def test_wide_block_vs_oracle(fgcn_math, case):
     blk.eval()
     sd_eval = {"l0." + k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu().clone()) for k, v in blk.state_dict().items()}
     with torch.no_grad():
-        out_e = blk.forward_nchw(x.float().to(dev()))
+        out_e = blk.forward_nchw(guarded.to(x.float(), dev()))
     want_e, _ = O.st_block(x, sd_eval, "l0", stride, residual, False, static_adjacency=static)
     assert rel_l2(out_e.cpu().numpy(), want_e.numpy()) < (1e-2 if fgcn_math == "bf16" else 2e-5)
     print(f"[{fgcn_math} {name} V={V}] fwd {fwd:.2e} flips {flips}")
@@ -254,8 +258,8 @@ def test_two_person_model_vs_oracle():
     sd64 = {k: (v.detach().double() if v.is_floating_point() else v.detach().clone()) for k, v in model.state_dict().items()}
     names = [n for n, _ in model.named_parameters()]
     oracle = RM.oracle_side(x.double(), labels, sd64, names)
-    model = model.to(dev()).train()
-    rep = RM.gradient_parity_report(model, x.float().to(dev()), labels.to(dev()), oracle=oracle)
+    model = guarded.to(model, dev()).train()
+    rep = RM.gradient_parity_report(model, guarded.to(x.float(), dev()), guarded.to(labels, dev()), oracle=oracle)
     print(f"[wide50] logits {rep['logits_err']:.2e} flips {rep['flips']} of {rep['decisions']} grad {rep['err_plain']:.2e} / "
           f"{rep['err_injected']:.2e}")
     assert rep["logits_err"] < 1e-5 and rep["loss_err"] < 1e-5, rep
@@ -269,9 +273,9 @@ def test_two_person_model_graph_replay():
     import torch.nn.functional as F
     from fusion_gcn_amd.session.procedures import GraphStep
     model, x, labels = _two_person_model()
-    model = model.to(dev()).train()
+    model = guarded.to(model, dev()).train()
     eager = copy.deepcopy(model)
-    xd, yd = x.float().to(dev()), labels.to(dev())
+    xd, yd = guarded.to(x.float(), dev()), guarded.to(labels, dev())
     step = GraphStep(verify=True)
     grads, losses = [], []
     for _ in range(3):
@@ -295,6 +299,6 @@ def test_two_person_model_graph_replay():
 def test_more_than_64_joints_fail_at_the_first_forward(static):
     from fusion_gcn_amd import _lib
     from fusion_gcn_amd.models.mmargcn.agcn import SpatialTemporalConv
-    blk = SpatialTemporalConv(64, 64, tree_adjacency(65, 0), static_adjacency=static).to(dev()).train()    # builds
+    blk = guarded.to(SpatialTemporalConv(64, 64, tree_adjacency(65, 0), static_adjacency=static), dev()).train()    # builds
     with pytest.raises(_lib.FgcnError, match="64"):
         blk.forward_nchw(torch.randn(1, 64, 4, 65, device=dev()))
