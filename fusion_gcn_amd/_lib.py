@@ -206,6 +206,9 @@ SIGNATURES = {
     "fgcn_clip_augment": (_I, [_P] * 6 + [_I] * 7 + [C.POINTER(C.c_float), _F, _F, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "fgcn_augment_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, C.POINTER(C.c_float), _F, _F, C.POINTER(C.c_float)]),
     "fgcn_clip_normalize": (_I, [_P] * 5 + [_I] * 10 + [_P]),
+    "fgcn_resample_index": (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
+    "fgcn_signal_prepare": (_I, [_P] * 6 + [_I] * 5 + [_P]),
+    "fgcn_imu_enhance": (_I, [_P] * 7 + [_I] * 7 + [_P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

@@ -28,6 +28,11 @@ Normalisation (reference: util/preprocessing/skeleton.py:normalize_skeleton, an 
 normalize=Normalize(...))`` takes RAW skeleton clips -- null frames padded, the centre joint of the first body at the origin, spine to z,
 shoulders to x -- with ``fgcn_clip_normalize``: once at upload on the resident path, per batch behind the copy on the streaming path, and
 before the augmentation where both are given: DESIGN.md section 8g.
+
+Inertial recordings (reference: SkeletonProcessor("imu_enhanced") and InertialProcessor, util/preprocessing/processor): ``ClipBatches(...,
+inertial=Inertial(frames=...))`` takes the RAW accelerometer / gyroscope recording -- resampled to the skeleton's frame count, zero-padded
+and min-max normalised (``fgcn_signal_prepare``), and with ``enhance=True`` appended as extra joints behind the normalised skeleton
+(``fgcn_imu_enhance``) -- after the normalisation and before the augmentation: DESIGN.md section 8h.
 """
 from __future__ import annotations
 
@@ -251,6 +256,71 @@ class Normalize:
             raise FgcnError(f"normalize: feature {feature_id!r} has {V} joints; the joint numbers {self.origin_joint}, {pairs} need more")
 
 
+class Inertial:
+    """What ``ClipBatches(inertial=...)`` does to every raw inertial recording (include/fgcn.h): the reference's
+    offline preprocessing of the ``inertial`` and ``skeleton_imu_enhanced`` features.
+
+    ``frames``: feature id -> the number of recorded frames of each sample, for the two features ``main`` (the skeleton, (samples, M, T,
+    V, C), whose count Ls is the length the recording is resampled to) and ``signal`` (the recording, (samples, L, S), Li frames of it
+    valid).  ``features[signal]`` becomes the (T, S) signal -- resampled by nearest neighbour, zero from frame Ls on, min-max normalised
+    over the padded array unless ``minmax=False`` (a constant recording gives 0 / 0 = NaN, as in the reference) -- or is left out of
+    the batch with ``drop_signal=True``.  ``enhance=True``: ``features[main]`` becomes (M, T, V + S / 3, 3), the skeleton with the
+    resampled, padded recording (not min-max normalised) appended as S / 3 joints of every body."""
+
+    def __init__(self, frames: Mapping[str, Sequence[int]], main: str = "skeleton", signal: str = "inertial", enhance: bool = False,
+                 minmax: bool = True, drop_signal: bool = False):
+        self.main, self.signal = str(main), str(signal)
+        self.enhance, self.minmax, self.drop_signal = bool(enhance), bool(minmax), bool(drop_signal)
+        if self.main == self.signal:
+            raise ValueError(f"main and signal are both {main!r}")
+        if set(frames) != {self.main, self.signal}:
+            raise ValueError(f"frames: expected the frame counts of {self.main!r} and {self.signal!r}, got {sorted(frames)}")
+        if not self.enhance and self.drop_signal:
+            raise ValueError("enhance=False with drop_signal=True leaves nothing to prepare")
+        self.frames = {}
+        for k in (self.main, self.signal):
+            v = np.asarray(frames[k])
+            if v.ndim != 1 or v.dtype.kind not in "iu" or (len(v) and v.min() < 1):
+                raise ValueError(f"frames[{k!r}]: expected one integer frame count >= 1 per sample")
+            self.frames[k] = v.astype(np.int32)
+        ls, li = self.frames[self.main], self.frames[self.signal]
+        if ls.shape != li.shape:
+            raise ValueError(f"frames: {len(ls)} counts for {self.main!r}, {len(li)} for {self.signal!r}")
+        bad = np.flatnonzero((ls == 1) & (li != 1))
+        if len(bad):                                        # the reference divides by Ls - 1
+            raise ValueError(f"frames: sample {int(bad[0])} has one {self.main} frame and {int(li[bad[0]])} {self.signal} frames: a "
+                             f"recording cannot be resampled to a single frame")
+
+    def check_shapes(self, shapes: Mapping[str, Sequence[int]], n: int) -> None:
+        """Refuses arrays (feature id -> shape with the sample axis) this preparation cannot take -- at construction, not mid-epoch."""
+        unknown = {self.main, self.signal} - set(shapes)
+        if unknown:
+            raise ValueError(f"inertial names features the data set does not have: {sorted(unknown)}")
+        main, sig = tuple(shapes[self.main]), tuple(shapes[self.signal])
+        if len(main) != 5 or len(sig) != 3:
+            raise FgcnError(f"inertial: expected {self.main!r} (samples, M, T, V, C) and {self.signal!r} (samples, L, S), got {main} and {sig}")
+        for k, limit, what in ((self.main, main[2], "T"), (self.signal, sig[1], "L")):
+            v = self.frames[k]
+            if v.shape != (n,) or v.max() > limit:
+                raise ValueError(f"frames[{k!r}]: expected {n} frame counts in [1, {limit}] ({what} of {k!r})")
+        if self.enhance and (sig[2] % 3 or main[4] not in (2, 3)):
+            raise FgcnError(f"inertial: enhance appends joints of three values to a skeleton of 2 or 3 coordinates; {self.signal!r} has "
+                            f"{sig[2]} values per frame, {self.main!r} {main[4]} coordinates")
+
+    def sample_shapes(self, shapes: Mapping[str, Sequence[int]]) -> Dict[str, tuple]:
+        """feature id -> the shape of a sample as the batch holds it, in the data set's order (the dropped signal left out)."""
+        out = {k: tuple(v[1:]) for k, v in shapes.items()}
+        M, T, V, _ = out[self.main]
+        S = out[self.signal][1]
+        if self.enhance:
+            out[self.main] = (M, T, V + S // 3, 3)
+        if self.drop_signal:
+            del out[self.signal]
+        else:
+            out[self.signal] = (T, S)
+        return out
+
+
 NORMALIZE_CHUNK = 2048      # clips per fgcn_clip_normalize call when a resident split is normalised at upload
 
 
@@ -266,12 +336,15 @@ class ClipBatches:
     tables of the last batch are kept in ``last_params`` (feature id -> (clips, 12) tensor).  ``normalize``: None = the stored clips are
     taken as they are; a ``Normalize`` = the (samples, M, T, V, C) arrays it names hold RAW skeletons and are normalised on the device
     -- a resident split once, at construction; a streamed batch behind its copy -- before any augmentation; ``last_plan`` (feature id ->
-    (frame_map, params)) keeps the tables of the last call."""
+    (frame_map, params)) keeps the tables of the last call.  ``inertial``: None = every feature as stored; an ``Inertial`` = the
+    signal it names holds RAW recordings, prepared on the device after the normalisation and before the augmentation (which sees the
+    prepared shapes) -- a resident split once, at construction; a streamed batch behind its copy; ``last_inertial`` keeps the
+    (clips, 2) minimum / maximum table of the last call."""
 
     def __init__(self, dataset: MultiModalDataset, batch_size: int, *, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
                  resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None,
-                 normalize: Optional[Normalize] = None):
+                 normalize: Optional[Normalize] = None, inertial: Optional[Inertial] = None):
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
@@ -287,16 +360,26 @@ class ClipBatches:
         self.resident = nbytes <= resident_budget if resident is None else bool(resident)
         self.labels = torch.from_numpy(np.asarray(dataset.labels_data).astype(np.int64))
         on_gpu = self.device.type == "cuda"
+        self.inertial, self.last_inertial = inertial, None
+        self.shapes = {k: tuple(a.shape[1:]) for k, a in self.arrays.items()}      # of a sample, as the batch holds it
+        if inertial is not None:
+            if not on_gpu:
+                raise FgcnError("ClipBatches(inertial=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
+            inertial.check_shapes({k: a.shape for k, a in self.arrays.items()}, n)
+            self.shapes = inertial.sample_shapes({k: a.shape for k, a in self.arrays.items()})
+        self.out_keys = list(self.shapes)
+        # the features the preparation writes: the enhanced skeleton, the prepared signal
+        self.inr_keys = [] if inertial is None else [k for k in self.out_keys if k == inertial.signal or (k == inertial.main and inertial.enhance)]
         self.augment, self.last_params = augment, {}
-        self.aug_keys = [k for k in self.keys if augment is not None and augment.applies_to(k)]
+        self.aug_keys = [k for k in self.out_keys if augment is not None and augment.applies_to(k)]
         if augment is not None:
             if not on_gpu:
                 raise FgcnError("ClipBatches(augment=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
             for k in self.aug_keys:
-                if len(self.arrays[k].shape) not in (3, 5):
-                    raise FgcnError(f"augment: feature {k!r} has shape {self.arrays[k].shape}; expected (samples, M, T, V, C) or "
+                if len(self.shapes[k]) not in (2, 4):
+                    raise FgcnError(f"augment: feature {k!r} has shape {(n, *self.shapes[k])}; expected (samples, M, T, V, C) or "
                                     f"(samples, T, S) -- leave it out with Augment(only=...)")
-                augment.joint_range(self.arrays[k].shape[1:])         # (a joint range the array does not have: refused here, not mid-epoch)
+                augment.joint_range(self.shapes[k])         # (a joint range the array does not have: refused here, not mid-epoch)
             unknown = (set(augment.valid_frames) | set(augment.only or ())) - set(self.keys)
             if unknown:
                 raise ValueError(f"augment names features the data set does not have: {sorted(unknown)}")
@@ -304,7 +387,7 @@ class ClipBatches:
             for k in self.aug_keys:
                 if k in augment.valid_frames:
                     v = np.asarray(augment.valid_frames[k])
-                    T = self.arrays[k].shape[-2] if len(self.arrays[k].shape) == 3 else self.arrays[k].shape[2]
+                    T = self.shapes[k][-2] if len(self.shapes[k]) == 2 else self.shapes[k][1]
                     if v.shape != (n,) or v.min() < 1 or v.max() > T:
                         raise ValueError(f"valid_frames[{k!r}]: expected {n} frame counts in [1, {T}]")
                     self.valid[k] = torch.from_numpy(v.astype(np.int32))
@@ -326,6 +409,15 @@ class ClipBatches:
                 for lo in range(0, n, NORMALIZE_CHUNK):
                     rows = torch.arange(lo, min(lo + NORMALIZE_CHUNK, n), dtype=torch.int64, device=self.device)
                     self._normalize(k, raw, rows, out=self.dev_feat[k][lo:lo + len(rows)])
+            if inertial is not None:                        # the same for the recordings, which read the normalised skeletons
+                raw = self.dev_feat
+                lens = [torch.from_numpy(inertial.frames[k]).to(self.device) for k in (inertial.signal, inertial.main)]
+                done = {k: torch.empty((n, *self.shapes[k]), dtype=torch.float32, device=self.device) for k in self.inr_keys}
+                for lo in range(0, n, NORMALIZE_CHUNK):
+                    rows = torch.arange(lo, min(lo + NORMALIZE_CHUNK, n), dtype=torch.int64, device=self.device)
+                    self._prepare(raw, rows, *lens, out={k: v[lo:lo + len(rows)] for k, v in done.items()})
+                self.dev_feat = {k: done.get(k, raw[k]) for k in self.out_keys}      # (the raw recordings are released)
+                del raw
             self.dev_labels = self.labels.to(self.device)
             if augment is not None:
                 self.dev_valid = {k: v.to(self.device) for k, v in self.valid.items()}
@@ -340,15 +432,25 @@ class ClipBatches:
             self.copy_stream = torch.cuda.Stream(self.device) if on_gpu else None
             self.copied = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
             self.consumed = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
-            if augment is not None or normalize is not None:
+            if augment is not None or normalize is not None or inertial is not None:
                 self.slot_rows = torch.arange(per, dtype=torch.int64, device=self.device)
             if normalize is not None:
                 # per slot: the normalised batch (the uploaded rows are the kernel's source); the slot's `consumed` event covers it
                 self.norm_out = [{k: torch.empty_like(self.dev[s][k]) for k in self.norm_keys} for s in range(2)]
+            if inertial is not None:
+                # per slot: the prepared features, under the same event, and the two frame counts of the slot's rows, staged and copied
+                # with the rows (signal first, as the kernels take them)
+                self.inr_out = [{k: torch.empty((per, *self.shapes[k]), dtype=torch.float32, device=self.device) for k in self.inr_keys}
+                                for _ in range(2)]
+                self.len_keys = (inertial.signal, inertial.main)
+                self.frames = {k: torch.from_numpy(inertial.frames[k]) for k in self.len_keys}
+                self.host_len = [{k: mk((per,), torch.int32) for k in self.len_keys} for _ in range(2)]
+                self.dev_len = [{k: torch.empty((per,), dtype=torch.int32, device=self.device) for k in self.len_keys} for _ in range(2)]
             if augment is not None:
                 # per slot: the augmented batch (what the consumer receives; the uploaded rows are the kernel's source), the clips' ids, and
                 # the valid frames of the slot's rows, staged and copied with the rows
-                self.aug_out = [{k: torch.empty_like(self.dev[s][k]) for k in self.aug_keys} for s in range(2)]
+                self.aug_out = [{k: torch.empty((per, *self.shapes[k]), dtype=torch.float32, device=self.device) for k in self.aug_keys}
+                                for _ in range(2)]
                 self.host_ids = [mk((per,), torch.int64) for _ in range(2)]
                 self.dev_ids = [torch.empty((per,), dtype=torch.int64, device=self.device) for _ in range(2)]
                 self.host_valid = [{k: mk((per,), torch.int32) for k in self.valid} for _ in range(2)]
@@ -402,8 +504,25 @@ class ClipBatches:
         self.last_plan[k] = (frame_map, params)
         return out
 
+    def _prepare(self, feats: Dict[str, torch.Tensor], rows: torch.Tensor, src_len: torch.Tensor, dst_len: torch.Tensor,
+                 out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Rows ``rows`` of the raw recordings (and of the normalised skeletons) in ``feats``, prepared into the buffers ``out``, on the
+        current stream -> the features of the batch; the frame counts are indexed like the rows of ``feats``."""
+        from . import ops
+        z = self.inertial
+        res = {}
+        for k in self.out_keys:
+            if k == z.main and z.enhance:
+                res[k] = ops.imu_enhance(feats[k], rows, feats[z.signal], rows, src_len, dst_len, out=out[k])
+            elif k == z.signal:
+                res[k], self.last_inertial = ops.signal_prepare(feats[k], rows, src_len, dst_len, self.shapes[k][0], minmax=z.minmax,
+                                                                out=out[k])
+            else:
+                res[k] = feats[k]
+        return res
+
     def _out(self, feats: Dict[str, torch.Tensor]) -> Features:
-        return feats[self.keys[0]] if len(self.keys) == 1 else feats
+        return feats[self.out_keys[0]] if len(self.out_keys) == 1 else feats
 
     def __iter__(self) -> Iterator[Tuple[Features, torch.Tensor, torch.Tensor]]:
         if self.resident:
@@ -429,6 +548,9 @@ class ClipBatches:
                 rows = np.asarray(a[order], dtype=np.float32)
                 self.host[slot][k][:m].copy_(torch.from_numpy(rows[back]))
             self.host_lab[slot][:m].copy_(self.labels[idx])
+            if self.inertial is not None:
+                for k in self.len_keys:
+                    self.host_len[slot][k][:m].copy_(self.frames[k][idx])
             if self.augment is not None:
                 self.host_ids[slot][:m].copy_(idx)
                 for k, v in self.valid.items():
@@ -439,6 +561,9 @@ class ClipBatches:
                     for k in self.keys:
                         self.dev[slot][k][:m].copy_(self.host[slot][k][:m], non_blocking=True)
                     self.dev_lab[slot][:m].copy_(self.host_lab[slot][:m], non_blocking=True)
+                    if self.inertial is not None:
+                        for k in self.len_keys:
+                            self.dev_len[slot][k][:m].copy_(self.host_len[slot][k][:m], non_blocking=True)
                     if self.augment is not None:
                         self.dev_ids[slot][:m].copy_(self.host_ids[slot][:m], non_blocking=True)
                         for k in self.valid:
@@ -465,8 +590,12 @@ class ClipBatches:
             for k in self.norm_keys:
                 # on the consumer's stream, behind the copy: the slot's rows are the source, `consumed` below covers kernel and consumer
                 feats[k] = self._normalize(k, self.dev[slot][k][:m], self.slot_rows[:m], out=self.norm_out[slot][k][:m])
+            if self.inertial is not None:
+                # the same for the recordings, which read the normalised skeletons where there are any
+                feats = self._prepare(feats, self.slot_rows[:m], *(self.dev_len[slot][k][:m] for k in self.len_keys),
+                                      out={k: v[:m] for k, v in self.inr_out[slot].items()})
             for k in self.aug_keys:
-                # the same for the augmentation, which reads the normalised rows where there are any
+                # the same for the augmentation, which reads the prepared rows where there are any
                 feats[k] = self._augment(k, feats[k], self.slot_rows[:m], self.dev_ids[slot][:m],
                                          self.dev_valid[slot][k][:m] if k in self.valid else None, out=self.aug_out[slot][k][:m])
             yield self._out(feats), self.dev_lab[slot][:m], idx

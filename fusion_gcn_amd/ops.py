@@ -2024,3 +2024,80 @@ def clip_normalize(src: torch.Tensor, idx: torch.Tensor, *, origin_joint: int, z
     check(_lib.load().fgcn_clip_normalize(_p(src), idx.data_ptr(), _p(out), _p(frame_map), _p(params), b, M, T, V, C, int(origin_joint),
                                           z0, z1, x0, x1, _stream()), "fgcn_clip_normalize")
     return out, frame_map, params
+
+
+# ---- preparation of raw inertial recordings as the batch is gathered (fgcn_signal_prepare / fgcn_imu_enhance) --------
+def resample_index(t: int, src_len: int, dst_len: int) -> int:
+    """The frame of a recording of ``src_len`` frames that frame ``t`` of its resampling to ``dst_len`` frames reads, on the HOST (no device
+    is touched), by the function the kernels call."""
+    out = ctypes.c_int()
+    check(_lib.load().fgcn_resample_index(int(t), int(src_len), int(dst_len), ctypes.byref(out)), "fgcn_resample_index")
+    return out.value
+
+
+def _rows(idx: torch.Tensor, rows: int, device, name: str) -> torch.Tensor:
+    """(b) int64 row numbers -- on the device, where they are trusted, or on the host, where they are checked and uploaded."""
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise _lib.FgcnError(f"{name}: expected (b,) int64, got {tuple(idx.shape)} {idx.dtype}")
+    if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows):
+        raise _lib.FgcnError(f"{name}: rows outside [0, {rows})")
+    return idx.to(device).contiguous()
+
+
+def _lengths(t: torch.Tensor, rows: int, name: str) -> None:
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows:
+        raise _lib.FgcnError(f"{name}: expected {rows} contiguous int32 on the device, got {t.dtype} {t.device} numel={t.numel()}")
+
+
+def signal_prepare(src: torch.Tensor, idx: torch.Tensor, src_len: torch.Tensor, dst_len: torch.Tensor, T: int, *, minmax: bool = True,
+                   out: Optional[torch.Tensor] = None):
+    """-> (out, stats): out[k] (T, S) = the recording in source row ``idx[k]`` of ``src`` resampled from ``src_len[idx[k]]`` to
+    ``dst_len[idx[k]]`` frames (nearest neighbour, the reference's index formula), zero-padded to ``T`` frames and -- ``minmax`` -- min-max
+    normalised over the padded array as the reference's ``normalize_signal`` does (include/fgcn.h); stats (b, 2): the minimum and the
+    maximum of the shifted array (0, 1 without ``minmax``).  src: (rows, L, S) contiguous float32 on the device; idx: (b) int64 on the
+    device (trusted) or on the host (checked); src_len, dst_len: (rows) int32 on the device, indexed by SOURCE row."""
+    ensure_device()
+    _chk(src, "signal_prepare.src")
+    if src.dim() != 3:
+        raise _lib.FgcnError(f"signal_prepare.src: expected (rows, L, S), got {tuple(src.shape)}")
+    rows, L, S = src.shape
+    idx = _rows(idx, rows, src.device, "signal_prepare.idx")
+    _lengths(src_len, rows, "signal_prepare.src_len"), _lengths(dst_len, rows, "signal_prepare.dst_len")
+    b, T = idx.numel(), int(T)
+    if out is None:
+        out = torch.empty((b, T, S), device=src.device, dtype=torch.float32)
+    _chk(out, "signal_prepare.out")
+    if tuple(out.shape) != (b, T, S):
+        raise _lib.FgcnError(f"signal_prepare.out: {tuple(out.shape)} for a batch of {(b, T, S)}")
+    stats = torch.empty((b, 2), device=src.device, dtype=torch.float32)
+    check(_lib.load().fgcn_signal_prepare(_p(src), idx.data_ptr(), src_len.data_ptr(), dst_len.data_ptr(), _p(out), _p(stats), b, L, S, T,
+                                          int(bool(minmax)), _stream()), "fgcn_signal_prepare")
+    return out, stats
+
+
+def imu_enhance(skel: torch.Tensor, skel_idx: torch.Tensor, imu: torch.Tensor, imu_idx: torch.Tensor, src_len: torch.Tensor,
+                dst_len: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> out (b, M, T, V + S / 3, 3): the reference's ``skeleton_imu_enhanced`` array (include/fgcn.h).  Joints ``[0, V)`` are row
+    ``skel_idx[k]`` of ``skel`` (rows, M, T, V, C), C = 2 or 3 -- the NORMALISED skeleton, e.g. what ``clip_normalize`` returned; joints
+    ``[V, V + S / 3)`` of every body are the recording in row ``imu_idx[k]`` of ``imu`` (rows, L, S) resampled from ``src_len`` to
+    ``dst_len`` frames and zero-padded to T, three values per joint.  src_len, dst_len: (rows of imu) int32 on the device."""
+    ensure_device()
+    _chk(skel, "imu_enhance.skel"), _chk(imu, "imu_enhance.imu")
+    if skel.dim() != 5 or imu.dim() != 3:
+        raise _lib.FgcnError(f"imu_enhance: expected skel (rows, M, T, V, C) and imu (rows, L, S), got {tuple(skel.shape)}, {tuple(imu.shape)}")
+    (M, T, V, C), (rows, L, S) = skel.shape[1:], imu.shape
+    skel_idx = _rows(skel_idx, skel.shape[0], skel.device, "imu_enhance.skel_idx")
+    imu_idx = _rows(imu_idx, rows, skel.device, "imu_enhance.imu_idx")
+    b = skel_idx.numel()
+    if imu_idx.numel() != b:
+        raise _lib.FgcnError(f"imu_enhance: {b} skeleton rows and {imu_idx.numel()} signal rows")
+    _lengths(src_len, rows, "imu_enhance.src_len"), _lengths(dst_len, rows, "imu_enhance.dst_len")
+    shape = (b, M, T, V + S // 3, 3)
+    if out is None:
+        out = torch.empty(shape, device=skel.device, dtype=torch.float32)
+    _chk(out, "imu_enhance.out")
+    if tuple(out.shape) != shape:
+        raise _lib.FgcnError(f"imu_enhance.out: {tuple(out.shape)} for a batch of {shape}")
+    check(_lib.load().fgcn_imu_enhance(_p(skel), skel_idx.data_ptr(), _p(imu), imu_idx.data_ptr(), src_len.data_ptr(), dst_len.data_ptr(),
+                                       _p(out), b, M, T, V, C, L, S, _stream()), "fgcn_imu_enhance")
+    return out

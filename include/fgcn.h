@@ -1055,6 +1055,38 @@ int fgcn_augment_params(unsigned sample, unsigned site, unsigned epoch, unsigned
 int fgcn_clip_normalize(const float* src, const long long* idx, float* out, int* frame_map, double* params, int b, int M, int T, int V, int C,
                         int origin, int z0, int z1, int x0, int x1, void* stream);
 
+/* Preparation of raw inertial recordings as the batch is gathered (data.ClipBatches(inertial=...)): what the
+ * reference's offline preprocessing does to the accelerometer / gyroscope recording of a sample.  The recording has Li frames of S values
+ * (stored in a row of L >= Li frames), the sample's skeleton recording has Ls frames, a clip has T >= Ls frames.
+ *
+ * Step 1, resample (NearestNeighborInterpolator, util/preprocessing/interpolator.py): frame t of the result, 0 <= t < Ls, is frame
+ *     r(t) = t                                          where Li == Ls (the reference takes the recording as it is),
+ *     r(t) = rint(t * ((Li - 1) / (Ls - 1)))            otherwise: the quotient first, then the product, both float64, ties to even
+ * of the recording; r = 0 where Ls == 1; r is clamped into [0, Li - 1].  Step 2, pad (pad_sequence_numpy): frames Ls .. T-1 are zero.
+ * Step 3a, the signal (InertialProcessor, normalize_signal): over the WHOLE padded (T, S) array -- the padding zeros take part --
+ *     mn = min x, mx = fl32(max x - mn), y = fl32(fl32(x - mn) / mx), all float32, the division correctly rounded.
+ * A constant array gives 0 / 0 = NaN, as in the reference; a NaN in the array makes mn, mx and every y NaN, as numpy's min and max do.
+ * Step 3b, the enhanced skeleton (SkeletonProcessor("imu_enhanced")): (M, T, V + S / 3, 3); joints 0 .. V-1 of every body are the
+ * skeleton's (a third coordinate of zero where it has two), joint V + j of EVERY body holds values 3j .. 3j+2 of the padded array of
+ * step 2 -- not min-max normalised, and zero from frame Ls on, whatever the skeleton's normalisation repeated into those frames.
+ *
+ * fgcn_resample_index: r(t) on the HOST (no device is touched), by the function both kernels call.  FGCN_E_BADARG: out == NULL or a length <= 0.
+ *
+ * fgcn_signal_prepare: steps 1, 2, 3a.  src (rows, L, S), idx (b) 8-byte integers on the device (they may repeat and need not be sorted;
+ * every idx[k] must be a row of src -- the caller's duty), src_len / dst_len 4-byte integers on the device indexed by SOURCE row (Li and
+ * Ls; a value outside [1, L] / [1, T] is clamped into it), out (b, T, S), stats (b, 2) receives mn, mx.  minmax == 0: steps 1 and 2
+ * alone, and stats receives 0, 1.  One launch, one workgroup per clip: minimum and maximum (order-independent, so two calls give the same
+ * bits), then the values.
+ * fgcn_imu_enhance: steps 1, 2, 3b.  skel (rows_s, M, T, V, C) with skel_idx (b), imu (rows_i, L, S) with imu_idx (b), src_len / dst_len
+ * indexed by the row of IMU, out (b, M, T, V + S / 3, 3).  One launch, one lane per output joint.  skel may be what fgcn_clip_normalize wrote.
+ * Both: rows need 4-byte alignment only.  FGCN_E_BADARG before any launch: a null pointer; a size <= 0; C not 2 or 3 and S % 3 != 0
+ * (enhance); out == an input; 2^31 or more elements in out, in a clip or in a recording. */
+int fgcn_resample_index(int t, int src_len, int dst_len, int* out);
+int fgcn_signal_prepare(const float* src, const long long* idx, const int* src_len, const int* dst_len, float* out, float* stats, int b, int L,
+                        int S, int T, int minmax, void* stream);
+int fgcn_imu_enhance(const float* skel, const long long* skel_idx, const float* imu, const long long* imu_idx, const int* src_len,
+                     const int* dst_len, float* out, int b, int M, int T, int V, int C, int L, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
