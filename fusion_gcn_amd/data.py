@@ -18,26 +18,26 @@ the same ``(features, labels, indices)`` triples, already on the device, in one 
   * streaming: rows are gathered from the memory map into one of two pinned host buffers and copied on a side HIP stream
     while the previous step computes (double buffering; the consumer waits on an event, never on the host).
 Data-parallel ranks take contiguous shards of every global batch (``dp.shard_batch``), all ranks shuffling with the same
-seed.  torch is plumbing here (pinned memory, streams, index_select); without augmentation nothing on this path calls the HIP kernels.
+seed.  torch is plumbing here (pinned memory, streams, index_select); without a stage (below) nothing on this path calls the HIP kernels.
 
-Augmentation (ours; the reference has none): ``ClipBatches(..., augment=Augment(...))`` replaces the row gather of each modality by one
-``fgcn_clip_augment`` call -- random rotation and scale of the joints, a random temporal window resampled to the clip's length -- whose
-random numbers are keyed by (seed, epoch, global sample index): DESIGN.md section 8f.
-
-Normalisation (reference: util/preprocessing/skeleton.py:normalize_skeleton, an offline per-clip loop): ``ClipBatches(...,
-normalize=Normalize(...))`` takes RAW skeleton clips -- null frames padded, the centre joint of the first body at the origin, spine to z,
-shoulders to x -- with ``fgcn_clip_normalize``: once at upload on the resident path, per batch behind the copy on the streaming path, and
-before the augmentation where both are given: DESIGN.md section 8g.
-
-Inertial recordings (reference: SkeletonProcessor("imu_enhanced") and InertialProcessor, util/preprocessing/processor): ``ClipBatches(...,
-inertial=Inertial(frames=...))`` takes the RAW accelerometer / gyroscope recording -- resampled to the skeleton's frame count, zero-padded
-and min-max normalised (``fgcn_signal_prepare``), and with ``enhance=True`` appended as extra joints behind the normalised skeleton
-(``fgcn_imu_enhance``) -- after the normalisation and before the augmentation: DESIGN.md section 8h.
+Preparation on the device: ``ClipBatches`` runs the stages it is given, in this order, each a HIP kernel of libfgcn (no host fallback)
+  * ``normalize=Normalize(...)`` (reference: util/preprocessing/skeleton.py:normalize_skeleton, an offline per-clip loop): RAW skeleton
+    clips -- null frames padded, the centre joint of the first body at the origin, spine to z, shoulders to x -- with
+    ``fgcn_clip_normalize``: DESIGN.md section 8g;
+  * ``inertial=Inertial(frames=...)`` (reference: SkeletonProcessor("imu_enhanced") and InertialProcessor, util/preprocessing/processor):
+    the RAW accelerometer / gyroscope recording -- resampled to the skeleton's frame count, zero-padded and min-max normalised
+    (``fgcn_signal_prepare``), and with ``enhance=True`` appended as extra joints behind the normalised skeleton (``fgcn_imu_enhance``):
+    section 8h;
+  * ``augment=Augment(...)`` (ours; the reference has none): one ``fgcn_clip_augment`` call in place of the row gather of each modality --
+    random rotation and scale of the joints, a random temporal window resampled to the clip's length -- whose random numbers are keyed
+    by (seed, epoch, global sample index): section 8f.
+The first two run once at upload on the resident path, the augmentation on every batch; on the streaming path all run per batch, behind
+the copy.  What ``ClipBatches`` asks of a stage is listed above ``Augment``.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Iterable, Iterator, Mapping, Optional, Sequence, Tuple, Union
+from typing import Dict, Iterable, Iterator, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import numpy.lib.format
@@ -162,6 +162,22 @@ class MultiModalDataset(torch.utils.data.Dataset):
 
 # ---- batches ------------------------------------------------------------------------------------------------------------------
 Features = Union[torch.Tensor, Dict[str, torch.Tensor]]
+Shapes = Dict[str, tuple]       # feature id -> the shape of a sample
+Feats = Dict[str, torch.Tensor]
+Tables = Dict[Optional[str], torch.Tensor]
+
+# A stage of ClipBatches' preparation on the device -- Normalize, Inertial, Augment, run in that order -- is a configuration object with
+#   name        its keyword of ClipBatches, for the refusal of a device without HIP kernels
+#   at_upload   True: a resident split takes it once, at construction; False: every batch does
+#   bind(shapes, n, keys) -> (shapes, writes)   at construction: refuses what the stage cannot take of ``n`` samples of ``shapes`` (as the
+#               stage before left them) in a data set with the feature ids ``keys``; -> the shapes behind the stage and the feature ids
+#               it writes, which are the ones that need an output buffer
+#   tables(writes, n) -> {name: (n,) array}   what the kernels read beside the rows, indexed by the sample's index in the data set;
+#               None names the sample ids themselves
+#   run(batches, feats, rows, tables, out) -> feats   launches on the current stream: rows ``rows`` of the arrays ``feats`` into the buffers
+#               ``out`` (feature id -> tensor, or None = a new one); ``tables[name][rows[j]]`` belongs to output row j, except the sample ids,
+#               which are listed by output row; what the stage keeps for inspection goes to ``batches.last_*``
+# A fourth stage is one more such class and one more entry of ClipBatches' stage list.
 
 
 class Augment:
@@ -193,6 +209,8 @@ class Augment:
         self.valid_frames = dict(valid_frames or {})
         self.only = None if only is None else frozenset(only)
 
+    name, at_upload = "augment", False
+
     def applies_to(self, feature_id: str) -> bool:
         return self.only is None or feature_id in self.only
 
@@ -204,6 +222,38 @@ class Augment:
         if hi > sample_shape[2]:
             raise ValueError(f"joints={self.joints!r} for an array of {sample_shape[2]} joints")
         return (lo, hi) if hi > lo else None
+
+    def bind(self, shapes: Shapes, n: int, keys: Sequence[str]) -> Tuple[Shapes, List[str]]:
+        writes = [k for k in shapes if self.applies_to(k)]
+        for k in writes:
+            if len(shapes[k]) not in (2, 4):
+                raise FgcnError(f"augment: feature {k!r} has shape {(n, *shapes[k])}; expected (samples, M, T, V, C) or "
+                                f"(samples, T, S) -- leave it out with Augment(only=...)")
+            self.joint_range(shapes[k])                 # (a joint range the array does not have: refused here, not mid-epoch)
+        unknown = (set(self.valid_frames) | set(self.only or ())) - set(keys)
+        if unknown:
+            raise ValueError(f"augment names features the data set does not have: {sorted(unknown)}")
+        for k, v in self.tables(writes, n).items():
+            if k is not None:
+                T = shapes[k][-2] if len(shapes[k]) == 2 else shapes[k][1]
+                if v.shape != (n,) or v.min() < 1 or v.max() > T:
+                    raise ValueError(f"valid_frames[{k!r}]: expected {n} frame counts in [1, {T}]")
+        return dict(shapes), writes
+
+    def tables(self, writes: Sequence[str], n: int) -> Dict[Optional[str], np.ndarray]:
+        """None: the clips' ids, which key the random numbers; feature id: the valid frames of its clips"""
+        valid = {k: np.asarray(self.valid_frames[k]).astype(np.int32) for k in writes if k in self.valid_frames}
+        return {None: np.arange(n, dtype=np.int64), **valid}
+
+    def run(self, batches: "ClipBatches", feats: Feats, rows: torch.Tensor, tables: Tables, out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        from . import ops
+        feats = dict(feats)
+        for k, o in out.items():
+            src = feats[k]
+            feats[k], batches.last_params[k] = ops.clip_augment(
+                src, rows, tables[None], seed=batches.seed, epoch=batches.epoch, site=self.site, max_angle=self.max_angle, scale=self.scale,
+                min_window=self.min_window, joints=self.joint_range(src.shape[1:]), valid=tables.get(k), out=o)
+        return feats
 
 
 class Normalize:
@@ -254,6 +304,29 @@ class Normalize:
             raise FgcnError(f"normalize: feature {feature_id!r} has {C} coordinates; expected 2 or 3, and 3 with an axis pair")
         if max([self.origin_joint] + [j for p in pairs for j in p]) >= V:
             raise FgcnError(f"normalize: feature {feature_id!r} has {V} joints; the joint numbers {self.origin_joint}, {pairs} need more")
+
+    name, at_upload = "normalize", True
+
+    def bind(self, shapes: Shapes, n: int, keys: Sequence[str]) -> Tuple[Shapes, List[str]]:
+        unknown = set(self.only or ()) - set(keys)
+        if unknown:
+            raise ValueError(f"normalize names features the data set does not have: {sorted(unknown)}")
+        writes = [k for k in shapes if self.applies_to(k)]
+        for k in writes:
+            self.check_shape(k, (n, *shapes[k]))
+        return dict(shapes), writes
+
+    def tables(self, writes: Sequence[str], n: int) -> Dict[Optional[str], np.ndarray]:
+        return {}
+
+    def run(self, batches: "ClipBatches", feats: Feats, rows: torch.Tensor, tables: Tables, out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        from . import ops
+        feats = dict(feats)
+        for k, o in out.items():
+            feats[k], frame_map, params = ops.clip_normalize(feats[k], rows, origin_joint=self.origin_joint, z_axis_joints=self.z_axis_joints,
+                                                             x_axis_joints=self.x_axis_joints, out=o)
+            batches.last_plan[k] = (frame_map, params)
+        return feats
 
 
 class Inertial:
@@ -320,8 +393,34 @@ class Inertial:
             out[self.signal] = (T, S)
         return out
 
+    name, at_upload = "inertial", True
 
-NORMALIZE_CHUNK = 2048      # clips per fgcn_clip_normalize call when a resident split is normalised at upload
+    def bind(self, shapes: Shapes, n: int, keys: Sequence[str]) -> Tuple[Shapes, List[str]]:
+        full = {k: (n, *v) for k, v in shapes.items()}
+        self.check_shapes(full, n)
+        after = self.sample_shapes(full)
+        return after, [k for k in after if k == self.signal or (k == self.main and self.enhance)]
+
+    def tables(self, writes: Sequence[str], n: int) -> Dict[Optional[str], np.ndarray]:
+        return {k: self.frames[k] for k in (self.signal, self.main)}
+
+    def run(self, batches: "ClipBatches", feats: Feats, rows: torch.Tensor, tables: Tables, out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        """reads the raw recordings and the normalised skeletons in ``feats``"""
+        from . import ops
+        src_len, dst_len = tables[self.signal], tables[self.main]
+        res = {}
+        for k, v in feats.items():
+            if k == self.main and self.enhance:
+                res[k] = ops.imu_enhance(v, rows, feats[self.signal], rows, src_len, dst_len, out=out[k])
+            elif k != self.signal:
+                res[k] = v
+            elif not self.drop_signal:
+                res[k], batches.last_inertial = ops.signal_prepare(v, rows, src_len, dst_len, feats[self.main].shape[2], minmax=self.minmax,
+                                                                   out=out[k])
+        return res
+
+
+NORMALIZE_CHUNK = 2048      # clips per call when a resident split is normalised and prepared at upload
 
 
 class ClipBatches:
@@ -330,16 +429,16 @@ class ClipBatches:
     ``batch_size`` is the global batch (the reference's config value); rank r of ``world`` receives clips
     ``[r*bs/world, (r+1)*bs/world)`` of each global batch.  ``shuffle`` permutes with ``seed + epoch`` (``set_epoch``), the
     same permutation on every rank.  ``resident``: True / False, or None = upload the split when it takes at most
-    ``resident_budget`` bytes.  Features come out float32, labels int64 (session.py:171-174).  ``augment``: None = the stored clips as
-    they are; an ``Augment`` = every clip of the modalities it names transformed on the device as it is gathered, a pure function of
-    (``seed``, the epoch ``set_epoch`` set, the clip's index in the data set) -- labels and ``indices`` are untouched, and the parameter
-    tables of the last batch are kept in ``last_params`` (feature id -> (clips, 12) tensor).  ``normalize``: None = the stored clips are
-    taken as they are; a ``Normalize`` = the (samples, M, T, V, C) arrays it names hold RAW skeletons and are normalised on the device
-    -- a resident split once, at construction; a streamed batch behind its copy -- before any augmentation; ``last_plan`` (feature id ->
-    (frame_map, params)) keeps the tables of the last call.  ``inertial``: None = every feature as stored; an ``Inertial`` = the
-    signal it names holds RAW recordings, prepared on the device after the normalisation and before the augmentation (which sees the
-    prepared shapes) -- a resident split once, at construction; a streamed batch behind its copy; ``last_inertial`` keeps the
-    (clips, 2) minimum / maximum table of the last call."""
+    ``resident_budget`` bytes.  Features come out float32, labels int64 (session.py:171-174).
+
+    ``normalize``, ``inertial``, ``augment``: None = the stored clips as they are; otherwise the stages (``self.stages``) run on the
+    device in that order, each on what the one before left: ``shapes`` holds the sample shapes behind the last, ``out_keys`` their ids.
+    A ``Normalize`` = the (samples, M, T, V, C) arrays it names hold RAW skeletons; ``last_plan`` (feature id -> (frame_map, params))
+    keeps the tables of the last call.  An ``Inertial`` = the signal it names holds RAW recordings; ``last_inertial`` keeps the (clips, 2)
+    minimum / maximum table of the last call.  Both take a resident split once, at construction (``dev_feat`` then holds the prepared
+    arrays), and a streamed batch behind its copy.  An ``Augment`` = every clip of the modalities it names transformed as it is gathered,
+    a pure function of (``seed``, the epoch ``set_epoch`` set, the clip's index in the data set) -- labels and ``indices`` are
+    untouched; ``last_params`` (feature id -> (clips, 12) tensor) keeps the parameter tables of the last batch."""
 
     def __init__(self, dataset: MultiModalDataset, batch_size: int, *, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
@@ -360,67 +459,33 @@ class ClipBatches:
         self.resident = nbytes <= resident_budget if resident is None else bool(resident)
         self.labels = torch.from_numpy(np.asarray(dataset.labels_data).astype(np.int64))
         on_gpu = self.device.type == "cuda"
-        self.inertial, self.last_inertial = inertial, None
+        self.normalize, self.inertial, self.augment = normalize, inertial, augment
+        self.stages = [s for s in (normalize, inertial, augment) if s is not None]      # in the order they run
+        self.last_plan, self.last_inertial, self.last_params = {}, None, {}
         self.shapes = {k: tuple(a.shape[1:]) for k, a in self.arrays.items()}      # of a sample, as the batch holds it
-        if inertial is not None:
+        self.writes, self.tables, after = {}, {}, {}        # per stage: the features it writes, its host tables, the shapes behind it
+        for s in self.stages:
             if not on_gpu:
-                raise FgcnError("ClipBatches(inertial=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
-            inertial.check_shapes({k: a.shape for k, a in self.arrays.items()}, n)
-            self.shapes = inertial.sample_shapes({k: a.shape for k, a in self.arrays.items()})
+                raise FgcnError(f"ClipBatches({s.name}=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
+            self.shapes, self.writes[s.name] = s.bind(self.shapes, n, self.keys)
+            after[s.name] = self.shapes
+            self.tables[s.name] = {t: torch.from_numpy(a) for t, a in s.tables(self.writes[s.name], n).items()}
         self.out_keys = list(self.shapes)
-        # the features the preparation writes: the enhanced skeleton, the prepared signal
-        self.inr_keys = [] if inertial is None else [k for k in self.out_keys if k == inertial.signal or (k == inertial.main and inertial.enhance)]
-        self.augment, self.last_params = augment, {}
-        self.aug_keys = [k for k in self.out_keys if augment is not None and augment.applies_to(k)]
-        if augment is not None:
-            if not on_gpu:
-                raise FgcnError("ClipBatches(augment=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
-            for k in self.aug_keys:
-                if len(self.shapes[k]) not in (2, 4):
-                    raise FgcnError(f"augment: feature {k!r} has shape {(n, *self.shapes[k])}; expected (samples, M, T, V, C) or "
-                                    f"(samples, T, S) -- leave it out with Augment(only=...)")
-                augment.joint_range(self.shapes[k])         # (a joint range the array does not have: refused here, not mid-epoch)
-            unknown = (set(augment.valid_frames) | set(augment.only or ())) - set(self.keys)
-            if unknown:
-                raise ValueError(f"augment names features the data set does not have: {sorted(unknown)}")
-            self.valid = {}
-            for k in self.aug_keys:
-                if k in augment.valid_frames:
-                    v = np.asarray(augment.valid_frames[k])
-                    T = self.shapes[k][-2] if len(self.shapes[k]) == 2 else self.shapes[k][1]
-                    if v.shape != (n,) or v.min() < 1 or v.max() > T:
-                        raise ValueError(f"valid_frames[{k!r}]: expected {n} frame counts in [1, {T}]")
-                    self.valid[k] = torch.from_numpy(v.astype(np.int32))
-        self.normalize, self.last_plan = normalize, {}
-        self.norm_keys = [k for k in self.keys if normalize is not None and normalize.applies_to(k)]
-        if normalize is not None:
-            if not on_gpu:
-                raise FgcnError("ClipBatches(normalize=...) runs a HIP kernel and needs device='cuda': there is no host fallback")
-            unknown = set(normalize.only or ()) - set(self.keys)
-            if unknown:
-                raise ValueError(f"normalize names features the data set does not have: {sorted(unknown)}")
-            for k in self.norm_keys:
-                normalize.check_shape(k, self.arrays[k].shape)
+        self.norm_keys = self.writes.get("normalize", [])
         if self.resident:
             self.dev_feat = {k: torch.from_numpy(np.array(a[:n], dtype=np.float32)).to(self.device)
                              for k, a in self.arrays.items()}
-            for k in self.norm_keys:                        # once, at upload: nothing is done per batch
-                raw, self.dev_feat[k] = self.dev_feat[k], torch.empty_like(self.dev_feat[k])
-                for lo in range(0, n, NORMALIZE_CHUNK):
-                    rows = torch.arange(lo, min(lo + NORMALIZE_CHUNK, n), dtype=torch.int64, device=self.device)
-                    self._normalize(k, raw, rows, out=self.dev_feat[k][lo:lo + len(rows)])
-            if inertial is not None:                        # the same for the recordings, which read the normalised skeletons
-                raw = self.dev_feat
-                lens = [torch.from_numpy(inertial.frames[k]).to(self.device) for k in (inertial.signal, inertial.main)]
-                done = {k: torch.empty((n, *self.shapes[k]), dtype=torch.float32, device=self.device) for k in self.inr_keys}
-                for lo in range(0, n, NORMALIZE_CHUNK):
-                    rows = torch.arange(lo, min(lo + NORMALIZE_CHUNK, n), dtype=torch.int64, device=self.device)
-                    self._prepare(raw, rows, *lens, out={k: v[lo:lo + len(rows)] for k, v in done.items()})
-                self.dev_feat = {k: done.get(k, raw[k]) for k in self.out_keys}      # (the raw recordings are released)
-                del raw
             self.dev_labels = self.labels.to(self.device)
-            if augment is not None:
-                self.dev_valid = {k: v.to(self.device) for k, v in self.valid.items()}
+            # the whole tables, indexed by source row; the sample ids (table None) are the row numbers themselves here
+            self.dev_tab = {s.name: {t: v.to(self.device) for t, v in self.tables[s.name].items() if t is not None} for s in self.stages}
+            for s in self.stages:
+                if s.at_upload:                             # once, in chunks: nothing is done per batch, and the next stage reads the result
+                    done = {k: torch.empty((n, *after[s.name][k]), dtype=torch.float32, device=self.device) for k in self.writes[s.name]}
+                    tabs = self.dev_tab.pop(s.name)
+                    for lo in range(0, n, NORMALIZE_CHUNK):
+                        rows = torch.arange(lo, min(lo + NORMALIZE_CHUNK, n), dtype=torch.int64, device=self.device)
+                        s.run(self, self.dev_feat, rows, {**tabs, None: rows}, {k: v[lo:lo + len(rows)] for k, v in done.items()})
+                    self.dev_feat = {k: done.get(k, self.dev_feat[k]) for k in after[s.name]}      # (what it replaced is released)
         else:
             per = batch_size // world
             mk = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=on_gpu)      # noqa: E731
@@ -432,29 +497,17 @@ class ClipBatches:
             self.copy_stream = torch.cuda.Stream(self.device) if on_gpu else None
             self.copied = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
             self.consumed = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
-            if augment is not None or normalize is not None or inertial is not None:
+            if self.stages:
                 self.slot_rows = torch.arange(per, dtype=torch.int64, device=self.device)
-            if normalize is not None:
-                # per slot: the normalised batch (the uploaded rows are the kernel's source); the slot's `consumed` event covers it
-                self.norm_out = [{k: torch.empty_like(self.dev[s][k]) for k in self.norm_keys} for s in range(2)]
-            if inertial is not None:
-                # per slot: the prepared features, under the same event, and the two frame counts of the slot's rows, staged and copied
-                # with the rows (signal first, as the kernels take them)
-                self.inr_out = [{k: torch.empty((per, *self.shapes[k]), dtype=torch.float32, device=self.device) for k in self.inr_keys}
-                                for _ in range(2)]
-                self.len_keys = (inertial.signal, inertial.main)
-                self.frames = {k: torch.from_numpy(inertial.frames[k]) for k in self.len_keys}
-                self.host_len = [{k: mk((per,), torch.int32) for k in self.len_keys} for _ in range(2)]
-                self.dev_len = [{k: torch.empty((per,), dtype=torch.int32, device=self.device) for k in self.len_keys} for _ in range(2)]
-            if augment is not None:
-                # per slot: the augmented batch (what the consumer receives; the uploaded rows are the kernel's source), the clips' ids, and
-                # the valid frames of the slot's rows, staged and copied with the rows
-                self.aug_out = [{k: torch.empty((per, *self.shapes[k]), dtype=torch.float32, device=self.device) for k in self.aug_keys}
-                                for _ in range(2)]
-                self.host_ids = [mk((per,), torch.int64) for _ in range(2)]
-                self.dev_ids = [torch.empty((per,), dtype=torch.int64, device=self.device) for _ in range(2)]
-                self.host_valid = [{k: mk((per,), torch.int32) for k in self.valid} for _ in range(2)]
-                self.dev_valid = [{k: torch.empty((per,), dtype=torch.int32, device=self.device) for k in self.valid} for _ in range(2)]
+            # per slot and stage: what the stage writes (the uploaded rows, or the stage before, are its source; the slot's `consumed`
+            # event covers it) and the table rows of the slot's clips, staged and copied with the clips
+            self.stage_out = [{s.name: {k: torch.empty((per, *after[s.name][k]), dtype=torch.float32, device=self.device)
+                                        for k in self.writes[s.name]} for s in self.stages} for _ in range(2)]
+            self.dev_tab = [{name: {t: torch.empty((per,), dtype=v.dtype, device=self.device) for t, v in tabs.items()}
+                             for name, tabs in self.tables.items()} for _ in range(2)]
+            # per slot, every table in the order it is staged and copied: (the table, the slot's pinned rows, the slot's device rows)
+            self.slot_tabs = [[(v, mk((per,), v.dtype), dev[name][t]) for name, tabs in self.tables.items() for t, v in tabs.items()]
+                              for dev in self.dev_tab]
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -485,54 +538,19 @@ class ClipBatches:
                     continue
             yield glob[shard_batch(len(glob), self.rank, self.world)]
 
-    def _augment(self, k: str, src: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, valid: Optional[torch.Tensor],
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Rows ``rows`` of ``src`` (the clips ``ids`` of the data set), augmented for this epoch, on the current stream."""
-        from . import ops
-        a = self.augment
-        out, params = ops.clip_augment(src, rows, ids, seed=self.seed, epoch=self.epoch, site=a.site, max_angle=a.max_angle, scale=a.scale,
-                                       min_window=a.min_window, joints=a.joint_range(src.shape[1:]), valid=valid, out=out)
-        self.last_params[k] = params
-        return out
-
-    def _normalize(self, k: str, src: torch.Tensor, rows: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-        """Rows ``rows`` of the raw clips ``src``, normalised into ``out``, on the current stream."""
-        from . import ops
-        z = self.normalize
-        out, frame_map, params = ops.clip_normalize(src, rows, origin_joint=z.origin_joint, z_axis_joints=z.z_axis_joints,
-                                                    x_axis_joints=z.x_axis_joints, out=out)
-        self.last_plan[k] = (frame_map, params)
-        return out
-
-    def _prepare(self, feats: Dict[str, torch.Tensor], rows: torch.Tensor, src_len: torch.Tensor, dst_len: torch.Tensor,
-                 out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """Rows ``rows`` of the raw recordings (and of the normalised skeletons) in ``feats``, prepared into the buffers ``out``, on the
-        current stream -> the features of the batch; the frame counts are indexed like the rows of ``feats``."""
-        from . import ops
-        z = self.inertial
-        res = {}
-        for k in self.out_keys:
-            if k == z.main and z.enhance:
-                res[k] = ops.imu_enhance(feats[k], rows, feats[z.signal], rows, src_len, dst_len, out=out[k])
-            elif k == z.signal:
-                res[k], self.last_inertial = ops.signal_prepare(feats[k], rows, src_len, dst_len, self.shapes[k][0], minmax=z.minmax,
-                                                                out=out[k])
-            else:
-                res[k] = feats[k]
-        return res
-
     def _out(self, feats: Dict[str, torch.Tensor]) -> Features:
         return feats[self.out_keys[0]] if len(self.out_keys) == 1 else feats
 
     def __iter__(self) -> Iterator[Tuple[Features, torch.Tensor, torch.Tensor]]:
         if self.resident:
+            per_batch = [s for s in self.stages if not s.at_upload]
+            written = {k for s in per_batch for k in self.writes[s.name]}
             for idx in self._shards():
                 di = idx.to(self.device)
-                if self.augment is None:
-                    feats = {k: v.index_select(0, di) for k, v in self.dev_feat.items()}
-                else:
-                    feats = {k: self._augment(k, v, di, di, self.dev_valid.get(k)) if k in self.aug_keys else v.index_select(0, di)
-                             for k, v in self.dev_feat.items()}
+                feats = self.dev_feat
+                for s in per_batch:                      # rows = ids = the shard's indices
+                    feats = s.run(self, feats, di, {**self.dev_tab[s.name], None: di}, dict.fromkeys(self.writes[s.name]))
+                feats = {k: v if k in written else v.index_select(0, di) for k, v in feats.items()}
                 yield self._out(feats), self.dev_labels.index_select(0, di), idx
             return
         on_gpu = self.device.type == "cuda"
@@ -548,26 +566,16 @@ class ClipBatches:
                 rows = np.asarray(a[order], dtype=np.float32)
                 self.host[slot][k][:m].copy_(torch.from_numpy(rows[back]))
             self.host_lab[slot][:m].copy_(self.labels[idx])
-            if self.inertial is not None:
-                for k in self.len_keys:
-                    self.host_len[slot][k][:m].copy_(self.frames[k][idx])
-            if self.augment is not None:
-                self.host_ids[slot][:m].copy_(idx)
-                for k, v in self.valid.items():
-                    self.host_valid[slot][k][:m].copy_(v[idx])
+            for table, host, _ in self.slot_tabs[slot]:
+                host[:m].copy_(table[idx])
             if on_gpu:
                 self.copy_stream.wait_event(self.consumed[slot])      # the consumer of the device slot's last batch is done
                 with torch.cuda.stream(self.copy_stream):
                     for k in self.keys:
                         self.dev[slot][k][:m].copy_(self.host[slot][k][:m], non_blocking=True)
                     self.dev_lab[slot][:m].copy_(self.host_lab[slot][:m], non_blocking=True)
-                    if self.inertial is not None:
-                        for k in self.len_keys:
-                            self.dev_len[slot][k][:m].copy_(self.host_len[slot][k][:m], non_blocking=True)
-                    if self.augment is not None:
-                        self.dev_ids[slot][:m].copy_(self.host_ids[slot][:m], non_blocking=True)
-                        for k in self.valid:
-                            self.dev_valid[slot][k][:m].copy_(self.host_valid[slot][k][:m], non_blocking=True)
+                    for _, host, dev in self.slot_tabs[slot]:
+                        dev[:m].copy_(host[:m], non_blocking=True)
                     self.copied[slot].record(self.copy_stream)
             else:
                 for k in self.keys:
@@ -587,17 +595,11 @@ class ClipBatches:
             if on_gpu:
                 torch.cuda.current_stream(self.device).wait_event(self.copied[slot])
             feats = {k: self.dev[slot][k][:m] for k in self.keys}
-            for k in self.norm_keys:
-                # on the consumer's stream, behind the copy: the slot's rows are the source, `consumed` below covers kernel and consumer
-                feats[k] = self._normalize(k, self.dev[slot][k][:m], self.slot_rows[:m], out=self.norm_out[slot][k][:m])
-            if self.inertial is not None:
-                # the same for the recordings, which read the normalised skeletons where there are any
-                feats = self._prepare(feats, self.slot_rows[:m], *(self.dev_len[slot][k][:m] for k in self.len_keys),
-                                      out={k: v[:m] for k, v in self.inr_out[slot].items()})
-            for k in self.aug_keys:
-                # the same for the augmentation, which reads the prepared rows where there are any
-                feats[k] = self._augment(k, feats[k], self.slot_rows[:m], self.dev_ids[slot][:m],
-                                         self.dev_valid[slot][k][:m] if k in self.valid else None, out=self.aug_out[slot][k][:m])
+            for s in self.stages:
+                # on the consumer's stream, behind the copy: the slot's rows (or the stage before) are the source, `consumed` below covers
+                # kernels and consumer
+                feats = s.run(self, feats, self.slot_rows[:m], {t: v[:m] for t, v in self.dev_tab[slot][s.name].items()},
+                              {k: v[:m] for k, v in self.stage_out[slot][s.name].items()})
             yield self._out(feats), self.dev_lab[slot][:m], idx
             if on_gpu:
                 self.consumed[slot].record(torch.cuda.current_stream(self.device))

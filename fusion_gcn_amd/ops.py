@@ -1925,6 +1925,31 @@ def rng_advance(step: torch.Tensor) -> None:
     check(_lib.load().fgcn_rng_advance(step.data_ptr(), _stream()), "fgcn_rng_advance")
 
 
+# ---- the arguments the four wrappers of ClipBatches' stages share (DESIGN.md sections 8f-8h) -------------------------------------------
+def _rows(idx: torch.Tensor, rows: int, device, name: str) -> torch.Tensor:
+    """(b) int64 row numbers -- on the device, where they are trusted, or on the host, where they are checked and uploaded."""
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise _lib.FgcnError(f"{name}: expected (b,) int64, got {tuple(idx.shape)} {idx.dtype}")
+    if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows):
+        raise _lib.FgcnError(f"{name}: rows outside [0, {rows})")
+    return idx.to(device).contiguous()
+
+
+def _lengths(t: torch.Tensor, rows: int, name: str) -> None:
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows:
+        raise _lib.FgcnError(f"{name}: expected {rows} contiguous int32 on the device, got {t.dtype} {t.device} numel={t.numel()}")
+
+
+def _batch_out(out: Optional[torch.Tensor], shape: Tuple[int, ...], device, name: str) -> torch.Tensor:
+    """``out``, which must have the batch's shape, or a new tensor of that shape"""
+    if out is None:
+        out = torch.empty(shape, device=device, dtype=torch.float32)
+    _chk(out, name)
+    if tuple(out.shape) != tuple(shape):
+        raise _lib.FgcnError(f"{name}: {tuple(out.shape)} for a batch of {tuple(shape)}")
+    return out
+
+
 # ---- augmentation of clips as the batch is gathered (fgcn_clip_augment / fgcn_augment_params; DESIGN.md section 8f) -------------------
 def _augment_scalars(max_angle, scale: float, min_window: float):
     if len(max_angle) != 3:
@@ -1958,22 +1983,14 @@ def clip_augment(src: torch.Tensor, idx: torch.Tensor, sample_ids: torch.Tensor,
         outer, T, inner, C = 1, src.shape[1], src.shape[2], src.shape[2]
     else:
         raise _lib.FgcnError(f"clip_augment.src: expected (rows, M, T, V, C) or (rows, T, S), got {tuple(src.shape)}")
+    idx = _rows(idx, src.shape[0], src.device, "clip_augment.idx")
     b = idx.numel()
-    for t, name in ((idx, "idx"), (sample_ids, "sample_ids")):
-        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != b:
-            raise _lib.FgcnError(f"clip_augment.{name}: expected ({b},) int64, got {tuple(t.shape)} {t.dtype}")
-    if not idx.is_cuda:
-        if b and (int(idx.min()) < 0 or int(idx.max()) >= src.shape[0]):
-            raise _lib.FgcnError(f"clip_augment.idx: rows outside [0, {src.shape[0]})")
-    idx, sample_ids = idx.to(src.device).contiguous(), sample_ids.to(src.device).contiguous()
-    if valid is not None and (not valid.is_cuda or valid.dtype != torch.int32 or not valid.is_contiguous() or valid.numel() != src.shape[0]):
-        raise _lib.FgcnError(f"clip_augment.valid: expected {src.shape[0]} contiguous int32 on the device, got {valid.dtype} {valid.device} "
-                             f"numel={valid.numel()}")
-    if out is None:
-        out = torch.empty((b, *src.shape[1:]), device=src.device, dtype=torch.float32)
-    _chk(out, "clip_augment.out")
-    if tuple(out.shape) != (b, *src.shape[1:]):
-        raise _lib.FgcnError(f"clip_augment.out: {tuple(out.shape)} for a batch of {(b, *src.shape[1:])}")
+    if sample_ids.dtype != torch.int64 or sample_ids.dim() != 1 or sample_ids.numel() != b:
+        raise _lib.FgcnError(f"clip_augment.sample_ids: expected ({b},) int64, got {tuple(sample_ids.shape)} {sample_ids.dtype}")
+    sample_ids = sample_ids.to(src.device).contiguous()
+    if valid is not None:
+        _lengths(valid, src.shape[0], "clip_augment.valid")
+    out = _batch_out(out, (b, *src.shape[1:]), src.device, "clip_augment.out")
     lo, hi = (0, 0) if joints is None else (int(joints[0]), int(joints[1]))
     ang, scale, min_window = _augment_scalars(max_angle, scale, min_window)
     params = torch.empty((b, 12), device=src.device, dtype=torch.float32)
@@ -2005,20 +2022,11 @@ def clip_normalize(src: torch.Tensor, idx: torch.Tensor, *, origin_joint: int, z
     if src.dim() != 5:
         raise _lib.FgcnError(f"clip_normalize.src: expected (rows, M, T, V, C), got {tuple(src.shape)}")
     M, T, V, C = src.shape[1:]
+    idx = _rows(idx, src.shape[0], src.device, "clip_normalize.idx")
     b = idx.numel()
-    if idx.dtype != torch.int64 or idx.dim() != 1:
-        raise _lib.FgcnError(f"clip_normalize.idx: expected ({b},) int64, got {tuple(idx.shape)} {idx.dtype}")
-    if not idx.is_cuda:
-        if b and (int(idx.min()) < 0 or int(idx.max()) >= src.shape[0]):
-            raise _lib.FgcnError(f"clip_normalize.idx: rows outside [0, {src.shape[0]})")
-    idx = idx.to(src.device).contiguous()
     z0, z1 = _joint_pair(z_axis_joints, "z_axis_joints")
     x0, x1 = _joint_pair(x_axis_joints, "x_axis_joints")
-    if out is None:
-        out = torch.empty((b, M, T, V, C), device=src.device, dtype=torch.float32)
-    _chk(out, "clip_normalize.out")
-    if tuple(out.shape) != (b, M, T, V, C):
-        raise _lib.FgcnError(f"clip_normalize.out: {tuple(out.shape)} for a batch of {(b, M, T, V, C)}")
+    out = _batch_out(out, (b, M, T, V, C), src.device, "clip_normalize.out")
     frame_map = torch.empty((b, M, T), device=src.device, dtype=torch.int32)
     params = torch.empty((b, 12), device=src.device, dtype=torch.float64)
     check(_lib.load().fgcn_clip_normalize(_p(src), idx.data_ptr(), _p(out), _p(frame_map), _p(params), b, M, T, V, C, int(origin_joint),
@@ -2033,20 +2041,6 @@ def resample_index(t: int, src_len: int, dst_len: int) -> int:
     out = ctypes.c_int()
     check(_lib.load().fgcn_resample_index(int(t), int(src_len), int(dst_len), ctypes.byref(out)), "fgcn_resample_index")
     return out.value
-
-
-def _rows(idx: torch.Tensor, rows: int, device, name: str) -> torch.Tensor:
-    """(b) int64 row numbers -- on the device, where they are trusted, or on the host, where they are checked and uploaded."""
-    if idx.dtype != torch.int64 or idx.dim() != 1:
-        raise _lib.FgcnError(f"{name}: expected (b,) int64, got {tuple(idx.shape)} {idx.dtype}")
-    if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows):
-        raise _lib.FgcnError(f"{name}: rows outside [0, {rows})")
-    return idx.to(device).contiguous()
-
-
-def _lengths(t: torch.Tensor, rows: int, name: str) -> None:
-    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows:
-        raise _lib.FgcnError(f"{name}: expected {rows} contiguous int32 on the device, got {t.dtype} {t.device} numel={t.numel()}")
 
 
 def signal_prepare(src: torch.Tensor, idx: torch.Tensor, src_len: torch.Tensor, dst_len: torch.Tensor, T: int, *, minmax: bool = True,
@@ -2064,11 +2058,7 @@ def signal_prepare(src: torch.Tensor, idx: torch.Tensor, src_len: torch.Tensor, 
     idx = _rows(idx, rows, src.device, "signal_prepare.idx")
     _lengths(src_len, rows, "signal_prepare.src_len"), _lengths(dst_len, rows, "signal_prepare.dst_len")
     b, T = idx.numel(), int(T)
-    if out is None:
-        out = torch.empty((b, T, S), device=src.device, dtype=torch.float32)
-    _chk(out, "signal_prepare.out")
-    if tuple(out.shape) != (b, T, S):
-        raise _lib.FgcnError(f"signal_prepare.out: {tuple(out.shape)} for a batch of {(b, T, S)}")
+    out = _batch_out(out, (b, T, S), src.device, "signal_prepare.out")
     stats = torch.empty((b, 2), device=src.device, dtype=torch.float32)
     check(_lib.load().fgcn_signal_prepare(_p(src), idx.data_ptr(), src_len.data_ptr(), dst_len.data_ptr(), _p(out), _p(stats), b, L, S, T,
                                           int(bool(minmax)), _stream()), "fgcn_signal_prepare")
@@ -2092,12 +2082,7 @@ def imu_enhance(skel: torch.Tensor, skel_idx: torch.Tensor, imu: torch.Tensor, i
     if imu_idx.numel() != b:
         raise _lib.FgcnError(f"imu_enhance: {b} skeleton rows and {imu_idx.numel()} signal rows")
     _lengths(src_len, rows, "imu_enhance.src_len"), _lengths(dst_len, rows, "imu_enhance.dst_len")
-    shape = (b, M, T, V + S // 3, 3)
-    if out is None:
-        out = torch.empty(shape, device=skel.device, dtype=torch.float32)
-    _chk(out, "imu_enhance.out")
-    if tuple(out.shape) != shape:
-        raise _lib.FgcnError(f"imu_enhance.out: {tuple(out.shape)} for a batch of {shape}")
+    out = _batch_out(out, (b, M, T, V + S // 3, 3), skel.device, "imu_enhance.out")
     check(_lib.load().fgcn_imu_enhance(_p(skel), skel_idx.data_ptr(), _p(imu), imu_idx.data_ptr(), src_len.data_ptr(), dst_len.data_ptr(),
                                        _p(out), b, M, T, V, C, L, S, _stream()), "fgcn_imu_enhance")
     return out

@@ -253,6 +253,61 @@ def test_drop_signal_yields_a_tensor_and_identity_augmentation_the_prepared_batc
         assert torch.equal(feats["skeleton"][:, :, :, 7:], enhanced[idx][:, :, :, 7:])
 
 
+def test_three_stages_compose_in_order_on_both_paths_and_across_ranks(raw_dataset):
+    """all three stages with real magnitudes, shuffled, epoch 2, batches of 4, 4, 2 (two slots, a ragged tail, a key whose shape a stage
+    changes): the resident and the streaming path deliver the same bits, two ranks (one resident, one streaming) concatenate to the
+    one-rank batches, and every batch is the stages composed by hand through ops -- normalise, prepare, augment"""
+    from fusion_gcn_amd import ops
+    from fusion_gcn_amd.data import Augment, ClipBatches, Inertial, Normalize
+    ds, skel, imu, frames = raw_dataset
+    Ls = frames["skeleton"]
+    aug = Augment(joints=(0, 7), valid_frames={"skeleton": Ls, "inertial": Ls})      # its default angles, scale and window
+
+    def epoch(resident, rank=0, world=1):
+        it = ClipBatches(ds, BS, shuffle=True, seed=5, rank=rank, world=world, device=DEV, resident=resident,
+                         normalize=Normalize(**KW7, only=["skeleton"]), inertial=Inertial(frames=frames, enhance=True),
+                         augment=aug)
+        it.set_epoch(2)
+        out = []
+        for feats, lab, idx in it:
+            assert list(feats) == ["inertial", "skeleton"] and set(it.last_params) == set(feats)
+            out.append(({k: v.cpu().clone() for k, v in feats.items()}, lab.cpu().clone(), idx.clone(),
+                        {k: v.cpu().clone() for k, v in it.last_params.items()}))
+        torch.cuda.synchronize()
+        assert it.resident == resident
+        return it, out
+
+    def same(a, b):
+        return (torch.equal(a[2], b[2]) and torch.equal(a[1], b[1])
+                and all(torch.equal(_bits(a[0][k]), _bits(b[0][k])) and torch.equal(_bits(a[3][k]), _bits(b[3][k])) for k in a[0]))
+
+    (it, res), (_, stream) = epoch(True), epoch(False)
+    assert [len(b[2]) for b in res] == [4, 4, 2] and len(stream) == 3
+    assert all(same(a, b) for a, b in zip(res, stream))
+    # 1. == 2.: the ranks' shards, one rank resident and one streaming, are the halves of the one-rank batches
+    (_, r0), (_, r1) = epoch(True, 0, 2), epoch(False, 1, 2)
+    assert len(r0) == len(r1) == 3
+    for one, a, b in zip(res, r0, r1):
+        both = ({k: torch.cat([a[0][k], b[0][k]]) for k in one[0]}, torch.cat([a[1], b[1]]), torch.cat([a[2], b[2]]),
+                {k: torch.cat([a[3][k], b[3][k]]) for k in one[3]})
+        assert same(one, both)
+    # 3. the stages by hand, in order
+    raw_skel, raw_imu = _f(skel), _f(imu)
+    li, ls = _i(frames["inertial"], torch.int32), _i(Ls, torch.int32)
+    assert it.shapes == {"inertial": (13, 6), "skeleton": (1, 13, 9, 3)}
+    for feats, _, idx, params in res:
+        b = len(idx)
+        norm, _, _ = ops.clip_normalize(raw_skel, idx, **KW7)
+        signal, _ = ops.signal_prepare(raw_imu, idx, li, ls, 13)
+        enhanced = ops.imu_enhance(norm, torch.arange(b), raw_imu, idx, li, ls)
+        valid = _i(Ls[idx.numpy()], torch.int32)
+        for k, src, joints in (("skeleton", enhanced, (0, 7)), ("inertial", signal, None)):
+            want, want_params = ops.clip_augment(src, torch.arange(b), idx, seed=5, epoch=2, site=0, max_angle=aug.max_angle, scale=aug.scale,
+                                                 min_window=aug.min_window, joints=joints, valid=valid)
+            assert torch.equal(_bits(feats[k]), _bits(want.cpu())), k
+            assert torch.equal(_bits(params[k]), _bits(want_params.cpu())), k
+
+
 def test_clip_batches_refuses_what_it_cannot_prepare(raw_dataset):
     from fusion_gcn_amd import _lib
     from fusion_gcn_amd.data import Augment, ClipBatches, Inertial
