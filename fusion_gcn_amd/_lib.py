@@ -209,6 +209,7 @@ SIGNATURES = {
     "fgcn_resample_index": (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
     "fgcn_signal_prepare": (_I, [_P] * 6 + [_I] * 5 + [_P]),
     "fgcn_imu_enhance": (_I, [_P] * 7 + [_I] * 7 + [_P]),
+    "fgcn_clip_streams": (_I, [_P] * 8 + [_I] * 5 + [_P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

@@ -30,9 +30,12 @@ Preparation on the device: ``ClipBatches`` runs the stages it is given, in this 
     section 8h;
   * ``augment=Augment(...)`` (ours; the reference has none): one ``fgcn_clip_augment`` call in place of the row gather of each modality --
     random rotation and scale of the joints, a random temporal window resampled to the clip's length -- whose random numbers are keyed
-    by (seed, epoch, global sample index): section 8f.
-The first two run once at upload on the resident path, the augmentation on every batch; on the streaming path all run per batch, behind
-the copy.  What ``ClipBatches`` asks of a stage is listed above ``Augment``.
+    by (seed, epoch, global sample index): section 8f;
+  * ``streams=Streams(parents, ...)`` (the bone and motion inputs 2s-AGCN is trained on; the reference has none): one ``fgcn_clip_streams``
+    call per skeleton feature -- joint minus parent joint, frame t+1 minus frame t inside the valid frames, and the motion of the bones,
+    of the clip as the stages before left it: section 8j.
+The first two run once at upload on the resident path, the augmentation and the streams on every batch; on the streaming path all run per
+batch, behind the copy.  What ``ClipBatches`` asks of a stage is listed above ``Augment``.
 """
 from __future__ import annotations
 
@@ -166,7 +169,7 @@ Shapes = Dict[str, tuple]       # feature id -> the shape of a sample
 Feats = Dict[str, torch.Tensor]
 Tables = Dict[Optional[str], torch.Tensor]
 
-# A stage of ClipBatches' preparation on the device -- Normalize, Inertial, Augment, run in that order -- is a configuration object with
+# A stage of ClipBatches' preparation on the device -- Normalize, Inertial, Augment, Streams, run in that order -- is a configuration object with
 #   name        its keyword of ClipBatches, for the refusal of a device without HIP kernels
 #   at_upload   True: a resident split takes it once, at construction; False: every batch does
 #   bind(shapes, n, keys) -> (shapes, writes)   at construction: refuses what the stage cannot take of ``n`` samples of ``shapes`` (as the
@@ -176,8 +179,12 @@ Tables = Dict[Optional[str], torch.Tensor]
 #               None names the sample ids themselves
 #   run(batches, feats, rows, tables, out) -> feats   launches on the current stream: rows ``rows`` of the arrays ``feats`` into the buffers
 #               ``out`` (feature id -> tensor, or None = a new one); ``tables[name][rows[j]]`` belongs to output row j, except the sample ids,
-#               which are listed by output row; what the stage keeps for inspection goes to ``batches.last_*``
-# A fourth stage is one more such class and one more entry of ClipBatches' stage list.
+#               which are listed by output row; what the stage keeps for inspection goes to ``batches.last_*``.  A per-batch stage that
+#               may run BEHIND another per-batch stage on the resident path (Streams) takes ``rows`` per feature too, {feature id: rows}:
+#               what the stage before wrote holds the batch's rows in order (rows 0..m-1), what it left out is still the resident array
+#               (the shard's indices).  The rows are handed over per feature rather than the left-out features gathered first: a gather
+#               would be one more pass over rows that the stage's own kernel gathers anyway.
+# A further stage is one more such class and one more entry of ClipBatches' stage list: Streams is the fourth.
 
 
 class Augment:
@@ -420,6 +427,126 @@ class Inertial:
         return res
 
 
+class Streams:
+    """What ``ClipBatches(streams=...)`` derives from every skeleton clip it hands out (include/fgcn.h): the input
+    streams of the two-stream AGCN family, from the clip as every stage before left it (the motion of a clip is not the resampled motion).
+
+    ``parents``: one entry per joint -- its parent joint, the joint itself for the root (whose bone is zero), or -1 for a joint that is
+    copied through (the sensor joints ``Inertial(enhance=True)`` appends).  ``streams``: distinct names of ``STREAMS``, at least one of
+    them derived: "joint" the clip itself, "bone" joint minus parent, "motion" frame t+1 minus frame t (zero from the last valid frame
+    on), "bone_motion" the motion of the bones.  One name: the feature keeps its id and holds that stream.  Several: "joint" keeps the
+    feature's id ``k``, every other comes out as ``f"{k}_{stream}"`` directly behind it, and ``k`` is left out of the batch unless "joint"
+    is named.  ``only``: the feature ids to apply to (default: every (M, T, V, C) feature with C of 2 or 3).  ``valid_frames``: feature
+    id -> the number of valid frames of each sample, as ``Augment.valid_frames`` (default: all T)."""
+
+    STREAMS = ("joint", "bone", "motion", "bone_motion")
+
+    def __init__(self, parents: Sequence[int], streams: Sequence[str] = ("bone",), only: Optional[Iterable[str]] = None,
+                 valid_frames: Optional[Mapping[str, Sequence[int]]] = None):
+        if isinstance(streams, str):
+            streams = (streams,)
+        self.streams = tuple(streams)
+        if not self.streams or len(set(self.streams)) != len(self.streams) or not set(self.streams) <= set(self.STREAMS):
+            raise ValueError(f"streams={streams!r}: expected distinct names of {self.STREAMS}, at least one")
+        if self.streams == ("joint",):
+            raise ValueError("streams=('joint',) derives nothing: name at least one of 'bone', 'motion', 'bone_motion'")
+        if any(isinstance(p, bool) or not isinstance(p, (int, np.integer)) for p in parents):
+            raise ValueError(f"parents={parents!r}: expected one joint number (or -1) per joint")
+        self.parents = tuple(int(p) for p in parents)
+        V = len(self.parents)
+        bad = [v for v, p in enumerate(self.parents) if not -1 <= p < V]
+        if V == 0 or bad:
+            raise ValueError(f"parents: expected {V or 'at least one'} entries in [-1, {V}); joint(s) {bad} have {[self.parents[v] for v in bad]}")
+        self.only = None if only is None else frozenset(only)
+        self.valid_frames = dict(valid_frames or {})
+        self._device_parents = {}       # device -> the (V) int32 table, built (and checked by ops) on the first batch there
+
+    @classmethod
+    def for_dataset(cls, name: str, extra_joints: int = 0, **kw) -> "Streams":
+        """The parents of a data set's skeleton (``"utd_mhad"``, ``"mmact"``, ``"ntu_rgb_d"``): its constants module's ``skeleton_edges``
+        are (child, parent) rows and its ``center_joint`` is the root; ``extra_joints`` entries of -1 follow for appended sensor joints."""
+        from .util.dynamic_import import import_dataset_constants
+        got = import_dataset_constants(name, ["skeleton_edges", "center_joint", "num_joints"])
+        if len(got) != 3:
+            raise ValueError(f"data set {name!r} has no skeleton graph constants")
+        edges, center, V = got
+        parents = {**{int(child): int(parent) for child, parent in np.asarray(edges).tolist()}, int(center): int(center)}
+        missing = sorted(set(range(V)) - set(parents))
+        if missing:
+            raise ValueError(f"data set {name!r}: joints {missing} of {V} appear in no edge as the child, and are not the centre joint")
+        if extra_joints < 0:
+            raise ValueError(f"extra_joints={extra_joints}")
+        return cls([parents[v] for v in range(V)] + [-1] * int(extra_joints), **kw)
+
+    name, at_upload = "streams", False
+
+    def applies_to(self, feature_id: str, sample_shape: Sequence[int]) -> bool:
+        if self.only is not None:
+            return feature_id in self.only
+        return len(sample_shape) == 4 and sample_shape[3] in (2, 3)
+
+    def output_ids(self, feature_id: str) -> Dict[str, str]:
+        """stream -> the id it comes out under, in the batch's order: the feature's own id first where it is kept"""
+        if len(self.streams) == 1:
+            return {self.streams[0]: feature_id}
+        ordered = [s for s in self.streams if s == "joint"] + [s for s in self.streams if s != "joint"]
+        return {s: feature_id if s == "joint" else f"{feature_id}_{s}" for s in ordered}
+
+    def bind(self, shapes: Shapes, n: int, keys: Sequence[str]) -> Tuple[Shapes, List[str]]:
+        unknown = (set(self.valid_frames) | set(self.only or ())) - set(keys)
+        if unknown:
+            raise ValueError(f"streams names features the data set does not have: {sorted(unknown)}")
+        applied = [k for k in shapes if self.applies_to(k, shapes[k])]
+        missing = (set(self.valid_frames) | set(self.only or ())) - set(applied)
+        if missing:
+            raise ValueError(f"streams names features that are not in the batch at this stage or that it does not apply to: {sorted(missing)}")
+        V = len(self.parents)
+        after, writes = {}, []
+        for k, shape in shapes.items():
+            if k not in applied:
+                after[k] = shape
+                continue
+            if len(shape) != 4 or shape[3] not in (2, 3):
+                raise FgcnError(f"streams: feature {k!r} has shape {(n, *shape)}; expected (samples, M, T, V, C) with C of 2 or 3 -- leave it "
+                                f"out with Streams(only=...)")
+            if shape[2] != V:
+                raise FgcnError(f"streams: feature {k!r} has {shape[2]} joints, parents has {V} entries")
+            if k in self.valid_frames:
+                v = np.asarray(self.valid_frames[k])
+                if v.shape != (n,) or v.dtype.kind not in "iu" or v.min() < 1 or v.max() > shape[1]:
+                    raise ValueError(f"valid_frames[{k!r}]: expected {n} frame counts in [1, {shape[1]}]")
+            for out_id in self.output_ids(k).values():
+                after[out_id] = shape
+                writes.append(out_id)
+        taken = [k for k in shapes if k not in applied] + writes
+        clash = sorted({k for k in taken if taken.count(k) > 1})
+        if clash:
+            raise ValueError(f"streams: the output ids {clash} are already features of the batch -- rename them or use Streams(only=...)")
+        return after, writes
+
+    def tables(self, writes: Sequence[str], n: int) -> Dict[Optional[str], np.ndarray]:
+        """feature id: the valid frames of its clips"""
+        return {k: np.asarray(v).astype(np.int32) for k, v in self.valid_frames.items()}
+
+    def run(self, batches: "ClipBatches", feats: Feats, rows: Union[torch.Tensor, Dict[str, torch.Tensor]], tables: Tables,
+            out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        """``rows`` per feature where the stage before wrote some features and not others (see the protocol above ``Augment``)"""
+        from . import ops
+        res, batches.last_streams = {}, {}
+        for k, src in feats.items():
+            if not self.applies_to(k, src.shape[1:]):
+                res[k] = src
+                continue
+            if src.device not in self._device_parents:
+                self._device_parents[src.device] = ops.stream_parents(self.parents, src.device)
+            ids = self.output_ids(k)
+            got = ops.clip_streams(src, rows[k] if isinstance(rows, dict) else rows, self._device_parents[src.device], streams=self.streams,
+                                   valid=tables.get(k), out={s: out[i] for s, i in ids.items() if out[i] is not None})
+            res.update({i: got[s] for s, i in ids.items()})
+            batches.last_streams[k] = list(ids.values())
+        return res
+
+
 NORMALIZE_CHUNK = 2048      # clips per call when a resident split is normalised and prepared at upload
 
 
@@ -438,12 +565,14 @@ class ClipBatches:
     minimum / maximum table of the last call.  Both take a resident split once, at construction (``dev_feat`` then holds the prepared
     arrays), and a streamed batch behind its copy.  An ``Augment`` = every clip of the modalities it names transformed as it is gathered,
     a pure function of (``seed``, the epoch ``set_epoch`` set, the clip's index in the data set) -- labels and ``indices`` are
-    untouched; ``last_params`` (feature id -> (clips, 12) tensor) keeps the parameter tables of the last batch."""
+    untouched; ``last_params`` (feature id -> (clips, 12) tensor) keeps the parameter tables of the last batch.  ``streams``: a
+    ``Streams`` = the last stage, on every batch: the skeleton features it names come out as their bone / motion streams (under the ids its
+    docstring lists); ``last_streams`` (feature id -> the ids it came out under) keeps the map of the last batch."""
 
     def __init__(self, dataset: MultiModalDataset, batch_size: int, *, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
                  resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None,
-                 normalize: Optional[Normalize] = None, inertial: Optional[Inertial] = None):
+                 normalize: Optional[Normalize] = None, inertial: Optional[Inertial] = None, streams: Optional[Streams] = None):
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
@@ -459,9 +588,14 @@ class ClipBatches:
         self.resident = nbytes <= resident_budget if resident is None else bool(resident)
         self.labels = torch.from_numpy(np.asarray(dataset.labels_data).astype(np.int64))
         on_gpu = self.device.type == "cuda"
-        self.normalize, self.inertial, self.augment = normalize, inertial, augment
-        self.stages = [s for s in (normalize, inertial, augment) if s is not None]      # in the order they run
-        self.last_plan, self.last_inertial, self.last_params = {}, None, {}
+        self.normalize, self.inertial, self.augment, self.streams = normalize, inertial, augment, streams
+        self.stages = [s for s in (normalize, inertial, augment, streams) if s is not None]      # in the order they run
+        self.last_plan, self.last_inertial, self.last_params, self.last_streams = {}, None, {}, {}
+        if streams is not None and augment is not None:
+            stale = sorted(k for k in streams.valid_frames if augment.applies_to(k))
+            if stale:                                       # the augmented clip fills all T frames: the table no longer describes it
+                raise ValueError(f"streams: valid_frames{stale} behind an Augment that resamples these features to all T frames -- give the "
+                                 f"table to the Augment alone")
         self.shapes = {k: tuple(a.shape[1:]) for k, a in self.arrays.items()}      # of a sample, as the batch holds it
         self.writes, self.tables, after = {}, {}, {}        # per stage: the features it writes, its host tables, the shapes behind it
         for s in self.stages:
@@ -478,6 +612,8 @@ class ClipBatches:
             self.dev_labels = self.labels.to(self.device)
             # the whole tables, indexed by source row; the sample ids (table None) are the row numbers themselves here
             self.dev_tab = {s.name: {t: v.to(self.device) for t, v in self.tables[s.name].items() if t is not None} for s in self.stages}
+            if sum(not s.at_upload for s in self.stages) > 1:      # the rows of what one per-batch stage wrote, for the next
+                self.batch_rows = torch.arange(batch_size // world, dtype=torch.int64, device=self.device)
             for s in self.stages:
                 if s.at_upload:                             # once, in chunks: nothing is done per batch, and the next stage reads the result
                     done = {k: torch.empty((n, *after[s.name][k]), dtype=torch.float32, device=self.device) for k in self.writes[s.name]}
@@ -547,9 +683,12 @@ class ClipBatches:
             written = {k for s in per_batch for k in self.writes[s.name]}
             for idx in self._shards():
                 di = idx.to(self.device)
-                feats = self.dev_feat
-                for s in per_batch:                      # rows = ids = the shard's indices
-                    feats = s.run(self, feats, di, {**self.dev_tab[s.name], None: di}, dict.fromkeys(self.writes[s.name]))
+                feats, rows = self.dev_feat, di          # rows = ids = the shard's indices, for the first per-batch stage
+                for s in per_batch:
+                    feats = s.run(self, feats, rows, {**self.dev_tab[s.name], None: di}, dict.fromkeys(self.writes[s.name]))
+                    if s is not per_batch[-1]:           # what it wrote holds the batch's rows in order, the rest is still the resident array
+                        rows = {k: self.batch_rows[:len(idx)] if k in self.writes[s.name] else rows[k] if isinstance(rows, dict) else rows
+                                for k in feats}
                 feats = {k: v if k in written else v.index_select(0, di) for k, v in feats.items()}
                 yield self._out(feats), self.dev_labels.index_select(0, di), idx
             return

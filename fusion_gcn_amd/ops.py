@@ -2086,3 +2086,52 @@ def imu_enhance(skel: torch.Tensor, skel_idx: torch.Tensor, imu: torch.Tensor, i
     check(_lib.load().fgcn_imu_enhance(_p(skel), skel_idx.data_ptr(), _p(imu), imu_idx.data_ptr(), src_len.data_ptr(), dst_len.data_ptr(),
                                        _p(out), b, M, T, V, C, L, S, _stream()), "fgcn_imu_enhance")
     return out
+
+
+# ---- the bone / motion streams as the batch is gathered (fgcn_clip_streams) ------------------------------------------
+STREAMS = ("joint", "bone", "motion", "bone_motion")     # the order of fgcn_clip_streams' output pointers
+
+
+def stream_parents(parents: Sequence[int], device) -> torch.Tensor:
+    """The parent table of ``clip_streams`` on the device: (V) int32.  Checked here, on the host, once: every entry is a joint number in
+    [0, V), the joint itself for the root, or -1 for a joint that is copied through (include/fgcn.h)."""
+    table = [int(p) for p in parents]
+    V = len(table)
+    bad = [v for v, p in enumerate(table) if not -1 <= p < V]
+    if V == 0 or bad:
+        raise _lib.FgcnError(f"clip_streams.parents: expected {V or 'at least one'} entries in [-1, {V}); joint(s) {bad} have {[table[v] for v in bad]}")
+    return torch.tensor(table, dtype=torch.int32).to(device)
+
+
+def clip_streams(src: torch.Tensor, idx: torch.Tensor, parents, *, streams: Sequence[str] = ("bone",), valid: Optional[torch.Tensor] = None,
+                 out: Optional[dict] = None) -> dict:
+    """-> {stream: (b, M, T, V, C) tensor} for the ``streams`` asked for, of source rows ``idx`` of ``src`` (include/fgcn.h): "joint" the
+    rows themselves, "bone" joint minus parent joint, "motion" frame t+1 minus frame t inside the valid frames, "bone_motion" the motion of
+    the bones; one launch for all of them.  src: (rows, M, T, V, C) contiguous float32 on the device, C = 2 or 3; idx: (b) int64 -- on the
+    device, where it is trusted to hold rows of ``src``, or on the host, where it is checked and uploaded; parents: what
+    ``stream_parents`` returned ((V) int32 on the device, checked when it was built), or a sequence of V ints, which is checked and
+    uploaded by this call; valid: None or (rows) int32 on the device, the valid frames of each SOURCE row; out: {stream: tensor to write}
+    for some or all of the streams."""
+    ensure_device()
+    _chk(src, "clip_streams.src")
+    if src.dim() != 5:
+        raise _lib.FgcnError(f"clip_streams.src: expected (rows, M, T, V, C), got {tuple(src.shape)}")
+    M, T, V, C = src.shape[1:]
+    streams = tuple(streams)
+    if not streams or len(set(streams)) != len(streams) or not set(streams) <= set(STREAMS) or set(streams) == {"joint"}:
+        raise _lib.FgcnError(f"clip_streams.streams: expected distinct names of {STREAMS} with at least one derived stream, got {streams!r}")
+    if not isinstance(parents, torch.Tensor) or not parents.is_cuda:
+        parents = stream_parents(parents.tolist() if isinstance(parents, torch.Tensor) else parents, src.device)
+    if parents.dtype != torch.int32 or not parents.is_contiguous() or parents.numel() != V:
+        raise _lib.FgcnError(f"clip_streams.parents: expected {V} contiguous int32 on the device, got {parents.dtype} numel={parents.numel()}")
+    idx = _rows(idx, src.shape[0], src.device, "clip_streams.idx")
+    b = idx.numel()
+    if valid is not None:
+        _lengths(valid, src.shape[0], "clip_streams.valid")
+    unknown = set(out or ()) - set(streams)
+    if unknown:
+        raise _lib.FgcnError(f"clip_streams.out: buffers for {sorted(unknown)}, which are not among the streams {streams!r}")
+    res = {s: _batch_out((out or {}).get(s), (b, M, T, V, C), src.device, f"clip_streams.out[{s!r}]") for s in streams}
+    check(_lib.load().fgcn_clip_streams(_p(src), idx.data_ptr(), parents.data_ptr(), _p(valid), *[_p(res.get(s)) for s in STREAMS], b, M, T, V, C,
+                                        _stream()), "fgcn_clip_streams")
+    return res

@@ -1087,6 +1087,34 @@ int fgcn_signal_prepare(const float* src, const long long* idx, const int* src_l
 int fgcn_imu_enhance(const float* skel, const long long* skel_idx, const float* imu, const long long* imu_idx, const int* src_len,
                      const int* dst_len, float* out, int b, int M, int T, int V, int C, int L, int S, void* stream);
 
+/* The input streams of the two-stream AGCN family, derived as the batch is gathered (data.ClipBatches(streams=...); DESIGN.md section
+ * 8j).  A clip x is (M, T, V, C) float32, C = 2 or 3; every body and coordinate is treated alike, [t, v] below names the C values of
+ * joint v in frame t.  parents[v] = p is the joint's parent; L is the valid frame count of the clip (T without a table).  Every value is
+ * ONE correctly rounded float32 subtraction, a copy or a zero -- there is no product and no fused operation, so a numpy float32
+ * restatement gives the same bits.
+ *
+ *     joint[t, v]       = x[t, v]
+ *     bone[t, v]        = x[t, v] - x[t, p]                 p == v (the root, as in 2s-AGCN): x - x, exactly +0 for a finite x;
+ *                       = x[t, v]                           p == -1: copied through (the sensor joints that imu_enhance appends hold
+ *                                                           sensor axes, not positions)
+ *     motion[t, v]      = x[t+1, v] - x[t, v]               for t < L - 1;   +0 for t >= L - 1
+ *     bone_motion[t, v] = bone[t+1, v] - bone[t, v]         for t < L - 1;   +0 for t >= L - 1.  Both bones are rounded to float32 first;
+ *                                                           for p == -1 it equals motion.
+ * bone and joint know nothing of L: they cover all T frames.  motion and bone_motion read frame t+1 only when t+1 < L: neither frame T nor
+ * any frame at or behind L is ever read for one of their values (the lanes of frames L-1 .. T-1 read frame L-1 and store the zero).
+ *
+ * fgcn_clip_streams: src (rows, M, T, V, C), idx (b) 8-byte integers on the device (they may repeat and need not be sorted; every idx[k]
+ * must be a row of src -- the caller's duty; the streaming path passes idx = 0..b-1), parents (V) 4-byte integers on the device (a value
+ * outside [-1, V) is clamped into it, so that none becomes an address: the host layer checks them once, when it builds the table), valid
+ * NULL or 4-byte integers on the device indexed by SOURCE row idx[k] (a value outside [1, T] is clamped into it).  joint, bone, motion,
+ * bone_motion: (b, M, T, V, C) each, or NULL = that stream is not wanted; at least one of bone, motion, bone_motion.  One launch, one lane
+ * per (row, body, frame, joint); which outputs exist is uniform over the launch; no atomics; two calls give the same bits.  Rows need
+ * 4-byte alignment only.
+ * FGCN_E_BADARG before any launch: src, idx or parents NULL; no derived output; b, M, T or V <= 0; C not 2 or 3; an output == src; more
+ * lanes than one grid holds (b * M * T * V > (2^31 - 1) * 256). */
+int fgcn_clip_streams(const float* src, const long long* idx, const int* parents, const int* valid, float* joint, float* bone, float* motion,
+                      float* bone_motion, int b, int M, int T, int V, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
