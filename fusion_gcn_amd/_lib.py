@@ -81,6 +81,18 @@ class OptimGuard(C.Structure):
 OPT_MAX_GROUPS = 8          # FGCN_OPT_MAX_GROUPS
 OPT_TILE4 = 1024            # FGCN_OPT_TILE4: 16-byte groups per row of the tile table, at most
 
+FUSE_MAX_STREAMS = 8        # FGCN_FUSE_MAX_STREAMS
+FUSE_PASS = 2048            # FGCN_FUSE_PASS
+FUSE_MAX_CANDIDATES = 1 << 20      # FGCN_FUSE_MAX_CANDIDATES
+FUSE_TRANSFORMS = {"none": 0, "softmax": 1}            # enum fgcn_fuse_transform
+FUSE_EXAMPLES, FUSE_IGNORED, FUSE_INVALID, FUSE_HEADER = range(4)      # enum fgcn_fuse_word: the words at the head of fgcn_fuse_sweep's counts
+
+
+class FuseIn(C.Structure):
+    """FgcnFuseIn: the score tensors of the stream models (device pointers, row strides in floats) and, for fgcn_score_fuse, their weights."""
+    _fields_ = [("scores", C.c_void_p * FUSE_MAX_STREAMS), ("ld", C.c_int * FUSE_MAX_STREAMS), ("weight", C.c_float * FUSE_MAX_STREAMS)]
+
+
 _I, _LL, _F, _D, _P = C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/fgcn.h one to one.  The fifteen kernels that take bfloat16 activation tensors carry `half_mask`
@@ -210,6 +222,8 @@ SIGNATURES = {
     "fgcn_signal_prepare": (_I, [_P] * 6 + [_I] * 5 + [_P]),
     "fgcn_imu_enhance": (_I, [_P] * 7 + [_I] * 7 + [_P]),
     "fgcn_clip_streams": (_I, [_P] * 8 + [_I] * 5 + [_P]),
+    "fgcn_score_fuse": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _I, _I, _P]),
+    "fgcn_fuse_sweep": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

@@ -517,6 +517,87 @@ class MisclassifiedSamplesList(_StateBacked, Metric):
         return f"{self.name}: {self._state().offset} samples seen"
 
 
+class StreamScores(Metric):
+    """The class scores of every sample of a split, kept on the device by sample index: what one trained stream model contributes to a
+    score-fusion ensemble (``ensemble.ScoreStore``).  Not state-backed: hand it to ``build_metrics`` as one of the
+    ``additional_metrics`` under a name that holds "val", run one validation pass per stream model, ``save`` each.
+
+    ``update((y_pred, y_true), indices=...)`` writes the batch's rows and labels at ``indices`` (``index_copy_``: it does not wait; indices
+    on the host are range-checked, indices on the device are trusted to be sample numbers below ``num_samples``); ``value`` is the host
+    ``(scores float32 (N, classes), labels int64 (N,), filled bool (N,))``; ``to_summary`` writes nothing."""
+
+    def __init__(self, name: str, num_samples: int, num_classes: int):
+        super().__init__(name)
+        if num_samples < 1 or not 1 <= num_classes <= _lib.CLS_MAX_CLASSES:
+            raise ValueError(f"StreamScores: num_samples={num_samples} (>= 1), num_classes={num_classes} (1..{_lib.CLS_MAX_CLASSES})")
+        self.num_samples, self.num_classes = int(num_samples), int(num_classes)
+        self._store = None                  # (scores, labels, filled) on the device, from the first update on
+
+    def update(self, val=None, indices=None, **kwargs):
+        y_pred, y_true = val
+        if not (torch.is_tensor(y_pred) and y_pred.is_cuda and torch.is_tensor(y_true) and y_true.is_cuda):
+            raise _lib.FgcnError("StreamScores: scores and labels must be on the HIP device (there is no host path)")
+        if indices is None:
+            raise ValueError("StreamScores: an update came without sample indices")
+        if y_pred.dim() != 2 or y_pred.shape[1] != self.num_classes or y_true.shape != y_pred.shape[:1]:
+            raise ValueError(f"StreamScores: scores {tuple(y_pred.shape)} and labels {tuple(y_true.shape)}, expected (rows, {self.num_classes}) and (rows,)")
+        if not (torch.is_tensor(indices) and indices.is_cuda):
+            host = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+            if host.numel() and not (0 <= int(host.min()) and int(host.max()) < self.num_samples):
+                raise ValueError(f"StreamScores: sample indices outside [0, {self.num_samples})")
+            indices = host.to(y_pred.device, non_blocking=True)
+        indices = indices.reshape(-1).to(torch.int64)
+        if indices.numel() != y_pred.shape[0]:
+            raise ValueError(f"StreamScores: {indices.numel()} indices for {y_pred.shape[0]} rows")
+        if self._store is None:
+            self._store = ops.score_store(self.num_samples, self.num_classes, y_pred.device)
+        elif self._store[0].device != y_pred.device:            # arrays installed by _load_arrays continue on the device
+            self._store = tuple(ops.device_copy(t, y_pred.device) for t in self._store)
+        scores, labels, filled = self._store
+        scores.index_copy_(0, indices, y_pred.detach().to(torch.float32))
+        labels.index_copy_(0, indices, y_true.to(torch.int64))
+        filled.index_fill_(0, indices, 1)
+
+    @property
+    def device_value(self):
+        """(scores, labels, filled uint8) on the device, or None before the first update"""
+        return self._store
+
+    @property
+    def value(self):
+        if self._store is None:
+            return (np.zeros((self.num_samples, self.num_classes), np.float32), np.full(self.num_samples, -1, np.int64),
+                    np.zeros(self.num_samples, bool))
+        scores, labels, filled = (t.cpu().numpy() for t in self._store)
+        return scores, labels, filled.astype(bool)
+
+    def reset(self):
+        if self._store is not None:
+            self._store[0].zero_()
+            self._store[1].fill_(-1)
+            self._store[2].zero_()
+
+    def _to_summary(self, summary, epoch: int):
+        pass
+
+    def _load_arrays(self, scores, labels, filled) -> None:
+        """Not part of the interface: installs host arrays shaped like ``value`` as the store, so that ``value`` / ``save`` / ``reset`` and
+        ``ScoreStore.from_metrics`` can be exercised where no device is (the next update would move them to its device)."""
+        scores, labels, filled = np.asarray(scores, np.float32), np.asarray(labels, np.int64), np.asarray(filled).astype(np.uint8)
+        if scores.shape != (self.num_samples, self.num_classes) or labels.shape != (self.num_samples,) or filled.shape != (self.num_samples,):
+            raise ValueError(f"StreamScores._load_arrays: expected scores {(self.num_samples, self.num_classes)}, labels and filled "
+                             f"{(self.num_samples,)}; got {scores.shape}, {labels.shape}, {filled.shape}")
+        self._store = tuple(torch.from_numpy(np.ascontiguousarray(a).copy()) for a in (scores, labels, filled))
+
+    def save(self, path: str) -> None:
+        """``.npz`` with ``scores`` float32 (N, classes), ``labels`` int64 (N,) and ``filled`` bool (N,) (waits for the device)"""
+        scores, labels, filled = self.value
+        np.savez(path, scores=scores, labels=labels, filled=filled)
+
+    def __str__(self):
+        return f"{self.name}: scores of {self.num_samples} samples"
+
+
 # ---- the container --------------------------------------------------------------------------------------------------------------
 class MetricsContainer:
     """Stores, updates and formats the metrics of a session.  A metric is a training metric when its name holds "train", a validation

@@ -2135,3 +2135,108 @@ def clip_streams(src: torch.Tensor, idx: torch.Tensor, parents, *, streams: Sequ
     check(_lib.load().fgcn_clip_streams(_p(src), idx.data_ptr(), parents.data_ptr(), _p(valid), *[_p(res.get(s)) for s in STREAMS], b, M, T, V, C,
                                         _stream()), "fgcn_clip_streams")
     return res
+
+
+# ---- score fusion of separately trained stream models (fgcn_score_fuse / fgcn_fuse_sweep) -----------------------------
+def _fuse_in(what: str, scores: Sequence[torch.Tensor]):
+    """-> (FuseIn without weights, S, rows, classes, device) of the stream models' score tensors: float32 (rows, classes) on one device,
+    classes contiguous, any row stride"""
+    scores = list(scores)
+    if not 1 <= len(scores) <= _lib.FUSE_MAX_STREAMS:
+        raise _lib.FgcnError(f"{what}: expected 1..{_lib.FUSE_MAX_STREAMS} score tensors, got {len(scores)}")
+    first = scores[0]
+    for s, z in enumerate(scores):
+        if not (torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and z.numel() and (z.shape[1] == 1 or z.stride(1) == 1)):
+            raise _lib.FgcnError(f"{what}: scores[{s}] must be a float32 (rows, classes) tensor on the device with contiguous classes "
+                                 f"(there is no host path)")
+        if z.shape != first.shape or z.device != first.device:
+            raise _lib.FgcnError(f"{what}: scores[{s}] is {tuple(z.shape)} on {z.device}, scores[0] is {tuple(first.shape)} on {first.device}")
+    rows, classes = first.shape
+    arg = _lib.FuseIn()
+    for s, z in enumerate(scores):
+        arg.scores[s] = z.data_ptr()
+        arg.ld[s] = z.stride(0) if rows > 1 else max(z.stride(0), classes)        # a single row's stride is arbitrary
+    return arg, len(scores), rows, classes, first.device
+
+
+def _fuse_transform(what: str, transform: str) -> int:
+    if transform not in _lib.FUSE_TRANSFORMS:
+        raise _lib.FgcnError(f"{what}: transform={transform!r}, expected one of {sorted(_lib.FUSE_TRANSFORMS)}")
+    return _lib.FUSE_TRANSFORMS[transform]
+
+
+def _host_f32(values) -> torch.Tensor:
+    """weights as float32 on the host (a device tensor is read back: weights are a handful of numbers)"""
+    if torch.is_tensor(values):
+        return values.detach().to(device="cpu", dtype=torch.float32)
+    return torch.as_tensor(values, dtype=torch.float64).to(torch.float32)
+
+
+def device_copy(values, device, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """A contiguous copy of a host array or tensor in a device buffer of this module's own (what ``ensemble.ScoreStore`` holds its scores
+    and labels in)."""
+    src = values if torch.is_tensor(values) else torch.as_tensor(values)
+    out = torch.empty(tuple(src.shape), dtype=dtype or src.dtype, device=device)
+    out.copy_(src)
+    return out
+
+
+def score_store(rows: int, classes: int, device):
+    """-> (scores float32 (rows, classes) zeros, labels int64 (rows,) of -1, filled uint8 (rows,) zeros): the device store of a
+    ``metrics.StreamScores``"""
+    return (torch.zeros((rows, classes), dtype=torch.float32, device=device), torch.full((rows,), -1, dtype=torch.int64, device=device),
+            torch.zeros((rows,), dtype=torch.uint8, device=device))
+
+
+def score_fuse(scores: Sequence[torch.Tensor], weights, transform: str = "none", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> fused (rows, classes) float32: ``float32(sum_s float64(w_s) * float64(t_s))`` of the stream models' scores, in stream order, with
+    t_s the scores themselves (``"none"``) or their float64-formed softmax (``"softmax"``) -- include/fgcn.h, fgcn_score_fuse; one launch.
+    scores: 1..8 float32 (rows, classes) device tensors (classes contiguous, any row stride); weights: one number per stream, converted to
+    float32 first; out: a float32 (rows, classes) device tensor with contiguous classes that is none of the inputs."""
+    mode = _fuse_transform("score_fuse", transform)
+    arg, S, rows, classes, device = _fuse_in("score_fuse", scores)          # (before the device check: a host tensor is refused as such anywhere)
+    ensure_device()
+    w = _host_f32(weights).reshape(-1)
+    if w.numel() != S:
+        raise _lib.FgcnError(f"score_fuse: {w.numel()} weights for {S} score tensors")
+    for s in range(S):
+        arg.weight[s] = float(w[s])
+    if out is None:
+        out = torch.empty((rows, classes), dtype=torch.float32, device=device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == device and out.dtype == torch.float32 and tuple(out.shape) == (rows, classes)
+              and (classes == 1 or out.stride(1) == 1)):
+        raise _lib.FgcnError(f"score_fuse: out must be a float32 {(rows, classes)} tensor on {device} with contiguous classes")
+    ld_out = out.stride(0) if rows > 1 else max(out.stride(0), classes)
+    check(_lib.load().fgcn_score_fuse(ctypes.byref(arg), S, mode, out.data_ptr(), ld_out, rows, classes, _stream()), "fgcn_score_fuse")
+    return out
+
+
+def fuse_sweep(scores: Sequence[torch.Tensor], candidates, labels: torch.Tensor, k: int, transform: str = "none",
+               counts: Optional[torch.Tensor] = None):
+    """-> (hits int64 (G, 2), header int64 (3,)), both views of one device buffer: for each of the G candidate weight vectors the top-1
+    and top-k hit counts of the fused scores under ``fgcn_classify_update``'s ranking rules, and the rows by label (``_lib.FUSE_EXAMPLES``,
+    ``FUSE_IGNORED``, ``FUSE_INVALID``) -- include/fgcn.h, fgcn_fuse_sweep; the call does not wait for the device.
+    candidates: (G, S) numbers, converted to float32 first (a host array is uploaded); labels: int64 (rows,) on the device;
+    counts: the int64 (3 + 2 G,) device buffer of an earlier call, to ADD to it (default: a zeroed one)."""
+    mode = _fuse_transform("fuse_sweep", transform)
+    arg, S, rows, classes, device = _fuse_in("fuse_sweep", scores)          # (before the device check: a host tensor is refused as such anywhere)
+    ensure_device()
+    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (rows,)):
+        raise _lib.FgcnError(f"fuse_sweep: labels must be contiguous int64 ({rows},) on the device")
+    if torch.is_tensor(candidates) and candidates.is_cuda:
+        cand = candidates.detach()
+        if cand.dtype != torch.float32 or not cand.is_contiguous() or cand.device != device:
+            cand = device_copy(cand, device, torch.float32)
+    else:
+        cand = device_copy(_host_f32(candidates), device)
+    if cand.dim() != 2 or cand.shape[1] != S or cand.shape[0] < 1:
+        raise _lib.FgcnError(f"fuse_sweep: candidates must be (G, {S}) with G >= 1, got {tuple(cand.shape)}")
+    G = cand.shape[0]
+    words = _lib.FUSE_HEADER + 2 * G
+    if counts is None:
+        counts = torch.zeros(words, dtype=torch.int64, device=device)
+    elif not (torch.is_tensor(counts) and counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == words):
+        raise _lib.FgcnError(f"fuse_sweep: counts must be a contiguous int64 ({words},) device tensor for {G} candidates")
+    check(_lib.load().fgcn_fuse_sweep(ctypes.byref(arg), S, mode, cand.data_ptr(), G, labels.data_ptr(), rows, classes, int(k),
+                                      counts.data_ptr(), _stream()), "fgcn_fuse_sweep")
+    return counts[_lib.FUSE_HEADER:].view(G, 2), counts[:_lib.FUSE_HEADER]

@@ -1115,6 +1115,56 @@ int fgcn_imu_enhance(const float* skel, const long long* skel_idx, const float* 
 int fgcn_clip_streams(const float* src, const long long* idx, const int* parents, const int* valid, float* joint, float* bone, float* motion,
                       float* bone_motion, int b, int M, int T, int V, int C, void* stream);
 
+/* Score fusion of separately trained stream models (ops.score_fuse / ops.fuse_sweep, ensemble.StreamEnsemble / ScoreStore; DESIGN.md
+ * section 8k): the 2s-AGCN family reports the accuracy of the weighted sum of its stream models' class scores.
+ *
+ * The fused value.  Streams s = 0 .. S-1, 1 <= S <= FGCN_FUSE_MAX_STREAMS; scores z_s float32 (rows, classes) with row stride
+ * ld_s >= classes; weights w_s float32.  Per row, the transformed scores t_s are
+ *     FGCN_FUSE_NONE:     t_s[c] = z_s[c], the raw logits, as 2s-AGCN adds them;
+ *     FGCN_FUSE_SOFTMAX:  t_s[c] = float32(exp((double)z_s[c] - (double)m) / sum), m = the row's maximum (NaN skipped; -inf for a row
+ *                         of NaN), sum = the float64 sum of those exponentials over the row: formed in float64, rounded ONCE.  The
+ *                         order of that sum's additions is fixed by the implementation (the same in both calls below and from call to
+ *                         call); a restatement that adds in another order agrees to ~1e-16 relative before the rounding, so to one
+ *                         float32 spacing after it.  A row holding a NaN or +inf, or nothing but -inf, is NaN in every element.
+ *     fused[r, c] = float32(acc_S),   acc_0 = +0.0,   acc_(s+1) = acc_s + (double)w_s * (double)t_s[r, c]      in stream order.
+ * A float32 times a float32 is exact in float64, so contracting the product into an fma changes no bit: in mode NONE the result is
+ * defined bit for bit.  Both calls below obtain t_s and fused from ONE device function each, so they cannot disagree.
+ *
+ * fgcn_score_fuse: writes fused into out (rows, classes) with row stride ld_out >= classes; columns [classes, ld_out) are not touched.
+ * One launch, one wave per row, no atomics; two calls give the same bits.  `in` is a HOST pointer; the struct travels by value.
+ *
+ * fgcn_fuse_sweep: for each of the G candidate weight vectors -- candidates (G, S) float32 ON THE DEVICE, row g = w_0 .. w_(S-1); the
+ * struct's `weight` is ignored -- it ADDS to counts (8-byte aligned, 3 + 2 G words of 8 bytes on the device; the caller zeroes it):
+ *     counts[FGCN_FUSE_EXAMPLES], counts[FGCN_FUSE_IGNORED], counts[FGCN_FUSE_INVALID]: the rows by label, once per call, not per candidate;
+ *     counts[FGCN_FUSE_HEADER + 2 g] top-1 hits and counts[FGCN_FUSE_HEADER + 2 g + 1] top-k hits of candidate g.
+ * The float32 fused values are ranked under exactly fgcn_classify_update's rules: NaN sorts above every number and equals NaN; with
+ * y = labels[r], rank(y) = #{j : fused_j > fused_y} + #{j < y : fused_j == fused_y}; a top-k hit is rank(y) < k and a top-1 hit is
+ * rank(y) == 0 (there: pred == y, the first index of the maximum -- the same thing); y == -100 is ignored and every other y outside
+ * [0, classes) is invalid, neither counts for any candidate; the only index derived from a label is clamped first.  So counts of
+ * candidate g equal what fgcn_classify_update counts on fgcn_score_fuse's output with candidate g's weights, exactly, in both transforms.
+ * One workgroup per row: its waves form t_s (one stream per wave at a time) once in LDS as float32, then every lane ranks the row
+ * under one candidate of its own -- the row is read from memory once per pass, not once per candidate.  A pass covers
+ * FGCN_FUSE_PASS candidates, whose counters live in LDS, each owned by one lane, and are added to counts with integer atomics (exact
+ * in any order) at the workgroup's end; G > FGCN_FUSE_PASS runs ceil(G / FGCN_FUSE_PASS) launches inside the call.  No float atomics;
+ * two calls on zeroed counts give the same bits.
+ *
+ * FGCN_E_BADARG before any launch: a null in / out / candidates / labels / counts, or a null scores[s] for s < S; S outside
+ * [1, FGCN_FUSE_MAX_STREAMS]; an unknown transform; rows <= 0; classes outside [1, FGCN_CLS_MAX_CLASSES]; an ld or ld_out < classes;
+ * k outside [1, classes]; G <= 0 or G > FGCN_FUSE_MAX_CANDIDATES; out equal to an input.  FGCN_E_ALIGN: counts not 8-byte aligned. */
+#define FGCN_FUSE_MAX_STREAMS 8
+#define FGCN_FUSE_PASS 2048                  /* candidates whose counters one launch of the sweep holds */
+#define FGCN_FUSE_MAX_CANDIDATES 1048576    /* 2^20: candidates of one fgcn_fuse_sweep call */
+enum fgcn_fuse_transform { FGCN_FUSE_NONE = 0, FGCN_FUSE_SOFTMAX = 1 };
+enum fgcn_fuse_word { FGCN_FUSE_EXAMPLES = 0, FGCN_FUSE_IGNORED = 1, FGCN_FUSE_INVALID = 2, FGCN_FUSE_HEADER = 3 };
+typedef struct FgcnFuseIn {
+    const float* scores[FGCN_FUSE_MAX_STREAMS];   /* device pointers; entries [S, 8) are not read */
+    int ld[FGCN_FUSE_MAX_STREAMS];                /* row strides in floats */
+    float weight[FGCN_FUSE_MAX_STREAMS];          /* fgcn_score_fuse only */
+} FgcnFuseIn;
+int fgcn_score_fuse(const FgcnFuseIn* in, int S, int transform, float* out, int ld_out, int rows, int classes, void* stream);
+int fgcn_fuse_sweep(const FgcnFuseIn* in, int S, int transform, const float* candidates, int G, const long long* labels, int rows,
+                    int classes, int k, unsigned long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
