@@ -278,6 +278,53 @@ def _geometry_sweep(lib):
         assert lib.fgcn_tconv_wgrad_slabs(n, nsplit) >= 1 and lib.fgcn_pw_wgrad_slabs(n, nsplit) >= 1
 
 
+def _cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def test_frame_chunk_heuristics_table(lib):
+    """The frame-chunk heuristics the launchers evaluate on the host, as a table: ops.gram_t_chunk (a hand copy of pick_t_chunk in
+    fgcn_joint.hip: 32 frames per workgroup, halved while B * chunks < 1024, not below 4) gives the chunk count of fgcn_joint_mix_chunks for
+    every B in 1..2048 and T in 1..300; the measured step's three (B, T) pairs and the (B, T) grid of the large-batch kernel tests
+    (tests/test_kernels_gpu.py) map to the chunks those tests claim; fgcn_spatial_tiles is the same rule with a floor of 8;
+    fgcn_spatial_wgrad_chunks aims at 512 workgroups up to B = 32 and at 1024 from B = 33 on, and tuning key 13 replaces that target."""
+    from fusion_gcn_amd import ops
+    chunks = lib.fgcn_joint_mix_chunks
+    for B in range(1, 2049):
+        for T in range(1, 301):
+            c = ops.gram_t_chunk(B, T)
+            if _cdiv(T, c) != chunks(B, T):
+                raise AssertionError((B, T, c, chunks(B, T)))
+    for (B, T), chunk in {(128, 300): 32, (128, 150): 16, (128, 75): 8,                   # the 64-clip step: T = 300 / 150 / 75
+                          (384, 20): 8, (512, 24): 16, (512, 40): 32,                    # the large-batch kernel tests
+                          (32, 300): 8, (32, 150): 4, (2, 300): 4, (3, 9): 4}.items():  # the 16-clip model test, the small kernel tests
+        assert ops.gram_t_chunk(B, T) == chunk, (B, T)
+        assert chunks(B, T) == _cdiv(T, chunk), (B, T)
+        assert lib.fgcn_spatial_tiles(B, T) == B * _cdiv(T, max(chunk, 8)), (B, T)
+    # the chunk is exactly the largest of 32 / 16 / 8 / 4 that leaves 1024 workgroups (or 4): the thresholds from both sides
+    assert ops.gram_t_chunk(512, 33) == 32 and ops.gram_t_chunk(511, 64) == 16 and ops.gram_t_chunk(1024, 1) == 32 and ops.gram_t_chunk(1023, 1) == 4
+
+    def wgrad_chunks(B, T, cin, cout, target):
+        nchunk = max(1, min(_cdiv(target, _cdiv(cin, 32) * _cdiv(cout, 64) * B), _cdiv(T, 4)))
+        return _cdiv(T, _cdiv(T, nchunk))
+    for cin, cout in ((32, 64), (64, 64), (4, 64), (128, 128), (256, 256)):
+        for T in (9, 12, 30, 75, 150, 300):
+            for B in (1, 2, 3, 16, 31, 32, 33, 34, 64, 128):
+                assert lib.fgcn_spatial_wgrad_chunks(B, T, cin, cout) == wgrad_chunks(B, T, cin, cout, 512 if B <= 32 else 1024), (B, T, cin, cout)
+    assert lib.fgcn_spatial_wgrad_chunks(32, 300, 32, 64) == 16 and lib.fgcn_spatial_wgrad_chunks(33, 300, 32, 64) == 30      # 512 -> 1024
+    # the measured step: 75 frames per workgroup at T = 300 (64 -> 64), the whole sample at T = 75 (256 -> 256); the kernel tests: 4 frames
+    assert lib.fgcn_spatial_wgrad_chunks(128, 300, 64, 64) == 4 and lib.fgcn_spatial_wgrad_chunks(128, 75, 256, 256) == 1
+    assert lib.fgcn_spatial_wgrad_chunks(2, 300, 64, 64) == 75 and lib.fgcn_spatial_wgrad_chunks(3, 30, 64, 64) == 8
+    try:
+        for target in (1, 24, 100000):
+            assert lib.fgcn_set_tuning(13, target) == 0
+            for B, T, cin, cout in ((3, 30, 64, 64), (2, 12, 128, 128), (2, 9, 4, 64), (1, 75, 256, 256), (33, 300, 32, 64)):
+                assert lib.fgcn_spatial_wgrad_chunks(B, T, cin, cout) == wgrad_chunks(B, T, cin, cout, target), (target, B, T, cin, cout)
+            assert lib.fgcn_spatial_wgrad_chunks(3, 30, 64, 64) == {1: 1, 24: 4, 100000: 8}[target]
+    finally:
+        assert lib.fgcn_set_tuning(13, 0) == 0
+
+
 def test_host_code_under_sanitizers(lib):
     """the launchers' HOST code (argument validation, tile geometry, FastDiv tables, slab / segment counts, the
     per-thread contexts) built with -fsanitize=address,undefined (fusion_gcn_amd.build.build_host_asan; the gfx950 code objects are the

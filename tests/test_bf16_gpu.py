@@ -13,6 +13,7 @@ from oracle import filler
 
 import guarded
 from guarded import guarded_allocations  # noqa: F401  (the fixture)
+from wgrad_splits import WGRAD_SPLIT_SHAPES, assert_shares_iterate, force_row_splits
 
 # every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
@@ -369,6 +370,37 @@ def test_halo_conv_and_weight_gradient_from_bfloat16_tensors(B, T, V, C, N, kt, 
     # ... and the values are the convolution of the rounded operands (the f32 call is pinned to float64 by the tests above)
     want = conv_ref(g32.double().cpu(), bf(wt[..., 0].permute(2, 1, 0).cpu()), kt, s, Tp, bias.double().cpu())
     assert rel_l2(outs[1][0].cpu().numpy(), want.numpy()) < TOL
+
+
+@pytest.mark.parametrize("B,T,V,K,N,kt,s", [WGRAD_SPLIT_SHAPES[0], WGRAD_SPLIT_SHAPES[2]])
+def test_weight_gradient_row_splits_from_bfloat16_tensors(B, T, V, K, N, kt, s, monkeypatch):
+    """fgcn_tconv_wgrad with half_mask 3 (both operands bfloat16 tensors) with 1, 2 and 3 row splits forced, so that a workgroup walks
+    several stages and a share crosses from one sample into the next (tests/wgrad_splits.py): against the float64 sums of the rounded
+    operands at the weight-gradient tolerance of test_weight_gradients_bf16, bit for bit against the call on f32 tensors holding the
+    same values, bitwise reproducible, and the library's own split count to rounding."""
+    from fusion_gcn_amd import _lib, ops
+    lib = _lib.load()
+    pad = (kt - 1) // 2
+    a16, g16 = gpu(rnd(B, T, V, K, seed=8)).to(torch.bfloat16), gpu(rnd(B, T, V, N, seed=9)).to(torch.bfloat16)
+    a32, g32 = a16.float(), g16.float()
+    ab, gb = a32.double().cpu(), g32.double().cpu()
+    want = torch.zeros(kt, K, N, dtype=torch.float64)
+    for j in range(kt):
+        for to in range(T):
+            if 0 <= to + j - pad < T:
+                want[j] += torch.einsum("bvk,bvn->kn", ab[:, to + j - pad], gb[:, to])
+    assert_shares_iterate(lib, "bf16", False, B, T * V, N)
+    default = ops.tconv_wgrad(a16, g16, taps=kt, stride=s)
+    tiles = ((K + 31) // 32) * ((N + 127) // 128 if N > 64 else 1)
+    for nsplit in (1, 2, 3):
+        seen = []
+        with monkeypatch.context() as m:
+            force_row_splits(m, lib, ops, nsplit, tiles, tiles, seen)
+            got, again, from32 = ops.tconv_wgrad(a16, g16, taps=kt, stride=s), ops.tconv_wgrad(a16, g16, taps=kt, stride=s), ops.tconv_wgrad(a32, g32, taps=kt, stride=s)
+        assert seen == [("taps", nsplit)] * 3, seen
+        assert rel_l2(got.cpu().numpy(), want.numpy()) < 1e-4, nsplit
+        assert torch.equal(got, again) and torch.equal(got, from32), nsplit
+        assert rel_l2(got.cpu().numpy(), default.cpu().numpy()) < TOL, nsplit
 
 
 def test_model_step_is_bit_identical_with_half_precision_conv_operands():

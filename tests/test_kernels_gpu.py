@@ -9,6 +9,7 @@ from conftest import rel_l2
 
 import guarded
 from guarded import guarded_allocations  # noqa: F401  (the fixture)
+from wgrad_splits import WGRAD_SPLIT_SHAPES, assert_shares_iterate, force_row_splits
 
 # every test runs on guarded allocations: NaN around each tensor the host layer creates, margins verified at teardown (tests/guarded.py)
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_allocations")]
@@ -1299,3 +1300,317 @@ def test_spatial_stage_with_batchnorm_shortcut_and_relu_in_one_kernel(V, T, cin,
     yg, _ = ops.spatial_fwd_tile(to_gpu(x), to_gpu(a), w3, to_gpu(bias), Cin=cin, Cout=cout, stats=False)
     two = ops.bn_act(yg, to_gpu(vec), res, rv, relu=True)
     assert rel_l2(g.cpu().numpy(), two.cpu().numpy()) < 2e-6
+
+
+# ---- the per-workgroup loop counts of the measured step -----------------------------------------------------------------------------
+# The launchers size a workgroup's share from the batch: at the shapes above every wave or workgroup does one unit of work, at the 64-clip
+# step (B = 128) the same kernels loop 4 to 59 times.  The tests below reach those loop counts at the smallest tensors that can: a large
+# batch of tiny frames where the library picks the chunk, the Python layer's own chunk where it passes one, tuning key 13, forced row splits.
+LOOP_GRID = [(384, 20, 8), (512, 24, 16), (512, 40, 32)]      # (B, T, frames per workgroup): 3 / 2 / 2 chunks, the last one 4 / 8 / 8 frames
+
+
+def rnd_dev(*shape, seed=0, scale=1.0):
+    """``rnd`` for the large-batch tests: seeded float32 normal numbers drawn on the device (distinct per sample and frame), guarded"""
+    g = torch.Generator(device=dev()).manual_seed(seed)
+    return guarded.put(torch.randn(*shape, generator=g, device=dev()) * scale, device=dev())
+
+
+def filled(shape, value):
+    return guarded.put(torch.full(shape, value, device=dev()), device=dev())
+
+
+def assert_frame_chunk(B, T, chunk):
+    """the geometry a test means to reach, through the exported host functions: a change of the heuristic must not turn it back into a
+    one-iteration test unnoticed"""
+    from fusion_gcn_amd import _lib
+    lib, nchunk = _lib.load(), -(-T // chunk)
+    assert lib.fgcn_joint_mix_chunks(B, T) == nchunk and lib.fgcn_spatial_tiles(B, T) == B * nchunk, (B, T, chunk)
+
+
+def err_by_samples(got, ref, step=64):
+    """rel-L2 of a device tensor against ``ref(b0, b1)``, the float64 reference of samples [b0, b1) formed on the device"""
+    num = torch.zeros((), dtype=torch.float64, device=got.device)
+    den = torch.zeros_like(num)
+    for b0 in range(0, got.shape[0], step):
+        mine = got[b0:b0 + step]
+        want = ref(b0, b0 + mine.shape[0]).reshape(mine.shape)
+        num += ((mine.double() - want) ** 2).sum()
+        den += (want ** 2).sum()
+    return float((num / den).sqrt())
+
+
+def sum_by_samples(ref, B, step=64):
+    """float64 column sums of ``ref`` over all samples"""
+    return sum(ref(b0, min(b0 + step, B)).flatten(0, -2).sum(0) for b0 in range(0, B, step))
+
+
+@pytest.mark.math_modes("f32")                  # (fgcn_joint_mix / fgcn_joint_mix_vec do not read the math mode)
+@pytest.mark.parametrize("B,T,chunk,cin", [(b, t, c, w) for b, t, c in LOOP_GRID for w in (4, 16, 64) if w < 64 or c == 8])
+def test_joint_mix_at_the_frame_chunks_of_the_full_step(B, T, chunk, cin):
+    """block.mix_agg / mix_dx / mix_demb with 8, 16 and 32 frames per workgroup -- the waves of a full chunk run their frame loop 2, 4 and
+    8 times, those of the ragged last chunk once or twice -- against float64 einsums formed on the device: 4 channels (a narrow group of
+    the channel-group kernel, and the dword kernel through its own item tables), 16 (one channel per lane; the dword kernel's embedding
+    gradient), 64 (two per lane); per-sample and shared matrices, dx with and without accumulation, and the loop-carried results:
+    max |agg| (``amax_out``) and the column sums of demb."""
+    from fusion_gcn_amd import block, ops
+    assert_frame_chunk(B, T, chunk)
+    V = 25
+    x, a = rnd_dev(B, T, V, cin, seed=600), rnd_dev(B, 3, V, V, seed=601, scale=0.3)
+    x64, a64 = x.double(), a.double()
+
+    def mats64(shared, b0, b1):
+        return a64[:1].expand(b1 - b0, -1, -1, -1) if shared else a64[b0:b1]
+    for shared in (False, True):
+        mats = a[:1] if shared else a
+        want = lambda b0, b1: torch.einsum("btvc,bkvw->btwkc", x64[b0:b1], mats64(shared, b0, b1))      # noqa: E731
+        agg, slot = filled((B, T, V, 3 * cin), 7.0), torch.zeros(1, device=dev(), dtype=torch.int32)
+        assert block.mix_agg(x, agg, mats, cin, amax_out=slot)
+        assert err_by_samples(agg, want) < FWD_TOL, shared
+        assert float(slot.view(torch.float32)) == float(agg.abs().max())
+        if cin == 4:
+            agg = filled((B, T, V, 3 * cin), 7.0)
+            ops.joint_mix(x, agg, mats, block.spec_agg(cin), in_channels=cin, out_channels=3 * cin)
+            assert err_by_samples(agg, want) < FWD_TOL, shared
+    dagg, base = rnd_dev(B, T, V, 3 * cin, seed=602), rnd_dev(B, T, V, cin, seed=603)
+    d64, base64 = dagg.double().view(B, T, V, 3, cin), base.double()
+    for shared, acc in ((False, True), (False, False), (True, False)):
+        mats = a[:1] if shared else a
+        want = lambda b0, b1: torch.einsum("btwkc,bkvw->btvc", d64[b0:b1], mats64(shared, b0, b1)) + (base64[b0:b1] if acc else 0)   # noqa: E731
+        dx = guarded.put(base, device=dev())
+        block.mix_dx(dagg, dx, mats, cin, accumulate=acc)
+        assert err_by_samples(dx, want) < FWD_TOL, (shared, acc)
+        if cin == 4:
+            dx = guarded.put(base, device=dev())
+            ops.joint_mix(dagg, dx, mats, block.spec_dx(cin), in_channels=3 * cin, out_channels=cin, accumulate=acc)
+            assert err_by_samples(dx, want) < FWD_TOL, (shared, acc)
+    del dagg, d64, base, base64
+    ic = cin
+    emb, ds = rnd_dev(B, T, V, 6 * ic, seed=604), rnd_dev(B, 3, V, V, seed=605)
+    ds64 = ds.double()
+
+    def want_demb(b0, b1):
+        e64 = emb[b0:b1].double().view(b1 - b0, T, V, 3, 2, ic)          # (64 samples at a time: the widest case is a 295 MB tensor)
+        dtheta = torch.einsum("bkvw,btwke->btvke", ds64[b0:b1], e64[..., 1, :])
+        dphi = torch.einsum("bkvw,btvke->btwke", ds64[b0:b1], e64[..., 0, :])
+        return torch.stack([dtheta, dphi], dim=4).reshape(b1 - b0, T, V, 6 * ic)
+    demb = filled((B, T, V, 6 * ic), 3.0)
+    sums = block.mix_demb(emb, demb, ds, ic)
+    assert err_by_samples(demb, want_demb) < FWD_TOL
+    e_sums = rel_l2(sums.cpu().numpy(), sum_by_samples(want_demb, B).cpu().numpy())
+    print(f"mix_demb B={B} T={T} ic={ic}: column sums over {B * T * V} rows {e_sums:.2e}")
+    assert e_sums < RED_TOL
+    if ic == 16:
+        demb = filled((B, T, V, 6 * ic), 3.0)
+        ops.joint_mix(emb, demb, ds, block.spec_demb(ic), in_channels=6 * ic, out_channels=6 * ic)
+        assert err_by_samples(demb, want_demb) < FWD_TOL
+
+
+@pytest.mark.math_modes("f32")                  # (fgcn_joint_mix_wide does not read the math mode)
+@pytest.mark.parametrize("B,T,chunk", LOOP_GRID[1:])
+def test_joint_mix_wide_at_the_frame_chunks_of_the_full_step(B, T, chunk):
+    """The joint mix of a 40-joint graph (ops.joint_mix_wide through block.mix_agg / mix_dx, 8 channels) with 16 and 32 frames per
+    workgroup against float64 einsums formed on the device; per-sample and shared matrices, dx with and without accumulation."""
+    from fusion_gcn_amd import block
+    assert_frame_chunk(B, T, chunk)
+    V, cin = 40, 8
+    x, a = rnd_dev(B, T, V, cin, seed=620), rnd_dev(B, 3, V, V, seed=621, scale=0.3)
+    dagg, base = rnd_dev(B, T, V, 3 * cin, seed=622), rnd_dev(B, T, V, cin, seed=623)
+    x64, a64, d64, base64 = x.double(), a.double(), dagg.double().view(B, T, V, 3, cin), base.double()
+    for shared, acc in ((False, True), (True, False)):
+        mats = a[:1] if shared else a
+        m64 = lambda b0, b1: a64[:1].expand(b1 - b0, -1, -1, -1) if shared else a64[b0:b1]      # noqa: E731
+        agg = filled((B, T, V, 3 * cin), 7.0)
+        assert not block.mix_agg(x, agg, mats, cin)
+        assert err_by_samples(agg, lambda b0, b1: torch.einsum("btvc,bkvw->btwkc", x64[b0:b1], m64(b0, b1))) < FWD_TOL, shared
+        dx = guarded.put(base, device=dev())
+        block.mix_dx(dagg, dx, mats, cin, accumulate=acc)
+        want = lambda b0, b1: torch.einsum("btwkc,bkvw->btvc", d64[b0:b1], m64(b0, b1)) + (base64[b0:b1] if acc else 0)   # noqa: E731
+        assert err_by_samples(dx, want) < FWD_TOL, (shared, acc)
+
+
+def spatial_fwd_at_frame_chunk(B, T, chunk, cin, cout):
+    from fusion_gcn_amd import ops
+    assert_frame_chunk(B, T, chunk)
+    V = 25
+    x, a = rnd_dev(B, T, V, cin, seed=610), rnd_dev(B, 3, V, V, seed=611, scale=0.3)
+    wd, bias = to_gpu(rnd(3, cin, cout, seed=612, scale=(3 * cin) ** -0.5)), to_gpu(rnd(cout, seed=613))
+    x64, a64, w64, b64 = x.double(), a.double(), wd.double(), bias.double()
+    want = lambda b0, b1: torch.einsum("btwkc,kco->btwo", torch.einsum("btvc,bkvw->btwkc", x64[b0:b1], a64[b0:b1]), w64) + b64   # noqa: E731
+    y, part = ops.spatial_fwd(x, a, ops.pack_spatial(wd.reshape(3 * cin, cout), cin), bias, Cin=cin, Cout=cout, stats=True)
+    assert part.shape[0] == B * -(-T // chunk)
+    assert err_by_samples(y, want) < FWD_TOL
+    s = part.double().sum(0).cpu()
+    e1 = rel_l2(s[0].numpy(), sum_by_samples(want, B).cpu().numpy())
+    e2 = rel_l2(s[1].numpy(), sum_by_samples(lambda b0, b1: want(b0, b1) ** 2, B).cpu().numpy())
+    print(f"spatial_fwd B={B} T={T} {cin}->{cout}: statistics over {B * T * V} rows {e1:.2e} {e2:.2e}")
+    assert e1 < RED_TOL and e2 < RED_TOL
+
+
+@pytest.mark.math_modes("f32")                  # (inputs narrower than 32 channels: the exact-f32 kernel in every mode)
+@pytest.mark.parametrize("B,T,chunk", LOOP_GRID)
+def test_spatial_forward_of_the_network_input_at_the_frame_chunks_of_the_full_step(B, T, chunk):
+    """ops.spatial_fwd 4 -> 64 with its BatchNorm partial sums, 8 / 16 / 32 frames per workgroup, against float64 formed on the device"""
+    spatial_fwd_at_frame_chunk(B, T, chunk, 4, 64)
+
+
+@pytest.mark.parametrize("B,T,chunk,cin,cout", [(b, t, c, 32, 64) for b, t, c in LOOP_GRID] + [(512, 24, 16, 64, 128)])
+def test_spatial_forward_at_the_frame_chunks_of_the_full_step(B, T, chunk, cin, cout):
+    """ops.spatial_fwd 32 -> 64 and 64 -> 128 (bf16x3: the two-frames-per-wave split kernel, whose ``st[...] +=`` statistics are carried
+    across the frame loop) with 8 / 16 / 32 frames per workgroup: y and the summed statistic partials against float64 formed on the device"""
+    spatial_fwd_at_frame_chunk(B, T, chunk, cin, cout)
+
+
+def gram_by_chunks(x, d, chunk):
+    """(B, nchunk, 3, V, V) float64: sum over the frames of each chunk of x[t]^T d[t, :, k]; x (B,T,V,w), d (B,T,V,3,w)"""
+    T = x.shape[1]
+    return torch.stack([torch.einsum("btvc,btwkc->bkvw", x[:, t0:t0 + chunk], d[:, t0:t0 + chunk]) for t0 in range(0, T, chunk)], dim=1)
+
+
+@pytest.mark.math_modes("f32")                  # (fgcn_joint_gram / _wide and the adjacency softmax do not read the math mode)
+@pytest.mark.parametrize("T", [37, 70])
+@pytest.mark.parametrize("chunk", [8, 16, 32])
+def test_joint_gram_at_the_frame_chunks_of_the_full_step(chunk, T, monkeypatch):
+    """ops.joint_gram with the 8 / 16 / 32 frames per workgroup that ops.gram_t_chunk picks at B = 128 (set here by replacing it; a ragged
+    last chunk: at T = 37 and 16 frames the waves run 4 / 4 / 2 rounds, one wave of the last chunk a single one): the three-item form
+    (joint_gram3_kernel with its next-frame prefetch), the generic form and the 40-joint form, 16 and 64 channels, every chunk's partial
+    matrix against the float64 sum over that chunk's frames, exact zeros in the padding, and the three-item partials through the
+    adjacency softmax and its backward (they read the chunk count from the partials' shape)."""
+    from fusion_gcn_amd import ops
+    monkeypatch.setattr(ops, "gram_t_chunk", lambda B, T: chunk)
+    B, nchunk = 2, -(-T // chunk)
+    for V in (25, 27, 40):
+        side = 64 if V > 32 else 32
+        for w in (16, 64):
+            emb = rnd(B, T, V, 6 * w, seed=630 + V + w)
+            e = emb.reshape(B, T, V, 3, 2, w)
+            want = torch.stack([torch.einsum("btvke,btwke->bkvw", e[:, t0:t0 + chunk, ..., 0, :], e[:, t0:t0 + chunk, ..., 1, :])
+                                for t0 in range(0, T, chunk)], dim=1)
+            part = ops.joint_gram(to_gpu(emb), to_gpu(emb), [(2 * k * w, (2 * k + 1) * w, w) for k in range(3)])
+            assert tuple(part.shape) == (B, nchunk, 3, side, side)
+            assert rel_l2(part[..., :V, :V].cpu().numpy(), want.numpy()) < RED_TOL, (V, w)
+            assert float(part[..., V:, :].abs().max()) == 0.0 and float(part[..., :, V:].abs().max()) == 0.0
+            score = (want.sum(1) / (w * T)).requires_grad_(True)
+            adj, d_a = rnd(3, V, V, seed=631, scale=0.2), rnd(B, 3, V, V, seed=632)
+            c_want = torch.softmax(score, dim=-2)
+            c, a_hat = ops.adj_softmax_fwd(part, 1.0 / (w * T), to_gpu(adj), B)
+            assert rel_l2(c.cpu().numpy(), c_want.detach().numpy()) < 1e-5 and rel_l2(a_hat.cpu().numpy(), (c_want.detach() + adj).numpy()) < 1e-5
+            (ds_want,) = torch.autograd.grad((c_want * d_a).sum(), score)
+            fake = torch.zeros(B, nchunk, 3, side, side, dtype=torch.float64)
+            for i in range(nchunk):                                  # dA^ spread unevenly over the chunks
+                fake[:, i, :, :V, :V] = d_a * (2.0 * (i + 1) / (nchunk * (nchunk + 1)))
+            d_a_hat, d_s = ops.adj_softmax_bwd(to_gpu(fake), 1.0 / (w * T), c, V)
+            assert rel_l2(d_a_hat.cpu().numpy(), d_a.numpy()) < 1e-6 and rel_l2(d_s.cpu().numpy(), (ds_want / (w * T)).numpy()) < 2e-5
+            # two different tensors, the first operand shared by the three items (dA^_k = x^T dagg_k): the generic kernel
+            x, dagg = rnd(B, T, V, w, seed=633 + V), rnd(B, T, V, 3 * w, seed=634 + w)
+            part = ops.joint_gram(to_gpu(x), to_gpu(dagg), [(0, k * w, w) for k in range(3)])
+            assert tuple(part.shape) == (B, nchunk, 3, side, side)
+            assert rel_l2(part[..., :V, :V].cpu().numpy(), gram_by_chunks(x, dagg.reshape(B, T, V, 3, w), chunk).numpy()) < RED_TOL, (V, w)
+
+
+@pytest.mark.math_modes("f32", "bf16x3")        # (f16x2 runs the bf16x3 kernel)
+@pytest.mark.parametrize("T", [37, 70])
+@pytest.mark.parametrize("chunk", [8, 16, 32])
+def test_joint_dagg_at_the_frame_chunks_of_the_full_step(chunk, T, monkeypatch):
+    """ops.joint_dagg with 8 / 16 / 32 frames per workgroup (ops.gram_t_chunk replaced; ragged last chunk): dx with and without
+    accumulation, with and without the gated shortcut gradients, and every chunk's partial gram against the float64 sum over that
+    chunk's frames.  (The kernel serves graphs of up to 32 joints: V = 25 and 27.)"""
+    from fusion_gcn_amd import ops
+    monkeypatch.setattr(ops, "gram_t_chunk", lambda B, T: chunk)
+    B, nchunk = 2, -(-T // chunk)
+    for V in (25, 27):
+        for C in (16, 64):
+            x, a = rnd(B, T, V, C, seed=640 + V), rnd(B, 3, V, V, seed=641, scale=0.3)
+            dagg, base = rnd(B, T, V, 3 * C, seed=642 + C), rnd(B, T, V, C, seed=643)
+            d4 = dagg.reshape(B, T, V, 3, C)
+            want_dx, want_g = torch.einsum("btwkc,bkvw->btvc", d4, a), gram_by_chunks(x, d4, chunk)
+            ident = guarded.to(torch.stack([torch.zeros(C), torch.ones(C), torch.ones(C), torch.zeros(C)]).float(), dev())
+            gated, want_gate = [], torch.zeros_like(want_dx)
+            for i in range(2):
+                e, pre = rnd(B, T, V, C, seed=644 + i), rnd(B, T, V, C, seed=646 + i)
+                _, mask = ops.bn_act(to_gpu(pre), ident, relu=True, sign_mask=True)
+                want_gate = want_gate + e * (pre.float() > 0)
+                gated.append((to_gpu(e), mask))
+            for acc, n_gated in ((False, 0), (True, 0), (False, 2), (True, 2)):
+                dx = to_gpu(base)
+                part = ops.joint_dagg(to_gpu(x), to_gpu(dagg), to_gpu(a), dx, accumulate=acc, gated=gated[:n_gated])
+                want = want_dx + (base if acc else 0) + (want_gate if n_gated else 0)
+                assert rel_l2(dx.cpu().numpy(), want.numpy()) < FWD_TOL, (V, C, acc, n_gated)
+                assert tuple(part.shape) == (B, nchunk, 3, 32, 32)
+                assert rel_l2(part[..., :V, :V].cpu().numpy(), want_g.numpy()) < RED_TOL, (V, C, acc, n_gated)
+                assert float(part[..., V:, :].abs().max()) == 0.0
+
+
+@pytest.mark.math_modes("f32", "bf16x3")        # (f16x2 runs the bf16x3 kernel)
+@pytest.mark.parametrize("V,T,cin,cout,B", [(25, 30, 64, 64, 3), (27, 12, 128, 128, 2), (22, 9, 4, 64, 2), (25, 75, 256, 256, 1)])
+def test_spatial_wgrad_with_many_frames_per_workgroup(V, T, cin, cout, B):
+    """ops.spatial_wgrad with tuning key 13 (the target workgroup count) at 1 -- one workgroup per sample and tile walks all T frames, up
+    to 19 rounds per wave -- and at a middle value that gives every sample two chunks, against the float64 einsum of
+    test_spatial_wgrad_fused_agg_recompute: per-sample and shared adjacency, bitwise reproducible, the default segmentation to rounding."""
+    from fusion_gcn_amd import _lib, ops
+    lib = _lib.load()
+    x, a, dy = rnd(B, T, V, cin, seed=95), rnd(B, 3, V, V, seed=96, scale=0.3), rnd(B, T, V, cout, seed=97)
+    want = torch.einsum("btwkc,btwo->kco", torch.einsum("btvc,bkvw->btwkc", x, a), dy).reshape(3 * cin, cout)
+    want1 = torch.einsum("btwkc,btwo->kco", torch.einsum("btvc,kvw->btwkc", x, a[0]), dy).reshape(3 * cin, cout)
+    default = ops.spatial_wgrad(to_gpu(x), to_gpu(dy), to_gpu(a))
+    tiles = -(-cin // 32) * -(-cout // 64)
+    for target, nchunk in ((1, 1), (2 * tiles * B, 2)):
+        try:
+            assert lib.fgcn_set_tuning(13, target) == 0
+            assert lib.fgcn_spatial_wgrad_chunks(B, T, cin, cout) == nchunk
+            got = ops.spatial_wgrad(to_gpu(x), to_gpu(dy), to_gpu(a))
+            again = ops.spatial_wgrad(to_gpu(x), to_gpu(dy), to_gpu(a))
+            shared = ops.spatial_wgrad(to_gpu(x), to_gpu(dy), to_gpu(a[:1]))
+        finally:
+            assert lib.fgcn_set_tuning(13, 0) == 0
+        assert tuple(got.shape) == (1, 3 * cin, cout)
+        assert rel_l2(got[0].cpu().numpy(), want.numpy()) < RED_TOL, target
+        assert torch.equal(got, again)
+        assert rel_l2(shared[0].cpu().numpy(), want1.numpy()) < RED_TOL, target
+        assert rel_l2(got.cpu().numpy(), default.cpu().numpy()) < RED_TOL, target
+
+
+# ---- weight-gradient row splits (shapes and geometry: tests/wgrad_splits.py) ----------------------------------------------------------
+@pytest.mark.parametrize("B,T,V,K,N,kt,s", WGRAD_SPLIT_SHAPES)
+def test_weight_gradient_row_splits(B, T, V, K, N, kt, s, monkeypatch, fgcn_math):
+    """ops.tconv_wgrad (all taps in one pass), the 1x1 multi-accumulator form and the per-tap ops.rows_wgrad with 1, 2 and 3 row splits
+    forced: a workgroup then walks several stages -- the prefetch of the next stage, the refill of the tap window at the first stage of a
+    sample inside a share, its extension from stage to stage -- where the library's own split count gives it one or two.  Against
+    float64; bitwise reproducible; the default split count to rounding.  Math mode f16x2 passes the operands' maxima, so its own
+    product form runs."""
+    from fusion_gcn_amd import _lib, ops
+    lib = _lib.load()
+    Tg = (T - 1) // s + 1
+    a, g = rnd(B, T, V, K, seed=650), rnd(B, Tg, V, N, seed=651)
+    ag, gg = to_gpu(a), to_gpu(g)
+    want = torch.zeros(kt, K, N, dtype=torch.float64)
+    taps, ta, tb, tc, td = ops.conv_tmap(kt, s)
+    for to in range(Tg):
+        for j in range(taps):
+            num = to * ta + j * tb + tc
+            if num >= 0 and num % td == 0 and num // td < T:
+                want[j] += torch.einsum("bvk,bvn->kn", a[:, num // td], g[:, to])
+    want_pw = torch.einsum("btvk,btvn->kn", a[:, ::s][:, :Tg], g).reshape(1, K, N)
+    amax = None
+    if fgcn_math == "f16x2":
+        slots = torch.zeros(2, device=dev(), dtype=torch.int32)
+        slots[0], slots[1] = torch.tensor(float(ag.abs().max())).view(torch.int32), torch.tensor(float(gg.abs().max())).view(torch.int32)
+        amax = (slots[0:1], slots[1:2])
+    tn = (N + 127) // 128 if N > 64 else 1
+    tiles_t, tiles_p = ((K + 31) // 32) * tn, -(-K // (32 * lib.fgcn_pw_wgrad_chunks(K, N))) * tn
+    forms = {"1x1": (lambda: ops.rows_wgrad(ag, gg, K=K, N=N, tmap=(1, s, 0, 0, 1), wide=True, amax=amax), want_pw),
+             "rows": (lambda: ops.rows_wgrad(ag, gg, K=K, N=N, tmap=ops.conv_tmap(kt, s), wide=False), want)}
+    if kt > 1:
+        forms["taps"] = (lambda: ops.tconv_wgrad(ag, gg, taps=kt, stride=s, all_taps=True, amax=amax), want)
+        assert_shares_iterate(lib, fgcn_math, False, B, Tg * V, N)
+    assert_shares_iterate(lib, fgcn_math, True, B, Tg * V, N)
+    default = {name: run() for name, (run, _) in forms.items()}
+    for nsplit in (1, 2, 3):
+        for name, (run, ref) in forms.items():
+            seen = []
+            with monkeypatch.context() as m:
+                force_row_splits(m, lib, ops, nsplit, tiles_t, tiles_p, seen)
+                got, again = run(), run()
+            assert seen and all(what == (name, nsplit) for what in seen), (name, nsplit, seen)
+            assert rel_l2(got.cpu().numpy().reshape(ref.shape), ref.numpy()) < RED_TOL, (name, nsplit)
+            assert torch.equal(got, again), (name, nsplit)
+            assert rel_l2(got.cpu().numpy(), default[name].cpu().numpy()) < RED_TOL, (name, nsplit)

@@ -1,6 +1,6 @@
 """Direct tests of entry points that so far ran only inside whole-model comparisons: fgcn_transpose (ops.transpose / transpose_into),
-fgcn_row_softmax_fwd / _bwd, fgcn_reduce_multi in its two per-item forms (ops.ReduceBatch, ops._reduce_slabs, ops.reduce_sum) and the tails of
-ops.group_mean / ops.col_sum -- against float64 torch, in math mode f32, on guarded allocations (tests/guarded.py): every input and output has
+fgcn_row_softmax_fwd / _bwd, fgcn_reduce_multi in its two per-item forms (ops.ReduceBatch, ops._reduce_slabs, ops.reduce_sum), the tails of
+ops.group_mean / ops.col_sum, and the elementwise reductions past the 1024-tile cap of fgcn_elem_tiles -- against float64 torch, in math mode f32, on guarded allocations (tests/guarded.py): every input and output has
 NaN in front of its first and behind its last element, and the margins are verified at teardown."""
 import pytest
 import torch
@@ -277,3 +277,76 @@ def test_col_sum_tails(rows, ld, C, coff):
     err = rel_l2(got.cpu().numpy(), x[:, coff:coff + C].double().sum(0).numpy())
     print(f"col_sum rows={rows} ld={ld} C={C} coff={coff}: {err:.2e}")
     assert err < RED_TOL
+
+
+# ---- the elementwise reductions past the tile cap --------------------------------------------------------------------------------------------
+def bn_vec(C, seed):
+    """(4, C) BatchNorm vector as fgcn_bn_finalize lays it out: mean, rstd, scale = gamma * rstd, shift = beta - mean * scale"""
+    mean, rstd = rnd(C, seed=seed) * 0.3, rnd(C, seed=seed + 1).abs() + 0.5
+    gamma, beta = rnd(C, seed=seed + 2).abs() + 0.5, rnd(C, seed=seed + 3) * 0.3
+    return torch.stack([mean, rstd, gamma * rstd, beta - mean * gamma * rstd])
+
+
+@pytest.mark.parametrize("rows,C", [(65537, 4), (65537, 12), (65537, 64), (70001, 4), (70001, 12), (70001, 64), (200000, 4), (200000, 12)])
+def test_elementwise_reductions_past_the_tile_cap(rows, C):
+    """fgcn_elem_tiles gives 64 rows per tile up to 1024 tiles and ceil(rows / 1024) rows per tile beyond: col_sum_kernel, the bn_act
+    backward reduce (gate from the sign image where rows * C is a multiple of 8, from the output tensor else; the three shortcut kinds; a
+    full-size and a per-group gradient whose groups of 50 rows end inside the tiles) and fgcn_bn_bwd_reduce_ld then walk 65 .. 196 rows
+    per tile where the other tests stop at 64.  At 70001 rows the tiles 1015 .. 1023 hold no row and must still write zero partials: the
+    partial buffers are guarded allocations (NaN until written), so a tile that is skipped fails the comparison.  Against float64 sums."""
+    from fusion_gcn_amd import _lib, ops
+    lib = _lib.load()
+    per_tile = -(-rows // 1024)
+    assert lib.fgcn_elem_tiles(rows) == 1024 and per_tile > 64
+    if rows == 70001:
+        assert 1023 * per_tile > rows                       # trailing tiles without a row
+    x = rnd(rows, C + 8, seed=rows + C) + 0.25
+    xg = put(x)
+    for name, got, want in (("all", ops.col_sum(xg, C + 8), x.double().sum(0)), ("window", ops.col_sum(xg, C, 4), x[:, 4:4 + C].double().sum(0))):
+        err = rel_l2(got.cpu().numpy(), want.numpy())
+        print(f"col_sum {name} rows={rows} C={C}: {err:.2e}")
+        assert err < RED_TOL
+    a, b, dout = rnd(rows, C, seed=rows + 1) * 1.7 + 0.3, rnd(rows, C, seed=rows + 2), rnd(rows, C, seed=rows + 3) + 0.25
+    vec_a, vec_b = bn_vec(C, 900), bn_vec(C, 910)
+    a_hat, b_hat = (a.double() - vec_a[0].double()) * vec_a[1].double(), (b.double() - vec_b[0].double()) * vec_b[1].double()
+    ag, bg, dg, vag, vbg = put(a), put(b), put(dout), put(vec_a), put(vec_b)
+    groups = [0] + ([50] if rows % 50 == 0 else [])         # (65537 and 70001 are primes: only 200000 rows divide into groups)
+    assert groups == [0] or per_tile % 50                   # the groups end inside the tiles
+    for res_mode in (0, 1, 2):
+        rb, rvb = (bg if res_mode else None), (vbg if res_mode == 2 else None)
+        out, mask = ops.bn_act(ag, vag, rb, rvb, relu=True, sign_mask=True)
+        assert (mask is not None) == ((rows * C) % 8 == 0)
+        gate = (out.cpu() > 0).double()
+        for grp in groups:
+            d = dout[:rows // grp] if grp else dout
+            dp = (d.double().repeat_interleave(grp, dim=0) if grp else d.double()) * gate
+            want = torch.stack([dp.sum(0), (dp * a_hat).sum(0), (dp * b_hat).sum(0)])[:3 if res_mode == 2 else 2]
+            _, _, sums = ops.bn_act_bwd(put(d) if grp else dg, None if mask is not None else out, ag, vag, rb, rvb, res_mode=res_mode, relu=True,
+                                        train=True, sign_mask=mask, grp_rows=grp)
+            err = rel_l2(sums[:want.shape[0]].cpu().numpy(), want.numpy())
+            print(f"bn_act_bwd_reduce rows={rows} C={C} res_mode={res_mode} grp_rows={grp}: {err:.2e}")
+            assert err < RED_TOL, (res_mode, grp)
+    wide = rnd(rows, C + 8, seed=rows + 4) + 0.25
+    _, sums = ops.bn_bwd_window(put(wide), 4, ag, vag, train=True)
+    dw = wide[:, 4:4 + C].double()
+    err = rel_l2(sums[:2].cpu().numpy(), torch.stack([dw.sum(0), (dw * a_hat).sum(0)]).numpy())
+    print(f"bn_bwd_reduce_ld rows={rows} C={C}: {err:.2e}")
+    assert err < RED_TOL
+
+
+@pytest.mark.parametrize("G,R,pool_splits,mean_splits", [(2, 4096, 64, 32), (512, 256, 2, 1)])
+def test_pooling_row_splits(G, R, pool_splits, mean_splits):
+    """ops.bn_act_pool / ops.group_mean with the largest split counts of their heuristics (64 and 32 workgroups per group: two long
+    groups) and with many short groups (two splits and one), asserted through the exported split functions; against float64 means"""
+    from fusion_gcn_amd import _lib, ops
+    lib, C = _lib.load(), 16
+    assert lib.fgcn_bn_act_pool_splits(G, R) == pool_splits and lib.fgcn_group_mean_splits(G, R) == mean_splits
+    a, b, vec = rnd(G, R, C, seed=G + R) + 0.2, rnd(G, R, C, seed=G + R + 1), bn_vec(C, 920)
+    want = torch.relu(a.double() * vec[2].double() + vec[3].double() + b.double())
+    pooled, mask = ops.bn_act_pool(put(a), put(vec), put(b), None, G)
+    e_pool = rel_l2(pooled.cpu().numpy(), want.mean(1).numpy())
+    out, mask_ref = ops.bn_act(put(a), put(vec), put(b), None, relu=True, sign_mask=True)
+    assert torch.equal(mask, mask_ref)
+    e_mean = rel_l2(ops.group_mean(out).cpu().numpy(), want.mean(1).numpy())
+    print(f"bn_act_pool ({G}, {R}): {e_pool:.2e}; group_mean: {e_mean:.2e}")
+    assert e_pool < RED_TOL and e_mean < RED_TOL
