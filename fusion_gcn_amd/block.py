@@ -497,8 +497,10 @@ def pool_epilogue_ok(cfg: BlockConfig, B: int, T: int, V: int, groups: int) -> b
 
 # ---- backward --------------------------------------------------------------------------------------------------------
 def zero_bias_floats(cfg: BlockConfig) -> int:
-    """floats of exactly-zero bias gradients a block hands out in train mode (conv_d x 3, the temporal conv, down, residual conv)"""
-    return (NUM_SUBSETS + 1 + int(cfg.has_down) + int(cfg.residual == "conv")) * cfg.cout
+    """floats of exactly-zero bias gradients a block hands out in train mode: NUM_SUBSETS slots for each of its two BatchNorm backward
+    passes (conv_d x 3; the temporal conv uses the first of its three: _BiasGrads.carry writes both groups with one launch), then the
+    shortcut convolutions' (residual conv, down)"""
+    return (2 * NUM_SUBSETS + int(cfg.has_down) + int(cfg.residual == "conv")) * cfg.cout
 
 
 class _BiasGrads:
@@ -506,23 +508,56 @@ class _BiasGrads:
     block output does not depend on such a bias and its gradient is exactly zero (the reference's autograd produces
     ~1e-9 rounding noise there): all of a block's are disjoint slices of ONE zero-filled
     allocation (one fill launch per block; every parameter still gets memory of its own).  Only eval-mode statistics make
-    them real column sums."""
+    them real column sums.
+
+    A step that is not finite (include/fgcn.h, "Non-finite values in the inputs", rule 3): the reference's gradient of such a bias is the
+    column sum of the BatchNorm backward's result, and that is NaN as soon as the pass's channel sum of dP * a_hat (the shortcut
+    BatchNorm's: of dP * b_hat) is not a number -- a non-finite dP or a NaN a_hat makes it so.  Both passes of a block (stage 0: the temporal
+    half, stage 1: the spatial half) write their sums into ONE (2, 3, C) tensor (``sums_out``), and ``carry`` writes s - s of those rows (0
+    for a number, NaN otherwise) over the slots: one launch per block, one more where the block has a shortcut convolution."""
 
     def __init__(self, cfg: BlockConfig, device, train: bool, zeros: Optional[torch.Tensor] = None):
-        self.train = train
+        self.train, self.c = train, cfg.cout
+        self.sums = torch.empty((2, 3, cfg.cout), device=device, dtype=torch.float32) if train else None
+        self.shortcuts: List[int] = []
         n = zero_bias_floats(cfg)
         # ``zeros``: this block's slice of a pool the MODEL filled once per step (one launch for the ten blocks instead of ten)
         if train and zeros is not None and zeros.numel() >= n:
             self.pool = zeros
         else:
-            self.pool = torch.zeros(n, device=device, dtype=torch.float32) if train else None
+            self.pool = torch.empty(n, device=device, dtype=torch.float32) if train else None      # (carry writes every slot)
         self.used = 0
 
-    def __call__(self, d: torch.Tensor, c: int) -> torch.Tensor:
+    def sums_out(self, stage: int) -> Optional[torch.Tensor]:
+        return self.sums[stage] if self.train else None
+
+    def main(self, d: torch.Tensor, stage: int, j: int = 0) -> torch.Tensor:
+        """the gradient of bias ``j`` in front of the BatchNorm of ``stage``"""
         if not self.train:
-            return ops.col_sum(d, c)
-        self.used += c
-        return self.pool[self.used - c:self.used]
+            return ops.col_sum(d, self.c)
+        slot = NUM_SUBSETS * stage + j
+        return self.pool[slot * self.c:(slot + 1) * self.c]
+
+    def shortcut(self, d: torch.Tensor, stage: int) -> torch.Tensor:
+        """the gradient of the bias of the shortcut convolution whose BatchNorm is the second one of ``stage``"""
+        if not self.train:
+            return ops.col_sum(d, self.c)
+        self.shortcuts.append(stage)
+        slot = 2 * NUM_SUBSETS + len(self.shortcuts) - 1
+        return self.pool[slot * self.c:(slot + 1) * self.c]
+
+    def carry(self) -> None:
+        """after both passes: the slots become 0, or NaN where their pass's sums are not numbers"""
+        if not self.train:
+            return
+        c, off = self.c, self.sums.storage_offset()
+        src = self.sums.as_strided((2, NUM_SUBSETS, c), (3 * c, 0, 1), off + c)                  # row 1 of each stage, NUM_SUBSETS times
+        torch.sub(src, src, out=self.pool[:2 * NUM_SUBSETS * c].view(2, NUM_SUBSETS, c))
+        n = len(self.shortcuts)
+        assert self.shortcuts in ([], [0], [1], [0, 1]), self.shortcuts       # (the view below strides from the first to the second stage)
+        if n:                                                                                    # row 2 of the stages that have a shortcut BatchNorm
+            src = self.sums.as_strided((n, c), (3 * c, 1), off + (3 * self.shortcuts[0] + 2) * c)
+            torch.sub(src, src, out=self.pool[2 * NUM_SUBSETS * c:(2 * NUM_SUBSETS + n) * c].view(n, c))
 
 
 def block_backward(d_o: torch.Tensor, S: Dict[str, Optional[torch.Tensor]], P: Dict[str, torch.Tensor],
@@ -587,19 +622,19 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
         ident = cfg.residual == "identity"       # its gated gradient goes to dx: written here, or (gate_in_dagg) added by the spatial backward below
         du, _, sums = ops.bn_act_bwd(d_o, S["o"], S["u"], S["vec_u"], x_h if ident else None, None, res_mode=int(ident), train=train,
                                      need_db=not gate_in_dagg, db=dx if ident and not gate_in_dagg else None, sign_mask=S["o_sign"],
-                                     grp_rows=grp_rows, da_bf16=half)
+                                     grp_rows=grp_rows, da_bf16=half, sums_out=bias_grad.sums_out(0))
         if gate_in_dagg:
             gated.append((d_o, S["o_sign"], grp_samples) if grp_samples else (as_extra(d_o), S["o_sign"]))   # dx += d_o * [o > 0]
         dx_live = ident and not gate_in_dagg
     else:
         du, dr, sums = ops.bn_act_bwd(d_o, S["o"], S["u"], S["vec_u"], S["r"], S["vec_r"], res_mode=2, train=train,
-                                      sign_mask=S["o_sign"], grp_rows=grp_rows, da_bf16=half, db_bf16=hs)
+                                      sign_mask=S["o_sign"], grp_rows=grp_rows, da_bf16=half, db_bf16=hs, sums_out=bias_grad.sums_out(0))
         G["residual.bn.weight"], G["residual.bn.bias"] = sums[2], sums[0].clone()   # own memory: sums[0] is tcn1.bn.bias too
         ops.rows_gemm(dr, W["res_t"], dx, K=cout, N=cx, tmap=(1, 1, 0, 0, s))   # frames t % s != 0 receive zeros
         dx_live = True
         G["residual.conv.weight"] = ops.rows_wgrad(x_h if dr.dtype == torch.bfloat16 else xf(), dr, K=cin, N=cout, tmap=(1, s, 0, 0, 1),
                                                    conv_param=(1, cin_true))
-        G["residual.conv.bias"] = bias_grad(dr, cout)
+        G["residual.conv.bias"] = bias_grad.shortcut(dr, 0)
     G["tcn1.bn.weight"], G["tcn1.bn.bias"] = sums[1], sums[0]
 
     # -- temporal conv -------------------------------------------------------------------------------------------------------
@@ -615,25 +650,26 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     # weight gradients are reduced straight into the parameter's (out, in, kt, 1) layout: autograd takes them as they are
     G["tcn1.conv.weight"] = ops.tconv_wgrad(S["g"], du, taps=kt, stride=s, conv_param=(1, cout), all_taps=False if pl.wide else None,
                                             amax=(S["amax"][1:2], bamax[0:1]) if pl.du_amax and pl.g_amax else None)
-    G["tcn1.conv.bias"] = bias_grad(du, cout)
+    G["tcn1.conv.bias"] = bias_grad.main(du, 0)
 
     # -- G = relu(BN(y) + down(x)) ---------------------------------------------------------------------------------------------
     if cfg.has_down:
         dy, dd, sums = ops.bn_act_bwd(dg, S["g"], S["y"], S["vec_y"], S["d"], S["vec_d"], res_mode=2, train=train,
-                                      sign_mask=S["g_sign"], da_bf16=half_dy, db_bf16=hs)
+                                      sign_mask=S["g_sign"], da_bf16=half_dy, db_bf16=hs, sums_out=bias_grad.sums_out(1))
         G["gcn1.down.1.weight"], G["gcn1.down.1.bias"] = sums[2], sums[0].clone()   # own memory: sums[0] is gcn1.bn.bias too
         pw_gemm(dd, W, "down_t", dx, K=cout, N=cx, accumulate=dx_live)
         dx_live = True
         G["gcn1.down.0.weight"] = ops.rows_wgrad(x_h if dd.dtype == torch.bfloat16 else xf(), dd, K=cin, N=cout, conv_param=(1, cin_true))
-        G["gcn1.down.0.bias"] = bias_grad(dd, cout)
+        G["gcn1.down.0.bias"] = bias_grad.shortcut(dd, 1)
     else:
         dy, _, sums = ops.bn_act_bwd(dg, S["g"], S["y"], S["vec_y"], x_h, None, res_mode=1, train=train, need_db=not gate_in_dagg,
                                      db=None if gate_in_dagg else dx, db_accumulate=dx_live, sign_mask=S["g_sign"],
-                                     partials=g_partials if fuse_sums else None, da_bf16=half_dy)
+                                     partials=g_partials if fuse_sums else None, da_bf16=half_dy, sums_out=bias_grad.sums_out(1))
         if gate_in_dagg:
             gated.append((as_extra(dg), S["g_sign"]))  # dx += dg * [g > 0]  (dx is still empty: both shortcuts are gated)
         dx_live = not gate_in_dagg
     G["gcn1.bn.weight"], G["gcn1.bn.bias"] = sums[1], sums[0]
+    bias_grad.carry()
 
     # -- conv_d and the joint aggregation ------------------------------------------------------------------------------------------
     a_hat = S["a_hat"]
@@ -659,7 +695,7 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     for k in range(NUM_SUBSETS):
         G[f"gcn1.conv_d.{k}.weight"] = gw[k]
         # three parameters, three buffers (the sum of the three biases is what the kernel adds: equal gradients)
-        G[f"gcn1.conv_d.{k}.bias"] = bias_grad(dy, cout) if train else (dbias if k == 0 else dbias.clone())
+        G[f"gcn1.conv_d.{k}.bias"] = bias_grad.main(dy, 1, k) if train else (dbias if k == 0 else dbias.clone())
     if pl.spatial_bwd == "tile":
         # dagg on chip: dx and dA^ in one launch (the bfloat16 x beside a bfloat16 dy, whatever dx is)
         part = ops.spatial_bwd_tile(dy, x_h if dy.dtype == torch.bfloat16 else xf(), a_hat, W["d_t_b3"], dx, accumulate=dx_live, gated=gated)

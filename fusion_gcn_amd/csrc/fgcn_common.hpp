@@ -127,6 +127,13 @@ int math_mode();   // FGCN_MATH_F32 / FGCN_MATH_BF16 / FGCN_MATH_BF16X3 (fgcn_se
 int products();    // FGCN_PRODUCTS_BF16X3 / FGCN_PRODUCTS_F16X2 inside FGCN_MATH_BF16X3 (fgcn_set_products)
 inline bool f16x2_products() { return math_mode() == FGCN_MATH_BF16X3 && products() == FGCN_PRODUCTS_F16X2; }
 
+// ---- device: ReLU with torch's rules for NaN (include/fgcn.h, "Non-finite values") --------------------------------------
+// relu_nan: max(v, 0) that keeps a NaN (fmaxf returns the other operand, so fmaxf(NaN, 0) is 0 and a NaN pre-activation would leave the
+// epilogue as a zero).  One v_maximum3_f32 where fmaxf was a canonicalising v_max_f32 and the v_max_f32 itself.
+// relu_open: the backward's gate, torch's `grad if !(y <= 0) else 0` -- a NaN output passes its gradient on.  [y > 0] on every other value.
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ bool relu_open(float y) { return !(y <= 0.f); }
+
 // ---- device: MFMA 32x32x2 f32 -----------------------------------------------------------------------------
 // A operand: lane l holds A[i = l & 31][k = l >> 5];  B operand: lane l holds B[k = l >> 5][j = l & 31];
 // C/D: lane l, register r holds D[row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5)][col = l & 31].
@@ -270,6 +277,12 @@ __device__ __forceinline__ float exp2i(int s) {               // 2^s for s in [-
     s = s < -126 ? -126 : (s > 127 ? 127 : s);
     return __builtin_bit_cast(float, (unsigned)(s + 127) << 23);
 }
+// An inf in a scaling block (the maxima are taken with fmaxf: a NaN is dropped, an inf is not) gives s = -114, and every OTHER value of the
+// block would be split as an f16 zero: finite, wrong results where the reference is finite and right.  amax_is_inf (biased exponent 255 of
+// the block's maximum) is uniform over the block; the block is then scaled by NaN instead of 2^s -- every product of the block, hence every
+// accumulator it reaches, is NaN (include/fgcn.h, "Non-finite values in the inputs", rule 3).
+__device__ __forceinline__ bool amax_is_inf(unsigned amax_bits) { return (amax_bits >> 23) == 0xffu; }
+__device__ __forceinline__ float block_scale(int s, bool inf_in_block) { return inf_in_block ? __builtin_nanf("") : exp2i(s); }
 
 // eight values (one lane's fragment) -> the two f16 parts, 16 bytes each
 __device__ __forceinline__ void split2h_x8(float v0, float v1, float v2, float v3, float v4, float v5, float v6, float v7, float sc,

@@ -173,7 +173,7 @@ __device__ __forceinline__ f32x4 ldx4(const float* p, long long e, bool half, in
     return load4(p + e, stream);
 }
 // ---- forward epilogue ----------------------------------------------------------------------------------------
-// MASK: also writes the sign bits of the result (bit e%8 of byte e/8 = [out[e] > 0]) for the backward passes, which then
+// MASK: also writes the sign bits of the result (bit e%8 of byte e/8 = [!(out[e] <= 0)]: set for a NaN, as torch's gate) for the backward passes, which then
 // read 1/32 of an activation instead of `out`; a lane pair shares a byte (n4 is even, host check).
 // O16: `out` is a bfloat16 tensor (store4_bf16; ld_out == C); the sign image is that of the f32 values (a value that rounds to zero
 // keeps its sign bit: the backward gates exactly as with f32 storage).
@@ -196,20 +196,20 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float* a, const float
         }
         if (relu) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = fmaxf(y[e], 0.f);
+            for (int e = 0; e < 4; ++e) y[e] = relu_nan(y[e]);
         }
         // (ld_out != C: the result goes into a channel window of a wider tensor -- MS-G3D's branch concatenation)
         if constexpr (O16) store4_bf16(reinterpret_cast<unsigned short*>(out) + i * 4, y, stream);
         else store4(ld_out == C ? out + i * 4 : out + (i * 4 / C) * ld_out + c, y, stream);
         if (MASK) {
-            const int nib = (y[0] > 0.f ? 1 : 0) | (y[1] > 0.f ? 2 : 0) | (y[2] > 0.f ? 4 : 0) | (y[3] > 0.f ? 8 : 0);
+            const int nib = (relu_open(y[0]) ? 1 : 0) | (relu_open(y[1]) ? 2 : 0) | (relu_open(y[2]) ? 4 : 0) | (relu_open(y[3]) ? 8 : 0);
             const int other = __shfl_xor(nib, 1);
             if (!(threadIdx.x & 1)) mask[i >> 1] = (unsigned char)(nib | (other << 4));
         }
     }
 }
 
-// [out > 0] of the four elements at offset o (multiple of 4) from the sign-bit image or from `out` itself
+// [!(out <= 0)] of the four elements at offset o (multiple of 4) from the sign-bit image or from `out` itself
 template <bool MASKED>
 __device__ __forceinline__ void relu_gate(f32x4& dp, const float* out, const unsigned char* mask, long long o) {
     if (MASKED) {
@@ -219,7 +219,7 @@ __device__ __forceinline__ void relu_gate(f32x4& dp, const float* out, const uns
     } else {
         const f32x4 y = *reinterpret_cast<const f32x4*>(out + o);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) dp[e] = y[e] > 0.f ? dp[e] : 0.f;
+        for (int e = 0; e < 4; ++e) dp[e] = relu_open(y[e]) ? dp[e] : 0.f;
     }
 }
 
@@ -269,7 +269,7 @@ __global__ void bn_act_bwd_reduce_kernel(const float* dout, const float* out, co
                     for (int e = 0; e < 4; ++e) dp[e] = (nib >> e) & 1 ? dp[e] : 0.f;
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) dp[e] = gv[e] > 0.f ? dp[e] : 0.f;
+                    for (int e = 0; e < 4; ++e) dp[e] = relu_open(gv[e]) ? dp[e] : 0.f;
                 }
             }
             const f32x4 ah = (av - mean_a) * rstd_a;
@@ -391,9 +391,9 @@ __global__ __launch_bounds__(256) void bn_act_pool_kernel(const float* a, const 
         if (RES == 1) y += r;
         else if (RES == 2) y += r * sc_b + sh_b;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = fmaxf(y[e], 0.f);
+        for (int e = 0; e < 4; ++e) y[e] = relu_nan(y[e]);
         sum += y;
-        const int nib = (y[0] > 0.f ? 1 : 0) | (y[1] > 0.f ? 2 : 0) | (y[2] > 0.f ? 4 : 0) | (y[3] > 0.f ? 8 : 0);
+        const int nib = (relu_open(y[0]) ? 1 : 0) | (relu_open(y[1]) ? 2 : 0) | (relu_open(y[2]) ? 4 : 0) | (relu_open(y[3]) ? 8 : 0);
         const int other = __shfl_xor(nib, 1);
         if (!(threadIdx.x & 1)) mask[o >> 3] = (unsigned char)(nib | (other << 4));
     };
@@ -463,8 +463,8 @@ __device__ __forceinline__ void stx8(float* p, long long e, f32x8 v, bool half, 
 }
 __device__ __forceinline__ f32x8 ldv8(const float* v, int c) { return f32x8{*reinterpret_cast<const f32x4*>(v + c), *reinterpret_cast<const f32x4*>(v + c + 4)}; }
 __device__ __forceinline__ int sign_byte(f32x8 y) {
-    return (y.lo[0] > 0.f ? 1 : 0) | (y.lo[1] > 0.f ? 2 : 0) | (y.lo[2] > 0.f ? 4 : 0) | (y.lo[3] > 0.f ? 8 : 0) | (y.hi[0] > 0.f ? 16 : 0) |
-           (y.hi[1] > 0.f ? 32 : 0) | (y.hi[2] > 0.f ? 64 : 0) | (y.hi[3] > 0.f ? 128 : 0);
+    return (relu_open(y.lo[0]) ? 1 : 0) | (relu_open(y.lo[1]) ? 2 : 0) | (relu_open(y.lo[2]) ? 4 : 0) | (relu_open(y.lo[3]) ? 8 : 0) |
+           (relu_open(y.hi[0]) ? 16 : 0) | (relu_open(y.hi[1]) ? 32 : 0) | (relu_open(y.hi[2]) ? 64 : 0) | (relu_open(y.hi[3]) ? 128 : 0);
 }
 __device__ __forceinline__ void gate8(f32x8& d, int bits) {
 #pragma unroll
@@ -497,8 +497,8 @@ __global__ __launch_bounds__(256) void bn_act8_kernel(const float* a, const floa
         if (relu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                y.lo[e] = fmaxf(y.lo[e], 0.f);
-                y.hi[e] = fmaxf(y.hi[e], 0.f);
+                y.lo[e] = relu_nan(y.lo[e]);
+                y.hi[e] = relu_nan(y.hi[e]);
             }
         }
         stx8(out, i * 8, y, hm & 4, stream);

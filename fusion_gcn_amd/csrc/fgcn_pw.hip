@@ -81,6 +81,7 @@ __global__ __launch_bounds__(256, 2) void pw_x3_kernel(PwP p) {
     const int ew = NP == 2 ? min(scale_exp_for(*reinterpret_cast<const unsigned*>(p.w3)), 126) : 0;
     float* smax = reinterpret_cast<float*>(Xh + NP * plane);         // NP == 2: the four waves' chunk maxima
     int ea = EA_NONE, abound = 0;
+    bool a_inf = false;                                              // NP == 2: the chunk being staged holds an inf (block_scale)
     const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, p.out_bytes);
     const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc((p.bias ? (const void*)p.bias : p.w3), p.bias ? (unsigned)p.N * 4u : 0u);
 
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void pw_x3_kernel(PwP p) {
         }
     };
     auto deposit = [&]() {
-        const float a_scale = ea == EA_NONE ? 1.f : exp2i(ea);
+        const float a_scale = ea == EA_NONE ? 1.f : block_scale(ea, a_inf);
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
             const int r = tid / TPR + RPP * i;
@@ -196,6 +197,7 @@ __global__ __launch_bounds__(256, 2) void pw_x3_kernel(PwP p) {
             if constexpr (NP == 2) {
                 const unsigned mb = __builtin_bit_cast(unsigned, fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
                 const int ec = __builtin_amdgcn_readfirstlane((mb >> 23) == 0u ? EA_NONE : min(scale_exp_for(mb), 126));
+                a_inf = __builtin_amdgcn_readfirstlane((int)amax_is_inf(mb)) != 0;
                 if (p.in_amax && tid == 0 && bn == 0) atomicMax(p.in_amax, mb);   // (the column tiles of a row tile stage the same rows)
                 // the chunk's scale: its own (largest magnitude into [2^14, 2^15)) whenever the accumulators can follow -- down always
                 // (exact), up while their magnitude bound stays below 2^120 (abound: log2 bound of |acc| in units of the scale in

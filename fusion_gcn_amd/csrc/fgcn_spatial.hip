@@ -355,6 +355,7 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
 
     const float* asrc = p.a_hat + (p.a_batched ? (long long)n * NS * V * V : 0);
     int eA = 0;                                                       // NP == 2: scale of this sample's A^ images
+    bool a_inf = false;                                               // ... which hold an inf (block_scale)
     if constexpr (NP == 2) {
         float m = 0.f;
         for (int i = tid; i < 3 * 32 * 32; i += 256) {
@@ -364,10 +365,12 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
         m = wave_reduce_max(m);
         if (lane == 0) bl[wave] = m;                                  // (bl is written again below, behind the barrier)
         __syncthreads();
-        eA = __builtin_amdgcn_readfirstlane(min(scale_exp_for(__builtin_bit_cast(unsigned, fmaxf(fmaxf(bl[0], bl[1]), fmaxf(bl[2], bl[3])))), 126));
+        const unsigned mA = __builtin_bit_cast(unsigned, fmaxf(fmaxf(bl[0], bl[1]), fmaxf(bl[2], bl[3])));
+        eA = __builtin_amdgcn_readfirstlane(min(scale_exp_for(mA), 126));
+        a_inf = __builtin_amdgcn_readfirstlane((int)amax_is_inf(mA)) != 0;
         __syncthreads();
     }
-    const float scA = exp2i(eA);
+    const float scA = block_scale(eA, a_inf);
     for (int i = tid; i < 3 * 32 * 32; i += 256) {
         const int k = i >> 10, w = (i >> 5) & 31, v = i & 31;
         const float a = (k < NS && v < V && w < V) ? asrc[(k * V + v) * V + w] : 0.f;
@@ -442,7 +445,7 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
             if constexpr (NP == 2) {
                 const float m = wave_reduce_max(wave_max_abs16(xr[1], wave_max_abs16(xr[0], 0.f)));
                 ex = __builtin_amdgcn_readfirstlane(min(scale_exp_for(__builtin_bit_cast(unsigned, m)), 126));
-                const float scx = exp2i(ex);
+                const float scx = block_scale(ex, amax_is_inf(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, m))));
 #pragma unroll
                 for (int f = 0; f < 2; ++f)
 #pragma unroll

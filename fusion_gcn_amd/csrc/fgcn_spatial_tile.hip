@@ -283,7 +283,8 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
 #pragma unroll
         for (int nu = 0; nu < NU; ++nu) {
             esc[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, coff[nu], (unsigned)p.Cout * 8u, 0));
-            esh[nu] = __builtin_fmaf(bv[nu], esc[nu], __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, coff[nu], (unsigned)p.Cout * 12u, 0)));
+            // (the bias joins the accumulator: folded into the shift, an inf scale gives inf - inf -- fgcn_tconv.hip's epilogue says more)
+            esh[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, coff[nu], (unsigned)p.Cout * 12u, 0));
             // (branch-free: without a shortcut BatchNorm the descriptor is empty, the load returns 0 and the scalar addend makes it 1)
             rsc[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrv, coff[nu], (unsigned)p.Cout * 8u, 0)) + res_unit;
             rsh[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrv, coff[nu], (unsigned)p.Cout * 12u, 0));   // (no BatchNorm: zero bytes -> 0)
@@ -309,9 +310,9 @@ __global__ __launch_bounds__(256, 2) void spatial_tile_x3_kernel(SpTileP p) {
                 for (int nu = 0; nu < NU; ++nu) {
                     const int row = wr * (16 * MTW) + mt * 16 + 4 * g4 + r;
                     const unsigned off = (row < nrows && coff[nu] != OOB) ? (unsigned)((m0 + row) * p.ld_y * 4) + coff[nu] : OOB;
-                    float val = __builtin_fmaf(acc[mt][nu][r], esc[nu], esh[nu]);
+                    float val = __builtin_fmaf(acc[mt][nu][r] + bv[nu], esc[nu], esh[nu]);
                     val += __builtin_fmaf(resv[mt & 1][nu][r], rsc[nu], rsh[nu]);
-                    val = fmaxf(val, 0.f);
+                    val = relu_nan(val);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), ry, off, 0, STR ? FGCN_STORE_AUX : 0);
                 }
             }

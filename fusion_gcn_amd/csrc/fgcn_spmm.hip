@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void graph_spmm_kernel(SpmmP p, const int* __r
         }
         if (p.relu) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], 0.f);
+            for (int e = 0; e < 4; ++e) acc[e] = relu_nan(acc[e]);
         }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, acc), rout, lane_off, out_off,
                                                STR ? FGCN_STORE_AUX : 0);
@@ -128,9 +128,9 @@ __global__ __launch_bounds__(256) void graph_spmm_kernel(SpmmP p, const int* __r
         asm volatile("s_nop 1");
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (MASK) {
-            // fgcn_bn_act's image: bit e % 8 of byte e / 8 = [out[e] > 0], e the element index in the contiguous (B, V, C) tensor; C % 8 == 0
+            // fgcn_bn_act's image: bit e % 8 of byte e / 8 = [!(out[e] <= 0)], e the element index in the contiguous (B, V, C) tensor; C % 8 == 0
             // (host check), so a lane pair shares a byte and a row owns C / 8 whole bytes
-            const int nib = (acc[0] > 0.f ? 1 : 0) | (acc[1] > 0.f ? 2 : 0) | (acc[2] > 0.f ? 4 : 0) | (acc[3] > 0.f ? 8 : 0);
+            const int nib = (relu_open(acc[0]) ? 1 : 0) | (relu_open(acc[1]) ? 2 : 0) | (relu_open(acc[2]) ? 4 : 0) | (relu_open(acc[3]) ? 8 : 0);
             const int other = __shfl_xor(nib, 1);
             const unsigned moff = (lane & 1) || c >= p.C ? OOB : (unsigned)c >> 3;
             __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(nib | (other << 4)), rm, moff, (unsigned)row * ((unsigned)p.C >> 3), 0);

@@ -420,6 +420,7 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
     constexpr int EA_NONE = 1000;
     const int ew = NP == 2 ? min(scale_exp_for(*reinterpret_cast<const unsigned*>(p.w4)), 126) : 0;
     int ea = EA_NONE, abound = 0;
+    bool a_inf = false;                              // NP == 2: the chunk being staged holds an inf (block_scale)
 
     bool row_ok[MTW];
     int th_lane[MTW];
@@ -521,7 +522,7 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
             }
     };
     auto deposit = [&](int kc, int lo = 0, int hi = 64) {   // split the staged rows into the three bf16 planes
-        const float a_scale = (NP == 2 && ea != EA_NONE) ? exp2i(ea) : 1.f;
+        const float a_scale = (NP == 2 && ea != EA_NONE) ? block_scale(ea, a_inf) : 1.f;
         f32x4 fsc = {0.f, 0.f, 0.f, 0.f}, fsh = fsc;
         const __amdgpu_buffer_rsrc_t rgo = buffer_rsrc((FIN ? (void*)p.fin_out : (void*)p.out), FIN ? p.in_bytes : 0u);
         const __amdgpu_buffer_rsrc_t rgm = buffer_rsrc((FIN ? (void*)p.fin_mask : (void*)p.out), FIN ? p.in_bytes >> 5 : 0u);
@@ -540,14 +541,14 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
                     const bool live = src_off[i] != OOB;
                     f32x4 v = stage[i] * fsc + fsh + stage2[i];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = live ? fmaxf(v[e], 0.f) : 0.f;
+                    for (int e = 0; e < 4; ++e) v[e] = live ? relu_nan(v[e]) : 0.f;
                     stage[i] = v;
                     // the first column tile's workgroups keep their own rows of G and its sign image (one dword = this row's 32
                     // channels of the chunk: the eight 4-bit groups of the row's eight lanes, gathered with three shuffles)
                     const bool mine = live && bn == 0 && r >= own0 && r < own0 + BMR;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rgo, mine ? src_off[i] : OOB,
                                                            (unsigned)kc * 4, 0);
-                    unsigned w = ((v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u))
+                    unsigned w = ((relu_open(v[0]) ? 1u : 0u) | (relu_open(v[1]) ? 2u : 0u) | (relu_open(v[2]) ? 4u : 0u) | (relu_open(v[3]) ? 8u : 0u))
                                  << (4 * (lane & 7));
                     w |= (unsigned)__shfl_xor((int)w, 1);
                     w |= (unsigned)__shfl_xor((int)w, 2);
@@ -615,6 +616,7 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
                 }
                 const unsigned mb = __builtin_bit_cast(unsigned, fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
                 const int ec = __builtin_amdgcn_readfirstlane((mb >> 23) == 0u ? EA_NONE : min(scale_exp_for(mb), 126));
+                a_inf = __builtin_amdgcn_readfirstlane((int)amax_is_inf(mb)) != 0;
                 if (p.in_amax && tid == 0 && bn == 0) atomicMax(p.in_amax, mb);   // (the column tiles of a row tile stage the same rows)
                 // the chunk's scale: its own (largest magnitude into [2^14, 2^15)) whenever the accumulators can follow -- down always
                 // (exact), up while their magnitude bound stays below 2^120 (abound: log2 bound of |acc| in units of the scale in
@@ -734,7 +736,9 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
 #pragma unroll
         for (int nu = 0; nu < NU; ++nu) {
             esc[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, coff[nu], (unsigned)p.N * 8u, 0));
-            esh[nu] = __builtin_fmaf(bv[nu], esc[nu], __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, coff[nu], (unsigned)p.N * 12u, 0)));
+            // (the bias is added to the accumulator, not folded into the shift as bias * scale + shift: with an inf scale the fold is inf - inf
+            // where (acc + bias) * scale is an inf of one sign -- include/fgcn.h, non-finite values, rule 1)
+            esh[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, coff[nu], (unsigned)p.N * 12u, 0));
             rsc[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrv, coff[nu], (unsigned)p.N * 8u, 0)) + res_unit;
             rsh[nu] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrv, coff[nu], (unsigned)p.N * 12u, 0));
         }
@@ -790,8 +794,8 @@ __global__ __launch_bounds__(256, (NP == 1 && !FIN && EPI != 4) ? 3 : 2) void co
                 const unsigned off = (rowoff[mt][r] == OOB || coff[nu] == OOB) ? OOB : rowoff[mt][r] + coff[nu];
                 float val = (NP == 2 ? acc[mt][nu][r] * un_a * un_w : acc[mt][nu][r]) + bv[nu];
                 if constexpr (fep) {
-                    val = __builtin_fmaf(acc[mt][nu][r], esc[nu], esh[nu]) + __builtin_fmaf(oldv[mt & 1][nu][r], rsc[nu], rsh[nu]);
-                    val = fmaxf(val, 0.f);
+                    val = __builtin_fmaf(val, esc[nu], esh[nu]) + __builtin_fmaf(oldv[mt & 1][nu][r], rsc[nu], rsh[nu]);
+                    val = relu_nan(val);
                 } else if constexpr (ldacc) {
                     val += oldv[mt & 1][nu][r];
                 }

@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void tconv_wgrad_x3_kerne
         ea = min(scale_exp_for(*p.a_amax), 126);                // (2^-ea must be a normal float too)
         eg = min(scale_exp_for(*p.g_amax), 126);
     }
-    const float sc_a = exp2i(ea), sc_g = exp2i(eg);
+    const float sc_a = block_scale(ea, NP == 2 && amax_is_inf(*p.a_amax)), sc_g = block_scale(eg, NP == 2 && amax_is_inf(*p.g_amax));
 
     // staging roles: a: row tid/8 + RA*i, channels k0 + (tid%8)*4;  g: row tid/GT + GRP*i, columns n0 + (tid%GT)*4
     const int a_row = tid >> 3, a_c4 = tid & 7, g_row = tid / GT, g_c4 = tid % GT;

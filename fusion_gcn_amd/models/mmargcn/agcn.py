@@ -351,10 +351,10 @@ class Model(nn.Module):
         self._bump_batch_counters()
         refresh_packed_weights(self)
         if self.training and torch.is_grad_enabled():
-            # the exactly-zero bias gradients of all blocks (block._BiasGrads): one zero-filled allocation and one fill launch per step
+            # the exactly-zero bias gradients of all blocks (block._BiasGrads): one allocation per step
             blocks = [m for m in self.layers if isinstance(m, SpatialTemporalConv)]
             sizes = [zero_bias_floats(b.cfg) for b in blocks]
-            zeros = torch.zeros(sum(sizes), device=h.device, dtype=torch.float32)
+            zeros = torch.empty(sum(sizes), device=h.device, dtype=torch.float32)      # (no fill: _BiasGrads.carry writes every slot, 0 or NaN)
             off = 0
             for b, n in zip(blocks, sizes):
                 b._zeros = zeros[off:off + n]

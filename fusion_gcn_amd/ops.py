@@ -1036,8 +1036,8 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps: float = 1e-5) ->
 def bn_act(a: torch.Tensor, vec_a: torch.Tensor, b: Optional[torch.Tensor] = None, vec_b: Optional[torch.Tensor] = None,
            relu: bool = True, out: Optional[torch.Tensor] = None, sign_mask: bool = False, out_bf16: bool = False):
     """act(a*scale_a + shift_a + [b | b*scale_b + shift_b]).  ``sign_mask``: -> (out, mask) where mask holds one bit per
-    element, [out > 0] (uint8, numel/8; None when the element count is not a multiple of 8) -- what the backward's
-    ReLU gate reads instead of ``out``.  ``out_bf16``: the result is stored as bfloat16 (round to nearest even; half_mask bit 2) -- for a
+    element, [!(out <= 0)] -- [out > 0], and set for a NaN, which passes its gradient as in torch -- (uint8, numel/8; None when the
+    element count is not a multiple of 8): what the backward's ReLU gate reads instead of ``out``.  ``out_bf16``: the result is stored as bfloat16 (round to nearest even; half_mask bit 2) -- for a
     tensor that only the bf16 kernels' staging reads (math mode bf16: the temporal conv's input).  ``a`` / ``b`` may be bfloat16 tensors
     themselves (half-precision activation storage, math mode bf16: half_mask bits 0 and 1)."""
     ensure_device()
@@ -1086,7 +1086,8 @@ def bn_act_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], a: torch.Tensor,
                b: Optional[torch.Tensor], vec_b: Optional[torch.Tensor], *, relu: bool = True, train: bool = True,
                res_mode: int, db: Optional[torch.Tensor] = None, db_accumulate: bool = False,
                sign_mask: Optional[torch.Tensor] = None, need_sums: bool = True, need_db: bool = True,
-               partials: Optional[torch.Tensor] = None, grp_rows: int = 0, da_bf16: bool = False, db_bf16: bool = False):
+               partials: Optional[torch.Tensor] = None, grp_rows: int = 0, da_bf16: bool = False, db_bf16: bool = False,
+               sums_out: Optional[torch.Tensor] = None):
     """Backward of bn_act.  Returns (da, db, sums (3, C)): sums[0] = d beta, sums[1] = d gamma_a, sums[2] = d gamma_b.
     ``da_bf16``: da is stored as bfloat16 (half_mask bit 3 of fgcn_bn_act_bwd_apply: the gradient of the temporal conv's output in math mode bf16).
     The ReLU gate is read from ``sign_mask`` (bn_act's bit image) when given, else from ``out``.  ``need_sums=False`` with
@@ -1095,9 +1096,13 @@ def bn_act_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], a: torch.Tensor,
     output, already divided by the group size -- instead of its rows x C broadcast.
     ``dout`` / ``a`` / ``b`` may be bfloat16 tensors (half-precision activation storage, math mode bf16: half_mask bits 0 to 2; the gate
     is then the sign image and a per-group ``dout`` stays float32); ``db_bf16``: a freshly allocated db (the shortcut branch's gradient) is
-    bfloat16 too (typed operands, C % 8 == 0, no accumulation)."""
+    bfloat16 too (typed operands, C % 8 == 0, no accumulation).  ``sums_out``: a (3, C) float32 tensor to hold the sums instead of a new one."""
     ensure_device()
     d16, a16 = _chka(dout, "bn_act_bwd.dout"), _chka(a, "bn_act_bwd.a")
+    if sums_out is not None:
+        _chk(sums_out, "bn_act_bwd.sums_out")
+        if tuple(sums_out.shape) != (3, a.shape[-1]):
+            raise _lib.FgcnError(f"bn_act_bwd: sums_out {tuple(sums_out.shape)} is not (3, {a.shape[-1]})")
     b16 = _chka(b, "bn_act_bwd.b") if (b is not None and res_mode == 2) else False      # (an identity shortcut is not read)
     typed = d16 or a16 or b16
     if typed and ((relu and sign_mask is None) or (d16 and grp_rows)):
@@ -1114,14 +1119,14 @@ def bn_act_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], a: torch.Tensor,
     if partials is not None:            # the producer of dout already summed (tconv_halo bn_bwd): (tiles, 2, C) -> sums[0:2]
         if res_mode == 2 or partials.shape[1:] != (2, C):
             raise _lib.FgcnError("bn_act_bwd: precomputed partials are (tiles, 2, C) sums of a BatchNorm without a second BatchNorm branch")
-        sums = torch.empty((3, C), device=a.device, dtype=torch.float32)
+        sums = torch.empty((3, C), device=a.device, dtype=torch.float32) if sums_out is None else sums_out
         reduce_sum(partials.view(partials.shape[0], -1), sums[:2].view(-1))
     elif need_sums or train:
         tiles = lib.fgcn_elem_tiles(rows)
         partials = torch.empty((tiles, 3, C), device=a.device, dtype=torch.float32)
         check(lib.fgcn_bn_act_bwd_reduce(_p(dout), grp_rows, gate_out, _p(sign_mask), _p(a), _p(vec_a), _p(b), _p(vec_b), _p(partials),
                                          tiles, rows, C, res_mode, int(relu), _half_mask(d16, a16, b16), _stream()), "fgcn_bn_act_bwd_reduce")
-        sums = torch.empty((3, C), device=a.device, dtype=torch.float32)
+        sums = torch.empty((3, C), device=a.device, dtype=torch.float32) if sums_out is None else sums_out
         reduce_sum(partials.view(tiles, -1), sums.view(-1))
     da = torch.empty_like(a, dtype=torch.bfloat16 if da_bf16 else torch.float32)
     db16 = False
@@ -1708,7 +1713,7 @@ def graph_spmm(x: torch.Tensor, csr, out: Optional[torch.Tensor] = None, relu: b
     val) from ``csr_from_dense`` (fgcn_graph_spmm): the adjacency product of the static-graph IMU convolution as a gather, float32 FMAs in
     ascending column order in every math mode.  x: (B, V, C) float32 whose rows may be wider than C (a channel window: last stride 1,
     x.stride(0) == V * x.stride(1)); b like out; vec_b: the (4, C) vector of ``bn_finalize``.  ``sign_mask``: -> (out, mask), mask = the
-    bit image [out > 0] in ``bn_act``'s format (None when C % 8 != 0: the backward then gates from ``out``)."""
+    bit image [!(out <= 0)] in ``bn_act``'s format (None when C % 8 != 0: the backward then gates from ``out``)."""
     ensure_device()
     row_ptr, col, val = csr
     if x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32 or x.stride(2) != 1 or (x.shape[0] > 1 and x.stride(0) != x.shape[1] * x.stride(1)):

@@ -39,6 +39,40 @@ const char* fgcn_last_error(void);
 /* 0 if the current HIP device is gfx950, FGCN_E_ARCH otherwise (message names the arch found). */
 int fgcn_check_device(void);
 
+/* Non-finite values in the inputs.  Classify every output element as finite, NaN, +inf or -inf.  "The reference" is the float64 restatement
+ * of an entry point (torch's composition of the same operation) run on the same float32 input with the same non-finite element in it.
+ * tests/test_nonfinite_gpu.py asserts exactly these rules (tests/nonfinite_ref.py counts swallowed / corrupted / spilled elements):
+ *   1. Elementwise kernels and epilogues reproduce the reference's class at every position: NaN stays NaN, +-inf keeps its sign, wherever
+ *      the value enters -- the pre-activation, the residual, the per-channel scale or shift.  fgcn_bn_act (every res_mode, with and without
+ *      the sign image, every half_mask, the four- and the eight-wide forms), fgcn_bn_act_pool, the add + ReLU built on fgcn_bn_act, the
+ *      BatchNorm + shortcut + ReLU epilogues of fgcn_tconv_halo_bn_relu and fgcn_spatial_fwd_tile_bn_relu, fgcn_graph_spmm's epilogue.
+ *      The ReLU is max(v, 0) that KEEPS a NaN (torch.relu; fmaxf(NaN, 0) is 0).  The two fused epilogues add the conv bias to the accumulator
+ *      before the scale: (acc + bias) * scale + shift, as the reference does, not acc * scale + (bias * scale + shift), which is inf - inf for an
+ *      inf scale.
+ *   2. The ReLU gate of the backward is torch's: grad if !(y <= 0) else 0.  A NaN output PASSES its gradient.  The sign image bit is
+ *      [!(out[e] <= 0)] (equal to [out[e] > 0] on every number; set for a NaN), and a gate read from `out` decides the same way.
+ *   3. Contractions never swallow and never corrupt silently (the row GEMMs, fgcn_pw_gemm, fgcn_tconv_halo, fgcn_joint_mix*, the spatial,
+ *      embedding and weight-gradient tile kernels, fgcn_row_softmax_*, the cross-entropy kernels): where the reference is non-finite the
+ *      result is non-finite -- NaN against +-inf need not match: an inf that went through a bf16 or f16 split is inf - inf = NaN in its second
+ *      part, and everything behind it is what the reference computes from a NaN there (ReLUs the reference closes at -inf are open at the
+ *      NaN) -- and where the reference is finite the result is within the tolerance of the same call on finite data, or non-finite.  A finite
+ *      wrong value is the failure.
+ *   4. Containment: with running-statistics BatchNorm (eval) a non-finite element of one sample leaves the other samples finite and within
+ *      that tolerance -- for a NaN in every math mode, for +-inf in f32, bf16x3 and bf16.  FGCN_PRODUCTS_F16X2 with an inf: rule 3 alone.  That
+ *      mode scales each staged block (a K chunk of a row tile, a frame pair, a sample's adjacency images, a whole tensor in the weight
+ *      gradient) by its largest magnitude; the maxima are taken with fmaxf, so a NaN does not move the scale but an inf does, and an inf's
+ *      scale would flush every other value of the block to an f16 zero.  A block whose maximum is an inf is scaled by NaN instead: every
+ *      accumulator it reaches is NaN, which may include rows of neighbouring samples in the same tile.
+ *   5. Structural zeros: fgcn_graph_spmm multiplies the STORED entries of its CSR matrix only, so its reference is torch's sparse product
+ *      over the same entries: a NaN in node u reaches the nodes with a stored entry in column u, not every node.  No other route skips a
+ *      product: the mixing matrices of fgcn_joint_mix* are dense operands, and 0 * NaN = NaN there.
+ * The conv-bias gradients in front of a batch-statistics BatchNorm, which the host of the AGCN block hands out as exact zeros
+ * (fusion_gcn_amd/block.py, _BiasGrads), are under rule 3 too: they are s - s of that BatchNorm backward's channel sums (fgcn_bn_act_bwd_reduce's
+ * row 1, the shortcut BatchNorm's row 2), 0 for a number and NaN otherwise.  The MS-G3D op wrappers (fusion_gcn_amd/fops.py, zero_bias_grad) still
+ * hand out plain zeros: not under these rules, and not tested.
+ * The earlier NaN rules stand beside these: fgcn_tmaxpool3_fwd (a NaN tap wins), fgcn_classify_update and the fused scores' ranking (NaN sorts
+ * above every number), fgcn_signal_prepare's min / max (a NaN in the array makes every output NaN). */
+
 /* Contexts: where the settings live that the launchers read on the host at call time -- the math mode, the product form and the
  * kernel-variant table below.  Every thread has a CURRENT context; a thread that never made one current reads (and, through the
  * setters below, writes) the process-wide defaults.  fgcn_ctx_create copies the calling thread's current settings into a new
@@ -505,7 +539,7 @@ int fgcn_bn_eval_coeffs(const float* gamma, const float* beta, const float* runn
 /* out = act( a*scale_a + shift_a + r ),  r = 0 | b | b*scale_b + shift_b          (agcn.py:113-115, :135-136)
  *   res_mode: 0 none, 1 identity, 2 batch-normalised.  vec_a / vec_b: the float[4][C] of fgcn_bn_finalize.
  *   rows x C elements, all tensors share row stride ld (== C). relu: 0/1. */
-/*   sign_mask (may be NULL; needs rows*C % 8 == 0): also stores bit e%8 of byte e/8 = [out[e] > 0] -- rows*C/8 bytes the
+/*   sign_mask (may be NULL; needs rows*C % 8 == 0): also stores bit e%8 of byte e/8 = [!(out[e] <= 0)] (set for a NaN: rule 2 above) -- rows*C/8 bytes the
  *   backward passes can read instead of the whole of `out` (the ReLU gate of the reference's autograd). */
 int fgcn_bn_act(const void* a, const float* vec_a, const void* b, const float* vec_b, void* out, unsigned char* sign_mask,
                 long long rows, int C, int res_mode, int relu, int half_mask, void* stream);
@@ -519,7 +553,7 @@ int fgcn_bn_act_pool_splits(int groups, int grp_rows);
 int fgcn_bn_act_pool(const void* a, const float* vec_a, const void* b, const float* vec_b, unsigned char* sign_mask,
                      float* partial, float* pooled, int groups, int grp_rows, int C, int res_mode, int half_mask, void* stream);
 
-/* Backward of the above, pass 1 (reductions): with dP = dout .* [out > 0] (or dout when relu = 0)
+/* Backward of the above, pass 1 (reductions): with dP = dout .* [!(out <= 0)] (or dout when relu = 0)
  *   partials[tile][0][c] = sum dP, [1] = sum dP * a_hat, [2] = sum dP * b_hat   (a_hat = (a-mean_a)*rstd_a).
  *   The gate comes from sign_mask when it is given (then `out` may be NULL), else from `out`.
  *   grp_rows (both passes; 0: dout is (rows, C)) > 0: the gradient of a POOLED output (fgcn_bn_act_pool) -- dout is float[rows / grp_rows][C],
@@ -670,7 +704,7 @@ int fgcn_transpose(const float* in, float* out, int B, int R, int C, int ld_in, 
  *   col and val must be followed by SEVEN more readable entries (the kernel fetches entries in groups of eight and ignores those
  *   past a row's end).  Column indices are not checked on the device.
  *   res_mode / vec_b / relu / sign_mask: the epilogue of fgcn_bn_act (0 none, 1 identity, 2 `b*scale + shift` from vec_b's float[4][C]);
- *   sign_mask (may be NULL; needs C % 8 == 0): bit e%8 of byte e/8 = [out[e] > 0], e = (b*V + v)*C + c -- fgcn_bn_act's image.
+ *   sign_mask (may be NULL; needs C % 8 == 0): bit e%8 of byte e/8 = [!(out[e] <= 0)], e = (b*V + v)*C + c -- fgcn_bn_act's image.
  *   With the CSR form of adj this is the layer's forward (no separate fgcn_bn_act pass), with that of adj^T and no epilogue its data
  *   gradient d_support = d_main . adj: both gathers, no atomics.  float32 FMAs in ascending column order in EVERY math mode: launches
  *   agree bit for bit and the math mode changes nothing.  FGCN_E_BADARG: C % 4 != 0, a null CSR array, B*V >= 2^29 rows or a tensor

@@ -12,7 +12,7 @@ every kernel is accurate to 1e-6.  So gradient parity is stated in three parts:
   (iii) the un-injected error must be explained by the flips (``explained_by_flips``: the part of the error that lives
         outside the injected run's error is attributed to them and bounded).
 
-The sign image layout is fgcn_bn_act's (include/fgcn.h): bit e % 8 of byte e / 8 = [out[e] > 0] over the flat channels-last
+The sign image layout is fgcn_bn_act's (include/fgcn.h): bit e % 8 of byte e / 8 = [!(out[e] <= 0)] (= [out[e] > 0], and set for a NaN) over the flat channels-last
 (B, T, V, C) tensor.  The oracle works in the reference's (B, C, T, V) layout (torch_src/models/mmargcn/agcn.py:186-188).
 """
 from __future__ import annotations
@@ -26,8 +26,9 @@ RELU_NAMES = ("g", "o")      # G = relu(BN(y) + down(x)) (agcn.py:113-115), O = 
 
 
 def pack_sign_image(t_nchw: torch.Tensor) -> np.ndarray:
-    """[t > 0] of an oracle (B, C, T, V) tensor as the kernels' bit image (uint8, numel / 8) of the (B, T, V, C) layout."""
-    bits = (t_nchw.permute(0, 2, 3, 1) > 0).contiguous().numpy().reshape(-1)
+    """[!(t <= 0)] of an oracle (B, C, T, V) tensor as the kernels' bit image (uint8, numel / 8) of the (B, T, V, C) layout: [t > 0] on every
+    number, and set for a NaN -- torch's ReLU backward passes the gradient at a NaN output, and so do the kernels' gates."""
+    bits = (~(t_nchw.permute(0, 2, 3, 1) <= 0)).contiguous().numpy().reshape(-1)
     return np.packbits(bits, bitorder="little")
 
 

@@ -44,6 +44,15 @@ def dev():
     return torch.device("cuda:0")
 
 
+def tolerances(bf16: bool, flips: int) -> tuple:
+    """What an entry is held to (the module docstring): (output, adj_c, running statistics, the un-injected backward's dx and parameter
+    gradients) -- relative L2, except the last in math mode bf16: the least cosine.  tests/test_nonfinite_gpu.py holds the finite part of a
+    poisoned run of the same entry to these."""
+    if bf16:
+        return 1e-2, 1e-2, 1e-2, 0.98
+    return 2e-5, 1e-5, 1e-5, (2e-4 if flips == 0 else 5e-3)
+
+
 def _check_entry(run: R.BlockRun, e: R.Entry, phase: str, ora: dict, fails: list) -> str:
     mode, bf16 = e.plan.mode, e.plan.mode == "bf16"
     tag = f"[{mode} {phase} {e.case.name}{' bf16-in' if e.half else ''} | {e.option_name}]"
@@ -54,7 +63,7 @@ def _check_entry(run: R.BlockRun, e: R.Entry, phase: str, ora: dict, fails: list
         fails.append(f"{tag}: the block planned {a['plans']}, the matrix predicted {e.plan}")
     # ---- forward
     fwd = R.rel_l2(a["out"].cpu().numpy(), ora["out"].numpy())
-    tol_out, tol_c, tol_rs = (1e-2, 1e-2, 1e-2) if bf16 else (2e-5, 1e-5, 1e-5)
+    tol_out, tol_c, tol_rs, _ = tolerances(bf16, 0)
     if not fwd < tol_out:
         fails.append(f"{tag}: forward {fwd:.3e} >= {tol_out:g}")
     if a["out_dtype"] != (torch.bfloat16 if e.plan.o_bf16 else torch.float32) or a["dx_dtype"] != (torch.bfloat16 if e.half else torch.float32):
@@ -81,7 +90,7 @@ def _check_entry(run: R.BlockRun, e: R.Entry, phase: str, ora: dict, fails: list
         worst = R.compare_grads_bf16(a, ora, fails, tag)
         line = f"fwd {fwd:.2e} worst cosine {worst[1]:.4f} ({worst[0]}) flips {flips}"
     else:
-        R.compare_grads(a, ora, 2e-4 if flips == 0 else 5e-3, fails, tag + " as is")
+        R.compare_grads(a, ora, tolerances(bf16, flips)[3], fails, tag + " as is")
         b = run.run(e, phase, inject=ora["images"])
         worst = R.compare_grads(b, ora, INJECTED_TOL, fails, tag + " injected")
         c = run.run(e, phase)           # a second run of the same entry on freshly poisoned memory: every sum has a fixed order
