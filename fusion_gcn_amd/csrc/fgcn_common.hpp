@@ -115,8 +115,10 @@ __device__ __forceinline__ unsigned fastdiv(unsigned n, FastDiv f) { return (uns
 // Kernel-variant selectors (fgcn_set_tuning): defaults are the measured-best variants; tests and tools/kbench.py
 // flip them to compare.  key 0: row-GEMM tile for <= 64 output channels, key 1: for wider outputs (see fgcn_gemm.hip);
 // key 4: halo conv register budget (0: 3
-// workgroups per CU, 1: 2); key 5: XCD-aware workgroup order, bit 0 row GEMM (off), bit 1 halo conv (off), bit 2
-// disables it for the weight gradient (on by default), bit 3 disables the column-tile-fastest grid of the row GEMM.
+// workgroups per CU, 1: 2); key 5: workgroup orders -- bit 0 turns the XCD-aware order ON for the row GEMM and bit 1 for the f32 halo
+// conv (off by default); bit 2 turns it OFF for the per-tap weight gradient (rows_wgrad), bit 4 for the split-bf16 spatial forward,
+// bit 5 for the split-bf16 halo conv and bit 6 for the split weight gradients (on by default); bit 3 turns off the column-tile-fastest
+// grid of the row GEMM.  The full list is the comment on fgcn_set_tuning in include/fgcn.h; tests/variants.py has one row per value.
 int tuning(int key);
 // true when a call that writes `bytes` of output should stream it (tuning key 10: 0 = from 96 MiB on, 1 = never, 2 = always)
 inline bool stream_out(long long bytes) {

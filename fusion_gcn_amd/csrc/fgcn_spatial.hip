@@ -725,7 +725,9 @@ extern "C" int fgcn_spatial_fwd(const float* x, const float* a_hat, const float*
                (unsigned)((long long)n_subsets * Cin * Cout * 2), 0, 0, 0};
     hipStream_t s = (hipStream_t)stream;
     int rc = -1;
-    if (split && !(fgcn::tuning(7) & 1)) {     // two frames per wave, split-bf16 aggregation (tuning key 7 bit 0: the older form)
+    // two frames per wave, split-bf16 aggregation (tuning key 7 bit 0: the older form below, which reads the three-part bf16 weights only:
+    // with the f16x2 products `wd` is the FGCN_PACK_SPLIT2H_ACC form and the bit selects nothing)
+    if (split && (!(fgcn::tuning(7) & 1) || fgcn::f16x2_products())) {
         switch (ci) {
             case 1: launch_spatial_x3<1>(p, s); break;
             case 2: launch_spatial_x3<2>(p, s); break;

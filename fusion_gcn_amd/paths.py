@@ -14,7 +14,7 @@ process); nothing else in the package reads the environment for a path decision.
 
 Every default below is a measured choice; the measurement is cited next to the field (records under profiles/, narrative in
 DESIGN.md / DESIGN_HISTORY.md).  Variants that lost their A/B twice were deleted in round 6 instead of carried as switches: the
-four-wave spatial backward (tuning key 11 = 2) and the weight-gradient side stream.
+four-wave spatial backward (its tuning key went with it) and the weight-gradient side stream.
 """
 from __future__ import annotations
 

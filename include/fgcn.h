@@ -89,8 +89,11 @@ int fgcn_ctx_set_current(fgcn_ctx* ctx);
 fgcn_ctx* fgcn_ctx_get_current(void);
 
 /* Select a kernel variant in the calling thread's current context (for tuning tools and same-box A/B runs -- value 0 of every key is the
- * measured-best default, every other form computes the same result in another summation order at most).  Keys 0..31 (others: FGCN_E_BADARG):
+ * measured-best default, every other form computes the same result in another summation order at most: tests/variants.py lists every
+ * (key, value) with the launcher's condition for it and the test that runs it).  Keys 0..31 (others: FGCN_E_BADARG); a key that is not
+ * listed is stored and read by nothing:
  *   0  row-GEMM tile when N <= 64: 0 = 128x(32*nt) rows per workgroup, 1 = 256-row tile (default), 2 = 256-row, double-buffered LDS
+ *      (launches of fewer than 256 workgroups run the 128-row tile whatever the key says, unless key 24 = 1)
  *   1  row GEMM, wider N: 0 = two barriers per K chunk, 1 = double-buffered LDS
  *   4  f32 halo conv: 0 = three workgroups per CU, 1 = two
  *   5  workgroup orders (bits): 1 row GEMM XCD-aware order on; 8 row GEMM column-tile-fastest off; 4 generic weight gradient (rows_wgrad) XCD-aware off;
@@ -102,13 +105,14 @@ fgcn_ctx* fgcn_ctx_get_current(void);
  *      512: fgcn_spatial_wgrad on exact-f32 MFMAs in math mode bf16x3 (default there: the split-bf16 form)
  *      1024: joint_dagg with its subset count / accumulate flag as run-time values (the form before the end of round 3); 2048: both at compile time,
  *      three workgroups per CU, one tile register set (default: one set per subset refilled a chunk ahead, two workgroups per CU)
- *   7  split-bf16 kernels (bits) 1: spatial forward, one frame per wave (older form); 2: halo conv on the 32x32x16 MFMA shape;
- *      4: the same for N <= 64 only; 8: split-bf16 halo conv at <= 64 output columns as 2 x 2 waves over 128-row tiles (default: 4 x 1 waves
- *      over 192-row tiles from 1536 tiles on); 16: the 4 x 1 form with a 128-column tile for every N > 64 (default: 64 < N <= 128 only); 32: never; 64: the 4 x 1 form at <= 64 columns whatever the tile count (tests)
+ *   7  split-bf16 kernels (bits) 1: spatial forward, one frame per wave (older form; bf16x3 products only -- it has no f16x2 form, and
+ *      with FGCN_PRODUCTS_F16X2 the bit selects nothing); 8: split-bf16 halo conv as 2 x 2 waves over 128-row tiles at every width (default:
+ *      4 x 1 waves over 192-row tiles up to 128 columns, see 64); 16: the 4 x 1 form with a 128-column tile for every N > 64 (default: 64 < N <= 128 only), and in
+ *      FGCN_MATH_BF16 the 4 x 1 forms at all (default there: 2 x 2); 32: never the 128-column 4 x 1 form; 64: the 4 x 1 forms whatever the
+ *      tile count (default: from 1536 192-row tiles on; tests)
+ *   8  fgcn_pw_gemm: 1 = one tile per workgroup (default: persistent workgroups that walk their XCD's tiles; same bits)
  *   10 output stores of the activation-writing kernels: 0 = non-temporal (streamed past L2) when the call writes 96 MiB or more, plain below;
  *      1 = always plain; 2 = always non-temporal (same results in every setting: tests/test_block_model_gpu.py)
- *   11 fgcn_spatial_bwd_tile: 2 = two four-wave workgroups per CU (8-22 % slower; parity-tested); calls with gated addends always run the
- *      eight-wave form
  *   12 joint gram of three equal-width items: 1 = the generic kernel (default: joint_gram3_kernel)
  *   13 fgcn_spatial_wgrad: workgroups to aim for (0 = 512 up to 32 samples, 1024 above)
  *   15 fgcn_spatial_bwd_tile: workgroups to aim for (0 = 256, one per CU; sets the segment count, i.e. the shape of `partial`)
@@ -119,7 +123,11 @@ fgcn_ctx* fgcn_ctx_get_current(void);
  *   21 fgcn_spatial_wgrad_tile / fgcn_emb_wgrad_tile: 2 = 64 x 64 tiles (default: the widest tiles the channels allow)
  *   22 fgcn_emb_fwd_tile: resident workgroups to aim for (0 = 512; sets the segment count)
  *   24 fgcn_rows_gemm*: 1 = the large-problem tiles (256 / 128 rows x the widest column tile) also where they leave fewer than 256
- *      workgroups (small problems otherwise take the smallest tiles that pad no extra column) */
+ *      workgroups (small problems otherwise take the smallest tiles that pad no extra column)
+ *   25 bfloat16 outputs (FGCN_MATH_BF16, half_mask) are stored plainly whatever key 10 says; (bits) 1: fgcn_tconv_halo, 2: fgcn_spatial_fwd_tile
+ *      follow key 10's rule for them too (non-temporal stores of the 32-byte pieces)
+ *   26 (bits) 1: fgcn_bn_act_bwd_reduce on bfloat16 operands (the eight-channels-per-thread kernel) with 256 threads per workgroup instead of
+ *      128 and twice the LDS (a thread then sums other rows: the partial sums differ in their last bits) */
 int fgcn_set_tuning(int key, int value);
 int fgcn_get_tuning(int key);
 
