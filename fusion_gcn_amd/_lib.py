@@ -222,6 +222,9 @@ SIGNATURES = {
     "fgcn_signal_prepare": (_I, [_P] * 6 + [_I] * 5 + [_P]),
     "fgcn_imu_enhance": (_I, [_P] * 7 + [_I] * 7 + [_P]),
     "fgcn_clip_streams": (_I, [_P] * 8 + [_I] * 5 + [_P]),
+    "fgcn_clip_window": (_I, [_P] * 6 + [_I] * 5 + [_F, _F, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
+    "fgcn_window_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, _F, _F, _I, C.POINTER(C.c_float)]),
+    "fgcn_clip_valid_frames": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "fgcn_score_fuse": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _I, _I, _P]),
     "fgcn_fuse_sweep": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
 }
@@ -234,6 +237,7 @@ CE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}       # enum fgcn_ce_reduction
 GUARD_STEP, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM, GUARD_COEF, GUARD_APPLY, GUARD_FIRST_STEP, GUARD_WORDS = range(8)
 GRAD_NORM_MAX_TILES = 512   # FGCN_GRAD_NORM_MAX_TILES
 NORMALIZE_MAX_T = 4096      # FGCN_NORMALIZE_MAX_T
+WINDOW_MODES = {"random": 0, "centre": 1}              # enum fgcn_window_mode
 
 _lib = None
 

@@ -28,14 +28,18 @@ Preparation on the device: ``ClipBatches`` runs the stages it is given, in this 
     the RAW accelerometer / gyroscope recording -- resampled to the skeleton's frame count, zero-padded and min-max normalised
     (``fgcn_signal_prepare``), and with ``enhance=True`` appended as extra joints behind the normalised skeleton (``fgcn_imu_enhance``):
     section 8h;
+  * ``window=Window(frames, ...)`` (ours; the recipe of the two-stream AGCN family's successors): one ``fgcn_clip_window`` call per modality -- a
+    part of the clip's VALID frames, a random one when training and the centred one when evaluating, resized to ``frames`` frames, for
+    which the model is then built (``ClipBatches.shapes``); ``valid_frames`` counts a stored split's valid frames on the device: section 8n;
   * ``augment=Augment(...)`` (ours; the reference has none): one ``fgcn_clip_augment`` call in place of the row gather of each modality --
     random rotation and scale of the joints, a random temporal window resampled to the clip's length -- whose random numbers are keyed
     by (seed, epoch, global sample index): section 8f;
   * ``streams=Streams(parents, ...)`` (the bone and motion inputs 2s-AGCN is trained on; the reference has none): one ``fgcn_clip_streams``
     call per skeleton feature -- joint minus parent joint, frame t+1 minus frame t inside the valid frames, and the motion of the bones,
     of the clip as the stages before left it: section 8j.
-The first two run once at upload on the resident path, the augmentation and the streams on every batch; on the streaming path all run per
-batch, behind the copy.  What ``ClipBatches`` asks of a stage is listed above ``Augment``.
+The first two run once at upload on the resident path -- and so does the window of an evaluation split, which has no random part -- the
+training window, the augmentation and the streams on every batch; on the streaming path all run per batch, behind the copy.  What
+``ClipBatches`` asks of a stage is listed above ``Augment``.
 """
 from __future__ import annotations
 
@@ -169,9 +173,10 @@ Shapes = Dict[str, tuple]       # feature id -> the shape of a sample
 Feats = Dict[str, torch.Tensor]
 Tables = Dict[Optional[str], torch.Tensor]
 
-# A stage of ClipBatches' preparation on the device -- Normalize, Inertial, Augment, Streams, run in that order -- is a configuration object with
+# A stage of ClipBatches' preparation on the device -- Normalize, Inertial, Window, Augment, Streams, run in that order -- is a configuration object with
 #   name        its keyword of ClipBatches, for the refusal of a device without HIP kernels
-#   at_upload   True: a resident split takes it once, at construction; False: every batch does
+#   at_upload   True: a resident split takes it once, at construction; False: every batch does (a class attribute, or one of the instance:
+#               Window(train=False) runs at upload, Window(train=True) per batch)
 #   bind(shapes, n, keys) -> (shapes, writes)   at construction: refuses what the stage cannot take of ``n`` samples of ``shapes`` (as the
 #               stage before left them) in a data set with the feature ids ``keys``; -> the shapes behind the stage and the feature ids
 #               it writes, which are the ones that need an output buffer
@@ -180,11 +185,12 @@ Tables = Dict[Optional[str], torch.Tensor]
 #   run(batches, feats, rows, tables, out) -> feats   launches on the current stream: rows ``rows`` of the arrays ``feats`` into the buffers
 #               ``out`` (feature id -> tensor, or None = a new one); ``tables[name][rows[j]]`` belongs to output row j, except the sample ids,
 #               which are listed by output row; what the stage keeps for inspection goes to ``batches.last_*``.  A per-batch stage that
-#               may run BEHIND another per-batch stage on the resident path (Streams) takes ``rows`` per feature too, {feature id: rows}:
-#               what the stage before wrote holds the batch's rows in order (rows 0..m-1), what it left out is still the resident array
+#               may run BEHIND another per-batch stage on the resident path (Augment behind Window, Streams behind both) takes ``rows`` per
+#               feature too, {feature id: rows}: what the stage before wrote holds the batch's rows in order (rows 0..m-1), what it left out is still the resident array
 #               (the shard's indices).  The rows are handed over per feature rather than the left-out features gathered first: a gather
 #               would be one more pass over rows that the stage's own kernel gathers anyway.
-# A further stage is one more such class and one more entry of ClipBatches' stage list: Streams is the fourth.
+# A further stage is one more such class and one more entry of ClipBatches' stage list: Streams was the fourth, Window is the fifth (it runs
+# third: in front of the rotation, which then touches W frames instead of T, and of the streams, whose motion is the windowed clip's).
 
 
 class Augment:
@@ -252,14 +258,16 @@ class Augment:
         valid = {k: np.asarray(self.valid_frames[k]).astype(np.int32) for k in writes if k in self.valid_frames}
         return {None: np.arange(n, dtype=np.int64), **valid}
 
-    def run(self, batches: "ClipBatches", feats: Feats, rows: torch.Tensor, tables: Tables, out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+    def run(self, batches: "ClipBatches", feats: Feats, rows: Union[torch.Tensor, Dict[str, torch.Tensor]], tables: Tables,
+            out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        """``rows`` per feature where the stage before (a per-batch ``Window``) wrote some features and not others (see the protocol above)"""
         from . import ops
         feats = dict(feats)
         for k, o in out.items():
             src = feats[k]
             feats[k], batches.last_params[k] = ops.clip_augment(
-                src, rows, tables[None], seed=batches.seed, epoch=batches.epoch, site=self.site, max_angle=self.max_angle, scale=self.scale,
-                min_window=self.min_window, joints=self.joint_range(src.shape[1:]), valid=tables.get(k), out=o)
+                src, rows[k] if isinstance(rows, dict) else rows, tables[None], seed=batches.seed, epoch=batches.epoch, site=self.site,
+                max_angle=self.max_angle, scale=self.scale, min_window=self.min_window, joints=self.joint_range(src.shape[1:]), valid=tables.get(k), out=o)
         return feats
 
 
@@ -547,7 +555,114 @@ class Streams:
         return res
 
 
-NORMALIZE_CHUNK = 2048      # clips per call when a resident split is normalised and prepared at upload
+class Window:
+    """What ``ClipBatches(window=...)`` does to every clip it hands out (include/fgcn.h): a part of the clip's VALID
+    frames, linearly interpolated to a window of ``frames`` frames -- the model is built for the window (``ClipBatches.shapes``), not for the
+    stored T.
+
+    ``frames``: the window's length W, an int for every modality or a mapping feature id -> int for modalities with different T (the
+    window then applies to the ids it names).  ``interval = (lo, hi)``, ``0 < lo <= hi <= 1``: the part's length as a fraction of the
+    recording.  ``train=True``: the length is uniform in the interval and the start uniform in what is left, drawn per (seed, epoch, clip)
+    as ``Augment`` draws -- from the counter word ``Augment`` leaves free, so the two are independent at one ``site`` -- on every batch.
+    ``train=False``: the centred part of length ``hi``, no random numbers; a resident split is windowed ONCE, at construction, and then
+    takes W / T of the memory.  All modalities of a sample take the same part of the recording.  ``valid_frames``: feature id -> the number
+    of valid frames of each sample (``data.valid_frames`` counts them; default: all T).  ``only``: the feature ids to window (default: all,
+    or the ids ``frames`` names); the others keep their T."""
+
+    name = "window"
+
+    def __init__(self, frames: Union[int, Mapping[str, int]], interval: Sequence[float] = (0.5, 1.0), train: bool = True,
+                 valid_frames: Optional[Mapping[str, Sequence[int]]] = None, only: Optional[Iterable[str]] = None, site: int = 0):
+        def count(w) -> int:
+            if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or w < 1:
+                raise ValueError(f"frames={frames!r}: expected a frame count >= 1, or one per feature id")
+            return int(w)
+        self.frames = {str(k): count(w) for k, w in frames.items()} if isinstance(frames, Mapping) else count(frames)
+        if isinstance(self.frames, dict) and not self.frames:
+            raise ValueError("frames={}: the window applies to no feature")
+        interval = tuple(float(x) for x in interval)
+        if len(interval) != 2 or not all(np.isfinite(interval)) or not 0.0 < interval[0] <= interval[1] <= 1.0:
+            raise ValueError(f"interval={interval!r}: expected (lo, hi) with 0 < lo <= hi <= 1")
+        self.interval, self.train, self.site = interval, bool(train), int(site)
+        self.mode = "random" if self.train else "centre"
+        self.at_upload = not self.train                     # nothing random in the centred part: a resident split takes it once
+        self.valid_frames = dict(valid_frames or {})
+        self.only = None if only is None else frozenset(only)
+        if self.only is not None and isinstance(self.frames, dict) and not self.only <= set(self.frames):
+            raise ValueError(f"only={sorted(self.only)} names features that frames={self.frames!r} gives no length")
+
+    def applies_to(self, feature_id: str) -> bool:
+        return (self.only is None or feature_id in self.only) and (not isinstance(self.frames, dict) or feature_id in self.frames)
+
+    def length(self, feature_id: str) -> int:
+        return self.frames[feature_id] if isinstance(self.frames, dict) else self.frames
+
+    def bind(self, shapes: Shapes, n: int, keys: Sequence[str]) -> Tuple[Shapes, List[str]]:
+        named = set(self.valid_frames) | set(self.only or ()) | set(self.frames if isinstance(self.frames, dict) else ())
+        if named - set(keys):
+            raise ValueError(f"window names features the data set does not have: {sorted(named - set(keys))}")
+        if named - set(shapes):
+            raise ValueError(f"window names features that are not in the batch at this stage: {sorted(named - set(shapes))}")
+        writes = [k for k in shapes if self.applies_to(k)]
+        stale = sorted(set(self.valid_frames) - set(writes))
+        if stale:
+            raise ValueError(f"window: valid_frames{stale} for features the window does not apply to")
+        after = dict(shapes)
+        for k in writes:
+            shape = shapes[k]
+            if len(shape) not in (2, 4):
+                raise FgcnError(f"window: feature {k!r} has shape {(n, *shape)}; expected (samples, M, T, V, C) or (samples, T, S) -- leave it "
+                                f"out with Window(only=...)")
+            t_axis = 0 if len(shape) == 2 else 1
+            if k in self.valid_frames:
+                v = np.asarray(self.valid_frames[k])
+                if v.shape != (n,) or v.dtype.kind not in "iu" or v.min() < 1 or v.max() > shape[t_axis]:
+                    raise ValueError(f"valid_frames[{k!r}]: expected {n} frame counts in [1, {shape[t_axis]}]")
+            after[k] = (*shape[:t_axis], self.length(k), *shape[t_axis + 1:])
+        return after, writes
+
+    def tables(self, writes: Sequence[str], n: int) -> Dict[Optional[str], np.ndarray]:
+        """None: the clips' ids, which key the random numbers (the centred part has none); feature id: the valid frames of its clips"""
+        valid = {k: np.asarray(self.valid_frames[k]).astype(np.int32) for k in writes if k in self.valid_frames}
+        return {None: np.arange(n, dtype=np.int64), **valid} if self.train else valid
+
+    def run(self, batches: "ClipBatches", feats: Feats, rows: Union[torch.Tensor, Dict[str, torch.Tensor]], tables: Tables,
+            out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        from . import ops
+        feats = dict(feats)
+        for k, o in out.items():
+            feats[k], batches.last_window[k] = ops.clip_window(
+                feats[k], rows[k] if isinstance(rows, dict) else rows, tables[None] if self.train else None, window=self.length(k),
+                interval=self.interval, mode=self.mode, seed=batches.seed, epoch=batches.epoch, site=self.site, valid=tables.get(k), out=o)
+        return feats
+
+
+NORMALIZE_CHUNK = 2048      # clips per call when a resident split is normalised, prepared and windowed at upload
+
+
+def valid_frames(dataset: MultiModalDataset, feature_id: str, device: Union[str, torch.device] = "cuda",
+                 chunk: int = NORMALIZE_CHUNK) -> np.ndarray:
+    """-> (n,) int32: the valid frames of every sample of feature ``feature_id`` of ``dataset`` -- 1 + the last frame in which any body holds
+    a value that is not zero, 1 for a clip that holds none (``fgcn_clip_valid_frames``, include/fgcn.h) -- the table ``Window``, ``Augment``
+    and ``Streams`` take as ``valid_frames[feature_id]`` (the reference's feature files do not hold it).  One pass over the stored array
+    in chunks of ``chunk`` clips: upload, count on the device, download; a memory-mapped split is read once, front to back, and never
+    held in memory as a whole.  Count the STORED clips of a raw split: ``Normalize`` repeats the valid frames up to T."""
+    from . import ops
+    if feature_id not in dataset.features_data:
+        raise ValueError(f"valid_frames: the data set has no feature {feature_id!r} (it has {sorted(dataset.features_data)})")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise FgcnError("valid_frames runs a HIP kernel and needs a 'cuda' device: there is no host fallback")
+    if chunk < 1:
+        raise ValueError(f"chunk={chunk}")
+    array, n = dataset.features_data[feature_id][1], len(dataset)
+    if array.ndim not in (3, 5):
+        raise FgcnError(f"valid_frames: feature {feature_id!r} has shape {tuple(array.shape)}; expected (samples, M, T, V, C) or (samples, T, S)")
+    out = np.empty(n, dtype=np.int32)
+    for lo in range(0, n, chunk):
+        clips = torch.from_numpy(np.array(array[lo:min(lo + chunk, n)], dtype=np.float32)).to(device)
+        out[lo:lo + len(clips)] = ops.clip_valid_frames(clips).cpu().numpy()
+    return out
 
 
 class ClipBatches:
@@ -567,12 +682,17 @@ class ClipBatches:
     a pure function of (``seed``, the epoch ``set_epoch`` set, the clip's index in the data set) -- labels and ``indices`` are
     untouched; ``last_params`` (feature id -> (clips, 12) tensor) keeps the parameter tables of the last batch.  ``streams``: a
     ``Streams`` = the last stage, on every batch: the skeleton features it names come out as their bone / motion streams (under the ids its
-    docstring lists); ``last_streams`` (feature id -> the ids it came out under) keeps the map of the last batch."""
+    docstring lists); ``last_streams`` (feature id -> the ids it came out under) keeps the map of the last batch.  ``window``: a ``Window`` =
+    the third stage, behind ``inertial`` and in front of ``augment``: every clip of the modalities it names comes out as a part of its valid
+    frames resized to the window's W frames -- ``shapes`` then holds W, and the model is built from ``shapes``; with ``train=False`` a
+    resident split is windowed once, at construction (``dev_feat`` holds W frames); ``last_window`` (feature id -> (clips, 2) tensor)
+    keeps the ``(o, r)`` table of the last call.  None, the default: no such stage, and every call issued is what it was."""
 
     def __init__(self, dataset: MultiModalDataset, batch_size: int, *, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
                  resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None,
-                 normalize: Optional[Normalize] = None, inertial: Optional[Inertial] = None, streams: Optional[Streams] = None):
+                 normalize: Optional[Normalize] = None, inertial: Optional[Inertial] = None, streams: Optional[Streams] = None,
+                 window: Optional[Window] = None):
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
@@ -588,9 +708,14 @@ class ClipBatches:
         self.resident = nbytes <= resident_budget if resident is None else bool(resident)
         self.labels = torch.from_numpy(np.asarray(dataset.labels_data).astype(np.int64))
         on_gpu = self.device.type == "cuda"
-        self.normalize, self.inertial, self.augment, self.streams = normalize, inertial, augment, streams
-        self.stages = [s for s in (normalize, inertial, augment, streams) if s is not None]      # in the order they run
-        self.last_plan, self.last_inertial, self.last_params, self.last_streams = {}, None, {}, {}
+        self.normalize, self.inertial, self.window, self.augment, self.streams = normalize, inertial, window, augment, streams
+        self.stages = [s for s in (normalize, inertial, window, augment, streams) if s is not None]      # in the order they run
+        self.last_plan, self.last_inertial, self.last_params, self.last_streams, self.last_window = {}, None, {}, {}, {}
+        for later in (augment, streams):
+            stale = sorted(k for k in later.valid_frames if window.applies_to(k)) if window is not None and later is not None else []
+            if stale:                                       # the windowed clip fills all W frames: the table no longer describes it
+                raise ValueError(f"{later.name}: valid_frames{stale} behind a Window that resizes these features to frames that are all valid "
+                                 f"-- give the table to the Window alone")
         if streams is not None and augment is not None:
             stale = sorted(k for k in streams.valid_frames if augment.applies_to(k))
             if stale:                                       # the augmented clip fills all T frames: the table no longer describes it

@@ -2142,6 +2142,85 @@ def clip_streams(src: torch.Tensor, idx: torch.Tensor, parents, *, streams: Sequ
     return res
 
 
+# ---- a part of the valid frames resized to a window as the batch is gathered (fgcn_clip_window / fgcn_clip_valid_frames) ----
+def _window_scalars(interval, mode: str):
+    if mode not in _lib.WINDOW_MODES:
+        raise _lib.FgcnError(f"window: mode {mode!r}, expected one of {sorted(_lib.WINDOW_MODES)}")
+    if len(interval) != 2:
+        raise _lib.FgcnError(f"window: interval needs two fractions (lo, hi), got {interval!r}")
+    return float(interval[0]), float(interval[1]), _lib.WINDOW_MODES[mode]
+
+
+def _clip_dims(src: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    """(outer, T, inner) of a (rows, M, T, V, C) or (rows, T, S) array"""
+    if src.dim() == 5:
+        return src.shape[1], src.shape[2], src.shape[3] * src.shape[4]
+    if src.dim() == 3:
+        return 1, src.shape[1], src.shape[2]
+    raise _lib.FgcnError(f"{name}: expected (rows, M, T, V, C) or (rows, T, S), got {tuple(src.shape)}")
+
+
+def window_params(sample: int, site: int, epoch: int, seed: int, interval=(1.0, 1.0), mode: str = "random") -> list:
+    """The table row of one sample on the HOST (no device is touched): [o, r], by the function the kernel calls."""
+    lo, hi, mode = _window_scalars(interval, mode)
+    out = (ctypes.c_float * 2)()
+    check(_lib.load().fgcn_window_params(int(sample) & 0xFFFFFFFF, int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, lo, hi, mode, out), "fgcn_window_params")
+    return list(out)
+
+
+def clip_window(src: torch.Tensor, idx: torch.Tensor, sample_ids: Optional[torch.Tensor], *, window: int, interval=(1.0, 1.0),
+                mode: str = "random", seed: int = 0, epoch: int = 0, site: int = 0, valid: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None):
+    """-> (out, params): out[k] = the part ``[o, o + r]`` of the valid frames of source row ``idx[k]`` of ``src``, linearly interpolated to
+    ``window`` frames (include/fgcn.h); params (b, 2): the rows' ``o`` and ``r``, fractions of the recording.  mode "random": ``r`` uniform
+    in ``interval``, ``o`` uniform in what is left, from the random numbers of sample ``sample_ids[k]`` in ``epoch``; "centre": ``r`` =
+    ``interval[1]``, centred, and ``sample_ids`` may be None.  src: (rows, M, T, V, C) or (rows, T, S) contiguous float32 on the device;
+    out: (b, M, window, V, C) or (b, window, S); idx, sample_ids: (b) int64 -- on the device, where ``idx`` is trusted to hold rows of
+    ``src``, or on the host, where it is checked and uploaded; valid: None or (rows) int32 on the device, the valid frames of each SOURCE
+    row (``clip_valid_frames`` counts them)."""
+    ensure_device()
+    _chk(src, "clip_window.src")
+    outer, T, inner = _clip_dims(src, "clip_window.src")
+    lo, hi, mode_id = _window_scalars(interval, mode)
+    W = int(window)
+    if W <= 0:
+        raise _lib.FgcnError(f"clip_window: window={window!r}, expected a frame count >= 1")
+    idx = _rows(idx, src.shape[0], src.device, "clip_window.idx")
+    b = idx.numel()
+    if sample_ids is not None:
+        if sample_ids.dtype != torch.int64 or sample_ids.dim() != 1 or sample_ids.numel() != b:
+            raise _lib.FgcnError(f"clip_window.sample_ids: expected ({b},) int64, got {tuple(sample_ids.shape)} {sample_ids.dtype}")
+        sample_ids = sample_ids.to(src.device).contiguous()
+    elif mode != "centre":
+        raise _lib.FgcnError("clip_window.sample_ids: None, which only mode 'centre' takes")
+    if valid is not None:
+        _lengths(valid, src.shape[0], "clip_window.valid")
+    shape = (b, src.shape[1], W, *src.shape[3:]) if src.dim() == 5 else (b, W, src.shape[2])
+    out = _batch_out(out, shape, src.device, "clip_window.out")
+    params = torch.empty((b, 2), device=src.device, dtype=torch.float32)
+    check(_lib.load().fgcn_clip_window(_p(src), idx.data_ptr(), None if sample_ids is None else sample_ids.data_ptr(), _p(valid), _p(out),
+                                       _p(params), b, outer, T, W, inner, lo, hi, mode_id, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                       int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, _stream()), "fgcn_clip_window")
+    return out, params
+
+
+def clip_valid_frames(src: torch.Tensor, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> (b) int32 on the device: the valid frames of source rows ``idx`` of ``src`` (default: of every row) -- 1 + the last frame in
+    which any body holds a value that is not zero (-0 is zero, a NaN is a value), 1 for a clip that holds none (include/fgcn.h).  src:
+    (rows, M, T, V, C) or (rows, T, S) contiguous float32 on the device; idx: (b) int64 on the device (trusted) or on the host (checked)."""
+    ensure_device()
+    _chk(src, "clip_valid_frames.src")
+    outer, T, inner = _clip_dims(src, "clip_valid_frames.src")
+    if idx is None:
+        idx = torch.arange(src.shape[0], dtype=torch.int64, device=src.device)
+    idx = _rows(idx, src.shape[0], src.device, "clip_valid_frames.idx")
+    b = idx.numel()
+    out = torch.empty((b,), device=src.device, dtype=torch.int32)
+    check(_lib.load().fgcn_clip_valid_frames(_p(src), idx.data_ptr(), out.data_ptr(), b, outer, T, inner, _stream()), "fgcn_clip_valid_frames")
+    return out
+
+
 # ---- score fusion of separately trained stream models (fgcn_score_fuse / fgcn_fuse_sweep; DESIGN.md section 8k) -----------------------------
 def _fuse_in(what: str, scores: Sequence[torch.Tensor]):
     """-> (FuseIn without weights, S, rows, classes, device) of the stream models' score tensors: float32 (rows, classes) on one device,

@@ -1157,6 +1157,58 @@ int fgcn_imu_enhance(const float* skel, const long long* skel_idx, const float* 
 int fgcn_clip_streams(const float* src, const long long* idx, const int* parents, const int* valid, float* joint, float* bone, float* motion,
                       float* bone_motion, int b, int M, int T, int V, int C, void* stream);
 
+/* A clip cropped to a part of its valid frames and resized to a window of W frames as the batch is gathered (data.ClipBatches(window=...);
+ * DESIGN.md section 8n): the recipe of the two-stream AGCN family's successors -- a random part when training, the centred one when
+ * evaluating, and a model built for W frames instead of the stored T.  fgcn_clip_augment's conventions: a sample is (outer, T, inner)
+ * float32, row k of `out` is made of source row idx[k], the random numbers are a pure function of (seed, site, epoch, sample_ids[k]), a word
+ * w gives the uniform u = (float)(w >> 8) * 2^-24, all arithmetic is float32 with every product and sum rounded on its own unless an fma
+ * is named.
+ *
+ * Parameters (the table row of the sample, 2 floats {o, r}: the part [o, o + r] of the recording, as fractions of it), with
+ * interval = (lo, hi), 0 < lo <= hi <= 1:
+ *     FGCN_WINDOW_RANDOM:  u0, u1 = words 0, 1 of ONE Philox block, philox(ctr = {(unsigned)sample, site, epoch, 2}, key = {lo32(seed),
+ *                          hi32(seed)}) -- fgcn_clip_augment uses counter words 0 and 1 at the same (seed, site), so the crop is
+ *                          independent of the rotation without a second site;
+ *                          r = min(lo + u0 * (hi - lo), hi);   o = min(u1 * (1 - r), 1 - r), the first 1 - r formed as
+ *                          (1 - hi) + (1 - u0) * (hi - lo) (1 - u0 is exact and no term is negative; exactly 0 for lo = hi = 1), the
+ *                          second as the one subtraction.  The two min() act on the last rounding alone: lo <= r <= hi and o + r <= 1
+ *                          (to the rounding of that sum) hold for every draw.
+ *     FGCN_WINDOW_CENTRE:  r = hi;   o = (1 - r) * 0.5.  No random numbers: seed, site, epoch and sample_ids are ignored.
+ * interval = (1, 1) gives exactly o = 0 and r = 1 in both modes.
+ *
+ * Output frame t, 0 <= t < W, all of `inner`: v = valid[idx[k]] (valid == NULL: T; a value outside [1, T] is clamped into it),
+ *     pos = (o + r * t / (W - 1)) * (v - 1), formed as fma(r * t, (v - 1) / (W - 1), o * (v - 1)) (the quotient counts as 0 for W == 1);
+ *     f0 = floor(pos) clamped to [0, v - 1], f1 = min(f0 + 1, v - 1), w = pos - f0, y = fma(w, x[f1] - x[f0], x[f0]).
+ * No frame at or behind v, and so no frame T behind a row, is ever read.  W may be smaller than, equal to or larger than T.
+ * Identity: with W == T, interval = (1, 1) and valid == NULL (or T), in either mode, pos == t and w == 0 exactly and `out` equals the
+ * gathered rows bit for bit.
+ * Non-finite inputs: rule 3 of "Non-finite values in the inputs" above -- an output that reads a non-finite value (x[f0] or x[f1], whatever
+ * w is: 0 * inf and inf - inf are NaN) is non-finite, NaN against +-inf need not match; an output that reads none is what it is on finite data.
+ *
+ * fgcn_clip_window: src (rows, outer, T, inner), idx / sample_ids (b) 8-byte integers on the device (idx may repeat and need not be sorted;
+ * every idx[k] must be a row of src -- the caller's duty; the streaming path passes idx = 0..b-1 and the real ids), valid NULL or 4-byte
+ * integers indexed by SOURCE row, out (b, outer, W, inner), params (b, 2) receives the table.  Two launches: one lane per row forms the
+ * table, then one lane per output element reads it back.  Rows need 4-byte alignment only.
+ * FGCN_E_BADARG before any launch: a null pointer (valid excepted, and sample_ids in mode CENTRE); b, outer, T, W or inner <= 0; an
+ * interval outside 0 < lo <= hi <= 1 or not finite; an unknown mode; out == src; W * inner >= 2^29 (a lane's index inside a body) or more
+ * workgroups than one grid holds.
+ *
+ * fgcn_window_params: the HOST copy of the table row (no device is touched), computed by the function the kernel calls: there is no
+ * transcendental function and contraction is off, so the device's row has the same bits.  The same refusals for its arguments.
+ *
+ * fgcn_clip_valid_frames: out[k] (4-byte integers on the device) = 1 + the largest t for which frame t of ANY of the `outer` bodies of
+ * source row idx[k] is not null, under fgcn_clip_normalize's definition: a frame of a body is null when all its `inner` values are zero
+ * (-0 counts as zero, a NaN as a value).  A null frame in front of a later frame that holds a value does not end the clip; a clip
+ * without a value gives 1, so the table lies in [1, T] and is what `valid` above, fgcn_clip_augment and fgcn_clip_streams take.  One
+ * launch, one workgroup per row, no atomics; 4-byte loads.  FGCN_E_BADARG before any launch: a null pointer; b, outer, T or inner <= 0;
+ * T * inner >= 2^29. */
+enum fgcn_window_mode { FGCN_WINDOW_RANDOM = 0, FGCN_WINDOW_CENTRE = 1 };
+int fgcn_clip_window(const float* src, const long long* idx, const long long* sample_ids, const int* valid, float* out, float* params, int b,
+                     int outer, int T, int W, int inner, float lo, float hi, int mode, unsigned long long seed, unsigned site, unsigned epoch,
+                     void* stream);
+int fgcn_window_params(unsigned sample, unsigned site, unsigned epoch, unsigned long long seed, float lo, float hi, int mode, float out2[2]);
+int fgcn_clip_valid_frames(const float* src, const long long* idx, int* out, int b, int outer, int T, int inner, void* stream);
+
 /* Score fusion of separately trained stream models (ops.score_fuse / ops.fuse_sweep, ensemble.StreamEnsemble / ScoreStore; DESIGN.md
  * section 8k): the 2s-AGCN family reports the accuracy of the weighted sum of its stream models' class scores.
  *
