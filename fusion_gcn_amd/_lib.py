@@ -218,6 +218,7 @@ SIGNATURES = {
     "fgcn_clip_augment": (_I, [_P] * 6 + [_I] * 7 + [C.POINTER(C.c_float), _F, _F, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "fgcn_augment_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, C.POINTER(C.c_float), _F, _F, C.POINTER(C.c_float)]),
     "fgcn_clip_normalize": (_I, [_P] * 5 + [_I] * 10 + [_P]),
+    "fgcn_clip_bodies": (_I, [_P] * 5 + [_I] * 6 + [_P]),
     "fgcn_resample_index": (_I, [_I, _I, _I, C.POINTER(C.c_int)]),
     "fgcn_signal_prepare": (_I, [_P] * 6 + [_I] * 5 + [_P]),
     "fgcn_imu_enhance": (_I, [_P] * 7 + [_I] * 7 + [_P]),
@@ -237,6 +238,8 @@ CE_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}       # enum fgcn_ce_reduction
 GUARD_STEP, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM, GUARD_COEF, GUARD_APPLY, GUARD_FIRST_STEP, GUARD_WORDS = range(8)
 GRAD_NORM_MAX_TILES = 512   # FGCN_GRAD_NORM_MAX_TILES
 NORMALIZE_MAX_T = 4096      # FGCN_NORMALIZE_MAX_T
+BODIES_MAX = 16             # FGCN_BODIES_MAX
+BODIES_MAX_T = 524288       # FGCN_BODIES_MAX_T
 WINDOW_MODES = {"random": 0, "centre": 1}              # enum fgcn_window_mode
 
 _lib = None

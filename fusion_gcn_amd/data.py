@@ -21,6 +21,10 @@ Data-parallel ranks take contiguous shards of every global batch (``dp.shard_bat
 seed.  torch is plumbing here (pinned memory, streams, index_select); without a stage (below) nothing on this path calls the HIP kernels.
 
 Preparation on the device: ``ClipBatches`` runs the stages it is given, in this order, each a HIP kernel of libfgcn (no host fallback)
+  * ``bodies=Bodies(...)`` (reference: datasets/ntu_rgb_d/io.py:SkeletonSample._filter_bodies, an offline per-clip loop): the tracker's
+    bodies of a RAW skeleton clip scored by the spread of their joints, and the most energetic ones kept, in descending order, with
+    ``fgcn_clip_bodies`` -- FIRST, since every later stage must see the selected bodies (``Normalize`` centres the clip by body 0):
+    section 8o;
   * ``normalize=Normalize(...)`` (reference: util/preprocessing/skeleton.py:normalize_skeleton, an offline per-clip loop): RAW skeleton
     clips -- null frames padded, the centre joint of the first body at the origin, spine to z, shoulders to x -- with
     ``fgcn_clip_normalize``: DESIGN.md section 8g;
@@ -37,7 +41,7 @@ Preparation on the device: ``ClipBatches`` runs the stages it is given, in this 
   * ``streams=Streams(parents, ...)`` (the bone and motion inputs 2s-AGCN is trained on; the reference has none): one ``fgcn_clip_streams``
     call per skeleton feature -- joint minus parent joint, frame t+1 minus frame t inside the valid frames, and the motion of the bones,
     of the clip as the stages before left it: section 8j.
-The first two run once at upload on the resident path -- and so does the window of an evaluation split, which has no random part -- the
+The first three run once at upload on the resident path -- and so does the window of an evaluation split, which has no random part -- the
 training window, the augmentation and the streams on every batch; on the streaming path all run per batch, behind the copy.  What
 ``ClipBatches`` asks of a stage is listed above ``Augment``.
 """
@@ -173,7 +177,7 @@ Shapes = Dict[str, tuple]       # feature id -> the shape of a sample
 Feats = Dict[str, torch.Tensor]
 Tables = Dict[Optional[str], torch.Tensor]
 
-# A stage of ClipBatches' preparation on the device -- Normalize, Inertial, Window, Augment, Streams, run in that order -- is a configuration object with
+# A stage of ClipBatches' preparation on the device -- Bodies, Normalize, Inertial, Window, Augment, Streams, run in that order -- is a configuration object with
 #   name        its keyword of ClipBatches, for the refusal of a device without HIP kernels
 #   at_upload   True: a resident split takes it once, at construction; False: every batch does (a class attribute, or one of the instance:
 #               Window(train=False) runs at upload, Window(train=True) per batch)
@@ -191,6 +195,8 @@ Tables = Dict[Optional[str], torch.Tensor]
 #               would be one more pass over rows that the stage's own kernel gathers anyway.
 # A further stage is one more such class and one more entry of ClipBatches' stage list: Streams was the fourth, Window is the fifth (it runs
 # third: in front of the rotation, which then touches W frames instead of T, and of the streams, whose motion is the windowed clip's).
+# Bodies is the sixth, it runs first: it decides what body 0 is, by which Normalize centres and rotates the clip, and how many body slots
+# every later stage and the model see.
 
 
 class Augment:
@@ -268,6 +274,67 @@ class Augment:
             feats[k], batches.last_params[k] = ops.clip_augment(
                 src, rows[k] if isinstance(rows, dict) else rows, tables[None], seed=batches.seed, epoch=batches.epoch, site=self.site,
                 max_angle=self.max_angle, scale=self.scale, min_window=self.min_window, joints=self.joint_range(src.shape[1:]), valid=tables.get(k), out=o)
+        return feats
+
+
+class Bodies:
+    """What ``ClipBatches(bodies=...)`` does to every raw skeleton clip (include/fgcn.h): the reference's
+    ``SkeletonSample._filter_bodies`` -- of the ``Mr`` bodies the tracker lists, the ``bodies`` with the highest ``body_score`` (the sum
+    over the channels of the standard deviation of the body's non-null frames), in descending order; a NaN score ranks first, equal
+    scores by the higher source index.  The (samples, Mr, T, V, C) arrays it applies to come out as (bodies, T, V, C).  ``only``: the
+    feature ids to select in (default: all); the others are handed out as stored."""
+
+    def __init__(self, bodies: int = 2, only: Optional[Iterable[str]] = None):
+        from ._lib import BODIES_MAX
+        if isinstance(bodies, bool) or not isinstance(bodies, (int, np.integer)) or not 1 <= bodies <= BODIES_MAX:
+            raise ValueError(f"bodies={bodies!r}: expected a number of bodies in [1, {BODIES_MAX}]")
+        self.bodies = int(bodies)
+        self.only = None if only is None else frozenset(only)
+
+    @classmethod
+    def for_dataset(cls, name: str, only: Optional[Iterable[str]] = None) -> "Bodies":
+        """The reference's number of bodies for a data set (``max_body_true`` of its constants module: ``"ntu_rgb_d"`` has one)."""
+        from .util.dynamic_import import import_dataset_constants
+        got = import_dataset_constants(name, ["max_body_true"])
+        if len(got) != 1:
+            raise ValueError(f"data set {name!r} has no max_body_true constant")
+        return cls(got[0], only=only)
+
+    def applies_to(self, feature_id: str) -> bool:
+        return self.only is None or feature_id in self.only
+
+    name, at_upload = "bodies", True
+
+    def bind(self, shapes: Shapes, n: int, keys: Sequence[str]) -> Tuple[Shapes, List[str]]:
+        from ._lib import BODIES_MAX
+        unknown = set(self.only or ()) - set(keys)
+        if unknown:
+            raise ValueError(f"bodies names features the data set does not have: {sorted(unknown)}")
+        writes = [k for k in shapes if self.applies_to(k)]
+        after = dict(shapes)
+        for k in writes:
+            shape = shapes[k]
+            if len(shape) != 4:
+                raise FgcnError(f"bodies: feature {k!r} has shape {(n, *shape)}; expected (samples, Mr, T, V, C) -- leave it out with "
+                                f"Bodies(only=...)")
+            if shape[0] < self.bodies:
+                raise FgcnError(f"bodies: feature {k!r} holds {shape[0]} bodies, {self.bodies} are to be kept")
+            if shape[0] > BODIES_MAX:
+                raise FgcnError(f"bodies: feature {k!r} holds {shape[0]} bodies, at most {BODIES_MAX}")
+            if shape[3] not in (2, 3):
+                raise FgcnError(f"bodies: feature {k!r} has {shape[3]} coordinates; expected 2 or 3")
+            after[k] = (self.bodies, *shape[1:])
+        return after, writes
+
+    def tables(self, writes: Sequence[str], n: int) -> Dict[Optional[str], np.ndarray]:
+        return {}
+
+    def run(self, batches: "ClipBatches", feats: Feats, rows: torch.Tensor, tables: Tables, out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        from . import ops
+        feats = dict(feats)
+        for k, o in out.items():
+            feats[k], order, scores = ops.clip_bodies(feats[k], rows, bodies=self.bodies, out=o)
+            batches.last_bodies[k] = (order, scores)
         return feats
 
 
@@ -641,12 +708,14 @@ NORMALIZE_CHUNK = 2048      # clips per call when a resident split is normalised
 
 
 def valid_frames(dataset: MultiModalDataset, feature_id: str, device: Union[str, torch.device] = "cuda",
-                 chunk: int = NORMALIZE_CHUNK) -> np.ndarray:
+                 chunk: int = NORMALIZE_CHUNK, bodies: Optional[Bodies] = None) -> np.ndarray:
     """-> (n,) int32: the valid frames of every sample of feature ``feature_id`` of ``dataset`` -- 1 + the last frame in which any body holds
     a value that is not zero, 1 for a clip that holds none (``fgcn_clip_valid_frames``, include/fgcn.h) -- the table ``Window``, ``Augment``
     and ``Streams`` take as ``valid_frames[feature_id]`` (the reference's feature files do not hold it).  One pass over the stored array
     in chunks of ``chunk`` clips: upload, count on the device, download; a memory-mapped split is read once, front to back, and never
-    held in memory as a whole.  Count the STORED clips of a raw split: ``Normalize`` repeats the valid frames up to T."""
+    held in memory as a whole.  Count the STORED clips of a raw split: ``Normalize`` repeats the valid frames up to T.  ``bodies``: the
+    ``Bodies`` that ``ClipBatches`` is given -- the count is then taken over the bodies it selects (``fgcn_clip_bodies``, then the count,
+    chunk by chunk on the device): a dropped body that outlives the kept ones does not stretch the table."""
     from . import ops
     if feature_id not in dataset.features_data:
         raise ValueError(f"valid_frames: the data set has no feature {feature_id!r} (it has {sorted(dataset.features_data)})")
@@ -658,9 +727,15 @@ def valid_frames(dataset: MultiModalDataset, feature_id: str, device: Union[str,
     array, n = dataset.features_data[feature_id][1], len(dataset)
     if array.ndim not in (3, 5):
         raise FgcnError(f"valid_frames: feature {feature_id!r} has shape {tuple(array.shape)}; expected (samples, M, T, V, C) or (samples, T, S)")
+    if bodies is not None:
+        if not bodies.applies_to(feature_id):
+            raise ValueError(f"valid_frames: bodies does not apply to feature {feature_id!r}")
+        bodies.bind({feature_id: tuple(array.shape[1:])}, n, list(dataset.features_data))      # (refuses what the selection cannot take)
     out = np.empty(n, dtype=np.int32)
     for lo in range(0, n, chunk):
         clips = torch.from_numpy(np.array(array[lo:min(lo + chunk, n)], dtype=np.float32)).to(device)
+        if bodies is not None:
+            clips = ops.clip_bodies(clips, torch.arange(len(clips), dtype=torch.int64, device=device), bodies=bodies.bodies)[0]
         out[lo:lo + len(clips)] = ops.clip_valid_frames(clips).cpu().numpy()
     return out
 
@@ -673,8 +748,12 @@ class ClipBatches:
     same permutation on every rank.  ``resident``: True / False, or None = upload the split when it takes at most
     ``resident_budget`` bytes.  Features come out float32, labels int64 (session.py:171-174).
 
-    ``normalize``, ``inertial``, ``augment``: None = the stored clips as they are; otherwise the stages (``self.stages``) run on the
-    device in that order, each on what the one before left: ``shapes`` holds the sample shapes behind the last, ``out_keys`` their ids.
+    ``bodies``, ``normalize``, ``inertial``, ``augment``: None = the stored clips as they are; otherwise the stages (``self.stages``) run on
+    the device in that order, each on what the one before left: ``shapes`` holds the sample shapes behind the last, ``out_keys`` their ids.
+    A ``Bodies`` = the FIRST stage: of the Mr bodies of the (samples, Mr, T, V, C) arrays it names, the M most energetic come out, in
+    descending order -- ``shapes`` then holds M, and the model is built from ``shapes``; ``last_bodies`` (feature id -> (order, scores))
+    keeps the tables of the last call.  A resident split is selected once, at construction (``dev_feat`` then holds M / Mr of the stored
+    bytes; whether a split is resident is still decided on the STORED size, which is what the upload holds until the selection is done).
     A ``Normalize`` = the (samples, M, T, V, C) arrays it names hold RAW skeletons; ``last_plan`` (feature id -> (frame_map, params))
     keeps the tables of the last call.  An ``Inertial`` = the signal it names holds RAW recordings; ``last_inertial`` keeps the (clips, 2)
     minimum / maximum table of the last call.  Both take a resident split once, at construction (``dev_feat`` then holds the prepared
@@ -692,7 +771,7 @@ class ClipBatches:
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
                  resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None,
                  normalize: Optional[Normalize] = None, inertial: Optional[Inertial] = None, streams: Optional[Streams] = None,
-                 window: Optional[Window] = None):
+                 window: Optional[Window] = None, bodies: Optional[Bodies] = None):
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
@@ -709,8 +788,10 @@ class ClipBatches:
         self.labels = torch.from_numpy(np.asarray(dataset.labels_data).astype(np.int64))
         on_gpu = self.device.type == "cuda"
         self.normalize, self.inertial, self.window, self.augment, self.streams = normalize, inertial, window, augment, streams
-        self.stages = [s for s in (normalize, inertial, window, augment, streams) if s is not None]      # in the order they run
+        self.bodies = bodies
+        self.stages = [s for s in (bodies, normalize, inertial, window, augment, streams) if s is not None]      # in the order they run
         self.last_plan, self.last_inertial, self.last_params, self.last_streams, self.last_window = {}, None, {}, {}, {}
+        self.last_bodies = {}
         for later in (augment, streams):
             stale = sorted(k for k in later.valid_frames if window.applies_to(k)) if window is not None and later is not None else []
             if stale:                                       # the windowed clip fills all W frames: the table no longer describes it

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import numbers
 import os
 import threading
 from typing import Optional, Sequence, Tuple
@@ -2037,6 +2038,31 @@ def clip_normalize(src: torch.Tensor, idx: torch.Tensor, *, origin_joint: int, z
     check(_lib.load().fgcn_clip_normalize(_p(src), idx.data_ptr(), _p(out), _p(frame_map), _p(params), b, M, T, V, C, int(origin_joint),
                                           z0, z1, x0, x1, _stream()), "fgcn_clip_normalize")
     return out, frame_map, params
+
+
+# ---- selection of a clip's most energetic bodies as the batch is gathered (fgcn_clip_bodies) ------------------------
+def clip_bodies(src: torch.Tensor, idx: torch.Tensor, *, bodies: int, out: Optional[torch.Tensor] = None):
+    """-> (out, order, scores): out[k] = the ``bodies`` bodies of source row ``idx[k]`` of ``src`` with the highest score, in descending
+    order, as the reference's ``_filter_bodies`` keeps them (include/fgcn.h): the score of a body is the sum over the channels of the
+    standard deviation of its non-null frames; a NaN score ranks first, equal scores by the higher source index.  order (b, Mr) int32:
+    the complete ranking of every clip; scores (b, Mr) float64, indexed by source body.  src: (rows, Mr, T, V, C) contiguous float32 on
+    the device, C = 2 or 3, ``1 <= bodies <= Mr <= 16``; idx: (b) int64 -- on the device, where it is trusted to hold rows of ``src``, or
+    on the host, where it is checked and uploaded."""
+    ensure_device()
+    _chk(src, "clip_bodies.src")
+    if src.dim() != 5:
+        raise _lib.FgcnError(f"clip_bodies.src: expected (rows, Mr, T, V, C), got {tuple(src.shape)}")
+    Mr, T, V, C = src.shape[1:]
+    if isinstance(bodies, bool) or not isinstance(bodies, numbers.Integral) or not 1 <= bodies <= Mr:
+        raise _lib.FgcnError(f"clip_bodies: bodies={bodies!r}, expected an integer in [1, {Mr}] (the bodies of src)")
+    idx = _rows(idx, src.shape[0], src.device, "clip_bodies.idx")
+    b = idx.numel()
+    out = _batch_out(out, (b, int(bodies), T, V, C), src.device, "clip_bodies.out")
+    order = torch.empty((b, Mr), device=src.device, dtype=torch.int32)
+    scores = torch.empty((b, Mr), device=src.device, dtype=torch.float64)
+    check(_lib.load().fgcn_clip_bodies(_p(src), idx.data_ptr(), _p(out), _p(order), _p(scores), b, Mr, int(bodies), T, V, C, _stream()),
+          "fgcn_clip_bodies")
+    return out, order, scores
 
 
 # ---- preparation of raw inertial recordings as the batch is gathered (fgcn_signal_prepare / fgcn_imu_enhance; DESIGN.md section 8h) --------

@@ -1097,6 +1097,38 @@ int fgcn_augment_params(unsigned sample, unsigned site, unsigned epoch, unsigned
 int fgcn_clip_normalize(const float* src, const long long* idx, float* out, int* frame_map, double* params, int b, int M, int T, int V, int C,
                         int origin, int z0, int z1, int x0, int x1, void* stream);
 
+/* Selection of a clip's most energetic bodies as the batch is gathered (data.ClipBatches(bodies=...)): the
+ * reference's SkeletonSample._filter_bodies (datasets/ntu_rgb_d/io.py) with body_score (util/preprocessing/skeleton.py) on source row
+ * idx[k].  It runs in FRONT of fgcn_clip_normalize, which centres and rotates the clip by body 0: this stage decides what body 0 is.  A
+ * clip is (Mr, T, V, C) float32, C = 2 or 3; the stage keeps M bodies, 1 <= M <= Mr <= FGCN_BODIES_MAX.
+ *
+ * Null frames.  A frame of a body is NULL when all its V * C values are zero (-0 counts as zero, a NaN as a value): fgcn_clip_normalize's
+ * definition.  (The reference tests sum() != 0 instead: the two differ only where non-zero values cancel exactly, and there this
+ * definition is the one that holds.)
+ * Score.  Let F be the body's non-null frames and n = |F| * V.  n == 0: the score is +0.  Otherwise it is the sum over the channels c of
+ * sqrt(sum_{t in F, v} (x[t, v, c] - mean_c)^2 / n) with mean_c = sum_{t in F, v} x[t, v, c] / n: the population standard deviation
+ * (numpy's std()), two passes, the mean first and then the squared deviations.  Arithmetic: float64 from the float32 input throughout.  The
+ * order of every sum is fixed and depends on (T, V, C) alone -- not on b, on the clip's place in the batch, on its address or on the number
+ * of workgroups -- and there are no floating-point atomics: a clip's score has the same bits alone and in any batch, in a second call, on
+ * the resident path and on the streaming path.  A body that holds a NaN or an inf has a NaN score.
+ * Ranking.  Descending score; a NaN ranks above every number (where numpy's argsort()[::-1] puts it; a NaN stays visible, DESIGN.md
+ * section 8l); equal scores, several NaNs included: the HIGHER source index first (what numpy's stable sort, reversed, gives for these sizes
+ * -- but the rule is this contract's, not numpy's).
+ * Output.  out[k, j] = src[idx[k], order[k, j]] for j < M: a copy, every value bit for bit.
+ *
+ * fgcn_clip_bodies: src (rows, Mr, T, V, C), idx (b) 8-byte integers on the device (they may repeat and need not be sorted; every idx[k]
+ * must be a row of src -- the caller's duty), out (b, M, T, V, C), order (b, Mr) 4-byte integers, the complete ranking (order[k, 0] is the
+ * source body with the highest score), scores (b, Mr) float64 indexed by SOURCE body.  M == Mr gives a pure reordering.  Two launches:
+ * one workgroup per (clip, body) scores it, then the workgroups of the gather rank the clip's scores by counting and copy.  No host read
+ * and no synchronising call.  Rows need 4-byte alignment only.
+ * FGCN_E_BADARG before any launch: a null pointer; b, Mr, M, T or V <= 0; M > Mr; Mr > FGCN_BODIES_MAX; C not 2 or 3; T * V * C >= 2^29 (a
+ * lane's index inside a body); T > FGCN_BODIES_MAX_T (the frame flags of a body stay in LDS, one bit a frame); b * Mr >= 2^31 (one grid
+ * does not hold more bodies); out == src. */
+#define FGCN_BODIES_MAX 16
+#define FGCN_BODIES_MAX_T 524288
+int fgcn_clip_bodies(const float* src, const long long* idx, float* out, int* order, double* scores, int b, int Mr, int M, int T, int V, int C,
+                     void* stream);
+
 /* Preparation of raw inertial recordings as the batch is gathered (data.ClipBatches(inertial=...)): what the
  * reference's offline preprocessing does to the accelerometer / gyroscope recording of a sample.  The recording has Li frames of S values
  * (stored in a row of L >= Li frames), the sample's skeleton recording has Ls frames, a clip has T >= Ls frames.
