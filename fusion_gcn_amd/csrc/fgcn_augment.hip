@@ -9,13 +9,11 @@
 // alignment.
 #include <cmath>
 
+#include "fgcn_clip.hpp"
 #include "fgcn_common.hpp"
 #include "fgcn_rng.hpp"
 
 namespace fgcn {
-
-// a word of the generator -> a float in [0, 1): the top 24 bits, exact
-__host__ __device__ inline float augment_uniform(unsigned w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }
 
 // The table row of one sample: A (3 x 3, row-major) = s Rz Ry Rx, then o, r, 0.  The ONE definition: the kernel and fgcn_augment_params
 // both call it.  Every product below is written out and contraction is off, so the host and the device differ in sinf / cosf alone.
@@ -25,9 +23,9 @@ __host__ __device__ inline void augment_params(unsigned sample, unsigned site, u
                                                float az, float scale, float min_window, float* out) {
 #pragma clang fp contract(off)
     const philox4 p0 = philox4x32_10(sample, site, epoch, 0u, k0, k1), p1 = philox4x32_10(sample, site, epoch, 1u, k0, k1);
-    const float tx = (2.0f * augment_uniform(p0.w[0]) - 1.0f) * ax, ty = (2.0f * augment_uniform(p0.w[1]) - 1.0f) * ay,
-                tz = (2.0f * augment_uniform(p0.w[2]) - 1.0f) * az;
-    const float s = 1.0f + (2.0f * augment_uniform(p0.w[3]) - 1.0f) * scale;
+    const float tx = (2.0f * clip_uniform(p0.w[0]) - 1.0f) * ax, ty = (2.0f * clip_uniform(p0.w[1]) - 1.0f) * ay,
+                tz = (2.0f * clip_uniform(p0.w[2]) - 1.0f) * az;
+    const float s = 1.0f + (2.0f * clip_uniform(p0.w[3]) - 1.0f) * scale;
     const float sx = sinf(tx), cx = cosf(tx), sy = sinf(ty), cy = cosf(ty), sz = sinf(tz), cz = cosf(tz);
     out[0] = s * (cz * cy);
     out[1] = s * (cz * sy * sx - sz * cx);
@@ -38,7 +36,7 @@ __host__ __device__ inline void augment_params(unsigned sample, unsigned site, u
     out[6] = s * (-sy);
     out[7] = s * (cy * sx);
     out[8] = s * (cy * cx);
-    const float u4 = augment_uniform(p1.w[0]), u5 = augment_uniform(p1.w[1]), span = 1.0f - min_window;
+    const float u4 = clip_uniform(p1.w[0]), u5 = clip_uniform(p1.w[1]), span = 1.0f - min_window;
     out[9] = u5 * ((1.0f - u4) * span);
     out[10] = min_window + u4 * span;
     out[11] = 0.0f;
@@ -78,21 +76,15 @@ __global__ __launch_bounds__(256) void augment_kernel(AugmentArgs a) {
     const long long ro = frame / a.T;
     const int row = (int)(ro / a.outer), o = (int)(ro % a.outer);
     const long long s = a.idx[row];
-    int v = a.T;
-    if (a.valid) v = min(max(a.valid[s], 1), a.T);       // the contract says 1 <= valid <= T; a value outside must not become an address
+    const int v = clip_valid(a.valid, s, a.T);
     const float* P = a.params + (long long)row * 12;
     const float off = P[9], win = P[10];
-    // pos = (o + r t / (T - 1)) (valid - 1) as o (valid - 1) + (r t) ((valid - 1) / (T - 1)): the quotient is exactly 1 for a full clip, so
-    // that the identity parameters read frame t itself
-    const float vm1 = (float)(v - 1), ratio = a.T > 1 ? vm1 / (float)(a.T - 1) : 0.0f;
-    const float pos = fmaf(win * (float)t, ratio, off * vm1);
-    const int f0 = min(max((int)floorf(pos), 0), v - 1), f1 = min(f0 + 1, v - 1);
-    const float w = pos - (float)f0;
+    const ClipLerp l = clip_lerp(t, a.T, v, off, win);   // the window [o, o + r] of the valid frames resampled to the clip's T frames
     const float* base = a.src + ((s * a.outer + o) * a.T) * (long long)a.inner + (long long)j * W;
-    const float *x0 = base + (long long)f0 * a.inner, *x1 = base + (long long)f1 * a.inner;
+    const float *x0 = base + (long long)l.f0 * a.inner, *x1 = base + (long long)l.f1 * a.inner;
     float y[W];
 #pragma unroll
-    for (int c = 0; c < W; ++c) y[c] = fmaf(w, x1[c] - x0[c], x0[c]);
+    for (int c = 0; c < W; ++c) y[c] = fmaf(l.w, x1[c] - x0[c], x0[c]);
     float* dst = a.out + frame * a.inner + (long long)j * W;
     if constexpr (W == 3) {
         if (j >= a.joint_lo && j < a.joint_hi) {

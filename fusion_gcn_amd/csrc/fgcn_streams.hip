@@ -7,6 +7,7 @@
 // stores C floats to each output that was asked for.  4-byte loads and stores: a row of 75 floats has no wider alignment.  Which
 // outputs exist is the same for every lane of a launch (kernel arguments: scalar branches); the one value read from memory that shapes
 // an address or a select is the row's valid frame count, clamped into [1, T], and a parent number, clamped into [-1, V).
+#include "fgcn_clip.hpp"
 #include "fgcn_common.hpp"
 
 namespace fgcn {
@@ -32,8 +33,7 @@ __global__ __launch_bounds__(256) void streams_kernel(StreamsArgs a) {
     const long long ro = frame / a.T;
     const int row = (int)(ro / a.M), o = (int)(ro % a.M);
     const long long s = a.idx[row];
-    int L = a.T;
-    if (a.valid) L = min(max(a.valid[s], 1), a.T);       // the contract says 1 <= valid <= T; a value outside must not become an address
+    const int L = clip_valid(a.valid, s, a.T);
     const bool parent = a.bone || a.bone_motion, next = a.motion || a.bone_motion;      // what this launch has to load
     const int pv = parent ? min(max(a.parents[v], -1), a.V - 1) : -1;
     const bool through = pv < 0;                         // a sensor joint: the bone is the joint itself

@@ -12,13 +12,11 @@
 // atomics; the lanes stride over a body's floats (4-byte loads, neighbours in memory) and keep the largest frame number they saw.
 #include <cmath>
 
+#include "fgcn_clip.hpp"
 #include "fgcn_common.hpp"
 #include "fgcn_rng.hpp"
 
 namespace fgcn {
-
-// a word of the generator -> a float in [0, 1): the top 24 bits, exact
-__host__ __device__ inline float window_uniform(unsigned w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }
 
 // The table row of one sample, {o, r}: the part [o, o + r] of the recording, as fractions of it.  The ONE definition: the kernel and
 // fgcn_window_params both call it; there is no transcendental function and contraction is off, so the two give the same bits.
@@ -35,7 +33,7 @@ __host__ __device__ inline void window_params(unsigned sample, unsigned site, un
         return;
     }
     const philox4 p = philox4x32_10(sample, site, epoch, 2u, k0, k1);
-    const float u0 = window_uniform(p.w[0]), u1 = window_uniform(p.w[1]), span = hi - lo;
+    const float u0 = clip_uniform(p.w[0]), u1 = clip_uniform(p.w[1]), span = hi - lo;
     const float r = fminf(lo + u0 * span, hi);
     const float rest = (1.0f - hi) + (1.0f - u0) * span;
     out[0] = fminf(u1 * rest, 1.0f - r);
@@ -74,18 +72,12 @@ __global__ __launch_bounds__(256) void window_kernel(WindowArgs a) {
     const unsigned row = body / (unsigned)a.outer, o = body - row * (unsigned)a.outer;
     const unsigned t = fastdiv(e, a.by_inner), j = e - t * (unsigned)a.inner;
     const long long s = a.idx[row];
-    int v = a.T;
-    if (a.valid) v = min(max(a.valid[s], 1), a.T);       // the contract says 1 <= valid <= T; a value outside must not become an address
+    const int v = clip_valid(a.valid, s, a.T);
     const float off = a.params[2 * (long long)row], win = a.params[2 * (long long)row + 1];
-    // pos = (o + r t / (W - 1)) (valid - 1) as o (valid - 1) + (r t) ((valid - 1) / (W - 1)): the quotient is exactly 1 for a full clip
-    // resized to its own length, so that the identity parameters read frame t itself
-    const float vm1 = (float)(v - 1), ratio = a.W > 1 ? vm1 / (float)(a.W - 1) : 0.0f;
-    const float pos = fmaf(win * (float)t, ratio, off * vm1);
-    const int f0 = min(max((int)floorf(pos), 0), v - 1), f1 = min(f0 + 1, v - 1);
-    const float w = pos - (float)f0;
+    const ClipLerp l = clip_lerp(t, a.W, v, off, win);   // the part [o, o + r] of the valid frames resized to W frames
     const float* base = a.src + ((s * a.outer + o) * a.T) * (long long)a.inner + j;
-    const float x0 = base[(long long)f0 * a.inner], x1 = base[(long long)f1 * a.inner];
-    a.out[(long long)body * a.per_body + e] = fmaf(w, x1 - x0, x0);
+    const float x0 = base[(long long)l.f0 * a.inner], x1 = base[(long long)l.f1 * a.inner];
+    a.out[(long long)body * a.per_body + e] = fmaf(l.w, x1 - x0, x0);
 }
 
 struct ValidFramesArgs {

@@ -1931,7 +1931,7 @@ def rng_advance(step: torch.Tensor) -> None:
     check(_lib.load().fgcn_rng_advance(step.data_ptr(), _stream()), "fgcn_rng_advance")
 
 
-# ---- the arguments the four wrappers of ClipBatches' stages share (DESIGN.md sections 8f-8h) -------------------------------------------
+# ---- the arguments the wrappers of ClipBatches' six stages share (DESIGN.md sections 8f-8o) --------------------------------------------
 def _rows(idx: torch.Tensor, rows: int, device, name: str) -> torch.Tensor:
     """(b) int64 row numbers -- on the device, where they are trusted, or on the host, where they are checked and uploaded."""
     if idx.dtype != torch.int64 or idx.dim() != 1:
@@ -1956,6 +1956,25 @@ def _batch_out(out: Optional[torch.Tensor], shape: Tuple[int, ...], device, name
     return out
 
 
+def _sample_ids(sample_ids: torch.Tensor, b: int, device, name: str) -> torch.Tensor:
+    """(b) int64 ids of the batch's samples, which key their random numbers, on the device"""
+    if sample_ids.dtype != torch.int64 or sample_ids.dim() != 1 or sample_ids.numel() != b:
+        raise _lib.FgcnError(f"{name}: expected ({b},) int64, got {tuple(sample_ids.shape)} {sample_ids.dtype}")
+    return sample_ids.to(device).contiguous()
+
+
+def _rng_words(seed: int, site: int, epoch: int) -> Tuple[int, int, int]:
+    """(seed, site, epoch) as the generator takes them: a 64-bit key and two 32-bit counter words"""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF
+
+
+def _clip_dims(src: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    """(outer, T, inner) of a (rows, M, T, V, C) or (rows, T, S) array"""
+    if src.dim() not in (3, 5):
+        raise _lib.FgcnError(f"{name}: expected (rows, M, T, V, C) or (rows, T, S), got {tuple(src.shape)}")
+    return (1, src.shape[1], src.shape[2]) if src.dim() == 3 else (src.shape[1], src.shape[2], src.shape[3] * src.shape[4])
+
+
 # ---- augmentation of clips as the batch is gathered (fgcn_clip_augment / fgcn_augment_params; DESIGN.md section 8f) -------------------
 def _augment_scalars(max_angle, scale: float, min_window: float):
     if len(max_angle) != 3:
@@ -1967,9 +1986,8 @@ def augment_params(sample: int, site: int, epoch: int, seed: int, max_angle=(0.0
                    min_window: float = 1.0) -> list:
     """The table row of one sample on the HOST (no device is touched): [A row-major (9), o, r, 0], by the function the kernel calls."""
     ang, scale, min_window = _augment_scalars(max_angle, scale, min_window)
-    out = (ctypes.c_float * 12)()
-    check(_lib.load().fgcn_augment_params(int(sample) & 0xFFFFFFFF, int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, ang, scale, min_window, out), "fgcn_augment_params")
+    out, (seed, site, epoch) = (ctypes.c_float * 12)(), _rng_words(seed, site, epoch)
+    check(_lib.load().fgcn_augment_params(int(sample) & 0xFFFFFFFF, site, epoch, seed, ang, scale, min_window, out), "fgcn_augment_params")
     return list(out)
 
 
@@ -1983,17 +2001,10 @@ def clip_augment(src: torch.Tensor, idx: torch.Tensor, sample_ids: torch.Tensor,
     None or (rows) int32 on the device, the valid frames of each SOURCE row; joints: None = no spatial part."""
     ensure_device()
     _chk(src, "clip_augment.src")
-    if src.dim() == 5:
-        outer, T, inner, C = src.shape[1], src.shape[2], src.shape[3] * src.shape[4], src.shape[4]
-    elif src.dim() == 3:
-        outer, T, inner, C = 1, src.shape[1], src.shape[2], src.shape[2]
-    else:
-        raise _lib.FgcnError(f"clip_augment.src: expected (rows, M, T, V, C) or (rows, T, S), got {tuple(src.shape)}")
+    outer, T, inner = _clip_dims(src, "clip_augment.src")
     idx = _rows(idx, src.shape[0], src.device, "clip_augment.idx")
     b = idx.numel()
-    if sample_ids.dtype != torch.int64 or sample_ids.dim() != 1 or sample_ids.numel() != b:
-        raise _lib.FgcnError(f"clip_augment.sample_ids: expected ({b},) int64, got {tuple(sample_ids.shape)} {sample_ids.dtype}")
-    sample_ids = sample_ids.to(src.device).contiguous()
+    sample_ids = _sample_ids(sample_ids, b, src.device, "clip_augment.sample_ids")
     if valid is not None:
         _lengths(valid, src.shape[0], "clip_augment.valid")
     out = _batch_out(out, (b, *src.shape[1:]), src.device, "clip_augment.out")
@@ -2001,8 +2012,8 @@ def clip_augment(src: torch.Tensor, idx: torch.Tensor, sample_ids: torch.Tensor,
     ang, scale, min_window = _augment_scalars(max_angle, scale, min_window)
     params = torch.empty((b, 12), device=src.device, dtype=torch.float32)
     check(_lib.load().fgcn_clip_augment(_p(src), idx.data_ptr(), sample_ids.data_ptr(), _p(valid), _p(out), _p(params),
-                                        b, outer, T, inner, C, lo, hi, ang, scale, min_window, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                        int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, _stream()), "fgcn_clip_augment")
+                                        b, outer, T, inner, src.shape[-1], lo, hi, ang, scale, min_window, *_rng_words(seed, site, epoch),
+                                        _stream()), "fgcn_clip_augment")
     return out, params
 
 
@@ -2177,21 +2188,11 @@ def _window_scalars(interval, mode: str):
     return float(interval[0]), float(interval[1]), _lib.WINDOW_MODES[mode]
 
 
-def _clip_dims(src: torch.Tensor, name: str) -> Tuple[int, int, int]:
-    """(outer, T, inner) of a (rows, M, T, V, C) or (rows, T, S) array"""
-    if src.dim() == 5:
-        return src.shape[1], src.shape[2], src.shape[3] * src.shape[4]
-    if src.dim() == 3:
-        return 1, src.shape[1], src.shape[2]
-    raise _lib.FgcnError(f"{name}: expected (rows, M, T, V, C) or (rows, T, S), got {tuple(src.shape)}")
-
-
 def window_params(sample: int, site: int, epoch: int, seed: int, interval=(1.0, 1.0), mode: str = "random") -> list:
     """The table row of one sample on the HOST (no device is touched): [o, r], by the function the kernel calls."""
     lo, hi, mode = _window_scalars(interval, mode)
-    out = (ctypes.c_float * 2)()
-    check(_lib.load().fgcn_window_params(int(sample) & 0xFFFFFFFF, int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
-                                         int(seed) & 0xFFFFFFFFFFFFFFFF, lo, hi, mode, out), "fgcn_window_params")
+    out, (seed, site, epoch) = (ctypes.c_float * 2)(), _rng_words(seed, site, epoch)
+    check(_lib.load().fgcn_window_params(int(sample) & 0xFFFFFFFF, site, epoch, seed, lo, hi, mode, out), "fgcn_window_params")
     return list(out)
 
 
@@ -2215,9 +2216,7 @@ def clip_window(src: torch.Tensor, idx: torch.Tensor, sample_ids: Optional[torch
     idx = _rows(idx, src.shape[0], src.device, "clip_window.idx")
     b = idx.numel()
     if sample_ids is not None:
-        if sample_ids.dtype != torch.int64 or sample_ids.dim() != 1 or sample_ids.numel() != b:
-            raise _lib.FgcnError(f"clip_window.sample_ids: expected ({b},) int64, got {tuple(sample_ids.shape)} {sample_ids.dtype}")
-        sample_ids = sample_ids.to(src.device).contiguous()
+        sample_ids = _sample_ids(sample_ids, b, src.device, "clip_window.sample_ids")
     elif mode != "centre":
         raise _lib.FgcnError("clip_window.sample_ids: None, which only mode 'centre' takes")
     if valid is not None:
@@ -2226,8 +2225,8 @@ def clip_window(src: torch.Tensor, idx: torch.Tensor, sample_ids: Optional[torch
     out = _batch_out(out, shape, src.device, "clip_window.out")
     params = torch.empty((b, 2), device=src.device, dtype=torch.float32)
     check(_lib.load().fgcn_clip_window(_p(src), idx.data_ptr(), None if sample_ids is None else sample_ids.data_ptr(), _p(valid), _p(out),
-                                       _p(params), b, outer, T, W, inner, lo, hi, mode_id, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                       int(site) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, _stream()), "fgcn_clip_window")
+                                       _p(params), b, outer, T, W, inner, lo, hi, mode_id, *_rng_words(seed, site, epoch), _stream()),
+          "fgcn_clip_window")
     return out, params
 
 
