@@ -150,6 +150,9 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
         for (int pl = 0; pl < 3; ++pl)
             wv[pl] = __builtin_amdgcn_raw_buffer_load_b128(rw, wvo[ot], so + pl * p.w_plane_bytes, 0);
     };
+    // the input's tiles: CT_IN is the next power of two (Cin = 192 runs CT_IN = 8).  The walk and its prefetch chains end at the last tile
+    // that holds channels -- a chain that requested tile n_ci's weights would hand them to the next frame's first step
+    const int n_ci = min(CT_IN, (p.Cin + 31) >> 5);
     load_x(t0 + wave, 0, xcur);
     if constexpr (MM == 2) {
 #pragma unroll
@@ -165,10 +168,10 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
         for (int i = 0; i < CT_OUT; ++i) acc[i] = zero16();
 
 #pragma unroll 1
-        for (int ci = 0; ci < CT_IN; ++ci) {
+        for (int ci = 0; ci < n_ci; ++ci) {
             // next tile's x (next channel tile, or the first tile of this wave's next frame) flies during the MFMAs
             if constexpr (!LATE_X) {
-                if (ci + 1 < CT_IN) load_x(t, ci + 1, xnxt);
+                if (ci + 1 < n_ci) load_x(t, ci + 1, xnxt);
                 else load_x(t + 4, 0, xnxt);
             }
             const int cleft = p.Cin - ci * 32;          // valid input channels in this tile
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
                     if (s < ksteps) agg = mfma32(xcur[s], ak[(2 * s + h) * AHS], agg);
                 if constexpr (LATE_X) {
                     if (k == NS - 1) {
-                        if (ci + 1 < CT_IN) load_x(t, ci + 1, xcur);
+                        if (ci + 1 < n_ci) load_x(t, ci + 1, xcur);
                         else load_x(t + 4, 0, xcur);
                     }
                 }
@@ -197,7 +200,7 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
                         if (gp == 1) {
                             ngp = 0;
                             if (k + 1 < NS) nk = k + 1;
-                            else if (ci + 1 < CT_IN) nci = ci + 1, nk = 0;
+                            else if (ci + 1 < n_ci) nci = ci + 1, nk = 0;
                             else nci = 0, nk = 0;
                         }
                         u32x2 h0, m0, l0, h1, m1, l1;
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
                         if constexpr (PREFETCH_W) {
                             if (g + 1 < nG) load_w(ci, k, g + 1, wnxt);
                             else if (k + 1 < NS) load_w(ci, k + 1, 0, wnxt);
-                            else if (ci + 1 < CT_IN) load_w(ci + 1, 0, 0, wnxt);
+                            else if (ci + 1 < n_ci) load_w(ci + 1, 0, 0, wnxt);
                             else load_w(0, 0, 0, wnxt);
                         } else {
                             load_w(ci, k, g, wcur);     // 256 output channels: no registers left for a second set
@@ -322,9 +325,13 @@ __global__ __launch_bounds__(256, ((CT_OUT <= 2 || (CT_OUT == 4 && (CT_IN <= 2 |
 // FGCN_PACK_SPLIT2H_ACC).  The step-2 accumulators carry S = ex + eA + e2 + ew; when a tile's natural S differs from the one in
 // force they are rescaled (a power of two: exact; upwards only while a running bound of log2 |acc| stays below 120, the remainder goes
 // into e2) and the epilogue multiplies 2^-S back out.
+// CT_IN: the input's 32-channel tiles, 1 / 2 / 4 / 8 at compile time; 0 = Cin / 32 read from the arguments, for the widths in between
+// (Cin = 96, 160, 192, 224: a 192-wide model's blocks).  The tile loop must end at the input's last tile: behind it lie the next row's
+// channels in x and the next subset's rows in the packed weights, both inside their buffers.
 template <int CT_IN, int NP = 3, bool STR = false>              // STR: non-temporal output stores (fgcn_common.hpp, stream_out)
 __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
     static_assert(NP == 2 || NP == 3, "three bf16 parts or two f16 parts");
+    const int n_ci = CT_IN ? CT_IN : p.Cin >> 5;
     constexpr int CT_OUT = 2, WROW = CT_OUT * 32;
     constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -439,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
         int S = S_NONE, abound = 0;                                   // NP == 2: scale exponent the accumulators carry, log2 bound of |acc|
 
 #pragma unroll 1
-        for (int ci = 0; ci < CT_IN; ++ci) {
+        for (int ci = 0; ci < n_ci; ++ci) {
             u32x4v xs[2][2][NP];                                      // [frame][16-joint step][part]
             int ex = 0;
             if constexpr (NP == 2) {
@@ -482,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
                     }
                 }
                 if constexpr (decltype(last)::value) {
-                    if (ci + 1 < CT_IN) {
+                    if (ci + 1 < n_ci) {
                         load_x(tA, ci + 1, xr[0]);
                         load_x(tA + 1, ci + 1, xr[1]);
                     } else {
@@ -527,7 +534,7 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
                     if (gp == 1) {
                         ngp = 0;
                         if (!decltype(last)::value) nk = k + 1;
-                        else if (ci + 1 < CT_IN) nci = ci + 1, nk = 0;
+                        else if (ci + 1 < n_ci) nci = ci + 1, nk = 0;
                         else nci = 0, nk = 0;
                     }
                     u32x4v b3[2][NP];
@@ -728,11 +735,12 @@ extern "C" int fgcn_spatial_fwd(const float* x, const float* a_hat, const float*
     // two frames per wave, split-bf16 aggregation (tuning key 7 bit 0: the older form below, which reads the three-part bf16 weights only:
     // with the f16x2 products `wd` is the FGCN_PACK_SPLIT2H_ACC form and the bit selects nothing)
     if (split && (!(fgcn::tuning(7) & 1) || fgcn::f16x2_products())) {
-        switch (ci) {
+        switch (Cin / 32) {
             case 1: launch_spatial_x3<1>(p, s); break;
             case 2: launch_spatial_x3<2>(p, s); break;
             case 4: launch_spatial_x3<4>(p, s); break;
             case 8: launch_spatial_x3<8>(p, s); break;
+            default: launch_spatial_x3<0>(p, s); break;      // 3, 5, 6 or 7 tiles (ci > 0: Cin <= 256)
         }
         return launch_status("spatial_fwd");
     }

@@ -12,8 +12,9 @@ from typing import Optional, Tuple
 
 from . import ops
 
-# widest input of fgcn_spatial_fwd (eight 32-channel tiles, fgcn_spatial.hip); a wider block input -- the 512 / 516 channels of the RGB
-# patch-feature modes' first block -- takes the joint mixing + row GEMM form of the spatial stage (the skeleton models never reach it)
+# widest input and output of fgcn_spatial_fwd (eight 32-channel tiles each, fgcn_spatial.hip); a wider block -- the 512 / 516 input channels of
+# the RGB patch-feature modes' first block, the 384 / 512 output channels of a model with start_feature_size 128 / 192 where the tile form
+# is off or not built (math mode f32) -- takes the joint mixing + row GEMM form of the spatial stage
 SPATIAL_FWD_MAX_C = 256
 
 
@@ -140,7 +141,7 @@ def plan_block(cfg, B: int, T: int, V: int, *, x_bf16: bool, train: bool, infere
     elif tile_form and o.spatial_tile and cout >= o.get("spatial_tile_min_cout", mode):
         spatial_fwd = "tile"
     else:
-        spatial_fwd = "fused" if (cfg.fused_spatial and cin <= SPATIAL_FWD_MAX_C and not wide) else "mix"
+        spatial_fwd = "fused" if (cfg.fused_spatial and max(cin, cout) <= SPATIAL_FWD_MAX_C and not wide) else "mix"
     staged = spatial_fwd != "tile_bn_relu"       # y, G and G's sign image exist (everything bfloat16 below needs a training step anyway)
     # (Y as bfloat16: not when the temporal data gradient is to carry the BatchNorm-backward sums -- that epilogue reads Y as float32)
     y_bf16 = bool(ha and o.half_spatial_out and not o.get("bn_sums_in_dgrad", mode) and spatial_fwd == "tile")

@@ -97,13 +97,13 @@ def flat_grads(model) -> torch.Tensor:
     return torch.cat([p.grad.detach().double().flatten().cpu() for _, p in model.named_parameters()])
 
 
-def oracle_side(x, labels, sd, names):
+def oracle_side(x, labels, sd, names, **kw):
     """The oracle's half of the report, computed once: logits, loss, the flat gradient in ``names`` order (the HIP model's
     named_parameters order) and the per-block ReLU sign images.  ``x`` / ``sd`` float64 for the strict comparison; bench.py's
-    cpu_baseline leg hands in the float32 run it times anyway."""
+    cpu_baseline leg hands in the float32 run it times anyway.  ``kw``: the oracle model's ``start`` / ``num_layers``."""
     from oracle import agcn_oracle as O
     cap: Dict[str, torch.Tensor] = {}
-    lo, los, grads_o, _ = O.loss_and_grads(x, labels, sd, capture=cap)
+    lo, los, grads_o, _ = O.loss_and_grads(x, labels, sd, capture=cap, **kw)
     flat_o = torch.cat([grads_o[n].double().flatten() for n in names])
     nblocks = sum(1 for k in cap if k.endswith(".g"))
     images = oracle_sign_images(cap, nblocks)
@@ -138,7 +138,9 @@ def gradient_parity_report(model, x_dev, labels_dev, x64=None, labels=None, sd64
                 taps.inject(ora)
             loss.backward()
             torch.cuda.synchronize()
-            out[f"err_{tag}"] = float((flat_grads(model) - flat_o).norm() / flat_o.norm())
+            flat = flat_grads(model)
+            out[f"err_{tag}"] = float((flat - flat_o).norm() / flat_o.norm())
+            out[f"cos_{tag}"] = float(torch.dot(flat, flat_o) / (flat.norm() * flat_o.norm()))
     finally:
         taps.close()
         if not keep_grads:

@@ -3,6 +3,8 @@
 routes.plan_block picks a kernel chain per stage from the math mode, the phase, the block's shape and the context's PathOptions.  ``matrix``
 lists, per math mode and phase, one option set per DISTINCT plan that ``CASES`` x ``option_sets`` can produce; tests/test_block_routes.py
 proves on the host that the list leaves no route out, tests/test_block_routes_gpu.py executes every entry against the float64 oracle.
+``WIDE_CASES`` is a second case list, the blocks of models wider than 64 / 128 / 256 channels; ``matrix(mode, phase, WIDE_CASES)`` is what
+tests/test_wide_channels_gpu.py executes (deduplicated on the route tuple: ``matrix_key``).
 
 A new PathOptions field has to be entered in ``OPTION_HANDLING`` and a new BlockPlan field in ``PLAN_CONTEXT_FIELDS`` / ``PLAN_ROUTE_FIELDS``
 (the closure test fails until it is): that is how a new route or option joins the check."""
@@ -37,6 +39,18 @@ CASES = (
     Case("noresidual64", 64, 64, 1, False, 25, 12, True, False),
     Case("down_s1", 64, 128, 1, True, 25, 12, True, False),
     Case("static64", 64, 64, 1, True, 25, 10, True, True),
+)
+# the same block at the channel widths of a model with start_feature_size 128 / 192, and a 320-wide one whose third 128-column tile is ragged:
+# three and four column tiles in the halo conv and pw_gemm, 6 to 16 k-steps of 32 channels per tap, 3 to 5 channel groups in the spatial weight
+# gradient.  The smallest shapes that still give every kernel two row tiles and a ragged last one at B = 3; from 192 channels upward behind
+# the 3-channel first block.  tests/test_wide_channels_gpu.py executes ``matrix(mode, phase, WIDE_CASES)``
+WIDE_CASES = (
+    Case("first128", 3, 128, 1, False, 25, 8, True, False),
+    Case("identity192", 192, 192, 1, True, 25, 8, True, False),
+    Case("down_s2_384", 192, 384, 2, True, 22, 9, True, False),
+    Case("identity320", 320, 320, 1, True, 18, 7, True, False),
+    Case("down_s2_512", 256, 512, 2, True, 25, 9, True, False),
+    Case("identity512", 512, 512, 1, True, 20, 6, True, False),
 )
 
 # ---- what the matrix knows of the two dataclasses (the closure test compares these tables with dataclasses.fields) ---------------------------
@@ -152,13 +166,13 @@ def dedupe_key(pl, case: Case, cfg, forms, mode: str, o) -> tuple:
     return (pl, routed, tuple(o.mix_vw_order) if runs_a_mix_kernel(pl) else None)
 
 
-def plan_all(mode: str, phase: str) -> List[Entry]:
-    """Every (case, input type, option set) the planner accepts, planned on the host: no dedupe"""
+def plan_all(mode: str, phase: str, cases: Tuple[Case, ...] = CASES) -> List[Entry]:
+    """Every (case, input type, option set) the planner accepts for ``cases``, planned on the host: no dedupe"""
     from fusion_gcn_amd import block, ops, routes
     train = phase == "train"
     out = []
     with ops.context(mode):
-        for case in CASES:
+        for case in cases:
             blk = make_block(case)
             cfg = blk.cfg
             forms = block.pack_weights({n: blk._tensor(n) for n in block.param_names(cfg)}, cfg)
@@ -172,13 +186,23 @@ def plan_all(mode: str, phase: str) -> List[Entry]:
     return out
 
 
+def matrix_key(e: Entry) -> tuple:
+    """What makes an entry a distinct run of its case.  CASES: the whole plan (``dedupe_key``).  WIDE_CASES: the kernels the plan runs and the
+    input type -- ROUTE_TUPLE, the pw routing, mix_vw_order, ``half`` -- and not the storage-type fields: which tensors a bf16 step stores as
+    bfloat16 does not depend on the width and is CASES' to cover, the tile and k-loop geometry is what a wide case adds"""
+    if e.case in WIDE_CASES:
+        return (route_tuple(e.plan),) + tuple(e.key[1:]) + (e.half,)
+    return e.key
+
+
 @functools.lru_cache(maxsize=None)
-def matrix(mode: str, phase: str) -> Tuple[Entry, ...]:
-    """One option set per distinct plan (``dedupe_key``) of every case: what the GPU module executes"""
+def matrix(mode: str, phase: str, cases: Tuple[Case, ...] = CASES) -> Tuple[Entry, ...]:
+    """One option set per distinct ``matrix_key`` of every case, and every entry of the default option set: what the GPU modules execute"""
     seen, out = set(), []
-    for e in plan_all(mode, phase):
-        if (e.case.name, e.key) not in seen:
-            seen.add((e.case.name, e.key))
+    for e in plan_all(mode, phase, cases):
+        k = (e.case.name, matrix_key(e))
+        if k not in seen or e.option_name == "default":
+            seen.add(k)
             out.append(e)
     return tuple(out)
 
@@ -240,8 +264,8 @@ class BlockRun:
     The run is made on guarded allocations (tests/guarded.py) and ends with the check of their margins: a route that stores outside a tensor
     the host layer allocated fails the entry.  ``poison`` stays: it reaches what autograd allocates in C++, the guard does not."""
 
-    def __init__(self, case: Case, device):
-        self.case, self.device = case, device
+    def __init__(self, case: Case, device, margin: int = guarded.MARGIN):
+        self.case, self.device, self.margin = case, device, margin
         self.blk = make_block(case).to(device)
         self.buffers0 = {k: v.detach().clone() for k, v in self.blk.named_buffers()}
         ora = oracle_case(case, "train")
@@ -254,7 +278,7 @@ class BlockRun:
         """``guard=False``: the same run on the allocator's own tensors (for the test that the guard changes no bit)"""
         if not guard:
             return self._run(entry, phase, inject)
-        with guarded.Guard() as g:
+        with guarded.Guard(margin=self.margin) as g:
             res = self._run(entry, phase, inject)
             g.check()
         return res

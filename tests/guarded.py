@@ -5,7 +5,7 @@ past its output, or loads past the end of an input row, damages or reads some OT
 ``Guard`` is active every device tensor the package's host layer creates (``torch.empty`` / ``zeros`` / ``full`` and their ``*_like`` forms
 inside ``MODULES``) aliases the middle of a buffer of its own:
 
-    [ MARGIN bytes 0xFF | the tensor, rounded up to 512 bytes | MARGIN bytes 0xFF ]
+    [ margin bytes 0xFF | the tensor, rounded up to 512 bytes | margin bytes 0xFF ]
 
 The tensor handed back is not a torch view of that buffer but an alias of the bytes from MARGIN on with a storage of its own (through DLPack):
 storage_offset() == 0 and no view relation, as a fresh allocation has.  The host layer keys on both (``Guard._alloc`` says where).
@@ -14,7 +14,8 @@ storage_offset() == 0 and no view relation, as a fresh allocation has.  The host
 buffers read before they are written give NaN (also the ones block_routes.poison cannot reach), and ``check()`` finds every byte a kernel
 stored into a margin and names the buffer, its allocating line and the damaged offsets.  MARGIN = 256 KiB is twice the largest block one
 workgroup stores (128 rows x 256 channels x 4 B) -- a design condition -- and a multiple of 512, so the tensors keep the alignment the caching
-allocator gives and no aligned16 dispatch of the library changes.
+allocator gives and no aligned16 dispatch of the library changes.  A test whose tensors are wider states its own condition and passes
+``Guard(margin=...)`` (tests/test_wide_channels_gpu.py: 512 channels, 512 KiB); MARGIN stays the default.
 
 Not covered: an overrun longer than a margin that skips it; a stray store of 0xFF bytes (a packed sign-image or dropout-mask byte with all
 eight bits set, an all-ones NaN: the margin's own fill, so the damage test ``byte != 0xFF`` cannot see it); a stray load whose value is
@@ -80,15 +81,15 @@ def _call_site() -> str:
 
 
 class _Buffer:
-    __slots__ = ("raw", "nbytes", "shape", "dtype", "site")
+    __slots__ = ("raw", "nbytes", "shape", "dtype", "site", "margin")
 
-    def __init__(self, raw, nbytes, shape, dtype, site):
-        self.raw, self.nbytes, self.shape, self.dtype, self.site = raw, nbytes, shape, dtype, site
+    def __init__(self, raw, nbytes, shape, dtype, site, margin=MARGIN):
+        self.raw, self.nbytes, self.shape, self.dtype, self.site, self.margin = raw, nbytes, shape, dtype, site, margin
 
     def margins(self):
         """(side, bytes of that margin, offset of its first byte relative to the tensor's start / end)"""
-        back = MARGIN + self.nbytes                       # (the rounding bytes behind the tensor belong to the back margin)
-        return (("front", self.raw[:MARGIN], -MARGIN), ("back", self.raw[back:], 0))
+        back = self.margin + self.nbytes                  # (the rounding bytes behind the tensor belong to the back margin)
+        return (("front", self.raw[:self.margin], -self.margin), ("back", self.raw[back:], 0))
 
 
 class _TorchProxy:
@@ -106,9 +107,13 @@ class Guard:
     """Context manager: guarded allocations inside ``MODULES`` (+ ``modules``) on ``device``'s type; ``check()`` verifies every margin.
 
     Not re-entrant, single-threaded.  ``trace=True`` additionally verifies the margins after every C-ABI entry point (the ``check`` that
-    ops passes each return code through) and names the entry point: slow, for locating a finding."""
+    ops passes each return code through) and names the entry point: slow, for locating a finding.  ``margin``: bytes of 0xFF on each side of
+    every tensor, a multiple of 512; MARGIN unless a test's tensors are wider than its design condition (the module docstring)."""
 
-    def __init__(self, device="cuda", trace: bool = False, modules=()):
+    def __init__(self, device="cuda", trace: bool = False, modules=(), margin: int = MARGIN):
+        if margin <= 0 or margin % ALIGN:
+            raise ValueError(f"margin = {margin}: a positive multiple of {ALIGN} bytes keeps the allocator's alignment")
+        self.margin = margin
         self.device_type = torch.device(device).type
         self.trace = trace
         self.extra = tuple(modules)
@@ -161,15 +166,16 @@ class Guard:
         for s in shape:
             numel *= s
         nbytes = numel * dtype.itemsize
-        raw = torch.full((MARGIN + round_up(nbytes, ALIGN) + MARGIN,), FILL, dtype=torch.uint8, device=device)
-        self.buffers.append(_Buffer(raw, nbytes, tuple(shape), dtype, site))
+        margin = self.margin
+        raw = torch.full((margin + round_up(nbytes, ALIGN) + margin,), FILL, dtype=torch.uint8, device=device)
+        self.buffers.append(_Buffer(raw, nbytes, tuple(shape), dtype, site, margin))
         self.handed_out += 1
         if not nbytes:
             return torch.empty_strided(tuple(shape), tuple(strides), dtype=dtype, device=device)      # no element: nothing to alias
-        # an alias of the bytes from MARGIN on with a storage of its own: storage_offset() == 0 and no view relation, as a fresh allocation
+        # an alias of the bytes from ``margin`` on with a storage of its own: storage_offset() == 0 and no view relation, as a fresh allocation
         # has -- the host layer keys on both (FlatOptimizer finds a parameter's place in its flat buffers by the storage offset of the
         # gradient view; autograd refuses an in-place op on a custom Function's output that is a view).  The storage keeps ``raw`` alive
-        alias = torch.from_dlpack(raw[MARGIN:MARGIN + nbytes])
+        alias = torch.from_dlpack(raw[margin:margin + nbytes])
         return torch.empty(0, dtype=dtype, device=device).set_(alias.untyped_storage(), 0, tuple(shape), tuple(strides))
 
     def _wrap(self, name: str):

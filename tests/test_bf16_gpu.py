@@ -74,7 +74,7 @@ def test_rows_gemm_bf16(B, T, V, K, N, kt, s):
     assert rel_l2(out.cpu().numpy(), conv_ref(x, w, kt, s, T_out, b).numpy()) > 1e-4
 
 
-@pytest.mark.parametrize("B,T,V,C,O", [(3, 20, 25, 64, 64), (2, 13, 18, 128, 256), (2, 9, 27, 64, 128)])
+@pytest.mark.parametrize("B,T,V,C,O", [(3, 20, 25, 64, 64), (2, 13, 18, 128, 256), (2, 9, 27, 64, 128), (2, 9, 18, 320, 320), (1, 12, 25, 512, 512)])
 def test_halo_conv_bf16_forward_and_data_gradient(B, T, V, C, O):
     from fusion_gcn_amd import block, ops
     wt = rnd(9, C, O, seed=4, scale=(9 * C) ** -0.5)
@@ -92,7 +92,8 @@ def test_halo_conv_bf16_forward_and_data_gradient(B, T, V, C, O):
 
 
 @pytest.mark.parametrize("B,T,V,K,N,kt,s", [(3, 20, 25, 64, 64, 9, 1), (2, 21, 25, 64, 128, 9, 2), (2, 13, 18, 128, 256, 9, 1),
-                                            (2, 30, 25, 192, 64, 1, 1), (1, 12, 25, 768, 256, 1, 1)])
+                                            (2, 30, 25, 192, 64, 1, 1), (1, 12, 25, 768, 256, 1, 1),
+                                            (2, 9, 18, 320, 320, 9, 1), (1, 12, 25, 512, 512, 9, 1)])
 def test_weight_gradients_bf16(B, T, V, K, N, kt, s):
     from fusion_gcn_amd import ops
     T_out = (T - 1) // s + 1
@@ -113,7 +114,7 @@ def test_weight_gradients_bf16(B, T, V, K, N, kt, s):
         assert rel_l2(got.cpu().numpy(), want.numpy()) < 1e-4
 
 
-@pytest.mark.parametrize("V,cin,cout", [(25, 64, 64), (18, 64, 128), (27, 128, 256), (25, 4, 64)])
+@pytest.mark.parametrize("V,cin,cout", [(25, 64, 64), (18, 64, 128), (27, 128, 256), (25, 4, 64), (22, 192, 192), (18, 96, 64)])
 def test_fused_spatial_forward_bf16(V, cin, cout):
     """Step 1 (x . A^_k) stays f32; its result and the conv_d weights are rounded for step 2."""
     from fusion_gcn_amd import ops
@@ -218,7 +219,8 @@ def test_spatial_wgrad_bf16(V, cin, cout):
     assert rel_l2(got[0].cpu().numpy(), want.numpy()) < 2e-3      # a few agg values round to the neighbouring bf16
 
 
-@pytest.mark.parametrize("V,T,ic,cx,B", [(25, 13, 16, 64, 2), (25, 7, 64, 256, 2), (27, 9, 32, 64, 1), (18, 10, 32, 128, 2), (22, 31, 64, 128, 1)])
+@pytest.mark.parametrize("V,T,ic,cx,B", [(25, 13, 16, 64, 2), (25, 7, 64, 256, 2), (27, 9, 32, 64, 1), (18, 10, 32, 128, 2), (22, 31, 64, 128, 1),
+                                         (18, 9, 80, 320, 2), (20, 6, 128, 512, 1)])
 def test_embedding_backward_tile_form_bf16(V, T, ic, cx, B):
     """fgcn_emb_dx_tile / fgcn_emb_wgrad_tile with ONE bf16 part (FGCN_MATH_BF16; reference agcn.py:104-106 under the mixed-precision
     step, session/procedures/step.py:55-78): emb, dS, the on-chip embedding gradient, x and the weights are each rounded to bfloat16
@@ -248,7 +250,8 @@ def test_embedding_backward_tile_form_bf16(V, T, ic, cx, B):
     assert torch.equal(dx, dx2)
 
 
-TILE_SHAPES = [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 64, 64, 2), (22, 31, 256, 256, 1)]
+TILE_SHAPES = [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 64, 64, 2), (22, 31, 256, 256, 1),
+               (18, 9, 320, 320, 2), (20, 6, 512, 512, 1)]
 
 
 @pytest.mark.parametrize("V,T,cin,cout,B", TILE_SHAPES)
@@ -292,7 +295,7 @@ def test_spatial_tile_kernels_with_one_bf16_part(V, T, cin, cout, B):
     assert torch.equal(dx, dx2) and torch.equal(part_g, part_g2)
 
 
-@pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 256, 64, 2), (18, 10, 128, 32, 2)])
+@pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 256, 64, 2), (18, 10, 128, 32, 2), (18, 9, 320, 32, 2), (25, 7, 512, 64, 2)])
 def test_embedding_forward_tile_form_bf16(V, T, cin, ic, B):
     """fgcn_emb_fwd_tile with ONE bf16 part (FGCN_MATH_BF16; agcn.py:104-106 under the mixed-precision step): x and the weights rounded to
     bfloat16 once, the embedding tile rounded once more for the gram; float32 accumulation."""
@@ -308,7 +311,7 @@ def test_embedding_forward_tile_form_bf16(V, T, cin, ic, B):
 
 
 # ---- half-precision STORAGE of the temporal conv's operands (include/fgcn.h, half_mask output bits; paths.half_storage) -------------
-@pytest.mark.parametrize("rows,C,res", [(1000, 64, 0), (777, 128, 1), (2048, 256, 2), (50, 8, 1)])
+@pytest.mark.parametrize("rows,C,res", [(1000, 64, 0), (777, 128, 1), (2048, 256, 2), (50, 8, 1), (900, 320, 1), (700, 512, 2)])
 def test_bn_act_and_its_backward_write_bfloat16(rows, C, res):
     """fgcn_bn_act (half_mask 4) / fgcn_bn_act_bwd_apply (half_mask 8): the bfloat16 tensor they write is the round-to-nearest-even of what
     the all-f32 calls write, bit for bit; the sign image and the sums are those of the f32 values."""
@@ -330,7 +333,8 @@ def test_bn_act_and_its_backward_write_bfloat16(rows, C, res):
 
 
 @pytest.mark.parametrize("B,T,V,C,N,kt,s", [(2, 20, 25, 64, 64, 9, 1), (2, 21, 25, 128, 128, 9, 2), (3, 13, 18, 256, 256, 9, 1),
-                                            (2, 30, 27, 64, 128, 5, 1), (1, 9, 32, 128, 64, 3, 1), (2, 12, 22, 64, 64, 9, 2)])
+                                            (2, 30, 27, 64, 128, 5, 1), (1, 9, 32, 128, 64, 3, 1), (2, 12, 22, 64, 64, 9, 2),
+                                            (2, 9, 18, 320, 320, 9, 1), (1, 12, 25, 512, 512, 9, 1)])
 def test_halo_conv_and_weight_gradient_from_bfloat16_tensors(B, T, V, C, N, kt, s):
     """fgcn_tconv_halo with half_mask 1 (forward, data gradient; strided passes) and fgcn_tconv_wgrad with half_mask 3 against the f32
     calls on the f32 tensors holding the same (bfloat16-representable) values: bit for bit -- the kernels stage the same bytes."""
@@ -508,7 +512,8 @@ def test_model_step_with_half_precision_activations():
     assert torch.equal(l1, l2) and s1 == s2 and torch.equal(g1, g2)
 
 
-@pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 256, 256, 2), (32, 5, 128, 64, 1)])
+@pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 256, 256, 2), (32, 5, 128, 64, 1),
+                                             (18, 9, 320, 320, 2), (20, 6, 512, 512, 1)])
 def test_spatial_backward_tile_kernels_from_a_bfloat16_dy(V, T, cin, cout, B):
     """fgcn_spatial_bwd_tile (half_mask 1) / fgcn_spatial_wgrad_tile (half_mask 2) on a bfloat16 dy against the f32 calls on the f32 tensor holding the
     same values: bit for bit (plain, accumulating, gated and per-group-gated forms of the fused backward)."""
@@ -573,7 +578,8 @@ def test_inference_kernels_in_bf16_mode():
     assert err < 5e-2, err      # (two realisations of ten blocks' bf16 roundings: see test_config5_model_against_the_reference)
 
 
-@pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 128, 32, 2), (27, 9, 64, 32, 1), (18, 10, 128, 64, 2), (22, 31, 256, 64, 1)])
+@pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 128, 32, 2), (27, 9, 64, 32, 1), (18, 10, 128, 64, 2), (22, 31, 256, 64, 1),
+                                          (18, 9, 320, 32, 2), (20, 6, 512, 64, 1)])
 def test_embedding_kernels_with_a_bfloat16_emb(V, T, cin, ic, B):
     """fgcn_emb_fwd_tile with half_mask 2 writes the bfloat16 rounding of what mask 0 writes (same gram partials); fgcn_emb_dx_tile /
     fgcn_emb_wgrad_tile with half_mask 1 on that tensor equal the f32 calls on the f32 tensor holding the same values, bit for bit."""
@@ -608,7 +614,8 @@ def h16(*shape, seed=0, scale=1.0):
     return gpu(rnd(*shape, seed=seed, scale=scale)).to(torch.bfloat16)
 
 
-@pytest.mark.parametrize("rows,C,res", [(1000, 64, 0), (777, 128, 1), (2048, 256, 2), (50, 8, 1), (600, 64, 2), (1000, 12, 1), (500, 20, 2)])   # (C % 8 != 0: the four-wide typed kernels)
+@pytest.mark.parametrize("rows,C,res", [(1000, 64, 0), (777, 128, 1), (2048, 256, 2), (50, 8, 1), (600, 64, 2), (1000, 12, 1), (500, 20, 2),   # (C % 8 != 0: the four-wide typed kernels)
+                                        (900, 320, 1), (700, 512, 2)])
 def test_batchnorm_passes_with_bfloat16_operands(rows, C, res):
     """fgcn_bn_act / fgcn_bn_act_pool / fgcn_bn_act_bwd_reduce / fgcn_bn_act_bwd_apply with a, the shortcut and the incoming
     gradient as bfloat16 tensors, in every combination the block produces, against the float32 entry points on the same values."""
@@ -642,7 +649,8 @@ def test_batchnorm_passes_with_bfloat16_operands(rows, C, res):
 
 
 @pytest.mark.parametrize("B,T,V,C,N,kt,s", [(2, 20, 25, 64, 64, 9, 1), (3, 13, 18, 256, 256, 9, 1), (2, 30, 27, 64, 128, 5, 1), (1, 9, 32, 128, 64, 3, 1),
-                                            (2, 21, 25, 128, 128, 9, 2), (8, 40, 25, 128, 128, 9, 1), (16, 64, 25, 64, 64, 9, 1)])
+                                            (2, 21, 25, 128, 128, 9, 2), (8, 40, 25, 128, 128, 9, 1), (16, 64, 25, 64, 64, 9, 1),
+                                            (2, 9, 18, 320, 320, 9, 1), (1, 12, 25, 512, 512, 9, 1)])
 def test_halo_conv_writes_bfloat16(B, T, V, C, N, kt, s):
     """fgcn_tconv_halo with half_mask 3: the output is the rounding of the float32 output of half_mask 1, the BatchNorm moments are
     those of the float32 values, bit for bit (forward with statistics; data gradient, also through the frame views of a strided conv)."""
@@ -671,7 +679,8 @@ def test_halo_conv_writes_bfloat16(B, T, V, C, N, kt, s):
         assert torch.equal(d16, d32.to(torch.bfloat16))
 
 
-@pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 256, 256, 2), (32, 5, 128, 64, 1), (22, 40, 64, 64, 3)])
+@pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 256, 256, 2), (32, 5, 128, 64, 1), (22, 40, 64, 64, 3),
+                                             (18, 9, 320, 320, 2), (20, 6, 512, 512, 1)])
 def test_spatial_tile_kernels_on_bfloat16_activations(V, T, cin, cout, B):
     """fgcn_spatial_fwd_tile (x in, y out), fgcn_spatial_wgrad_tile (x, dy), fgcn_spatial_bwd_tile (dy, x, dx, gated addends) against
     the float32 / bfloat16-dy forms on the same values: equal inputs give equal bits, a bfloat16 output is the rounded float32 output."""
@@ -706,7 +715,8 @@ def test_spatial_tile_kernels_on_bfloat16_activations(V, T, cin, cout, B):
             assert torch.equal(d1, d0.to(torch.bfloat16)) and torch.equal(p0, p1)
 
 
-@pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 128, 32, 2), (27, 9, 64, 32, 1), (18, 10, 128, 64, 2), (22, 31, 256, 64, 1)])
+@pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 128, 32, 2), (27, 9, 64, 32, 1), (18, 10, 128, 64, 2), (22, 31, 256, 64, 1),
+                                          (18, 9, 320, 32, 2), (20, 6, 512, 64, 1)])
 def test_embedding_kernels_on_bfloat16_activations(V, T, cin, ic, B):
     """fgcn_emb_fwd_tile (x in), fgcn_emb_dx_tile (dx read-modify-written as bfloat16), fgcn_emb_wgrad_tile (x in) against the bfloat16-emb
     forms on the same values."""
@@ -742,7 +752,7 @@ def test_embedding_kernels_on_bfloat16_activations(V, T, cin, ic, B):
 
 
 @pytest.mark.parametrize("B,T,V,K,N,s", [(2, 20, 25, 64, 128, 1), (2, 21, 25, 64, 128, 2), (3, 10, 18, 128, 256, 2), (2, 9, 27, 4, 64, 1), (2, 40, 25, 128, 64, 1),
-                                         (1, 300, 25, 256, 128, 1)])
+                                         (1, 300, 25, 256, 128, 1), (2, 9, 18, 320, 320, 1), (2, 13, 22, 256, 512, 2)])
 def test_row_gemms_on_bfloat16_activations(B, T, V, K, N, s):
     """fgcn_rows_gemm / fgcn_pw_gemm with a half_mask (the shortcut convolutions of the blocks that change width or stride): a bfloat16 input gives the bits
     of the float32 call on the same values, a bfloat16 output is the rounded float32 output with the float32 BatchNorm sums; also the
@@ -784,7 +794,8 @@ def test_row_gemms_on_bfloat16_activations(B, T, V, K, N, s):
         assert torch.equal(d0, d1)
 
 
-@pytest.mark.parametrize("B,T,V,cin,cout,s", [(2, 20, 25, 64, 128, 1), (2, 21, 25, 64, 128, 2), (2, 12, 18, 128, 256, 2), (1, 30, 27, 128, 64, 1)])
+@pytest.mark.parametrize("B,T,V,cin,cout,s", [(2, 20, 25, 64, 128, 1), (2, 21, 25, 64, 128, 2), (2, 12, 18, 128, 256, 2), (1, 30, 27, 128, 64, 1),
+                                              (2, 9, 18, 320, 320, 1), (2, 13, 22, 256, 512, 2)])
 def test_shortcut_branch_backward_on_bfloat16_tensors(B, T, V, cin, cout, s):
     """The backward of the blocks that change width or stride under half-precision activation storage: the shortcut BatchNorm's gradient as a
     bfloat16 tensor (fgcn_bn_act_bwd_apply, half_mask bit 4), the 1x1 weight gradient from bfloat16 operands (fgcn_pw_wgrad, half_mask 3), and the fused spatial

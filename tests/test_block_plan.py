@@ -11,10 +11,12 @@ MODES = ("f32", "bf16x3", "f16x2", "bf16")
 JOINTS = (25, 27, 22, 33, 64)
 PHASES = {"train": (True, False), "eval": (False, False), "inference": (False, True)}       # -> (train, inference)
 # (cin, cout, stride, residual, static adjacency, input frames): the ten blocks of the headline model (64 clips x 2 bodies, T = 300), a
-# static-adjacency block and the 512-channel first block of the RGB patch-feature modes
+# static-adjacency block, the 512-channel first block of the RGB patch-feature modes
 HEADLINE = [(3, 64, 1, False, False, 300)] + [(64, 64, 1, True, False, 300)] * 3 + [(64, 128, 2, True, False, 300)] + \
            [(128, 128, 1, True, False, 150)] * 2 + [(128, 256, 2, True, False, 150)] + [(256, 256, 1, True, False, 75)] * 2
-BLOCKS = HEADLINE + [(64, 64, 1, True, True, 300), (512, 64, 1, False, False, 128)]
+# ... and the blocks of a 128- / 192-wide model (start_feature_size=128: 256 -> 512 and 512 -> 512; 192: 192 -> 384) and a 320-wide one
+WIDE = [(256, 512, 2, True, False, 150), (512, 512, 1, True, False, 75), (320, 320, 1, True, False, 75), (192, 384, 2, True, False, 150)]
+BLOCKS = HEADLINE + [(64, 64, 1, True, True, 300), (512, 64, 1, False, False, 128)] + WIDE
 TILE_OR_BF16 = ("emb_bf16", "y_bf16", "g_bf16", "shortcuts_bf16", "u_bf16", "o_bf16", "dy_bf16", "dshortcuts_bf16", "dg_bf16", "dx_bf16",
                 "half_activations", "x_bf16")
 

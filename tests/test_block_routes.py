@@ -1,5 +1,6 @@
 """The route matrix of tests/block_routes.py is closed: every route the planner can produce for an AGCN block at <= 32 joints is an entry of the
-matrix that tests/test_block_routes_gpu.py executes against the float64 oracle.  Host only (routes.plan_block and the availability queries are
+matrix that tests/test_block_routes_gpu.py executes against the float64 oracle, and the same for the blocks of 128 .. 512 channels
+(block_routes.WIDE_CASES) and the matrix that tests/test_wide_channels_gpu.py executes.  Host only (routes.plan_block and the availability queries are
 host functions of the built library)."""
 import dataclasses
 import inspect
@@ -69,8 +70,9 @@ def test_the_matrix_leaves_no_route_out(mode, phase):
     in_matrix = {f: {getattr(e.plan, f) for e in entries} for f in R.PLAN_ROUTE_FIELDS}
     # (1) every value of every route field that the planner sweep of test_block_plan.py produces appears in the matrix
     for f, vals in _sweep_values(mode, phase).items():
-        # the 512-channel first block of the RGB patch-feature modes is the sweep's only block beyond the fused spatial kernel's width: its
-        # forward "mix" at <= 32 joints is reached here by fused_spatial=False (identity64_unfused), checked like every other value
+        # the 512-channel first block of the RGB patch-feature modes and the blocks of 320 .. 512 channels are the sweep's blocks beyond the fused
+        # spatial kernel's width: their forward "mix" at <= 32 joints is reached here by fused_spatial=False (identity64_unfused), checked like
+        # every other value
         assert vals <= in_matrix[f], (mode, phase, f, vals - in_matrix[f])
     # (2) the values no default-option run reaches
     for want, modes, phases in R.MUST_REACH:
@@ -94,3 +96,42 @@ def test_the_matrix_leaves_no_route_out(mode, phase):
     floor = {"f32": (4, 8), "bf16x3": (9, 68), "f16x2": (7, 45), "bf16": (5, 37)}[mode]
     if phase == "train":
         assert len(default) >= floor[0] and len(combos - default) >= floor[1], (len(default), len(combos - default), floor)
+
+
+# entries of the wide matrix per mode, (train, eval): what tests/test_wide_channels_gpu.py runs.  Under the whole-plan dedupe of CASES math mode
+# bf16's train phase would hold 168; on the route tuple (block_routes.matrix_key) it is 126
+WIDE_ENTRIES = {"f32": (28, 28), "bf16x3": (69, 63), "f16x2": (58, 55), "bf16": (126, 60)}
+
+
+@pytest.mark.parametrize("phase", R.PHASES)
+@pytest.mark.parametrize("mode", R.ALL_MODES)
+def test_the_wide_matrix_leaves_no_route_out(mode, phase):
+    """WIDE_CASES (128 .. 512 channels): every route combination the planner produces for a wide case under ``option_sets``, per case, input
+    type, pw routing and mix order, is an entry of the wide matrix; every default-option entry is kept; no wide case is planned onto the
+    > 32-joint path; and the tile forms are really what the wide blocks run"""
+    entries = R.matrix(mode, phase, R.WIDE_CASES)
+    everything = R.plan_all(mode, phase, R.WIDE_CASES)
+    assert entries and all(e.plan.mode == mode and e.plan.train == (phase == "train") and not e.plan.wide and not e.plan.pool_groups for e in entries)
+    assert {e.case for e in entries} == set(R.WIDE_CASES)
+    reach = {(e.case.name, e.half, R.route_tuple(e.plan)) for e in everything}
+    kept = {(e.case.name, e.half, R.route_tuple(e.plan)) for e in entries}
+    lost = reach - kept
+    assert not lost, [(c, h, dict(zip(R.ROUTE_TUPLE, t))) for c, h, t in sorted(lost, key=str)]
+    assert {(e.case.name, R.matrix_key(e)) for e in everything} == {(e.case.name, R.matrix_key(e)) for e in entries}
+    kept_default = [e for e in entries if e.option_name == "default"]
+    assert kept_default == [e for e in everything if e.option_name == "default"]
+    assert len({(e.case.name, R.matrix_key(e)) for e in entries}) == len(entries)    # the default set comes first: no key runs twice
+    for f, v, modes in R.UNREACHABLE:
+        if mode in modes:
+            assert v not in {getattr(e.plan, f) for e in everything}, (mode, phase, f, v)
+    # the dedupe on the route tuple drops storage-type variants only: every plan it drops differs from the kept entry of its key in fields
+    # outside ROUTE_TUPLE alone (by construction of the key), and CASES' matrix holds every value of those fields that a wide case takes
+    narrow = {f: {getattr(e.plan, f) for e in R.matrix(mode, phase)} for f in R.PLAN_ROUTE_FIELDS if f not in R.ROUTE_TUPLE}
+    for f, vals in narrow.items():
+        assert {getattr(e.plan, f) for e in everything} <= vals, (mode, phase, f)
+    print(f"{mode} {phase}: {len(entries)} wide entries of {len(everything)} planned")
+    assert len(entries) >= WIDE_ENTRIES[mode][phase == "eval"], (len(entries), WIDE_ENTRIES[mode])      # (they only grow with option sets)
+    if mode != "f32":                # the default options send 192 .. 512 channels to the tile forms and the halo conv, as a wide model runs them
+        for c in R.WIDE_CASES[1:]:
+            pl = next(e.plan for e in kept_default if e.case == c and not e.half)
+            assert pl.spatial_bwd == "tile" and pl.spatial_wgrad == "tile" and pl.temporal_fwd in ("halo", "halo_parity"), (c.name, pl)

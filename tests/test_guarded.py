@@ -43,6 +43,40 @@ def test_a_changed_margin_byte_is_reported_with_side_offset_and_call_site(side):
     assert g.buffers == []                  # references dropped, also after a failure
 
 
+def test_a_wider_margin_is_laid_out_checked_and_reported_like_the_default_one():
+    """``Guard(margin=)``: the tensor starts ``margin`` bytes into its buffer, both margins are that long and 0xFF, damage at their far ends (beyond
+    where the default margin would stop) is found and reported relative to the tensor; the default stays MARGIN; a margin that would break the
+    512-byte alignment is refused"""
+    wide = 2 * MARGIN
+    with cpu_guard(margin=wide) as g:
+        t = torch.empty((3, 5), device="cpu", dtype=torch.float32)
+        b = g.buffers[-1]
+        assert b.raw.numel() == wide + 512 + wide and t.data_ptr() - b.raw.data_ptr() == wide and t.data_ptr() % 512 == b.raw.data_ptr() % 512
+        assert bool(t.isnan().all()) and bool((b.raw[:wide] == 255).all()) and bool((b.raw[wide + 60:] == 255).all())
+        (front, fm, fbase), (back, bm, bbase) = b.margins()
+        assert (front, fm.numel(), fbase, back, bm.numel(), bbase) == ("front", wide, -wide, "back", 512 - 60 + wide, 0)
+        t.fill_(1.0)
+        p = g.put(TORCH.arange(6.0))
+        assert p.data_ptr() - g.buffers[-1].raw.data_ptr() == wide and g.buffers[-1].margin == wide
+        g.check()                                            # clean, and the tensor's own bytes are not margin
+        torch.zeros(4, device="cpu")
+        g.buffers[-1].raw[0] = 1                             # the first byte of the front margin ...
+        g.buffers[-1].raw[-1] = 1                            # ... and the last of the back one
+        with pytest.raises(AssertionError) as exc:
+            g.check()
+    msg = str(exc.value)
+    assert f"front margin damaged, 1 bytes, offsets {-wide}..{-wide} relative to the tensor's start" in msg
+    assert f"back margin damaged, 1 bytes, offsets {512 - 16 + wide - 1}..{512 - 16 + wide - 1} relative to the tensor's end" in msg
+    with cpu_guard() as g:
+        torch.empty(4, device="cpu")
+        assert g.margin == MARGIN and g.buffers[-1].margin == MARGIN and g.buffers[-1].raw.numel() == MARGIN + 512 + MARGIN
+        g.check()
+    for bad in (0, -512, MARGIN + 4):
+        with pytest.raises(ValueError, match="multiple of 512"):
+            Guard(device="cpu", margin=bad)
+    assert guarded.active() is None
+
+
 def test_first_last_and_count_of_a_damaged_range():
     with cpu_guard() as g:
         torch.zeros((2, 3), device="cpu", dtype=torch.bfloat16)

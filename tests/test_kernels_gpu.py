@@ -115,6 +115,9 @@ def test_rows_gemm_data_gradient_map(kt, s, T):
     (2, 7, 32, 64, 64, 5, 1),       # V = 32, 5 taps
     (3, 40, 25, 256, 256, 9, 1),    # 256 channels
     (2, 11, 25, 64, 64, 7, 1),      # 7 taps: not instantiated -> falls back to the per-tap kernel
+    (1, 12, 25, 512, 512, 9, 1),    # the widths of a 128- / 192-wide model: four column tiles, 16 chunks of K
+    (2, 9, 18, 320, 320, 9, 1),     # 10 chunks of K, a ragged 64-column third tile
+    (2, 9, 20, 768, 256, 9, 1),     # 24 chunks of K
 ])
 def test_tconv_wgrad_all_taps_in_one_pass(B, T, V, K, N, kt, s):
     """The multi-tap temporal weight gradient equals autograd's conv weight gradient (and the per-tap kernel)."""
@@ -161,7 +164,10 @@ def test_all_taps_weight_gradient_over_random_shapes():
 
 @pytest.mark.parametrize("B,T,V,C,O,s", [(3, 20, 25, 64, 64, 1), (2, 21, 25, 64, 128, 2), (2, 20, 27, 128, 128, 2),
                                          (2, 13, 18, 128, 256, 1), (3, 7, 32, 32, 96, 1), (2, 1, 25, 64, 64, 2),
-                                         (1, 40, 25, 256, 256, 1), (2, 9, 20, 64, 64, 2)])
+                                         (1, 40, 25, 256, 256, 1), (2, 9, 20, 64, 64, 2),
+                                         # three and four 128-column tiles, a ragged 64-column third one, 6 .. 16 k-steps per tap
+                                         (2, 13, 25, 192, 192, 1), (2, 9, 18, 320, 320, 1), (1, 12, 25, 512, 512, 1),
+                                         (2, 13, 22, 256, 512, 2), (2, 9, 20, 192, 384, 2)])
 def test_halo_temporal_conv_forward_and_data_gradient(B, T, V, C, O, s):
     """The halo-tile kernel (input staged once per channel chunk, parity-split strides) vs the per-frame formula,
     through the same helpers the block uses; tiles straddle sample boundaries (T*V is not a multiple of 128)."""
@@ -199,7 +205,7 @@ def test_halo_temporal_conv_forward_and_data_gradient(B, T, V, C, O, s):
 @pytest.mark.parametrize("rows,K,N,ld_in,ld_out", [
     (3000, 64, 96, 64, 96), (2999, 96, 64, 96, 64), (1283, 128, 384, 128, 384), (517, 192, 128, 192, 128), (4097, 256, 768, 256, 768),
     (130, 384, 256, 384, 256), (1000, 64, 128, 64, 128), (127, 32, 4, 36, 8), (12000, 64, 192, 64, 192), (70000, 64, 64, 64, 64),
-    (700, 96, 192, 96, 192), (300, 32, 128, 32, 128), (513, 160, 132, 160, 136)])
+    (700, 96, 192, 96, 192), (300, 32, 128, 32, 128), (513, 160, 132, 160, 136), (700, 512, 512, 512, 512), (517, 320, 480, 320, 480)])
 def test_persistent_pointwise_gemm(rows, K, N, ld_in, ld_out):
     """ops.pw_gemm (fgcn_pw.hip): the block's 1x1 convolutions in the split-bf16 modes -- out = in . W + bias with BatchNorm
     partial sums, and the accumulating form -- against float64; ragged last tile, 32-channel tail chunk (K = 96), one and several
@@ -241,7 +247,8 @@ def test_persistent_pointwise_gemm(rows, K, N, ld_in, ld_out):
 
 
 @pytest.mark.math_modes("bf16x3")
-@pytest.mark.parametrize("B,T,V,C", [(3, 37, 25, 64), (2, 21, 25, 128), (2, 9, 27, 256), (1, 50, 22, 64), (5, 3, 18, 128), (2, 40, 32, 64)])
+@pytest.mark.parametrize("B,T,V,C", [(3, 37, 25, 64), (2, 21, 25, 128), (2, 9, 27, 256), (1, 50, 22, 64), (5, 3, 18, 128), (2, 40, 32, 64),
+                                     (2, 9, 25, 320), (1, 12, 20, 512)])
 def test_halo_temporal_conv_with_the_input_stage_fused(B, T, V, C):
     """North-star kernel 2 as the north star states it: G = relu(BatchNorm(y) + x) (agcn.py:113-115) formed INSIDE the 9x1 temporal
     conv while it stages its image (`fuse_in`), against the two-pass form (bn_act, then the conv on G): the conv output and its
@@ -306,6 +313,8 @@ def test_rows_wgrad(B, T, V, K, N, kt, s):
     (2, 9, 20, 160, 36, 1),       # 5 chunks, ragged N
     (1, 1, 5, 32, 4, 1),          # tiny: one frame, one chunk
     (2, 10, 25, 224, 64, 1),      # 7 chunks: not a multiple of the per-wave chunk count (tile tail reads zeros)
+    (1, 12, 25, 512, 512, 1),     # 16 chunks, four column tiles
+    (2, 9, 18, 320, 320, 1),      # 10 chunks, a ragged 64-column third tile
 ])
 def test_pointwise_wgrad_channel_chunks(B, T, V, K, N, s):
     """1x1 weight gradients on the multi-accumulator kernel (one accumulator per 32-channel chunk) equal autograd and the
@@ -600,7 +609,10 @@ def test_halo_conv_wave_arrangements_agree(B, T, V, C):
 
 @pytest.mark.math_modes("bf16x3")
 @pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 64, 64, 2),
-                                             (16, 8, 128, 128, 1), (32, 5, 64, 96, 1), (22, 31, 256, 256, 1), (25, 300, 64, 64, 1)])
+                                             (16, 8, 128, 128, 1), (32, 5, 64, 96, 1), (22, 31, 256, 256, 1), (25, 300, 64, 64, 1),
+                                             (25, 7, 256, 512, 2), (20, 6, 512, 512, 1), (18, 9, 320, 320, 2), (22, 9, 192, 384, 1),
+                                             (27, 5, 384, 768, 1),
+                                             (22, 9, 192, 192, 2)])      # six input tiles in the two-frames-per-wave form it is compared with
 def test_spatial_forward_tile_form(V, T, cin, cout, B):
     """The fused spatial forward in its tile form (fgcn_spatial_tile.hip: 128 / V whole frames per workgroup, the aggregation of a
     (channel tile, subset) pair formed once per workgroup into an LDS image): y = sum_k (x . A^_k) . Wd_k + bias against the float64
@@ -620,9 +632,10 @@ def test_spatial_forward_tile_form(V, T, cin, cout, B):
     assert rel_l2(s[1].numpy(), (y.double() ** 2).sum((0, 1, 2)).cpu().numpy()) < RED_TOL
     y2, part2 = ops.spatial_fwd_tile(to_gpu(x), to_gpu(a), w3, to_gpu(bias), Cin=cin, Cout=cout, stats=True)
     assert torch.equal(y, y2) and torch.equal(part, part2)
-    y_old, _ = ops.spatial_fwd(to_gpu(x), to_gpu(a), ops.pack_spatial(to_gpu(wd.reshape(3 * cin, cout)), cin), to_gpu(bias), Cin=cin,
-                               Cout=cout, stats=False)
-    assert rel_l2(y.cpu().numpy(), y_old.cpu().numpy()) < FWD_TOL
+    if max(cin, cout) <= 256:                   # (the width of the two-frames-per-wave form: eight 32-channel tiles)
+        y_old, _ = ops.spatial_fwd(to_gpu(x), to_gpu(a), ops.pack_spatial(to_gpu(wd.reshape(3 * cin, cout)), cin), to_gpu(bias), Cin=cin,
+                                   Cout=cout, stats=False)
+        assert rel_l2(y.cpu().numpy(), y_old.cpu().numpy()) < FWD_TOL
     shared, _ = ops.spatial_fwd_tile(to_gpu(x), to_gpu(a[:1]), w3, None, Cin=cin, Cout=cout, stats=False)
     want1 = torch.einsum("btwkc,kco->btwo", torch.einsum("btvc,kvw->btwkc", x.double(), a[0].double()), wd.double())
     assert rel_l2(shared.cpu().numpy(), want1.numpy()) < FWD_TOL
@@ -655,7 +668,9 @@ def test_joint_dagg_fused_dx_and_gram(V, T, C, B):
 @pytest.mark.math_modes("bf16x3", "f16x2")
 @pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 64, 64, 2),
                                              (16, 8, 128, 128, 1), (32, 5, 64, 64, 1), (22, 31, 256, 256, 1), (25, 300, 64, 64, 1),
-                                             (17, 23, 64, 128, 2), (21, 12, 128, 64, 3)])
+                                             (17, 23, 64, 128, 2), (21, 12, 128, 64, 3),
+                                             (25, 7, 256, 512, 2), (20, 6, 512, 512, 1), (18, 9, 320, 320, 2), (22, 9, 192, 384, 1),
+                                             (27, 5, 384, 768, 1)])
 def test_spatial_backward_tile_form(V, T, cin, cout, B):
     """The fused backward of the spatial stage in tile form (fgcn_spatial_bwd_tile.hip: dagg = dy . Wd on chip only): dx (+)=
     sum_k dagg_k . A^_k^T and the partial grams dA^_k = x^T dagg_k against the float64 einsums (backward of agcn.py:103-111), with and
@@ -713,7 +728,9 @@ def test_spatial_backward_tile_form(V, T, cin, cout, B):
 @pytest.mark.math_modes("bf16x3", "f16x2")
 @pytest.mark.parametrize("V,T,cin,cout,B", [(25, 13, 64, 64, 2), (25, 7, 128, 256, 2), (27, 9, 64, 128, 1), (18, 10, 64, 64, 2),
                                              (16, 8, 128, 128, 1), (32, 5, 64, 64, 1), (22, 31, 256, 256, 1), (25, 300, 64, 64, 1),
-                                             (17, 23, 64, 128, 2), (21, 12, 128, 64, 3), (25, 20, 192, 64, 5), (19, 2, 64, 192, 3)])
+                                             (17, 23, 64, 128, 2), (21, 12, 128, 64, 3), (25, 20, 192, 64, 5), (19, 2, 64, 192, 3),
+                                             (25, 7, 256, 512, 2), (20, 6, 512, 512, 1), (18, 9, 320, 320, 2), (22, 9, 192, 384, 1),
+                                             (27, 5, 384, 768, 1)])
 def test_spatial_weight_gradient_tile_form(V, T, cin, cout, B):
     """conv_d's weight gradient in tile form (fgcn_spatial_wgrad_tile.hip: agg = x . A^ on chip only) against the float64 einsum
     (backward of agcn.py:103-111 with respect to conv_d[k].weight): per-sample and shared adjacency, ragged last frame group,
@@ -766,7 +783,8 @@ def test_spatial_weight_gradient_tile_form(V, T, cin, cout, B):
 
 @pytest.mark.math_modes("bf16x3", "f16x2")
 @pytest.mark.parametrize("V,T,cin,ic,B", [(25, 13, 64, 16, 2), (25, 7, 256, 64, 2), (27, 9, 64, 32, 1), (18, 10, 128, 32, 2), (16, 8, 128, 64, 1),
-                                          (32, 5, 64, 16, 1), (22, 31, 256, 64, 1), (25, 300, 64, 16, 1), (17, 23, 32, 16, 2), (21, 12, 96, 32, 3)])
+                                          (32, 5, 64, 16, 1), (22, 31, 256, 64, 1), (25, 300, 64, 16, 1), (17, 23, 32, 16, 2), (21, 12, 96, 32, 3),
+                                          (25, 7, 512, 64, 2), (18, 9, 320, 32, 2)])
 def test_embedding_forward_tile_form(V, T, cin, ic, B):
     """The forward of the attention embeddings with the affinity gram on chip (fgcn_emb_fwd_tile.hip; reference agcn.py:104-106): emb = x . Wemb
     + b and the partial grams theta_k^T phi_k against the float64 formulas -- ic = 16 / 32 (all six groups in one workgroup) and 64 (one subset
@@ -832,7 +850,7 @@ def emb_backward_reference(emb, ds, x, w, ic):
 
 EMB_TILE_SHAPES = [(25, 13, 16, 64, 2), (25, 7, 64, 256, 2), (27, 9, 32, 64, 1), (18, 10, 16, 64, 2), (16, 8, 32, 128, 1), (32, 5, 64, 128, 1),
                    (22, 31, 64, 256, 1), (25, 300, 16, 64, 1), (17, 23, 48, 128, 2), (21, 12, 32, 128, 3), (25, 20, 16, 128, 3),
-                   (19, 2, 128, 64, 2)]
+                   (19, 2, 128, 64, 2), (18, 9, 80, 320, 2), (20, 6, 128, 512, 2)]
 
 
 @pytest.mark.math_modes("bf16x3", "f16x2")
@@ -913,7 +931,7 @@ def test_embedding_backward_tile_form(V, T, ic, cx, B):
 
 
 @pytest.mark.math_modes("bf16x3", "f16x2")
-@pytest.mark.parametrize("B,T,V,C", [(3, 20, 25, 64), (2, 13, 18, 128), (1, 40, 25, 256), (2, 9, 27, 64)])
+@pytest.mark.parametrize("B,T,V,C", [(3, 20, 25, 64), (2, 13, 18, 128), (1, 40, 25, 256), (2, 9, 27, 64), (2, 13, 18, 320), (1, 12, 25, 512)])
 def test_halo_data_gradient_emits_the_batchnorm_backward_sums(B, T, V, C, fgcn_math):
     """fgcn_tconv_halo with bn_a / bn_mask / bn_vec: the data gradient dG and, from its epilogue, sum dP and sum dP * a_hat with
     dP = dG * [G > 0] (backward of G = relu(BN(a) + x), agcn.py:113-115) -- against the float64 formulas and against the
@@ -1020,7 +1038,7 @@ def test_joint_gram_general_operands():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C,res_mode", [(64, 0), (64, 1), (128, 2), (256, 2), (16, 1), (12, 1)])
+@pytest.mark.parametrize("C,res_mode", [(64, 0), (64, 1), (128, 2), (256, 2), (16, 1), (12, 1), (320, 2), (512, 2), (384, 1)])
 def test_batchnorm_epilogue_forward_backward(C, res_mode):
     from fusion_gcn_amd import ops
     rows = 3 * 17 * 25
@@ -1239,7 +1257,8 @@ def _eval_vec(C, seed):
 
 @pytest.mark.math_modes("bf16x3")
 @pytest.mark.parametrize("B,T,V,C,kt,res", [(3, 37, 25, 64, 9, "identity"), (2, 21, 25, 128, 9, "identity"), (2, 9, 27, 256, 9, "conv"),
-                                            (1, 50, 22, 64, 9, "none"), (2, 40, 32, 128, 5, "identity"), (130, 5, 18, 64, 3, "conv")])
+                                            (1, 50, 22, 64, 9, "none"), (2, 40, 32, 128, 5, "identity"), (130, 5, 18, 64, 3, "conv"),
+                                            (2, 9, 25, 512, 9, "identity"), (2, 9, 18, 320, 9, "conv")])
 def test_temporal_conv_with_batchnorm_shortcut_and_relu_in_one_kernel(B, T, V, C, kt, res):
     """North-star kernel 2 as the north star states it, inference form (fgcn_tconv_halo_bn_relu): out = relu(BN(conv(g) + bias) +
     [x | BN_r(r)]) against float64 and against the two-kernel form (fgcn_tconv_halo + fgcn_bn_act with the same eval-mode vectors),
@@ -1278,7 +1297,8 @@ def test_temporal_conv_with_batchnorm_shortcut_and_relu_in_one_kernel(B, T, V, C
 
 @pytest.mark.math_modes("bf16x3")
 @pytest.mark.parametrize("V,T,cin,cout,B,down", [(25, 13, 64, 64, 2, False), (25, 7, 128, 256, 2, True), (27, 9, 64, 128, 1, True),
-                                                  (18, 10, 128, 128, 2, False), (22, 31, 256, 256, 1, False), (32, 5, 64, 64, 3, False)])
+                                                  (18, 10, 128, 128, 2, False), (22, 31, 256, 256, 1, False), (32, 5, 64, 64, 3, False),
+                                                  (25, 7, 256, 512, 2, True), (20, 6, 512, 512, 1, False)])
 def test_spatial_stage_with_batchnorm_shortcut_and_relu_in_one_kernel(V, T, cin, cout, B, down):
     """North-star kernel 1, inference form (fgcn_spatial_fwd_tile_bn_relu): g = relu(BN(sum_k (x . A^_k) . Wd_k + bias) + [x | BN_d(d)])
     against float64 and against fgcn_spatial_fwd_tile + fgcn_bn_act; identity shortcut (cin == cout) and the down branch."""
