@@ -116,7 +116,7 @@ SIGNATURES = {
     "fgcn_rows_gemm_batched2": (_I, [_P, _P, _P, _I, _LL, _LL, _LL, _I, _LL, _LL, _LL, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_rows_gemm_tiles": (_I, [_LL]),
     "fgcn_tconv_halo_tiles": (_I, [_I, _I, _I, _I]),
-    "fgcn_tconv_halo": (_I, [_P] * 5 + [_I] * 18 + [_P] * 8 + [_I, _P]),
+    "fgcn_tconv_halo": (_I, [_P] * 3 + [_I] + [_P] * 2 + [_I] * 18 + [_P] * 8 + [_I, _P]),
     "fgcn_tconv_halo_bn_sums": (_I, []),
     "fgcn_rows_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, TMap, _I, _P]),
     "fgcn_tconv_wgrad_slabs": (_I, [_I, _I]),
@@ -175,7 +175,7 @@ SIGNATURES = {
     "fgcn_bn_bwd_reduce_ld": (_I, [_P, _I, _P, _P, _P, _I, _LL, _I, _P]),
     "fgcn_bn_bwd_apply_ld": (_I, [_P, _I, _P, _P, _P, _P, _LL, _I, _I, _P]),
     "fgcn_col_sum": (_I, [_P, _P, _LL, _I, _I, _P]),
-    "fgcn_spatial_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fgcn_spatial_fwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_spatial_tiles": (_I, [_I, _I]),
     "fgcn_spatial_fwd_tile": (_I, [_P] * 6 + [_I] * 9 + [_P]),
     "fgcn_spatial_fwd_tile_tiles": (_I, [_I, _I, _I]),
@@ -192,7 +192,7 @@ SIGNATURES = {
     "fgcn_unfold_windows": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_pw_gemm_available": (_I, []),
     "fgcn_pw_gemm_tiles": (_I, [_LL]),
-    "fgcn_pw_gemm": (_I, [_P] * 5 + [_LL] + [_I] * 5 + [_P, _I, _P]),
+    "fgcn_pw_gemm": (_I, [_P] * 3 + [_I] + [_P] * 2 + [_LL] + [_I] * 5 + [_P, _I, _P]),
     "fgcn_data_bn_tiles": (_I, [_I, _I]),
     "fgcn_data_bn_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fgcn_data_bn_apply": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -27,6 +27,23 @@ static inline fgcn_ctx& cur() { return t_current ? *t_current : g_default; }
 int tuning(int key) { return (key >= 0 && key < 32) ? cur().tuning[key] : 0; }
 int math_mode() { return cur().math_mode; }
 int products() { return cur().products; }
+
+const char* pack_form_name(int form) {
+    static const char* const names[] = {"FGCN_PACK_PLAIN",      "FGCN_PACK_K4",      "FGCN_PACK_SPLIT3",
+                                        "FGCN_PACK_SPLIT3_ACC", "FGCN_PACK_SPLIT2H", "FGCN_PACK_SPLIT2H_ACC"};
+    return form >= 0 && form <= FGCN_PACK_SPLIT2H_ACC ? names[form] : "no FGCN_PACK_* form";
+}
+const char* math_mode_name(int mode) {
+    return mode == FGCN_MATH_F32 ? "FGCN_MATH_F32" : mode == FGCN_MATH_BF16 ? "FGCN_MATH_BF16" : "FGCN_MATH_BF16X3";
+}
+int check_conv_form(const char* what, int w_form) {
+    const int mm = math_mode();
+    const bool ok = mm == FGCN_MATH_F32 ? w_form == FGCN_PACK_K4
+                                        : (w_form == FGCN_PACK_SPLIT3 || (mm == FGCN_MATH_BF16X3 && w_form == FGCN_PACK_SPLIT2H));
+    FGCN_REQUIRE(ok, FGCN_E_BADARG, "%s: w_form=%d (%s) is not a weight form of math mode %s", what, w_form, pack_form_name(w_form),
+                 math_mode_name(mm));
+    return FGCN_OK;
+}
 }  // namespace fgcn
 
 extern "C" int fgcn_ctx_create(fgcn_ctx** out) {
@@ -75,7 +92,7 @@ extern "C" int fgcn_set_tuning(int key, int value) {
 
 extern "C" int fgcn_get_tuning(int key) { return fgcn::tuning(key); }
 
-extern "C" int fgcn_version(void) { return 200; }  // 0.2.0
+extern "C" int fgcn_version(void) { return 300; }  // 0.3.0: w_form (include/fgcn.h, "Product form")
 
 extern "C" const char* fgcn_last_error(void) { return fgcn::error_buffer(); }
 

@@ -127,7 +127,14 @@ inline bool stream_out(long long bytes) {
 }
 int math_mode();   // FGCN_MATH_F32 / FGCN_MATH_BF16 / FGCN_MATH_BF16X3 (fgcn_set_math_mode)
 int products();    // FGCN_PRODUCTS_BF16X3 / FGCN_PRODUCTS_F16X2 inside FGCN_MATH_BF16X3 (fgcn_set_products)
-inline bool f16x2_products() { return math_mode() == FGCN_MATH_BF16X3 && products() == FGCN_PRODUCTS_F16X2; }
+// Mode "f16x2" = FGCN_MATH_BF16X3 + FGCN_PRODUCTS_F16X2.  For mode-level decisions only (which kernels the mode offers: the
+// *_available queries, the inference forms): the layout of a weight argument is never read from here, the caller states it (w_form)
+inline bool f16x2_mode() { return math_mode() == FGCN_MATH_BF16X3 && products() == FGCN_PRODUCTS_F16X2; }
+// w_form of fgcn_tconv_halo / fgcn_pw_gemm (a FGCN_PACK_* constant) against the math mode, before anything else: FGCN_MATH_F32 takes
+// FGCN_PACK_K4, FGCN_MATH_BF16 FGCN_PACK_SPLIT3, FGCN_MATH_BF16X3 FGCN_PACK_SPLIT3 or FGCN_PACK_SPLIT2H.  (fgcn_api.hip)
+const char* pack_form_name(int form);
+const char* math_mode_name(int mode);
+int check_conv_form(const char* what, int w_form);
 
 // ---- device: ReLU with torch's rules for NaN (include/fgcn.h, "Non-finite values") --------------------------------------
 // relu_nan: max(v, 0) that keeps a NaN (fmaxf returns the other operand, so fmaxf(NaN, 0) is 0 and a NaN pre-activation would leave the

@@ -386,8 +386,9 @@ extern "C" int fgcn_pw_gemm_available(void) {
 
 // half_mask (math mode bf16, half-precision activation storage): bit 0 = `in` is a bfloat16 tensor, bit 1 = `out` is (not with
 // accumulation); strides in elements; stat_partials: the moments of the float32 results
-extern "C" int fgcn_pw_gemm(const void* in, void* out, const void* w3, const float* bias, float* stat_partials, long long rows,
+extern "C" int fgcn_pw_gemm(const void* in, void* out, const void* w3, int w_form, const float* bias, float* stat_partials, long long rows,
                             int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, int half_mask, void* stream_) {
+    if (int e = fgcn::check_conv_form("pw_gemm", w_form)) return e;
     FGCN_REQUIRE((half_mask & ~3) == 0 && !((half_mask & 2) && accumulate), FGCN_E_BADARG, "pw_gemm: half_mask=%d (a bfloat16 output: no accumulation)",
                  half_mask);
     const bool in16 = half_mask & 1, out16 = half_mask & 2;
@@ -406,7 +407,8 @@ extern "C" int fgcn_pw_gemm(const void* in, void* out, const void* w3, const flo
     p.M = rows;
     p.in_bytes = (unsigned)in_bytes; p.out_bytes = (unsigned)out_bytes; p.w_plane_bytes = (unsigned)plane;
     p.K = K; p.N = N; p.ld_in = ld_in; p.ld_out = ld_out; p.accumulate = accumulate;
-    p.in_amax = fgcn::f16x2_products() ? in_amax : nullptr;
+    const bool two = w_form == FGCN_PACK_SPLIT2H;      // two f16 parts: the f16x2 products
+    p.in_amax = two ? in_amax : nullptr;
     const bool narrow = N <= 64;
     p.tiles_m = (int)cdiv(rows, 128);
     p.tiles_n = (int)cdiv(N, narrow ? 64 : 128);
@@ -419,7 +421,7 @@ extern "C" int fgcn_pw_gemm(const void* in, void* out, const void* w3, const flo
     if (fgcn::tuning(8) == 1) per = p.per_xcd;
     p.wg_per_xcd = p.per_xcd < per ? p.per_xcd : per;
     const dim3 grid((unsigned)(p.wg_per_xcd * 8));
-    const bool one = fgcn::math_mode() == FGCN_MATH_BF16, two = fgcn::f16x2_products();
+    const bool one = fgcn::math_mode() == FGCN_MATH_BF16;
     const size_t lds = (size_t)128 * 128 * (one ? 1 : (two ? 2 : 3)) + 16;
     hipStream_t s = (hipStream_t)stream_;
     const bool str = !accumulate && !out16 && fgcn::stream_out(rows * (long long)N * 4);

@@ -648,7 +648,7 @@ __global__ __launch_bounds__(256, 2) void spatial_fwd_x3_kernel(SpatialP p) {
 using namespace fgcn;
 
 template <int CI>
-static void launch_spatial_x3(const SpatialP& p, hipStream_t s) {
+static void launch_spatial_x3(const SpatialP& p, bool two, hipStream_t s) {      // two: FGCN_PACK_SPLIT2H_ACC weights
     const size_t lds = (size_t)9 * 32 * AHB + (4 * 2 * 64 + 4 * 32 * TTS + 64) * sizeof(float);
     dim3 grid((unsigned)cdiv(p.T, p.t_chunk), (unsigned)p.B, (unsigned)cdiv(p.Cout, 64));
     SpatialP q = p;
@@ -661,7 +661,7 @@ static void launch_spatial_x3(const SpatialP& p, hipStream_t s) {
         grid = dim3((unsigned)(q.per_xcd * 8));
     }
     const bool str = fgcn::stream_out((long long)p.B * p.T * p.V * p.Cout * 4);
-    if (fgcn::f16x2_products()) {
+    if (two) {
         if (str) hipLaunchKernelGGL((spatial_fwd_x3_kernel<CI, 2, true>), grid, dim3(256), lds, s, q);
         else hipLaunchKernelGGL((spatial_fwd_x3_kernel<CI, 2>), grid, dim3(256), lds, s, q);
     } else {
@@ -707,9 +707,16 @@ static int dispatch_out(int co, const SpatialP& p, hipStream_t s) {
     return -1;
 }
 
-extern "C" int fgcn_spatial_fwd(const float* x, const float* a_hat, const float* wd, const float* bias_sum, float* y,
+extern "C" int fgcn_spatial_fwd(const float* x, const float* a_hat, const float* wd, int w_form, const float* bias_sum, float* y,
                                 float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
                                 int n_subsets, int a_hat_batched, void* stream) {
+    // the form of wd against the math mode and the input width, before anything else: the split kernel (FGCN_MATH_BF16X3, whole 32-channel
+    // tiles) takes an accumulator-ordered split form, everything else the k-interleaved float32 one
+    const bool split = fgcn::math_mode() == FGCN_MATH_BF16X3 && Cin > 0 && Cin % 32 == 0;
+    const bool two = w_form == FGCN_PACK_SPLIT2H_ACC;      // two f16 parts: the f16x2 products
+    FGCN_REQUIRE(split ? (w_form == FGCN_PACK_SPLIT3_ACC || two) : w_form == FGCN_PACK_K4, FGCN_E_BADARG,
+                 "spatial_fwd: w_form=%d (%s) is not the weight form of math mode %s with Cin=%d (%s)", w_form, fgcn::pack_form_name(w_form),
+                 fgcn::math_mode_name(fgcn::math_mode()), Cin, split ? "FGCN_PACK_SPLIT3_ACC or FGCN_PACK_SPLIT2H_ACC" : "FGCN_PACK_K4");
     FGCN_REQUIRE(x && a_hat && wd && y, FGCN_E_BADARG, "spatial_fwd: null pointer");
     FGCN_REQUIRE(B > 0 && B <= 65535 && T > 0 && V > 0 && V <= FGCN_MAX_V && Cin > 0 && Cout > 0, FGCN_E_BADARG,
                  "spatial_fwd: bad sizes B=%d T=%d V=%d Cin=%d Cout=%d", B, T, V, Cin, Cout);
@@ -722,9 +729,8 @@ extern "C" int fgcn_spatial_fwd(const float* x, const float* a_hat, const float*
     auto tiles = [](int c) { int t = (c + 31) / 32; return t <= 1 ? 1 : t <= 2 ? 2 : t <= 4 ? 4 : t <= 8 ? 8 : -1; };
     const int ci = tiles(Cin), co = tiles(Cout);
     FGCN_REQUIRE(ci > 0 && co > 0, FGCN_E_BADARG, "spatial_fwd: at most 256 channels (Cin=%d Cout=%d)", Cin, Cout);
-    const bool split = fgcn::math_mode() == FGCN_MATH_BF16X3 && Cin % 32 == 0;   // wd: fgcn_pack_split3(acc_order) form
     const long long x_bytes = (long long)B * T * V * ld_x * 4;
-    const long long w_bytes = (long long)n_subsets * Cin * Cout * (split ? (fgcn::f16x2_products() ? 4 : 6) : 4);
+    const long long w_bytes = (long long)n_subsets * Cin * Cout * (split ? (two ? 4 : 6) : 4);
     FGCN_REQUIRE(fits_buffer(x_bytes), FGCN_E_BADARG, "spatial_fwd: x must be smaller than 2 GiB (32-bit buffer offsets)");
     FGCN_REQUIRE(aligned16(x) || true, FGCN_E_ALIGN, "spatial_fwd: alignment");
     SpatialP p{x, a_hat, wd, bias_sum, y, stat_partials, B, T, V, Cin, Cout, ld_x, ld_y, n_subsets, a_hat_batched,
@@ -733,14 +739,14 @@ extern "C" int fgcn_spatial_fwd(const float* x, const float* a_hat, const float*
     hipStream_t s = (hipStream_t)stream;
     int rc = -1;
     // two frames per wave, split-bf16 aggregation (tuning key 7 bit 0: the older form below, which reads the three-part bf16 weights only:
-    // with the f16x2 products `wd` is the FGCN_PACK_SPLIT2H_ACC form and the bit selects nothing)
-    if (split && (!(fgcn::tuning(7) & 1) || fgcn::f16x2_products())) {
+    // for a FGCN_PACK_SPLIT2H_ACC `wd` the bit selects nothing)
+    if (split && (!(fgcn::tuning(7) & 1) || two)) {
         switch (Cin / 32) {
-            case 1: launch_spatial_x3<1>(p, s); break;
-            case 2: launch_spatial_x3<2>(p, s); break;
-            case 4: launch_spatial_x3<4>(p, s); break;
-            case 8: launch_spatial_x3<8>(p, s); break;
-            default: launch_spatial_x3<0>(p, s); break;      // 3, 5, 6 or 7 tiles (ci > 0: Cin <= 256)
+            case 1: launch_spatial_x3<1>(p, two, s); break;
+            case 2: launch_spatial_x3<2>(p, two, s); break;
+            case 4: launch_spatial_x3<4>(p, two, s); break;
+            case 8: launch_spatial_x3<8>(p, two, s); break;
+            default: launch_spatial_x3<0>(p, two, s); break;      // 3, 5, 6 or 7 tiles (ci > 0: Cin <= 256)
         }
         return launch_status("spatial_fwd");
     }

@@ -392,7 +392,7 @@ static int sp_tile_frames(int V) { return 128 / V; }
 // 1 when fgcn_spatial_fwd_tile runs these sizes in the current math mode (split-bf16 products, whole 64-channel input groups,
 // 16..32 joints: at most 8 frames per 128-row tile)
 extern "C" int fgcn_spatial_fwd_tile_available(int V, int Cin, int Cout) {
-    return (((fgcn::math_mode() == FGCN_MATH_BF16X3 && !fgcn::f16x2_products()) || fgcn::math_mode() == FGCN_MATH_BF16) && V >= 16 && V <= FGCN_MAX_V &&
+    return (((fgcn::math_mode() == FGCN_MATH_BF16X3 && !fgcn::f16x2_mode()) || fgcn::math_mode() == FGCN_MATH_BF16) && V >= 16 && V <= FGCN_MAX_V &&
             Cin % 64 == 0 && Cout % 4 == 0) ? 1 : 0;
 }
 

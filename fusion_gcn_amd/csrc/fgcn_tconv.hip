@@ -880,8 +880,9 @@ constexpr bool halo_k32_built(int NT, int KC, int NP, int EPI, bool FIN, int WR,
     return NT == 2 || (NT == 4 && (EPI == 0 || EPI == 3));
 }
 
-// the body of fgcn_tconv_halo and fgcn_tconv_halo_bn_relu (ep_vec: the inference output stage); half_mask as for fgcn_tconv_halo
-static int tconv_halo_impl(const float* in, float* out, const float* w4, const float* bias, float* stat_partials,
+// the body of fgcn_tconv_halo and fgcn_tconv_halo_bn_relu (ep_vec: the inference output stage); half_mask as for fgcn_tconv_halo; w_form: the
+// layout of w4, already checked against the math mode (check_conv_form)
+static int tconv_halo_impl(const float* in, float* out, const float* w4, int w_form, const float* bias, float* stat_partials,
                            int B, int Th, int V, int K, int N, int ld_in, int ld_out,
                            int T_in_full, int in_s, int in_o, int Th_in,
                            int T_out_full, int out_s, int out_o,
@@ -892,18 +893,19 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
     const bool in16 = half_mask & 1, out16 = half_mask & 2;
     FGCN_REQUIRE(in && out && w4, FGCN_E_BADARG, "tconv_halo: null pointer");
     const bool fep = ep_vec != nullptr;
-    FGCN_REQUIRE(!fep || ((fgcn::math_mode() == FGCN_MATH_BF16X3 || fgcn::math_mode() == FGCN_MATH_BF16) && !fgcn::f16x2_products() && !in16 &&
-                          !accumulate && !bn_a && !stat_partials && !(fin_vec || fin_res || fin_out || fin_mask) && taps > 1 && out_s == 1 && out_o == 0 &&
-                          T_out_full == Th && aligned16(ep_vec) && (!ep_res || aligned16(ep_res)) && (!ep_rvec || ep_res)),
-                 FGCN_E_BADARG, "tconv_halo_bn_relu: the inference output stage needs the split kernel (bf16x3 products or bf16), the tap form, a "
-                 "plain output view, no statistics / accumulation / fused input stage");
+    const bool two = w_form == FGCN_PACK_SPLIT2H;                                           // two f16 parts: the f16x2 products
+    // (the inference output stage: fgcn_tconv_halo_bn_relu has checked the mode and hands over a FGCN_PACK_SPLIT3 form)
+    FGCN_REQUIRE(!fep || (!in16 && !accumulate && !bn_a && !stat_partials && !(fin_vec || fin_res || fin_out || fin_mask) && taps > 1 && out_s == 1 &&
+                          out_o == 0 && T_out_full == Th && aligned16(ep_vec) && (!ep_res || aligned16(ep_res)) && (!ep_rvec || ep_res)),
+                 FGCN_E_BADARG, "tconv_halo_bn_relu: the inference output stage needs the tap form, a plain output view, no statistics / "
+                 "accumulation / fused input stage");
     FGCN_REQUIRE(!in16 || (fgcn::math_mode() == FGCN_MATH_BF16 && !(fin_vec || fin_res || fin_out || fin_mask) && !(taps == 1 && K % 64 == 0)),
                  FGCN_E_BADARG, "tconv_halo: a bfloat16 input needs math mode bf16, the tap form and no fused input stage");
     // (a bfloat16 output: the plain store epilogue, with or without the forward moments)
     FGCN_REQUIRE(!out16 || (!accumulate && !bn_a && !fep && ld_out % 2 == 0), FGCN_E_BADARG,
                  "tconv_halo: a bfloat16 output is written by the plain store epilogue (no accumulation, no BatchNorm-backward sums)");
     const bool fin = fin_vec || fin_res || fin_out || fin_mask;
-    FGCN_REQUIRE(!fin || !fgcn::f16x2_products(), FGCN_E_BADARG, "tconv_halo: the fused input stage is not built for the f16x2 products");
+    FGCN_REQUIRE(!fin || !two, FGCN_E_BADARG, "tconv_halo: the fused input stage is not built for the f16x2 products");
     FGCN_REQUIRE(!fin || (fin_vec && fin_res && fin_out && fin_mask && fgcn_tconv_halo_bn_sums() && !bn_a && !accumulate && taps > 1 &&
                           ld_in == K && in_s == 1 && in_o == 0 && Th_in == T_in_full && Th_in == Th && aligned16(fin_res) &&
                           aligned16(fin_out) && aligned16(fin_vec) && ((uintptr_t)fin_mask & 3u) == 0),
@@ -928,7 +930,6 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
     // FGCN_MATH_BF16X3 / FGCN_MATH_BF16: w4 is the split form (fgcn_pack_split3: three bf16 parts of [tap][K/8][N][8]) = 6 bytes
     // per weight; the bf16 mode reads part 0 only (the round-to-nearest-even bf16 of the weight)
     const long long in_bytes = (long long)B * T_in_full * V * ld_in * (in16 ? 2 : 4);
-    const bool two = fgcn::f16x2_products();                                                // FGCN_PACK_SPLIT2H weights: two f16 parts
     const long long w_bytes = (long long)taps * K * N * (mm != FGCN_MATH_F32 ? (two ? 4 : 6) : 4);   // split form in both bf16 modes
     const long long out_bytes = (long long)B * T_out_full * V * ld_out * (out16 ? 2 : 4);
     FGCN_REQUIRE(fits_buffer(in_bytes) && fits_buffer(w_bytes) && fits_buffer(out_bytes), FGCN_E_BADARG,
@@ -948,7 +949,7 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
     p.bn_a = bn_a; p.bn_mask = bn_mask; p.bn_vec = bn_vec;
     p.fin_vec = fin_vec; p.fin_res = fin_res; p.fin_out = fin_out; p.fin_mask = fin_mask;
     p.ep_vec = ep_vec; p.ep_res = ep_res; p.ep_rvec = ep_rvec;
-    p.in_amax = fgcn::f16x2_products() ? in_amax : nullptr;
+    p.in_amax = two ? in_amax : nullptr;
     const int d0 = tc, d1 = (taps - 1) * tb + tc;
     p.dmin = d0 < d1 ? d0 : d1;
     const int dmax = d0 < d1 ? d1 : d0;
@@ -1035,15 +1036,16 @@ static int tconv_halo_impl(const float* in, float* out, const float* w4, const f
 // input: masks 0, 1, 3).  A bfloat16 input (G of fgcn_bn_act, dU of fgcn_bn_act_bwd_apply) is bit-identical to the call on the f32 tensor those
 // kernels would have written: the bf16 kernel rounds its input to bfloat16, to nearest even, as it stages it.  A bfloat16 output takes the plain
 // store epilogue; stat_partials are then the forward moments of the float32 accumulators.
-extern "C" int fgcn_tconv_halo(const void* in, void* out, const float* w4, const float* bias, float* stat_partials,
+extern "C" int fgcn_tconv_halo(const void* in, void* out, const float* w4, int w_form, const float* bias, float* stat_partials,
                                int B, int Th, int V, int K, int N, int ld_in, int ld_out,
                                int T_in_full, int in_s, int in_o, int Th_in,
                                int T_out_full, int out_s, int out_o,
                                int taps, int tb, int tc, int accumulate, const float* bn_a, const unsigned char* bn_mask,
                                const float* bn_vec, const float* fin_vec, const float* fin_res, float* fin_out,
                                unsigned char* fin_mask, unsigned* in_amax, int half_mask, void* stream) {
+    if (int e = fgcn::check_conv_form("tconv_halo", w_form)) return e;
     FGCN_REQUIRE(half_mask == 0 || half_mask == 1 || half_mask == 3, FGCN_E_BADARG, "tconv_halo: half_mask=%d (0, 1 or 3)", half_mask);
-    return tconv_halo_impl(static_cast<const float*>(in), static_cast<float*>(out), w4, bias, stat_partials, B, Th, V, K, N, ld_in, ld_out, T_in_full,
+    return tconv_halo_impl(static_cast<const float*>(in), static_cast<float*>(out), w4, w_form, bias, stat_partials, B, Th, V, K, N, ld_in, ld_out, T_in_full,
                            in_s, in_o, Th_in, T_out_full, out_s, out_o, taps, tb, tc, accumulate, bn_a, bn_mask, bn_vec, fin_vec, fin_res, fin_out,
                            fin_mask, in_amax, stream, half_mask, nullptr, nullptr, nullptr);
 }
@@ -1058,6 +1060,9 @@ extern "C" int fgcn_tconv_halo_bn_relu(const float* in, float* out, const float*
                                        const float* res, const float* res_vec, int B, int T, int V, int K, int N, int ld_in, int ld_out,
                                        int taps, int tb, int tc, void* stream) {
     FGCN_REQUIRE(bn_vec, FGCN_E_BADARG, "tconv_halo_bn_relu: the BatchNorm vector is required");
-    return tconv_halo_impl(in, out, w4, bias, nullptr, B, T, V, K, N, ld_in, ld_out, T, 1, 0, T, T, 1, 0, taps, tb, tc, 0, nullptr, nullptr, nullptr,
+    // a mode-level refusal: w4 is taken as the fgcn_pack_split3 form, which the split modes other than "f16x2" keep
+    FGCN_REQUIRE((fgcn::math_mode() == FGCN_MATH_BF16X3 || fgcn::math_mode() == FGCN_MATH_BF16) && !fgcn::f16x2_mode(), FGCN_E_BADARG,
+                 "tconv_halo_bn_relu: the inference output stage needs the split kernel (bf16x3 products or bf16)");
+    return tconv_halo_impl(in, out, w4, FGCN_PACK_SPLIT3, bias, nullptr, B, T, V, K, N, ld_in, ld_out, T, 1, 0, T, T, 1, 0, taps, tb, tc, 0, nullptr, nullptr, nullptr,
                            nullptr, nullptr, nullptr, nullptr, nullptr, stream, 0, bn_vec, res, res_vec);
 }

@@ -569,7 +569,7 @@ static int twgrad_launch(const float* a, const float* g, float* partial, int B, 
     p.chunk_mode = chunk_mode;
     p.win_rows = chunk_mode ? p.stage_rows : p.stage_rows + (nacc - 1) * V;
     p.a_bytes = (unsigned)a_bytes; p.g_bytes = (unsigned)g_bytes; p.p_bytes = (unsigned)p_bytes;
-    const bool two = x3 && fgcn::f16x2_products() && a_amax && g_amax;     // both maxima known: the f16x2 form
+    const bool two = x3 && fgcn::math_mode() == FGCN_MATH_BF16X3 && a_amax && g_amax;     // both maxima given: the f16x2 form
     p.a_amax = two ? a_amax : nullptr;
     p.g_amax = two ? g_amax : nullptr;
     const int planes = chunk_mode ? nacc : 1;

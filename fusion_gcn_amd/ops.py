@@ -23,8 +23,9 @@ TMAP_POINTWISE = (1, 1, 0, 0, 1)
 
 
 MATH_MODES = {"f32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 2}     # FGCN_MATH_F32 / _BF16 / _BF16X3 (include/fgcn.h)
-# "f16x2" = FGCN_MATH_BF16X3 with FGCN_PRODUCTS_F16X2 in the convolution / 1x1 kernels: the weight forms built in this mode are
-# FGCN_PACK_SPLIT2H (``ScaledWeights``) and a kernel call takes the product form of the weights it is handed
+# "f16x2" = FGCN_MATH_BF16X3 with FGCN_PRODUCTS_F16X2: the weight forms built in this mode are FGCN_PACK_SPLIT2H (``ScaledWeights``).
+# A kernel call states the form of the weights it is handed (`w_form`, set where the wrapper validates them); nothing but
+# ``set_math_mode`` writes a context's settings
 X3_MODES = ("bf16x3", "f16x2")        # float32-accurate split modes (every kernel outside the conv / 1x1 family is bf16x3 in both)
 
 
@@ -40,7 +41,6 @@ class Context:
 
     def __init__(self, handle: Optional[int], paths: Optional[PathOptions] = None):
         self.handle = handle            # None: the process-wide defaults
-        self.f16x2 = False              # the math mode's product form ("f16x2" = FGCN_MATH_BF16X3 + two-way f16 products)
         self._paths = paths             # None: the process defaults (dataclass defaults + FGCN_PATHS), made on first use
 
     @property
@@ -96,7 +96,6 @@ def context(mode: Optional[str] = None):
     handle = ctypes.c_void_p()
     check(_lib.load().fgcn_ctx_create(ctypes.byref(handle)), "fgcn_ctx_create")
     ctx = Context(handle.value, current_context().paths.copy())
-    ctx.f16x2 = current_context().f16x2
     with use_context(ctx):
         if mode is not None:
             set_math_mode(mode)
@@ -143,7 +142,6 @@ def set_math_mode(mode: str) -> None:
     if mode not in MATH_MODES:
         raise _lib.FgcnError(f"unknown math mode {mode!r} (f32 | bf16 | bf16x3 | f16x2)")
     check(_lib.load().fgcn_set_math_mode(MATH_MODES[mode]), "fgcn_set_math_mode")
-    current_context().f16x2 = mode == "f16x2"
     check(_lib.load().fgcn_set_products(int(mode == "f16x2")), "fgcn_set_products")
 
 
@@ -153,13 +151,14 @@ def paths() -> PathOptions:
 
 
 def get_math_mode() -> str:
-    m = _lib.load().fgcn_get_math_mode()
-    return "f16x2" if (m == 2 and current_context().f16x2) else {0: "f32", 1: "bf16", 2: "bf16x3"}[m]
+    lib = _lib.load()
+    m = lib.fgcn_get_math_mode()
+    return "f16x2" if (m == 2 and lib.fgcn_get_products() == 1) else {0: "f32", 1: "bf16", 2: "bf16x3"}[m]
 
 
 class ScaledWeights:
     """A FGCN_PACK_SPLIT2H form (include/fgcn.h): one device buffer = 16-byte header (float bits of max |W|) + the two f16 parts of
-    W * 2^s in the fragment order of the split kernels; what ``tconv_halo`` / ``pw_gemm`` stream with FGCN_PRODUCTS_F16X2."""
+    W * 2^s in the fragment order of the split kernels; what ``tconv_halo`` / ``pw_gemm`` stream for the f16x2 products."""
 
     def __init__(self, taps: int, K: int, N: int, device, acc_order: bool = False):
         self.taps, self.K, self.N, self.acc_order = taps, K, N, acc_order
@@ -177,19 +176,6 @@ class ScaledWeights:
     def parts(self) -> torch.Tensor:
         """(2, taps, K/8, N, 8) float16 view of the two parts (tests)."""
         return self.buf[16:].view(torch.float16).view(2, self.taps, self.kgroups, self.N, 8)
-
-
-def _mode_products() -> None:
-    """The product form of the current math mode (f16x2: two-way f16 splits) -- for entry points that take no weight form of their
-    own to read it from, and after a wrapper that switched the form for one call (the library's product form is process-global)."""
-    if _lib.load().fgcn_get_math_mode() == 2:
-        check(_lib.load().fgcn_set_products(int(current_context().f16x2)), "fgcn_set_products")
-
-
-def _use_products_of(w) -> None:
-    """The conv / 1x1 kernels take the product form of the weights they are handed (in math mode bf16x3)."""
-    if _lib.load().fgcn_get_math_mode() == 2:
-        check(_lib.load().fgcn_set_products(int(isinstance(w, ScaledWeights))), "fgcn_set_products")
 
 
 def pack_split2h(w: torch.Tensor) -> ScaledWeights:
@@ -395,15 +381,14 @@ def tconv_halo(inp: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, *, Th: in
     if isinstance(w4, ScaledWeights):
         if not split:
             raise _lib.FgcnError("tconv_halo: FGCN_PACK_SPLIT2H weights need math mode bf16x3 / f16x2")
-        w_taps, K, N = w4.taps, w4.K, w4.N
+        w_taps, K, N, w_form = w4.taps, w4.K, w4.N, "split2h_acc" if w4.acc_order else "split2h"      # (the library refuses the _acc order)
     elif split:
         if w4.dtype != torch.bfloat16 or w4.dim() != 5 or w4.shape[0] != 3 or w4.shape[4] != 8 or not w4.is_contiguous():
             raise _lib.FgcnError(f"tconv_halo: math mode {get_math_mode()} takes pack_split3 weights, got {w4.dtype} {tuple(w4.shape)}")
-        w_taps, K, N = w4.shape[1], w4.shape[2] * 8, w4.shape[3]
+        w_taps, K, N, w_form = w4.shape[1], w4.shape[2] * 8, w4.shape[3], "split3"
     else:
         _chk(w4, "tconv_halo.w4")
-        w_taps, K, N = w4.shape[0], w4.shape[1] * 4, w4.shape[2]
-    _use_products_of(w4)
+        w_taps, K, N, w_form = w4.shape[0], w4.shape[1] * 4, w4.shape[2], "k4"
     if (Bo, Vo) != (B, V) or w_taps != taps or (not split and w4.shape[3] != 4) or K > ld_in or N > ld_out:
         raise _lib.FgcnError(f"tconv_halo: shape mismatch in={tuple(inp.shape)} out={tuple(out.shape)} weights (taps, K, N) = {(w_taps, K, N)}")
     in_s, in_o, Th_in = in_view if in_view is not None else (1, 0, T_in)
@@ -428,7 +413,7 @@ def tconv_halo(inp: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, *, Th: in
             raise _lib.FgcnError("tconv_halo: fuse_in needs the (4, K) BatchNorm vector, a shortcut and an output like the input "
                                  "(contiguous, K channels) and the uint8 sign image of numel / 8 bytes")
         fin = (_p(vec), _p(res), _p(g), g_sign.data_ptr())
-    check(lib.fgcn_tconv_halo(_p(inp), _p(out), w4.data_ptr(), _p(bias), _p(part), B, Th, V, K, N, ld_in, ld_out,
+    check(lib.fgcn_tconv_halo(_p(inp), _p(out), w4.data_ptr(), _lib.PACK_MODES[w_form], _p(bias), _p(part), B, Th, V, K, N, ld_in, ld_out,
                               T_in, in_s, in_o, Th_in, T_out, out_s, out_o, taps, tb, tc, int(accumulate), *bn, *fin,
                               _p(amax_out), _half_mask(in16, out16), _stream()), "fgcn_tconv_halo")
     return part
@@ -458,7 +443,6 @@ def tconv_halo_bn_relu(inp: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, *
             raise _lib.FgcnError(f"tconv_halo_bn_relu: the shortcut {tuple(res.shape)} must be laid out like the output {tuple(out.shape)}")
     if res_vec is not None and (res is None or tuple(res_vec.shape) != (4, N)):
         raise _lib.FgcnError("tconv_halo_bn_relu: res_vec is the (4, N) BatchNorm vector of a given shortcut")
-    _mode_products()
     check(_lib.load().fgcn_tconv_halo_bn_relu(_p(inp), _p(out), w4.data_ptr(), _p(bias), _p(vec), _p(res), _p(res_vec), B, T, V, K, N, ld_in,
                                               out.shape[3], taps, tb, tc, _stream()), "fgcn_tconv_halo_bn_relu")
     return out
@@ -483,7 +467,6 @@ def spatial_fwd_tile_bn_relu(x: torch.Tensor, a_hat: torch.Tensor, w3: torch.Ten
     if res_vec is not None and (res is None or tuple(res_vec.shape) != (4, Cout)):
         raise _lib.FgcnError("spatial_fwd_tile_bn_relu: res_vec is the (4, Cout) BatchNorm vector of a given shortcut")
     g = torch.empty((B, T, V, Cout), device=x.device, dtype=torch.float32)
-    _mode_products()
     check(_lib.load().fgcn_spatial_fwd_tile_bn_relu(_p(x), _p(a_hat), w3.data_ptr(), _p(bias), _p(g), _p(vec), _p(res), ld_res, _p(res_vec),
                                                     B, T, V, Cin, Cout, ld_x, Cout, int(a_hat.shape[0] == B), _stream()),
           "fgcn_spatial_fwd_tile_bn_relu")
@@ -507,19 +490,18 @@ def pw_gemm(inp: torch.Tensor, w3, out: torch.Tensor, *, bias: Optional[torch.Te
     if isinstance(w3, ScaledWeights):
         if w3.taps != 1:
             raise _lib.FgcnError("pw_gemm: a one-tap FGCN_PACK_SPLIT2H form expected")
-        K, N = w3.K, w3.N
+        K, N, w_form = w3.K, w3.N, "split2h_acc" if w3.acc_order else "split2h"
     elif w3.dtype != torch.bfloat16 or w3.dim() != 5 or w3.shape[0] != 3 or w3.shape[1] != 1 or w3.shape[4] != 8 or not w3.is_contiguous():
         raise _lib.FgcnError(f"pw_gemm: pack_split3 weights of a (1, K, N) matrix expected, got {w3.dtype} {tuple(w3.shape)}")
     else:
-        K, N = w3.shape[2] * 8, w3.shape[3]
-    _use_products_of(w3)
+        K, N, w_form = w3.shape[2] * 8, w3.shape[3], "split3"
     ld_in, ld_out = inp.shape[-1], out.shape[-1]
     rows = inp.numel() // ld_in
     if out.numel() // ld_out != rows or K > ld_in or N > ld_out:
         raise _lib.FgcnError(f"pw_gemm: shape mismatch in={tuple(inp.shape)} out={tuple(out.shape)} weights (K, N) = {(K, N)}")
     lib = _lib.load()
     part = torch.empty((lib.fgcn_pw_gemm_tiles(rows), 2, N), device=inp.device, dtype=torch.float32) if stats else None
-    check(lib.fgcn_pw_gemm(_p(inp), _p(out), w3.data_ptr(), _p(bias), _p(part), rows, K, N, ld_in, ld_out, int(accumulate),
+    check(lib.fgcn_pw_gemm(_p(inp), _p(out), w3.data_ptr(), _lib.PACK_MODES[w_form], _p(bias), _p(part), rows, K, N, ld_in, ld_out, int(accumulate),
                            _p(amax_out), _half_mask(in16, out16), _stream()), "fgcn_pw_gemm")
     return part
 
@@ -622,8 +604,8 @@ def rows_wgrad(a: torch.Tensor, g: torch.Tensor, *, K: int, N: int, tmap=TMAP_PO
     """(taps, K, N) weight gradient: sum over rows of a[src(row, tap), k] * g[row, n].  1x1 convolutions with K a multiple
     of 32 take the multi-accumulator kernel (``wide``; False forces the generic per-tap kernel).  ``conv_param`` returns
     the gradient in the convolution parameter's own layout (see ``_reduce_slabs``).  ``amax = (slot of a, slot of g)``: the
-    one-element int32 tensors in which ``tconv_halo`` / ``pw_gemm`` left the operands' largest magnitudes (math mode f16x2: the
-    split kernel then forms its products from two-way f16 splits; without them it runs bf16x3)."""
+    one-element int32 tensors in which ``tconv_halo`` / ``pw_gemm`` left the operands' largest magnitudes (the split modes bf16x3 /
+    f16x2: with both given the split kernel forms its products from two-way f16 splits; without them it runs bf16x3)."""
     ensure_device()
     a16, g16 = _chka(a, "rows_wgrad.a"), _chka(g, "rows_wgrad.g")      # math mode bf16: both bfloat16 (half_mask 3 of fgcn_pw_wgrad: the 1x1 form, K % 32 == 0)
     if a16 != g16 or (a16 and (a_coff or g_coff or amax is not None)):
@@ -650,11 +632,8 @@ def rows_wgrad(a: torch.Tensor, g: torch.Tensor, *, K: int, N: int, tmap=TMAP_PO
         slabs = lib.fgcn_pw_wgrad_slabs(N, nsplit)
         partial = torch.empty((slabs, K, N), device=a.device, dtype=torch.float32)
         am = (None, None) if amax is None or a_coff or g_coff else (amax[0].data_ptr(), amax[1].data_ptr())
-        if am[0] is not None and lib.fgcn_get_math_mode() == 2:
-            check(lib.fgcn_set_products(1), "fgcn_set_products")   # (operand scales given: the f16x2 form of the split kernel)
         check(lib.fgcn_pw_wgrad(_p(a, a_coff), _p(g, g_coff), _p(partial), B, T_g, V, K, N, ld_a, ld_g, T_a, ta, 0,
                                 nsplit, *am, _half_mask(a16, g16), _stream()), "fgcn_pw_wgrad")
-        _mode_products()
         return _reduce_slabs(partial.view(slabs, 1, K, N), 1, K, N, out, accumulate, conv_param)
     if a16:
         raise _lib.FgcnError("rows_wgrad: bfloat16 operands take the 1x1 multi-accumulator form only (K % 32 == 0, one tap)")
@@ -715,11 +694,8 @@ def tconv_wgrad(a: torch.Tensor, g: torch.Tensor, *, taps: int, stride: int = 1,
     am = (None, None) if amax is None else (amax[0].data_ptr(), amax[1].data_ptr())      # (bfloat16 operands: refused with amax above)
     for par, tap0, ntaps, shift0 in calls:
         th_a = (T_a - par + stride - 1) // stride
-        if am[0] is not None and lib.fgcn_get_math_mode() == 2:
-            check(lib.fgcn_set_products(1), "fgcn_set_products")   # (operand scales given: the f16x2 form of the split kernel)
         check(lib.fgcn_tconv_wgrad(_p(a), _p(g), _p(partial), B, T_g, V, K, N, K, N, T_a, stride, par, th_a,
                                    ntaps, shift0, tap0, stride, taps, nsplit, *am, _half_mask(in16, in16), _stream()), "fgcn_tconv_wgrad")
-    _mode_products()
     return _reduce_slabs(partial, taps, K, N, out, accumulate, conv_param)
 
 
@@ -1446,29 +1422,28 @@ def spatial_fwd(x: torch.Tensor, a_hat: torch.Tensor, wd: torch.Tensor, bias_sum
     B, T, V, ld_x = x.shape
     ns = a_hat.shape[1]
     if isinstance(wd, ScaledWeights):                      # FGCN_PACK_SPLIT2H_ACC: the f16x2 form of the kernel
+        w_form = "split2h_acc"
         w_ok = get_math_mode() in X3_MODES and Cin % 32 == 0 and wd.acc_order and (wd.taps, wd.K, wd.N) == (1, ns * Cin, Cout)
     elif get_math_mode() in X3_MODES and Cin % 32 == 0:    # weights in the pack_spatial split form
+        w_form = "split3_acc"
         w_ok = wd.dtype == torch.bfloat16 and tuple(wd.shape) == (3, 1, ns * Cin // 8, Cout, 8) and wd.is_contiguous()
     else:
+        w_form = "k4"
         w_ok = wd.dtype == torch.float32 and tuple(wd.shape) == (ns * Cin // 4, Cout, 4) and wd.is_contiguous()
     if not w_ok or a_hat.shape[0] not in (1, B) or a_hat.shape[2:] != (V, V):
         raise _lib.FgcnError(f"spatial_fwd: shape mismatch x={tuple(x.shape)} a_hat={tuple(a_hat.shape)} "
                              f"(math mode {get_math_mode()}: weights from pack_spatial)")
-    _use_products_of(wd)
     lib = _lib.load()
     y = torch.empty((B, T, V, Cout), device=x.device, dtype=torch.float32)
     part = torch.empty((lib.fgcn_spatial_tiles(B, T), 2, Cout), device=x.device, dtype=torch.float32) if stats else None
-    check(lib.fgcn_spatial_fwd(_p(x), _p(a_hat), wd.data_ptr(), _p(bias_sum), _p(y), _p(part), B, T, V, Cin, Cout, ld_x, Cout, ns,
+    check(lib.fgcn_spatial_fwd(_p(x), _p(a_hat), wd.data_ptr(), _lib.PACK_MODES[w_form], _p(bias_sum), _p(y), _p(part), B, T, V, Cin, Cout, ld_x, Cout, ns,
                                int(a_hat.shape[0] == B), _stream()), "fgcn_spatial_fwd")
     return y, part
 
 
 def spatial_fwd_tile_available(V: int, Cin: int, Cout: int) -> bool:
-    """Whether ``spatial_fwd_tile`` runs these sizes in the current math mode (bf16x3 products or bf16, Cin % 64 == 0, 16 <= V <= 32).  A pure
-    query: the answer is formed from the MODE's product form, whatever form the last kernel call of this context left selected."""
-    if current_context().f16x2:
-        return False
-    return _lib.load().fgcn_get_math_mode() in (1, 2) and 16 <= V <= 32 and Cin % 64 == 0 and Cout % 4 == 0 and Cin > 0
+    """Whether ``spatial_fwd_tile`` runs these sizes in the current math mode (bf16x3 products or bf16, Cin % 64 == 0, 16 <= V <= 32)."""
+    return Cin > 0 and bool(_lib.load().fgcn_spatial_fwd_tile_available(V, Cin, Cout))
 
 
 def spatial_fwd_tile(x: torch.Tensor, a_hat: torch.Tensor, w3: torch.Tensor, bias_sum: Optional[torch.Tensor], *, Cin: int,
@@ -1487,7 +1462,6 @@ def spatial_fwd_tile(x: torch.Tensor, a_hat: torch.Tensor, w3: torch.Tensor, bia
         raise _lib.FgcnError(f"spatial_fwd_tile: shape mismatch x={tuple(x.shape)} a_hat={tuple(a_hat.shape)} w3={tuple(w3.shape)} "
                              "(weights: pack_split3 of the (1, 3 Cin, Cout) matrix)")
     lib = _lib.load()
-    _mode_products()
     y = torch.empty((B, T, V, Cout), device=x.device, dtype=torch.bfloat16 if y_bf16 else torch.float32)
     part = torch.empty((lib.fgcn_spatial_fwd_tile_tiles(B, T, V), 2, Cout), device=x.device, dtype=torch.float32) if stats else None
     check(lib.fgcn_spatial_fwd_tile(_p(x), _p(a_hat), w3.data_ptr(), _p(bias_sum), _p(y), _p(part), B, T, V, Cin, Cout, ld_x, Cout,
@@ -1542,7 +1516,6 @@ def spatial_bwd_tile(dy: torch.Tensor, x: torch.Tensor, a_hat: torch.Tensor, w3:
         raise _lib.FgcnError(f"spatial_bwd_tile: shape mismatch dy={tuple(dy.shape)} x={tuple(x.shape)} a_hat={tuple(a_hat.shape)} "
                              f"dx={tuple(dx.shape)} w3={tuple(w3.shape)} (weights: pack_split3 of the (1, Cout, 3 Cin) matrix)")
     lib = _lib.load()
-    _mode_products()
     nseg = lib.fgcn_spatial_bwd_tile_segments(B, T, V)
     partial = torch.empty((B, max(nseg, 1), 3, 32, 32), device=x.device, dtype=torch.float32)
     check(lib.fgcn_spatial_bwd_tile(_p(dy), _p(x), _p(a_hat), w3.data_ptr(), _p(dx), _p(partial), B, T, V, Cin, Cout, Cout, Cin,

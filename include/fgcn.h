@@ -73,11 +73,14 @@ int fgcn_check_device(void);
  * The earlier NaN rules stand beside these: fgcn_tmaxpool3_fwd (a NaN tap wins), fgcn_classify_update and the fused scores' ranking (NaN sorts
  * above every number), fgcn_signal_prepare's min / max (a NaN in the array makes every output NaN). */
 
-/* Contexts: where the settings live that the launchers read on the host at call time -- the math mode, the product form and the
- * kernel-variant table below.  Every thread has a CURRENT context; a thread that never made one current reads (and, through the
+/* Contexts: where the settings live that the launchers read on the host at call time -- the math mode, the product form that belongs to
+ * it and the kernel-variant table below.  Every thread has a CURRENT context; a thread that never made one current reads (and, through the
  * setters below, writes) the process-wide defaults.  fgcn_ctx_create copies the calling thread's current settings into a new
  * context; fgcn_ctx_set_current(ctx) makes it current for the CALLING THREAD ONLY (NULL: back to the process-wide defaults);
- * fgcn_set_math_mode / fgcn_set_products / fgcn_set_tuning then change that context and nothing else.  Two threads with two contexts
+ * fgcn_set_math_mode / fgcn_set_products / fgcn_set_tuning then change that context and nothing else.  NO KERNEL ENTRY POINT MODIFIES A
+ * CONTEXT: the setters are the only writers, so what fgcn_get_math_mode / fgcn_get_products / fgcn_get_tuning return is the same before
+ * and after any launch (tests/test_weight_form_gpu.py), and nothing a launcher needs to know about one of its ARGUMENTS is read from
+ * here -- the layout of a weight argument is stated by the caller (w_form, below).  Two threads with two contexts
  * -- two models in two math modes on two streams -- therefore never see each other's settings (tests/test_context_gpu.py).  A caller
  * whose work continues on another thread (an autograd backward) makes the same context current there for the duration of its calls:
  * fusion_gcn_amd.ops.context_bound does that for every autograd Function of the host.  A context must not be destroyed while it is
@@ -105,8 +108,8 @@ fgcn_ctx* fgcn_ctx_get_current(void);
  *      512: fgcn_spatial_wgrad on exact-f32 MFMAs in math mode bf16x3 (default there: the split-bf16 form)
  *      1024: joint_dagg with its subset count / accumulate flag as run-time values (the form before the end of round 3); 2048: both at compile time,
  *      three workgroups per CU, one tile register set (default: one set per subset refilled a chunk ahead, two workgroups per CU)
- *   7  split-bf16 kernels (bits) 1: spatial forward, one frame per wave (older form; bf16x3 products only -- it has no f16x2 form, and
- *      with FGCN_PRODUCTS_F16X2 the bit selects nothing); 8: split-bf16 halo conv as 2 x 2 waves over 128-row tiles at every width (default:
+ *   7  split-bf16 kernels (bits) 1: spatial forward, one frame per wave (older form; FGCN_PACK_SPLIT3_ACC weights only -- it has no f16x2
+ *      form, and for FGCN_PACK_SPLIT2H_ACC weights the bit selects nothing); 8: split-bf16 halo conv as 2 x 2 waves over 128-row tiles at every width (default:
  *      4 x 1 waves over 192-row tiles up to 128 columns, see 64); 16: the 4 x 1 form with a 128-column tile for every N > 64 (default: 64 < N <= 128 only), and in
  *      FGCN_MATH_BF16 the 4 x 1 forms at all (default there: 2 x 2); 32: never the 128-column 4 x 1 form; 64: the 4 x 1 forms whatever the
  *      tile count (default: from 1536 192-row tiles on; tests)
@@ -150,15 +153,32 @@ int fgcn_get_tuning(int key);
 #define FGCN_MATH_BF16X3 2
 int fgcn_set_math_mode(int mode);
 int fgcn_get_math_mode(void);
-/* Product form of the convolution / 1x1 kernels inside FGCN_MATH_BF16X3 (every other kernel is unaffected):
+/* Product form: the second half of the math-mode setting inside FGCN_MATH_BF16X3 (FGCN_MATH_BF16X3 + FGCN_PRODUCTS_F16X2 is the mode
+ * the host calls "f16x2").  It is a MODE-LEVEL setting: it says which weight forms the owner of the model keeps (FGCN_PACK_SPLIT2H[_ACC]
+ * instead of FGCN_PACK_SPLIT3[_ACC]) and is read by mode-level decisions only -- fgcn_spatial_fwd_tile_available, and
+ * fgcn_tconv_halo_bn_relu / fgcn_spatial_fwd_tile_bn_relu, which take fgcn_pack_split3 forms and refuse with FGCN_PRODUCTS_F16X2 selected.
+ * No launcher derives the layout of a weight argument from it.
+ *
+ * THE FORM OF A WEIGHT ARGUMENT IS STATED BY THE CALLER.  The entry points that accept weights in more than one layout --
+ * fgcn_tconv_halo, fgcn_pw_gemm, fgcn_spatial_fwd -- take `int w_form`, a FGCN_PACK_* constant (below), as the argument DIRECTLY AFTER
+ * THE WEIGHT POINTER.  It is checked against the math mode (and, for fgcn_spatial_fwd, Cin) before anything else; a pair outside this
+ * table is FGCN_E_BADARG with a message that names the form and the mode:
+ *     fgcn_tconv_halo, fgcn_pw_gemm    FGCN_MATH_F32                        FGCN_PACK_K4
+ *                                      FGCN_MATH_BF16                       FGCN_PACK_SPLIT3
+ *                                      FGCN_MATH_BF16X3                     FGCN_PACK_SPLIT3 or FGCN_PACK_SPLIT2H
+ *     fgcn_spatial_fwd                 FGCN_MATH_BF16X3 and Cin % 32 == 0   FGCN_PACK_SPLIT3_ACC or FGCN_PACK_SPLIT2H_ACC
+ *                                      anything else                        FGCN_PACK_K4
+ * (fgcn_pw_gemm runs in the split modes only: fgcn_pw_gemm_available.)  The byte bound of the weight buffer, the kernel instantiation and
+ * whether in_amax is recorded all follow w_form: a FGCN_PACK_SPLIT2H form runs the f16x2 products whatever fgcn_get_products says, a
+ * FGCN_PACK_SPLIT3 form the bf16x3 ones.  The weight gradients have no weight argument: they run their f16x2 form in FGCN_MATH_BF16X3
+ * when both operand scales are given (a_amax / g_amax, below).
  *   FGCN_PRODUCTS_BF16X3  six bf16 partial products from exact three-way bf16 splits (above);
  *   FGCN_PRODUCTS_F16X2   three f16 products from two-way f16 splits: x 2^s = h + l (11 + 11 significand bits + the sign of l: within
  *                         2^-24 |x| while l is a normal f16), l.l dropped (<= 2^-24 |a.b|) -- half the matrix work at float32-class
  *                         accuracy.  f16 has 5 exponent bits, so every operand BLOCK is scaled by an exact power of two that puts its
  *                         largest magnitude into [2^14, 2^15): activations per staged (row tile, channel chunk) inside the kernels
  *                         (the accumulator carries the scale, only ever towards larger magnitudes), weights per packed form
- *                         (FGCN_PACK_SPLIT2H).  Error model per operand element: max(2^-24 |x|, 2^-40 * block maximum).  Weights must
- *                         then be FGCN_PACK_SPLIT2H forms. */
+ *                         (FGCN_PACK_SPLIT2H).  Error model per operand element: max(2^-24 |x|, 2^-40 * block maximum). */
 #define FGCN_PRODUCTS_BF16X3 0
 #define FGCN_PRODUCTS_F16X2 1
 int fgcn_set_products(int products);
@@ -275,14 +295,15 @@ int fgcn_tconv_halo_bn_sums(void);
  * shortcut x, laid out like `in`), formed as the rows are staged; G (fin_out, like `in`) and its sign image (fin_mask, fgcn_bn_act's
  * layout, rows*K/8 bytes) are written once as by-products (the backward's weight gradient and ReLU gate read them): what an
  * fgcn_bn_act(res_mode = 1, relu = 1) pass in front of this call computes, without that pass. */
-int fgcn_tconv_halo(const void* in, void* out, const float* w4, const float* bias, float* stat_partials,
+int fgcn_tconv_halo(const void* in, void* out, const float* w4, int w_form, const float* bias, float* stat_partials,
                     int B, int Th, int V, int K, int N, int ld_in, int ld_out,
                     int T_in_full, int in_s, int in_o, int Th_in,
                     int T_out_full, int out_s, int out_o,
                     int taps, int tb, int tc, int accumulate, const float* bn_a, const unsigned char* bn_mask,
                     const float* bn_vec, const float* fin_vec, const float* fin_res, float* fin_out, unsigned char* fin_mask,
                     unsigned* in_amax, int half_mask, void* stream);
-/* in_amax (may be NULL; FGCN_PRODUCTS_F16X2 only): a device word that receives, by integer atomic maximum (order-independent), the
+/* w_form: the layout of w4 ("Product form" above: FGCN_PACK_K4, FGCN_PACK_SPLIT3 or FGCN_PACK_SPLIT2H).
+ * in_amax (may be NULL; written with FGCN_PACK_SPLIT2H weights only): a device word that receives, by integer atomic maximum (order-independent), the
  * float bits of max |in| over everything this call stages -- zero it before the first call that should count; the weight gradient of
  * the same tensor takes it as its operand scale (fgcn_tconv_wgrad). */
 
@@ -321,8 +342,8 @@ int fgcn_pw_wgrad(const void* a, const void* g, float* partial, int B, int T_g, 
                   int ld_a, int ld_g, int T_a_full, int a_s, int a_o, int nsplit,
                   const unsigned* a_amax, const unsigned* g_amax, int half_mask, void* stream);
 /* a_amax / g_amax (both weight-gradient entry points; may be NULL): device words holding the float bits of max |a| / max |g| over
- * the whole tensors, as fgcn_tconv_halo / fgcn_pw_gemm leave them in `in_amax`.  With both given and FGCN_PRODUCTS_F16X2 selected the
- * split kernel runs its f16x2 form (operands scaled by the exact powers of two that put those maxima into [2^14, 2^15)); without
+ * the whole tensors, as fgcn_tconv_halo / fgcn_pw_gemm leave them in `in_amax`.  With both given in FGCN_MATH_BF16X3 (whatever the
+ * product form of the context: the call states its form by what it passes) the split kernel runs its f16x2 form (operands scaled by the exact powers of two that put those maxima into [2^14, 2^15)); without
  * them it runs the bf16x3 form.  A bfloat16 operand pair (half_mask 3) takes neither: FGCN_E_BADARG. */
 
 /* dst[i] (+)= sum_s src[s*count + i]   (deterministic tree-free column sum; also bias / adj_b gradients) */
@@ -378,7 +399,7 @@ int fgcn_pack_split3(unsigned short* dst, const float* src, int taps, int K, int
  *                         exponent of that maximum (scaled maximum in [2^14, 2^15); s = 0 for an all-zero form).  Needs
  *                         fgcn_pack_run_scaled (the maximum is a pass of its own). */
 #define FGCN_PACK_SPLIT2H 4
-/*   FGCN_PACK_SPLIT2H_ACC the same with the k order of FGCN_PACK_SPLIT3_ACC (fgcn_spatial_fwd's weights with FGCN_PRODUCTS_F16X2) */
+/*   FGCN_PACK_SPLIT2H_ACC the same with the k order of FGCN_PACK_SPLIT3_ACC (fgcn_spatial_fwd's weights for the f16x2 products) */
 #define FGCN_PACK_SPLIT2H_ACC 5
 typedef struct {
     const float* src;
@@ -597,10 +618,12 @@ int fgcn_col_sum(const float* x, float* partials, long long rows, int C, int ld,
 /* y[(n,t,w), o] = sum_k bd_k[o] + sum_c Wd_k[o][c] * sum_v x[(n,t,v), c] * a_hat[n][k][v][w]
  *   = conv_d[k](x . A^_k) summed over the K subsets (agcn.py:103-111) in ONE kernel: A^ staged in LDS, the joint
  *   aggregation and the Cin x Cout contraction chained on MFMA without materialising agg.
- *   wd: k-interleaved packed float[K*Cin/4][Cout][4] with wd[(k*Cin+c)/4][o][(k*Cin+c)%4] = Wd_k[o][c] (Cin % 4 == 0);
+ *   wd: k-interleaved packed float[K*Cin/4][Cout][4] with wd[(k*Cin+c)/4][o][(k*Cin+c)%4] = Wd_k[o][c] (Cin % 4 == 0; FGCN_PACK_K4), or in
+ *   FGCN_MATH_BF16X3 with Cin % 32 == 0 the accumulator-ordered split of the same matrix (FGCN_PACK_SPLIT3_ACC / FGCN_PACK_SPLIT2H_ACC);
+ *   w_form says which ("Product form" above);
  *   bias_sum: float[Cout] (= sum_k bd_k) or NULL.
  *   stat_partials: float[fgcn_spatial_tiles(B,T)][2][Cout] or NULL. */
-int fgcn_spatial_fwd(const float* x, const float* a_hat, const float* wd, const float* bias_sum, float* y,
+int fgcn_spatial_fwd(const float* x, const float* a_hat, const float* wd, int w_form, const float* bias_sum, float* y,
                      float* stat_partials, int B, int T, int V, int Cin, int Cout, int ld_x, int ld_y,
                      int n_subsets, int a_hat_batched, void* stream);
 int fgcn_spatial_tiles(int B, int T);
@@ -864,9 +887,9 @@ int fgcn_unfold_windows(const float* in, float* out, int B, int T, int T_out, in
  * (K = 64..384) to hide their own staging latency and store tail.  fgcn_pw_gemm_available() = 1 in FGCN_MATH_BF16X3 / FGCN_MATH_BF16. */
 int fgcn_pw_gemm_available(void);
 int fgcn_pw_gemm_tiles(long long rows);
-int fgcn_pw_gemm(const void* in, void* out, const void* w3, const float* bias, float* stat_partials, long long rows,
+int fgcn_pw_gemm(const void* in, void* out, const void* w3, int w_form, const float* bias, float* stat_partials, long long rows,
                  int K, int N, int ld_in, int ld_out, int accumulate, unsigned* in_amax, int half_mask, void* stream);
-/* (w3: the FGCN_PACK_SPLIT2H form with FGCN_PRODUCTS_F16X2 selected; in_amax as for fgcn_tconv_halo) */
+/* (w_form: FGCN_PACK_SPLIT3, or in FGCN_MATH_BF16X3 FGCN_PACK_SPLIT2H -- "Product form" above; in_amax as for fgcn_tconv_halo) */
 
 /* ---- the two ends of the step: input BatchNorm and loss (fgcn_head.hip) ------------------------------------------------------
  * `data_bn` = nn.BatchNorm1d(M*V*C) over the network input x (N, M, T, V, C) viewed as (N, M*V*C, T)

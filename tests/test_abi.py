@@ -16,6 +16,9 @@ def lib():
     return _lib.load()
 
 
+K4, SPLIT3, SPLIT3_ACC, SPLIT2H, SPLIT2H_ACC = (_lib.PACK_MODES[k] for k in ("k4", "split3", "split3_acc", "split2h", "split2h_acc"))   # FGCN_PACK_*
+
+
 def _declared_symbols():
     text = open(os.path.join(ROOT, "include", "fgcn.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -56,8 +59,10 @@ def test_host_side_validation(lib):
     assert lib.fgcn_joint_mix(p16, p16, p16, 1, 1, 33, 4, 4, 4, 4, 1, 0, item, 1, 0, None) == -1
     assert b"bad B/T/V" in lib.fgcn_last_error()
     # spatial kernel: more than 256 channels
-    assert lib.fgcn_spatial_fwd(p16, p16, p16, None, p16, None, 1, 1, 25, 512, 64, 512, 64, 3, 1, None) == -1
-    assert lib.fgcn_spatial_fwd(p16, p16, p16, None, p16, None, 1, 1, 25, 3, 64, 4, 64, 3, 1, None) == -2   # Cin % 4
+    assert lib.fgcn_get_math_mode() == 0          # (conftest: this module runs in math mode f32, whose weight form is FGCN_PACK_K4)
+    assert lib.fgcn_spatial_fwd(p16, p16, p16, K4, None, p16, None, 1, 1, 25, 512, 64, 512, 64, 3, 1, None) == -1
+    assert b"at most 256 channels" in lib.fgcn_last_error()
+    assert lib.fgcn_spatial_fwd(p16, p16, p16, K4, None, p16, None, 1, 1, 25, 3, 64, 4, 64, 3, 1, None) == -2   # Cin % 4
     # the fused BatchNorm + activation without its input, its vector or its output (both entry points of the shared body)
     for args in ((None, p16, None, None, p16), (p16, None, None, None, p16), (p16, p16, None, None, None)):
         assert lib.fgcn_bn_act(*args, None, 16, 8, 0, 1, 0, None) == -1
@@ -72,10 +77,11 @@ def test_host_side_validation(lib):
     assert b"pivot" in lib.fgcn_last_error()
     assert lib.fgcn_bn_finalize(p16, 1, 10, p16, p16, None, None, 0.1, 1e-5, p16, 8, p16, 8, 4, None) == -1
     # half_mask (half-precision activation storage): a mask the kernel is not built for, and bfloat16 tensors outside math mode bf16
-    halo = (p16, p16, p16, None, None, 1, 4, 25, 32, 32, 32, 32, 4, 1, 0, 4, 4, 1, 0, 9, 1, -4)      # ... up to tc; then accumulate, 8 pointers
+    halo = (None, None, 1, 4, 25, 32, 32, 32, 32, 4, 1, 0, 4, 4, 1, 0, 9, 1, -4)      # bias ... up to tc; then accumulate, 8 pointers
     assert lib.fgcn_bn_act(p16, p16, None, None, p16, None, 16, 8, 0, 1, 8, None) == -1                  # bit 3 does not exist
     assert b"half_mask" in lib.fgcn_last_error()
-    assert lib.fgcn_tconv_halo(*halo, 0, *[None] * 8, 2, None) == -1   # out without in
+    assert lib.fgcn_tconv_halo(p16, p16, p16, K4, *halo, 0, *[None] * 8, 2, None) == -1   # out without in
+    assert b"half_mask" in lib.fgcn_last_error()
     assert lib.fgcn_spatial_bwd_tile(p16, p16, p16, p16, p16, p16, 1, 4, 25, 64, 64, 64, 64, 64, 1, 0, None, 0, None, None, None, 5, None) == -1
     assert lib.fgcn_emb_dx_tile(p16, p16, p16, p16, p16, 1, 4, 25, 16, 64, 96, 64, 1, 0, None, 2, None) == -1
     mode = lib.fgcn_get_math_mode()
@@ -95,7 +101,7 @@ def test_host_side_validation(lib):
             assert b"half_mask" in lib.fgcn_last_error()
             assert fn(*args, p16, None, 3, None) == -1 and fn(*args, None, p16, 3, None) == -1
         lib.fgcn_set_math_mode(1)          # bf16: the combinations the kernels are not built for are refused in the mode that takes bfloat16 tensors too
-        assert lib.fgcn_tconv_halo(*halo, 1, *[None] * 8, 3, None) == -1                              # a bfloat16 output, accumulating
+        assert lib.fgcn_tconv_halo(p16, p16, p16, SPLIT3, *halo, 1, *[None] * 8, 3, None) == -1       # a bfloat16 output, accumulating
         assert b"no accumulation" in lib.fgcn_last_error()
         assert lib.fgcn_bn_act_bwd_reduce(p16, 4, None, p16, p16, p16, None, None, p16, 1, 16, 8, 0, 1, 1, None) == -1   # a bfloat16 per-group dout
         assert b"float32 per-group gradient" in lib.fgcn_last_error()
@@ -106,6 +112,70 @@ def test_host_side_validation(lib):
         assert b"half_mask" in lib.fgcn_last_error()
     finally:
         lib.fgcn_set_math_mode(mode)
+
+
+def test_weight_form_is_checked_against_the_math_mode(lib):
+    """`w_form` of fgcn_tconv_halo / fgcn_pw_gemm / fgcn_spatial_fwd (include/fgcn.h, "Product form"): a value that is no FGCN_PACK_* form,
+    and every (math mode, form) pair outside the header's table, is FGCN_E_BADARG with a message that names the form and the mode.  The
+    check comes before every other: a refused form is reported where another argument is wrong too, and an accepted form with a null
+    input is refused for the pointer (so no call of this test reaches a launch).  The product form of the context plays no part: the
+    table is the same with FGCN_PRODUCTS_F16X2 selected."""
+    buf = (C.c_float * 64)()
+    p16 = (C.addressof(buf) + 15) // 16 * 16
+    names = {0: "FGCN_PACK_PLAIN", K4: "FGCN_PACK_K4", SPLIT3: "FGCN_PACK_SPLIT3", SPLIT3_ACC: "FGCN_PACK_SPLIT3_ACC", SPLIT2H: "FGCN_PACK_SPLIT2H",
+             SPLIT2H_ACC: "FGCN_PACK_SPLIT2H_ACC"}
+    modes = {0: "FGCN_MATH_F32", 1: "FGCN_MATH_BF16", 2: "FGCN_MATH_BF16X3"}
+    conv_ok = {0: {K4}, 1: {SPLIT3}, 2: {SPLIT3, SPLIT2H}}
+    B, T, V, K, N = 2, 8, 5, 32, 64
+
+    def halo(form):
+        return lib.fgcn_tconv_halo(p16, p16, p16, form, None, None, B, T, V, K, N, K, N, T, 1, 0, T, T, 1, 0, 1, 1, 0, 0, *[None] * 8, 0, None)
+
+    def pw(form):
+        return lib.fgcn_pw_gemm(p16, p16, p16, form, None, None, B * T * V, K, N, K, N, 0, None, 0, None)
+
+    def spatial(form, cin):
+        return lib.fgcn_spatial_fwd(p16, p16, p16, form, None, p16, None, B, T, V, cin, N, cin, N, 3, 0, None)
+
+    def refused(rc, form, mode):
+        err = lib.fgcn_last_error().decode()
+        assert rc == -1 and "w_form" in err and modes[mode] in err, (rc, err)
+        assert (names[form] if form in names else str(form)) in err, err
+
+    mode, products = lib.fgcn_get_math_mode(), lib.fgcn_get_products()
+    try:
+        for m in modes:
+            assert lib.fgcn_set_math_mode(m) == 0
+            for prod in (0, 1):
+                assert lib.fgcn_set_products(prod) == 0
+                for form in (-1, 0, K4, SPLIT3, SPLIT3_ACC, SPLIT2H, SPLIT2H_ACC, 6, 1000):
+                    if form not in conv_ok[m]:
+                        refused(halo(form), form, m)
+                        refused(pw(form), form, m)
+                    for cin in (32, 4):                        # whole 32-channel tiles (the split kernel in bf16x3), and not
+                        ok = {SPLIT3_ACC, SPLIT2H_ACC} if (m == 2 and cin % 32 == 0) else {K4}
+                        if form not in ok:
+                            refused(spatial(form, cin), form, m)
+                # the check comes first: a refused form is reported even where another argument is wrong too (a null input)
+                bad = SPLIT2H if m != 2 else K4
+                assert lib.fgcn_tconv_halo(None, p16, p16, bad, None, None, B, T, V, K, N, K, N, T, 1, 0, T, T, 1, 0, 1, 1, 0, 0, *[None] * 8, 0, None) == -1
+                assert "w_form" in lib.fgcn_last_error().decode()
+                assert lib.fgcn_pw_gemm(None, p16, p16, bad, None, None, B * T * V, K, N, K, N, 0, None, 0, None) == -1
+                assert "w_form" in lib.fgcn_last_error().decode()
+                assert lib.fgcn_spatial_fwd(None, p16, p16, SPLIT3, None, p16, None, B, T, V, 32, N, 32, N, 3, 0, None) == -1
+                assert "w_form" in lib.fgcn_last_error().decode()
+                # ... and an accepted form passes it: the same calls with a null input are refused for the pointer
+                good = sorted(conv_ok[m])[-1]
+                assert lib.fgcn_tconv_halo(None, p16, p16, good, None, None, B, T, V, K, N, K, N, T, 1, 0, T, T, 1, 0, 1, 1, 0, 0, *[None] * 8, 0, None) == -1
+                assert "null pointer" in lib.fgcn_last_error().decode()
+                assert lib.fgcn_pw_gemm(None, p16, p16, good, None, None, B * T * V, K, N, K, N, 0, None, 0, None) == -1
+                assert "null pointer" in lib.fgcn_last_error().decode()
+                for form in ((SPLIT3_ACC, SPLIT2H_ACC) if m == 2 else (K4,)):
+                    assert lib.fgcn_spatial_fwd(None, p16, p16, form, None, p16, None, B, T, V, 32, N, 32, N, 3, 0, None) == -1
+                    assert "null pointer" in lib.fgcn_last_error().decode()
+    finally:
+        lib.fgcn_set_math_mode(mode)
+        lib.fgcn_set_products(products)
 
 
 def test_tile_kernel_geometry_and_tuning_keys(lib):
