@@ -226,6 +226,9 @@ SIGNATURES = {
     "fgcn_clip_window": (_I, [_P] * 6 + [_I] * 5 + [_F, _F, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "fgcn_window_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, _F, _F, _I, C.POINTER(C.c_float)]),
     "fgcn_clip_valid_frames": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "fgcn_clip_sensors": (_I, [_P] * 7 + [_I] * 6 + [C.POINTER(C.c_float), _F, _F, _I, C.POINTER(C.c_float), _F, _I, C.c_ulonglong, C.c_uint,
+                               C.c_uint, _P]),
+    "fgcn_sensors_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, C.POINTER(C.c_float), _F, _F, _I, _F, _I, C.POINTER(C.c_float)]),
     "fgcn_score_fuse": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _I, _I, _P]),
     "fgcn_fuse_sweep": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
 }
@@ -241,6 +244,8 @@ NORMALIZE_MAX_T = 4096      # FGCN_NORMALIZE_MAX_T
 BODIES_MAX = 16             # FGCN_BODIES_MAX
 BODIES_MAX_T = 524288       # FGCN_BODIES_MAX_T
 WINDOW_MODES = {"random": 0, "centre": 1}              # enum fgcn_window_mode
+SENSORS_MAX = 16            # FGCN_SENSORS_MAX
+SENSORS_MAX_KNOTS = 8       # FGCN_SENSORS_MAX_KNOTS
 
 _lib = None
 

@@ -16,7 +16,8 @@
 namespace fgcn {
 
 // The table row of one sample: A (3 x 3, row-major) = s Rz Ry Rx, then o, r, 0.  The ONE definition: the kernel and fgcn_augment_params
-// both call it.  Every product below is written out and contraction is off, so the host and the device differ in sinf / cosf alone.
+// both call it.  Every product here and in clip_rotation is written out and contraction is off, so the host and the device differ in sinf /
+// cosf alone.
 // 2u - 1 is exact (a multiple of 2^-23 of magnitude <= 1); 1 - r is formed as (1 - u4) (1 - min_window), whose first factor is exact: o
 // keeps its relative accuracy when the window nearly fills the recording.  Zero magnitudes and min_window = 1 give the identity, 0 and 1.
 __host__ __device__ inline void augment_params(unsigned sample, unsigned site, unsigned epoch, unsigned k0, unsigned k1, float ax, float ay,
@@ -26,16 +27,7 @@ __host__ __device__ inline void augment_params(unsigned sample, unsigned site, u
     const float tx = (2.0f * clip_uniform(p0.w[0]) - 1.0f) * ax, ty = (2.0f * clip_uniform(p0.w[1]) - 1.0f) * ay,
                 tz = (2.0f * clip_uniform(p0.w[2]) - 1.0f) * az;
     const float s = 1.0f + (2.0f * clip_uniform(p0.w[3]) - 1.0f) * scale;
-    const float sx = sinf(tx), cx = cosf(tx), sy = sinf(ty), cy = cosf(ty), sz = sinf(tz), cz = cosf(tz);
-    out[0] = s * (cz * cy);
-    out[1] = s * (cz * sy * sx - sz * cx);
-    out[2] = s * (cz * sy * cx + sz * sx);
-    out[3] = s * (sz * cy);
-    out[4] = s * (sz * sy * sx + cz * cx);
-    out[5] = s * (sz * sy * cx - cz * sx);
-    out[6] = s * (-sy);
-    out[7] = s * (cy * sx);
-    out[8] = s * (cy * cx);
+    clip_rotation(tx, ty, tz, s, out);
     const float u4 = clip_uniform(p1.w[0]), u5 = clip_uniform(p1.w[1]), span = 1.0f - min_window;
     out[9] = u5 * ((1.0f - u4) * span);
     out[10] = min_window + u4 * span;

@@ -38,11 +38,15 @@ Preparation on the device: ``ClipBatches`` runs the stages it is given, in this 
   * ``augment=Augment(...)`` (ours; the reference has none): one ``fgcn_clip_augment`` call in place of the row gather of each modality --
     random rotation and scale of the joints, a random temporal window resampled to the clip's length -- whose random numbers are keyed
     by (seed, epoch, global sample index): section 8f;
+  * ``sensors=Sensors(...)`` (ours; the reference has none): one ``fgcn_clip_sensors`` call per inertial feature -- the (T, S) signal and
+    the sensor joints of an enhanced skeleton -- a random rotation of the sensor frame, a gain per sensor, a smooth magnitude warp, additive
+    jitter and the drop of a whole sensor, keyed like the augmentation and by (frame, sensor), then (``minmax=True``) the min-max
+    normalisation that ``Inertial(minmax=False)`` left out; behind ``augment``, whose resampling would smooth the jitter: section 8p;
   * ``streams=Streams(parents, ...)`` (the bone and motion inputs 2s-AGCN is trained on; the reference has none): one ``fgcn_clip_streams``
     call per skeleton feature -- joint minus parent joint, frame t+1 minus frame t inside the valid frames, and the motion of the bones,
     of the clip as the stages before left it: section 8j.
 The first three run once at upload on the resident path -- and so does the window of an evaluation split, which has no random part -- the
-training window, the augmentation and the streams on every batch; on the streaming path all run per batch, behind the copy.  The six
+training window, the two augmentations and the streams on every batch; on the streaming path all run per batch, behind the copy.  The seven
 classes live in stages.py and are imported here; what ``ClipBatches`` asks of a stage is the docstring of their base, ``stages.Stage``.
 """
 from __future__ import annotations
@@ -56,7 +60,7 @@ import torch
 
 from ._lib import FgcnError
 from .dp import shard_batch
-from .stages import Augment, Bodies, Inertial, Normalize, Stage, Streams, Window      # noqa: F401 (`from .data import Window` still works)
+from .stages import Augment, Bodies, Inertial, Normalize, Sensors, Stage, Streams, Window      # noqa: F401 (`from .data import Window` still works)
 
 HEADER_BYTES = 128      # data_writer.py:19: np.memmap(out_path, dtype, "w+", 128, shape)
 
@@ -238,13 +242,18 @@ class ClipBatches:
     the third stage, behind ``inertial`` and in front of ``augment``: every clip of the modalities it names comes out as a part of its valid
     frames resized to the window's W frames -- ``shapes`` then holds W, and the model is built from ``shapes``; with ``train=False`` a
     resident split is windowed once, at construction (``dev_feat`` holds W frames); ``last_window`` (feature id -> (clips, 2) tensor)
-    keeps the ``(o, r)`` table of the last call.  None, the default: no such stage, and every call issued is what it was."""
+    keeps the ``(o, r)`` table of the last call.  ``sensors``: a ``Sensors`` = the stage behind ``augment`` and in front of ``streams``, on
+    every batch: the sensors of the (T, S) signals and -- with ``Sensors(joints=...)`` -- the sensor joints of the (M, T, V, 3) arrays it
+    applies to come out rotated, scaled, warped, jittered and dropped, a pure function of (``seed``, the epoch, the clip's index in the
+    data set) as the augmentation is, every body and both arrays of a sample with the same values; ``last_sensors`` (feature id ->
+    ((clips, 12 + 12 G) parameter table, (clips, 2) minimum / maximum table)) keeps the tables of the last batch.  None, the default: no such
+    stage, and every call issued is what it was."""
 
     def __init__(self, dataset: MultiModalDataset, batch_size: int, *, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 1, rank: int = 0, world: int = 1, device: Union[str, torch.device] = "cuda",
                  resident: Optional[bool] = None, resident_budget: int = 64 << 30, augment: Optional[Augment] = None,
                  normalize: Optional[Normalize] = None, inertial: Optional[Inertial] = None, streams: Optional[Streams] = None,
-                 window: Optional[Window] = None, bodies: Optional[Bodies] = None):
+                 window: Optional[Window] = None, bodies: Optional[Bodies] = None, sensors: Optional[Sensors] = None):
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
@@ -261,8 +270,10 @@ class ClipBatches:
         self.labels = torch.from_numpy(np.asarray(dataset.labels_data).astype(np.int64))
         on_gpu = self.device.type == "cuda"
         self.bodies, self.normalize, self.inertial, self.window, self.augment, self.streams = bodies, normalize, inertial, window, augment, streams
-        self.stages = [s for s in (bodies, normalize, inertial, window, augment, streams) if s is not None]      # THE order they run in
+        self.sensors = sensors
+        self.stages = [s for s in (bodies, normalize, inertial, window, augment, sensors, streams) if s is not None]      # THE order they run in
         self.last_bodies, self.last_plan, self.last_inertial, self.last_window, self.last_params, self.last_streams = {}, {}, None, {}, {}, {}
+        self.last_sensors = {}
         for i, later in enumerate(self.stages):
             for earlier in self.stages[:i]:
                 stale = sorted(k for k in later.valid_frames if earlier.fills_frames(k))
@@ -358,7 +369,12 @@ class ClipBatches:
                 di = idx.to(self.device)
                 feats, rows = self.dev_feat, di          # rows = ids = the shard's indices, for the first per-batch stage
                 for s in per_batch:
-                    feats = s.run(self, feats, rows, {**self.dev_tab[s.name], None: di}, dict.fromkeys(self.writes[s.name]))
+                    # a table is indexed by the rows of its feature: the whole table for a feature that is still the resident array, the
+                    # batch's entries in order for one an earlier per-batch stage wrote (only a stage that does not fill the frames, a
+                    # Sensors, leaves a later stage such a table)
+                    tabs = {t: v.index_select(0, di) if isinstance(rows, dict) and rows.get(t, di) is not di else v
+                            for t, v in self.dev_tab[s.name].items()}
+                    feats = s.run(self, feats, rows, {**tabs, None: di}, dict.fromkeys(self.writes[s.name]))
                     if s is not per_batch[-1]:           # what it wrote holds the batch's rows in order, the rest is still the resident array
                         rows = {k: self.batch_rows[:len(idx)] if k in self.writes[s.name] else Stage.rows_of(rows, k) for k in feats}
                 feats = {k: v if k in written else v.index_select(0, di) for k, v in feats.items()}

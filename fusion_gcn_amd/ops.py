@@ -1990,6 +1990,71 @@ def clip_augment(src: torch.Tensor, idx: torch.Tensor, sample_ids: torch.Tensor,
     return out, params
 
 
+# ---- augmentation of inertial recordings as the batch is gathered (fgcn_clip_sensors / fgcn_sensors_params) -----------
+def _sensors_scalars(max_angle, scale: float, warp: float, warp_knots: int, drop: float):
+    if len(max_angle) != 3:
+        raise _lib.FgcnError(f"sensors: max_angle needs three angles (x, y, z), got {max_angle!r}")
+    return (ctypes.c_float * 3)(*[float(a) for a in max_angle]), float(scale), float(warp), int(warp_knots), float(drop)
+
+
+def _sensors_jitter(jitter, sensors: int):
+    """``jitter`` as one value per sensor: a scalar for all of them, or ``sensors`` values"""
+    values = [float(jitter)] * sensors if isinstance(jitter, numbers.Real) else [float(j) for j in jitter]
+    if len(values) != sensors:
+        raise _lib.FgcnError(f"sensors: jitter holds {len(values)} values for {sensors} sensors")
+    return (ctypes.c_float * max(sensors, 1))(*values)
+
+
+def sensors_params(sample: int, site: int, epoch: int, seed: int, sensors: int, max_angle=(0.0, 0.0, 0.0), scale: float = 0.0,
+                   warp: float = 0.0, warp_knots: int = 4, drop: float = 0.0) -> list:
+    """The table row of one sample with ``sensors`` sensors on the HOST (no device is touched): [R row-major (9), 0, 0, 0], then per sensor
+    [gain, drop flag, 0, 0, knots (8)], by the functions the kernel calls."""
+    ang, scale, warp, warp_knots, drop = _sensors_scalars(max_angle, scale, warp, warp_knots, drop)
+    sensors = int(sensors)
+    out, (seed, site, epoch) = (ctypes.c_float * (12 + 12 * max(sensors, 0)))(), _rng_words(seed, site, epoch)
+    check(_lib.load().fgcn_sensors_params(int(sample) & 0xFFFFFFFF, site, epoch, seed, ang, scale, warp, warp_knots, drop, sensors, out),
+          "fgcn_sensors_params")
+    return list(out)
+
+
+def clip_sensors(src: torch.Tensor, idx: torch.Tensor, sample_ids: torch.Tensor, *, seed: int, epoch: int, site: int = 0,
+                 max_angle=(0.0, 0.0, 0.0), scale: float = 0.0, warp: float = 0.0, warp_knots: int = 4, jitter=0.0, drop: float = 0.0,
+                 joints: Optional[Tuple[int, int]] = None, minmax: bool = False, valid: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None):
+    """-> (out, params, stats): out[k] = source row ``idx[k]`` of ``src`` with every sensor (a triple of values) rotated, scaled, warped in
+    magnitude, jittered and dropped in its valid frames with the random numbers of sample ``sample_ids[k]`` in ``epoch`` (include/fgcn.h);
+    params (b, 12 + 12 G): the rows' rotation, then gain, drop flag and knots of each of the G sensors; stats (b, 2): minimum and maximum
+    of the shifted clip (0, 1 without ``minmax``).  src: (rows, T, S) with S % 3 == 0, whose S / 3 column triples are the sensors
+    (``joints`` None), or (rows, M, T, V, 3) with ``joints = (lo, hi)``, whose joints ``[lo, hi)`` of every body are; contiguous float32 on
+    the device.  idx, sample_ids: (b) int64 -- on the device, where ``idx`` is trusted to hold rows of ``src``, or on the host, where it is
+    checked and uploaded; valid: None or (rows) int32 on the device, the valid frames of each SOURCE row; jitter: a scalar or one value
+    per sensor, in the stored units; minmax: (rows, T, S) only."""
+    ensure_device()
+    _chk(src, "clip_sensors.src")
+    outer, T, inner = _clip_dims(src, "clip_sensors.src")
+    if src.dim() == 3 and joints is None:
+        lo, hi = 0, inner // 3
+    elif src.dim() == 5 and joints is not None and src.shape[-1] == 3:
+        lo, hi = int(joints[0]), int(joints[1])
+    else:
+        raise _lib.FgcnError(f"clip_sensors.src: expected (rows, T, S) without joints or (rows, M, T, V, 3) with joints=(lo, hi), got "
+                             f"{tuple(src.shape)} with joints={joints!r}")
+    idx = _rows(idx, src.shape[0], src.device, "clip_sensors.idx")
+    b = idx.numel()
+    sample_ids = _sample_ids(sample_ids, b, src.device, "clip_sensors.sample_ids")
+    if valid is not None:
+        _lengths(valid, src.shape[0], "clip_sensors.valid")
+    out = _batch_out(out, (b, *src.shape[1:]), src.device, "clip_sensors.out")
+    ang, scale, warp, warp_knots, drop = _sensors_scalars(max_angle, scale, warp, warp_knots, drop)
+    sigma = _sensors_jitter(jitter, max(hi - lo, 0))
+    params = torch.empty((b, 12 + 12 * max(hi - lo, 0)), device=src.device, dtype=torch.float32)
+    stats = torch.empty((b, 2), device=src.device, dtype=torch.float32)
+    check(_lib.load().fgcn_clip_sensors(_p(src), idx.data_ptr(), sample_ids.data_ptr(), _p(valid), _p(out), _p(params), _p(stats), b, outer, T,
+                                        inner, lo, hi, ang, scale, warp, warp_knots, sigma, drop, int(bool(minmax)),
+                                        *_rng_words(seed, site, epoch), _stream()), "fgcn_clip_sensors")
+    return out, params, stats
+
+
 # ---- normalisation of raw skeleton clips as the batch is gathered (fgcn_clip_normalize; DESIGN.md section 8g) --------------------------
 def _joint_pair(pair, name: str) -> Tuple[int, int]:
     if pair is None:

@@ -1,4 +1,4 @@
-"""The stages of ``ClipBatches``' preparation on the device: ``Stage``, what data.py asks of one and what they share, and the six stages,
+"""The stages of ``ClipBatches``' preparation on the device: ``Stage``, what data.py asks of one and what they share, and the seven stages,
 whose ``run`` calls the HIP wrappers of ops.py (no host fallback).  data.py's module docstring says what each does and in which order."""
 from __future__ import annotations
 
@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import BODIES_MAX, FgcnError
+from ._lib import BODIES_MAX, SENSORS_MAX, SENSORS_MAX_KNOTS, FgcnError
 
 Shapes = Dict[str, tuple]       # feature id -> the shape of a sample
 Feats = Dict[str, torch.Tensor]
@@ -18,11 +18,12 @@ Rows = Union[torch.Tensor, Dict[str, torch.Tensor]]
 # A further stage is one more subclass of Stage here and one more entry of the tuple that builds ClipBatches.stages: Streams was the fourth,
 # Window is the fifth (it runs third: in front of the rotation, which then touches W frames instead of T, and of the streams, whose motion is
 # the windowed clip's).  Bodies is the sixth, it runs first: it decides what body 0 is, by which Normalize centres and rotates the clip, and
-# how many body slots every later stage and the model see.
+# how many body slots every later stage and the model see.  Sensors is the seventh, it runs sixth: behind Augment, whose resampling would smooth
+# its jitter, and in front of Streams, which derive their streams from the clip the model sees.
 
 class Stage:
-    """A stage of ClipBatches' preparation on the device -- Bodies, Normalize, Inertial, Window, Augment, Streams, run in that order -- is a
-    configuration object with
+    """A stage of ClipBatches' preparation on the device -- Bodies, Normalize, Inertial, Window, Augment, Sensors, Streams, run in that order --
+    is a configuration object with
       name        its keyword of ClipBatches, for the refusal of a device without HIP kernels
       at_upload   True: a resident split takes it once, at construction; False: every batch does (a class attribute, or one of the instance:
                   Window(train=False) runs at upload, Window(train=True) per batch)
@@ -34,11 +35,12 @@ class Stage:
       run(batches, feats, rows, tables, out) -> feats   launches on the current stream: rows ``rows`` of the arrays ``feats`` into the buffers
                   ``out`` (feature id -> tensor, or None = a new one); ``tables[name][rows[j]]`` belongs to output row j, except the sample ids,
                   which are listed by output row; what the stage keeps for inspection goes to ``batches.last_*``.  A per-batch stage that
-                  may run BEHIND another per-batch stage on the resident path (Augment behind Window, Streams behind both) takes ``rows`` per
-                  feature too, {feature id: rows} (``rows_of`` reads either): what the stage before wrote holds the batch's rows in order
-                  (rows 0..m-1), what it left out is still the resident array (the shard's indices).  The rows are handed over per feature
-                  rather than the left-out features gathered first: a gather would be one more pass over rows that the stage's own kernel
-                  gathers anyway.
+                  may run BEHIND another per-batch stage on the resident path (Augment behind Window, Sensors behind both, Streams behind
+                  all) takes ``rows`` per feature too, {feature id: rows} (``rows_of`` reads either): what the stage before wrote holds the
+                  batch's rows in order (rows 0..m-1), what it left out is still the resident array (the shard's indices).  The rows are
+                  handed over per feature rather than the left-out features gathered first: a gather would be one more pass over rows that
+                  the stage's own kernel gathers anyway.  A table goes with its feature's rows: where the stage before wrote the feature
+                  without filling its frames (Sensors), ``ClipBatches`` hands the next stage the batch's table entries in order.
       fills_frames(feature_id) -> bool   True: every frame of the feature is valid behind the stage, so that a ``valid_frames`` table of a
                   later stage no longer describes it (``ClipBatches`` refuses one); ``fills`` then says how, for that refusal
     The class holds what the stages share and nothing more."""
@@ -163,6 +165,108 @@ class Augment(Stage):
             feats[k], batches.last_params[k] = ops.clip_augment(
                 src, self.rows_of(rows, k), tables[None], seed=batches.seed, epoch=batches.epoch, site=self.site, max_angle=self.max_angle,
                 scale=self.scale, min_window=self.min_window, joints=self.joint_range(src.shape[1:]), valid=tables.get(k), out=o)
+        return feats
+
+
+class Sensors(Stage):
+    """What ``ClipBatches(sensors=...)`` does to the inertial half of every clip it hands out (include/fgcn.h): the
+    standard perturbations of wearable-sensor data, behind ``augment`` (whose resampling would smooth the jitter) and in front of
+    ``streams`` (which must see the clip the model sees).
+
+    A sensor is a triple of values: columns ``3g .. 3g+2`` of a ``(T, S)`` signal with ``S % 3 == 0``, and -- with ``joints = (lo, hi)`` --
+    joint ``lo + g`` of every body of an ``(M, T, V, 3)`` array (the sensor joints ``Inertial(enhance=True)`` appends; the other joints
+    are gathered unchanged).  ``max_angle``: the largest rotation of the sensor frame about x, y, z in radians, ONE rotation per sample,
+    independent of ``Augment``'s; ``scale``: the gain of each sensor is uniform in 1 +- scale; ``warp``: a smooth factor 1 + delta(t) over
+    the valid frames, the Catmull-Rom curve through ``warp_knots`` values uniform in +-warp per sensor (``warp_knots``: 0, or 2..8);
+    ``jitter``: the standard deviation of the additive normal noise, a scalar or one value per sensor, in the STORED units (accelerometer
+    and gyroscope units differ by orders of magnitude); ``drop``: the probability that a whole sensor comes out as zeros.  All bodies of
+    an array, and the signal and the enhanced skeleton of one sample, receive the same values.
+
+    The values are taken as physical ones, zero meaning no signal: data prepared on the device uses ``Inertial(minmax=False)`` and this
+    stage's ``minmax=True``, which applies the reference's min-max normalisation AFTER the augmentation, to the ``(T, S)`` signals only,
+    over the whole padded array by ``Inertial``'s float32 formula.  Stored features that were min-max normalised offline have their zero
+    somewhere else: the rotation and the drop are not meaningful for them (gain, warp and jitter act on the shifted values).
+    ``valid_frames``: feature id -> the number of valid frames of each sample (the frames behind them are copied, so the padding stays
+    zero; default: all T).  ``only``: the feature ids to apply to (default: every feature of a shape above; features of other shapes are then left
+    alone, except that a ``(T, S)`` feature with ``S % 3 == 0`` and more than 16 triples is refused rather than skipped: it looks like a
+    recording the kernel cannot take, and ``only=`` says which features are meant); ``site`` separates two uses of one seed (``Augment``
+    and ``Window`` at the same site draw from other counter words)."""
+
+    name, at_upload = "sensors", False
+
+    def __init__(self, max_angle: Sequence[float] = (0.3, 0.3, 0.3), scale: float = 0.1, warp: float = 0.0, warp_knots: int = 4,
+                 jitter: Union[float, Sequence[float]] = 0.0, drop: float = 0.0, joints: Optional[Tuple[int, int]] = None,
+                 minmax: bool = False, valid_frames: Optional[Mapping[str, Sequence[int]]] = None, site: int = 0,
+                 only: Optional[Iterable[str]] = None):
+        self.max_angle = tuple(float(a) for a in max_angle)
+        if len(self.max_angle) != 3 or not all(np.isfinite(self.max_angle)):
+            raise ValueError(f"max_angle: three finite angles (x, y, z), got {max_angle!r}")
+        for what, value in (("scale", scale), ("warp", warp), ("drop", drop)):
+            if not 0.0 <= value < 1.0:
+                raise ValueError(f"{what}={value} outside [0, 1)")
+        whole = not isinstance(warp_knots, bool) and isinstance(warp_knots, (int, np.integer))
+        if not whole or not (warp_knots == 0 or 2 <= warp_knots <= SENSORS_MAX_KNOTS):
+            raise ValueError(f"warp_knots={warp_knots!r}: expected 0 or a number of knots in [2, {SENSORS_MAX_KNOTS}]")
+        self.jitter = float(jitter) if np.ndim(jitter) == 0 else tuple(float(j) for j in jitter)
+        if not all(np.isfinite(j) and j >= 0.0 for j in np.atleast_1d(self.jitter)):
+            raise ValueError(f"jitter={jitter!r}: expected finite values >= 0")
+        if joints is not None and not 0 <= joints[0] < joints[1]:
+            raise ValueError(f"joints={joints!r}: expected (lo, hi) with 0 <= lo < hi")
+        self.scale, self.warp, self.warp_knots, self.drop = float(scale), float(warp), int(warp_knots), float(drop)
+        self.joints = None if joints is None else (int(joints[0]), int(joints[1]))
+        self.minmax, self.site = bool(minmax), int(site)
+        super().__init__(only, valid_frames)
+
+    def sensor_range(self, sample_shape: Sequence[int]) -> Optional[Tuple[int, int]]:
+        """The units of three values of a sample of this shape that are sensors; None: the stage does not apply to the shape."""
+        if len(sample_shape) == 2 and sample_shape[1] % 3 == 0 and sample_shape[1] > 0:
+            return 0, sample_shape[1] // 3
+        if len(sample_shape) == 4 and sample_shape[3] == 3 and self.joints is not None:
+            return self.joints
+        return None
+
+    def bind(self, shapes: Shapes, n: int, keys: Sequence[str]) -> Tuple[Shapes, List[str]]:
+        self.refuse_unknown(set(self.valid_frames) | set(self.only or ()), keys, shapes)
+        writes = []
+        for k in shapes:
+            if not self.applies_to(k):
+                continue
+            span = self.sensor_range(shapes[k])
+            if span is None:
+                if self.only is None:
+                    continue
+                raise FgcnError(f"sensors: feature {k!r} has shape {(n, *shapes[k])}; expected (samples, T, S) with S % 3 == 0 or, with "
+                                f"joints=(lo, hi), (samples, M, T, V, 3) -- leave it out with Sensors(only=...)")
+            lo, hi = span
+            if len(shapes[k]) == 4 and hi > shapes[k][2]:
+                raise ValueError(f"joints={self.joints!r} for an array of {shapes[k][2]} joints (feature {k!r})")
+            if hi - lo > SENSORS_MAX:
+                raise FgcnError(f"sensors: feature {k!r} holds {hi - lo} sensors, at most {SENSORS_MAX} -- leave it out with Sensors(only=...)")
+            if np.ndim(self.jitter) and len(self.jitter) != hi - lo:
+                raise ValueError(f"jitter holds {len(self.jitter)} values, feature {k!r} has {hi - lo} sensors")
+            writes.append(k)
+        stale = sorted(set(self.valid_frames) - set(writes))
+        if stale:
+            raise ValueError(f"sensors: valid_frames{stale} for features the stage does not apply to")
+        for k in writes:
+            if k in self.valid_frames:
+                self.frame_table(k, n, shapes[k][0] if len(shapes[k]) == 2 else shapes[k][1])
+        return dict(shapes), writes
+
+    def tables(self, writes: Sequence[str], n: int) -> Dict[Optional[str], np.ndarray]:
+        """None: the clips' ids, which key the random numbers; feature id: the valid frames of its clips"""
+        return {None: np.arange(n, dtype=np.int64), **self.frame_tables(writes)}
+
+    def run(self, batches, feats: Feats, rows: Rows, tables: Tables, out: Dict[str, Optional[torch.Tensor]]) -> Feats:
+        """``rows`` per feature where the stage before (a per-batch ``Window`` or ``Augment``) wrote some features and not others (see ``Stage``)"""
+        feats = dict(feats)
+        for k, o in out.items():
+            src = feats[k]
+            feats[k], params, stats = ops.clip_sensors(
+                src, self.rows_of(rows, k), tables[None], seed=batches.seed, epoch=batches.epoch, site=self.site, max_angle=self.max_angle,
+                scale=self.scale, warp=self.warp, warp_knots=self.warp_knots, jitter=self.jitter, drop=self.drop,
+                joints=self.joints if src.dim() == 5 else None, minmax=self.minmax and src.dim() == 3, valid=tables.get(k), out=o)
+            batches.last_sensors[k] = (params, stats)
         return feats
 
 

@@ -1264,6 +1264,84 @@ int fgcn_clip_window(const float* src, const long long* idx, const long long* sa
 int fgcn_window_params(unsigned sample, unsigned site, unsigned epoch, unsigned long long seed, float lo, float hi, int mode, float out2[2]);
 int fgcn_clip_valid_frames(const float* src, const long long* idx, int* out, int b, int outer, int T, int inner, void* stream);
 
+/* Augmentation of inertial recordings as the batch is gathered (data.ClipBatches(sensors=...)): the four standard
+ * perturbations of wearable-sensor data -- a random rotation of the sensor frame, a random gain per sensor, a smooth magnitude warp over
+ * time, additive jitter -- and the drop of a whole sensor.  fgcn_clip_augment's conventions: a sample is (outer, T, inner) float32, row k
+ * of `out` is made of source row idx[k], the random numbers are a pure function of (seed, site, epoch, sample_ids[k]), a word w gives the
+ * uniform u = (float)(w >> 8) * 2^-24, all arithmetic is float32 with every product and sum rounded on its own unless an fma is named.
+ *
+ * Sensors.  A SENSOR is a triple of values; inner = 3 * units, and the sensors are units [joint_lo, joint_hi), G = joint_hi - joint_lo of
+ * them, 1 <= G <= FGCN_SENSORS_MAX.  In a (T, S) signal (outer = 1, inner = S, the range [0, S / 3)) sensor g is columns 3g .. 3g+2; in an
+ * (M, T, V, 3) array (outer = M, inner = 3 V) sensor g is joint joint_lo + g of EVERY body.  The units outside the range are copied through
+ * by the same gather.  Values are physical ones, zero meaning no signal.  No draw is keyed by the body: all bodies of an array receive the
+ * same values for a sensor (fgcn_imu_enhance's invariant "joint V + j of every body holds the recording" is kept), and two arrays of one
+ * sample that hold the same G sensors -- the signal and the enhanced skeleton -- share every draw: equal inputs give equal outputs bit for
+ * bit.
+ *
+ * Random words: philox(ctr = {(unsigned)sample, site, epoch, j}, key = {lo32(seed), hi32(seed)}).  fgcn_clip_augment uses j = 0, 1 and
+ * fgcn_clip_window j = 2 at the same (seed, site); this stage uses j = 3 for the sample, j = 16 + 4g + {0, 1, 2} for sensor g and
+ * j = 2^20 + t * G + g for the jitter of frame t, sensor g: the three stages are independent without a second site.
+ *
+ * Parameters (the table row of the sample, 12 + 12 G floats).  Floats 0..11, from block 3:
+ *     theta_a = (2 u_a - 1) * max_angle[a], a = x, y, z, from words 0..2 (2u - 1 is exact);
+ *     R = Rz(theta_z) * Ry(theta_y) * Rx(theta_x), each entry the sum of its one or two products of sinf / cosf values, formed by the
+ *     function fgcn_clip_augment forms its matrix with (at s = 1);   row[0..11] = {R row-major (9), 0, 0, 0}.
+ * ONE rotation per sample, shared by all its sensors: they sit in one device frame.  It is independent of fgcn_clip_augment's rotation
+ * of the skeleton: a change of camera view does not turn a body-worn sensor's axes.
+ * Floats 12 + 12g .. 12 + 12g + 11, the group of sensor g, from blocks 16 + 4g (gain, drop), 16 + 4g + 1 (knots 0..3), 16 + 4g + 2 (knots 4..7):
+ *     s_g = 1 + (2 u_0 - 1) * scale;   dropped iff word_1 < (unsigned)(drop * 2^32), an integer compare (the product in float64, as in
+ *     fgcn_dropout_fwd);   d_{g,k} = (2 u - 1) * warp for k < K = warp_knots, u from word k & 3 of the knot's block;
+ *     group = {s_g, 1.0 if dropped else 0.0, 0, 0, d_{g,0..7} with the knots k >= K as 0}.
+ *
+ * A valid frame t < v of sensor g (v = valid[idx[k]]; valid == NULL: T; a value outside [1, T] is clamped into it), x its source triple:
+ *   1. y_c = s_g * fma(R[c][2], x_2, fma(R[c][1], x_1, R[c][0] * x_0)).
+ *   2. Magnitude warp, K >= 2 (K == 0: this step is skipped):  q = t * ((K - 1) / (v - 1)), the quotient first (q = 0 when v == 1);
+ *      i = min(floor(q), K - 2);  f = q - i;  p0 = d[max(i - 1, 0)], p1 = d[i], p2 = d[i + 1], p3 = d[min(i + 2, K - 1)] (the end knots
+ *      repeated);  the Catmull-Rom value through them in Horner form, in exactly this order:
+ *          ca = p2 - p0;   cb = ((2 p0 - 5 p1) + 4 p2) - p3;   cc = (3 (p1 - p2) + p3) - p0;
+ *          delta = p1 + 0.5 * (f * (ca + f * (cb + f * cc)));   m = 1 + delta;   y_c = m * y_c.
+ *      warp == 0 gives knots of +-0, delta = +-0 and m == 1 exactly.
+ *   3. Jitter, sigma_g != 0 (sigma_g == 0: the step is skipped, there is no addition: a -0 that reaches this step leaves it as -0).  From the block {w0..w3} of (t, g):
+ *      u1 = ((w0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (w1 >> 8) * 2^-24;  rad = sqrtf(-2 * logf(u1));  n_0 = rad * cospif(2 u2),
+ *      n_1 = rad * sinpif(2 u2);  n_2 = the cosine branch of (w2, w3);  y_c = y_c + sigma_g * n_c (a product, then a sum).  sigma is in the
+ *      STORED units, one value per sensor: accelerometer and gyroscope units differ by orders of magnitude.
+ *   4. Drop: a dropped sensor's valid frames are +0, whatever steps 1 to 3 gave (there is no rescaling of the kept sensors).
+ * Frames at or behind v are copied bit for bit: the padding stays zero.
+ * minmax != 0, (T, S) signals only (outer == 1): step 3a of fgcn_signal_prepare applied AFTER the augmentation, over the whole (T, inner)
+ * array, the padding zeros included, by the same float32 formula: mn = min y, mx = fl32(max y - mn), out = fl32(fl32(y - mn) / mx), the
+ * division correctly rounded; stats[k] = {mn, mx}.  The result equals the formula applied to the minmax == 0 output of the same call,
+ * bit for bit.  minmax == 0: stats[k] = {0, 1}.  (Data prepared by fgcn_signal_prepare is prepared with ITS minmax == 0 for this.)
+ * Identity: zero angles, scale = warp = drop = 0, zero jitter and minmax == 0 give the gathered rows, as VALUES: step 1 with R = I is
+ * fma(0, x_2, fma(0, x_1, 1 * x_0)), which returns a -0 input as +0 where the 0 * x terms are +0 (fgcn_clip_augment's identity does the
+ * same).  The sign of a zero is kept only in what is copied: frames at or behind v and units outside the sensor range.
+ * Non-finite inputs: rule 3 of "Non-finite values in the inputs" above -- a triple of a kept sensor that reads a non-finite value is
+ * non-finite in all three values (0 * inf and 0 * NaN are NaN), NaN against +-inf need not match; a dropped sensor is +0, it reads
+ * nothing.  With minmax, a NaN in the augmented array makes mn, mx and the whole clip NaN, as numpy's min and max do.
+ *
+ * fgcn_clip_sensors: src (rows, outer, T, inner), idx / sample_ids (b) 8-byte integers on the device (idx may repeat and need not be sorted;
+ * every idx[k] must be a row of src -- the caller's duty; the streaming path passes idx = 0..b-1 and the real ids), valid NULL or 4-byte
+ * integers indexed by SOURCE row, out (b, outer, T, inner), params (b, 12 + 12 G) receives the table, stats (b, 2); jitter: G floats on the
+ * HOST.  Two launches: one lane per (row, table group) forms the table, then one lane per (row, outer, frame, unit) reads it back -- with
+ * minmax one workgroup per clip, which stores the augmented values, takes their minimum and maximum (order-independent, no atomics) and
+ * has every lane normalise the values it stored itself.  The result does not depend on b or on a row's place in the batch.  Rows need
+ * 4-byte alignment only.  No fgcn_set_tuning key is read.
+ * FGCN_E_BADARG before any launch: a null pointer (valid excepted); b, outer, T or inner <= 0; inner % 3 != 0; a sensor range that is empty
+ * or outside 0 <= joint_lo < joint_hi <= inner / 3; G > FGCN_SENSORS_MAX; an angle that is not finite; scale, warp or drop outside [0, 1);
+ * warp_knots neither 0 nor in [2, FGCN_SENSORS_MAX_KNOTS]; a jitter value that is negative or not finite; minmax with outer != 1;
+ * out == src; T * G >= 2^31 - 2^20 (the jitter's counter words); T * inner >= 2^29; more lanes than one grid holds.
+ *
+ * fgcn_sensors_params: the HOST copy of the table row of a sample with `sensors` = G sensors, 12 + 12 G floats (no device is touched),
+ * computed by the functions the kernel calls; the device's row differs from it in R alone, by the two sinf / cosf implementations.  The
+ * same refusals for its arguments. */
+#define FGCN_SENSORS_MAX 16
+#define FGCN_SENSORS_MAX_KNOTS 8
+int fgcn_clip_sensors(const float* src, const long long* idx, const long long* sample_ids, const int* valid, float* out, float* params,
+                      float* stats, int b, int outer, int T, int inner, int joint_lo, int joint_hi, const float max_angle[3], float scale,
+                      float warp, int warp_knots, const float* jitter, float drop, int minmax, unsigned long long seed, unsigned site,
+                      unsigned epoch, void* stream);
+int fgcn_sensors_params(unsigned sample, unsigned site, unsigned epoch, unsigned long long seed, const float max_angle[3], float scale, float warp,
+                        int warp_knots, float drop, int sensors, float* out);
+
 /* Score fusion of separately trained stream models (ops.score_fuse / ops.fuse_sweep, ensemble.StreamEnsemble / ScoreStore; DESIGN.md
  * section 8k): the 2s-AGCN family reports the accuracy of the weighted sum of its stream models' class scores.
  *
