@@ -231,6 +231,18 @@ SIGNATURES = {
     "fgcn_sensors_params": (_I, [C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, C.POINTER(C.c_float), _F, _F, _I, _F, _I, C.POINTER(C.c_float)]),
     "fgcn_score_fuse": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _I, _I, _P]),
     "fgcn_fuse_sweep": (_I, [C.POINTER(FuseIn), _I, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
+    "fgcn_stc_splits": (_I, [_I, _I]),
+    "fgcn_stc_mean_t": (_I, [_P] * 2 + [_I] * 4 + [_P]),
+    "fgcn_stc_gate_s": (_I, [_P] * 4 + [_I] * 3 + [_P]),
+    "fgcn_stc_mean_v": (_I, [_P] * 3 + [_I] * 4 + [_P]),
+    "fgcn_stc_gates_tc": (_I, [_P] * 11 + [_I] * 3 + [_P]),
+    "fgcn_stc_apply": (_I, [_P] * 5 + [_I] * 4 + [_P]),
+    "fgcn_stc_bwd_qr": (_I, [_P] * 6 + [_I] * 4 + [_P]),
+    "fgcn_stc_bwd_tc": (_I, [_P] * 16 + [_I] * 3 + [_P]),
+    "fgcn_stc_bwd_ds": (_I, [_P] * 3 + [_I] * 4 + [_P]),
+    "fgcn_stc_bwd_s": (_I, [_P] * 10 + [_I] * 4 + [_P]),
+    "fgcn_stc_bwd_apply": (_I, [_P] * 7 + [_I] * 4 + [_P]),
+    "fgcn_stc_param_grads": (_I, [_P] * 16 + [_I] * 3 + [_P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

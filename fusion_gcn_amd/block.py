@@ -15,10 +15,11 @@ Kernel schedule of one block, train mode (B = N*M samples):
                (else: rows_gemm / pw_gemm(theta|phi 1x1) -> joint_gram) -> adj_softmax (A^ = A + B + C)
             spatial_fwd  [fused x.A^_k + conv_d, BN partial sums]   (or joint_mix + rows_gemm when fused_spatial=False)
             bn_finalize -> [rows_gemm(down) -> bn_finalize] -> bn_act (BN + down/identity + ReLU = G)
+            [BlockConfig.attention: stc_forward, MS-AAGCN's STC attention G' = G (1 + s)(1 + tg)(1 + cg); the temporal conv reads G']
             tconv_halo (9x1 temporal conv, stride 1; rows_gemm for stride 2) with BN partial sums -> bn_finalize
             [rows_gemm(residual 1x1 stride s) -> bn_finalize] -> bn_act (BN + residual + ReLU = O)
   backward  bn_act_bwd (O)  -> tconv_halo(data gradient 9x1; two parity passes when strided) / tconv_wgrad(all taps)
-            -> bn_act_bwd (G)
+            [-> stc_backward (dG' -> dG in place, the attention's eight parameter gradients)] -> bn_act_bwd (G)
             spatial_wgrad_tile [bf16x3, channels in 64s: conv_d's weight gradient, aggregation on chip, whole frame tiles]
                (else: spatial_wgrad up to 128 outputs; beyond: joint_mix_vec(agg) -> pw_wgrad)
             -> spatial_bwd_tile [bf16x3, >= 64 inputs: dagg = dY.Wd on chip, dx and dA^ in one launch]
@@ -56,6 +57,7 @@ class BlockConfig:
     has_down: bool = False
     static_adjacency: bool = False  # ST-GCN special case: A^ = A + B, no data-dependent C_k
     fused_spatial: bool = True      # north-star fused kernel vs. joint_mix + rows_gemm
+    attention: bool = False         # MS-AAGCN's STC attention between the graph convolution and the temporal conv
 
     @property
     def ic(self) -> int:
@@ -87,7 +89,14 @@ def param_names(cfg: BlockConfig) -> List[str]:
     names += ["tcn1.conv.weight", "tcn1.conv.bias", "tcn1.bn.weight", "tcn1.bn.bias"]
     if cfg.residual == "conv":
         names += ["residual.conv.weight", "residual.conv.bias", "residual.bn.weight", "residual.bn.bias"]
+    if cfg.attention:                # (appended: the positions of a block's other parameters do not depend on it)
+        names += stc_names()
     return names
+
+
+def stc_names() -> List[str]:
+    """the eight tensors of the STC attention module, registered on gcn1 behind everything else it holds"""
+    return [f"gcn1.{n}" for n in ops.STC_PARAMS]
 
 
 def bn_names(cfg: BlockConfig) -> List[str]:
@@ -456,6 +465,11 @@ def _temporal_stage(x, S, P, bufs, W, cfg: BlockConfig, pl: BlockPlan, x32):
     Tp = (T - 1) // s + 1
     dev = x.device
     new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
+    if cfg.attention:
+        # G' = G (1 + s)(1 + tg)(1 + cg): the temporal conv and its weight gradient read G'; the pre-gate G stays for the attention's
+        # backward and the ReLU gate (every gate is > 0: G's sign image is G''s too)
+        S["g_att"], S["stc"] = ops.stc_forward(S["g"], [P[n] for n in stc_names()])
+    g_t = S["g_att"] if cfg.attention else S["g"]        # the temporal conv's input
     if pl.temporal_bn_relu:
         # north-star kernel 2 as the north star states it, inference form: temporal conv + BatchNorm + shortcut + ReLU in one kernel
         vec_u = _bn_vec(None, B * Tp * V, P, bufs, "tcn1.bn", False)
@@ -465,13 +479,13 @@ def _temporal_stage(x, S, P, bufs, W, cfg: BlockConfig, pl: BlockPlan, x32):
             ops.rows_gemm(x, W["res"], r, K=cin, N=cout, tmap=(1, s, 0, 0, 1), bias=P["residual.conv.bias"])
             vec_r = _bn_vec(None, B * Tp * V, P, bufs, "residual.bn", False)
         o = new(B, Tp, V, cout)
-        ops.tconv_halo_bn_relu(S["g"], W["t4"], o, taps=kt, tb=1, tc=-((kt - 1) // 2), vec=vec_u, bias=P["tcn1.conv.bias"],
+        ops.tconv_halo_bn_relu(g_t, W["t4"], o, taps=kt, tb=1, tc=-((kt - 1) // 2), vec=vec_u, bias=P["tcn1.conv.bias"],
                                res=x if cfg.residual == "identity" else r, res_vec=vec_r)
         S.update(u=None, vec_u=vec_u, r=None, vec_r=vec_r, o=o, o_sign=None)
         return o, S
     u = torch.empty((B, Tp, V, cout), device=dev, dtype=torch.bfloat16) if pl.u_bf16 else new(B, Tp, V, cout)
     # (plan.fuse_g: the conv's first argument is the BatchNorm input y; it forms G and its sign image on the way)
-    part = temporal_fwd(S["y"] if pl.fuse_g else S["g"], u, W, P["tcn1.conv.bias"], kt, s, stats=train, route=pl.temporal_fwd,
+    part = temporal_fwd(S["y"] if pl.fuse_g else g_t, u, W, P["tcn1.conv.bias"], kt, s, stats=train, route=pl.temporal_fwd,
                         fuse_in=(S["vec_y"], x, S["g"], S["g_sign"]) if pl.fuse_g else None, amax_out=S["amax"][1:2] if pl.g_amax else None)
     vec_u = _bn_vec(part, B * Tp * V, P, bufs, "tcn1.bn", train)
     r, vec_r = None, None
@@ -648,9 +662,13 @@ def _block_backward(d_o, S, P, W, cfg: BlockConfig, train: bool, need_dx: bool, 
     g_partials = temporal_dgrad(du, dg, W, kt, s, bn_bwd=(S["y"], S["g_sign"], S["vec_y"]) if fuse_sums else None,
                                 amax_out=bamax[0:1] if pl.du_amax else None, route=pl.temporal_dgrad)
     # weight gradients are reduced straight into the parameter's (out, in, kt, 1) layout: autograd takes them as they are
-    G["tcn1.conv.weight"] = ops.tconv_wgrad(S["g"], du, taps=kt, stride=s, conv_param=(1, cout), all_taps=False if pl.wide else None,
+    G["tcn1.conv.weight"] = ops.tconv_wgrad(S["g_att"] if cfg.attention else S["g"], du, taps=kt, stride=s, conv_param=(1, cout), all_taps=False if pl.wide else None,
                                             amax=(S["amax"][1:2], bamax[0:1]) if pl.du_amax and pl.g_amax else None)
     G["tcn1.conv.bias"] = bias_grad.main(du, 0)
+    if cfg.attention:
+        # dG' -> dG in place (the plan keeps both float32 in an attention block), and the module's eight parameter gradients
+        _, stc_grads = ops.stc_backward(dg, S["g"], S["stc"], [P[n] for n in stc_names()], out=dg)
+        G.update(zip(stc_names(), stc_grads))
 
     # -- G = relu(BN(y) + down(x)) ---------------------------------------------------------------------------------------------
     if cfg.has_down:

@@ -854,4 +854,34 @@ class FusedDropout(torch.nn.Dropout):
         return dropout(x, self, self.p, self.training)
 
 
+class _StcAttention(torch.autograd.Function):
+    """g' = g (1 + s)(1 + tg)(1 + cg), the STC attention module of MS-AAGCN (include/fgcn.h, "STC attention"): ops.stc_forward /
+    ops.stc_backward; inputs g, then the eight parameter tensors in ops.STC_PARAMS order."""
+
+    @staticmethod
+    def forward(ctx, g, *params):
+        g = g.contiguous()
+        out, saved = ops.stc_forward(g, params)
+        ctx.save_for_backward(g, *params, *(saved[k] for k in _STC_SAVED))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        g, *rest = ctx.saved_tensors
+        params, saved = rest[:len(ops.STC_PARAMS)], dict(zip(_STC_SAVED, rest[len(ops.STC_PARAMS):]))
+        dg, grads = ops.stc_backward(d_out.contiguous(), g, saved, params)
+        return (dg, *grads)
+
+
+_STC_SAVED = ("mt", "s", "m", "tg", "cm", "h", "cg")
+
+
+def stc_attention(g: torch.Tensor, conv_sa: torch.nn.Conv1d, conv_ta: torch.nn.Conv1d, fc1c: torch.nn.Linear, fc2c: torch.nn.Linear) -> torch.Tensor:
+    """Differentiable STC attention of g (B, T, V, C) float32 channels-last (C in 64s, V <= 64): the spatial gate ``conv_sa`` =
+    Conv1d(C, 1, k, padding=(k - 1) // 2) over the joints of mean_t g (k = V for an odd V, else V - 1), the temporal gate ``conv_ta`` =
+    Conv1d(C, 1, 9, padding=4) over the frames, the channel gate ``fc1c`` = Linear(C, C / 2) -> ReLU -> ``fc2c`` = Linear(C / 2, C); each gate
+    multiplies by 1 + sigmoid(.).  The modules are parameter containers: three passes over g each way, no torch arithmetic."""
+    return _StcAttention.apply(g, conv_sa.weight, conv_sa.bias, conv_ta.weight, conv_ta.bias, fc1c.weight, fc1c.bias, fc2c.weight, fc2c.bias)
+
+
 ops.bind_all_functions(globals())     # every Function's backward runs in its forward's library context (ops.Context)

@@ -32,10 +32,10 @@ class unit_gcn(_base.GraphConvParams):
 
     ADJ_PARAM = "PA"
 
-    def __init__(self, in_channels, out_channels, A, coff_embedding=4, num_subset=3):
+    def __init__(self, in_channels, out_channels, A, coff_embedding=4, num_subset=3, attention=False):
         if (coff_embedding, num_subset) != (4, 3):
             raise ValueError("the HIP AGCN block implements coff_embedding=4, num_subset=3")
-        super().__init__(in_channels, out_channels, torch.from_numpy(np.asarray(A, dtype=np.float32)), num_subset)
+        super().__init__(in_channels, out_channels, torch.from_numpy(np.asarray(A, dtype=np.float32)), num_subset, attention=attention)
         self.num_subset, self.inter_c = num_subset, self.embedding_channels
         self.soft, self.relu = nn.Softmax(-2), nn.ReLU()
 
@@ -73,7 +73,7 @@ class Model(nn.Module):
         adj = kwargs.get("adjacency_matrix")
         if adj is None:
             adj = GraphPartitionStrategy().get_adjacency_matrix_array(graph)
-        kw = {k: kwargs.get(k, default) for k, default in (("static_adjacency", False), ("fused_spatial", True))}
+        kw = {k: kwargs.get(k, default) for k, default in (("static_adjacency", False), ("fused_spatial", True), ("attention", False))}
         self.data_bn = nn.BatchNorm1d(num_persons * num_channels * num_joints)
         bn_init(self.data_bn, 1)
         for i, (cin, cout, stride) in enumerate(_LAYERS, start=1):

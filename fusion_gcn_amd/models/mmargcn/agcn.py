@@ -87,7 +87,7 @@ class GraphConvParams(_KernelBacked):
     ADJ_PARAM = "adj_b"
     BRANCHES = ("conv_a", "conv_b", "conv_d")        # theta, phi (out/4 channels each), W_d (out channels)
 
-    def __init__(self, in_channels: int, out_channels: int, adjacency: torch.Tensor, num_subsets: int):
+    def __init__(self, in_channels: int, out_channels: int, adjacency: torch.Tensor, num_subsets: int, attention: bool = False):
         super().__init__()
         self.setattr_adjacency(adjacency)
         self.adj_c = [None] * num_subsets            # last forward's data-dependent adjacencies (metrics side output)
@@ -99,6 +99,24 @@ class GraphConvParams(_KernelBacked):
                      if in_channels != out_channels else _identity)
         self.bn = nn.BatchNorm2d(out_channels)
         self.reset_parameters(num_subsets)
+        if attention:
+            self.add_stc_attention(out_channels, adjacency.shape[-1])
+
+    def add_stc_attention(self, channels: int, num_joints: int) -> None:
+        """The parameters of MS-AAGCN's STC attention module (Shi et al., TIP 2020; block.py evaluates it between the graph convolution and
+        the temporal conv), registered behind everything else and drawn after it: the spatial gate's convolution over the joints (the
+        largest odd kernel <= the joint count, xavier-normal), the temporal gate's nine-tap convolution and the channel gate's second layer
+        (zero: both gates start at 1 + sigmoid(0)), the channel gate's first layer (kaiming-normal); biases zero."""
+        k = ops.stc_sa_kernel(num_joints)
+        self.conv_sa = nn.Conv1d(channels, 1, k, padding=(k - 1) // 2)
+        self.conv_ta = nn.Conv1d(channels, 1, ops.STC_TA_TAPS, padding=(ops.STC_TA_TAPS - 1) // 2)
+        self.fc1c = nn.Linear(channels, channels // 2)
+        self.fc2c = nn.Linear(channels // 2, channels)
+        with torch.no_grad():
+            nn.init.xavier_normal_(self.conv_sa.weight)
+            nn.init.kaiming_normal_(self.fc1c.weight)
+            for t in (self.conv_sa.bias, self.conv_ta.weight, self.conv_ta.bias, self.fc1c.bias, self.fc2c.weight, self.fc2c.bias):
+                t.zero_()
 
     def setattr_adjacency(self, adjacency: torch.Tensor) -> None:
         setattr(self, self.ADJ_PARAM, nn.Parameter(torch.full_like(adjacency, 1e-6)))
@@ -119,10 +137,10 @@ class GraphConvParams(_KernelBacked):
 
 class SpatialGraphConv(GraphConvParams):
     def __init__(self, in_channels: int, out_channels: int, adj: np.ndarray, coff_embedding: int = 4,
-                 num_subsets: int = 3):
+                 num_subsets: int = 3, attention: bool = False):
         if coff_embedding != 4 or num_subsets != 3:
             raise ValueError("the HIP AGCN block implements coff_embedding=4, num_subsets=3 (the reference's only use)")
-        super().__init__(in_channels, out_channels, torch.from_numpy(np.asarray(adj, dtype=np.float32)), num_subsets)
+        super().__init__(in_channels, out_channels, torch.from_numpy(np.asarray(adj, dtype=np.float32)), num_subsets, attention=attention)
         self.inter_channels, self.num_subsets = self.embedding_channels, num_subsets
 
 
@@ -143,9 +161,10 @@ class SpatialTemporalConv(nn.Module):
     _GCN, _TCN = SpatialGraphConv, TemporalConv
 
     def __init__(self, in_channels, out_channels, adj, stride=1, residual=True, static_adjacency: bool = False,
-                 fused_spatial: bool = True):
+                 fused_spatial: bool = True, attention: bool = False):
         super().__init__()
-        self.gcn1 = self._GCN(in_channels, out_channels, adj)
+        # (attention=False: the graph convolution is constructed exactly as before -- no module, no random draw, no state-dict key)
+        self.gcn1 = self._GCN(in_channels, out_channels, adj, attention=True) if attention else self._GCN(in_channels, out_channels, adj)
         self.tcn1 = self._TCN(out_channels, out_channels, stride=stride)
         self.out_channels = out_channels
         kind = residual_kind(in_channels, out_channels, stride, residual)
@@ -153,7 +172,7 @@ class SpatialTemporalConv(nn.Module):
                          "conv": lambda: self._TCN(in_channels, out_channels, kernel_size=1, stride=stride)}[kind]()
         self.cfg = BlockConfig(cin=in_channels, cout=out_channels, stride=stride, residual=kind,
                                has_down=in_channels != out_channels, static_adjacency=static_adjacency,
-                               fused_spatial=fused_spatial)
+                               fused_spatial=fused_spatial, attention=attention)
         self.cfg.validate()
         self._wcache = None          # ((math mode, parameter addresses), packing.PackedWeights)
         self._wversions = None       # parameter versions the packed contents were built from
@@ -290,13 +309,15 @@ class Model(nn.Module):
 
     def __init__(self, data_shape: tuple, num_classes: int, graph, num_layers: int = 10, start_feature_size: int = 64,
                  without_fc=False, dropout: float = 0., static_adjacency: bool = False, fused_spatial: bool = True,
-                 adjacency_matrix: Optional[np.ndarray] = None):
+                 adjacency_matrix: Optional[np.ndarray] = None, attention: bool = False):
         super().__init__()
         # data_shape = (num_persons, num_frames, num_joints, num_channels)
         num_persons, _, num_joints, num_channels = data_shape
         adj = adjacency_matrix if adjacency_matrix is not None else GraphPartitionStrategy().get_adjacency_matrix_array(graph)
         self.data_bn = nn.BatchNorm1d(num_persons * num_channels * num_joints)
         kw = dict(static_adjacency=static_adjacency, fused_spatial=fused_spatial)
+        if attention:                # MS-AAGCN's STC attention in every block (model_args `attention: true`)
+            kw["attention"] = True
         # all ten blocks are constructed (and draw their initial weights) before the list is cut to num_layers, as in the
         # reference (:152-164): a shorter model built from the same seed then starts from the same parameters, `fc` included
         blocks, cin = [], num_channels

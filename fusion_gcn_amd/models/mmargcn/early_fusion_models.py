@@ -28,7 +28,7 @@ from .rgb_feature_models import agcn_kwargs
 
 # model_args the reference forwards to agcn.Model (defaults are agcn.Model's own), plus this build's block switches
 _FORWARDED = ("num_layers", "without_fc")
-_BUILD_SWITCHES = ("static_adjacency", "fused_spatial")
+_BUILD_SWITCHES = ("static_adjacency", "fused_spatial", "attention")
 
 
 class _AgcnBehindAdapter(nn.Module):

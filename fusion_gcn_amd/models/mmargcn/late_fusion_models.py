@@ -23,7 +23,7 @@ class SkeletonImuGCN(nn.Module):
         self.imu_gcn = imu_models.ImuGCN(data_shape, num_classes, **{**kwargs, "inter_signal_back_connections": True,
                                                                    "include_additional_top_layer": True, "without_fc": True})
         self.agcn = agcn.Model(data_shape["skeleton"], num_classes, graph, num_layers=kwargs.get("num_layers", 10),
-                               without_fc=True, dropout=kwargs.get("dropout", 0.))
+                               without_fc=True, dropout=kwargs.get("dropout", 0.), attention=kwargs.get("attention", False))
         self.fusion = get_fusion(fusion_type, concatenate_dim=-1)
         branches = 2 if fusion_type == "concatenate" else 1
         self.fc = nn.Linear(branches * self.agcn.out_channels, num_classes)

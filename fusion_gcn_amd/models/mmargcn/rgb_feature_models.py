@@ -16,7 +16,7 @@ from . import agcn
 
 
 def agcn_kwargs(kwargs) -> dict:
-    return dict(num_layers=kwargs.get("num_layers", 10), without_fc=kwargs.get("without_fc", False))
+    return dict(num_layers=kwargs.get("num_layers", 10), without_fc=kwargs.get("without_fc", False), attention=kwargs.get("attention", False))
 
 
 def groups_graph(edges) -> Graph:

@@ -2387,3 +2387,151 @@ def fuse_sweep(scores: Sequence[torch.Tensor], candidates, labels: torch.Tensor,
     check(_lib.load().fgcn_fuse_sweep(ctypes.byref(arg), S, mode, cand.data_ptr(), G, labels.data_ptr(), rows, classes, int(k),
                                       counts.data_ptr(), _stream()), "fgcn_fuse_sweep")
     return counts[_lib.FUSE_HEADER:].view(G, 2), counts[:_lib.FUSE_HEADER]
+
+
+# ---- STC attention (fgcn_stc.hip; include/fgcn.h, "STC attention") --------------------------------------------------------------------
+STC_PARAMS = ("conv_sa.weight", "conv_sa.bias", "conv_ta.weight", "conv_ta.bias", "fc1c.weight", "fc1c.bias", "fc2c.weight", "fc2c.bias")
+STC_TA_TAPS = 9
+
+
+def stc_sa_kernel(V: int) -> int:
+    """taps of the spatial gate's convolution over V joints: the largest odd number <= V"""
+    return V if V % 2 else V - 1
+
+
+def stc_param_shapes(C: int, V: int) -> Tuple[Tuple[int, ...], ...]:
+    """the shapes of ``STC_PARAMS`` for C channels on a graph of V joints"""
+    return ((1, C, stc_sa_kernel(V)), (1,), (1, C, STC_TA_TAPS), (1,), (C // 2, C), (C // 2,), (C, C // 2), (C,))
+
+
+def _stc_dims(g: torch.Tensor, name: str) -> Tuple[int, int, int, int]:
+    _chk(g, name)
+    if g.dim() != 4:
+        raise _lib.FgcnError(f"{name}: expected (B, T, V, C), got {tuple(g.shape)}")
+    return tuple(g.shape)
+
+
+def _stc_params(params: Sequence[torch.Tensor], C: int, V: int, name: str) -> List[torch.Tensor]:
+    params = [p.detach() for p in params]
+    shapes = stc_param_shapes(C, V)
+    if len(params) != len(shapes):
+        raise _lib.FgcnError(f"{name}: expected the {len(shapes)} tensors {', '.join(STC_PARAMS)}")
+    for p, shape, key in zip(params, shapes, STC_PARAMS):
+        _chk(p, f"{name}.{key}")
+        if tuple(p.shape) != shape:
+            raise _lib.FgcnError(f"{name}: {key} is {tuple(p.shape)}, expected {shape} for {C} channels and {V} joints")
+    return params
+
+
+def stc_mean_t(g: torch.Tensor) -> torch.Tensor:
+    """forward pass (a): mt (B, V, C) = mean_t g"""
+    ensure_device()
+    B, T, V, C = _stc_dims(g, "stc_mean_t.g")
+    mt = torch.empty((B, V, C), device=g.device, dtype=torch.float32)
+    check(_lib.load().fgcn_stc_mean_t(_p(g), _p(mt), B, T, V, C, _stream()), "fgcn_stc_mean_t")
+    return mt
+
+
+def stc_gate_s(mt: torch.Tensor, w_sa: torch.Tensor, b_sa: torch.Tensor) -> torch.Tensor:
+    """s (B, V) = sigmoid(conv_sa(mt))"""
+    B, V, C = mt.shape
+    s = torch.empty((B, V), device=mt.device, dtype=torch.float32)
+    check(_lib.load().fgcn_stc_gate_s(_p(mt), _p(w_sa), _p(b_sa), _p(s), B, V, C, _stream()), "fgcn_stc_gate_s")
+    return s
+
+
+def stc_mean_v(g: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """forward pass (b): m (B, T, C) = mean_v g (1 + s)"""
+    B, T, V, C = g.shape
+    m = torch.empty((B, T, C), device=g.device, dtype=torch.float32)
+    check(_lib.load().fgcn_stc_mean_v(_p(g), _p(s), _p(m), B, T, V, C, _stream()), "fgcn_stc_mean_v")
+    return m
+
+
+def stc_gates_tc(m: torch.Tensor, w_ta, b_ta, w1, b1, w2, b2):
+    """-> tg (B, T), cm (B, C), h (B, C / 2), cg (B, C): the temporal and the channel gate from m, one workgroup per sample"""
+    B, T, C = m.shape
+    new = lambda *shape: torch.empty(shape, device=m.device, dtype=torch.float32)  # noqa: E731
+    tg, cm, h, cg = new(B, T), new(B, C), new(B, C // 2), new(B, C)
+    check(_lib.load().fgcn_stc_gates_tc(_p(m), _p(w_ta), _p(b_ta), _p(w1), _p(b1), _p(w2), _p(b2), _p(tg), _p(cm), _p(h), _p(cg), B, T, C,
+                                        _stream()), "fgcn_stc_gates_tc")
+    return tg, cm, h, cg
+
+
+def stc_apply(g: torch.Tensor, s: torch.Tensor, tg: torch.Tensor, cg: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """forward pass (c): out = g (1 + s)(1 + tg)(1 + cg)"""
+    B, T, V, C = g.shape
+    if out is None:
+        out = torch.empty((B, T, V, C), device=g.device, dtype=torch.float32)
+    check(_lib.load().fgcn_stc_apply(_p(g), _p(s), _p(tg), _p(cg), _p(out), B, T, V, C, _stream()), "fgcn_stc_apply")
+    return out
+
+
+def stc_forward(g: torch.Tensor, params: Sequence[torch.Tensor]):
+    """The STC attention module: g (B, T, V, C) float32, ``params`` the eight tensors of ``STC_PARAMS`` -> (g', saved): three passes over g
+    and two launches of one workgroup per sample; ``saved`` holds the gates and the means the backward reads (``stc_backward``)."""
+    ensure_device()
+    B, T, V, C = _stc_dims(g, "stc_forward.g")
+    w_sa, b_sa, w_ta, b_ta, w1, b1, w2, b2 = _stc_params(params, C, V, "stc_forward")
+    mt = stc_mean_t(g)
+    s = stc_gate_s(mt, w_sa, b_sa)
+    m = stc_mean_v(g, s)
+    tg, cm, h, cg = stc_gates_tc(m, w_ta, b_ta, w1, b1, w2, b2)
+    return stc_apply(g, s, tg, cg), dict(mt=mt, s=s, m=m, tg=tg, cm=cm, h=h, cg=cg)
+
+
+def stc_bwd_qr(dout: torch.Tensor, g: torch.Tensor, s: torch.Tensor, tg: torch.Tensor):
+    """backward pass (A): -> q (B, T, C) = sum_v p (1 + s) and the per-split terms (B, splits, V, C) of r = sum_t p (1 + tg), p = dout g"""
+    B, T, V, C = g.shape
+    lib = _lib.load()
+    q = torch.empty((B, T, C), device=g.device, dtype=torch.float32)
+    rpart = torch.empty((B, lib.fgcn_stc_splits(B, T), V, C), device=g.device, dtype=torch.float32)
+    check(lib.fgcn_stc_bwd_qr(_p(dout), _p(g), _p(s), _p(tg), _p(q), _p(rpart), B, T, V, C, _stream()), "fgcn_stc_bwd_qr")
+    return q, rpart
+
+
+def stc_bwd_ds(dm: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """backward pass (B): the per-split terms (B, splits, V) of sum_{t, c} dm g"""
+    B, T, V, C = g.shape
+    lib = _lib.load()
+    dspart = torch.empty((B, lib.fgcn_stc_splits(B, T), V), device=g.device, dtype=torch.float32)
+    check(lib.fgcn_stc_bwd_ds(_p(dm), _p(g), _p(dspart), B, T, V, C, _stream()), "fgcn_stc_bwd_ds")
+    return dspart
+
+
+def stc_bwd_apply(dout: torch.Tensor, s, tg, cg, dm: torch.Tensor, dmt: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """backward pass (C): out = dout (1 + s)(1 + tg)(1 + cg) + dm (1 + s) / V + dmt / T  (``out`` may be ``dout``)"""
+    B, T, V, C = dout.shape
+    if out is None:
+        out = torch.empty((B, T, V, C), device=dout.device, dtype=torch.float32)
+    check(_lib.load().fgcn_stc_bwd_apply(_p(dout), _p(s), _p(tg), _p(cg), _p(dm), _p(dmt), _p(out), B, T, V, C, _stream()), "fgcn_stc_bwd_apply")
+    return out
+
+
+def stc_backward(dout: torch.Tensor, g: torch.Tensor, saved: dict, params: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None):
+    """Backward of ``stc_forward``: dout = the gradient of g', g the module's INPUT, ``saved`` the forward's dict -> (dg, the eight parameter
+    gradients in ``STC_PARAMS`` order, each in its parameter's shape).  ``out``: where dg goes (it may be ``dout``).  Three passes over the
+    activation-sized tensors, two launches of one workgroup per sample and one for the parameter gradients; fixed-order sums."""
+    ensure_device()
+    B, T, V, C = _stc_dims(g, "stc_backward.g")
+    _chk(dout, "stc_backward.dout")
+    if tuple(dout.shape) != (B, T, V, C) or (out is not None and (tuple(out.shape) != (B, T, V, C) or out.dtype != torch.float32 or not out.is_contiguous())):
+        raise _lib.FgcnError(f"stc_backward: dout {tuple(dout.shape)} / out against g {tuple(g.shape)}")
+    w_sa, _, w_ta, _, w1, _, w2, _ = P = _stc_params(params, C, V, "stc_backward")
+    mt, s, m, tg, cm, h, cg = (saved[k] for k in ("mt", "s", "m", "tg", "cm", "h", "cg"))
+    lib, k = _lib.load(), stc_sa_kernel(V)
+    new = lambda *shape: torch.empty(shape, device=g.device, dtype=torch.float32)  # noqa: E731
+    q, rpart = stc_bwd_qr(dout, g, s, tg)
+    dzc, dhpre, dcm, dzt, dm = new(B, C), new(B, C // 2), new(B, C), new(B, T), new(B, T, C)
+    dwta_part, dbta_part = new(B, C, STC_TA_TAPS), new(B)
+    check(lib.fgcn_stc_bwd_tc(_p(q), _p(m), _p(tg), _p(cg), _p(cm), _p(h), _p(w_ta), _p(w1), _p(w2), _p(dzc), _p(dhpre), _p(dcm), _p(dzt), _p(dm),
+                              _p(dwta_part), _p(dbta_part), B, T, C, _stream()), "fgcn_stc_bwd_tc")
+    dspart = stc_bwd_ds(dm, g)
+    dzs, dmt, dwsa_part, dbsa_part = new(B, V), new(B, V, C), new(B, C, k), new(B)
+    check(lib.fgcn_stc_bwd_s(_p(rpart), _p(dspart), _p(cg), _p(s), _p(mt), _p(w_sa), _p(dzs), _p(dmt), _p(dwsa_part), _p(dbsa_part), B, T, V, C,
+                             _stream()), "fgcn_stc_bwd_s")
+    dg = stc_bwd_apply(dout, s, tg, cg, dm, dmt, out)
+    grads = [torch.empty_like(p) for p in P]
+    check(lib.fgcn_stc_param_grads(_p(dzc), _p(dhpre), _p(cm), _p(h), _p(dwta_part), _p(dbta_part), _p(dwsa_part), _p(dbsa_part),
+                                   *(_p(t) for t in grads), B, V, C, _stream()), "fgcn_stc_param_grads")
+    return dg, grads

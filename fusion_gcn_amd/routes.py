@@ -149,12 +149,15 @@ def plan_block(cfg, B: int, T: int, V: int, *, x_bf16: bool, train: bool, infere
     # weight gradient (tap counts it is built for).  (The inline code asked the two routes without V here, a wide graph already excluded.)
     pad = (kt - 1) // 2
     per_pass = [kt] if s == 1 else [len([j for j in range(kt) if (j - pad) % s == par]) for par in range(s)]
-    g_bf16 = bool(half_storage and kt > 1 and not wide and t_fwd != "rows" and t_dgrad != "rows"
+    # An attention block (BlockConfig.attention) keeps G, G', dU and dG float32 and forms G in a pass of its own: the STC kernels between
+    # the graph convolution and the temporal conv are float32, and fuse_g / bn_sums_in_dgrad fuse across the place where the gate sits
+    att = bool(getattr(cfg, "attention", False))
+    g_bf16 = bool(not att and half_storage and kt > 1 and not wide and t_fwd != "rows" and t_dgrad != "rows"
                   and all(n in ops.TWGRAD_TAPS_SPLIT for n in per_pass if n))
     g_sign = staged and (rows * cout) % 8 == 0
     # (the conv's fused input stage exists with the bf16x3 / bf16 products only: fgcn_tconv_halo refuses it with the f16x2 products, whose
     # BatchNorm-sums epilogue -- halo_sums -- does exist)
-    fuse_g = bool(staged and o.fuse_g and not f16x2 and not g_bf16 and not ha and not cfg.has_down and halo9 and halo_sums
+    fuse_g = bool(not att and staged and o.fuse_g and not f16x2 and not g_bf16 and not ha and not cfg.has_down and halo9 and halo_sums
                   and cin == cout and V <= 32 and (rows * cout) % 8 == 0)
     if g_bf16 and not g_sign:    # (no sign image: the backward would gate on g itself, which it reads as f32 -- cout % 64 == 0 rules it out)
         raise ops._lib.FgcnError("half-precision storage of G needs the sign image (element count a multiple of 8)")
@@ -180,7 +183,7 @@ def plan_block(cfg, B: int, T: int, V: int, *, x_bf16: bool, train: bool, infere
     # the kernel that forms the spatial term of dx adds both from their sign images
     gate_in_dagg = bool((o.gated_shortcuts_tile if bwd_tile else o.gated_shortcuts) and o.fused_dagg and not wide and not cfg.has_down
                         and cfg.residual == "identity" and cin == cfg.cin and cout % 8 == 0 and o_sign and g_sign and fits32(o_numel))
-    bn_sums = bool(o.get("bn_sums_in_dgrad", mode) and cout <= o.bn_sums_max_c and train and s == 1 and not cfg.has_down and g_sign
+    bn_sums = bool(not att and o.get("bn_sums_in_dgrad", mode) and cout <= o.bn_sums_max_c and train and s == 1 and not cfg.has_down and g_sign
                    and "t_t4" in forms and halo_sums and not wide)
     # dG: written by the temporal data gradient's halo kernel from a bfloat16 dU; not when that kernel's epilogue carries the BatchNorm sums
     dg_bf16 = bool(ha and g_bf16 and t_dgrad != "rows" and not bn_sums and g_sign)

@@ -1392,6 +1392,55 @@ int fgcn_score_fuse(const FgcnFuseIn* in, int S, int transform, float* out, int 
 int fgcn_fuse_sweep(const FgcnFuseIn* in, int S, int transform, const float* candidates, int G, const long long* labels, int rows,
                     int classes, int k, unsigned long long* counts, void* stream);
 
+/* STC attention: the spatial-temporal-channel attention module of MS-AAGCN (Shi et al., TIP 2020) between the graph convolution and the
+ * temporal convolution of an AGCN block (ops.stc_*, fops.stc_attention, BlockConfig.attention).
+ *
+ * G (B, T, V, C) float32 channels-last, contiguous; C a multiple of 64, V <= FGCN_MAX_V_WIDE, B <= 65535, T * V * C < 2^31.  With sg =
+ * the logistic sigmoid, k = V for an odd V and V - 1 otherwise, p = (k - 1) / 2, and the parameters in torch's layouts -- w_sa (1, C, k),
+ * b_sa (1), w_ta (1, C, 9), b_ta (1), w1 (C / 2, C), b1 (C / 2), w2 (C, C / 2), b2 (C):
+ *     mt[b, v, c] = mean_t G                      s[b, v]  = sg(b_sa + sum_{c, j} w_sa[c, j] mt[b, v + j - p, c])    (zero beyond the joints)
+ *     m[b, t, c]  = mean_v G (1 + s[b, v])        tg[b, t] = sg(b_ta + sum_{c, j} w_ta[c, j] m[b, t + j - 4, c])     (zero beyond the frames)
+ *     cm[b, c]    = mean_t (1 + tg[b, t]) m       h = relu(w1 cm + b1)       cg = sg(w2 h + b2)
+ *     G'          = ((G (1 + s[b, v])) (1 + tg[b, t])) (1 + cg[b, c])
+ * Forward: fgcn_stc_mean_t (mt), fgcn_stc_gate_s (s), fgcn_stc_mean_v (m), fgcn_stc_gates_tc (tg, cm, h, cg), fgcn_stc_apply (G'; out may
+ * be g).  Three passes over G, two launches of one workgroup per sample.  No kernel reads another sample's data.
+ *
+ * Backward, with dG' = dout and p = dG' G:
+ *     fgcn_stc_bwd_qr     q[b, t, c] = sum_v p (1 + s), and rpart (B, fgcn_stc_splits(B, T), V, C): the per-split terms of
+ *                         r[b, v, c] = sum_t p (1 + tg)                                                       one pass over dout and g
+ *     fgcn_stc_bwd_tc     one workgroup per sample: dzc (B, C), dhpre (B, C / 2), dcm (B, C) -- the gradients at w2 h + b2, w1 cm + b1 and
+ *                         cm --, dzt (B, T) at conv_ta's output, dm (B, T, C) = dcm (1 + tg) / T + conv_ta^T dzt, and the sample's terms of
+ *                         conv_ta's gradients dwta_part (B, C, 9), dbta_part (B)
+ *     fgcn_stc_bwd_ds     dspart (B, fgcn_stc_splits(B, T), V): the per-split terms of sum_{t, c} dm G            one pass over g
+ *     fgcn_stc_bwd_s      one workgroup per sample: dzs (B, V) at conv_sa's output from sum_c (1 + cg) r + (sum_{t, c} dm G) / V,
+ *                         dmt (B, V, C) = conv_sa^T dzs, the sample's terms dwsa_part (B, C, k), dbsa_part (B)
+ *     fgcn_stc_bwd_apply  dg = dout (1 + s)(1 + tg)(1 + cg) + dm (1 + s) / V + dmt / T                            (dg may be dout)
+ *     fgcn_stc_param_grads  the eight parameter gradients in the parameters' layouts: sums over the samples, in sample order
+ * Every sum has an order fixed by (B, T, V, C) alone; no atomics; two calls give the same bits.  Nothing is skipped on a value: a NaN
+ * reaches the sums the definition gives it and no other ("Non-finite values in the inputs").  The ReLU's gate is that of relu_open.
+ * FGCN_E_BADARG before any launch: a null pointer, a size outside the limits above.  FGCN_E_ALIGN: a tensor that is read or written in
+ * 16-byte groups (g, out, dout, dg, mt, m, cg, dm, dmt) not 16-byte aligned.  fgcn_stc_splits: host only; 0 for B <= 0 or T <= 0. */
+int fgcn_stc_splits(int B, int T);
+int fgcn_stc_mean_t(const float* g, float* mt, int B, int T, int V, int C, void* stream);
+int fgcn_stc_gate_s(const float* mt, const float* w_sa, const float* b_sa, float* s, int B, int V, int C, void* stream);
+int fgcn_stc_mean_v(const float* g, const float* s, float* m, int B, int T, int V, int C, void* stream);
+int fgcn_stc_gates_tc(const float* m, const float* w_ta, const float* b_ta, const float* w1, const float* b1, const float* w2, const float* b2,
+                      float* tg, float* cm, float* h, float* cg, int B, int T, int C, void* stream);
+int fgcn_stc_apply(const float* g, const float* s, const float* tg, const float* cg, float* out, int B, int T, int V, int C, void* stream);
+int fgcn_stc_bwd_qr(const float* dout, const float* g, const float* s, const float* tg, float* q, float* rpart, int B, int T, int V, int C,
+                    void* stream);
+int fgcn_stc_bwd_tc(const float* q, const float* m, const float* tg, const float* cg, const float* cm, const float* h, const float* w_ta,
+                    const float* w1, const float* w2, float* dzc, float* dhpre, float* dcm, float* dzt, float* dm, float* dwta_part,
+                    float* dbta_part, int B, int T, int C, void* stream);
+int fgcn_stc_bwd_ds(const float* dm, const float* g, float* dspart, int B, int T, int V, int C, void* stream);
+int fgcn_stc_bwd_s(const float* rpart, const float* dspart, const float* cg, const float* s, const float* mt, const float* w_sa, float* dzs,
+                   float* dmt, float* dwsa_part, float* dbsa_part, int B, int T, int V, int C, void* stream);
+int fgcn_stc_bwd_apply(const float* dout, const float* s, const float* tg, const float* cg, const float* dm, const float* dmt, float* dg, int B,
+                       int T, int V, int C, void* stream);
+int fgcn_stc_param_grads(const float* dzc, const float* dhpre, const float* cm, const float* h, const float* dwta_part, const float* dbta_part,
+                         const float* dwsa_part, const float* dbsa_part, float* d_wsa, float* d_bsa, float* d_wta, float* d_bta, float* d_w1,
+                         float* d_b1, float* d_w2, float* d_b2, int B, int V, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
