@@ -243,6 +243,16 @@ SIGNATURES = {
     "fgcn_stc_bwd_s": (_I, [_P] * 10 + [_I] * 4 + [_P]),
     "fgcn_stc_bwd_apply": (_I, [_P] * 7 + [_I] * 4 + [_P]),
     "fgcn_stc_param_grads": (_I, [_P] * 16 + [_I] * 3 + [_P]),
+    "fgcn_ctr_chunk": (_I, []),
+    "fgcn_ctr_split_frames": (_I, [_I] * 4),
+    "fgcn_ctr_mean_t": (_I, [_P] * 2 + [_I] * 4 + [_P]),
+    "fgcn_ctr_mean_t_bwd": (_I, [_P] * 2 + [_I] * 5 + [_P]),
+    "fgcn_ctr_tanh": (_I, [_P] * 2 + [_I] * 3 + [_P]),
+    "fgcn_ctr_aggregate": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "fgcn_ctr_bwd_dx3": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "fgcn_ctr_bwd_da": (_I, [_P] * 3 + [_I] * 4 + [_P]),
+    "fgcn_ctr_bwd_small": (_I, [_P] * 11 + [_I] * 4 + [_P]),
+    "fgcn_ctr_param_grads": (_I, [_P] * 9 + [_I] * 4 + [_P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

@@ -884,4 +884,78 @@ def stc_attention(g: torch.Tensor, conv_sa: torch.nn.Conv1d, conv_ta: torch.nn.C
     return _StcAttention.apply(g, conv_sa.weight, conv_sa.bias, conv_ta.weight, conv_ta.bias, fc1c.weight, fc1c.bias, fc2c.weight, fc2c.bias)
 
 
+class _CtrMeanT(torch.autograd.Function):
+    """xm (B, V, C) = mean_t x of x (B, T, V, C), C any multiple of 4 (ops.ctr_mean_t); the backward broadcasts dxm / T over the frames"""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.T = x.shape[1]
+        return ops.ctr_mean_t(x)
+
+    @staticmethod
+    def backward(ctx, d_xm):
+        return ops.ctr_mean_t_bwd(d_xm.contiguous(), ctx.T)
+
+
+def ctr_mean_t(x: torch.Tensor) -> torch.Tensor:
+    return _CtrMeanT.apply(x.contiguous())
+
+
+class _CtrAggregate(torch.autograd.Function):
+    """y = sum_k A'_k x3_k with CTR-GC's refined topology (include/fgcn.h, "CTR graph convolution"): ops.ctr_forward / ops.ctr_backward.
+    Kept for the backward: the inputs and th = tanh(x1 - x2) (B, K, V, V, R); A' itself is formed again on chip."""
+
+    @staticmethod
+    def forward(ctx, x3, x12, w4, b4, alpha, pa):
+        y, th = ops.ctr_forward(x3, x12, w4, b4, alpha, pa)
+        ctx.save_for_backward(x3, th, w4, b4, alpha, pa)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        x3, th, w4, b4, alpha, pa = ctx.saved_tensors
+        dx3, dx12, d_w4, d_b4, d_alpha, d_pa = ops.ctr_backward(d_y.contiguous(), x3, th, w4, b4, alpha, pa)
+        return dx3, dx12, d_w4, d_b4, d_alpha, (d_pa if ctx.needs_input_grad[5] else None)
+
+
+def ctr_aggregate(x3: torch.Tensor, x12: torch.Tensor, w4: torch.Tensor, b4: torch.Tensor, alpha: torch.Tensor, pa: torch.Tensor) -> torch.Tensor:
+    """Differentiable aggregation of CTR-GCN's graph convolution, all float32 channels-last: x3 (B, T, V, 3 Cout) = the three conv3_k(x),
+    x12 (B, V, 6 R) = the three conv1_k(xm) then the three conv2_k(xm) of xm = mean_t x, w4 (3, Cout, R), b4 (3, Cout), alpha (1),
+    pa (3, V, V) -> y (B, T, V, Cout).  V <= 32, Cout in 64s up to 512, R in 4s up to 64; anything else raises."""
+    return _CtrAggregate.apply(x3.contiguous(), x12.contiguous(), w4.contiguous(), b4.contiguous(), alpha.contiguous(), pa.contiguous())
+
+
+class _CtrAggregateConvs(torch.autograd.Function):
+    """_CtrAggregate on the three subsets' conv4 parameters: w4 (3, Cout, R) and b4 (3, Cout) are gathered here, and the gradients come
+    back per parameter in the parameter's shape.  Inputs: x3, x12, alpha, pa, then the three weights (Cout, R, 1, 1), then the three biases."""
+
+    @staticmethod
+    def forward(ctx, x3, x12, alpha, pa, *wb):
+        K = len(wb) // 2
+        C, R = wb[0].shape[0], wb[0].shape[1]
+        w4 = torch.empty((K, C, R), device=x3.device, dtype=torch.float32)
+        b4 = torch.empty((K, C), device=x3.device, dtype=torch.float32)
+        for k in range(K):
+            w4[k].copy_(wb[k].detach().reshape(C, R))
+            b4[k].copy_(wb[K + k].detach())
+        y, th = ops.ctr_forward(x3, x12, w4, b4, alpha, pa)
+        ctx.save_for_backward(x3, th, w4, b4, alpha, pa)
+        ctx.shapes = [tuple(t.shape) for t in wb]
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        x3, th, w4, b4, alpha, pa = ctx.saved_tensors
+        dx3, dx12, d_w4, d_b4, d_alpha, d_pa = ops.ctr_backward(d_y.contiguous(), x3, th, w4, b4, alpha, pa)
+        K = len(ctx.shapes) // 2
+        return (dx3, dx12, d_alpha, (d_pa if ctx.needs_input_grad[3] else None), *(d_w4[k].view(ctx.shapes[k]) for k in range(K)),
+                *(d_b4[k] for k in range(K)))
+
+
+def ctr_aggregate_convs(x3: torch.Tensor, x12: torch.Tensor, conv4s: Sequence[torch.nn.Conv2d], alpha: torch.Tensor, pa: torch.Tensor) -> torch.Tensor:
+    """``ctr_aggregate`` with w4 / b4 given as the three subsets' ``conv4`` modules (parameter containers)"""
+    return _CtrAggregateConvs.apply(x3.contiguous(), x12.contiguous(), alpha.contiguous(), pa.contiguous(), *[c.weight for c in conv4s],
+                                    *[c.bias for c in conv4s])
+
+
 ops.bind_all_functions(globals())     # every Function's backward runs in its forward's library context (ops.Context)

@@ -2535,3 +2535,105 @@ def stc_backward(dout: torch.Tensor, g: torch.Tensor, saved: dict, params: Seque
     check(lib.fgcn_stc_param_grads(_p(dzc), _p(dhpre), _p(cm), _p(h), _p(dwta_part), _p(dbta_part), _p(dwsa_part), _p(dbsa_part),
                                    *(_p(t) for t in grads), B, V, C, _stream()), "fgcn_stc_param_grads")
     return dg, grads
+
+
+# ---- CTR graph convolution (fgcn_ctr.hip; include/fgcn.h, "CTR graph convolution") -----------------------------------------------------
+CTR_K = 3
+
+
+def ctr_reduction(in_channels: int) -> int:
+    """R, the width of CTR-GC's two embeddings: 8 for the 3 (or 9) channel input, else a eighth of the input width"""
+    return 8 if in_channels in (3, 9) else in_channels // 8
+
+
+def ctr_geometry(B: int, T: int, V: int, Cout: int) -> Tuple[int, int, int]:
+    """-> (frame splits, frames per split, frames per LDS chunk) of ``ctr_aggregate`` / ``ctr_bwd_dx3`` (host only)"""
+    lib = _lib.load()
+    fps = lib.fgcn_ctr_split_frames(B, T, V, Cout)
+    if fps <= 0:
+        raise _lib.FgcnError(f"ctr_geometry: no geometry for (B, T, V, Cout) = {(B, T, V, Cout)}")
+    return (T + fps - 1) // fps, fps, lib.fgcn_ctr_chunk()
+
+
+def ctr_mean_t(x: torch.Tensor) -> torch.Tensor:
+    """xm (B, V, C) = mean_t x, x (B, T, V, C) with C any multiple of 4"""
+    ensure_device()
+    B, T, V, C = _stc_dims(x, "ctr_mean_t.x")
+    xm = torch.empty((B, V, C), device=x.device, dtype=torch.float32)
+    check(_lib.load().fgcn_ctr_mean_t(_p(x), _p(xm), B, T, V, C, _stream()), "fgcn_ctr_mean_t")
+    return xm
+
+
+def ctr_mean_t_bwd(dxm: torch.Tensor, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx (B, T, V, C) = dxm / T in every frame; ``out``: a gradient the broadcast is ADDED to"""
+    ensure_device()
+    _chk(dxm, "ctr_mean_t_bwd.dxm")
+    B, V, C = dxm.shape
+    acc = out is not None
+    if acc:
+        _chk(out, "ctr_mean_t_bwd.out")
+        if tuple(out.shape) != (B, T, V, C):
+            raise _lib.FgcnError(f"ctr_mean_t_bwd: out {tuple(out.shape)} against {(B, T, V, C)}")
+    else:
+        out = torch.empty((B, T, V, C), device=dxm.device, dtype=torch.float32)
+    check(_lib.load().fgcn_ctr_mean_t_bwd(_p(dxm), _p(out), B, T, V, C, int(acc), _stream()), "fgcn_ctr_mean_t_bwd")
+    return out
+
+
+def _ctr_dims(x3: torch.Tensor, x12: torch.Tensor, w4: torch.Tensor, b4: torch.Tensor, alpha: torch.Tensor, pa: torch.Tensor, name: str):
+    for t, key in ((x3, "x3"), (x12, "x12"), (w4, "w4"), (b4, "b4"), (alpha, "alpha"), (pa, "pa")):
+        _chk(t, f"{name}.{key}")
+    if x3.dim() != 4 or w4.dim() != 3 or w4.shape[0] != CTR_K:
+        raise _lib.FgcnError(f"{name}: expected x3 (B, T, V, 3 Cout) and w4 (3, Cout, R), got {tuple(x3.shape)} and {tuple(w4.shape)}")
+    B, T, V, KC = x3.shape
+    _, C, R = w4.shape
+    if KC != CTR_K * C or tuple(x12.shape) != (B, V, 2 * CTR_K * R) or tuple(b4.shape) != (CTR_K, C) or alpha.numel() != 1 \
+            or tuple(pa.shape) != (CTR_K, V, V):
+        raise _lib.FgcnError(f"{name}: x3 {tuple(x3.shape)}, x12 {tuple(x12.shape)}, w4 {tuple(w4.shape)}, b4 {tuple(b4.shape)}, alpha "
+                             f"{tuple(alpha.shape)}, pa {tuple(pa.shape)} do not describe one CTR graph convolution")
+    return B, T, V, C, R
+
+
+def ctr_tanh(x12: torch.Tensor, R: int) -> torch.Tensor:
+    """th (B, K, V, V, R) = tanh(x1_k[b, u] - x2_k[b, v]) from x12 (B, V, 2 K R)"""
+    B, V, _ = x12.shape
+    th = torch.empty((B, CTR_K, V, V, R), device=x12.device, dtype=torch.float32)
+    check(_lib.load().fgcn_ctr_tanh(_p(x12), _p(th), B, V, R, _stream()), "fgcn_ctr_tanh")
+    return th
+
+
+def ctr_forward(x3: torch.Tensor, x12: torch.Tensor, w4: torch.Tensor, b4: torch.Tensor, alpha: torch.Tensor, pa: torch.Tensor):
+    """CTR-GC's aggregation y[b, t, u, c] = sum_k sum_v A'_k[b, u, v, c] x3[b, t, v, k Cout + c] with the refined topology A' formed on chip
+    (include/fgcn.h, "CTR graph convolution") -> (y (B, T, V, Cout), th): ``th`` is what the backward keeps beside the inputs."""
+    ensure_device()
+    B, T, V, C, R = _ctr_dims(x3, x12, w4, b4, alpha, pa, "ctr_forward")
+    lib = _lib.load()
+    th = ctr_tanh(x12, R)
+    y = torch.empty((B, T, V, C), device=x3.device, dtype=torch.float32)
+    check(lib.fgcn_ctr_aggregate(_p(x3), _p(th), _p(w4), _p(b4), _p(alpha), _p(pa), _p(y), B, T, V, C, R, _stream()), "fgcn_ctr_aggregate")
+    return y, th
+
+
+def ctr_backward(dy: torch.Tensor, x3: torch.Tensor, th: torch.Tensor, w4: torch.Tensor, b4: torch.Tensor, alpha: torch.Tensor, pa: torch.Tensor):
+    """Backward of ``ctr_forward`` -> (dx3, dx12, d_w4, d_b4, d_alpha, d_pa).  dA' (B, K, V, V, Cout) is written once and read by the
+    one-workgroup-per-(sample, subset) kernel; the cross-sample sums are one launch, samples in sample order."""
+    ensure_device()
+    _chk(dy, "ctr_backward.dy")
+    B, T, V, KC = x3.shape
+    _, C, R = w4.shape
+    if tuple(dy.shape) != (B, T, V, C):
+        raise _lib.FgcnError(f"ctr_backward: dy {tuple(dy.shape)} against {(B, T, V, C)}")
+    lib = _lib.load()
+    new = lambda *shape: torch.empty(shape, device=dy.device, dtype=torch.float32)  # noqa: E731
+    dx3 = new(B, T, V, KC)
+    check(lib.fgcn_ctr_bwd_dx3(_p(dy), _p(th), _p(w4), _p(b4), _p(alpha), _p(pa), _p(dx3), B, T, V, C, R, _stream()), "fgcn_ctr_bwd_dx3")
+    da = new(B, CTR_K, V, V, C)
+    check(lib.fgcn_ctr_bwd_da(_p(dy), _p(x3), _p(da), B, T, V, C, _stream()), "fgcn_ctr_bwd_da")
+    dz, dx12 = new(B, CTR_K, V, V, R), new(B, V, 2 * CTR_K * R)
+    s2, s1, dpa_part, dal_part = new(B, CTR_K, C, R), new(B, CTR_K, C), new(B, CTR_K, V, V), new(B, CTR_K)
+    check(lib.fgcn_ctr_bwd_small(_p(da), _p(th), _p(w4), _p(b4), _p(alpha), _p(dz), _p(dx12), _p(s2), _p(s1), _p(dpa_part), _p(dal_part),
+                                 B, V, C, R, _stream()), "fgcn_ctr_bwd_small")
+    d_w4, d_b4, d_pa, d_alpha = new(CTR_K, C, R), new(CTR_K, C), new(CTR_K, V, V), new(*alpha.shape)
+    check(lib.fgcn_ctr_param_grads(_p(s2), _p(s1), _p(dpa_part), _p(dal_part), _p(alpha), _p(d_w4), _p(d_b4), _p(d_pa), _p(d_alpha),
+                                   B, V, C, R, _stream()), "fgcn_ctr_param_grads")
+    return dx3, dx12, d_w4, d_b4, d_alpha, d_pa

@@ -1441,6 +1441,49 @@ int fgcn_stc_param_grads(const float* dzc, const float* dhpre, const float* cm, 
                          const float* dwsa_part, const float* dbsa_part, float* d_wsa, float* d_bsa, float* d_wta, float* d_bta, float* d_w1,
                          float* d_b1, float* d_w2, float* d_b2, int B, int V, int C, void* stream);
 
+/* CTR graph convolution: the channel-wise topology refinement graph convolution of CTR-GCN (Chen et al., ICCV 2021) (ops.ctr_*,
+ * fops.ctr_aggregate / fops.ctr_mean_t, models/ctrgcn).
+ *
+ * All tensors float32, channels-last, contiguous, in every math mode.  K = 3 subsets; x3 (B, T, V, K Cout) holds conv3_k(x) at channel
+ * k Cout + c; x12 (B, V, 2 K R) holds x1_k = conv1_k(xm) at k R + r and x2_k = conv2_k(xm) at (K + k) R + r, xm = mean_t x; w4 (K, Cout, R),
+ * b4 (K, Cout), alpha (1), pa (K, V, V):
+ *     th[b, k, u, v, r]  = tanh(x1_k[b, u, r] - x2_k[b, v, r])                                         (B, K, V, V, R)
+ *     A'_k[b, u, v, c]   = alpha (b4[k, c] + sum_r w4[k, c, r] th[b, k, u, v, r]) + pa[k, u, v]        never written to memory
+ *     y[b, t, u, c]      = sum_k sum_v A'_k[b, u, v, c] x3[b, t, v, k Cout + c]
+ * A' is not symmetric: u is the output joint, v the joint summed over.
+ * Limits: V <= 32, Cout a multiple of 64 up to 512, R a multiple of 4 up to 64, B <= 65535, T V K Cout < 2^31; fgcn_ctr_mean_t(_bwd): C any
+ * multiple of 4 with T V C < 2^31.
+ *
+ * Forward: fgcn_ctr_mean_t (xm), fgcn_ctr_tanh (th), fgcn_ctr_aggregate (y).  Backward, with dy the gradient of y:
+ *     fgcn_ctr_bwd_dx3      dx3[b, t, v, k Cout + c] = sum_u A'_k[b, u, v, c] dy[b, t, u, c]
+ *     fgcn_ctr_bwd_da       da (B, K, V, V, Cout): dA'_k[b, u, v, c] = sum_t dy[b, t, u, c] x3[b, t, v, k Cout + c], all frames in frame order
+ *     fgcn_ctr_bwd_small    one workgroup per (sample, subset): dz (B, K, V, V, R) = alpha (sum_c dA' w4) (1 - th^2), dx12 (dx1 = sum_v dz,
+ *                           dx2 = -sum_u dz), and the sample's terms s2_part (B, K, Cout, R) = sum_{u, v} dA' th, s1_part (B, K, Cout) =
+ *                           sum_{u, v} dA', dpa_part (B, K, V, V) = sum_c dA', dalpha_part (B, K) = <b4, s1> + <w4, s2>
+ *     fgcn_ctr_param_grads  d_pa = sum_b dpa_part, d_w4 = alpha sum_b s2_part, d_b4 = alpha sum_b s1_part, d_alpha = sum dalpha_part: one
+ *                           launch, samples in sample order
+ *     fgcn_ctr_mean_t_bwd   dx[b, t, v, c] = dxm[b, v, c] / T, added to dx when `accumulate`
+ * fgcn_ctr_aggregate and fgcn_ctr_bwd_dx3 split the frames over workgroups, fgcn_ctr_split_frames(B, T, V, Cout) frames each (host only; 0
+ * for sizes outside the limits), and every workgroup of the three walks its frames through LDS in chunks of fgcn_ctr_chunk() frames.
+ * Every sum has an order fixed by the sizes alone; no atomics; two calls give the same bits.  No forward kernel reads another sample's
+ * data.  Nothing is skipped on a value: alpha == 0 still multiplies ("Non-finite values in the inputs").
+ * FGCN_E_BADARG before any launch: a null pointer, a size outside the limits above.  FGCN_E_ALIGN: a tensor that is read or written in
+ * 16-byte groups (x, xm, dxm, dx, x3, th, w4, and dy of fgcn_ctr_bwd_dx3) not 16-byte aligned. */
+int fgcn_ctr_chunk(void);
+int fgcn_ctr_split_frames(int B, int T, int V, int Cout);
+int fgcn_ctr_mean_t(const float* x, float* xm, int B, int T, int V, int C, void* stream);
+int fgcn_ctr_mean_t_bwd(const float* dxm, float* dx, int B, int T, int V, int C, int accumulate, void* stream);
+int fgcn_ctr_tanh(const float* x12, float* th, int B, int V, int R, void* stream);
+int fgcn_ctr_aggregate(const float* x3, const float* th, const float* w4, const float* b4, const float* alpha, const float* pa, float* y,
+                       int B, int T, int V, int Cout, int R, void* stream);
+int fgcn_ctr_bwd_dx3(const float* dy, const float* th, const float* w4, const float* b4, const float* alpha, const float* pa, float* dx3,
+                     int B, int T, int V, int Cout, int R, void* stream);
+int fgcn_ctr_bwd_da(const float* dy, const float* x3, float* da, int B, int T, int V, int Cout, void* stream);
+int fgcn_ctr_bwd_small(const float* da, const float* th, const float* w4, const float* b4, const float* alpha, float* dz, float* dx12,
+                       float* s2_part, float* s1_part, float* dpa_part, float* dalpha_part, int B, int V, int Cout, int R, void* stream);
+int fgcn_ctr_param_grads(const float* s2_part, const float* s1_part, const float* dpa_part, const float* dalpha_part, const float* alpha,
+                         float* d_w4, float* d_b4, float* d_pa, float* d_alpha, int B, int V, int Cout, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
