@@ -253,6 +253,13 @@ SIGNATURES = {
     "fgcn_ctr_bwd_da": (_I, [_P] * 3 + [_I] * 4 + [_P]),
     "fgcn_ctr_bwd_small": (_I, [_P] * 11 + [_I] * 4 + [_P]),
     "fgcn_ctr_param_grads": (_I, [_P] * 9 + [_I] * 4 + [_P]),
+    "fgcn_shift_joint_rows": (_I, [_LL, _I, _I]),
+    "fgcn_shift_joint_stage": (_I, [_I]),
+    "fgcn_shift_frame_split": (_I, [_I] * 5),
+    "fgcn_shift_joint": (_I, [_P] * 5 + [_LL] + [_I] * 5 + [_P]),
+    "fgcn_shift_dmask": (_I, [_P] * 3 + [_I] * 4 + [_P]),
+    "fgcn_shift_frame": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "fgcn_shift_frame_bwd": (_I, [_P] * 5 + [_I] * 6 + [_P]),
 }
 
 # enum fgcn_cls_word: the 8-byte words at the head of a classify state (include/fgcn.h)

@@ -958,4 +958,113 @@ def ctr_aggregate_convs(x3: torch.Tensor, x12: torch.Tensor, conv4s: Sequence[to
                                     *[c.bias for c in conv4s])
 
 
+class _JointShift(torch.autograd.Function):
+    """out[r, v, c] = x[r, (v + dir c) mod V, c] (tanh(mask[v, c]) + 1) (include/fgcn.h, "Shift graph convolution"): ops.joint_shift_forward /
+    ops.joint_shift_backward.  x is kept for the mask's gradient alone."""
+
+    @staticmethod
+    def forward(ctx, x, mask, direction: int):
+        ctx.direction = direction
+        ctx.save_for_backward(x if (mask is not None and mask.requires_grad) else None, mask)
+        return ops.joint_shift_forward(x, mask, direction)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x, mask = ctx.saved_tensors
+        dx, dmask = ops.joint_shift_backward(d_out.contiguous(), x, mask, ctx.direction, need_dmask=x is not None and ctx.needs_input_grad[1])
+        return dx, dmask, None
+
+
+def joint_shift(x: torch.Tensor, mask: Optional[torch.Tensor] = None, direction: int = 1) -> torch.Tensor:
+    """Differentiable joint shift of x (B, T, V, C) float32 channels-last: channel c of joint v takes joint (v + direction c) mod V, times the
+    gate tanh(mask) + 1 of the (V, C) parameter ``mask`` (any shape with V C elements; V 3 for the 4-wide input).  V <= 64, C = 4 or a
+    multiple of 64 up to 512; anything else raises."""
+    return _JointShift.apply(x.contiguous(), None if mask is None else mask.contiguous(), direction)
+
+
+class _FrameShift(torch.autograd.Function):
+    """The learnable, linearly interpolated shift along the frames (include/fgcn.h, "Shift graph convolution"): ops.frame_shift_forward /
+    ops.frame_shift_backward -> (out, BatchNorm partial sums of out or an empty tensor)"""
+
+    @staticmethod
+    def forward(ctx, x, pos, stride: int, relu: bool, stats: bool):
+        out, part = ops.frame_shift_forward(x, pos, stride, relu, stats)
+        ctx.stride, ctx.relu = stride, relu
+        ctx.save_for_backward(x, pos)
+        if part is None:
+            part = torch.empty(0, device=x.device)
+        ctx.mark_non_differentiable(part)
+        ctx.set_materialize_grads(False)
+        return out, part
+
+    @staticmethod
+    def backward(ctx, d_out, _d_part):
+        if d_out is None:
+            return (None,) * 5
+        x, pos = ctx.saved_tensors
+        dx, dpos = ops.frame_shift_backward(d_out.contiguous(), x, pos, ctx.stride, ctx.relu)
+        return dx, dpos, None, None, None
+
+
+def frame_shift(x: torch.Tensor, pos: torch.Tensor, stride: int = 1, relu: bool = False, stats: bool = False):
+    """Differentiable frame shift of x (B, T, V, C) by the per-channel positions ``pos`` (C): out[b, to] = (1 - f) tap(to stride + k) +
+    f tap(to stride + k + 1) with k = floor(pos), f = pos - k, tap = (``relu`` of) x inside the clip and 0 outside; T_out = (T - 1) // stride + 1.
+    ``stats``: -> (out, BatchNorm partial sums of out for ``bn_act``), from the pass that writes out.  C a multiple of 64 up to 512, V <= 64,
+    stride 1 or 2; anything else raises."""
+    out, part = _FrameShift.apply(x.contiguous(), pos.contiguous(), stride, relu, stats)
+    return (out, part) if stats else out
+
+
+def linear_weight_forms(weight: torch.Tensor, k_pad: int = 0) -> Tuple[Form, Form]:
+    """Forms of a (Cin, Cout) matrix parameter as the row GEMM's (1, Cin + k_pad, Cout) operand and its transpose (1, Cout, Cin + k_pad) for the
+    data gradient; the k_pad input channels are zero rows."""
+    cin, cout = weight.shape
+    return (Form("plain", 1, cin + k_pad, cout, [Seg(weight, st_k=cout, st_n=1, klen=cin, nlen=cout)]),
+            Form("plain", 1, cout, cin + k_pad, [Seg(weight, st_k=1, st_n=cout, klen=cout, nlen=cin)]))
+
+
+class _LinearParams(torch.autograd.Function):
+    """y = x @ W + b on the rows of x with W a (Cin, Cout) parameter: ``w`` / ``wt`` / ``bias`` are its packed forms, the weight gradient comes
+    out of the reduction in the parameter's own layout."""
+
+    @staticmethod
+    def forward(ctx, x, w, wt, bias, zero_bias_grad: bool, weight, bias_param):
+        B, T, V, ld = x.shape
+        _, K, N = w.shape
+        out = torch.empty((B, T, V, N), device=x.device, dtype=torch.float32)
+        xin = x.view(B, T * V, 1, ld)
+        ops.rows_gemm(xin, w, out.view(B, T * V, 1, N), K=K, N=N, bias=bias)
+        ctx.save_for_backward(xin, wt)
+        ctx.x_shape, ctx.w_shape, ctx.b_shape = x.shape, tuple(weight.shape), tuple(bias_param.shape)
+        ctx.zero_bias = zero_pool.take(N, x.device) if zero_bias_grad else None
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        xin, wt = ctx.saved_tensors
+        _, N, K = wt.shape
+        B, T, V, ld = ctx.x_shape
+        d_out = d_out.contiguous().view(B, T * V, 1, N)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(xin)
+            ops.rows_gemm(d_out, wt, dx, K=N, N=K)
+            dx = dx.view(ctx.x_shape)
+        if ctx.needs_input_grad[5]:
+            dw = ops.rows_wgrad(xin, d_out, K=K, N=N)[0, :ctx.w_shape[0]]
+        if ctx.needs_input_grad[6]:
+            db = (ctx.zero_bias if ctx.zero_bias is not None else ops.col_sum(d_out, N)).view(ctx.b_shape)
+        return dx, None, None, None, None, dw, db
+
+
+def linear_params(x: torch.Tensor, forms: ParamForms, name: str, weight: torch.Tensor, bias: torch.Tensor, zero_bias_grad: bool = False) -> torch.Tensor:
+    """x (B, T, V, Cin [+ zero pad channels]) @ ``weight`` (Cin, Cout) + ``bias`` (Cout elements, any shape); the packed forms live in ``forms``
+    under ``name``.  ``zero_bias_grad``: the bias feeds a train-mode BatchNorm, its gradient is exactly zero and is returned as such."""
+    x = x.contiguous()
+    k_pad = x.shape[-1] - weight.shape[0]
+    w, wt = forms.get_pair(name, (".w", ".wt"), lambda: linear_weight_forms(weight, k_pad), x.device)
+    b = forms.get(name + ".b", lambda: bias_form([bias]), x.device)
+    return _LinearParams.apply(x, w, wt, b, zero_bias_grad, weight, bias)
+
+
 ops.bind_all_functions(globals())     # every Function's backward runs in its forward's library context (ops.Context)

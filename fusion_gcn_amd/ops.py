@@ -2637,3 +2637,137 @@ def ctr_backward(dy: torch.Tensor, x3: torch.Tensor, th: torch.Tensor, w4: torch
     check(lib.fgcn_ctr_param_grads(_p(s2), _p(s1), _p(dpa_part), _p(dal_part), _p(alpha), _p(d_w4), _p(d_b4), _p(d_pa), _p(d_alpha),
                                    B, V, C, R, _stream()), "fgcn_ctr_param_grads")
     return dx3, dx12, d_w4, d_b4, d_alpha, d_pa
+
+
+# ---- Shift graph convolution (fgcn_shift.hip; include/fgcn.h, "Shift graph convolution") -----------------------------------------------
+SHIFT_MAX_V = 64
+SHIFT_MAX_C = 512
+
+
+def _shift_wide(C: int) -> bool:
+    return C >= 64 and C % 64 == 0 and C <= SHIFT_MAX_C
+
+
+def _shift_dims(x: torch.Tensor, name: str, narrow: bool) -> Tuple[int, int, int, int]:
+    _chk(x, name)
+    if x.dim() != 4:
+        raise _lib.FgcnError(f"{name}: expected a (B, T, V, C) tensor, got {tuple(x.shape)}")
+    B, T, V, C = x.shape
+    if V > SHIFT_MAX_V:
+        raise _lib.FgcnError(f"{name}: V={V} joints, the shift kernels take at most {SHIFT_MAX_V}")
+    if not (_shift_wide(C) or (narrow and C == 4)):
+        raise _lib.FgcnError(f"{name}: C={C} channels, the shift kernels take {'4 or ' if narrow else ''}a multiple of 64 up to {SHIFT_MAX_C}")
+    return B, T, V, C
+
+
+def _shift_mask(mask: Optional[torch.Tensor], V: int, C: int, name: str) -> int:
+    """-> the row stride of the (V, C) gate parameter (3 or 4 for the 4-wide input); any shape with those V * stride elements"""
+    if mask is None:
+        return C
+    _chk(mask, f"{name}.mask")
+    ld = mask.numel() // V
+    if mask.numel() != V * ld or not (ld == C or (C == 4 and ld == 3)):
+        raise _lib.FgcnError(f"{name}: mask {tuple(mask.shape)} is not a (V, C) = ({V}, {C}) gate")
+    return ld
+
+
+def _shift_dir(direction: int, name: str) -> int:
+    if direction not in (1, -1):
+        raise _lib.FgcnError(f"{name}: direction={direction!r} is neither +1 nor -1")
+    return int(direction)
+
+
+def shift_geometry(kind: str, B: int, T: int, V: int, C: int, stride: int = 1) -> Tuple[int, int, int]:
+    """-> (workgroup chunks, rows per chunk, rows per LDS stage) of the joint shift over its B T rows (``kind`` "joint": a workgroup walks
+    its chunk's rows stage by stage; the 4-wide input is not staged: one row), or (frame splits, output frames per split, 1) of the frame
+    shift (``kind`` "frame"); host only"""
+    lib = _lib.load()
+    if kind == "joint":
+        n, per, stage = B * T, lib.fgcn_shift_joint_rows(B * T, V, C), (1 if C == 4 else lib.fgcn_shift_joint_stage(V))
+    elif kind == "frame":
+        n, per, stage = (T - 1) // stride + 1, lib.fgcn_shift_frame_split(B, T, V, C, stride), 1
+    else:
+        raise _lib.FgcnError(f"shift_geometry: kind {kind!r} (joint | frame)")
+    if per <= 0 or stage <= 0:
+        raise _lib.FgcnError(f"shift_geometry: no {kind} geometry for (B, T, V, C, stride) = {(B, T, V, C, stride)}")
+    return (n + per - 1) // per, per, stage
+
+
+def joint_shift_forward(x: torch.Tensor, mask: Optional[torch.Tensor] = None, direction: int = 1) -> torch.Tensor:
+    """out[r, v, c] = x[r, (v + direction c) mod V, c] * (tanh(mask[v, c]) + 1) (include/fgcn.h, "Shift graph convolution"); x (B, T, V, C)
+    with C = 4 (three channels and a zero pad) or a multiple of 64, mask None or V * C elements (V * 3 for the 4-wide input)"""
+    ensure_device()
+    B, T, V, C = _shift_dims(x, "joint_shift_forward.x", True)
+    ld = _shift_mask(mask, V, C, "joint_shift_forward")
+    out = torch.empty_like(x)
+    check(_lib.load().fgcn_shift_joint(_p(x), _p(mask), None, _p(out), None, B * T, V, C, ld, _shift_dir(direction, "joint_shift_forward"), 0,
+                                       _stream()), "fgcn_shift_joint")
+    return out
+
+
+def joint_shift_backward(dout: torch.Tensor, x: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None, direction: int = 1,
+                         need_dmask: bool = True):
+    """Backward of ``joint_shift_forward`` -> (dx, dmask or None).  dmask rides in the dx pass as per-workgroup terms, summed in workgroup
+    order (``reduce_sum``); ``x`` is read for it alone."""
+    ensure_device()
+    B, T, V, C = _shift_dims(dout, "joint_shift_backward.dout", True)
+    ld = _shift_mask(mask, V, C, "joint_shift_backward")
+    direction = _shift_dir(direction, "joint_shift_backward")
+    want = mask is not None and need_dmask
+    part = None
+    if want:
+        _chk(x, "joint_shift_backward.x")
+        if x.shape != dout.shape:
+            raise _lib.FgcnError(f"joint_shift_backward: x {tuple(x.shape)} against dout {tuple(dout.shape)}")
+        chunks = shift_geometry("joint", B, T, V, C)[0]
+        part = torch.empty((chunks, V, C), device=dout.device, dtype=torch.float32)
+    lib = _lib.load()
+    dx = torch.empty_like(dout)
+    check(lib.fgcn_shift_joint(_p(dout), _p(mask), _p(x) if want else None, _p(dx), _p(part), B * T, V, C, ld, -direction, 1, _stream()),
+          "fgcn_shift_joint")
+    if not want:
+        return dx, None
+    sums = torch.empty((V, C), device=dout.device, dtype=torch.float32)
+    reduce_sum(part.view(part.shape[0], -1), sums.view(-1))
+    dmask = torch.empty_like(mask)
+    check(lib.fgcn_shift_dmask(_p(sums), _p(mask), _p(dmask), V, C, ld, direction, _stream()), "fgcn_shift_dmask")
+    return dx, dmask
+
+
+def _shift_frame_args(x: torch.Tensor, pos: torch.Tensor, stride: int, name: str):
+    B, T, V, C = _shift_dims(x, f"{name}.x", False)
+    _chk(pos, f"{name}.pos")
+    if pos.numel() != C:
+        raise _lib.FgcnError(f"{name}: pos {tuple(pos.shape)} against C={C}")
+    if stride not in (1, 2):
+        raise _lib.FgcnError(f"{name}: stride={stride!r}, the frame shift takes 1 or 2")
+    return B, T, V, C, (T - 1) // stride + 1
+
+
+def frame_shift_forward(x: torch.Tensor, pos: torch.Tensor, stride: int = 1, relu: bool = False, stats: bool = False):
+    """out[b, to, v, c] = (1 - f) tap(to s + k) + f tap(to s + k + 1), k = floor(pos[c]), f = pos[c] - k, tap = (relu of) x inside the clip and
+    0 outside -> (out (B, T_out, V, C), BatchNorm partial sums of out in ``bn_finalize``'s layout or None)"""
+    ensure_device()
+    B, T, V, C, T_out = _shift_frame_args(x, pos, stride, "frame_shift_forward")
+    out = torch.empty((B, T_out, V, C), device=x.device, dtype=torch.float32)
+    part = None
+    if stats:
+        part = torch.empty((B * shift_geometry("frame", B, T, V, C, stride)[0], 2, C), device=x.device, dtype=torch.float32)
+    check(_lib.load().fgcn_shift_frame(_p(x), _p(pos), _p(out), _p(part), B, T, V, C, stride, int(relu), _stream()), "fgcn_shift_frame")
+    return out, part
+
+
+def frame_shift_backward(dout: torch.Tensor, x: torch.Tensor, pos: torch.Tensor, stride: int = 1, relu: bool = False):
+    """Backward of ``frame_shift_forward`` -> (dx in its gather form, dpos with k held constant)"""
+    ensure_device()
+    B, T, V, C, T_out = _shift_frame_args(x, pos, stride, "frame_shift_backward")
+    _chk(dout, "frame_shift_backward.dout")
+    if tuple(dout.shape) != (B, T_out, V, C):
+        raise _lib.FgcnError(f"frame_shift_backward: dout {tuple(dout.shape)} against {(B, T_out, V, C)}")
+    dx = torch.empty_like(x)
+    part = torch.empty((B * shift_geometry("frame", B, T, V, C, stride)[0], C), device=x.device, dtype=torch.float32)
+    check(_lib.load().fgcn_shift_frame_bwd(_p(dout), _p(x), _p(pos), _p(dx), _p(part), B, T, V, C, stride, int(relu), _stream()),
+          "fgcn_shift_frame_bwd")
+    dpos = torch.empty_like(pos)
+    reduce_sum(part, dpos.view(-1))
+    return dx, dpos

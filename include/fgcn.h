@@ -1484,6 +1484,60 @@ int fgcn_ctr_bwd_small(const float* da, const float* th, const float* w4, const 
 int fgcn_ctr_param_grads(const float* s2_part, const float* s1_part, const float* dpa_part, const float* dalpha_part, const float* alpha,
                          float* d_w4, float* d_b4, float* d_pa, float* d_alpha, int B, int V, int Cout, int R, void* stream);
 
+/* Shift graph convolution: the two shift operations of Shift-GCN (Cheng et al., CVPR 2020) (ops.joint_shift_* / ops.frame_shift_*,
+ * fops.joint_shift / fops.frame_shift, models/shiftgcn).
+ *
+ * All tensors float32, channels-last, contiguous, in every math mode.  Rows are r = (b, t); activations are (B, T, V, C).
+ *
+ * Joint shift (dir = +1 or -1, optional gate parameter mask (V, C)):
+ *     g[v, c]      = tanh(mask[v, c]) + 1                     (1 when no mask is given)
+ *     out[r, v, c] = x[r, (v + dir c) mod V, c] * g[v, c]
+ *     dx[r, u, c]  = dout[r, w, c] * g[w, c],  w = (u - dir c) mod V
+ *     dmask[v, c]  = (1 - tanh(mask[v, c])^2) * sum_r dout[r, v, c] x[r, (v + dir c) mod V, c]
+ * The channel index runs far past V (C = 64 at V = 25 wraps twice): mod is the true modulo of a possibly negative number.  Limits: V <= 64;
+ * C = 4 (the 3-channel input, which travels as 4 with a zero fourth channel) or a multiple of 64 up to 512; rows < 2^31 / (V C).  C = 4:
+ * the mask and dmask have a row stride `mask_ld` of 3 or 4, and the pad channel is written as zero in out, dx and dmask.
+ *     fgcn_shift_joint   out[r, v, c] = in[r, (v + dir c) mod V, c] * g, with g = g[v, c] (`source_gate` 0: the forward) or g = g[source
+ *                        joint, c] (`source_gate` 1: the data gradient, called with in = dout and the forward's dir NEGATED).  With `x` and
+ *                        `part` (chunks, V, C) (both or neither; they need the mask and source_gate) the same pass leaves the terms
+ *                        part[chunk, v, c] = sum_{r in chunk} in[r, source joint, c] x[r, v, c]; chunk = the cdiv(rows, fgcn_shift_joint_rows)
+ *                        row ranges one workgroup walks.  fgcn_reduce_sum adds them in chunk order.
+ *     fgcn_shift_dmask   dmask[v, c] = (1 - tanh(mask[v, c])^2) * sums[(v + dir c) mod V, c] from the summed terms, dir the FORWARD's
+ *     fgcn_shift_joint_rows   rows one workgroup walks (host only; 0 for sizes outside the limits)
+ *     fgcn_shift_joint_stage  rows of a 64-channel tile one LDS stage holds, which a workgroup's rows are walked in (host only; 0 for V > 64)
+ *
+ * Frame shift (per-channel position pos (C), stride s in {1, 2}, optional ReLU on the input):
+ *     T_out = (T - 1) / s + 1
+ *     k = floor(pos[c]),  f = pos[c] - k,  phi = identity or relu
+ *     tap(t)           = phi(x[b, t, v, c]) if 0 <= t < T, else 0      (not read outside the clip)
+ *     out[b, to, v, c] = (1 - f) tap(to s + k) + f tap(to s + k + 1)
+ *     dx[b, t, v, c]   = phi'(x[b, t, v, c]) ((1 - f) dout[b, (t - k) / s, v, c]  where s divides t - k and the quotient is in [0, T_out)
+ *                                              + f dout[b, (t - k - 1) / s, v, c]  where s divides t - k - 1 and the quotient is in [0, T_out))
+ *     dpos[c]          = sum_{b, to, v} dout[b, to, v, c] (tap(to s + k + 1) - tap(to s + k))
+ * dx is the gather form.  dpos is the derivative with k held constant (what autograd gives for f = pos - floor(pos).detach()): at an integer
+ * position the right derivative.  k is clamped to +-2^26 as a float before it becomes an integer: pos = +-1e9 gives all-zero output and a zero
+ * dpos.  A non-finite pos gives NaN through f in every output of its channel and in no other.  Limits: C a multiple of 64 up to 512, V <= 64,
+ * any T >= 1, B <= 65535, B T < 2^31 / (V C).
+ *     fgcn_shift_frame       out, and with `part` (B nsplit, 2, C) the BatchNorm partial sums (sum, sum of squares) of out in the layout
+ *                            fgcn_bn_finalize takes, summed in the pass that writes out; nsplit = cdiv(T_out, fgcn_shift_frame_split)
+ *     fgcn_shift_frame_bwd   dx and dpos_part (B nsplit, C), the workgroups' terms of dpos (fgcn_reduce_sum adds them in order)
+ *     fgcn_shift_frame_split output frames one workgroup walks (host only; 0 for sizes outside the limits)
+ * `relu`, the stride and the partial sums select kernel instantiations, they are not run-time branches.
+ *
+ * Every sum has an order fixed by the sizes alone; no atomics; two calls give the same bits.  No kernel reads another row's (joint shift)
+ * or another sample's (frame shift) data for out / dx.  Nothing is skipped on a value ("Non-finite values in the inputs"): a gate of 1 and
+ * a weight f = 0 still multiply.  FGCN_E_BADARG before any launch: a null pointer, a size outside the limits.  FGCN_E_ALIGN: in, out or
+ * part of fgcn_shift_joint (read or written in 16-byte groups) not 16-byte aligned; the frame shift reads and writes single floats. */
+int fgcn_shift_joint_rows(long long rows, int V, int C);
+int fgcn_shift_joint_stage(int V);
+int fgcn_shift_frame_split(int B, int T, int V, int C, int stride);
+int fgcn_shift_joint(const float* in, const float* mask, const float* x, float* out, float* part, long long rows, int V, int C, int mask_ld,
+                     int dir, int source_gate, void* stream);
+int fgcn_shift_dmask(const float* sums, const float* mask, float* dmask, int V, int C, int mask_ld, int dir, void* stream);
+int fgcn_shift_frame(const float* x, const float* pos, float* out, float* part, int B, int T, int V, int C, int stride, int relu, void* stream);
+int fgcn_shift_frame_bwd(const float* dout, const float* x, const float* pos, float* dx, float* dpos_part, int B, int T, int V, int C, int stride,
+                         int relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
